@@ -13,7 +13,12 @@ bench.py --gpus N` launches itself through torch.distributed.run when it is not 
 `--scaling weak` (default) keeps the pages per GPU fixed, `--scaling strong` fixes the GLOBAL batch
 (256 pages unless --global-pages) and splits it over the ranks.
 
-Prints ONE JSON line on rank 0.  Extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, runs --warmup untimed and --steps timed train steps (no HIP
+events in them), writes the last timed step's outputs when --dump-outputs DIR is given, and prints the headline
+(`value`, `ms_per_step`, `step`, `per_rank`):
+  step         -- whole-step FLOP accounting: algorithmic TFLOP/s, fraction of the direct-convolution MFMA
+                  ceiling, fraction of the executed-MFMA floor.
+`--full` adds every other leg, each still switchable with its --no-* option:
   roofline     -- the dominant kernel family (Winograd F(4x4,3x3) conv3x3 64->64, forward + data gradient), timed live with
                   HIP events on the launching stream inside the timed steps (every 10th).  Its transform-domain products run on
                   the bf16 matrix pipe (f32 operands as three bf16 pieces, six products): the launch's matrix floor is below its
@@ -32,10 +37,14 @@ Prints ONE JSON line on rank 0.  Extra objects:
                   the MFMA-dense kernels run power-limited, and by how much differs from box to box.
   sustained    -- >= 5 s of back-to-back train steps after the headline measurement (same batch), reported
                   separately: long enough for an external utilisation sampler to see the GPU work.
-  step         -- whole-step FLOP accounting: algorithmic TFLOP/s, fraction of the direct-convolution MFMA
-                  ceiling, fraction of the executed-MFMA floor.
   cpu_baseline -- the CPU oracle (oracle/cova_oracle.py, a restatement of the reference's torch-CPU path)
                   timed on this host: 2-page and 16-page batches, forward and forward+backward+Adam, medians.
+  forward_only, dropin_module_loop -- eval forward, and the drop-in nn.Module with torch.optim.Adam.
+
+--dump-outputs DIR (rank 0): what the last timed train step hands its caller, as DIR/<name>.npy (float32 / float64):
+`loss`, `pred` (per-box class indices), `params` (the flat parameters after Adam), `grads` (the flat gradients Adam
+read), `bn_buffers` (BatchNorm running statistics and counters, state_dict order).  Inputs, weights and dropout masks
+are seeded, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import datetime
@@ -101,6 +110,33 @@ def make_device_batch(seed, device, pages=None, config=2):
                                                                     seed).items() if torch.is_tensor(v)}
     batch["images"] = torch.rand((pages, 3, wl["H"], wl["W"]), generator=g, device=device, dtype=torch.float32)
     return batch
+
+
+DUMP_MAX_ELEMENTS = 1 << 22                        # per array: 16 MB of float32, so a dump stays under 64 MB in all
+DUMP_SAMPLE_SEED = 123
+
+
+def dump_outputs(out_dir, trainer, loss, pred):
+    """--dump-outputs: the last timed step's loss and predictions and the state it left (parameters after Adam, gradients,
+    BatchNorm buffers) as out_dir/<name>.npy.  An array of more than DUMP_MAX_ELEMENTS elements (the parameters and
+    gradients of configs 3 and 5) is replaced by the same seeded sample of its elements every run.  -> {name: shape}"""
+    import numpy as np
+    import torch
+    arrays = {"loss": loss.detach().reshape(1).double(),
+              "pred": pred.detach().reshape(-1).float(),                # class indices: exact in float32
+              "params": trainer.pbucket.flat.detach().float(),
+              "grads": trainer.gbucket.flat.detach().float(),
+              "bn_buffers": torch.cat([v.detach().reshape(-1).double() for v in trainer.buffers.values()])}
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        if a.size > DUMP_MAX_ELEMENTS:
+            idx = np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, DUMP_MAX_ELEMENTS, replace=False)
+            a = a[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 # ------------------------------------------------------------------------------------ FLOP accounting
@@ -276,7 +312,7 @@ def clock_leg(args):
         return {"error": "rocprofv3 not found"}
     tmp = tempfile.mkdtemp(prefix="cova_clk_", dir="/tmp")
     cmd = [exe, "--pmc", "GRBM_GUI_ACTIVE", "-d", tmp, "--", sys.executable, os.path.abspath(__file__), "--steps", "3", "--warmup", "2",
-           "--no-cpu-baseline", "--sustained-seconds", "0", "--no-ab", "--no-clock-leg", "--config", str(args.config)]
+           "--full", "--no-cpu-baseline", "--sustained-seconds", "0", "--no-ab", "--no-clock-leg", "--config", str(args.config)]
     env = dict(os.environ, TMPDIR="/tmp")
     try:
         r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
@@ -377,6 +413,12 @@ def main():
     ap.add_argument("--global-pages", type=int, default=256, help="--scaling strong: global batch")
     ap.add_argument("--roi-op", choices=("pool", "align"), default="pool",
                     help="pool = the reference's RoIPool (the metric's configuration); align = the RoIAlign variant")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg besides the headline: roofline and per-kernel times, sustained, forward-only, "
+                         "A/B, drop-in module, clock and CPU-baseline legs (the --no-* options below apply to this mode)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, predictions, parameters, gradients, BatchNorm buffers) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ab", action="store_true", help="skip the A/B legs (f32-MFMA forms of conv1 / the 3x3 main loop)")
     ap.add_argument("--no-clock-leg", action="store_true",
@@ -391,6 +433,8 @@ def main():
                     help="deadline (s) of every phase of a multi-rank run and of the process group's collectives: past it "
                          "rank 0 prints a JSON line with \"error\" instead of hanging")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -504,14 +548,18 @@ def run(args, guard, rank, local_rank, world):
     in_step = dominant + [n for n in ("cova_conv1_fwd_tail", "cova_conv1_fwd", "cova_conv1_wgrad_poolbwd",
                                       "cova_conv3x3_wgrad4_partial") if n in timed]
     prof = {name: [] for name in (_lib.lib().protos if os.environ.get("COVA_PROFILE_ALL") else in_step)}
+    # (a plain run brackets nothing: the events serve the --full report only)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        _lib.PROFILE = prof if i % EVENT_EVERY == 0 else None
-        loss, _ = trainer.train_step(batch)
+        _lib.PROFILE = prof if args.full and i % EVENT_EVERY == 0 else None
+        loss, box_pred = trainer.train_step(batch)
     barrier()
     dt = time.perf_counter() - t0
     _lib.PROFILE = None
-    if not os.environ.get("COVA_PROFILE_ALL"):
+    if args.dump_outputs and rank == 0:
+        guard.enter("dump outputs")
+        dump_outputs(args.dump_outputs, trainer, loss, box_pred)
+    if args.full and not os.environ.get("COVA_PROFILE_ALL"):
         _lib.PROFILE = {name: [] for name in timed if name not in in_step}
         for _ in range(min(args.steps, 5)):
             trainer.train_step(batch)
@@ -532,7 +580,7 @@ def run(args, guard, rank, local_rank, world):
         ev = [p for n in names for p in prof.get(n, []) if pred is None or pred(p[2])]
         return (sum(p[0].elapsed_time(p[1]) for p in ev) / len(ev), len(ev)) if ev else (0.0, 0)
 
-    if os.environ.get("COVA_PROFILE_ALL") and rank == 0:
+    if args.full and os.environ.get("COVA_PROFILE_ALL") and rank == 0:
         rows = [(sum(p[0].elapsed_time(p[1]) for p in v) / args.steps, len(v) / args.steps, k) for k, v in prof.items() if v]
         for ms, n, k in sorted(rows, reverse=True):
             print("%-36s %5.1f calls/step %8.3f ms/step" % (k, n, ms), file=sys.stderr)
@@ -540,7 +588,7 @@ def run(args, guard, rank, local_rank, world):
 
     # sustained leg: >= N seconds of back-to-back train steps (reported separately from the headline)
     sustained = None
-    if args.sustained_seconds > 0:
+    if args.full and args.sustained_seconds > 0:
         guard.enter("sustained leg", args.collective_timeout + 2 * args.sustained_seconds)
         # step count fixed up front from the headline rate (+5 %: every rank runs the same number of steps and the leg
         # must last AT LEAST the stated time)
@@ -555,21 +603,26 @@ def run(args, guard, rank, local_rank, world):
                      "seconds": round(dt_s, 2), "ms_per_step": round(1e3 * dt_s / n_s, 3)}
 
     # forward only (eval mode, running statistics): the second number SURVEY.md section 8d asks for
-    guard.enter("forward-only leg")
-    for _ in range(2):
-        trainer.predict(batch)
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        trainer.predict(batch)
-    barrier()
-    dt_fwd = max_over_ranks(time.perf_counter() - t1)
+    forward_only = None
+    if args.full:
+        guard.enter("forward-only leg")
+        for _ in range(2):
+            trainer.predict(batch)
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            trainer.predict(batch)
+        barrier()
+        dt_fwd = max_over_ranks(time.perf_counter() - t1)
+        forward_only = {"value": round(global_pages * args.steps / dt_fwd, 2), "unit": "webpages/s",
+                        "ms_per_step": round(1e3 * dt_fwd / args.steps, 3),
+                        "mode": "eval forward (running statistics) + per-box argmax, same batch"}
 
     # A/B legs in the same process, same trainer (the engine queries workspace sizes per step): the f32-MFMA forms of the
     # kernels that run on the bf16 matrix pipe by default -- conv1 forward + weight gradient (cova_set_option 7) and the
     # F(4x4,3x3) forward / data-gradient main loop (option 9) -- each 3 warm-up + 10 timed steps
     ab = {}
-    if world == 1 and not args.no_ab:
+    if args.full and world == 1 and not args.no_ab:
         guard.enter("A/B legs")
         pre7, pre9 = os.environ.get("COVA_CONV1_F32") == "1", os.environ.get("COVA_W4_F32") == "1"
         for key, opt, pre, what in (("default", 0, False, "the headline's kernels, timed like the other two legs (no events)"),
@@ -601,7 +654,7 @@ def run(args, guard, rank, local_rank, world):
     # argmax + .item(), CE-sum + .item(), backward, torch.optim.Adam.step) -- two host reads per step
     dropin = None
     guard.enter("report")
-    if world == 1 and args.config in (2, 3) and args.roi_op == "pool":
+    if args.full and world == 1 and args.config in (2, 3) and args.roi_op == "pool":
         import contextlib
         import warnings
         from cova_web_object_detection_amd.models import CoVA
@@ -800,11 +853,10 @@ def run(args, guard, rank, local_rank, world):
                                      % (" [here: f32-MFMA kernels, COVA_CONV1_F32=1]" if os.environ.get("COVA_CONV1_F32") == "1" else "",
                                         " [here: f32-MFMA main loop, COVA_W4_F32=1]" if os.environ.get("COVA_W4_F32") == "1" else ""),
                        "loss": round(loss_val, 3)},
-            "roofline": roof, "step": step, "other_kernels": others,
-            "forward_only": {"value": round(global_pages * args.steps / dt_fwd, 2), "unit": "webpages/s",
-                             "ms_per_step": round(1e3 * dt_fwd / args.steps, 3),
-                             "mode": "eval forward (running statistics) + per-box argmax, same batch"},
+            "step": step,
         }
+        if args.full:
+            out.update(roofline=roof, other_kernels=others, forward_only=forward_only)
         if ab:
             out["ab"] = ab
         if sustained:
@@ -814,10 +866,10 @@ def run(args, guard, rank, local_rank, world):
                                    "(0 on one rank)"}
         if dropin:
             out["dropin_module_loop"] = dropin
-        if world == 1 and not args.no_clock_leg and args.roi_op == "pool":
+        if args.full and world == 1 and not args.no_clock_leg and args.roi_op == "pool":
             torch.cuda.synchronize()
             out["clock_leg"] = clock_leg(args)
-        if world == 1 and not args.no_cpu_baseline and args.roi_op == "pool":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.roi_op == "pool":
             out["cpu_baseline"] = cpu_baseline(wl, not args.cpu_baseline_quick)
         print(json.dumps(out), flush=True)
     guard.finish()

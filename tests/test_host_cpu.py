@@ -133,6 +133,28 @@ def test_bench_flop_accounting_matches_survey_8d():
     assert bench.CFG["backbone"] == "resnet18" and bench.WORKLOADS[4]["pages"] == 32
 
 
+def test_bench_dump_outputs_writes_float_arrays(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every file is float32 / float64, the parameters are the trainer's flat buffer, and an array
+    above the size cap becomes the same seeded sample on every call."""
+    import types
+    import bench
+    trainer = types.SimpleNamespace(pbucket=types.SimpleNamespace(flat=torch.arange(10, dtype=torch.float32)),
+                                    gbucket=types.SimpleNamespace(flat=-torch.arange(10, dtype=torch.float32)),
+                                    buffers={"bn.running_mean": torch.ones(3), "bn.num_batches_tracked": torch.tensor(7)})
+    loss, pred = torch.tensor(2.5), torch.tensor([0, 3, 1])
+    shapes = bench.dump_outputs(str(tmp_path / "a"), trainer, loss, pred)
+    assert shapes == {"loss": [1], "pred": [3], "params": [10], "grads": [10], "bn_buffers": [4]}
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in shapes}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["loss"][0] == 2.5 and got["pred"].tolist() == [0, 3, 1]
+    assert np.array_equal(got["params"], np.arange(10)) and got["bn_buffers"].tolist() == [1, 1, 1, 7]
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMENTS", 4)
+    bench.dump_outputs(str(tmp_path / "b"), trainer, loss, pred)
+    bench.dump_outputs(str(tmp_path / "c"), trainer, loss, pred)
+    b, c = np.load(str(tmp_path / "b" / "params.npy")), np.load(str(tmp_path / "c" / "params.npy"))
+    assert b.shape == (4,) and np.array_equal(b, c) and np.all(np.diff(b) > 0)
+
+
 def test_trainer_checkpoint_round_trip_on_cpu_buffers():
     """HotPathTrainer's flat buckets are device agnostic: the save-best / reload-best cycle of train.py:84,94 and an
     optimizer-state round trip can be checked without a GPU (no device work is launched)."""
