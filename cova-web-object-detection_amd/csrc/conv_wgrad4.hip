@@ -675,19 +675,22 @@ COVA_API int cova_conv3x3_wgrad4_partial(const float *act, const float *act_abc,
     return launch_wgrad4(act, act_abc, act_relu, dz, dz2, dz_abc, dz_out, ws, B, H, W, (hipStream_t)stream);
 }
 
-// Fold + final transform of up to four convolutions' partials (pairs 1..3 nullable) into their OIHW gradients
+// Fold + final transform of up to four convolutions' partials into their OIHW gradients.  A (NULL, NULL) pair is a skipped
+// slot (a frozen weight: no partial launch filled it); the non-null pairs are folded in slot order, each exactly as when
+// all four are given.  All four NULL: no launch.
 COVA_API int cova_conv3x3_wgrad4_finish(const float *ws0, float *dw0, const float *ws1, float *dw1, const float *ws2,
                                         float *dw2, const float *ws3, float *dw3, int B, int H, int W, void *stream)
 {
-    COVA_REQUIRE(ws0 && dw0 && B > 0 && H > 0 && W > 0);
-    COVA_REQUIRE((ws1 == nullptr) == (dw1 == nullptr) && (ws2 == nullptr) == (dw2 == nullptr) &&
-                 (ws3 == nullptr) == (dw3 == nullptr));
+    COVA_REQUIRE(B > 0 && H > 0 && W > 0);
+    COVA_REQUIRE((ws0 == nullptr) == (dw0 == nullptr) && (ws1 == nullptr) == (dw1 == nullptr) &&
+                 (ws2 == nullptr) == (dw2 == nullptr) && (ws3 == nullptr) == (dw3 == nullptr));
     const float *ws[4] = {ws0, ws1, ws2, ws3};
     float *dw[4] = {dw0, dw1, dw2, dw3};
     Wg4FinishJobs jobs{};
     int n = 0;
     for (int i = 0; i < 4; ++i)
         if (ws[i]) { jobs.part[n] = ws[i]; jobs.dw[n] = dw[i]; ++n; }
+    if (n == 0) return COVA_OK;
     const int grid = wg4_geometry(B, H, W).grid;
     hipLaunchKernelGGL(wgrad4_finish_kernel, dim3(4096 / 64, n), dim3(1024), 0, (hipStream_t)stream, jobs, grid);
     COVA_LAUNCH_CHECK();

@@ -20,6 +20,65 @@ call, query = _lib.call, _lib.query
 BN_MOMENTUM, BN_EPS, LEAKY_SLOPE = 0.1, 1e-5, 0.2   # nn.BatchNorm defaults; models.py:156
 
 
+# ------------------------------------------------------------------------------- per-layer modes, gradient plan
+# ``training`` of the forward stages is a bool (every layer in that mode: model.train() / model.eval()) or a mapping
+# {BatchNorm prefix ("convnet.1.", "convnet.4.0.bn1.", "decoder.2.", ...) or Dropout name ("decoder.0", "decoder.3"): bool}
+# (per-module .training, e.g. ``model.train(); model.convnet.eval()``); layers the mapping does not name are in train mode.
+# An eval-mode BatchNorm normalises with its running statistics and leaves its buffers alone; an eval-mode Dropout is the
+# identity.
+DROPOUT_KEYS = ("decoder.0", "decoder.3")
+
+
+def is_train(training, key):
+    """train (True) / eval (False) flag of the layer ``key`` under ``training`` (a bool or a per-layer mapping)."""
+    if isinstance(training, bool):
+        return training
+    if hasattr(training, "get"):
+        return bool(training.get(key, True))
+    return bool(training)
+
+
+def collapse_modes(modes):
+    """{layer: bool} -> the bool when every layer shares one mode (then the launches are exactly those of the bool)."""
+    vals = set(bool(v) for v in modes.values())
+    return vals.pop() if len(vals) == 1 else dict(modes)
+
+
+# Backward stages that a gradient plan may leave out (grad_plan):
+#   "convstack"   RoIPool / RoIAlign backward + the whole conv-stack backward (the forward then keeps no activations)
+#   "stem"        block 0's first data gradient (its residual into the pool output included), the stem BatchNorm / ReLU /
+#                 max-pool backward (resnet50: the first Bottleneck's input gradient)
+#   "conv1_wgrad" the 7x7 conv1 weight gradient (cova_conv1_wgrad*)
+#   "wgrad:K"     the weight gradient of layer1 convolution K (a state_dict key; the 3x3 ones and the resnet50 conv1 1x1s)
+#   "bbox"        the positional encoder's backward; "addl" the additional-feature BatchNorm's backward
+PLAN_STAGES = ("convstack", "stem", "conv1_wgrad", "bbox", "addl")
+
+
+def grad_plan(need, want_dimg=False):
+    """(state_dict keys of the parameters that need a gradient, images need one?) -> frozenset of the backward stages to
+    issue.  A stage is left out only when nothing downstream of it is wanted; every other pattern computes more than it
+    needs (the caller drops the gradients of frozen parameters)."""
+    need = set(need)
+    plan = set()
+    if any(k.startswith("bbox_feat_encoder.") for k in need):
+        plan.add("bbox")
+    if any(k.startswith("bn_additional_feat.") for k in need):
+        plan.add("addl")
+    if want_dimg or any(k.startswith("convnet.") for k in need):
+        plan.add("convstack")
+        if want_dimg or need & {"convnet.0.weight", "convnet.1.weight", "convnet.1.bias"}:
+            plan.add("stem")
+        if "convnet.0.weight" in need:
+            plan.add("conv1_wgrad")
+        plan.update("wgrad:" + k for k in need if k.startswith("convnet.4.") and ".conv" in k)
+    return frozenset(plan)
+
+
+def full_plan(params):
+    """The plan of a step in which every parameter of ``params`` needs its gradient (no stage left out)."""
+    return grad_plan(list(params))
+
+
 def on_device_of(argpos):
     """Run an engine entry point under the device guard of its tensors (argument `argpos`): the host-side size
     queries (persistent-grid sizes, workspace sizes) then consult the SAME device the launches go to -- the reference
@@ -83,13 +142,14 @@ def check_batch(cfg, images, bboxes, additional_feats, context_indices, training
         if context_indices.shape[1] > GAT_MAX_K:
             raise ValueError("n_context > %d (-cs > %d) is not supported by the wave-per-node kernel"
                              % (GAT_MAX_K, GAT_MAX_K // 2))
-    if training and N == 1:
-        # torch.nn.functional.batch_norm's _verify_batch_size, hit by the first BatchNorm1d of the forward
-        width = cfg["bbox_hidden_dim"] or A or None
-        if width is None:
-            width = (backbone_feat(cfg) + (cfg["hidden_dim"] if cfg["use_context"] else 0))
-        raise ValueError("Expected more than 1 value per channel when training, got input size "
-                         "torch.Size([1, %d])" % width)
+    if N == 1:
+        # torch.nn.functional.batch_norm's _verify_batch_size, hit by the first train-mode BatchNorm1d of the forward
+        T = backbone_feat(cfg) + cfg["bbox_hidden_dim"] + A + (cfg["hidden_dim"] if cfg["use_context"] else 0)
+        for width, prefix in ((cfg["bbox_hidden_dim"], "bbox_feat_encoder.1."), (A, "bn_additional_feat."),
+                              (T, "decoder.2.")):
+            if width and is_train(training, prefix):
+                raise ValueError("Expected more than 1 value per channel when training, got input size "
+                                 "torch.Size([1, %d])" % width)
 
 
 def backbone_feat(cfg):
@@ -166,7 +226,7 @@ def bn_finalize_bwd(part, nparts, C, count, dgamma, dbeta, unit, abc_from=None, 
             call("cova_bn_finalize_bwd", p, n, C, float(cnt), dg, db, out)
 
     fin(part, nparts, count, dgamma, dbeta)
-    if STAT_SYNC is not None:
+    if STAT_SYNC is not None and not frozen:            # (an eval-mode layer has no batch coupling to exchange)
         gp, gn, gc = _global_stats(part, nparts, 2 * C, count, unit)
         scratch = _empty((2, C), part)
         fin(gp, gn, gc, scratch[0], scratch[1])
@@ -217,6 +277,7 @@ def bn_tail_bwd(st, count, gout, prefix, like):
 
 def bn_params(prefix, params, buffers, C, like, training, partial=None, nparts=0, count=0,
               update_running=True, unit="boxes"):
+    training = is_train(training, prefix)
     st = bn_state(C, like, count, training)
     g, b = params[prefix + "weight"], params[prefix + "bias"]
     rm, rv = buffers[prefix + "running_mean"], buffers[prefix + "running_var"]
@@ -339,7 +400,8 @@ def is_bottleneck(params):
 @on_device_of(0)
 def convstack_fwd(images, params, buffers, training, save=True, lazy_out=False):
     """images NCHW [B,3,H,W] -> feature map NHWC [B,Hf,Wf,C]  (models.py:49-51,125);
-    with ``lazy_out`` (Winograd path) a LazyFeature instead of the tensor."""
+    with ``lazy_out`` (Winograd path) a LazyFeature instead of the tensor.  ``training``: a bool or per-BatchNorm modes
+    (is_train); ``save``: keep what the backward needs."""
     _check(images)
     B, _, H, W = images.shape
     H1, W1 = query("cova_conv_out_size", H, 7, 2, 3), query("cova_conv_out_size", W, 7, 2, 3)
@@ -354,9 +416,10 @@ def convstack_fwd(images, params, buffers, training, save=True, lazy_out=False):
     # conv1 + bn1 + relu + maxpool
     y1 = _empty((B, H1, W1, C64), images)
     nt1 = query("cova_conv1_num_partials", B, H, W)
-    part = _empty((nt1, 2, C64), images) if training else None
+    stem_train = is_train(training, "convnet.1.")
+    part = _empty((nt1, 2, C64), images) if stem_train else None
     # (the kernel reads the OIHW weight itself: no layout-prep launch)
-    if training and tails_on():
+    if stem_train and tails_on():
         bn1, tail = bn_tail_fwd("convnet.1.", params, buffers, C64, images, B * H1 * W1)
         call("cova_conv1_fwd_tail", images, params["convnet.0.weight"], y1, part, B, H, W, tail.ptr)
     else:
@@ -365,12 +428,12 @@ def convstack_fwd(images, params, buffers, training, save=True, lazy_out=False):
     p1 = _empty((B, H2, W2, C64), images)
     idx = _empty((B, H2, W2, C64), images, torch.uint8)
     # ymax = y1 at each window's arg-max: lets the last data-gradient conv take bn1's backward sums
-    want_ymax = save and (training or bottleneck)
+    want_ymax = save and (stem_train or bottleneck)
     ymax = _empty((B, H2, W2, C64), images) if want_ymax else None
     call("cova_bn_relu_maxpool_fwd", y1, bn1.scale, bn1.shift, p1, idx, ymax, B, H1, W1)
     sv.update(y1=y1, bn1=bn1, idx=idx, ymax=ymax)
     if bottleneck:
-        feat = _layer1_bottleneck_fwd(p1, params, buffers, training, lazy_out, sv)
+        feat = _layer1_bottleneck_fwd(p1, params, buffers, training, save, lazy_out, sv)
     else:
         feat = _layer1_basic_fwd(p1, params, buffers, training, save, lazy_out, sv)
     return feat, (sv if save else None)
@@ -405,7 +468,11 @@ def conv3_weights(ws, like):
 
 
 def conv_bn_fwd(u, inp, abc, relu, out, prefix, params, buffers, training, part, nt, R, B, H, W):
-    """3x3 conv (input relu?(abc . inp) on load) followed by a BatchNorm whose statistics it produces -> BNState"""
+    """3x3 conv (input relu?(abc . inp) on load) followed by a BatchNorm whose statistics it produces -> BNState.
+    An eval-mode BatchNorm (``training`` resolved for ``prefix``) takes no statistics: ``part`` is not written."""
+    training = is_train(training, prefix)
+    if not training:
+        part = None
     if training and tails_on():
         st, tail = bn_tail_fwd(prefix, params, buffers, C64, inp, R)
         conv3x3_pro(u, inp, None, abc, relu, None, None, None, None, None, None, None, out, part, B, H, W, tail)
@@ -415,7 +482,8 @@ def conv_bn_fwd(u, inp, abc, relu, out, prefix, params, buffers, training, part,
 
 
 def conv_bn_pair_fwd(ua, ub, x, z1, z2, pa, pb, params, buffers, training, part, nt, R, B, H, W):
-    """z1 = conv_a(x), bn_a;  z2 = conv_b(relu(bn_a(z1))) with a1 formed on load, bn_b  -> (BNState a, BNState b)"""
+    """z1 = conv_a(x), bn_a;  z2 = conv_b(relu(bn_a(z1))) with a1 formed on load, bn_b  -> (BNState a, BNState b).
+    Each BatchNorm follows its own mode (the tailed form only for a train-mode layer)."""
     bna = conv_bn_fwd(ua, x, None, 0, z1, pa, params, buffers, training, part, nt, R, B, H, W)
     bnb = conv_bn_fwd(ub, z1, bna.abc, 1, z2, pb, params, buffers, training, part, nt, R, B, H, W)
     return bna, bnb
@@ -425,7 +493,6 @@ def _layer1_basic_fwd(p1, params, buffers, training, save, lazy_out, sv):
     """layer1 of ResNet-18: two BasicBlocks (the reference's backbone, models.py:49-51)"""
     images = p1
     B, H, W, H1, W1, H2, W2 = sv["dims"]
-    infer = not training and not save
     wf, wd = sv.pop("_w3")                            # (requested in front of the stem, convstack_fwd)
     sv["wd"] = wd
     R = B * H2 * W2
@@ -433,7 +500,8 @@ def _layer1_basic_fwd(p1, params, buffers, training, save, lazy_out, sv):
     x = p1
     blocks = []
     for blk in (0, 1):
-        if infer:
+        ta, tb = is_train(training, BN3_KEYS[2 * blk]), is_train(training, BN3_KEYS[2 * blk + 1])
+        if not save and not ta and not tb:
             # inference: running statistics are known up front, so BatchNorm (+ residual) + ReLU sit in the conv
             # prologues / epilogues -- two launches per BasicBlock, nothing else touches the maps
             bna = bn_params(BN3_KEYS[2 * blk], params, buffers, C64, images, False)
@@ -454,7 +522,7 @@ def _layer1_basic_fwd(p1, params, buffers, training, save, lazy_out, sv):
             blocks.append(dict(x=x, z1=z1, a1=None, z2=None, out=out, bna=bna, bnb=bnb))
             x = feat = out
             continue
-        part = _empty((nt, 2, C64), images) if training else None
+        part = _empty((nt, 2, C64), images) if ta or tb else None
         z1, z2 = _empty((B, H2, W2, C64), images), _empty((B, H2, W2, C64), images)
         bna, bnb = conv_bn_pair_fwd(wf[2 * blk], wf[2 * blk + 1], x, z1, z2, BN3_KEYS[2 * blk], BN3_KEYS[2 * blk + 1],
                                     params, buffers, training, part, nt, R, B, H2, W2)
@@ -464,7 +532,7 @@ def _layer1_basic_fwd(p1, params, buffers, training, save, lazy_out, sv):
             feat = LazyFeature(z2, x, bnb.scale, bnb.shift)
         else:
             out = _empty((B, H2, W2, C64), images)
-            if blk == 0 and training and tails_on():
+            if blk == 0 and save and tb and tails_on():
                 # ... with its ReLU decisions as bits: the mask source of the next block's conv1 data gradient
                 out_bits = _empty((R, 2), images, torch.int32)
                 call("cova_bn_act_fwd_bits", z2, bnb.scale, bnb.shift, x, out, out_bits, R)
@@ -493,14 +561,14 @@ def conv1x1(inp, in2, abc, relu, w, w_trans, out, part, R, cin, cout, addend=Non
          z, mean, invstd, z2, mean2, invstd2, out, part, part2, R, cin, cout)
 
 
-def _layer1_bottleneck_fwd(p1, params, buffers, training, lazy_out, sv):
+def _layer1_bottleneck_fwd(p1, params, buffers, training, save, lazy_out, sv):
     B, H, W, H1, W1, H2, W2 = sv["dims"]
     R = B * H2 * W2
     nt = conv3_num_partials(B, H2, W2)
 
-    def stats(cin, cout):
+    def stats(cin, cout, prefix):
         n = query("cova_conv1x1_num_partials", R, cin, cout)
-        return (_empty((n, 2, cout), p1) if training else None), n
+        return (_empty((n, 2, cout), p1) if is_train(training, prefix) else None), n
 
     def bn(prefix, C, part, n):
         return bn_params(prefix, params, buffers, C, p1, training, part, n, R, unit="pages")
@@ -511,7 +579,7 @@ def _layer1_bottleneck_fwd(p1, params, buffers, training, lazy_out, sv):
     for blk in (0, 1, 2):
         pre = "convnet.4.%d." % blk
         s = dict(cin=cin, pre=pre)
-        part, n = stats(cin, C64)
+        part, n = stats(cin, C64, pre + "bn1.")
         s["z1"] = _empty((B, H2, W2, C64), p1)
         if pending is None:
             conv1x1(x, None, None, 0, params[pre + "conv1.weight"], 0, s["z1"], part, R, cin, C64)
@@ -520,25 +588,26 @@ def _layer1_bottleneck_fwd(p1, params, buffers, training, lazy_out, sv):
             # than a separate bn + residual + ReLU kernel)
             x = _empty((B, H2, W2, C256), p1)
             # ... together with its ReLU decisions, one bit per element: the mask source of this block's input gradient
-            s["x_bits"] = _empty((R, C256 // 32), p1, torch.int32) if training else None
+            s["x_bits"] = (_empty((R, C256 // 32), p1, torch.int32)
+                           if save and is_train(training, "convnet.4.%d.bn3." % (blk - 1)) else None)
             call("cova_conv1x1_materialize", pending[0], pending[1], pending[2], params[pre + "conv1.weight"], x,
                  s["x_bits"], s["z1"], part, R)
             blocks[-1]["out"] = x
         s["x"] = x
         s["bn1"] = bn(pre + "bn1.", C64, part, n)
         uf, s["ud"] = ufs[blk], uds[blk]
-        part = _empty((nt, 2, C64), p1) if training else None
+        part = _empty((nt, 2, C64), p1) if is_train(training, pre + "bn2.") else None
         s["z2"] = _empty((B, H2, W2, C64), p1)
         s["bn2"] = conv_bn_fwd(uf, s["z1"], s["bn1"].abc, 1, s["z2"], pre + "bn2.", params, buffers, training, part, nt,
                                R, B, H2, W2)
-        part, n = stats(C64, C256)
+        part, n = stats(C64, C256, pre + "bn3.")
         s["z3"] = _empty((B, H2, W2, C256), p1)
         conv1x1(s["z2"], None, s["bn2"].abc, 1, params[pre + "conv3.weight"], 0, s["z3"], part, R, C64, C256)
         s["bn3"] = bn(pre + "bn3.", C256, part, n)
         bn3 = s["bn3"]
         s["out"] = None
         if blk == 0:
-            part, n = stats(C64, C256)
+            part, n = stats(C64, C256, pre + "downsample.1.")
             s["zd"] = _empty((B, H2, W2, C256), p1)
             conv1x1(x, None, None, 0, params[pre + "downsample.0.weight"], 0, s["zd"], part, R, C64, C256)
             s["bnd"] = bn(pre + "downsample.1.", C256, part, n)
@@ -603,12 +672,16 @@ def _lin_conv_bn_bwd(v, act, act_abc, act_relu, w, st, R, gout, bn_prefix, w_key
     return avec, m, cvec
 
 
-def _layer1_bottleneck_bwd(sv, g, params, gout, grads, head_part):
+def _layer1_bottleneck_bwd(sv, g, params, gout, grads, head_part, plan=None):
     """Backward of the three Bottlenecks.  ``g`` = gradient w.r.t. the last block's output, already
     ReLU-masked.  The two 64->256 convolutions (conv3, downsample) and their BatchNorms run in linear form:
     sums, weight gradient and data gradient come from v^T a, a^T a, sum a, sum v, so no 256-channel conv
     output is read in the backward (``head_part``, RoIPool's own sums for the last bn3, is not needed).
-    Returns the ReLU-masked gradient w.r.t. the max-pool output (sv['pool_part'] holds the stem's sums)."""
+    Returns the ReLU-masked gradient w.r.t. the max-pool output (sv['pool_part'] holds the stem's sums), or None when
+    ``plan`` (grad_plan) leaves out the "stem" stage.  A 3x3 / conv1 weight whose "wgrad:" stage is left out gets no
+    weight-gradient launch (the 3x3 data gradient then reads its operand through the two-tensor prologue)."""
+    if plan is None:
+        plan = full_plan(params)
     B, H, W, H1, W1, H2, W2 = sv["dims"]
     R = B * H2 * W2
     nt = conv3_num_partials(B, H2, W2)
@@ -631,22 +704,26 @@ def _layer1_bottleneck_bwd(sv, g, params, gout, grads, head_part):
         dg, db, abc2 = _bn_abc_from_partials(part, nd, bn2, R, gout, pre + "bn2.", g)
         grads[pre + "bn2.weight"], grads[pre + "bn2.bias"] = dg, db
         # conv2 (3x3): Winograd weight / data gradient, bn1's ReLU mask + sums in the epilogue
-        dw = _gbuf(gout, pre + "conv2.weight", (C64, C64, 3, 3), g)
-        # ... with dz2 = abc2 . (dy2, z2) as its side output: the data gradient below reads one tensor, no prologue
-        dzm = _empty((B, H2, W2, C64), g)
-        call("cova_conv3x3_wgrad4_partial", s["z1"], bn1.abc, 1, dy2, s["z2"], abc2, dzm, ws3, B, H2, W2)
-        call("cova_conv3x3_wgrad4_finish", ws3, dw, None, None, None, None, None, None, B, H2, W2)
-        d_in, d_in2, d_abc = dzm, None, None
-        grads[pre + "conv2.weight"] = dw
+        if "wgrad:" + pre + "conv2.weight" in plan:
+            dw = _gbuf(gout, pre + "conv2.weight", (C64, C64, 3, 3), g)
+            # ... with dz2 = abc2 . (dy2, z2) as its side output: the data gradient below reads one tensor, no prologue
+            dzm = _empty((B, H2, W2, C64), g)
+            call("cova_conv3x3_wgrad4_partial", s["z1"], bn1.abc, 1, dy2, s["z2"], abc2, dzm, ws3, B, H2, W2)
+            call("cova_conv3x3_wgrad4_finish", ws3, dw, None, None, None, None, None, None, B, H2, W2)
+            d_in, d_in2, d_abc = dzm, None, None
+            grads[pre + "conv2.weight"] = dw
+        else:
+            d_in, d_in2, d_abc = dy2, s["z2"], abc2
         dy1 = _empty((B, H2, W2, C64), g)
         part = _empty((nt, 2, C64), g)
         dg, db, abc1 = dgrad_bn_bwd(s["ud"], d_in, d_in2, d_abc, None, None, bn1.scale, bn1.shift, s["z1"], bn1, dy1, part,
                                     nt, R, gout, pre + "bn1.", B, H2, W2)
         grads[pre + "bn1.weight"], grads[pre + "bn1.bias"] = dg, db
         # conv1 (Cin->64): dz1 = abc1 . (dy1, z1) on load
-        dw = _gbuf(gout, pre + "conv1.weight", (C64, cin, 1, 1), g)
-        call("cova_conv1x1_wgrad", dy1, s["z1"], abc1, s["x"], None, 0, dw, ws1, R, C64, cin)
-        grads[pre + "conv1.weight"] = dw
+        if "wgrad:" + pre + "conv1.weight" in plan:
+            dw = _gbuf(gout, pre + "conv1.weight", (C64, cin, 1, 1), g)
+            call("cova_conv1x1_wgrad", dy1, s["z1"], abc1, s["x"], None, 0, dw, ws1, R, C64, cin)
+            grads[pre + "conv1.weight"] = dw
         if blk > 0:
             # gradient w.r.t. the previous block's output = conv1's data gradient + the identity branch,
             # masked by that output's ReLU (its BatchNorm sums are taken by the next iteration's v^T a)
@@ -663,6 +740,8 @@ def _layer1_bottleneck_bwd(sv, g, params, gout, grads, head_part):
             wdn = params[pre + "downsample.0.weight"]
             avd, md, cvd = _lin_conv_bn_bwd(g, s["x"], None, 0, wdn, s["bnd"], R, gout, pre + "downsample.1.",
                                             pre + "downsample.0.weight", grads, ws1)
+            if "stem" not in plan:
+                return None
             t = _empty((B, H2, W2, C64), g)
             conv1x1(dy1, s["z1"], abc1, 0, w1, 1, t, None, R, C64, C64)
             sv["pool_part"], sv["pool_npart"] = _empty((nd, 2, C64), g), nd
@@ -733,24 +812,36 @@ def _bn_abc_from_partials(part, nparts, st, R, gout, prefix, like):
     return dgamma, dbeta, abc
 
 
-def _layer1_bwd_fused(sv, dfeat, gout, grads, head_part=None):
+def _layer1_bwd_fused(sv, dfeat, gout, grads, head_part=None, plan=None):
     """Backward of the two BasicBlocks with every BatchNorm-backward apply (except the one fed by
     RoIPool's scatter) and both a1 = relu(bn1(z1)) recomputations folded into the Winograd kernels.
-    Returns the gradient w.r.t. the max-pool output; sv['pool_abc'] = (dgamma, dbeta, abc) of the stem's BatchNorm."""
+    Returns the gradient w.r.t. the max-pool output; sv['pool_abc'] = (dgamma, dbeta, abc) of the stem's BatchNorm.
+    ``plan`` (grad_plan; None = everything): a 3x3 weight without its "wgrad:" stage gets no partial launch (its finish
+    slot is empty, the data gradient that follows reads its operand through the two-tensor prologue); without "stem"
+    block 0's conv1 data gradient is not issued and None is returned."""
+    if plan is None:
+        plan = frozenset(["stem"] + ["wgrad:%s.weight" % k for k in CONV3_KEYS])
     B, H, W, H1, W1, H2, W2 = sv["dims"]
     R = B * H2 * W2
     # weight gradients: the four launches leave their per-block partial sums in four workspaces, ONE launch at the end
     # folds and transforms them (4 x 67 MB at configs[1]; a shared workspace would need a finish launch per convolution)
     wg = "cova_conv3x3_wgrad4"
     nws = query("cova_conv3x3_wgrad4_workspace_floats", B, H2, W2)
-    ws_all = _empty((4, nws), dfeat)
-    jobs = []
+    wanted = [k for k in CONV3_KEYS if "wgrad:%s.weight" % k in plan]
+    ws_all = _empty((len(wanted), nws), dfeat) if wanted else None
+    jobs = {}               # finish slot (launch order: block 1 conv2, conv1, block 0 conv2, conv1) -> (workspace, dw)
 
-    def wgrad(act, act_abc, act_relu, dz, dz2, dz_abc, dw):
-        """-> the gradient operand dz_abc . (dz, dz2) as a materialised map (F(4x4) kernel's side output) or None"""
-        out = torch.empty_like(dz) if dz_abc is not None else None
-        call(wg + "_partial", act, act_abc, act_relu, dz, dz2, dz_abc, out, ws_all[len(jobs)], B, H2, W2)
-        jobs.append(dw)
+    def wgrad(key, act, act_abc, act_relu, dz, dz2, dz_abc, side=True):
+        """-> the gradient operand dz_abc . (dz, dz2) as a materialised map (F(4x4) kernel's side output) or None;
+        nothing is launched for a weight outside the plan"""
+        if key not in wanted:
+            return None
+        dw = _gbuf(gout, key + ".weight", (64, 64, 3, 3), dfeat)
+        out = torch.empty_like(dz) if dz_abc is not None and side else None
+        ws = ws_all[len(jobs)]
+        call(wg + "_partial", act, act_abc, act_relu, dz, dz2, dz_abc, out, ws, B, H2, W2)
+        jobs[3 - CONV3_KEYS.index(key)] = (ws, dw)
+        grads[key + ".weight"] = dw
         return out
 
     nt = conv3_num_partials(B, H2, W2)
@@ -778,9 +869,7 @@ def _layer1_bwd_fused(sv, dfeat, gout, grads, head_part=None):
             dg, db, g_abc = pend
             g_in, g_in2 = dA, s["z2"]
         grads[pb + "weight"], grads[pb + "bias"] = dg, db
-        dw = _gbuf(gout, kb + ".weight", (64, 64, 3, 3), dfeat)
-        dzm = wgrad(s["z1"], bna.abc, 1, g_in, g_in2, g_abc, dw)
-        grads[kb + ".weight"] = dw
+        dzm = wgrad(kb, s["z1"], bna.abc, 1, g_in, g_in2, g_abc)
         if dzm is not None:             # the data gradient below reads the materialised operand: one tensor, no prologue
             g_in, g_in2, g_abc = dzm, None, None
         # ---- dgrad of conv2 with bn1's ReLU mask (recomputed from z1) + backward sums in the epilogue
@@ -789,9 +878,11 @@ def _layer1_bwd_fused(sv, dfeat, gout, grads, head_part=None):
         dg, db, abc_a = dgrad_bn_bwd(sv["wd"][2 * blk + 1], g_in, g_in2, g_abc, None, None, bna.scale, bna.shift, s["z1"],
                                      bna, dy_a, part, nt, R, gout, pa, B, H2, W2)
         grads[pa + "weight"], grads[pa + "bias"] = dg, db
-        dw = _gbuf(gout, ka + ".weight", (64, 64, 3, 3), dfeat)
-        dzm = wgrad(s["x"], None, 0, dy_a, s["z1"], abc_a, dw)
-        grads[ka + ".weight"] = dw
+        last_dgrad = blk == 1 or "stem" in plan         # (block 0's conv1 data gradient: only for the stem's backward)
+        dzm = wgrad(ka, s["x"], None, 0, dy_a, s["z1"], abc_a, side=last_dgrad)
+        if not last_dgrad:
+            dA = None
+            break
         d_in, d_in2, d_abc = (dy_a, s["z1"], abc_a) if dzm is None else (dzm, None, None)
         # ---- dgrad of conv1 (+ residual gradient); for block 1 the epilogue prepares block 0's bn2
         dx = torch.empty_like(dA)
@@ -810,10 +901,11 @@ def _layer1_bwd_fused(sv, dfeat, gout, grads, head_part=None):
             conv3x3_pro(sv["wd"][2 * blk], d_in, d_in2, d_abc, 0, dres, None, None, None, None, None, None, dx,
                         None, B, H2, W2)
         dA = dx
-    fin = []
-    for i in range(4):
-        fin += [ws_all[i], jobs[i]]
-    call(wg + "_finish", *fin, B, H2, W2)
+    if jobs:
+        fin = []
+        for i in range(4):
+            fin += list(jobs.get(i, (None, None)))
+        call(wg + "_finish", *fin, B, H2, W2)
     return dA
 
 
@@ -835,7 +927,7 @@ def masked_grad_and_sums(dout, last, R):
 
 
 @on_device_of(1)
-def convstack_bwd(sv, dfeat, gout=None, head_part=None, params=None, want_dimg=False):
+def convstack_bwd(sv, dfeat, gout=None, head_part=None, params=None, want_dimg=False, plan=None):
     """dfeat NHWC [B,Hf,Wf,C] -> {state_dict key: grad} for the convs and BatchNorms of the stack; with ``want_dimg`` also
     the gradient w.r.t. the images (NCHW) under the key "__images__" (needs ``params``: conv1's weight).
 
@@ -843,7 +935,8 @@ def convstack_bwd(sv, dfeat, gout=None, head_part=None, params=None, want_dimg=F
     in front of them in their epilogue (and its finalize in their tail), so only the last block's bn2
     (whose incoming gradient is RoIPool's scatter) needs a stand-alone reduction / finalize.
     ``params`` is needed by the resnet50 extension (its 1x1 convs read the weights directly) and by ``want_dimg``
-    (conv1's weight)."""
+    (conv1's weight).  ``plan`` (grad_plan; None = every gradient): the stages it leaves out are not launched and their
+    gradients are absent from the result."""
     if want_dimg and (params is None or "convnet.0.weight" not in params):
         raise ValueError("convstack_bwd(want_dimg=True) needs params with 'convnet.0.weight' (the transposed conv1)")
     if sv["kind"] == "bottleneck" and params is None:
@@ -851,16 +944,21 @@ def convstack_bwd(sv, dfeat, gout=None, head_part=None, params=None, want_dimg=F
     B, H, W, H1, W1, H2, W2 = sv["dims"]
     R = B * H2 * W2
     grads = {}
+    if plan is not None and want_dimg:
+        plan = plan | {"stem"}
     if sv["kind"] == "bottleneck":
         if head_part is None:          # piecewise API (_get_visual_features): mask + sums stand-alone
             dfeat, head_part = masked_grad_and_sums(dfeat, sv["last"], R)
-        dA = _layer1_bottleneck_bwd(sv, dfeat, params, gout, grads, head_part)
+        dA = _layer1_bottleneck_bwd(sv, dfeat, params, gout, grads, head_part, plan)
     else:
-        dA = _layer1_bwd_fused(sv, dfeat, gout, grads, head_part)
+        dA = _layer1_bwd_fused(sv, dfeat, gout, grads, head_part, plan)
+    if dA is None:                      # the plan ends at layer1 (stem frozen, no image gradient)
+        return grads
     # maxpool + relu + bn1, then conv1's weight gradient
     bn1 = sv["bn1"]
-    ws1 = _empty((query("cova_conv1_wgrad_workspace_floats", B, H, W),), dfeat)
-    dw1 = _gbuf(gout, "convnet.0.weight", (64, 3, 7, 7), dfeat)
+    wgrad1 = plan is None or "conv1_wgrad" in plan
+    ws1 = _empty((query("cova_conv1_wgrad_workspace_floats", B, H, W),), dfeat) if wgrad1 else None
+    dw1 = _gbuf(gout, "convnet.0.weight", (64, 3, 7, 7), dfeat) if wgrad1 else None
     pool_abc = sv.get("pool_abc")
     if pool_abc is None and sv.get("pool_part") is not None:        # (resnet50 stack: its last launch left the partials)
         dg = _gbuf(gout, "convnet.1.weight", (C64,), dfeat)
@@ -871,7 +969,8 @@ def convstack_bwd(sv, dfeat, gout=None, head_part=None, params=None, want_dimg=F
         # dA is already ReLU-masked (epilogue of the last data-gradient conv): the pooling/BN backward
         # apply is folded into conv1's weight-gradient kernel, dy1 is never written
         dg, db, abc = pool_abc
-        call("cova_conv1_wgrad_poolbwd", sv["images"], sv["y1"], dA, sv["idx"], abc, dw1, ws1, B, H, W)
+        if wgrad1:
+            call("cova_conv1_wgrad_poolbwd", sv["images"], sv["y1"], dA, sv["idx"], abc, dw1, ws1, B, H, W)
         if want_dimg:                   # images.requires_grad: dy1 written out once, then the transposed convolution
             dy1 = torch.empty_like(sv["y1"])
             call("cova_pool_bwd_dy1", dA, sv["idx"], sv["y1"], abc, dy1, B, H1, W1)
@@ -883,12 +982,15 @@ def convstack_bwd(sv, dfeat, gout=None, head_part=None, params=None, want_dimg=F
         dg = _gbuf(gout, "convnet.1.weight", (C64,), dfeat)
         db = _gbuf(gout, "convnet.1.bias", (C64,), dfeat)
         coef = bn_finalize_bwd(part, npart, C64, B * H1 * W1, dg, db, "pages", frozen=bn1.frozen)
-        dy1 = torch.empty_like(sv["y1"])
-        call("cova_bn_relu_maxpool_bwd_apply", dA, sv["idx"], sv["y1"], bn1.scale, bn1.shift, bn1.mean,
-             bn1.invstd, coef, dy1, B, H1, W1)
-        call("cova_conv1_wgrad", sv["images"], dy1, dw1, ws1, B, H, W)
+        if wgrad1 or want_dimg:
+            dy1 = torch.empty_like(sv["y1"])
+            call("cova_bn_relu_maxpool_bwd_apply", dA, sv["idx"], sv["y1"], bn1.scale, bn1.shift, bn1.mean,
+                 bn1.invstd, coef, dy1, B, H1, W1)
+        if wgrad1:
+            call("cova_conv1_wgrad", sv["images"], dy1, dw1, ws1, B, H, W)
     grads["convnet.1.weight"], grads["convnet.1.bias"] = dg, db
-    grads["convnet.0.weight"] = dw1
+    if wgrad1:
+        grads["convnet.0.weight"] = dw1
     if want_dimg:
         dimg = torch.empty_like(sv["images"])
         call("cova_conv1_dgrad", dy1, params["convnet.0.weight"], dimg, B, H, W)
@@ -984,7 +1086,8 @@ def bn1d_fused(training):
 
 def bn1d_fwd(x, ldx, N, C, prefix, params, buffers, training, out, ldo, relu, drop=None):
     """BatchNorm1d (+ReLU) of x [N,C] into out.  ``drop`` = (p, seed, mask or None): also the Dropout of the result
-    -> returns (BNState, dropped, mask)."""
+    -> returns (BNState, dropped, mask).  ``training``: bool or per-layer modes (resolved for ``prefix``)."""
+    training = is_train(training, prefix)
     if bn1d_fused(training) and N > 0:
         st = bn_state(C, x, N, True)
         dropped = mask = None
@@ -1168,11 +1271,14 @@ def dropout_fwd(x, ld, N, C, p, seed, mask=None):
 
 def decoder_fwd(x, N, T, params, buffers, training, p, seeds=(0, 0), masks=None):
     """models.py:83-90 on the concatenated features x [N,T]: Dropout, Linear, BN1d, ReLU, Dropout,
-    Linear.  ``masks`` (two uint8 [N,T] keep-masks) override the generated ones (parity tests)."""
+    Linear.  ``masks`` (two uint8 [N,T] keep-masks) override the generated ones (parity tests).  Each Dropout
+    ("decoder.0", "decoder.3") and the BatchNorm follow their own mode in ``training`` (is_train)."""
     NC = params["decoder.5.weight"].shape[0]
-    drop = training and (p > 0 or masks is not None)
-    sv = dict(N=N, T=T, NC=NC, drop=drop, p=p)
-    xd, m1 = dropout_fwd(x, T, N, T, p, seeds[0], masks[0] if masks else None) if drop else (x, None)
+    active = p > 0 or masks is not None
+    drop1 = is_train(training, DROPOUT_KEYS[0]) and active
+    drop = is_train(training, DROPOUT_KEYS[1]) and active
+    sv = dict(N=N, T=T, NC=NC, drop=drop, drop1=drop1, p=p)
+    xd, m1 = dropout_fwd(x, T, N, T, p, seeds[0], masks[0] if masks else None) if drop1 else (x, None)
     z = _empty((N, T), x)
     call("cova_sgemm", 0, 1, N, T, T, xd, T, params["decoder.1.weight"], T, z, T,
          params["decoder.1.bias"], 0)
@@ -1205,7 +1311,7 @@ def decoder_bwd(sv, dlogits, params, gout=None):
     dW1 = _gbuf(gout, "decoder.1.weight", (T, T), dlogits)
     call("cova_sgemm", 1, 0, T, T, N, dz, T, sv["xd"], T, dW1, T, None, 0)
     dx = dyd        # (dead by now: reuse)
-    if sv["drop"]:  # the first Dropout's backward in the GEMM's epilogue (one launch less, same bits)
+    if sv.get("drop1", sv["drop"]):  # the first Dropout's backward in the GEMM's epilogue (one launch less, same bits)
         call("cova_sgemm_dropout_bwd", 0, 0, N, T, T, dz, T, params["decoder.1.weight"], T, dx, T, sv["m1"], float(p))
     else:
         call("cova_sgemm", 0, 0, N, T, T, dz, T, params["decoder.1.weight"], T, dx, T, None, 0)
@@ -1217,8 +1323,10 @@ def decoder_bwd(sv, dlogits, params, gout=None):
 # ------------------------------------------------------------------------------- whole model
 @on_device_of(3)
 def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_indices, training,
-              seeds=(0, 0), masks=None, save=True):
-    """CoVA.forward (models.py:94-122) -> (logits [N,n_classes], saved-for-backward or None)."""
+              seeds=(0, 0), masks=None, save=True, plan=None):
+    """CoVA.forward (models.py:94-122) -> (logits [N,n_classes], saved-for-backward or None).
+    ``training``: a bool (whole model) or per-layer modes {BatchNorm prefix / Dropout name: bool} (is_train).
+    ``plan`` (grad_plan, with ``save``): without its "convstack" stage the conv stack keeps no activations."""
     N = bboxes.shape[0]
     PH, PW = cfg["roi_output_size"]
     n_vis = (C256 if is_bottleneck(params) else C64) * PH * PW
@@ -1227,7 +1335,8 @@ def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_in
     D = cfg["hidden_dim"] if cfg["use_context"] else 0
     T = F + D
     align = cfg.get("roi_op", "pool") == "align"
-    feat, sv_conv = convstack_fwd(images, params, buffers, training, save, lazy_out=not align)
+    save_conv = save and (plan is None or "convstack" in plan)
+    feat, sv_conv = convstack_fwd(images, params, buffers, training, save_conv, lazy_out=not align)
     comb = _empty((N, T), images)
     scale = cfg.get("spatial_scale") or feat.shape[1] / images.shape[2]   # models.py:56
     sv = dict(cfg=cfg, N=N, F=F, D=D, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=sv_conv, comb=comb)
@@ -1252,32 +1361,40 @@ def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_in
 
 
 @on_device_of(1)
-def model_bwd(sv, dlogits, params, gout=None, after_head=None, want_dimg=False):
+def model_bwd(sv, dlogits, params, gout=None, after_head=None, want_dimg=False, plan=None):
     """-> {state_dict key: gradient} for every trainable parameter (+ "__images__" with ``want_dimg``).  ``gout`` (optional)
     maps keys to pre-allocated destinations, e.g. views into one flat all-reduce bucket.
     ``after_head`` (optional callable) runs once every gradient outside the conv stack is final
-    (the trainer starts their all-reduce there, under the conv-stack backward)."""
+    (the trainer starts their all-reduce there, under the conv-stack backward).
+    ``plan`` (grad_plan; None = every gradient): the backward stages it leaves out are not launched and their gradients
+    are absent from the result (the forward must have had the same plan)."""
+    if plan is not None and want_dimg:
+        plan = plan | {"convstack", "stem"}
     N, F, D, T, n_vis, Hd, A = (sv[k] for k in ("N", "F", "D", "T", "n_vis", "Hd", "A"))
     dcomb, grads = decoder_bwd(sv["dec"], dlogits, params, gout)
     if D > 0:
         grads.update(gat_stack_bwd(sv["gat"], dcomb, T, N, F, D, params, gout))
-    if A > 0:
+    if A > 0 and (plan is None or "addl" in plan):
         st = sv["addl"]
         dz = _empty((N, A), dcomb)
         dg, db = bn_backward(dcomb[:, n_vis + Hd:], T, None, 0, sv["addl_in"], A, st, N, dz, A, None, 0,
                              gout, "bn_additional_feat.")
         grads["bn_additional_feat.weight"], grads["bn_additional_feat.bias"] = dg, db
-    if Hd > 0:
+    if Hd > 0 and (plan is None or "bbox" in plan):
         grads.update(bbox_bwd(sv["bbox"], dcomb[:, n_vis:], T, gout))
     if after_head is not None:
         after_head()
     conv = sv["conv"]
+    if plan is not None and "convstack" not in plan:
+        return grads
+    if conv is None:
+        raise RuntimeError("model_bwd: the forward kept no conv-stack activations (its plan had no 'convstack' stage)")
     if N > 0 and sv["roi"]["zmax"] is not None:
         dfeat, head_part = roipool_bwd_bn(sv["roi"], dcomb, T, conv["last"], gout)
-        grads.update(convstack_bwd(conv, dfeat, gout, head_part, params, want_dimg))
+        grads.update(convstack_bwd(conv, dfeat, gout, head_part, params, want_dimg, plan))
     else:
         dfeat = roialign_bwd(sv["roi"], dcomb, T) if sv["roi"].get("kind") == "align" else roipool_bwd(sv["roi"], dcomb, T)
-        grads.update(convstack_bwd(conv, dfeat, gout, None, params, want_dimg))
+        grads.update(convstack_bwd(conv, dfeat, gout, None, params, want_dimg, plan))
     return grads
 
 

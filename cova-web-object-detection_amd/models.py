@@ -103,6 +103,34 @@ def _verify_batch_size(training, n, width):
                          "torch.Size([1, %d])" % width)
 
 
+def _layer_modes(model):
+    """Each BatchNorm's and Dropout's own ``.training`` ({BatchNorm prefix / Dropout name: bool}, engine.is_train), or
+    one bool when they all agree (whole-model train() / eval(): exactly the launches of the single flag)."""
+    modes = {}
+    for name, m in model.named_modules():
+        if isinstance(m, nn.modules.batchnorm._BatchNorm):
+            modes[name + "."] = m.training
+        elif isinstance(m, nn.Dropout):
+            modes[name] = m.training
+    return engine.collapse_modes(modes) if modes else model.training
+
+
+def _plan(keys, values, want_dimg):
+    """engine.grad_plan of a call whose parameters ``keys``/``values`` follow their own requires_grad; None when
+    autograd wants nothing of it (no saved activations, no backward)."""
+    if not torch.is_grad_enabled():
+        return None
+    need = [k for k, v in zip(keys, values) if v.requires_grad]
+    if not need and not want_dimg:
+        return None
+    return engine.grad_plan(need, want_dimg)
+
+
+def _only_wanted(ctx, first, keys, grads):
+    """Gradients in autograd's order; None for every input that does not require one (frozen parameters)."""
+    return tuple(grads.get(k) if ctx.needs_input_grad[first + i] else None for i, k in enumerate(keys))
+
+
 def _saved_or_raise(sv):
     """The saved activations are released by the first backward (like autograd's saved tensors)."""
     if sv is None:
@@ -116,7 +144,7 @@ class _CoVAFn(torch.autograd.Function):
     """Whole forward pass as one autograd node: backward runs engine.model_bwd."""
 
     @staticmethod
-    def forward(ctx, model, need_grad, images, bboxes, additional_feats, context_indices,
+    def forward(ctx, model, modes, plan, images, bboxes, additional_feats, context_indices,
                 *param_values):
         keys = model._param_keys
         params = dict(zip(keys, [p.detach() for p in param_values]))
@@ -124,27 +152,27 @@ class _CoVAFn(torch.autograd.Function):
         seeds = model._next_dropout_seeds()
         logits, sv = engine.model_fwd(model._cfg, params, buffers, _f32c(images), _f32c(bboxes),
                                       _f32c(additional_feats), _i64c(context_indices),
-                                      model.training, seeds, model._forced_masks, save=need_grad)
-        ctx.sv, ctx.params, ctx.keys = sv, params, keys
+                                      modes, seeds, model._forced_masks, save=plan is not None, plan=plan)
+        ctx.sv, ctx.params, ctx.keys, ctx.plan = sv, params, keys, plan
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
         _saved_or_raise(ctx.sv)
-        want_dimg = bool(ctx.needs_input_grad[2])            # images.requires_grad (the reference gets it from autograd)
-        grads = engine.model_bwd(ctx.sv, dlogits.contiguous(), ctx.params, want_dimg=want_dimg)
+        want_dimg = bool(ctx.needs_input_grad[3])            # images.requires_grad (the reference gets it from autograd)
+        grads = engine.model_bwd(ctx.sv, dlogits.contiguous(), ctx.params, want_dimg=want_dimg, plan=ctx.plan)
         ctx.sv = None
-        return (None, None, grads.get("__images__"), None, None, None) + tuple(grads.get(k) for k in ctx.keys)
+        return (None, None, None, grads.get("__images__"), None, None, None) + _only_wanted(ctx, 7, ctx.keys, grads)
 
 
 class _VisualFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, model, need_grad, images, bboxes, *param_values):
+    def forward(ctx, model, modes, plan, images, bboxes, *param_values):
         keys = model._conv_keys
         params = dict(zip(keys, [p.detach() for p in param_values]))
         _, buffers = _named_tensors(model)
         images, bboxes = _f32c(images), _f32c(bboxes)
-        feat, sv = engine.convstack_fwd(images, params, buffers, model.training, need_grad)
+        feat, sv = engine.convstack_fwd(images, params, buffers, modes, plan is not None and "convstack" in plan)
         out = torch.empty((bboxes.shape[0], model.n_visual_feat), device=images.device)
         if model._cfg["roi_op"] == "align":
             rsv = engine.roialign_fwd(feat, bboxes, model.roi_pool.output_size, model.roi_pool.spatial_scale,
@@ -153,15 +181,16 @@ class _VisualFn(torch.autograd.Function):
         else:
             rsv = engine.roipool_fwd(feat, bboxes, model.roi_pool.output_size,
                                      model.roi_pool.spatial_scale, out, model.n_visual_feat)
-        ctx.sv, ctx.rsv, ctx.keys, ctx.nv, ctx.params = sv, rsv, keys, model.n_visual_feat, params
+        ctx.sv, ctx.rsv, ctx.keys, ctx.nv, ctx.params, ctx.plan = sv, rsv, keys, model.n_visual_feat, params, plan
         return out
 
     @staticmethod
     def backward(ctx, gout):
         bwd = engine.roialign_bwd if ctx.rsv.get("kind") == "align" else engine.roipool_bwd
         gfeat = bwd(ctx.rsv, gout.contiguous(), ctx.nv)
-        grads = engine.convstack_bwd(ctx.sv, gfeat, params=ctx.params, want_dimg=bool(ctx.needs_input_grad[2]))
-        return (None, None, grads.get("__images__"), None) + tuple(grads.get(k) for k in ctx.keys)
+        grads = engine.convstack_bwd(ctx.sv, gfeat, params=ctx.params, want_dimg=bool(ctx.needs_input_grad[3]),
+                                     plan=ctx.plan)
+        return (None, None, None, grads.get("__images__"), None) + _only_wanted(ctx, 5, ctx.keys, grads)
 
 
 class _BBoxFn(torch.autograd.Function):
@@ -172,14 +201,14 @@ class _BBoxFn(torch.autograd.Function):
         _, buffers = _named_tensors(model)
         bboxes = _f32c(bboxes)
         out = torch.empty((bboxes.shape[0], model.bbox_hidden_dim), device=bboxes.device)
-        ctx.sv = engine.bbox_fwd(bboxes, params, buffers, model.training, out, model.bbox_hidden_dim)
+        ctx.sv = engine.bbox_fwd(bboxes, params, buffers, _layer_modes(model), out, model.bbox_hidden_dim)
         ctx.keys, ctx.hd = keys, model.bbox_hidden_dim
         return out
 
     @staticmethod
     def backward(ctx, gout):
         grads = engine.bbox_bwd(ctx.sv, gout.contiguous(), ctx.hd)
-        return (None, None) + tuple(grads.get(k) for k in ctx.keys)
+        return (None, None) + _only_wanted(ctx, 2, ctx.keys, grads)
 
 
 class _BN1dFn(torch.autograd.Function):
@@ -201,7 +230,7 @@ class _BN1dFn(torch.autograd.Function):
         N, C = x.shape
         dz = torch.empty_like(x)
         dg, db = engine.bn_backward(gout.contiguous(), C, None, 0, x, C, ctx.st, N, dz, C)
-        return None, dz, dg, db
+        return (None, dz if ctx.needs_input_grad[1] else None) + _only_wanted(ctx, 2, ("w", "b"), {"w": dg, "b": db})
 
 
 class _HipBatchNorm1d(nn.BatchNorm1d):
@@ -435,12 +464,13 @@ class CoVA(nn.Module):
         """images [B,3,H,W] f32, bboxes [N,5] f32 = [batch_idx,x1,y1,x2,y2], additional_feats
         [N,A] f32, context_indices int64 [N,K] (-1 pads) -> scores [N,n_classes] (models.py:94-122)."""
         _require_cuda(images, bboxes, additional_feats, context_indices)
-        engine.check_batch(self._cfg, images, bboxes, additional_feats, context_indices, self.training)
+        modes = _layer_modes(self)
+        engine.check_batch(self._cfg, images, bboxes, additional_feats, context_indices, modes)
         if bboxes.shape[0] == 0:
             return torch.empty((0, self.n_classes), device=images.device)
         values = [p for _, p in self.named_parameters()]
-        need_grad = torch.is_grad_enabled() and (images.requires_grad or any(p.requires_grad for p in values))
-        return _CoVAFn.apply(self, need_grad, images, bboxes, additional_feats, context_indices,
+        plan = _plan(self._param_keys, values, images.requires_grad)
+        return _CoVAFn.apply(self, modes, plan, images, bboxes, additional_feats, context_indices,
                              *values)
 
     def _get_visual_features(self, images, bboxes):
@@ -450,8 +480,8 @@ class CoVA(nn.Module):
                                % (tuple(images.shape), tuple(bboxes.shape)))
         named = dict(self.named_parameters())
         values = [named[k] for k in self._conv_keys]
-        need_grad = torch.is_grad_enabled() and (images.requires_grad or any(p.requires_grad for p in values))
-        return _VisualFn.apply(self, need_grad, images, bboxes, *values)
+        plan = _plan(self._conv_keys, values, images.requires_grad)
+        return _VisualFn.apply(self, _layer_modes(self), plan, images, bboxes, *values)
 
     def _get_bbox_features(self, bboxes):
         """[x,y,w,h,asp_ratio] -> Linear -> BN -> ReLU (models.py:129-148)."""
@@ -459,7 +489,7 @@ class CoVA(nn.Module):
             _require_cuda(bboxes)
             if bboxes.dim() != 2 or bboxes.shape[1] != 5:
                 raise RuntimeError("expected bboxes [N, 5], got %s" % (tuple(bboxes.shape),))
-            _verify_batch_size(self.training, bboxes.shape[0], self.bbox_hidden_dim)
+            _verify_batch_size(self.bbox_feat_encoder[1].training, bboxes.shape[0], self.bbox_hidden_dim)
             named = dict(self.named_parameters())
             return _BBoxFn.apply(self, bboxes, *[named[k] for k in self._bbox_keys])
         return bboxes[:, :0]

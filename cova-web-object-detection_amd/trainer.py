@@ -57,6 +57,11 @@ class FlatBucket:
         return dist.all_reduce(self.flat[lo:hi], op=dist.ReduceOp.SUM, group=group, async_op=async_op)
 
 
+def _named_by(name, entries):
+    """state_dict key / BatchNorm prefix ``name`` is named by one of ``entries`` (keys or key prefixes)."""
+    return any(name.startswith(e) or e.startswith(name) for e in entries)
+
+
 def shard_pages(n_pages, rank, world_size):
     """Contiguous page range [lo, hi) of this rank (whole pages only)."""
     base, rem = divmod(n_pages, world_size)
@@ -82,10 +87,16 @@ def shard_batch(batch, rank, world_size):
 
 
 class HotPathTrainer:
-    """Owns flat parameters / gradients / Adam moments on one GPU and runs training steps."""
+    """Owns flat parameters / gradients / Adam moments on one GPU and runs training steps.
+
+    Fine-tuning: ``frozen`` (state_dict keys or key prefixes, e.g. ("convnet.",)) get no gradient work (engine.grad_plan
+    leaves out every backward stage that only they need) and are not touched by Adam (no update, no weight decay, moments
+    unchanged: torch.optim.Adam's treatment of a parameter whose grad is None).  ``bn_eval`` (keys or prefixes of
+    BatchNorm layers) normalise with their running statistics, leave their buffers alone and take no part in the SyncBN
+    exchange.  Flat buffers, state_dict() and optimizer_state_dict() keep their layout either way."""
 
     def __init__(self, cfg, state_dict, device, lr=5e-4, weight_decay=1e-3, betas=(0.9, 0.999),
-                 eps=1e-8, world_size=1, process_group=None, dropout_seed=123, sync_bn=False):
+                 eps=1e-8, world_size=1, process_group=None, dropout_seed=123, sync_bn=False, frozen=(), bn_eval=()):
         self.cfg = dict(cfg)
         self.device = torch.device(device)
         spec = state_dict_spec(**{k: cfg[k] for k in ("roi_output_size", "n_classes", "use_context",
@@ -108,10 +119,39 @@ class HotPathTrainer:
         self.world_size, self.group = world_size, process_group
         self.step_count, self.dropout_seed = 0, int(dropout_seed)
         self.sync_bn = bool(sync_bn) and world_size > 1
+        self._setup_finetune(tuple(frozen), tuple(bn_eval))
         self._ar_events = []              # (start, end) HIP events around the collective waits of optimizer_step
         self.measure_allreduce = True     # record them (up to 4096 steps; exposed_allreduce_ms() drains the list)
         if world_size > 1:
             self.broadcast_state(src=0)
+
+    def _setup_finetune(self, frozen, bn_eval):
+        for what, entries, names in (("frozen", frozen, list(self.params)),
+                                     ("bn_eval", bn_eval, [k[:-len("running_mean")] for k in self.buffers
+                                                           if k.endswith("running_mean")])):
+            unknown = [e for e in entries if not any(_named_by(n, (e,)) for n in names)]
+            if unknown:
+                raise ValueError("%s names no %s: %s" % (what, "parameter" if what == "frozen" else "BatchNorm", unknown))
+        self.frozen = frozenset(k for k in self.params if _named_by(k, frozen))
+        eval_bns = [k[:-len("running_mean")] for k in self.buffers if k.endswith("running_mean")]
+        eval_bns = [p for p in eval_bns if _named_by(p, bn_eval)]
+        # (no entry: the bool of today's steps, exactly its launches)
+        self.modes = {p: False for p in eval_bns} if eval_bns else True
+        self.plan = engine.grad_plan([k for k in self.params if k not in self.frozen]) if self.frozen else None
+        # Adam over the runs of trainable tensors (a run spans the alignment padding between adjacent views)
+        keys, n = list(self.pbucket.offsets), self.pbucket.flat.numel()
+        ends = [self.pbucket.offsets[k][0] for k in keys[1:]] + [n]
+        runs = []
+        for k, hi in zip(keys, ends):
+            if k in self.frozen:
+                continue
+            lo = self.pbucket.offsets[k][0]
+            if runs and runs[-1][1] == lo:
+                runs[-1][1] = hi
+            else:
+                runs.append([lo, hi])
+        self._adam_runs = [tuple(r) for r in runs]
+        self.conv_frozen = all(k in self.frozen for k in self.params if k.startswith("convnet."))
 
     def broadcast_state(self, src=0):
         """Rank `src`'s parameters, BatchNorm buffers, Adam moments and step count to every rank: replicas start (and
@@ -219,7 +259,7 @@ class HotPathTrainer:
         # _stat_sync has from its all-reduce -- every rank raises together instead of one rank leaving the others
         # blocked in a collective.
         engine.check_batch(self.cfg, batch["images"], batch["bboxes"], batch["additional_feats"],
-                           batch["context_indices"], not self.sync_bn)
+                           batch["context_indices"], self.modes if not self.sync_bn else False)
         self.step_count += 1
         base = (self.dropout_seed * 0x9E3779B1 + 2 * self.step_count) & 0xFFFFFFFFFFFF
         if self.sync_bn:
@@ -227,12 +267,13 @@ class HotPathTrainer:
         try:
             logits, sv = engine.model_fwd(self.cfg, self.params, self.buffers, batch["images"],
                                           batch["bboxes"], batch["additional_feats"],
-                                          batch["context_indices"], True, (base, base + 1), masks)
+                                          batch["context_indices"], self.modes, (base, base + 1), masks,
+                                          plan=self.plan)
             loss, dl, pred = engine.ce_sum(logits, batch["labels"])
             self._head_work = None
             overlap = self.world_size > 1 and engine.OPTIONS.overlap_allreduce
             engine.model_bwd(sv, dl, self.params, self.grads,
-                             after_head=self._reduce_head if overlap else None)
+                             after_head=self._reduce_head if overlap else None, plan=self.plan)
         finally:
             engine.STAT_SYNC = None
         return loss, pred
@@ -275,18 +316,29 @@ class HotPathTrainer:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(st)
             if getattr(self, "_head_work", None) is not None:
-                self.gbucket.all_reduce_range(0, self._head_offset(), self.group)
+                if not self.conv_frozen:            # (a frozen conv stack has no gradients to exchange)
+                    self.gbucket.all_reduce_range(0, self._head_offset(), self.group)
                 self._head_work.wait()
                 self._head_work = None
+            elif self.conv_frozen:
+                lo = self._head_offset()
+                if lo < self.gbucket.flat.numel():
+                    self.gbucket.all_reduce_range(lo, self.gbucket.flat.numel(), self.group)
             else:
                 self.gbucket.all_reduce_sum(self.group)
             if timing:
                 e1.record(st)
                 self._ar_events.append((e0, e1))
         b1, b2 = self.hp["betas"]
-        engine.call("cova_adam_step", self.pbucket.flat, self.gbucket.flat, self.exp_avg,
-                    self.exp_avg_sq, self.pbucket.flat.numel(), self.step_count, self.hp["lr"], b1, b2,
-                    self.hp["eps"], self.hp["weight_decay"])
+        if not self.frozen:
+            engine.call("cova_adam_step", self.pbucket.flat, self.gbucket.flat, self.exp_avg,
+                        self.exp_avg_sq, self.pbucket.flat.numel(), self.step_count, self.hp["lr"], b1, b2,
+                        self.hp["eps"], self.hp["weight_decay"])
+            return
+        for lo, hi in self._adam_runs:          # frozen tensors: parameters and moments untouched
+            engine.call("cova_adam_step", self.pbucket.flat[lo:hi], self.gbucket.flat[lo:hi], self.exp_avg[lo:hi],
+                        self.exp_avg_sq[lo:hi], hi - lo, self.step_count, self.hp["lr"], b1, b2,
+                        self.hp["eps"], self.hp["weight_decay"])
 
     def train_step(self, batch, masks=None):
         """optimizer.zero_grad(); forward; loss; backward; optimizer.step()  (train.py:45-60).

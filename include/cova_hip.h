@@ -125,6 +125,8 @@ int cova_conv3x3_wgrad4_partial(const float *act, const float *act_abc /*nullabl
                                 const float *dz2 /*nullable*/, const float *dz_abc /*nullable*/,
                                 float *dz_out /*nullable: also writes A*dz + B*dz2 + C, NHWC [B,H,W,64]*/, float *ws, int B,
                                 int H, int W, void *stream);
+/* finish: every (ws_i, dw_i) pair is nullable as a pair -- a (NULL, NULL) slot is skipped (a frozen weight whose partial
+ * launch was not issued); the given pairs are folded exactly as when all four are present; all four NULL issues no launch. */
 int cova_conv3x3_wgrad4_finish(const float *ws0, float *dw0, const float *ws1, float *dw1, const float *ws2,
                                float *dw2, const float *ws3, float *dw3, int B, int H, int W, void *stream);
 int cova_conv3x3_wgrad4(const float *act, const float *dz, float *dw /*OIHW*/, float *ws, int B, int H, int W,
