@@ -51,13 +51,16 @@ def collapse_modes(modes):
 #   "conv1_wgrad" the 7x7 conv1 weight gradient (cova_conv1_wgrad*)
 #   "wgrad:K"     the weight gradient of layer1 convolution K (a state_dict key; the 3x3 ones and the resnet50 conv1 1x1s)
 #   "bbox"        the positional encoder's backward; "addl" the additional-feature BatchNorm's backward
-PLAN_STAGES = ("convstack", "stem", "conv1_wgrad", "bbox", "addl")
+# with the optional layer2 stage (``layer2=True``, backbone_layers=2) also:
+#   "layer1"      layer2 block 0's data gradients into layer1's output (3x3 s2 and 1x1 s2, one launch) and everything of
+#                 layer1 and below; "wgrad:convnet.5.K" the weight gradient of layer2 convolution K
+PLAN_STAGES = ("convstack", "stem", "conv1_wgrad", "bbox", "addl", "layer1")
 
 
-def grad_plan(need, want_dimg=False):
+def grad_plan(need, want_dimg=False, layer2=False):
     """(state_dict keys of the parameters that need a gradient, images need one?) -> frozenset of the backward stages to
     issue.  A stage is left out only when nothing downstream of it is wanted; every other pattern computes more than it
-    needs (the caller drops the gradients of frozen parameters)."""
+    needs (the caller drops the gradients of frozen parameters).  ``layer2``: the model has the layer2 stage."""
     need = set(need)
     plan = set()
     if any(k.startswith("bbox_feat_encoder.") for k in need):
@@ -71,12 +74,22 @@ def grad_plan(need, want_dimg=False):
         if "convnet.0.weight" in need:
             plan.add("conv1_wgrad")
         plan.update("wgrad:" + k for k in need if k.startswith("convnet.4.") and ".conv" in k)
+        if layer2:
+            if want_dimg or any(k.startswith(("convnet.0.", "convnet.1.", "convnet.4.")) for k in need):
+                plan.add("layer1")
+            plan.update("wgrad:" + k for k in need if k.startswith("convnet.5.") and k.endswith(("conv1.weight",
+                                                                                              "conv2.weight",
+                                                                                              "downsample.0.weight")))
     return frozenset(plan)
+
+
+def has_layer2(params):
+    return "convnet.5.0.conv1.weight" in params
 
 
 def full_plan(params):
     """The plan of a step in which every parameter of ``params`` needs its gradient (no stage left out)."""
-    return grad_plan(list(params))
+    return grad_plan(list(params), layer2=has_layer2(params))
 
 
 def on_device_of(argpos):
@@ -155,12 +168,14 @@ def check_batch(cfg, images, bboxes, additional_feats, context_indices, training
 def backbone_feat(cfg):
     PH, PW = cfg["roi_output_size"]
     from .weights import backbone_channels
-    return backbone_channels(cfg.get("backbone", "resnet18")) * PH * PW
+    return backbone_channels(cfg.get("backbone", "resnet18"), cfg.get("backbone_layers", 1)) * PH * PW
 
 
-def feature_map_size(n):
-    """conv1 (7,2,3) then maxpool (3,2,1): models.py:53-56 does this with a dummy forward."""
-    return query("cova_conv_out_size", query("cova_conv_out_size", n, 7, 2, 3), 3, 2, 1)
+def feature_map_size(n, backbone_layers=1):
+    """conv1 (7,2,3) then maxpool (3,2,1): models.py:53-56 does this with a dummy forward; layer2's first conv (3,2,1)
+    halves it once more."""
+    n = query("cova_conv_out_size", query("cova_conv_out_size", n, 7, 2, 3), 3, 2, 1)
+    return query("cova_conv_out_size", n, 3, 2, 1) if backbone_layers == 2 else n
 
 
 # ------------------------------------------------------------------------------- BatchNorm
@@ -407,6 +422,8 @@ def convstack_fwd(images, params, buffers, training, save=True, lazy_out=False):
     H1, W1 = query("cova_conv_out_size", H, 7, 2, 3), query("cova_conv_out_size", W, 7, 2, 3)
     H2, W2 = query("cova_conv_out_size", H1, 3, 2, 1), query("cova_conv_out_size", W1, 3, 2, 1)
     bottleneck = is_bottleneck(params)
+    layer2 = has_layer2(params)
+    lazy_out = lazy_out and not layer2              # layer2 reads layer1's output: materialised
     sv = {"images": images, "dims": (B, H, W, H1, W1, H2, W2), "kind": "bottleneck" if bottleneck else "basic"}
     # the Winograd images of the 3x3 weights: one small launch
     if bottleneck:
@@ -436,6 +453,8 @@ def convstack_fwd(images, params, buffers, training, save=True, lazy_out=False):
         feat = _layer1_bottleneck_fwd(p1, params, buffers, training, save, lazy_out, sv)
     else:
         feat = _layer1_basic_fwd(p1, params, buffers, training, save, lazy_out, sv)
+    if layer2:
+        feat = _layer2_fwd(feat, params, buffers, training, save, sv)
     return feat, (sv if save else None)
 
 
@@ -909,6 +928,119 @@ def _layer1_bwd_fused(sv, dfeat, gout, grads, head_part=None, plan=None):
     return dA
 
 
+# ---- optional layer2 stage (backbone_layers=2: torchvision resnet18 children()[:-4]): two BasicBlocks 64 -> 128 channels,
+# block 0 at stride 2 with the 1x1 stride-2 downsample.  Convolutions: the channel-generic NHWC kernels of
+# csrc/conv_nhwc.hip; BatchNorm: the channel-generic statistics / finalize / apply kernels (cova_colstats,
+# cova_bn_finalize_*, cova_bn_act(2)_fwd, cova_bn_bwd_reduce / _apply), so SyncBN exchanges their rows like any other.
+C128 = 2 * C64
+L2 = "convnet.5."
+# (state_dict key, Ci, k, stride, pad) of the five convolutions, in forward order
+L2_CONVS = [(L2 + "0.conv1", C64, 3, 2, 1), (L2 + "0.conv2", C128, 3, 1, 1), (L2 + "0.downsample.0", C64, 1, 2, 0),
+            (L2 + "1.conv1", C128, 3, 1, 1), (L2 + "1.conv2", C128, 3, 1, 1)]
+
+
+def conv_nhwc_prep(w, fwd=True, dgrad=True):
+    """OIHW weight -> (forward operand, data-gradient operand) of the NHWC kernels (either None when not asked for)."""
+    co, ci, k, _ = w.shape
+    wf = _empty((k * k * ci, co), w) if fwd else None
+    wd = _empty((k * k * co, ci), w) if dgrad else None
+    call("cova_conv_nhwc_prep", w, wf, wd, co, ci, k)
+    return wf, wd
+
+
+def _layer2_fwd(x, params, buffers, training, save, sv):
+    """layer1's output x [B,H2,W2,64] -> layer2's output [B,H3,W3,128]; sv["layer2"] keeps what _layer2_bwd needs."""
+    B, H2, W2, _ = x.shape
+    H3, W3 = query("cova_conv_out_size", H2, 3, 2, 1), query("cova_conv_out_size", W2, 3, 2, 1)
+    R = B * H3 * W3
+    ops = {key: conv_nhwc_prep(params[key + ".weight"], dgrad=save) for key, *_ in L2_CONVS}
+    geo = {key: rest for key, *rest in L2_CONVS}
+
+    def conv(inp, key):
+        ci, k, s, p = geo[key]
+        out = _empty((B, H3, W3, C128), x)
+        call("cova_conv_nhwc_fwd", inp, ops[key][0], out, B, inp.shape[1], inp.shape[2], ci, C128, k, s, p)
+        return out
+
+    def bn(z, prefix):
+        if is_train(training, prefix):
+            part, n = colstats(z, C128, R, C128)
+            return bn_params(prefix, params, buffers, C128, z, training, part, n, R, unit="pages")
+        return bn_params(prefix, params, buffers, C128, z, training)
+
+    z1 = conv(x, L2 + "0.conv1")
+    s1 = bn(z1, L2 + "0.bn1.")
+    a1 = bn_act(z1, s1)
+    z2 = conv(a1, L2 + "0.conv2")
+    s2 = bn(z2, L2 + "0.bn2.")
+    zd = conv(x, L2 + "0.downsample.0")
+    sd = bn(zd, L2 + "0.downsample.1.")
+    out0 = _empty((B, H3, W3, C128), x)
+    call("cova_bn_act2_fwd", z2, s2.scale, s2.shift, zd, sd.scale, sd.shift, out0, R, C128, 1)
+    z3 = conv(out0, L2 + "1.conv1")
+    s3 = bn(z3, L2 + "1.bn1.")
+    a3 = bn_act(z3, s3)
+    z4 = conv(a3, L2 + "1.conv2")
+    s4 = bn(z4, L2 + "1.bn2.")
+    out1 = bn_act(z4, s4, res=out0)
+    if save:
+        sv["layer2"] = dict(dims=(B, H2, W2, H3, W3), wd={k: v[1] for k, v in ops.items()}, x=x, z1=z1, s1=s1, a1=a1,
+                            z2=z2, s2=s2, zd=zd, sd=sd, out0=out0, z3=z3, s3=s3, a3=a3, z4=z4, s4=s4, out1=out1)
+    return out1
+
+
+def _layer2_bwd(s, g, gout, grads, plan=None):
+    """g = dL/d(layer2's output), not yet ReLU-masked -> dL/d(layer1's output) (None when the plan has no "layer1"
+    stage: block 0's two data gradients are then not launched).  Weight gradients only for the plan's "wgrad:" keys."""
+    B, H2, W2, H3, W3 = s["dims"]
+    R = B * H3 * W3
+    geo = {key: rest for key, *rest in L2_CONVS}
+
+    def wgrad(inp, dz, key):
+        if plan is not None and "wgrad:%s.weight" % key not in plan:
+            return
+        ci, k, st, p = geo[key]
+        dw = _gbuf(gout, key + ".weight", (C128, ci, k, k), g)
+        ws = _empty((query("cova_conv_nhwc_wgrad_workspace_floats", B, H3, W3, ci, C128, k),), g)
+        call("cova_conv_nhwc_wgrad", inp, dz, dw, ws, B, inp.shape[1], inp.shape[2], ci, C128, k, st, p)
+        grads[key + ".weight"] = dw
+
+    def dgrad(dz, key, addend=None):
+        dx = torch.empty_like(dz)
+        call("cova_conv_nhwc_dgrad", dz, s["wd"][key], None, None, addend, dx, B, H3, W3, C128, C128, 3, 1, 1)
+        return dx
+
+    def bnb(dout, act, z, st, prefix, dres=None):
+        dz = torch.empty_like(z)
+        dg, db = bn_backward(dout, C128, act, C128, z, C128, st, R, dz, C128, dres, C128 if dres is not None else 0,
+                             gout, prefix, unit="pages")
+        grads[prefix + "weight"], grads[prefix + "bias"] = dg, db
+        return dz
+
+    # block 1: out1 = relu(bn2(z4) + out0), z4 = conv2(a3), a3 = relu(bn1(z3)), z3 = conv1(out0)
+    gres = torch.empty_like(g)
+    dz4 = bnb(g, s["out1"], s["z4"], s["s4"], L2 + "1.bn2.", dres=gres)
+    wgrad(s["a3"], dz4, L2 + "1.conv2")
+    dz3 = bnb(dgrad(dz4, L2 + "1.conv2"), s["a3"], s["z3"], s["s3"], L2 + "1.bn1.")
+    wgrad(s["out0"], dz3, L2 + "1.conv1")
+    dout0 = dgrad(dz3, L2 + "1.conv1", addend=gres)
+    # block 0: out0 = relu(bn2(z2) + bnd(zd)), z2 = conv2(a1), a1 = relu(bn1(z1)), z1 = conv1(x), zd = downsample(x)
+    gres0 = torch.empty_like(g)
+    dz2 = bnb(dout0, s["out0"], s["z2"], s["s2"], L2 + "0.bn2.", dres=gres0)
+    dzd = bnb(gres0, None, s["zd"], s["sd"], L2 + "0.downsample.1.")
+    wgrad(s["a1"], dz2, L2 + "0.conv2")
+    wgrad(s["x"], dzd, L2 + "0.downsample.0")
+    dz1 = bnb(dgrad(dz2, L2 + "0.conv2"), s["a1"], s["z1"], s["s1"], L2 + "0.bn1.")
+    wgrad(s["x"], dz1, L2 + "0.conv1")
+    if plan is not None and "layer1" not in plan:
+        return None
+    # both stride-2 data gradients land on layer1's output: one launch, the downsample's as one more tap
+    dx = torch.empty_like(s["x"])
+    call("cova_conv_nhwc_dgrad", dz1, s["wd"][L2 + "0.conv1"], dzd, s["wd"][L2 + "0.downsample.0"], None, dx,
+         B, H2, W2, C64, C128, 3, 2, 1)
+    return dx
+
+
 def masked_grad_and_sums(dout, last, R):
     """Stand-alone form of what cova_roipool_bwd_bn fuses: g = dout * (out > 0) and the partial rows of
     (sum g, sum g*xhat(z)) for the BatchNorm in front of the feature map."""
@@ -945,7 +1077,12 @@ def convstack_bwd(sv, dfeat, gout=None, head_part=None, params=None, want_dimg=F
     R = B * H2 * W2
     grads = {}
     if plan is not None and want_dimg:
-        plan = plan | {"stem"}
+        plan = plan | {"stem", "layer1"}
+    if sv.get("layer2") is not None:
+        dfeat = _layer2_bwd(sv["layer2"], dfeat, gout, grads, plan)
+        if dfeat is None:               # the plan ends at layer2 (layer1 and the stem frozen, no image gradient)
+            return grads
+        head_part = None
     if sv["kind"] == "bottleneck":
         if head_part is None:          # piecewise API (_get_visual_features): mask + sums stand-alone
             dfeat, head_part = masked_grad_and_sums(dfeat, sv["last"], R)
@@ -1329,7 +1466,7 @@ def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_in
     ``plan`` (grad_plan, with ``save``): without its "convstack" stage the conv stack keeps no activations."""
     N = bboxes.shape[0]
     PH, PW = cfg["roi_output_size"]
-    n_vis = (C256 if is_bottleneck(params) else C64) * PH * PW
+    n_vis = (C256 if is_bottleneck(params) else C128 if has_layer2(params) else C64) * PH * PW
     Hd, A = cfg["bbox_hidden_dim"], cfg["n_additional_feat"]
     F = n_vis + Hd + A
     D = cfg["hidden_dim"] if cfg["use_context"] else 0
@@ -1369,7 +1506,7 @@ def model_bwd(sv, dlogits, params, gout=None, after_head=None, want_dimg=False, 
     ``plan`` (grad_plan; None = every gradient): the backward stages it leaves out are not launched and their gradients
     are absent from the result (the forward must have had the same plan)."""
     if plan is not None and want_dimg:
-        plan = plan | {"convstack", "stem"}
+        plan = plan | {"convstack", "stem", "layer1"}
     N, F, D, T, n_vis, Hd, A = (sv[k] for k in ("N", "F", "D", "T", "n_vis", "Hd", "A"))
     dcomb, grads = decoder_bwd(sv["dec"], dlogits, params, gout)
     if D > 0:

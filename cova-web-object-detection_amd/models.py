@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import engine
-from .weights import backbone_channels
+from .weights import backbone_channels, check_backbone_layers
 
 GAT_MAX_K = engine.GAT_MAX_K
 
@@ -30,15 +30,20 @@ _FIELDS = ("roi_output_size", "n_classes", "use_context", "hidden_dim", "bbox_hi
 
 
 class _ParamBlock(nn.Module):
-    """BasicBlock-shaped parameter holder: conv1, bn1, relu, conv2, bn2 (torchvision naming)."""
+    """BasicBlock-shaped parameter holder: conv1, bn1, relu, conv2, bn2 (torchvision naming); with ``cin != c`` (layer2's
+    block 0) conv1 has stride 2 and a downsample = Sequential(conv 1x1 stride 2, bn) follows."""
 
-    def __init__(self, c):
+    def __init__(self, c, cin=None):
         super().__init__()
-        self.conv1 = nn.Conv2d(c, c, 3, 1, 1, bias=False)
+        cin = c if cin is None else cin
+        stride = 1 if cin == c else 2
+        self.conv1 = nn.Conv2d(cin, c, 3, stride, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(c)
         self.relu = nn.ReLU(inplace=True)
         self.conv2 = nn.Conv2d(c, c, 3, 1, 1, bias=False)
         self.bn2 = nn.BatchNorm2d(c)
+        if cin != c:
+            self.downsample = nn.Sequential(nn.Conv2d(cin, c, 1, stride, bias=False), nn.BatchNorm2d(c))
 
     def forward(self, x):
         raise RuntimeError("parameter container only; the conv stack runs in libcova_hip.so")
@@ -123,7 +128,7 @@ def _plan(keys, values, want_dimg):
     need = [k for k, v in zip(keys, values) if v.requires_grad]
     if not need and not want_dimg:
         return None
-    return engine.grad_plan(need, want_dimg)
+    return engine.grad_plan(need, want_dimg, layer2=any(k.startswith("convnet.5.") for k in keys))
 
 
 def _only_wanted(ctx, first, keys, grads):
@@ -344,7 +349,7 @@ class CoVA(nn.Module):
     def __init__(self, roi_output_size, img_H, n_classes, use_context=True, hidden_dim=384,
                  bbox_hidden_dim=32, n_additional_feat=0, drop_prob=0.2, class_names=None,
                  backbone="resnet18", n_heads=1, n_gat_layers=1, backbone_state_dict=None, roi_op="pool",
-                 sampling_ratio=2, roi_aligned=False):
+                 sampling_ratio=2, roi_aligned=False, backbone_layers=1):
         """The first nine arguments exactly as the reference's CoVA (models.py:10-34; called positionally
         at main.py:122-132).  Keyword-only-in-practice extensions, whose defaults are the reference's
         model: ``backbone`` 'resnet18' | 'resnet50' (torchvision ``children()[:-5]`` of either),
@@ -353,7 +358,10 @@ class CoVA(nn.Module):
         the offline stand-in for the reference's ``pretrained=True`` download (models.py:49).
         ``roi_op='align'`` swaps RoIPool (the reference's operator and the parity path) for torchvision's RoIAlign
         (``sampling_ratio``, ``roi_aligned`` as in ``torchvision.ops.RoIAlign``).
-        ``img_H`` is only used for the RoIPool scale (models.py:53-56): pages may be any H x W."""
+        ``img_H`` is only used for the RoIPool scale (models.py:53-56): pages may be any H x W.
+        ``backbone_layers=2`` (resnet18 only) keeps torchvision's ``layer2`` after layer1 (``children()[:-4]``): 128
+        channels at stride 8, parameters under ``convnet.5.``."""
+        check_backbone_layers(backbone, backbone_layers)
         if roi_op not in ("pool", "align"):
             raise ValueError("roi_op must be 'pool' (the reference, models.py:58) or 'align'")
         super(CoVA, self).__init__()
@@ -371,23 +379,26 @@ class CoVA(nn.Module):
         # state_dict is supplied (the explicit backbone_state_dict= argument: a dict or a path; no hidden
         # environment state) or a reference checkpoint is loaded afterwards with load_state_dict.
         c = engine.C64
-        c_out = backbone_channels(backbone)
+        c_out = backbone_channels(backbone, backbone_layers)
         conv1 = nn.Conv2d(3, c, 7, 2, 3, bias=False)
         if backbone == "resnet18":
             layer1 = nn.Sequential(_ParamBlock(c), _ParamBlock(c))
         else:
             layer1 = nn.Sequential(_ParamBottleneck(c, c, True), _ParamBottleneck(c_out, c, False),
                                    _ParamBottleneck(c_out, c, False))
-        self.backbone = backbone
+        self.backbone, self.backbone_layers = backbone, backbone_layers
+        stages = [layer1]
+        if backbone_layers == 2:
+            stages.append(nn.Sequential(_ParamBlock(c_out, c), _ParamBlock(c_out)))
         self.convnet = nn.Sequential(conv1, nn.BatchNorm2d(c), nn.ReLU(inplace=True),
-                                     nn.MaxPool2d(3, 2, 1), layer1)
+                                     nn.MaxPool2d(3, 2, 1), *stages)
         for m in self.convnet.modules():
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
         self._init_backbone(backbone_state_dict)
         c = c_out
         # models.py:53-56 reads the output size off a dummy forward; it is a closed form
-        feat_h = engine.feature_map_size(img_H)
+        feat_h = engine.feature_map_size(img_H, backbone_layers)
         self.roi_pool = _RoIPoolSpec(roi_output_size, feat_h / img_H)
         self.n_visual_feat = c * roi_output_size[0] * roi_output_size[1]
         self.n_feat = self.n_visual_feat + self.bbox_hidden_dim + self.n_additional_feat
@@ -417,7 +428,8 @@ class CoVA(nn.Module):
                          n_additional_feat=n_additional_feat, drop_prob=float(drop_prob),
                          spatial_scale=self.roi_pool.spatial_scale, backbone=backbone,
                          n_heads=n_heads, n_gat_layers=n_gat_layers, roi_op=roi_op,
-                         sampling_ratio=int(sampling_ratio), roi_aligned=bool(roi_aligned))
+                         sampling_ratio=int(sampling_ratio), roi_aligned=bool(roi_aligned),
+                         backbone_layers=backbone_layers)
         self._param_keys = [k for k, _ in self.named_parameters()]
         self._conv_keys = [k for k in self._param_keys if k.startswith("convnet.")]
         self._bbox_keys = [k for k in self._param_keys if k.startswith("bbox_feat_encoder.")]
@@ -444,7 +456,8 @@ class CoVA(nn.Module):
             sd = source
         mapped = {}
         for k, v in sd.items():
-            for src, dst in (("conv1.", "0."), ("bn1.", "1."), ("layer1.", "4.")):
+            for src, dst in (("conv1.", "0."), ("bn1.", "1."), ("layer1.", "4."), ("layer2.", "5."))[:3 + (
+                    self.backbone_layers == 2)]:
                 if k.startswith(src):
                     mapped[dst + k[len(src):]] = v
         missing = self.convnet.load_state_dict(mapped, strict=True)

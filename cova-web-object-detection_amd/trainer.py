@@ -101,7 +101,8 @@ class HotPathTrainer:
         self.device = torch.device(device)
         spec = state_dict_spec(**{k: cfg[k] for k in ("roi_output_size", "n_classes", "use_context",
                                                      "hidden_dim", "bbox_hidden_dim", "n_additional_feat",
-                                                     "backbone", "n_heads", "n_gat_layers") if k in cfg})
+                                                     "backbone", "n_heads", "n_gat_layers", "backbone_layers")
+                                  if k in cfg})
         pshapes = OrderedDict((k, s) for k, s in spec if is_param_key(k))
         self.pbucket = FlatBucket(pshapes, self.device)
         self.gbucket = FlatBucket(pshapes, self.device)
@@ -137,7 +138,8 @@ class HotPathTrainer:
         eval_bns = [p for p in eval_bns if _named_by(p, bn_eval)]
         # (no entry: the bool of today's steps, exactly its launches)
         self.modes = {p: False for p in eval_bns} if eval_bns else True
-        self.plan = engine.grad_plan([k for k in self.params if k not in self.frozen]) if self.frozen else None
+        self.plan = (engine.grad_plan([k for k in self.params if k not in self.frozen],
+                                      layer2=engine.has_layer2(self.params)) if self.frozen else None)
         # Adam over the runs of trainable tensors (a run spans the alignment padding between adjacent views)
         keys, n = list(self.pbucket.offsets), self.pbucket.flat.numel()
         ends = [self.pbucket.offsets[k][0] for k in keys[1:]] + [n]

@@ -26,10 +26,20 @@ def _bn_entries(prefix, c):
     ]
 
 
-def backbone_channels(backbone="resnet18"):
-    """Channels of the truncated ResNet's output: layer1 of ResNet-18 keeps 64, of ResNet-50 expands to 256."""
+def check_backbone_layers(backbone="resnet18", backbone_layers=1):
+    """1 = conv1..layer1 (the reference's children()[:-5]); 2 = also ResNet-18's layer2 (children()[:-4])."""
+    if backbone_layers not in (1, 2) or isinstance(backbone_layers, bool):
+        raise ValueError("backbone_layers must be 1 (the reference, models.py:49-51) or 2 (resnet18 layer2 kept)")
+    if backbone_layers == 2 and backbone != "resnet18":
+        raise ValueError("backbone_layers=2 is built for backbone='resnet18' only")
+
+
+def backbone_channels(backbone="resnet18", backbone_layers=1):
+    """Channels of the truncated ResNet's output: layer1 of ResNet-18 keeps 64, of ResNet-50 expands to 256; ResNet-18's
+    layer2 has 128."""
     if backbone == "resnet18":
-        return BACKBONE_CHANNELS
+        check_backbone_layers(backbone, backbone_layers)
+        return 2 * BACKBONE_CHANNELS if backbone_layers == 2 else BACKBONE_CHANNELS
     if backbone == "resnet50":
         return 4 * BACKBONE_CHANNELS
     raise ValueError("backbone must be 'resnet18' (the reference, models.py:49) or 'resnet50' (extension)")
@@ -46,14 +56,17 @@ def gat_prefixes(n_heads=1, n_gat_layers=1):
 
 def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=384,
                     bbox_hidden_dim=32, n_additional_feat=0, backbone="resnet18", n_heads=1,
-                    n_gat_layers=1):
+                    n_gat_layers=1, backbone_layers=1):
     """Ordered (key, shape) list, identical to ``reference CoVA(...).state_dict()`` for the defaults.
 
     Extensions (BASELINE.json configs[2], configs[4]; absent from the reference, defaults keep its
     behaviour): ``backbone="resnet50"`` = torchvision resnet50 ``children()[:-5]`` (3 Bottleneck
     blocks, 256 output channels, torchvision's key names); ``n_heads`` / ``n_gat_layers`` = several
     GraphAttentionLayer heads of hidden_dim/n_heads channels each, concatenated, stacked n_gat_layers
-    times (layer 0 reads the n_feat own features, later layers the previous layer's hidden_dim)."""
+    times (layer 0 reads the n_feat own features, later layers the previous layer's hidden_dim);
+    ``backbone_layers=2`` = resnet18 ``children()[:-4]``: layer2 (two BasicBlocks, 64 -> 128 channels at stride 2, block 0
+    with the 1x1 downsample) under ``convnet.5.`` with torchvision's key names."""
+    check_backbone_layers(backbone, backbone_layers)
     c = BACKBONE_CHANNELS
     spec = [("convnet.0.weight", (c, 3, 7, 7))]
     spec += _bn_entries("convnet.1.", c)
@@ -78,7 +91,18 @@ def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidde
             if blk == 0:
                 spec.append((p + "downsample.0.weight", (cout, c, 1, 1)))
                 spec += _bn_entries(p + "downsample.1.", cout)
-    n_visual = backbone_channels(backbone) * roi_output_size[0] * roi_output_size[1]
+    if backbone_layers == 2:
+        c2 = 2 * c
+        for blk in (0, 1):
+            p = "convnet.5.%d." % blk
+            spec.append((p + "conv1.weight", (c2, c if blk == 0 else c2, 3, 3)))
+            spec += _bn_entries(p + "bn1.", c2)
+            spec.append((p + "conv2.weight", (c2, c2, 3, 3)))
+            spec += _bn_entries(p + "bn2.", c2)
+            if blk == 0:
+                spec.append((p + "downsample.0.weight", (c2, c, 1, 1)))
+                spec += _bn_entries(p + "downsample.1.", c2)
+    n_visual = backbone_channels(backbone, backbone_layers) * roi_output_size[0] * roi_output_size[1]
     n_feat = n_visual + bbox_hidden_dim + n_additional_feat
     if bbox_hidden_dim > 0:
         spec += [("bbox_feat_encoder.0.weight", (bbox_hidden_dim, 5)),

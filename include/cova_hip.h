@@ -241,6 +241,26 @@ int cova_conv1x1_lin_dgrad(const float *v, const float *avec, const float *w, co
                            const float *mask_shift, const float *z, const float *mean, const float *invstd,
                            float *out, float *stat_part, long long R, void *stream);
 
+/* ---- optional layer2 stage (CoVA(backbone_layers=2): torchvision resnet18 children()[:-4], one stage more than
+ * models.py:49-51 keeps): channel-generic NHWC convolutions, csrc/conv_nhwc.hip.  k in {1, 3}, stride in {1, 2},
+ * pad < k, Ci and Co multiples of 64 (weight gradient: Co a multiple of 128); input [B,H,W,Ci], output
+ * [B,Ho,Wo,Co] with Ho = (H + 2 pad - k) / stride + 1.  f32 MFMA (exact f32 products), no float atomics. */
+/* OIHW [Co,Ci,k,k] -> forward operand [k*k*Ci][Co] and data-gradient operand [k*k*Co][Ci] (either nullable) */
+int cova_conv_nhwc_prep(const float *w_oihw, float *w_fwd, float *w_dgrad, int Co, int Ci, int k, void *stream);
+int cova_conv_nhwc_fwd(const float *in, const float *w_fwd, float *out, int B, int H, int W, int Ci, int Co, int k,
+                       int stride, int pad, void *stream);
+/* dx [B,H,W,Ci] = data gradient of the (k, stride, pad) convolution for dy [B,Ho,Wo,Co] (+ that of a 1x1 pad-0
+ * convolution of the same stride for dy2, nullable with w2_dgrad) (+ addend [B,H,W,Ci], nullable).  Every element of dx
+ * is written, positions no output reads included (zeros). */
+int cova_conv_nhwc_dgrad(const float *dy, const float *w_dgrad, const float *dy2, const float *w2_dgrad,
+                         const float *addend, float *dx, int B, int H, int W, int Ci, int Co, int k, int stride, int pad,
+                         void *stream);
+/* dw OIHW = sum over pixels of in (x) dy: per-block partial sums in ws, folded in a fixed order by a second launch */
+int cova_conv_nhwc_wgrad_num_partials(int B, int Ho, int Wo, int Ci, int Co, int k);
+int cova_conv_nhwc_wgrad_workspace_floats(int B, int Ho, int Wo, int Ci, int Co, int k);
+int cova_conv_nhwc_wgrad(const float *in, const float *dy, float *dw, float *ws, int B, int H, int W, int Ci, int Co,
+                         int k, int stride, int pad, void *stream);
+
 /* ------------------------------------------------------------------ BatchNorm / ReLU / MaxPool
  * replaces: nn.BatchNorm2d / nn.BatchNorm1d (train: batch statistics + running-stat update with
  * momentum, unbiased running_var; eval: running statistics), nn.ReLU, the BasicBlock residual
