@@ -62,6 +62,37 @@ def _named_by(name, entries):
     return any(name.startswith(e) or e.startswith(name) for e in entries)
 
 
+OPTIMIZERS = ("adam", "adamw", "sgd")           # index = the algorithm code of cova_optim_step
+_GROUP_HP = ("lr", "weight_decay", "betas", "eps", "momentum", "dampening", "nesterov")
+_ADAM_HP = ("lr", "weight_decay", "betas", "eps")                      # the "hp" of an optimizer_state_dict
+
+
+def _entries(spec):
+    return (spec,) if isinstance(spec, str) else tuple(spec)
+
+
+def _check_sgd_group(algorithm, hp):
+    if algorithm == "sgd" and hp["nesterov"] and (hp["momentum"] <= 0 or hp["dampening"] != 0):
+        raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+
+
+def group_runs(offsets, n, frozen, owner):
+    """Merged runs [lo, hi, group] of the flat buffer: adjacent trainable tensors of one group form one run (a run spans
+    the alignment padding behind each of its views); frozen keys (``owner`` has none) split runs and are left out."""
+    keys = list(offsets)
+    ends = [offsets[k][0] for k in keys[1:]] + [n]
+    runs = []
+    for k, hi in zip(keys, ends):
+        if k in frozen:
+            continue
+        lo, gid = offsets[k][0], owner[k]
+        if runs and runs[-1][1] == lo and runs[-1][2] == gid:
+            runs[-1][1] = hi
+        else:
+            runs.append([lo, hi, gid])
+    return [tuple(r) for r in runs]
+
+
 def shard_pages(n_pages, rank, world_size):
     """Contiguous page range [lo, hi) of this rank (whole pages only)."""
     base, rem = divmod(n_pages, world_size)
@@ -93,10 +124,24 @@ class HotPathTrainer:
     leaves out every backward stage that only they need) and are not touched by Adam (no update, no weight decay, moments
     unchanged: torch.optim.Adam's treatment of a parameter whose grad is None).  ``bn_eval`` (keys or prefixes of
     BatchNorm layers) normalise with their running statistics, leave their buffers alone and take no part in the SyncBN
-    exchange.  Flat buffers, state_dict() and optimizer_state_dict() keep their layout either way."""
+    exchange.  Flat buffers, state_dict() and optimizer_state_dict() keep their layout either way.
+
+    Optimizer ("Optimizer options"): ``optimizer`` "adam" (torch.optim.Adam, L2 added to the gradient),
+    "adamw" or "sgd" (with ``momentum``, ``dampening``, ``nesterov``); ``param_groups`` [{"params": key or key prefixes,
+    overrides of lr / weight_decay / betas / eps / momentum / dampening / nesterov}, ...] (unclaimed trainable keys go to a
+    default group of the constructor's values, appended last); ``max_grad_norm`` clips as
+    torch.nn.utils.clip_grad_norm_(params, max_grad_norm) over the trainable parameters.  These run as one cova_optim_step
+    launch (plus cova_grad_norm's two launches when clipping) with no host synchronisation.  With none of them set, the
+    step is today's cova_adam_step."""
 
     def __init__(self, cfg, state_dict, device, lr=5e-4, weight_decay=1e-3, betas=(0.9, 0.999),
-                 eps=1e-8, world_size=1, process_group=None, dropout_seed=123, sync_bn=False, frozen=(), bn_eval=()):
+                 eps=1e-8, world_size=1, process_group=None, dropout_seed=123, sync_bn=False, frozen=(), bn_eval=(),
+                 optimizer="adam", momentum=0.0, dampening=0.0, nesterov=False, param_groups=None,
+                 max_grad_norm=None, norm_type=2.0):
+        if optimizer not in OPTIMIZERS:
+            raise ValueError("optimizer must be one of %s, got %r" % (OPTIMIZERS, optimizer))
+        if float(norm_type) != 2.0:
+            raise ValueError("norm_type must be 2.0 (the only gradient norm implemented), got %r" % (norm_type,))
         self.cfg = dict(cfg)
         self.device = torch.device(device)
         spec = state_dict_spec(**{k: cfg[k] for k in ("roi_output_size", "n_classes", "use_context",
@@ -121,6 +166,7 @@ class HotPathTrainer:
         self.step_count, self.dropout_seed = 0, int(dropout_seed)
         self.sync_bn = bool(sync_bn) and world_size > 1
         self._setup_finetune(tuple(frozen), tuple(bn_eval))
+        self._setup_optimizer(optimizer, momentum, dampening, nesterov, param_groups, max_grad_norm)
         self._ar_events = []              # (start, end) HIP events around the collective waits of optimizer_step
         self.measure_allreduce = True     # record them (up to 4096 steps; exposed_allreduce_ms() drains the list)
         if world_size > 1:
@@ -155,15 +201,77 @@ class HotPathTrainer:
         self._adam_runs = [tuple(r) for r in runs]
         self.conv_frozen = all(k in self.frozen for k in self.params if k.startswith("convnet."))
 
+    def _setup_optimizer(self, optimizer, momentum, dampening, nesterov, param_groups, max_grad_norm):
+        """Resolve the parameter groups to merged runs of the flat bucket, once.  The default group (unclaimed trainable
+        keys) is ``self.hp`` itself, so today's hyper-parameter dict, its checkpoint field and edits of it keep working."""
+        self.optimizer = optimizer
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.hp.update(momentum=float(momentum), dampening=float(dampening), nesterov=bool(nesterov))
+        claimed, groups = {}, []
+        for i, spec in enumerate(param_groups or ()):
+            if "params" not in spec:
+                raise ValueError("param_groups[%d] has no 'params'" % i)
+            extra = [k for k in spec if k != "params" and k not in _GROUP_HP]
+            if extra:
+                raise ValueError("param_groups[%d]: unknown option(s) %s (allowed: %s)" % (i, extra, _GROUP_HP))
+            entries = _entries(spec["params"])
+            unknown = [e for e in entries if not any(_named_by(k, (e,)) for k in self.params)]
+            if unknown:
+                raise ValueError("param_groups[%d] names no parameter: %s" % (i, unknown))
+            keys = [k for k in self.params if _named_by(k, entries)]
+            twice = [k for k in keys if k in claimed]
+            if twice:
+                raise ValueError("%s claimed by param_groups[%d] and [%d]" % (twice[:4], claimed[twice[0]], i))
+            claimed.update((k, i) for k in keys)
+            g = dict(params=[k for k in keys if k not in self.frozen], **{k: self.hp[k] for k in _GROUP_HP})
+            g.update((k, v) for k, v in spec.items() if k != "params")
+            groups.append(g)
+        rest = [k for k in self.params if k not in self.frozen and k not in claimed]
+        if rest or not groups:
+            self.hp["params"] = rest
+            groups.append(self.hp)
+        if len(groups) > 16:
+            raise ValueError("at most 16 parameter groups (cova_optim_step), got %d" % len(groups))
+        for g in groups:
+            g["betas"] = tuple(float(b) for b in g["betas"])
+            g["nesterov"] = bool(g["nesterov"])
+            _check_sgd_group(optimizer, g)
+        self._groups = groups
+        owner = {k: i for i, g in enumerate(groups) for k in g["params"]}
+        self.optim_runs = group_runs(self.pbucket.offsets, self.pbucket.flat.numel(), self.frozen, owner)
+        # no new option: optimizer_step() is today's cova_adam_step launch(es), the checkpoint format today's
+        self._fused = optimizer != "adam" or param_groups is not None or self.max_grad_norm is not None
+        self.momentum_buffer = torch.zeros_like(self.pbucket.flat) if optimizer == "sgd" else None
+        self._buf_exists = [False] * len(groups)     # per group: torch creates the momentum buffer on its first step
+        self.last_grad_norm = None
+        self._norm_ws = None
+        rows, start = [], 0
+        for lo, hi, gid in self.optim_runs:
+            rows.append((lo, hi, gid, start))
+            start += hi - lo
+        self._seg_total = start
+        self._seg = torch.tensor(rows, dtype=torch.int64).view(-1, 4).to(self.device) if self._fused else None
+
+    @property
+    def param_groups(self):
+        """The live parameter groups ({"params": [keys], lr, weight_decay, betas, eps, momentum, dampening, nesterov}): a
+        hyper-parameter edited between steps (a manual schedule) applies at the next optimizer_step().  Membership is
+        fixed at construction."""
+        return self._groups
+
     def broadcast_state(self, src=0):
         """Rank `src`'s parameters, BatchNorm buffers, Adam moments and step count to every rank: replicas start (and
         resume) from ONE state even when the ranks were built from rank-local checkpoints."""
         import torch.distributed as dist
-        for t in [self.pbucket.flat, self.exp_avg, self.exp_avg_sq] + [self.buffers[k] for k in sorted(self.buffers)]:
+        extra = [self.momentum_buffer] if self.momentum_buffer is not None else []
+        for t in [self.pbucket.flat, self.exp_avg, self.exp_avg_sq] + extra + [self.buffers[k] for k in sorted(self.buffers)]:
             dist.broadcast(t, src=src, group=self.group)
-        step = torch.tensor([self.step_count], dtype=torch.int64, device=self.device)
+        flags = [int(b) for b in self._buf_exists] if self.momentum_buffer is not None else []
+        step = torch.tensor([self.step_count] + flags, dtype=torch.int64, device=self.device)
         dist.broadcast(step, src=src, group=self.group)
-        self.step_count = int(step.item())
+        got = step.tolist()
+        self.step_count = int(got[0])
+        self._buf_exists = [bool(b) for b in got[1:]] if flags else self._buf_exists
 
     def exposed_allreduce_ms(self):
         """Mean time per step the stream spent in optimizer_step's gradient collectives (HIP events on the compute
@@ -223,25 +331,58 @@ class HotPathTrainer:
     def optimizer_state_dict(self):
         """Adam moments + step count (the reference keeps no optimizer state in its checkpoints, train.py:84;
         with this a run can be resumed exactly)."""
-        return dict(step=self.step_count, exp_avg=self.exp_avg.detach().clone(),
-                    exp_avg_sq=self.exp_avg_sq.detach().clone(), hp=dict(self.hp))
+        st = dict(step=self.step_count, exp_avg=self.exp_avg.detach().clone(),
+                  exp_avg_sq=self.exp_avg_sq.detach().clone(), hp={k: self.hp[k] for k in _ADAM_HP})
+        if self._fused:     # (with no new option the format stays today's: an Adam checkpoint has no "algorithm")
+            st.update(algorithm=self.optimizer,
+                      groups=[dict(params=list(g["params"]), **{k: g[k] for k in _GROUP_HP}) for g in self._groups],
+                      momentum_buffer=None if self.momentum_buffer is None else self.momentum_buffer.detach().clone(),
+                      momentum_buffer_exists=list(self._buf_exists))
+        return st
+
+    def _check_optimizer_state(self, state):
+        """(what is wrong with `state` beyond the Adam fields, or None) -- a checkpoint without "algorithm" is Adam's."""
+        algorithm = state.get("algorithm", "adam")
+        if algorithm != self.optimizer:
+            return "optimizer state of algorithm %r, this trainer runs %r" % (algorithm, self.optimizer)
+        groups = state.get("groups")
+        if groups is not None and [list(g.get("params", ())) for g in groups] != [g["params"] for g in self._groups]:
+            return "optimizer state with other parameter groups (%d groups)" % len(groups)
+        buf = state.get("momentum_buffer")
+        if buf is not None and not (torch.is_tensor(buf) and buf.numel() == self.pbucket.flat.numel()):
+            return "momentum buffer of the wrong size (expected %d elements)" % self.pbucket.flat.numel()
+        if len(state.get("momentum_buffer_exists", self._buf_exists)) != len(self._groups):
+            return "momentum_buffer_exists does not have one flag per group"
+        return None
 
     def load_optimizer_state_dict(self, state, broadcast=False):
-        """Adam moments, step count and hyper-parameters.  Local by default; `broadcast=True` makes it a collective every
-        rank must call (validated on all ranks first) after which every rank holds rank 0's moments, step count and
-        hyper-parameters."""
+        """Moments (Adam) or momentum buffer (SGD), step count and hyper-parameters.  Local by default; `broadcast=True`
+        makes it a collective every rank must call (validated on all ranks first) after which every rank holds rank 0's
+        moments, step count and hyper-parameters.  A state of another algorithm raises (on every rank when broadcasting)."""
         ok = all(k in state for k in ("step", "exp_avg", "exp_avg_sq"))
         sized = ok and all(torch.is_tensor(state[k]) and state[k].numel() == self.exp_avg.numel() for k in ("exp_avg", "exp_avg_sq"))
+        problem = self._check_optimizer_state(state)
         if broadcast and self.world_size > 1:
-            self._all_ranks_ok(ok and sized, "load_optimizer_state_dict")       # (sizes too: see load_state_dict)
+            self._all_ranks_ok(ok and sized and problem is None, "load_optimizer_state_dict")   # (sizes too: see load_state_dict)
         if not ok:
             raise KeyError("optimizer state lacks one of step / exp_avg / exp_avg_sq")
         if not sized:
             raise ValueError("optimizer state moments of the wrong size (expected %d elements)" % self.exp_avg.numel())
+        if problem is not None:
+            raise ValueError(problem)
         self.step_count = int(state["step"])
         self.exp_avg.copy_(state["exp_avg"].to(self.device).view_as(self.exp_avg))
         self.exp_avg_sq.copy_(state["exp_avg_sq"].to(self.device).view_as(self.exp_avg_sq))
         self.hp.update(state.get("hp", {}))
+        for g, s in zip(self._groups, state.get("groups") or ()):
+            g.update((k, s[k]) for k in _GROUP_HP if k in s)
+        if self.momentum_buffer is not None:
+            buf = state.get("momentum_buffer")
+            if buf is not None:
+                self.momentum_buffer.copy_(buf.to(self.device).view_as(self.momentum_buffer))
+            else:
+                self.momentum_buffer.zero_()
+            self._buf_exists = [bool(b) for b in state.get("momentum_buffer_exists", [False] * len(self._groups))]
         if broadcast and self.world_size > 1:
             import torch.distributed as dist
             for t in (self.exp_avg, self.exp_avg_sq):
@@ -253,6 +394,22 @@ class HotPathTrainer:
             m = meta.tolist()
             self.step_count = int(m[0])
             self.hp.update(lr=m[1], weight_decay=m[2], betas=(m[3], m[4]), eps=m[5])
+            if self._fused:
+                self._broadcast_groups()
+
+    def _broadcast_groups(self):
+        """Rank 0's per-group hyper-parameters, momentum buffer and its per-group flags to every rank."""
+        import torch.distributed as dist
+        rows = [[g["lr"], g["weight_decay"], g["betas"][0], g["betas"][1], g["eps"], g["momentum"], g["dampening"],
+                 float(g["nesterov"]), float(b)] for g, b in zip(self._groups, self._buf_exists)]
+        meta = torch.tensor(rows, dtype=torch.float64, device=self.device)
+        dist.broadcast(meta, src=0, group=self.group)
+        for g, r in zip(self._groups, meta.tolist()):
+            g.update(lr=r[0], weight_decay=r[1], betas=(r[2], r[3]), eps=r[4], momentum=r[5], dampening=r[6],
+                     nesterov=bool(r[7]))
+        self._buf_exists = [bool(r[8]) for r in meta.tolist()]
+        if self.momentum_buffer is not None:
+            dist.broadcast(self.momentum_buffer, src=0, group=self.group)
 
     def forward_backward(self, batch, masks=None):
         """Forward + CE(sum) + backward into the flat gradient bucket.  Returns (loss, pred)."""
@@ -331,6 +488,9 @@ class HotPathTrainer:
             if timing:
                 e1.record(st)
                 self._ar_events.append((e0, e1))
+        if self._fused:
+            self._fused_step()
+            return
         b1, b2 = self.hp["betas"]
         if not self.frozen:
             engine.call("cova_adam_step", self.pbucket.flat, self.gbucket.flat, self.exp_avg,
@@ -341,6 +501,35 @@ class HotPathTrainer:
             engine.call("cova_adam_step", self.pbucket.flat[lo:hi], self.gbucket.flat[lo:hi], self.exp_avg[lo:hi],
                         self.exp_avg_sq[lo:hi], hi - lo, self.step_count, self.hp["lr"], b1, b2,
                         self.hp["eps"], self.hp["weight_decay"])
+
+    def _fused_step(self):
+        """Clip (optional) and update every group in one cova_optim_step launch.  Under DDP this runs after both phases
+        of the all-reduce, so every rank takes the norm of the same reduced gradients and clips identically; the clip
+        coefficient stays on the device and scales g as the kernel loads it, so the gradient bucket keeps the unclipped
+        reduced gradients and no host read happens."""
+        flat, n = self.pbucket.flat, self.pbucket.flat.numel()
+        gscale = None
+        if self.max_grad_norm is not None:
+            if self._norm_ws is None:
+                n_ws = engine.query("cova_grad_norm_workspace_doubles", self._seg_total)
+                self._norm_ws = torch.empty(n_ws, dtype=torch.float64, device=self.device)
+            out = torch.empty(2, dtype=torch.float32, device=self.device)        # [norm, clip coefficient]
+            engine.call("cova_grad_norm", self.gbucket.flat, n, self._seg, len(self.optim_runs), self._seg_total,
+                        self.max_grad_norm, self._norm_ws, out)
+            self.last_grad_norm, gscale = out[0], out[1:]
+        if not self.optim_runs:
+            return
+        # host table [groups][9], read by the launch itself (kernel arguments): lr, wd, beta1, beta2, eps, momentum,
+        # dampening, nesterov, momentum buffer exists
+        table = torch.tensor([[g["lr"], g["weight_decay"], g["betas"][0], g["betas"][1], g["eps"], g["momentum"],
+                               g["dampening"], float(g["nesterov"]), float(b)]
+                              for g, b in zip(self._groups, self._buf_exists)], dtype=torch.float64)
+        sgd = self.optimizer == "sgd"
+        engine.call("cova_optim_step", OPTIMIZERS.index(self.optimizer), flat, self.gbucket.flat,
+                    self.momentum_buffer if sgd else self.exp_avg, None if sgd else self.exp_avg_sq, n, self._seg,
+                    len(self.optim_runs), self._seg_total, table.data_ptr(), len(self._groups), self.step_count, gscale)
+        if sgd:
+            self._buf_exists = [b or g["momentum"] != 0 for g, b in zip(self._groups, self._buf_exists)]
 
     def train_step(self, batch, masks=None):
         """optimizer.zero_grad(); forward; loss; backward; optimizer.step()  (train.py:45-60).

@@ -446,6 +446,34 @@ int cova_ce_sum(const float *logits, const int64_t *labels /*nullable*/, int N, 
 int cova_adam_step(float *p, const float *g, float *m, float *v, long long n, int step, double lr,
                    double beta1, double beta2, double eps, double weight_decay, void *stream);
 int cova_colsum(const float *x, int ldx, int R, int C, float *out, void *stream);
+
+/* ------------------------------------------------------------------ parameter-group optimizers (optim.hip)
+ * replaces: torch.optim.Adam / torch.optim.AdamW / torch.optim.SGD(param_groups).step() and
+ * torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) for HotPathTrainer(optimizer=, param_groups=,
+ * max_grad_norm=).
+ * segs: DEVICE int64 [n_seg][4] = {lo, hi, group, start}: row r updates elements [lo, hi) of p / g / m / v with the
+ * hyper-parameters of group `group`; `start` = the sum of the lengths of rows 0..r-1, total = the sum of all lengths.
+ * Rows must not overlap (frozen tensors are simply left out); 0 <= lo <= hi <= n, or the row is skipped.
+ * groups: HOST double [n_groups][9] = lr, weight_decay, beta1, beta2, eps, momentum, dampening, nesterov (0/1),
+ * momentum buffer exists (0/1); n_groups <= 16.  Read at launch time (kernel arguments: no copy, no synchronisation);
+ * bias corrections come from `step` in double as in cova_adam_step.
+ * algo 0 = adam: L2 added to the gradient; per element the arithmetic of cova_adam_step (one group = its bits);
+ * algo 1 = adamw: p *= 1 - lr*wd, then the Adam update without the L2 term;
+ * algo 2 = sgd (torch semantics): g += wd*p (wd != 0); with momentum != 0: buf = g on a group's first step (buffer
+ *          flag 0), else buf = momentum*buf + (1-dampening)*g; g = nesterov ? g + momentum*buf : buf; p -= lr*g.
+ *          m = momentum buffer (nullable when every momentum is 0), v unused (nullable).
+ * gscale (nullable, DEVICE [1]): multiplied into g as it is loaded (the clip coefficient of cova_grad_norm); g itself
+ * is not written. */
+int cova_optim_step(int algo, float *p, const float *g, float *m, float *v, long long n, const long long *segs, int n_seg,
+                    long long total, const double *groups, int n_groups, int step, const float *gscale, void *stream);
+/* doubles of cova_grad_norm's workspace for `total` elements (one partial per block of its first launch) */
+int cova_grad_norm_workspace_doubles(long long total);
+/* global L2 norm of the segments of g (same table; group ignored), deterministic: per-block sums of squares in double over
+ * fixed slices, folded in a fixed order by a second launch (no float atomics: reruns and ranks holding the same
+ * gradients get the same bits).  out: DEVICE float [2] = norm, clip coefficient min(1, max_norm / (norm + 1e-6)) in f32 as torch computes
+ * it; a non-finite norm propagates (NaN -> NaN coefficient, inf -> 0), error_if_nonfinite=False. */
+int cova_grad_norm(const float *g, long long n, const long long *segs, int n_seg, long long total, double max_norm,
+                   double *workspace, float *out, void *stream);
 /* evaluation decision (train.py:131-153): per page and class column, page-local indices of the k
  * highest-scoring boxes, best first; page_start [n_pages+1] are box offsets; out [n_pages,NC,k] */
 int cova_page_class_topk(const float *logits, const int64_t *page_start, int n_pages, int NC, int k,
