@@ -1543,3 +1543,66 @@ def ce_sum(logits, labels, want_grad=True, gscale=1.0):
     pred = _empty((N,), logits, torch.int64)
     call("cova_ce_sum", logits, labels, N, NC, float(gscale), loss, dl, pred)
     return loss, dl, pred
+
+
+# ------------------------------------------------------------------------------------------- configurable criterion
+LOSS_MAX_CLASSES = 16
+LOSS_REDUCTIONS = ("sum", "mean")
+
+
+def check_loss_options(n_classes, class_weight=None, label_smoothing=0.0, focal_gamma=0.0, ignore_index=None,
+                       reduction="sum"):
+    """Host validation of the criterion's options (ValueError each) -> normalised dict for ce_loss_fwd / ce_loss_bwd.
+    ``class_weight``: anything torch.as_tensor takes, or None; it is only checked here, not stored."""
+    import math
+    if not 0 < int(n_classes) <= LOSS_MAX_CLASSES:
+        raise ValueError("the criterion kernels take 1..%d classes, got %r" % (LOSS_MAX_CLASSES, n_classes))
+    if reduction not in LOSS_REDUCTIONS:
+        raise ValueError("loss reduction must be one of %s, got %r" % (LOSS_REDUCTIONS, reduction))
+    eps, gamma = float(label_smoothing), float(focal_gamma)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError("label_smoothing must be in [0, 1), got %r" % (label_smoothing,))
+    if not (gamma == 0.0 or (gamma >= 1.0 and math.isfinite(gamma))):
+        raise ValueError("focal_gamma must be 0 (cross-entropy) or a finite value >= 1, got %r" % (focal_gamma,))
+    if gamma != 0.0 and eps != 0.0:
+        raise ValueError("focal_gamma and label_smoothing cannot be combined")
+    if ignore_index is not None:
+        ignore_index = int(ignore_index)
+        if 0 <= ignore_index < int(n_classes):
+            raise ValueError("ignore_index %d names a class (n_classes = %d)" % (ignore_index, n_classes))
+    if class_weight is not None:
+        w = torch.as_tensor(class_weight).detach().double().cpu()
+        if w.dim() != 1 or w.numel() != int(n_classes):
+            raise ValueError("class_weight must hold n_classes = %d values, got shape %s" % (n_classes, tuple(w.shape)))
+        if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+            raise ValueError("class_weight must be finite and non-negative, got %s" % w.tolist())
+    return dict(label_smoothing=eps, focal_gamma=gamma, ignore_index=ignore_index, reduction=reduction)
+
+
+def _loss_args(opts):
+    ig = opts.get("ignore_index")
+    return (float(opts.get("label_smoothing", 0.0)), float(opts.get("focal_gamma", 0.0)), 0 if ig is None else int(ig),
+            0 if ig is None else 1)
+
+
+def ce_loss_fwd(logits, labels, class_weight, opts, metrics=None, want_pred=True, workspace=None):
+    """Phase 1 of the configurable criterion -> (acc float64 [3] = numerator, denominator, kept rows; pred).  Adds the
+    batch to the device counters ``metrics`` (int64 [NC*NC + 4]) when given.  No host read."""
+    N, NC = logits.shape
+    n_ws = query("cova_ce_loss_workspace_doubles", N)
+    if workspace is None or workspace.numel() < n_ws:
+        workspace = _empty((n_ws,), logits, torch.float64)
+    acc = _empty((3,), logits, torch.float64)
+    pred = _empty((N,), logits, torch.int64) if want_pred else None
+    call("cova_ce_loss_fwd", logits, labels, N, NC, class_weight, *_loss_args(opts), acc, pred, metrics, workspace)
+    return acc, pred
+
+
+def ce_loss_bwd(logits, labels, class_weight, opts, acc, grad_scale=None, want_loss=True, want_grad=True):
+    """Phase 2: ``acc`` (device; all-reduced first under data parallelism with "mean") -> (loss f32 [1], dlogits)."""
+    N, NC = logits.shape
+    loss = _empty((1,), logits) if want_loss else None
+    dl = _empty((N, NC), logits) if want_grad else None
+    call("cova_ce_loss_bwd", logits, labels, N, NC, class_weight, *_loss_args(opts), acc,
+         1 if opts.get("reduction", "sum") == "mean" else 0, grad_scale, loss, dl)
+    return loss, dl

@@ -24,6 +24,7 @@ from . import engine
 from .weights import backbone_channels, check_backbone_layers
 
 GAT_MAX_K = engine.GAT_MAX_K
+LOSS_MAX_CLASSES = engine.LOSS_MAX_CLASSES
 
 _FIELDS = ("roi_output_size", "n_classes", "use_context", "hidden_dim", "bbox_hidden_dim",
            "n_additional_feat", "drop_prob")
@@ -506,3 +507,68 @@ class CoVA(nn.Module):
             named = dict(self.named_parameters())
             return _BBoxFn.apply(self, bboxes, *[named[k] for k in self._bbox_keys])
         return bboxes[:, :0]
+
+
+# ------------------------------------------------------------------------------------- criterion
+class _CELossFn(torch.autograd.Function):
+    """cova_ce_loss_fwd + cova_ce_loss_bwd as one autograd node (gradient with respect to the logits only)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, opts):
+        lg, lb = _f32c(logits), _i64c(labels)
+        acc, _ = engine.ce_loss_fwd(lg, lb, weight, opts, want_pred=False)
+        loss, _ = engine.ce_loss_bwd(lg, lb, weight, opts, acc, want_grad=False)
+        ctx.save_for_backward(lg, lb, acc)
+        ctx.weight, ctx.opts = weight, opts
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad):
+        lg, lb, acc = ctx.saved_tensors
+        # the incoming scalar gradient stays on the device: the kernel multiplies it into dlogits
+        gs = grad.detach().to(torch.float32).reshape(1).contiguous()
+        _, dl = engine.ce_loss_bwd(lg, lb, ctx.weight, ctx.opts, acc, grad_scale=gs, want_loss=False)
+        return dl, None, None, None
+
+
+class CrossEntropyLoss(nn.Module):
+    """torch.nn.CrossEntropyLoss's arguments and defaults on the HIP criterion kernels, plus ``focal_gamma`` (0, or >= 1:
+    w[y] (1-p_y)^gamma (-log p_y); not together with label_smoothing).  ``forward(logits [N, C] f32, labels [N] int64)``
+    returns the device scalar.  Differences from torch: reduction "none" and probability targets are
+    not implemented; "mean" over a zero denominator (every box ignored) gives 0 with a zero gradient, not NaN; a label
+    outside [0, C) that is not ``ignore_index`` is skipped like an ignored one instead of raising a device assert."""
+
+    def __init__(self, weight=None, ignore_index=-100, reduction="mean", label_smoothing=0.0, focal_gamma=0.0):
+        super().__init__()
+        if reduction == "none":
+            raise ValueError('reduction="none" (per-box losses) is not implemented; use "mean" or "sum"')
+        w = None if weight is None else torch.as_tensor(weight).detach().to(torch.float32).contiguous().clone()
+        if w is not None and w.dim() != 1:
+            raise ValueError("weight must be one-dimensional (one value per class), got shape %s" % (tuple(w.shape),))
+        # the class count is the logits' width, known at the first forward: until then the weight's own length (the
+        # checks of its values and of the scalar options do not depend on it)
+        engine.check_loss_options(LOSS_MAX_CLASSES if w is None else max(int(w.numel()), 1), w, label_smoothing,
+                                  focal_gamma, None, reduction)
+        self.register_buffer("weight", w)
+        ig = int(ignore_index)
+        self.ignore_index, self.reduction = ig, reduction
+        self.label_smoothing, self.focal_gamma = float(label_smoothing), float(focal_gamma)
+
+    def forward(self, input, target):
+        _require_cuda(input, target)
+        if input.dim() != 2 or target.dim() != 1 or target.shape[0] != input.shape[0]:
+            raise ValueError("CrossEntropyLoss takes logits [N, C] and class labels [N], got %s and %s"
+                             % (tuple(input.shape), tuple(target.shape)))
+        if target.is_floating_point():
+            raise ValueError("probability targets are not implemented: labels must be integer class indices")
+        if self.weight is not None:
+            _require_cuda(self.weight)
+        opts = engine.check_loss_options(input.shape[1], self.weight, self.label_smoothing, self.focal_gamma,
+                                         None, self.reduction)
+        # torch's ignore_index may name a class (rows of that class are then skipped): no range check here
+        opts["ignore_index"] = self.ignore_index
+        return _CELossFn.apply(input, target, self.weight, opts)
+
+    def extra_repr(self):
+        return "ignore_index=%d, reduction=%r, label_smoothing=%g, focal_gamma=%g" % (
+            self.ignore_index, self.reduction, self.label_smoothing, self.focal_gamma)

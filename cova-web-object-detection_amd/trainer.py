@@ -117,6 +117,46 @@ def shard_batch(batch, rank, world_size):
                 context_indices=ctx, labels=batch["labels"][sel].contiguous())
 
 
+class LossMetrics:
+    """Per-class counters of the criterion, accumulated on the device by cova_ce_loss_fwd (no host read per step) and
+    read once per epoch: ``buf`` int64 [NC*NC + 4] = confusion[label][pred] of the kept boxes, kept boxes, bad labels, and
+    the float64 running sums of the loss numerator and denominator (include/cova_hip.h)."""
+
+    def __init__(self, n_classes, device, trainer=None):
+        self.n_classes, self.trainer = int(n_classes), trainer
+        self.buf = torch.zeros(self.n_classes ** 2 + 4, dtype=torch.int64, device=device)
+
+    def reset(self):
+        self.buf.zero_()
+
+    def read(self, reduce=True):
+        """-> dict of host values: confusion (numpy int64 [NC, NC], row = label, column = prediction), kept, bad_labels,
+        loss (numerator / denominator, or the numerator with loss_reduction "sum"), loss_numerator, loss_denominator,
+        per-class recall and precision (NaN where undefined).  One device-to-host copy; under data parallelism with
+        ``reduce`` one all-reduce before it (counts travel as float64: exact below 2**53)."""
+        import numpy as np
+        nc, m = self.n_classes, self.n_classes ** 2
+        tr = self.trainer
+        if reduce and tr is not None and tr.world_size > 1:
+            import torch.distributed as dist
+            t = torch.cat([self.buf[:m + 2].to(torch.float64), self.buf[m + 2:].view(torch.float64)])
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=tr.group)
+            host = t.cpu().numpy()
+            ints, sums = np.rint(host[:m + 2]).astype(np.int64), host[m + 2:]
+        else:
+            host = self.buf.cpu().numpy()
+            ints, sums = host[:m + 2], host[m + 2:].view(np.float64)
+        conf = ints[:m].reshape(nc, nc).copy()
+        num, den = float(sums[0]), float(sums[1])
+        mean = tr is not None and tr.loss_options["loss_reduction"] == "mean"
+        with np.errstate(divide="ignore", invalid="ignore"):
+            diag = np.diag(conf).astype(np.float64)
+            recall, precision = diag / conf.sum(axis=1), diag / conf.sum(axis=0)
+        return dict(confusion=conf, kept=int(ints[m]), bad_labels=int(ints[m + 1]),
+                    loss=(num / den if den > 0 else 0.0) if mean else num, loss_numerator=num, loss_denominator=den,
+                    recall=recall, precision=precision)
+
+
 class HotPathTrainer:
     """Owns flat parameters / gradients / Adam moments on one GPU and runs training steps.
 
@@ -132,12 +172,19 @@ class HotPathTrainer:
     default group of the constructor's values, appended last); ``max_grad_norm`` clips as
     torch.nn.utils.clip_grad_norm_(params, max_grad_norm) over the trainable parameters.  These run as one cova_optim_step
     launch (plus cova_grad_norm's two launches when clipping) with no host synchronisation.  With none of them set, the
-    step is today's cova_adam_step."""
+    step is today's cova_adam_step.
+
+    Criterion ("Criterion options"): ``class_weight`` (n_classes values), ``label_smoothing``,
+    ``focal_gamma`` (0 or >= 1), ``ignore_index`` (a label outside [0, n_classes): such boxes stay graph context but are
+    not scored), ``loss_reduction`` "sum" | "mean" (under data parallelism the mean over the GLOBAL batch) and
+    ``track_metrics`` (``trainer.metrics``: confusion counts and loss sums kept on the device).  Any of them takes the step
+    from cova_ce_sum to cova_ce_loss_fwd / cova_ce_loss_bwd; with none of them set the step is today's cova_ce_sum."""
 
     def __init__(self, cfg, state_dict, device, lr=5e-4, weight_decay=1e-3, betas=(0.9, 0.999),
                  eps=1e-8, world_size=1, process_group=None, dropout_seed=123, sync_bn=False, frozen=(), bn_eval=(),
                  optimizer="adam", momentum=0.0, dampening=0.0, nesterov=False, param_groups=None,
-                 max_grad_norm=None, norm_type=2.0):
+                 max_grad_norm=None, norm_type=2.0, class_weight=None, label_smoothing=0.0, focal_gamma=0.0,
+                 ignore_index=None, loss_reduction="sum", track_metrics=False):
         if optimizer not in OPTIMIZERS:
             raise ValueError("optimizer must be one of %s, got %r" % (OPTIMIZERS, optimizer))
         if float(norm_type) != 2.0:
@@ -167,6 +214,7 @@ class HotPathTrainer:
         self.sync_bn = bool(sync_bn) and world_size > 1
         self._setup_finetune(tuple(frozen), tuple(bn_eval))
         self._setup_optimizer(optimizer, momentum, dampening, nesterov, param_groups, max_grad_norm)
+        self._setup_criterion(class_weight, label_smoothing, focal_gamma, ignore_index, loss_reduction, track_metrics)
         self._ar_events = []              # (start, end) HIP events around the collective waits of optimizer_step
         self.measure_allreduce = True     # record them (up to 4096 steps; exposed_allreduce_ms() drains the list)
         if world_size > 1:
@@ -251,6 +299,46 @@ class HotPathTrainer:
             start += hi - lo
         self._seg_total = start
         self._seg = torch.tensor(rows, dtype=torch.int64).view(-1, 4).to(self.device) if self._fused else None
+
+    def _setup_criterion(self, class_weight, label_smoothing, focal_gamma, ignore_index, loss_reduction, track_metrics):
+        """``class_weight`` becomes a device tensor that may be edited in place; the scalar options live in
+        ``loss_options`` and are read (and checked) at every step: they travel as kernel arguments."""
+        nc = int(self.cfg["n_classes"])
+        engine.check_loss_options(nc, class_weight, label_smoothing, focal_gamma, ignore_index, loss_reduction)
+        self.class_weight = (None if class_weight is None else
+                             torch.as_tensor(class_weight).detach().to(torch.float32).to(self.device).contiguous().clone())
+        self.loss_options = dict(label_smoothing=float(label_smoothing), focal_gamma=float(focal_gamma),
+                                 ignore_index=None if ignore_index is None else int(ignore_index),
+                                 loss_reduction=loss_reduction)
+        self.metrics = LossMetrics(nc, self.device, self) if track_metrics else None
+        self._loss_ws = None
+
+    def _criterion(self):
+        """None: the step's criterion is cova_ce_sum (no option set); else the checked options of this step."""
+        o = self.loss_options
+        if (self.class_weight is None and self.metrics is None and o["label_smoothing"] == 0.0
+                and o["focal_gamma"] == 0.0 and o["ignore_index"] is None and o["loss_reduction"] == "sum"):
+            return None
+        return engine.check_loss_options(int(self.cfg["n_classes"]), None, o["label_smoothing"], o["focal_gamma"],
+                                         o["ignore_index"], o["loss_reduction"])
+
+    @property
+    def loss_path(self):
+        """The entry point(s) the next step's criterion runs through: "cova_ce_sum" or "cova_ce_loss"."""
+        return "cova_ce_sum" if self._criterion() is None else "cova_ce_loss"
+
+    def _criterion_fwd_bwd(self, logits, labels, opts, metrics, want_grad=True):
+        """cova_ce_loss_fwd, the all-reduce of its three float64 sums where the mean is over the global batch, and
+        cova_ce_loss_bwd -> (loss [1], dlogits, pred)."""
+        n_ws = engine.query("cova_ce_loss_workspace_doubles", logits.shape[0])
+        if self._loss_ws is None or self._loss_ws.numel() < n_ws:
+            self._loss_ws = torch.empty(n_ws, dtype=torch.float64, device=self.device)
+        acc, pred = engine.ce_loss_fwd(logits, labels, self.class_weight, opts, metrics, workspace=self._loss_ws)
+        if self.world_size > 1 and opts["reduction"] == "mean":
+            import torch.distributed as dist
+            dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=self.group)
+        loss, dl = engine.ce_loss_bwd(logits, labels, self.class_weight, opts, acc, want_grad=want_grad)
+        return loss, dl, pred
 
     @property
     def param_groups(self):
@@ -412,7 +500,9 @@ class HotPathTrainer:
             dist.broadcast(self.momentum_buffer, src=0, group=self.group)
 
     def forward_backward(self, batch, masks=None):
-        """Forward + CE(sum) + backward into the flat gradient bucket.  Returns (loss, pred)."""
+        """Forward + criterion + backward into the flat gradient bucket.  Returns (loss, pred): the local CE sum, or
+        with criterion options the local sum ("sum") / the mean over the global batch ("mean")."""
+        opts = self._criterion()
         # With SyncBN a one-box shard is legal (the statistics are over the whole batch, as torch.nn.SyncBatchNorm
         # accepts it): the train-mode "more than 1 value per channel" check then applies to the GLOBAL box count, which
         # _stat_sync has from its all-reduce -- every rank raises together instead of one rank leaving the others
@@ -428,7 +518,11 @@ class HotPathTrainer:
                                           batch["bboxes"], batch["additional_feats"],
                                           batch["context_indices"], self.modes, (base, base + 1), masks,
                                           plan=self.plan)
-            loss, dl, pred = engine.ce_sum(logits, batch["labels"])
+            if opts is None:
+                loss, dl, pred = engine.ce_sum(logits, batch["labels"])
+            else:
+                loss, dl, pred = self._criterion_fwd_bwd(logits, batch["labels"], opts,
+                                                         None if self.metrics is None else self.metrics.buf)
             self._head_work = None
             overlap = self.world_size > 1 and engine.OPTIONS.overlap_allreduce
             engine.model_bwd(sv, dl, self.params, self.grads,
@@ -573,3 +667,12 @@ class HotPathTrainer:
                                      batch["context_indices"], False, save=False)
         _, _, pred = engine.ce_sum(logits, None, want_grad=False)
         return logits, pred
+
+    @torch.no_grad()
+    def loss(self, batch):
+        """Validation loss: eval-mode forward (running statistics, as predict) and the configured criterion (without
+        options CrossEntropyLoss(reduction="sum")).  Returns the device scalar; ``metrics`` is not touched."""
+        logits, _ = self.predict(batch)
+        opts = self._criterion() or engine.check_loss_options(int(self.cfg["n_classes"]))
+        loss, _, _ = self._criterion_fwd_bwd(logits, batch["labels"], opts, None, want_grad=False)
+        return loss[0]

@@ -474,6 +474,38 @@ int cova_grad_norm_workspace_doubles(long long total);
  * it; a non-finite norm propagates (NaN -> NaN coefficient, inf -> 0), error_if_nonfinite=False. */
 int cova_grad_norm(const float *g, long long n, const long long *segs, int n_seg, long long total, double max_norm,
                    double *workspace, float *out, void *stream);
+/* ------------------------------------------------------------------ configurable criterion (loss.hip)
+ * replaces: F.cross_entropy(logits, labels, weight=, ignore_index=, label_smoothing=, reduction="sum" | "mean"), the focal
+ * loss, and the per-step .item() reads of loss and accuracy (train.py:54,57), for HotPathTrainer(class_weight=,
+ * label_smoothing=, focal_gamma=, ignore_index=, loss_reduction=, track_metrics=) and models.CrossEntropyLoss.
+ * cova_ce_sum stays the criterion of a trainer without those options.
+ * Per kept row n with label y, p = softmax(l_n), C = NC, w = class_weight (1 when NULL):
+ *   focal_gamma == 0: (1-eps) w[y] (-log p_y) + (eps/C) sum_k w[k] (-log p_k), eps = label_smoothing in [0, 1);
+ *   focal_gamma >= 1: w[y] (1-p_y)^gamma (-log p_y), label_smoothing must be 0; 1-p_y = sum of the other p_k.
+ * A row whose label equals ignore_index (has_ignore_index != 0) is skipped: no loss, a zero dlogits row, in no count.  A
+ * row whose label is outside [0, NC) and not the ignore label is skipped the same way and counted as a bad label.  No
+ * logit is read out of bounds.  NC <= 16.
+ * Two phases, so that the denominator can be summed over ranks between them:
+ * fwd: acc DEVICE double [3] = loss numerator, denominator (sum of w[y] over kept rows), kept rows; pred (nullable) =
+ *   per-row argmax as cova_ce_sum (first maximum wins, every row); metrics (nullable) DEVICE int64 [NC*NC + 4], ADDED
+ *   to: [label*NC + pred] confusion counts of kept rows, [NC*NC] kept rows, [NC*NC+1] bad labels, and, as float64 bit
+ *   patterns, [NC*NC+2] numerator and [NC*NC+3] denominator running sums.  workspace: DEVICE double
+ *   [cova_ce_loss_workspace_doubles(N)], any contents.
+ * bwd: reads acc_total[0..1] from DEVICE memory; reduction_mean == 0: loss = numerator, dlogits unscaled; != 0: both
+ *   divided by the denominator (a zero denominator gives loss 0 and dlogits 0).  grad_scale (nullable, DEVICE [1]) is
+ *   multiplied into dlogits (autograd's incoming gradient).  loss_out (f32 [1]) and dlogits ([N,NC]) are each nullable.
+ * Row arithmetic in f32 as cova_ce_sum; sums over rows in float64 over fixed 2048-row slices folded in a fixed order:
+ * bit-reproducible, a function of N alone, no float atomics, no host read.  Defaults (no weight, eps = gamma = 0, no
+ * ignore label, sum) give cova_ce_sum's dlogits and pred bit for bit and its loss to one f32 ulp. */
+int cova_ce_loss_workspace_doubles(int N);
+int cova_ce_loss_fwd(const float *logits, const int64_t *labels, int N, int NC, const float *class_weight /*nullable [NC]*/,
+                     double label_smoothing, double focal_gamma, long long ignore_index, int has_ignore_index,
+                     double *acc, int64_t *pred /*nullable [N]*/, int64_t *metrics /*nullable*/, double *workspace,
+                     void *stream);
+int cova_ce_loss_bwd(const float *logits, const int64_t *labels, int N, int NC, const float *class_weight /*nullable [NC]*/,
+                     double label_smoothing, double focal_gamma, long long ignore_index, int has_ignore_index,
+                     const double *acc_total, int reduction_mean, const float *grad_scale /*nullable*/,
+                     float *loss_out /*nullable*/, float *dlogits /*nullable*/, void *stream);
 /* evaluation decision (train.py:131-153): per page and class column, page-local indices of the k
  * highest-scoring boxes, best first; page_start [n_pages+1] are box offsets; out [n_pages,NC,k] */
 int cova_page_class_topk(const float *logits, const int64_t *page_start, int n_pages, int NC, int k,
