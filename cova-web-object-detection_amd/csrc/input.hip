@@ -11,17 +11,31 @@
 
 namespace {
 
+// Source page of output page b: b itself, or page_idx[b] of a [P,H,W,3] store when GATHER.  An index outside
+// [0,P) yields -1 and the page is skipped (the host refuses such a list before the launch).
+template <bool GATHER>
+__device__ __forceinline__ long long source_page(const int *__restrict__ page_idx, int P, long long b)
+{
+    if (!GATHER) return b;
+    const int s = page_idx[b];
+    return (s >= 0 && s < P) ? (long long)s : -1;
+}
+
 // 4 consecutive pixels per thread: 12 bytes in (3 x 32-bit loads), one float4 store per channel plane.
+template <bool GATHER>
 __global__ __launch_bounds__(256) void u8_nhwc_to_f32_nchw_kernel(const uint8_t *__restrict__ src,
                                                                    float *__restrict__ dst,
                                                                    long long npix4, long long plane,
-                                                                   long long total_pix)
+                                                                   long long total_pix,
+                                                                   const int *__restrict__ page_idx, int P)
 {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < npix4;
          i += (long long)gridDim.x * blockDim.x) {
         const long long p = i * 4;                 // first pixel (flat over B*H*W); H*W % 4 == 0
         const long long b = p / plane, q = p - b * plane;
-        const uint32_t *s32 = reinterpret_cast<const uint32_t *>(src + p * 3);
+        const long long sp = source_page<GATHER>(page_idx, P, b);      // 64-bit: a store may exceed 4 GiB
+        if (GATHER && sp < 0) continue;
+        const uint32_t *s32 = reinterpret_cast<const uint32_t *>(src + (sp * plane + q) * 3);
         const uint32_t w0 = s32[0], w1 = s32[1], w2 = s32[2];
         uint8_t v[12];
 #pragma unroll
@@ -41,14 +55,19 @@ __global__ __launch_bounds__(256) void u8_nhwc_to_f32_nchw_kernel(const uint8_t 
 }
 
 // generic tail-safe variant (H*W not a multiple of 4 or unaligned buffers)
+template <bool GATHER>
 __global__ __launch_bounds__(256) void u8_nhwc_to_f32_nchw_scalar_kernel(
-    const uint8_t *__restrict__ src, float *__restrict__ dst, long long plane, long long total_pix)
+    const uint8_t *__restrict__ src, float *__restrict__ dst, long long plane, long long total_pix,
+    const int *__restrict__ page_idx, int P)
 {
     for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < total_pix;
          p += (long long)gridDim.x * blockDim.x) {
         const long long b = p / plane, q = p - b * plane;
+        const long long sp = source_page<GATHER>(page_idx, P, b);
+        if (GATHER && sp < 0) continue;
+        const uint8_t *s = src + (sp * plane + q) * 3;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) dst[(b * 3 + c) * plane + q] = (float)src[p * 3 + c] / 255.f;
+        for (int c = 0; c < 3; ++c) dst[(b * 3 + c) * plane + q] = (float)s[c] / 255.f;
     }
 }
 
@@ -104,11 +123,28 @@ COVA_API int cova_images_u8_to_f32(const uint8_t *u8_nhwc, float *f32_nchw, int 
     const long long plane = (long long)H * W, total = plane * B;
     hipStream_t st = (hipStream_t)stream;
     if (plane % 4 == 0 && ((uintptr_t)u8_nhwc & 3) == 0 && ((uintptr_t)f32_nchw & 15) == 0)
-        hipLaunchKernelGGL(u8_nhwc_to_f32_nchw_kernel, dim3(grid_for(total / 4)), dim3(256), 0, st,
-                           u8_nhwc, f32_nchw, total / 4, plane, total);
+        hipLaunchKernelGGL(u8_nhwc_to_f32_nchw_kernel<false>, dim3(grid_for(total / 4)), dim3(256), 0, st,
+                           u8_nhwc, f32_nchw, total / 4, plane, total, (const int *)nullptr, 0);
     else
-        hipLaunchKernelGGL(u8_nhwc_to_f32_nchw_scalar_kernel, dim3(grid_for(total)), dim3(256), 0, st,
-                           u8_nhwc, f32_nchw, plane, total);
+        hipLaunchKernelGGL(u8_nhwc_to_f32_nchw_scalar_kernel<false>, dim3(grid_for(total)), dim3(256), 0, st,
+                           u8_nhwc, f32_nchw, plane, total, (const int *)nullptr, 0);
+    COVA_LAUNCH_CHECK();
+    return COVA_OK;
+}
+
+// the same ToTensor of pages page_idx[0..B) (device int32, each in [0,P)) of a resident u8 [P,H,W,3] store
+COVA_API int cova_pages_u8_gather_f32(const uint8_t *store_u8, const int *page_idx, int P, int B, int H, int W,
+                                      float *f32_nchw, void *stream)
+{
+    COVA_REQUIRE(store_u8 && page_idx && f32_nchw && P > 0 && B > 0 && H > 0 && W > 0);
+    const long long plane = (long long)H * W, total = plane * B;
+    hipStream_t st = (hipStream_t)stream;
+    if (plane % 4 == 0 && ((uintptr_t)store_u8 & 3) == 0 && ((uintptr_t)f32_nchw & 15) == 0)
+        hipLaunchKernelGGL(u8_nhwc_to_f32_nchw_kernel<true>, dim3(grid_for(total / 4)), dim3(256), 0, st,
+                           store_u8, f32_nchw, total / 4, plane, total, page_idx, P);
+    else
+        hipLaunchKernelGGL(u8_nhwc_to_f32_nchw_scalar_kernel<true>, dim3(grid_for(total)), dim3(256), 0, st,
+                           store_u8, f32_nchw, plane, total, page_idx, P);
     COVA_LAUNCH_CHECK();
     return COVA_OK;
 }

@@ -5,6 +5,13 @@
 ``x,y,w,h,label`` rows; ToTensor (/255, CHW), the xywh->xyxy conversion, the page-index column,
 the labels and the batch-global context-window table are produced on the GPU
 (cova_images_u8_to_f32, cova_collate_boxes).  4x fewer bytes over PCIe than fp32 images.
+With ``sampling_fraction < 1`` the background boxes are sampled on the device as datasets.py:101-110
+does on the host (cova_sample_boxes, cova_collate_selected).
+
+``DeviceDataset`` keeps a whole split on the card (pages as uint8, rows, additional features) and yields
+shuffled, sampled, collated batches (``load_data``, datasets.py:193-265): a batch is a page gather by
+index (cova_pages_u8_gather_f32) plus the same sampling and collation kernels; ``epoch_plan`` is the
+host-side order of an epoch.
 
 ``attention_rows`` is the dump of extract_attn_wts_and_visualize.py:104-135.
 """
@@ -14,16 +21,87 @@ import torch
 from . import engine
 from ._lib import call
 
+_M64 = (1 << 64) - 1
+
+
+def mix64(s, x):
+    """The 64-bit counter hash of csrc/common.h (hash_mix64) on Python integers."""
+    z = (s + 0x9E3779B97F4A7C15 * ((x + 1) & _M64)) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def stream_seed(seed, epoch):
+    """The sampling stream of one epoch: key(page, box) = mix64(mix64(stream_seed, page id), box) >> 1."""
+    return mix64(mix64(0, int(seed) & _M64), int(epoch) & _M64)
+
+
+def keep_count(sampling_fraction, n):
+    """Size of the reference's draw for a page of n boxes (datasets.py:103), in Python float64 as there."""
+    return int(sampling_fraction * n)
+
+
+def _check_fraction(sampling_fraction):
+    sf = float(sampling_fraction)
+    if not (0.0 < sf <= 1.0):                              # datasets.py:37
+        raise ValueError("sampling_fraction must be in (0, 1], got %r" % (sampling_fraction,))
+    return sf
+
+
+def _check_rows(r, where):
+    try:
+        a = np.asarray(r, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("%s: rows are not numeric" % where)
+    if a.size % 5 or (a.ndim == 2 and a.shape[1] != 5) or a.ndim > 2:
+        raise ValueError("%s: rows must be [n,5] = x,y,w,h,label, got shape %s" % (where, a.shape))
+    a = a.reshape(-1, 5)
+    if not np.isfinite(a).all():
+        raise ValueError("%s: rows hold non-finite values" % where)
+    return a
+
+
+def _read_kept_total(out_offs, B):
+    """The host read of a sampled batch: 4 bytes, after the two sampling launches on the current stream."""
+    return int(out_offs[B].item())
+
+
+def _sample_and_collate(dev, cs, A, rows_d, addl_d, offs_d, starts_d, pid_d, keep_d, keys_d, B, N, sseed, n_out=None):
+    """cova_sample_boxes + cova_collate_selected on the current stream.  ``n_out`` is the number of kept boxes when the
+    host knows it (everything kept); None reads it back from the device: the one 4-byte host read of a sampled batch."""
+    ws = torch.empty((N + B,), dtype=torch.int32, device=dev)
+    sel = torch.empty((N,), dtype=torch.int32, device=dev)
+    out_offs = torch.empty((B + 1,), dtype=torch.int32, device=dev)
+    call("cova_sample_boxes", rows_d, offs_d, starts_d, pid_d, keep_d, B, N, keys_d, sseed, ws, sel, out_offs)
+    if n_out is None:
+        n_out = _read_kept_total(out_offs, B)
+    K = 2 * cs
+    bboxes = torch.empty((n_out, 5), dtype=torch.float32, device=dev)
+    labels = torch.empty((n_out,), dtype=torch.int64, device=dev)
+    ctx = torch.empty((n_out, K) if K else (0, 0), dtype=torch.int64, device=dev)   # datasets.py:130
+    addl = torch.empty((n_out, A), dtype=torch.float32, device=dev)
+    call("cova_collate_selected", rows_d, sel, out_offs, B, n_out, cs, bboxes, labels, ctx if K else None,
+         addl_d if A else None, A, addl if A else None)
+    return dict(bboxes=bboxes, additional_feats=addl, context_indices=ctx, labels=labels,
+                page_start=out_offs.to(torch.int64))
+
 
 class DeviceCollate:
-    def __init__(self, context_size, device, n_additional_feat=0, pin=False):
+    def __init__(self, context_size, device, n_additional_feat=0, pin=False, sampling_fraction=1.0, seed=0):
         assert context_size >= 0
         self.cs, self.device, self.A = int(context_size), torch.device(device), int(n_additional_feat)
         self.pin = bool(pin)            # stage host arrays in pinned memory: H2D copies become asynchronous
+        self.sf, self.seed = _check_fraction(sampling_fraction), int(seed)
 
-    def __call__(self, u8_pages, rows_per_page, additional_feats=None):
+    def __call__(self, u8_pages, rows_per_page, additional_feats=None, page_ids=None, epoch=0, keys=None):
         """u8_pages: uint8 [B,H,W,3] (numpy or torch, host or device); rows_per_page: list of
-        float32 [n,5] arrays.  Returns the batch dict the trainer / CoVA.forward consume."""
+        float32 [n,5] arrays.  Returns the batch dict the trainer / CoVA.forward consume.
+
+        With ``sampling_fraction < 1`` each page keeps its labelled boxes and the int(sf * n) boxes of smallest key
+        (datasets.py:101-110).  The key of a box is a hash of (seed, epoch, page id, box index); ``page_ids`` are the
+        dataset-wide page ids (default: the position in the batch).  ``keys`` (int64 [N], non-negative) injects the keys
+        instead: ``keys[perm[j]] = j`` per page reproduces the reference's ``np.random.permutation`` draw ``perm``."""
         u8 = torch.as_tensor(np.ascontiguousarray(u8_pages) if isinstance(u8_pages, np.ndarray)
                              else u8_pages)
         assert u8.dtype == torch.uint8 and u8.dim() == 4 and u8.shape[3] == 3
@@ -38,9 +116,11 @@ class DeviceCollate:
         host = (lambda t: t.pin_memory()) if self.pin else (lambda t: t)
         u8 = (host(u8) if u8.device.type == "cpu" else u8).to(dev, non_blocking=True).contiguous()
         rows_d = host(torch.from_numpy(rows)).to(dev, non_blocking=True)
-        offs_d = host(torch.from_numpy(offs)).to(dev, non_blocking=True)
         images = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
         call("cova_images_u8_to_f32", u8, images, B, H, W)
+        if self.sf < 1.0 or keys is not None:
+            return self._sampled(images, rows_d, counts, offs, additional_feats, page_ids, epoch, keys, host)
+        offs_d = host(torch.from_numpy(offs)).to(dev, non_blocking=True)
         bboxes = torch.empty((N, 5), dtype=torch.float32, device=dev)
         labels = torch.empty((N,), dtype=torch.int64, device=dev)
         K = 2 * self.cs
@@ -52,6 +132,217 @@ class DeviceCollate:
             addl = torch.as_tensor(additional_feats, dtype=torch.float32).to(dev).contiguous()
         return dict(images=images, bboxes=bboxes, additional_feats=addl, context_indices=ctx,
                     labels=labels, page_start=offs_d.to(torch.int64))
+
+    def _sampled(self, images, rows_d, counts, offs, additional_feats, page_ids, epoch, keys, host):
+        dev, B, N = self.device, len(counts), int(offs[-1])
+        if page_ids is None:
+            pids = np.arange(B, dtype=np.int64)
+        else:
+            pids = np.asarray(page_ids, dtype=np.int64).reshape(-1)
+            if pids.shape[0] != B or (pids < 0).any() or (pids >= 2 ** 31).any():
+                raise ValueError("page_ids must hold one id in [0, 2**31) per page")
+        keep = np.asarray([keep_count(self.sf, n) for n in counts], dtype=np.int64)
+        ints = np.concatenate([offs.astype(np.int64), keep, pids]).astype(np.int32)      # one small upload
+        ints_d = host(torch.from_numpy(ints)).to(dev, non_blocking=True)
+        offs_d, keep_d, pid_d = ints_d[:B + 1], ints_d[B + 1:2 * B + 1], ints_d[2 * B + 1:]
+        keys_d = None
+        if keys is not None:
+            k = np.ascontiguousarray(np.asarray(keys, dtype=np.int64).reshape(-1))
+            if k.shape[0] != N or (k < 0).any():
+                raise ValueError("keys must hold one non-negative integer per box")
+            keys_d = host(torch.from_numpy(k)).to(dev, non_blocking=True)
+        A, addl_d = 0, None
+        if additional_feats is not None:
+            addl_d = torch.as_tensor(additional_feats, dtype=torch.float32).to(dev).contiguous()
+            if addl_d.dim() != 2 or addl_d.shape[0] != N:
+                raise ValueError("additional_feats must be [N, A] with one row per box")
+            A = int(addl_d.shape[1])
+        out = _sample_and_collate(dev, self.cs, A, rows_d, addl_d, offs_d, None, pid_d, keep_d, keys_d, B, N,
+                                  stream_seed(self.seed, epoch))
+        out["images"] = images
+        return out
+
+
+def epoch_plan(n_pages, batch_size, shuffle, seed, epoch, drop_last=False, rank=0, world_size=1, order=None):
+    """Page ids of every step of one epoch for this rank (host only): a list of int64 arrays.
+
+    The order is ``order`` if given (any sequence of ids in [0, n_pages)), else a permutation that is a function of
+    ``(seed, epoch)`` alone when ``shuffle`` (numpy's frozen RandomState stream seeded with the two; torch's
+    RandomSampler stream is NOT reproduced), else 0..n_pages-1.  A global batch is ``batch_size * world_size``
+    consecutive entries; a rank takes ``trainer.shard_pages`` of it, i.e. the pages ``trainer.shard_batch`` cuts out of
+    the single-process batch.  The short last batch is kept (DataLoader drop_last=False) unless ``drop_last``; a last
+    global batch with fewer pages than ranks is always dropped (some rank would get no page and the step's collectives
+    would not match)."""
+    from .trainer import shard_pages
+    n_pages, batch_size, rank, world_size = int(n_pages), int(batch_size), int(rank), int(world_size)
+    if n_pages < 0 or batch_size < 1 or world_size < 1 or not (0 <= rank < world_size):
+        raise ValueError("epoch_plan: need n_pages >= 0, batch_size >= 1 and 0 <= rank < world_size")
+    if order is not None:
+        ids = np.asarray(order).reshape(-1)
+        if ids.size and (ids.dtype.kind not in "iu" or (ids < 0).any() or (ids >= n_pages).any()):
+            raise ValueError("epoch_plan: order must hold integer page ids in [0, %d)" % n_pages)
+        ids = ids.astype(np.int64)
+    elif shuffle:
+        ids = np.random.RandomState([int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF,
+                                     (int(epoch) >> 32) & 0xFFFFFFFF]).permutation(n_pages).astype(np.int64)
+    else:
+        ids = np.arange(n_pages, dtype=np.int64)
+    g = batch_size * world_size
+    plan = []
+    for s in range(0, ids.shape[0], g):
+        glob = ids[s:s + g]
+        if glob.shape[0] < (g if drop_last else world_size):
+            break
+        lo, hi = shard_pages(glob.shape[0], rank, world_size)
+        plan.append(glob[lo:hi].copy())
+    return plan
+
+
+class DeviceDataset:
+    """A whole split resident on the GPU: ``[P,H,W,3]`` uint8 pages, the x,y,w,h,label rows of every page back to back
+    and (optionally) the additional features.  ``batches`` yields ``DeviceCollate``'s batch dict for the pages of every
+    step of ``epoch_plan``, plus ``page_ids`` (device int64 [B]) and ``img_ids`` (host array of names)."""
+
+    STAGING_BYTES = 64 << 20           # pinned staging buffer of the one-off upload
+
+    def __init__(self, u8_pages, rows_per_page, context_size, device, additional_feats=None, img_ids=None):
+        if int(context_size) < 0:
+            raise ValueError("context_size must be >= 0")
+        self.cs, self.device = int(context_size), torch.device(device)
+        if isinstance(u8_pages, (list, tuple)):
+            pages = [torch.as_tensor(np.ascontiguousarray(p) if isinstance(p, np.ndarray) else p) for p in u8_pages]
+            if not pages or any(p.shape != pages[0].shape for p in pages):
+                raise ValueError("u8_pages: a non-empty list of equal-shape pages is needed")
+            shape = (len(pages),) + tuple(pages[0].shape)
+        else:
+            pages = torch.as_tensor(np.ascontiguousarray(u8_pages) if isinstance(u8_pages, np.ndarray) else u8_pages)
+            shape = tuple(pages.shape)
+        first = pages[0] if isinstance(pages, list) else pages
+        if len(shape) != 4 or shape[3] != 3 or shape[0] < 1 or first.dtype != torch.uint8:
+            raise ValueError("u8_pages must be uint8 [P,H,W,3], got %s %s" % (first.dtype, shape))
+        P, H, W, _ = shape
+        self.P, self.H, self.W = P, H, W
+        if len(rows_per_page) != P:
+            raise ValueError("rows_per_page must hold one [n,5] array per page")
+        rows = [_check_rows(r, "page %d" % i) for i, r in enumerate(rows_per_page)]
+        self.counts = np.asarray([r.shape[0] for r in rows], dtype=np.int64)          # host copies: the plan of an epoch
+        self.starts = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int64)  # is computed without a device read
+        n_total = int(self.starts[-1])
+        if n_total >= 2 ** 31:
+            raise ValueError("too many boxes for int32 row ids")
+        rows = np.concatenate(rows, 0) if n_total else np.zeros((0, 5), np.float32)
+        self.A, addl = 0, None
+        if additional_feats is not None:
+            if isinstance(additional_feats, (list, tuple)):
+                parts = [np.asarray(a, dtype=np.float32).reshape(int(n), -1) if int(n) else None
+                         for a, n in zip(additional_feats, self.counts)]
+                parts = [a for a in parts if a is not None]
+                if len(additional_feats) != P or any(a.shape[1] != parts[0].shape[1] for a in parts):
+                    raise ValueError("additional_feats must hold one [n,A] array per page")
+                addl = np.concatenate(parts, 0) if parts else np.zeros((0, 0), np.float32)
+            else:
+                addl = np.asarray(torch.as_tensor(additional_feats).cpu(), dtype=np.float32)
+            if addl.ndim != 2 or addl.shape[0] != n_total or not np.isfinite(addl).all():
+                raise ValueError("additional_feats must be finite [N, A] with one row per box")
+            self.A = int(addl.shape[1])
+        if img_ids is None:
+            self.img_ids = np.asarray([str(i) for i in range(P)])
+        else:
+            self.img_ids = np.asarray(img_ids)
+            if self.img_ids.shape != (P,):
+                raise ValueError("img_ids must hold one name per page")
+        dev = self.device
+        self.rows = torch.from_numpy(np.ascontiguousarray(rows)).to(dev)
+        self.addl = torch.from_numpy(np.ascontiguousarray(addl)).to(dev) if self.A else None
+        self.store = torch.empty((P, H, W, 3), dtype=torch.uint8, device=dev)
+        self._upload(pages)
+        torch.cuda.synchronize(dev)
+
+    def _upload(self, pages):
+        if not isinstance(pages, list) and pages.device.type != "cpu":
+            self.store.copy_(pages)
+            return
+        page_bytes = self.H * self.W * 3
+        chunk = max(1, min(self.P, self.STAGING_BYTES // max(page_bytes, 1)))
+        staging = torch.empty((chunk, self.H, self.W, 3), dtype=torch.uint8).pin_memory()
+        stream = torch.cuda.current_stream(self.device)
+        for lo in range(0, self.P, chunk):
+            hi = min(self.P, lo + chunk)
+            if isinstance(pages, list):
+                for k in range(lo, hi):
+                    staging[k - lo].copy_(pages[k])
+            else:
+                staging[:hi - lo].copy_(pages[lo:hi])
+            self.store[lo:hi].copy_(staging[:hi - lo], non_blocking=True)
+            stream.synchronize()                          # the staging buffer is reused by the next chunk
+
+    def __len__(self):
+        return self.P
+
+    def batches(self, batch_size, shuffle=False, sampling_fraction=1.0, seed=0, epoch=0, drop_last=False, rank=0,
+                world_size=1, order=None, prefetch=True):
+        """One epoch of batches (a generator).  Train: ``shuffle=True, sampling_fraction=sf``; val / test: batch 10,
+        no shuffle, no sampling (datasets.py:227-258).  With ``prefetch`` batch i+1 is assembled on a side stream while
+        the consumer works on batch i.  With ``sampling_fraction == 1`` there is no host read at all; otherwise one
+        4-byte read per batch (the number of kept boxes), on the side stream."""
+        sf = _check_fraction(sampling_fraction)
+        plan = epoch_plan(self.P, batch_size, shuffle, seed, epoch, drop_last, rank, world_size, order)
+        return self._iterate(plan, sf, stream_seed(seed, epoch), bool(prefetch))
+
+    def _iterate(self, plan, sf, sseed, prefetch):
+        if not plan:
+            return
+        dev = self.device
+        # the whole epoch's index tables go up in one copy: per step [page ids | batch offsets | row starts | keep counts]
+        parts, where, pos = [], [], 0
+        for ids in plan:
+            n = self.counts[ids]
+            part = np.concatenate([ids, np.concatenate([[0], np.cumsum(n)]), self.starts[ids],
+                                   [keep_count(sf, int(c)) for c in n]]).astype(np.int32)
+            parts.append(part)
+            where.append((pos, int(ids.shape[0]), int(n.sum())))
+            pos += part.shape[0]
+        table = torch.from_numpy(np.concatenate(parts)).to(dev)
+        ids64 = torch.from_numpy(np.concatenate(plan)).to(dev)
+        starts64 = np.concatenate([[0], np.cumsum([len(ids) for ids in plan])])
+
+        def assemble(step):
+            pos, B, N = where[step]
+            ids_d, offs_d = table[pos:pos + B], table[pos + B:pos + 2 * B + 1]
+            starts_d, keep_d = table[pos + 2 * B + 1:pos + 3 * B + 1], table[pos + 3 * B + 1:pos + 4 * B + 1]
+            images = torch.empty((B, 3, self.H, self.W), dtype=torch.float32, device=dev)
+            call("cova_pages_u8_gather_f32", self.store, ids_d, self.P, B, self.H, self.W, images)
+            out = _sample_and_collate(dev, self.cs, self.A, self.rows, self.addl, offs_d, starts_d, ids_d, keep_d, None,
+                                      B, N, sseed, n_out=N if sf == 1.0 else None)
+            out["images"] = images
+            out["page_ids"] = ids64[int(starts64[step]):int(starts64[step + 1])]
+            out["img_ids"] = self.img_ids[plan[step]]
+            return out
+
+        if not prefetch:
+            for step in range(len(plan)):
+                yield assemble(step)
+            return
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))           # the tables above were uploaded on the caller's stream
+
+        def preload(step):
+            with torch.cuda.stream(side):
+                batch = assemble(step)
+                ev = torch.cuda.Event()
+                ev.record(side)
+            return batch, ev
+
+        pending = preload(0)
+        for step in range(len(plan)):
+            batch, ev = pending
+            cur = torch.cuda.current_stream(dev)
+            cur.wait_event(ev)
+            for v in batch.values():
+                if torch.is_tensor(v):
+                    v.record_stream(cur)         # allocated on the side stream, consumed on this one
+            pending = preload(step + 1) if step + 1 < len(plan) else None
+            yield batch
 
 
 class Prefetcher:

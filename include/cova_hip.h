@@ -520,6 +520,42 @@ int cova_images_u8_to_f32(const uint8_t *u8_nhwc, float *f32_nchw, int B, int H,
 int cova_collate_boxes(const float *rows, const int *page_offsets, int B, int N, int context_size,
                        float *bboxes, long long *labels, long long *ctx /*nullable if context_size==0*/,
                        void *stream);
+/* ---- device-resident dataset: page gather, background-box sampling, collation of the kept boxes ----
+ * cova_pages_u8_gather_f32: cova_images_u8_to_f32 of the pages page_idx[0..B) (DEVICE int32, each in [0,P)) of a
+ *   resident u8 [P,H,W,3] store -> f32 [B,3,H,W]; the same arithmetic, bit-identical results; page offsets are 64-bit
+ *   (the store may exceed 4 GiB).  The host checks the index list; an index outside [0,P) leaves its output page unwritten.
+ * cova_sample_boxes (datasets.py:101-110): page p of the batch owns n = page_offsets[p+1] - page_offsets[p] boxes
+ *   (page_offsets DEVICE int32 [B+1], page_offsets[B] = N); its box i is row row_starts[p] + i of `rows` ([*,5] =
+ *   x,y,w,h,label; row_starts DEVICE int32 [B], NULL: page_offsets[p], the rows of the batch back to back).  Box i is kept
+ *   if its rank among the page's (key, i) pairs -- smaller key first, ties to the lower i -- is < keep_counts[p] (DEVICE
+ *   int32 [B]; the host computes int(sampling_fraction * n) in float64 as the reference does), or if rows[.,4] != 0 (the
+ *   float test of datasets.py:106).  sel (int32 [N]) receives the kept SOURCE row ids in ascending order, first N_out
+ *   valid; out_offsets (int32 [B+1]) the page offsets of the kept boxes, out_offsets[B] = N_out.  Any n is valid (0, 1,
+ *   thousands), and so is a page that keeps nothing.
+ *   keys (nullable): DEVICE int64 [N], non-negative, compared as integers, keys[page_offsets[p] + i] for box i (tests
+ *   inject the reference's permutation: key[perm[j]] = j).  NULL: the key is 63 bits of a counter hash,
+ *       mix(s, x) = z ^ (z >> 31),  z = (z ^ (z >> 27)) * 0x94D049BB133111EB,  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9,
+ *                   z = s + 0x9E3779B97F4A7C15 * (x + 1)              (all modulo 2^64; the mixer of the dropout masks)
+ *       key(p, i) = mix(mix(stream_seed, pid), i) >> 1,   pid = page_ids[p] (DEVICE int32 [B]), or p when page_ids is NULL
+ *   so a page's sample depends on (stream_seed, pid) alone -- not on the batch it lands in, its position, the batch size,
+ *   the rank or the world size.  The host folds seed and epoch: stream_seed = mix(mix(0, seed), epoch).
+ *   workspace: DEVICE int32 [cova_sample_boxes_workspace_ints(B, N)] = N + B, any contents.  Two launches, no atomics, no
+ *   host read: bit-deterministic.
+ * cova_collate_selected: cova_collate_boxes over the kept boxes: box g of the output is source row sel[g], its page the
+ *   p with out_offsets[p] <= g < out_offsets[p+1]; the context window runs over the kept boxes of the page (the reference
+ *   builds it after sampling, datasets.py:117-128).  addl_out [N_out,A] = addl_in[sel[g], :] (both nullable when A == 0).
+ *   N_out is a host value (out_offsets[B], the one host read of a sampled batch).  Bit-exact as cova_collate_boxes. */
+int cova_pages_u8_gather_f32(const uint8_t *store_u8, const int *page_idx, int P, int B, int H, int W, float *f32_nchw,
+                             void *stream);
+int cova_sample_boxes_workspace_ints(int B, int N);
+int cova_sample_boxes(const float *rows, const int *page_offsets, const int *row_starts /*nullable*/,
+                      const int *page_ids /*nullable*/, const int *keep_counts, int B, int N,
+                      const long long *keys /*nullable*/, unsigned long long stream_seed, int *workspace, int *sel,
+                      int *out_offsets, void *stream);
+int cova_collate_selected(const float *rows, const int *sel, const int *out_offsets, int B, int N_out, int context_size,
+                          float *bboxes, long long *labels, long long *ctx /*nullable if context_size==0*/,
+                          const float *addl_in /*nullable if A==0*/, int A, float *addl_out /*nullable if A==0*/,
+                          void *stream);
 /* attention export rows (extract_attn_wts_and_visualize.py:104-135): out [N, 5+5K] =
  * x,y,w,h,label, K x (x,y,w,h) of the context boxes (0 for pads), K attention weights */
 int cova_attn_export_rows(const float *bboxes, const long long *ctx, const float *attn,
