@@ -146,9 +146,15 @@ class LossMetrics:
         else:
             host = self.buf.cpu().numpy()
             ints, sums = host[:m + 2], host[m + 2:].view(np.float64)
-        conf = ints[:m].reshape(nc, nc).copy()
+        return self.decode(ints, sums, nc, tr is not None and tr.loss_options["loss_reduction"] == "mean")
+
+    @staticmethod
+    def decode(ints, sums, nc, mean):
+        """read()'s dict from host copies of the NC*NC + 2 integer counters and the two float64 sums."""
+        import numpy as np
+        m = nc * nc
+        conf = np.asarray(ints[:m]).reshape(nc, nc).copy()
         num, den = float(sums[0]), float(sums[1])
-        mean = tr is not None and tr.loss_options["loss_reduction"] == "mean"
         with np.errstate(divide="ignore", invalid="ignore"):
             diag = np.diag(conf).astype(np.float64)
             recall, precision = diag / conf.sum(axis=1), diag / conf.sum(axis=0)

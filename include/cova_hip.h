@@ -510,6 +510,19 @@ int cova_ce_loss_bwd(const float *logits, const int64_t *labels, int N, int NC, 
  * highest-scoring boxes, best first; page_start [n_pages+1] are box offsets; out [n_pages,NC,k] */
 int cova_page_class_topk(const float *logits, const int64_t *page_start, int n_pages, int NC, int k,
                          int64_t *out, void *stream);
+/* evaluation of a split (eval.hip; train.py:131-154 over a whole loader, for evaluation.evaluate_split): page p of the
+ * batch owns boxes page_start[p] .. page_start[p+1] (DEVICE int64 [B+1]).  For class c in 1..NC-1 let t be the lowest
+ * page-local index with labels == c (the [0, 0] of train.py:151).  rank[row, c-1] = number of boxes j of the page with
+ * v_j > v_t, or v_j == v_t and j < t, in column c: the position of the labelled box in cova_page_class_topk's order (score
+ * descending, ties to the lower index), so "the labelled box is among the top k" is 0 <= rank < k for every k.  A page
+ * without a box of class c gets -1.  top1[row, c-1] (nullable) = page-local index of the best box of the column in that
+ * order, -1 for an empty page.  row = page_ids[p] (DEVICE int32 [B]), or p when page_ids is NULL; a row outside [0, P) is
+ * skipped (the host validates ids), rows of pages not in the batch are not written (the caller pre-fills the [P, NC-1]
+ * int32 tables with -2 = not evaluated).  Labels outside [0, NC) match no class.  Any page size (0, 1, thousands of
+ * boxes); 2 <= NC <= 16.  One launch, one wave per (page, class), no workspace, no atomics, no host read. */
+int cova_eval_page_ranks(const float *logits, const int64_t *labels, const int64_t *page_start,
+                         const int *page_ids /*nullable [B]*/, int B, int NC, int P, int *rank,
+                         int *top1 /*nullable [P,NC-1]*/, void *stream);
 
 /* ---- device-side input pipeline --------------------------------------
  * ToTensor of datasets.py:41-45,96-97: u8 [B,H,W,3] -> f32 [B,3,H,W], value/255 (bit-exact) */

@@ -1,0 +1,404 @@
+"""GPU tests of split evaluation and the epoch loop: cova_eval_page_ranks against the reference's own decisions
+(golden/evaluate_split.npz), cova_page_class_topk and the numpy oracle (tests/eval_oracle.py); evaluate_split against
+HotPathTrainer.evaluate, the CPU oracle and its own rank shards; fit against the same loop written out by hand."""
+import functools
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from cova_web_object_detection_amd import _lib, engine, evaluation, weights  # noqa: E402
+from cova_web_object_detection_amd.evaluation import EvalReport, evaluate_split, fit, step_lr  # noqa: E402
+from cova_web_object_detection_amd.pipeline import DeviceDataset  # noqa: E402
+from cova_web_object_detection_amd.trainer import HotPathTrainer, LossMetrics  # noqa: E402
+from oracle import cova_oracle as O  # noqa: E402
+import eval_oracle as EO  # noqa: E402
+
+DEV = "cuda:0"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def run_kernel(logits, labels, page_start, nc, page_ids=None, P=None, want_top1=True):
+    """cova_eval_page_ranks on one batch -> (rank, top1) numpy int32 [P, nc-1], the tables pre-filled with -2."""
+    B = len(page_start) - 1
+    P = B if P is None else P
+    lg = torch.as_tensor(np.ascontiguousarray(logits, dtype=np.float32)).to(DEV).reshape(-1, nc)
+    lb = torch.as_tensor(np.ascontiguousarray(labels, dtype=np.int64)).to(DEV)
+    if lg.shape[0] == 0:                       # the entry point wants valid pointers even when every page is empty
+        lg, lb = torch.zeros((1, nc), device=DEV), torch.zeros(1, dtype=torch.int64, device=DEV)
+    ps = torch.as_tensor(np.asarray(page_start, dtype=np.int64)).to(DEV)
+    ids = None if page_ids is None else torch.as_tensor(np.asarray(page_ids, dtype=np.int32)).to(DEV)
+    rank = torch.full((P, nc - 1), -2, dtype=torch.int32, device=DEV)
+    top1 = torch.full((P, nc - 1), -2, dtype=torch.int32, device=DEV) if want_top1 else None
+    engine.call("cova_eval_page_ranks", lg, lb, ps, ids, B, nc, P, rank, top1)
+    torch.cuda.synchronize()
+    return rank.cpu().numpy(), None if top1 is None else top1.cpu().numpy()
+
+
+# ---------------------------------------------------------------- 1. the reference's decisions
+@pytest.mark.parametrize("tag,batch", [("a", 10), ("b", 4)])
+def test_kernel_reproduces_the_reference_fixture(tag, batch):
+    fx = np.load(GOLDEN + "/evaluate_split.npz")
+    counts, logits, labels = fx[tag + "/counts"], fx[tag + "/logits"], fx[tag + "/labels"]
+    start = np.concatenate([[0], np.cumsum(counts)])
+    P = len(counts)
+    rank = np.full((P, 3), -2, dtype=np.int32)
+    top1 = rank.copy()
+    for s in range(0, P, batch):                                   # the loader's batches, injected one by one
+        e = min(s + batch, P)
+        r, t = run_kernel(logits[start[s]:start[e]], labels[start[s]:start[e]], start[s:e + 1] - start[s], 4,
+                          page_ids=np.arange(s, e), P=P)
+        written = (r != -2).any(axis=1)
+        assert written.tolist() == [s <= p < e for p in range(P)]
+        rank[written], top1[written] = r[written], t[written]
+    rep = EvalReport(rank, top1, fx[tag + "/names"])
+    for k in (1, 3):
+        ref = fx["%s/img_acc_k%d" % (tag, k)]
+        assert np.array_equal(rep.hits(k).astype(np.int32), ref[:, 1:])
+        assert np.array_equal(rep.img_acc(k), ref) and np.array_equal(rep.class_acc(k), fx["%s/class_acc_k%d" % (tag, k)])
+    assert np.array_equal(rep.macro_acc(fx[tag + "/webpage_info"], fx[tag + "/domains"]), fx[tag + "/macro_acc"],
+                          equal_nan=True)
+
+
+# ---------------------------------------------------------------- 2. / 3. cova_page_class_topk and the numpy oracle
+def tie_case(nc=4, seed=3):
+    """Pages of 0, 1, 11, 64, 65, 230 and 1000 boxes, logits quantised to 0.5 (ties are frequent), page 2 without
+    class 2, page 3 with two boxes of class 1 (the first counts), labels outside [0, nc) on page 5."""
+    rs = np.random.RandomState(seed)
+    counts = [0, 1, 11, 64, 65, 230, 1000]
+    start = np.concatenate([[0], np.cumsum(counts)])
+    logits = (np.round(rs.standard_normal((start[-1], nc)) * 2) / 2).astype(np.float32)
+    labels = np.zeros(start[-1], dtype=np.int64)
+    for p, n in enumerate(counts):
+        pos = rs.permutation(n)[:nc - 1]
+        labels[start[p] + pos] = np.arange(1, len(pos) + 1)
+    labels[start[2]:start[3]][labels[start[2]:start[3]] == 2] = 0
+    page3 = np.nonzero(labels[start[3]:start[4]] == 0)[0]
+    labels[start[3] + page3[[5, 40]]] = 1
+    labels[start[5] + np.nonzero(labels[start[5]:start[6]] == 0)[0][:3]] = [nc, -1, 1 << 40]
+    return counts, start, logits, labels
+
+
+@pytest.mark.parametrize("nc", [4, 7, 16])
+def test_kernel_equals_the_numpy_oracle_exactly(nc):
+    counts, start, logits, labels = tie_case(nc, seed=nc)
+    rank, top1 = run_kernel(logits, labels, start, nc)
+    ref_rank, ref_top1 = EO.page_ranks(logits, labels, start, nc)
+    assert np.array_equal(rank, ref_rank) and np.array_equal(top1, ref_top1)
+    assert (rank[0] == -1).all() and (top1[0] == -1).all()                   # the empty page
+    assert rank[1].tolist() == [0] + [-1] * (nc - 2) and (top1[1] == 0).all()  # one box, labelled class 1
+    assert rank[2, 1] == -1 and (rank[2, [0, 2]] >= 0).all()                 # the page missing class 2
+
+
+@pytest.mark.parametrize("k", [1, 3, 5])
+def test_rank_below_k_is_membership_in_the_topk_list(k):
+    counts, start, logits, labels = tie_case()
+    rank, top1 = run_kernel(logits, labels, start, 4)
+    out = torch.empty((len(counts), 4, k), dtype=torch.int64, device=DEV)
+    _lib.call("cova_page_class_topk", torch.from_numpy(logits).to(DEV), torch.from_numpy(start.astype(np.int64)).to(DEV),
+              len(counts), 4, k, out)
+    topk = out.cpu().numpy()
+    ties = 0
+    for p in range(len(counts)):
+        lab = labels[start[p]:start[p + 1]]
+        for c in (1, 2, 3):
+            where = np.nonzero(lab == c)[0]
+            member = bool(where.size) and int(where[0]) in topk[p, c].tolist()
+            assert member == (0 <= rank[p, c - 1] < k), (p, c)
+            assert top1[p, c - 1] == topk[p, c, 0], (p, c)
+            if where.size:
+                ties += int((logits[start[p]:start[p + 1], c] == logits[start[p] + where[0], c]).sum() > 1)
+    assert ties >= 6                                                         # the labelled boxes do sit in ties
+    two = np.nonzero(labels[start[3]:start[4]] == 1)[0]
+    assert len(two) == 3 and rank[3, 0] == EO.page_ranks(logits, labels, start, 4)[0][3, 0]
+
+
+# ---------------------------------------------------------------- 4. scatter
+def test_rows_outside_the_batch_keep_minus_two_and_bad_ids_are_skipped():
+    counts, start, logits, labels = tie_case()
+    sel = [2, 3, 4, 5]
+    s = np.concatenate([[0], np.cumsum([counts[i] for i in sel])])
+    lg = np.concatenate([logits[start[i]:start[i + 1]] for i in sel])
+    lb = np.concatenate([labels[start[i]:start[i + 1]] for i in sel])
+    ref_rank, ref_top1 = EO.page_ranks(lg, lb, s, 4)
+    rank, top1 = run_kernel(lg, lb, s, 4, page_ids=[6, 9, -1, 0], P=8)          # ids 9 and -1 are outside [0, 8)
+    assert np.array_equal(rank[6], ref_rank[0]) and np.array_equal(rank[0], ref_rank[3])
+    assert np.array_equal(top1[6], ref_top1[0]) and np.array_equal(top1[0], ref_top1[3])
+    assert (rank[[1, 2, 3, 4, 5, 7]] == -2).all() and (top1[[1, 2, 3, 4, 5, 7]] == -2).all()
+    rank2, none = run_kernel(lg, lb, s, 4, page_ids=[6, 9, -1, 0], P=8, want_top1=False)   # top1 is optional
+    assert none is None and np.array_equal(rank2, rank)
+    with pytest.raises(_lib.CovaHipError):
+        run_kernel(np.zeros((s[-1], 17), np.float32), lb, s, 17)                 # NC <= 16
+
+
+# ---------------------------------------------------------------- the split of the trainer tests
+CFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8,
+           n_additional_feat=0, drop_prob=0.2)
+CS = 6
+
+
+def page_set(P=15, img=96, seed=4):
+    """The construction of tests/test_sampling_gpu.py's page_set."""
+    rs = np.random.RandomState(seed)
+    u8 = rs.randint(0, 256, (P, img, img, 3)).astype(np.uint8)
+    rows = []
+    for _ in range(P):
+        n = int(rs.randint(11, 40))
+        wh = rs.uniform(6, 40, (n, 2))
+        xy = rs.uniform(0, 1, (n, 2)) * (img - wh)
+        lab = np.zeros((n, 1))
+        lab[rs.permutation(n)[:3], 0] = [1, 2, 3]
+        rows.append(np.concatenate([xy, wh, lab], 1).astype(np.float32))
+    return u8, rows
+
+
+def seeded(seed=77):
+    return weights.seeded_state_dict(seed, logit_gain=2.0, **{k: v for k, v in CFG.items() if k != "drop_prob"})
+
+
+@functools.lru_cache(maxsize=None)
+def split37():
+    """37 pages and the CPU oracle's tables, margins and logit scale (O.collate_reference + O.forward at batch 10)."""
+    u8, rows = page_set(P=37, seed=4)
+    sd = seeded()
+    ranks, margin, scale = [], [], 0.0
+    for s in range(0, 37, 10):
+        b = O.collate_reference(u8[s:s + 10], rows[s:s + 10], CS)
+        logits = O.forward(sd, b["images"], b["bboxes"], b["additional_feats"], b["context_indices"], CFG, False)
+        logits = logits.detach().numpy()
+        start = np.concatenate([[0], np.cumsum([r.shape[0] for r in rows[s:s + 10]])])
+        ranks.append(EO.page_ranks(logits, b["labels"].numpy(), start, 4)[0])
+        margin.append(EO.margins(logits, b["labels"].numpy(), start, 4))
+        scale = max(scale, float(np.abs(logits).max()))
+    return u8, rows, np.concatenate(ranks), np.concatenate(margin), scale
+
+
+def assert_ranks_equal_where_decided(got, ref, margin, scale):
+    """The project's rule for integer outputs: exact where the margin exceeds ten times the 1e-4 forward tolerance; at
+    most 5 % of the decisions may be left out."""
+    decided = margin > 1e-3 * scale
+    left_out = int((~decided).sum())
+    print("near-ties left out: %d of %d; ranks differing among them: %d"
+          % (left_out, decided.size, int((got != ref)[~decided].sum())))
+    assert left_out <= 0.05 * decided.size
+    assert np.array_equal(got[decided], ref[decided])
+
+
+def test_evaluate_split_equals_the_per_batch_route():
+    u8, rows = page_set(P=37, seed=4)
+    ds = DeviceDataset(u8, rows, CS, DEV)
+    tr = HotPathTrainer(CFG, seeded(), DEV)
+    rep = evaluate_split(tr, ds)
+    assert rep.evaluated.all() and rep.unlabelled.tolist() == [0, 0, 0, 0] and rep.loss is None
+    assert rep.img_ids.tolist() == ds.img_ids.tolist()
+    for k in (1, 3):
+        hits, first = [], []
+        for batch in ds.batches(10):
+            topk, ok = tr.evaluate(batch, batch["page_start"], k=k)
+            hits.append(ok.cpu().numpy())
+            first.append(topk[:, 1:, 0].cpu().numpy())
+        assert np.array_equal(rep.hits(k), np.concatenate(hits))
+        assert np.array_equal(rep.top1, np.concatenate(first))
+    assert 0 < rep.hits(3).sum() and not rep.hits(1).all()
+    again = evaluate_split(tr, ds, batch_size=7, prefetch=False)                   # another batch size: same pages
+    assert again.evaluated.all()
+
+
+def test_evaluate_split_against_the_cpu_oracle():
+    u8, rows, ref, margin, scale = split37()
+    rep = evaluate_split(HotPathTrainer(CFG, seeded(), DEV), DeviceDataset(u8, rows, CS, DEV))
+    assert_ranks_equal_where_decided(rep.ranks, ref, margin, scale)
+    ref_rep, decided = EvalReport(ref), margin > 1e-3 * scale
+    for k in (1, 3):
+        print("k = %d: hit / miss decisions differing from the oracle: %d" % (k, int((rep.hits(k) != ref_rep.hits(k)).sum())))
+        assert np.array_equal(rep.hits(k)[decided], ref_rep.hits(k)[decided])
+
+
+def test_rank_shards_merge_to_the_single_rank_tables():
+    u8, rows, _, margin, scale = split37()
+    ds, tr = DeviceDataset(u8, rows, CS, DEV), HotPathTrainer(CFG, seeded(), DEV)
+    whole = evaluate_split(tr, ds)
+    parts = [evaluate_split(tr, ds, rank=r, world_size=2, merge=False) for r in (0, 1)]
+    assert parts[0].evaluated.tolist() == [p < 19 for p in range(37)]
+    assert parts[1].evaluated.tolist() == [p >= 19 for p in range(37)]
+    merged = EvalReport.merge(parts)
+    assert merged.evaluated.all()
+    assert_ranks_equal_where_decided(merged.ranks, whole.ranks, margin, scale)
+    few = DeviceDataset(u8[:2], rows[:2], CS, DEV)                                 # fewer pages than ranks
+    parts = [evaluate_split(tr, few, rank=r, world_size=3, merge=False) for r in range(3)]
+    assert [int(p.evaluated.sum()) for p in parts] == [1, 1, 0]
+    decided = margin[:2] > 1e-3 * scale
+    assert np.array_equal(EvalReport.merge(parts).ranks[decided], whole.ranks[:2][decided])
+
+
+def refuse_host_reads(monkeypatch, allowed):
+    """Tensor.cpu / item / numpy / tolist raise unless ``allowed[0]`` > 0 -> the originals."""
+    orig = {n: getattr(torch.Tensor, n) for n in ("cpu", "item", "numpy", "tolist")}
+
+    def guard(name):
+        def f(self, *a, **kw):
+            if allowed[0] <= 0 and (name != "numpy" or self.is_cuda):
+                raise AssertionError("host read (%s) where none is allowed" % name)
+            return orig[name](self, *a, **kw)
+        return f
+    for n in orig:
+        monkeypatch.setattr(torch.Tensor, n, guard(n))
+    return orig
+
+
+def allowing(fn, allowed, calls=None):
+    def f(*a, **kw):
+        allowed[0] += 1
+        if calls is not None:
+            calls.append(1)
+        try:
+            return fn(*a, **kw)
+        finally:
+            allowed[0] -= 1
+    return f
+
+
+@pytest.mark.parametrize("with_loss", [False, True])
+def test_evaluate_split_reads_back_once(monkeypatch, with_loss):
+    u8, rows = page_set(P=23, seed=6)
+    ds, tr = DeviceDataset(u8, rows, CS, DEV), HotPathTrainer(CFG, seeded(), DEV)
+    ref = evaluate_split(tr, ds, with_loss=with_loss)
+    allowed, copies = [0], []
+    refuse_host_reads(monkeypatch, allowed)
+    monkeypatch.setattr(evaluation, "_read_tables", allowing(evaluation._read_tables, allowed, copies))
+    with pytest.raises(AssertionError, match="host read"):
+        torch.zeros(1, device=DEV).item()
+    for prefetch in (True, False):
+        del copies[:]
+        rep = evaluate_split(tr, ds, with_loss=with_loss, prefetch=prefetch)
+        assert len(copies) == 1
+        assert np.array_equal(rep.ranks, ref.ranks) and np.array_equal(rep.top1, ref.top1)
+        assert rep.loss == ref.loss
+
+
+@pytest.mark.parametrize("options", [{}, dict(class_weight=[0.2, 1.0, 2.0, 1.5], label_smoothing=0.1, loss_reduction="mean")])
+def test_with_loss_gives_the_validation_loss_and_confusion(options):
+    u8, rows = page_set(P=23, seed=6)
+    ds = DeviceDataset(u8, rows, CS, DEV)
+    tr = HotPathTrainer(CFG, seeded(), DEV, track_metrics=True, **options)
+    rep = evaluate_split(tr, ds, with_loss=True)
+    assert int(tr.metrics.buf.abs().sum()) == 0                                   # trainer.metrics is not touched
+    conf = np.zeros((4, 4), dtype=np.int64)
+    total, weight = 0.0, 0.0
+    w = np.asarray(options.get("class_weight", [1.0] * 4))
+    for batch in ds.batches(10):
+        _, pred = tr.predict(batch)
+        lab = batch["labels"].cpu().numpy()
+        np.add.at(conf, (lab, pred.cpu().numpy()), 1)
+        bw = float(w[lab].sum())
+        total += float(tr.loss(batch)) * (bw if options else 1.0)                 # "mean": the batch's loss is per weight
+        weight += bw
+    ref = total / weight if options else total
+    print("validation loss %.9g, sum over batches %.9g" % (rep.loss, ref))
+    assert abs(rep.loss - ref) <= 2e-4 * abs(ref)
+    assert np.array_equal(rep.confusion, conf) and rep.metrics["kept"] == conf.sum() == sum(r.shape[0] for r in rows)
+
+
+# ---------------------------------------------------------------- fit
+def hand_loop(tr, train, val, n_epochs, bs, sf, seed, interval, schedule, k):
+    """fit written out from train_step, metrics.read and evaluate_split."""
+    base = [g["lr"] for g in tr.param_groups]
+    best, best_state, best_epoch, history = 0.0, None, None, []
+    tr.metrics.reset()
+    for epoch in range(1, n_epochs + 1):
+        for batch in train.batches(bs, shuffle=True, sampling_fraction=sf, seed=seed, epoch=epoch):
+            tr.train_step(batch)
+        m = tr.metrics.read()
+        tr.metrics.reset()
+        rec = dict(loss=m["loss_numerator"] / m["kept"], accuracy=100.0 * np.trace(m["confusion"]) / m["kept"],
+                   boxes=m["kept"], eval_acc=None)
+        history.append(rec)
+        if epoch == 1 or epoch % interval == 0 or epoch == n_epochs:
+            rec["eval_acc"] = float(evaluate_split(tr, val).class_acc(k)[1:].mean())
+            if rec["eval_acc"] > best:
+                best, best_epoch = rec["eval_acc"], epoch
+                best_state = tr.state_dict()
+        for g, lr in zip(tr.param_groups, base):
+            g["lr"] = lr * schedule(epoch)
+    return best, best_epoch, best_state, history
+
+
+def test_fit_equals_the_loop_written_out_by_hand(tmp_path):
+    u8, rows = page_set()
+    v8, vrows = page_set(P=37, seed=9)                  # 111 decisions at k = 3: some hit from the first epoch on
+    train, val = DeviceDataset(u8, rows, CS, DEV), DeviceDataset(v8, vrows, CS, DEV)
+    sd = seeded()
+    kw = dict(lr=2e-3, track_metrics=True)
+    a, b, c = (HotPathTrainer(CFG, sd, DEV, **kw) for _ in range(3))
+    log, ckpt = str(tmp_path / "log.txt"), str(tmp_path / "best.pth")
+    res = fit(a, train, val, 4, 3, sampling_fraction=0.9, seed=12, eval_interval=2, lr_schedule=step_lr(2, 0.5),
+              checkpoint=ckpt, log_file=log, k=3)
+    best, best_epoch, best_state, history = hand_loop(b, train, val, 4, 3, 0.9, 12, 2, step_lr(2, 0.5), 3)
+    assert res.epochs_run == 4 and not res.stopped_early and len(res.history) == 4
+    assert (res.best_eval_acc, res.best_epoch) == (best, best_epoch) and best_epoch is not None
+    for got, ref in zip(res.history, history):
+        for key in ("loss", "accuracy", "boxes", "eval_acc"):
+            assert got[key] == ref[key], (got["epoch"], key)
+    assert [h["eval_acc"] is not None for h in res.history] == [True, True, False, True]
+    assert [h["lr"][0] for h in res.history] == [2e-3, 2e-3, 1e-3, 1e-3]
+    assert history[0]["boxes"] < sum(r.shape[0] for r in rows)                     # background boxes were sampled
+    # the reloaded state is the saved best, and the trajectory behind it (Adam moments, step count) is the hand loop's
+    saved, now = torch.load(ckpt, map_location=DEV), a.state_dict()
+    assert list(saved) == list(now) == list(best_state)
+    for key in now:
+        assert torch.equal(now[key], saved[key]) and torch.equal(now[key], best_state[key]), key
+    assert torch.equal(a.exp_avg, b.exp_avg) and torch.equal(a.exp_avg_sq, b.exp_avg_sq) and a.step_count == b.step_count
+    assert not torch.equal(now["convnet.0.weight"], sd["convnet.0.weight"].to(DEV))
+    # the log carries those values in the reference's lines
+    lines = open(log).read().splitlines()
+    epochs = [l for l in lines if l.startswith("Epoch:")]
+    assert len(epochs) == 4
+    for line, h in zip(epochs, res.history):
+        m = re.fullmatch(r"Epoch: ( ?\d+)  Loss: (\d+\.\d{4})  Accuracy: (\d+\.\d\d)%  \((\d+\.\d\d)s\)", line)
+        assert m and int(m.group(1)) == h["epoch"]
+        assert m.group(2) == "%.4f" % h["loss"] and m.group(3) == "%.2f" % h["accuracy"]
+    vals = [l for l in lines if l.startswith("[VAL]")]
+    assert [re.match(r"\[VAL\] Avg_class_Accuracy: (\d+\.\d\d)% \(", l).group(1) for l in vals] == \
+        ["%.2f" % h["eval_acc"] for h in res.history if h["eval_acc"] is not None]
+    assert sum(l.startswith(("Price top-3-Acc", "Title top-3-Acc", "Image top-3-Acc")) for l in lines) == 9
+    # a second identical run (the best kept in memory this time)
+    res2 = fit(c, train, val, 4, 3, sampling_fraction=0.9, seed=12, eval_interval=2, lr_schedule=step_lr(2, 0.5), k=3)
+    assert [(h["loss"], h["accuracy"], h["boxes"], h["eval_acc"]) for h in res2.history] == \
+        [(h["loss"], h["accuracy"], h["boxes"], h["eval_acc"]) for h in res.history]
+    for key, v in c.state_dict().items():
+        assert torch.equal(v, now[key]), key
+
+
+def test_fit_decisions_follow_its_own_history_and_the_schedule_skips_the_stopping_epoch():
+    u8, rows = page_set(P=6)
+    ds = DeviceDataset(u8, rows, CS, DEV)
+    tr = HotPathTrainer(CFG, seeded(), DEV, track_metrics=True)
+    scheduled = []
+    res = fit(tr, ds, ds, 8, 3, sampling_fraction=1.0, eval_interval=1, patience=1, k=3,
+              lr_schedule=lambda e: scheduled.append(e) or 1.0)
+    ctl = evaluation.EpochController(8, 1, 1)                   # whatever the accuracies were, the decisions are these
+    for h in res.history:
+        assert h["eval_acc"] is not None and 0.0 <= h["eval_acc"] <= 100.0
+        best, stop = ctl.update(h["epoch"], h["eval_acc"])
+        assert best == h["is_best"] and stop == (res.stopped_early and h["epoch"] == res.epochs_run)
+    assert (res.best_eval_acc, res.best_epoch, res.epochs_run) == (ctl.best_eval_acc, ctl.best_epoch, len(res.history))
+    assert scheduled == list(range(1, res.epochs_run + (0 if res.stopped_early else 1)))
+    assert int(tr.metrics.buf.abs().sum()) == 0                                    # read and reset every epoch
+
+
+def test_fit_step_loop_reads_nothing_back(monkeypatch):
+    u8, rows = page_set(P=9)
+    ds = DeviceDataset(u8, rows, CS, DEV)
+    tr = HotPathTrainer(CFG, seeded(), DEV, track_metrics=True)
+    allowed, reads, evals = [0], [], []
+    refuse_host_reads(monkeypatch, allowed)
+    monkeypatch.setattr(LossMetrics, "read", allowing(LossMetrics.read, allowed, reads))
+    monkeypatch.setattr(evaluation, "evaluate_split", allowing(evaluation.evaluate_split, allowed, evals))
+    res = fit(tr, ds, ds, 3, 2, sampling_fraction=1.0, seed=3, eval_interval=2)
+    assert res.epochs_run == 3 and len(reads) == 3 and len(evals) == 3             # epochs 1, 2 and the last
+    with pytest.raises(AssertionError, match="host read"):                         # and the guard does bite
+        fit(tr, ds, ds, 1, 2, sampling_fraction=0.9, seed=3)
