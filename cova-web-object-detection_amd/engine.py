@@ -129,20 +129,26 @@ def _check(t, dtype=torch.float32):
     return t
 
 
-def check_batch(cfg, images, bboxes, additional_feats, context_indices, training):
+def check_batch(cfg, images, bboxes, additional_feats, context_indices, training, visual_feats=None):
     """Shape contract of CoVA.forward (models.py:94-122), checked on the host before any launch (the
     kernels take raw pointers): the errors torch raises inside the reference's forward for malformed
     input -- conv2d's channel check, the [N,5] roi layout, the cat/Linear width mismatch, gather
     broadcasting, BatchNorm1d's train-mode batch-size check -- with the same exception types.
     Index VALUES are not read here (that would cost a device sync): ids outside [0, N) are treated
-    as pads by the kernels, memory-safe; the reference raises IndexError for them on CPU."""
-    if images.dim() != 4 or images.shape[1] != 3:
+    as pads by the kernels, memory-safe; the reference raises IndexError for them on CPU.
+    With ``visual_feats`` (cached RoI features, check_visual_feats) ``images`` may be None."""
+    if images is None:
+        if visual_feats is None:
+            raise RuntimeError("a batch without images needs cached visual features (visual_feats)")
+    elif images.dim() != 4 or images.shape[1] != 3:
         raise RuntimeError("expected images [B, 3, H, W] (conv1 has 3 input channels, models.py:49), got %s"
                            % (tuple(images.shape),))
     if bboxes.dim() != 2 or bboxes.shape[1] != 5:
         raise RuntimeError("expected bboxes [N, 5] = [batch_idx, x1, y1, x2, y2] (models.py:97), got %s"
                            % (tuple(bboxes.shape),))
     N, A = bboxes.shape[0], cfg["n_additional_feat"]
+    if visual_feats is not None:
+        check_visual_feats(cfg, visual_feats, N)
     if additional_feats.dim() != 2 or tuple(additional_feats.shape) != (N, A):
         raise RuntimeError("expected additional_feats [%d, %d] (n_additional_feat, models.py:98,110), got %s"
                            % (N, A, tuple(additional_feats.shape)))
@@ -1460,10 +1466,16 @@ def decoder_bwd(sv, dlogits, params, gout=None):
 # ------------------------------------------------------------------------------- whole model
 @on_device_of(3)
 def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_indices, training,
-              seeds=(0, 0), masks=None, save=True, plan=None):
+              seeds=(0, 0), masks=None, save=True, plan=None, visual_feats=None):
     """CoVA.forward (models.py:94-122) -> (logits [N,n_classes], saved-for-backward or None).
     ``training``: a bool (whole model) or per-layer modes {BatchNorm prefix / Dropout name: bool} (is_train).
-    ``plan`` (grad_plan, with ``save``): without its "convstack" stage the conv stack keeps no activations."""
+    ``plan`` (grad_plan, with ``save``): without its "convstack" stage the conv stack keeps no activations.
+    ``visual_feats`` = (table [R, n_vis], row_ids int32 [N]) (features.FeatureCache): the conv stack and the RoI op are
+    skipped and cova_feat_rows_gather fills comb[:, :n_vis]; ``images`` may be None; with ``save`` the plan must lack
+    "convstack" (nothing is kept to run that backward from)."""
+    if visual_feats is not None:
+        return _model_fwd_cached(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks,
+                                 save, plan, visual_feats)
     N = bboxes.shape[0]
     PH, PW = cfg["roi_output_size"]
     n_vis = (C256 if is_bottleneck(params) else C128 if has_layer2(params) else C64) * PH * PW
@@ -1482,6 +1494,12 @@ def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_in
                                  cfg.get("roi_aligned", False), comb, T)
     else:
         sv["roi"] = roipool_fwd(feat, bboxes, (PH, PW), scale, comb, T)
+    return _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks, save, sv)
+
+
+def _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks, save, sv):
+    """Everything behind the visual columns of ``sv["comb"]``: positional encoder, additional features, GAT, decoder."""
+    N, F, D, T, n_vis, Hd, A, comb = (sv[k] for k in ("N", "F", "D", "T", "n_vis", "Hd", "A", "comb"))
     if Hd > 0:
         sv["bbox"] = bbox_fwd(bboxes, params, buffers, training, comb[:, n_vis:], T)
     if A > 0:
@@ -1495,6 +1513,49 @@ def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_in
     logits, sv["dec"] = decoder_fwd(comb, N, T, params, buffers, training, cfg["drop_prob"], seeds,
                                     masks)
     return logits, (sv if save else None)
+
+
+def check_visual_feats(cfg, visual_feats, N):
+    """Host-side contract of (table, row_ids): a dense f32 table [R, n_vis] and one int32 row id per box, on one device.
+    Id VALUES are not read (a device sync); cova_feat_rows_gather writes zeros for an id outside [0, R)."""
+    try:
+        table, row_ids = visual_feats
+    except (TypeError, ValueError):
+        raise ValueError("visual_feats must be (table [R, n_vis], row_ids int32 [N])")
+    n_vis = backbone_feat(cfg)
+    if not (torch.is_tensor(table) and table.dim() == 2 and table.shape[1] == n_vis and table.dtype == torch.float32
+            and table.is_contiguous()):
+        raise ValueError("visual_feats: the table must be a dense float32 [R, %d] tensor (n_vis of this configuration), "
+                         "got %s" % (n_vis, (tuple(table.shape), table.dtype) if torch.is_tensor(table) else type(table)))
+    if not (torch.is_tensor(row_ids) and row_ids.dim() == 1 and row_ids.dtype == torch.int32 and row_ids.is_contiguous()):
+        raise ValueError("visual_feats: row_ids must be a contiguous int32 vector")
+    if row_ids.shape[0] != N:
+        raise ValueError("visual_feats: %d row ids for %d boxes" % (row_ids.shape[0], N))
+    if table.shape[0] == 0 and N > 0:
+        raise ValueError("visual_feats: %d boxes and an empty table" % N)
+    if row_ids.device != table.device:
+        raise ValueError("visual_feats: table on %s, row_ids on %s" % (table.device, row_ids.device))
+    return table, row_ids
+
+
+@on_device_of(3)
+def _model_fwd_cached(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks, save, plan,
+                      visual_feats):
+    """model_fwd with the visual columns taken from a feature table: no conv stack, no RoI op."""
+    N = bboxes.shape[0]
+    table, row_ids = check_visual_feats(cfg, visual_feats, N)
+    if save and (plan is None or "convstack" in plan):
+        raise ValueError("model_fwd: cached visual features keep nothing for the conv-stack backward; the gradient plan "
+                         "must leave out 'convstack' (a frozen conv stack)")
+    n_vis = table.shape[1]
+    Hd, A = cfg["bbox_hidden_dim"], cfg["n_additional_feat"]
+    F = n_vis + Hd + A
+    D = cfg["hidden_dim"] if cfg["use_context"] else 0
+    T = F + D
+    comb = _empty((N, T), bboxes)
+    sv = dict(cfg=cfg, N=N, F=F, D=D, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=None, roi=None, comb=comb)
+    call("cova_feat_rows_gather", table, table.shape[0], n_vis, row_ids, N, comb, T)
+    return _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks, save, sv)
 
 
 @on_device_of(1)

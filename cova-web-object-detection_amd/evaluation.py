@@ -172,13 +172,17 @@ def _read_tables(blob):
 
 @torch.no_grad()
 def evaluate_split(trainer, dataset, batch_size=10, rank=0, world_size=1, group=None, with_loss=False, prefetch=True,
-                   merge=True):
+                   merge=True, features=None):
     """Evaluate every page of ``dataset`` (a DeviceDataset) in dataset order, nothing shuffled, sampled or dropped
     (datasets.py:227-258) -> EvalReport.  Under data parallelism every rank calls this with its ``rank``; the tables are
     merged by one all_reduce(MAX) (``merge=False`` leaves a rank's own tables: other ranks' pages stay -2, see
     EvalReport.merge).  ``with_loss`` also runs cova_ce_loss_fwd with the trainer's criterion options into counters of the
-    report's own (``trainer.metrics`` is not touched).  No host read before the copy at the end."""
+    report's own (``trainer.metrics`` is not touched).  No host read before the copy at the end.
+    ``features`` (a features.FeatureCache of this trainer's conv stack over ``dataset``): checked once on entry (one
+    host read), then every batch takes its visual rows from the table: no page gather, conv stack or RoI op."""
     start = time.time()
+    if features is not None:
+        features.check(trainer, dataset)
     dev, nc, P = trainer.device, int(trainer.cfg["n_classes"]), len(dataset)
     if nc < 2:
         raise ValueError("evaluation needs at least one non-background class")
@@ -196,7 +200,7 @@ def evaluate_split(trainer, dataset, batch_size=10, rank=0, world_size=1, group=
         opts = trainer._criterion() or engine.check_loss_options(nc)
     pos = 0
     for ids, batch in zip(plan, dataset.batches(batch_size, order=np.arange(lo, hi, dtype=np.int64), world_size=1,
-                                                prefetch=prefetch)):
+                                                prefetch=prefetch, features=features)):
         B = int(ids.shape[0])
         logits, _ = trainer.predict(batch)
         engine.call("cova_eval_page_ranks", logits, batch["labels"], batch["page_start"], ids32[pos:pos + B], B, nc, P,
@@ -269,7 +273,8 @@ def _log(log_file, lines):
 
 
 def fit(trainer, train_set, val_set, n_epochs, batch_size, sampling_fraction=0.9, seed=0, eval_interval=3, patience=7,
-        lr_schedule=None, checkpoint=None, log_file=None, k=1, rank=0, world_size=1, group=None, class_names=None):
+        lr_schedule=None, checkpoint=None, log_file=None, k=1, rank=0, world_size=1, group=None, class_names=None,
+        train_features=None, val_features=None):
     """train.train_model: ``n_epochs`` epochs of ``trainer.train_step`` over ``train_set`` (shuffled, background boxes
     sampled), ``evaluate_split`` on ``val_set`` at epoch 1, every ``eval_interval`` epochs and at the last epoch,
     save-best / patience / reload-best -> FitResult.
@@ -279,10 +284,17 @@ def fit(trainer, train_set, val_set, n_epochs, batch_size, sampling_fraction=0.9
     ``lr_schedule``: epoch -> factor on every group's lr as it was on entry, applied after each completed epoch and not
     after the one that stops early (scheduler.step(), train.py:91).  Rank 0 appends the reference's lines to
     ``log_file`` and keeps the best state_dict (``torch.save`` to ``checkpoint``, else a clone in memory); the best is
-    reloaded at the end on every rank.  Every rank sees the same merged tables and takes the same decisions."""
+    reloaded at the end on every rank.  Every rank sees the same merged tables and takes the same decisions.
+    ``train_features`` / ``val_features`` (features.FeatureCache over ``train_set`` / ``val_set``, for a trainer whose
+    conv stack is frozen with its BatchNorms in eval mode): checked once on entry; the steps and the evaluations then
+    take the visual rows from the tables."""
     if trainer.metrics is None:
         raise ValueError("fit needs a trainer built with track_metrics=True (the epoch's loss and accuracy are read "
                          "from trainer.metrics)")
+    if train_features is not None:
+        train_features.check(trainer, train_set)
+    if val_features is not None:
+        val_features.check(trainer, val_set)
     ctl = EpochController(n_epochs, eval_interval, patience)
     nc = int(trainer.cfg["n_classes"])
     names = _names(class_names, nc)
@@ -292,7 +304,7 @@ def fit(trainer, train_set, val_set, n_epochs, batch_size, sampling_fraction=0.9
     for epoch in range(1, ctl.n_epochs + 1):
         start = time.time()
         for batch in train_set.batches(batch_size, shuffle=True, sampling_fraction=sampling_fraction, seed=seed,
-                                       epoch=epoch, rank=rank, world_size=world_size):
+                                       epoch=epoch, rank=rank, world_size=world_size, features=train_features):
             trainer.train_step(batch)
         m = trainer.metrics.read()
         trainer.metrics.reset()
@@ -307,7 +319,8 @@ def fit(trainer, train_set, val_set, n_epochs, batch_size, sampling_fraction=0.9
         history.append(rec)
         epochs_run = epoch
         if ctl.should_evaluate(epoch):
-            report = evaluate_split(trainer, val_set, rank=rank, world_size=world_size, group=group)
+            report = evaluate_split(trainer, val_set, rank=rank, world_size=world_size, group=group,
+                                    features=val_features)
             rec["class_acc"] = report.class_acc(k)
             rec["eval_acc"] = float(rec["class_acc"][1:].mean())
             if rank == 0:

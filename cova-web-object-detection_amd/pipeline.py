@@ -67,9 +67,11 @@ def _read_kept_total(out_offs, B):
     return int(out_offs[B].item())
 
 
-def _sample_and_collate(dev, cs, A, rows_d, addl_d, offs_d, starts_d, pid_d, keep_d, keys_d, B, N, sseed, n_out=None):
+def _sample_and_collate(dev, cs, A, rows_d, addl_d, offs_d, starts_d, pid_d, keep_d, keys_d, B, N, sseed, n_out=None,
+                        want_sel=False):
     """cova_sample_boxes + cova_collate_selected on the current stream.  ``n_out`` is the number of kept boxes when the
-    host knows it (everything kept); None reads it back from the device: the one 4-byte host read of a sampled batch."""
+    host knows it (everything kept); None reads it back from the device: the one 4-byte host read of a sampled batch.
+    ``want_sel``: also return the kept SOURCE row ids (int32 [n_out]) under "sel"."""
     ws = torch.empty((N + B,), dtype=torch.int32, device=dev)
     sel = torch.empty((N,), dtype=torch.int32, device=dev)
     out_offs = torch.empty((B + 1,), dtype=torch.int32, device=dev)
@@ -83,8 +85,11 @@ def _sample_and_collate(dev, cs, A, rows_d, addl_d, offs_d, starts_d, pid_d, kee
     addl = torch.empty((n_out, A), dtype=torch.float32, device=dev)
     call("cova_collate_selected", rows_d, sel, out_offs, B, n_out, cs, bboxes, labels, ctx if K else None,
          addl_d if A else None, A, addl if A else None)
-    return dict(bboxes=bboxes, additional_feats=addl, context_indices=ctx, labels=labels,
-                page_start=out_offs.to(torch.int64))
+    out = dict(bboxes=bboxes, additional_feats=addl, context_indices=ctx, labels=labels,
+               page_start=out_offs.to(torch.int64))
+    if want_sel:
+        out["sel"] = sel[:n_out]
+    return out
 
 
 class DeviceCollate:
@@ -280,16 +285,20 @@ class DeviceDataset:
         return self.P
 
     def batches(self, batch_size, shuffle=False, sampling_fraction=1.0, seed=0, epoch=0, drop_last=False, rank=0,
-                world_size=1, order=None, prefetch=True):
+                world_size=1, order=None, prefetch=True, features=None):
         """One epoch of batches (a generator).  Train: ``shuffle=True, sampling_fraction=sf``; val / test: batch 10,
         no shuffle, no sampling (datasets.py:227-258).  With ``prefetch`` batch i+1 is assembled on a side stream while
         the consumer works on batch i.  With ``sampling_fraction == 1`` there is no host read at all; otherwise one
-        4-byte read per batch (the number of kept boxes), on the side stream."""
+        4-byte read per batch (the number of kept boxes), on the side stream.
+        ``features`` (a features.FeatureCache built over this dataset): the pages are not gathered; the batch has no
+        ``images`` and carries ``visual_feats`` = (the cache's table, the kept boxes' row ids) instead."""
         sf = _check_fraction(sampling_fraction)
+        if features is not None:
+            features.check_dataset(self)
         plan = epoch_plan(self.P, batch_size, shuffle, seed, epoch, drop_last, rank, world_size, order)
-        return self._iterate(plan, sf, stream_seed(seed, epoch), bool(prefetch))
+        return self._iterate(plan, sf, stream_seed(seed, epoch), bool(prefetch), features)
 
-    def _iterate(self, plan, sf, sseed, prefetch):
+    def _iterate(self, plan, sf, sseed, prefetch, features=None):
         if not plan:
             return
         dev = self.device
@@ -310,11 +319,15 @@ class DeviceDataset:
             pos, B, N = where[step]
             ids_d, offs_d = table[pos:pos + B], table[pos + B:pos + 2 * B + 1]
             starts_d, keep_d = table[pos + 2 * B + 1:pos + 3 * B + 1], table[pos + 3 * B + 1:pos + 4 * B + 1]
-            images = torch.empty((B, 3, self.H, self.W), dtype=torch.float32, device=dev)
-            call("cova_pages_u8_gather_f32", self.store, ids_d, self.P, B, self.H, self.W, images)
+            if features is None:
+                images = torch.empty((B, 3, self.H, self.W), dtype=torch.float32, device=dev)
+                call("cova_pages_u8_gather_f32", self.store, ids_d, self.P, B, self.H, self.W, images)
             out = _sample_and_collate(dev, self.cs, self.A, self.rows, self.addl, offs_d, starts_d, ids_d, keep_d, None,
-                                      B, N, sseed, n_out=N if sf == 1.0 else None)
-            out["images"] = images
+                                      B, N, sseed, n_out=N if sf == 1.0 else None, want_sel=features is not None)
+            if features is None:
+                out["images"] = images
+            else:       # the sampler's kept SOURCE row ids are the table's row ids (with sf == 1 it keeps every row)
+                out["visual_feats"] = (features.table, out.pop("sel"))
             out["page_ids"] = ids64[int(starts64[step]):int(starts64[step + 1])]
             out["img_ids"] = self.img_ids[plan[step]]
             return out
@@ -341,6 +354,8 @@ class DeviceDataset:
             for v in batch.values():
                 if torch.is_tensor(v):
                     v.record_stream(cur)         # allocated on the side stream, consumed on this one
+            if features is not None:
+                batch["visual_feats"][1].record_stream(cur)
             pending = preload(step + 1) if step + 1 < len(plan) else None
             yield batch
 

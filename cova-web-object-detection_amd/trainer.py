@@ -254,6 +254,18 @@ class HotPathTrainer:
                 runs.append([lo, hi])
         self._adam_runs = [tuple(r) for r in runs]
         self.conv_frozen = all(k in self.frozen for k in self.params if k.startswith("convnet."))
+        conv_bns = [k[:-len("running_mean")] for k in self.buffers if k.startswith("convnet.") and k.endswith("running_mean")]
+        self.conv_bn_eval = all(not engine.is_train(self.modes, p) for p in conv_bns)
+
+    def check_cached_features(self):
+        """Cached RoI features stand for a conv stack that no step changes: every ``convnet.`` parameter frozen and every
+        ``convnet.`` BatchNorm in eval mode (host flags, no device read)."""
+        if not self.conv_frozen:
+            raise ValueError("cached visual features need a frozen conv stack: build the trainer with "
+                             "frozen=('convnet.',) (a trainable convnet. parameter would leave the cache stale)")
+        if not self.conv_bn_eval:
+            raise ValueError("cached visual features need the conv stack's BatchNorms in eval mode: build the trainer "
+                             "with bn_eval=('convnet.',) (a train-mode BatchNorm normalises with batch statistics)")
 
     def _setup_optimizer(self, optimizer, momentum, dampening, nesterov, param_groups, max_grad_norm):
         """Resolve the parameter groups to merged runs of the flat bucket, once.  The default group (unclaimed trainable
@@ -507,23 +519,28 @@ class HotPathTrainer:
 
     def forward_backward(self, batch, masks=None):
         """Forward + criterion + backward into the flat gradient bucket.  Returns (loss, pred): the local CE sum, or
-        with criterion options the local sum ("sum") / the mean over the global batch ("mean")."""
+        with criterion options the local sum ("sum") / the mean over the global batch ("mean").  A batch with
+        ``visual_feats`` (DeviceDataset.batches(features=)) skips the conv stack and the RoI op; it raises ValueError
+        unless the conv stack is frozen with its BatchNorms in eval mode."""
         opts = self._criterion()
         # With SyncBN a one-box shard is legal (the statistics are over the whole batch, as torch.nn.SyncBatchNorm
         # accepts it): the train-mode "more than 1 value per channel" check then applies to the GLOBAL box count, which
         # _stat_sync has from its all-reduce -- every rank raises together instead of one rank leaving the others
         # blocked in a collective.
-        engine.check_batch(self.cfg, batch["images"], batch["bboxes"], batch["additional_feats"],
-                           batch["context_indices"], self.modes if not self.sync_bn else False)
+        vis = batch.get("visual_feats")
+        if vis is not None:
+            self.check_cached_features()
+        engine.check_batch(self.cfg, batch.get("images"), batch["bboxes"], batch["additional_feats"],
+                           batch["context_indices"], self.modes if not self.sync_bn else False, vis)
         self.step_count += 1
         base = (self.dropout_seed * 0x9E3779B1 + 2 * self.step_count) & 0xFFFFFFFFFFFF
         if self.sync_bn:
             engine.STAT_SYNC = self._stat_sync(batch)
         try:
-            logits, sv = engine.model_fwd(self.cfg, self.params, self.buffers, batch["images"],
+            logits, sv = engine.model_fwd(self.cfg, self.params, self.buffers, batch.get("images"),
                                           batch["bboxes"], batch["additional_feats"],
                                           batch["context_indices"], self.modes, (base, base + 1), masks,
-                                          plan=self.plan)
+                                          plan=self.plan, visual_feats=vis)
             if opts is None:
                 loss, dl, pred = engine.ce_sum(logits, batch["labels"])
             else:
@@ -541,7 +558,9 @@ class HotPathTrainer:
         """SyncBN bookkeeping of one step: whole-batch / local element-count ratios for the page-shaped
         (conv stack) and box-shaped (BatchNorm1d) statistics; one tiny all-reduce + host read."""
         import torch.distributed as dist
-        n_pages, n_boxes = int(batch["images"].shape[0]), int(batch["bboxes"].shape[0])      # host ints: no device read
+        images = batch.get("images")                                                           # host ints: no device read
+        n_pages = int(images.shape[0]) if images is not None else int(batch["page_start"].shape[0]) - 1
+        n_boxes = int(batch["bboxes"].shape[0])
         total = torch.tensor([n_pages, n_boxes], dtype=torch.float64, device=self.device)
         dist.all_reduce(total, op=dist.ReduceOp.SUM, group=self.group)
         tot = total.tolist()                                                                   # the step's one host read
@@ -665,12 +684,14 @@ class HotPathTrainer:
 
     @torch.no_grad()
     def predict(self, batch):
-        """Eval-mode forward (running statistics) -> (logits, per-box argmax)."""
-        engine.check_batch(self.cfg, batch["images"], batch["bboxes"], batch["additional_feats"],
-                           batch["context_indices"], False)
-        logits, _ = engine.model_fwd(self.cfg, self.params, self.buffers, batch["images"],
+        """Eval-mode forward (running statistics) -> (logits, per-box argmax).  A batch with ``visual_feats`` (cached RoI
+        features, features.FeatureCache) needs no images: the rows come from the table."""
+        vis = batch.get("visual_feats")
+        engine.check_batch(self.cfg, batch.get("images"), batch["bboxes"], batch["additional_feats"],
+                           batch["context_indices"], False, vis)
+        logits, _ = engine.model_fwd(self.cfg, self.params, self.buffers, batch.get("images"),
                                      batch["bboxes"], batch["additional_feats"],
-                                     batch["context_indices"], False, save=False)
+                                     batch["context_indices"], False, save=False, visual_feats=vis)
         _, _, pred = engine.ce_sum(logits, None, want_grad=False)
         return logits, pred
 

@@ -574,6 +574,17 @@ int cova_collate_selected(const float *rows, const int *sel, const int *out_offs
 int cova_attn_export_rows(const float *bboxes, const long long *ctx, const float *attn,
                           const long long *labels, int N, int K, float *out, void *stream);
 
+/* ---- cached RoI visual features (feat.hip; features.FeatureCache) ----
+ * out[g*ld_out + c] = table[row_ids[g]*C + c] for c < C: rows row_ids[0..N) (DEVICE int32, the SOURCE row ids `sel` of
+ * cova_sample_boxes) of a dense f32 table [R, C] into the first C columns of out (leading dimension ld_out >= C, e.g.
+ * comb[:, :n_vis] with ld_out = T).  Columns C..ld_out of out are not touched.  Row offsets into the table are 64-bit (the
+ * table may exceed 4 GiB).  A row id outside [0, R) writes a row of zeros (memory-safe and defined; the host refuses such
+ * ids where it knows them).  float4 loads and stores when C % 4 == 0, ld_out % 4 == 0 and both bases are 16-byte aligned,
+ * else a scalar path with the same bytes out (an odd T makes every row start of comb unaligned).  N == 0 returns without
+ * a launch.  One launch, no atomics, no workspace, capturable. */
+int cova_feat_rows_gather(const float *table /*[R,C] dense*/, long long R, int C, const int *row_ids /*DEVICE int32 [N]*/,
+                          int N, float *out, int ld_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
