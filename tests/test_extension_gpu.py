@@ -155,8 +155,13 @@ def test_linear_form_of_conv_bn_backward(R, pro):
         call("cova_conv1x1_vprod", d(v), d(act), d(aabc) if pro else None, 1 if pro else 0, out, ws, R)
     assert torch.equal(lin, lin2)                            # fixed reduction order
     P, G, S, SU = lin[:16384].view(256, 64), lin[16384:20480].view(64, 64), lin[20480:20544], lin[20544:]
-    close(P, v.double().t() @ a, 2e-5, "P")
-    close(G, a.t() @ a, 2e-5, "G")
+    # f32 error class, not a reduced-precision one: the yardstick is torch's f32 matmul of the same operands on the CPU
+    # (2 err + 2e-7, the form of test_conv1_bf16_split_error_class; about 0.5 - 1.0e-6) from R = 777 on; the operand
+    # pieces themselves are held exactly by tests/test_split_products_gpu.py
+    refP, refG, a32 = v.double().t() @ a, a.t() @ a, a.float()
+    rel = lambda got, ref: float((got.double() - ref).abs().max() / ref.abs().max())
+    close(P, refP, min(2e-5, 2.0 * rel(v.t() @ a32, refP) + 2e-7) if R >= 777 else 2e-5, "P")
+    close(G, refG, min(2e-5, 2.0 * rel(a32.t() @ a32, refG) + 2e-7) if R >= 777 else 2e-5, "G")
     close(S, a.sum(0), 2e-5, "S")
     close(SU, v.double().sum(0), 1e-4, "SU")
     if R < 2:
