@@ -13,6 +13,11 @@ shuffled, sampled, collated batches (``load_data``, datasets.py:193-265): a batc
 index (cova_pages_u8_gather_f32) plus the same sampling and collation kernels; ``epoch_plan`` is the
 host-side order of an epoch.
 
+With ``spatial_k > 0`` (both classes) the context table is ``[N, 2*context_size + spatial_k]``: the DOM-order window plus
+the ``spatial_k`` nearest other boxes of the page, built by one cova_context_knn launch over the collated (kept) boxes --
+after the sampling, on the stream that collated them.  ``DeviceDataset.with_context`` gives the same resident split another
+graph.
+
 ``attention_rows`` is the dump of extract_attn_wts_and_visualize.py:104-135.
 """
 import numpy as np
@@ -62,29 +67,51 @@ def _check_rows(r, where):
     return a
 
 
+def _check_graph(context_size, spatial_k):
+    """(context_size, spatial_k) as ints; ValueError for a negative spatial_k or a table wider than the GAT kernels take."""
+    cs, ks = int(context_size), int(spatial_k)
+    if ks < 0:
+        raise ValueError("spatial_k must be >= 0, got %r" % (spatial_k,))
+    if ks and 2 * cs + ks > engine.GAT_MAX_K:
+        raise ValueError("context table of width 2*%d + %d = %d: the graph attention kernels take at most %d neighbour slots"
+                         % (cs, ks, 2 * cs + ks, engine.GAT_MAX_K))
+    return cs, ks
+
+
+def _context_knn(bboxes, offs_d, B, cs, ks):
+    """cova_context_knn on the current stream: the [N, 2*cs + ks] table of collated boxes (page offsets ``offs_d``)."""
+    n = int(bboxes.shape[0])
+    ctx = torch.empty((n, 2 * cs + ks), dtype=torch.int64, device=bboxes.device)
+    call("cova_context_knn", bboxes, offs_d, B, n, cs, ks, ctx)
+    return ctx
+
+
 def _read_kept_total(out_offs, B):
     """The host read of a sampled batch: 4 bytes, after the two sampling launches on the current stream."""
     return int(out_offs[B].item())
 
 
 def _sample_and_collate(dev, cs, A, rows_d, addl_d, offs_d, starts_d, pid_d, keep_d, keys_d, B, N, sseed, n_out=None,
-                        want_sel=False):
+                        want_sel=False, ks=0):
     """cova_sample_boxes + cova_collate_selected on the current stream.  ``n_out`` is the number of kept boxes when the
     host knows it (everything kept); None reads it back from the device: the one 4-byte host read of a sampled batch.
-    ``want_sel``: also return the kept SOURCE row ids (int32 [n_out]) under "sel"."""
+    ``want_sel``: also return the kept SOURCE row ids (int32 [n_out]) under "sel".  ``ks > 0``: the collation writes no
+    window; cova_context_knn builds the whole [n_out, 2*cs + ks] table over the kept boxes."""
     ws = torch.empty((N + B,), dtype=torch.int32, device=dev)
     sel = torch.empty((N,), dtype=torch.int32, device=dev)
     out_offs = torch.empty((B + 1,), dtype=torch.int32, device=dev)
     call("cova_sample_boxes", rows_d, offs_d, starts_d, pid_d, keep_d, B, N, keys_d, sseed, ws, sel, out_offs)
     if n_out is None:
         n_out = _read_kept_total(out_offs, B)
-    K = 2 * cs
+    K = 0 if ks else 2 * cs
     bboxes = torch.empty((n_out, 5), dtype=torch.float32, device=dev)
     labels = torch.empty((n_out,), dtype=torch.int64, device=dev)
     ctx = torch.empty((n_out, K) if K else (0, 0), dtype=torch.int64, device=dev)   # datasets.py:130
     addl = torch.empty((n_out, A), dtype=torch.float32, device=dev)
-    call("cova_collate_selected", rows_d, sel, out_offs, B, n_out, cs, bboxes, labels, ctx if K else None,
+    call("cova_collate_selected", rows_d, sel, out_offs, B, n_out, K // 2, bboxes, labels, ctx if K else None,
          addl_d if A else None, A, addl if A else None)
+    if ks:
+        ctx = _context_knn(bboxes, out_offs, B, cs, ks)
     out = dict(bboxes=bboxes, additional_feats=addl, context_indices=ctx, labels=labels,
                page_start=out_offs.to(torch.int64))
     if want_sel:
@@ -93,9 +120,10 @@ def _sample_and_collate(dev, cs, A, rows_d, addl_d, offs_d, starts_d, pid_d, kee
 
 
 class DeviceCollate:
-    def __init__(self, context_size, device, n_additional_feat=0, pin=False, sampling_fraction=1.0, seed=0):
+    def __init__(self, context_size, device, n_additional_feat=0, pin=False, sampling_fraction=1.0, seed=0, spatial_k=0):
         assert context_size >= 0
-        self.cs, self.device, self.A = int(context_size), torch.device(device), int(n_additional_feat)
+        self.cs, self.ks = _check_graph(context_size, spatial_k)
+        self.device, self.A = torch.device(device), int(n_additional_feat)
         self.pin = bool(pin)            # stage host arrays in pinned memory: H2D copies become asynchronous
         self.sf, self.seed = _check_fraction(sampling_fraction), int(seed)
 
@@ -106,12 +134,17 @@ class DeviceCollate:
         With ``sampling_fraction < 1`` each page keeps its labelled boxes and the int(sf * n) boxes of smallest key
         (datasets.py:101-110).  The key of a box is a hash of (seed, epoch, page id, box index); ``page_ids`` are the
         dataset-wide page ids (default: the position in the batch).  ``keys`` (int64 [N], non-negative) injects the keys
-        instead: ``keys[perm[j]] = j`` per page reproduces the reference's ``np.random.permutation`` draw ``perm``."""
+        instead: ``keys[perm[j]] = j`` per page reproduces the reference's ``np.random.permutation`` draw ``perm``.
+
+        With ``spatial_k > 0`` ``context_indices`` is [N, 2*context_size + spatial_k] (cova_context_knn over the kept
+        boxes); the rows must be finite (ValueError)."""
         u8 = torch.as_tensor(np.ascontiguousarray(u8_pages) if isinstance(u8_pages, np.ndarray)
                              else u8_pages)
         assert u8.dtype == torch.uint8 and u8.dim() == 4 and u8.shape[3] == 3
         B, H, W, _ = u8.shape
         assert len(rows_per_page) == B
+        if self.ks:
+            rows_per_page = [_check_rows(r, "page %d" % i) for i, r in enumerate(rows_per_page)]
         counts = [int(np.asarray(r).reshape(-1, 5).shape[0]) for r in rows_per_page]
         N = sum(counts)
         rows = np.concatenate([np.asarray(r, dtype=np.float32).reshape(-1, 5) for r in rows_per_page], 0) \
@@ -128,9 +161,11 @@ class DeviceCollate:
         offs_d = host(torch.from_numpy(offs)).to(dev, non_blocking=True)
         bboxes = torch.empty((N, 5), dtype=torch.float32, device=dev)
         labels = torch.empty((N,), dtype=torch.int64, device=dev)
-        K = 2 * self.cs
+        K = 0 if self.ks else 2 * self.cs
         ctx = torch.empty((N, K) if K else (0, 0), dtype=torch.int64, device=dev)   # datasets.py:130
-        call("cova_collate_boxes", rows_d, offs_d, B, N, self.cs, bboxes, labels, ctx if K else None)
+        call("cova_collate_boxes", rows_d, offs_d, B, N, K // 2, bboxes, labels, ctx if K else None)
+        if self.ks:
+            ctx = _context_knn(bboxes, offs_d, B, self.cs, self.ks)
         if additional_feats is None:
             addl = torch.empty((N, 0), dtype=torch.float32, device=dev)
         else:
@@ -163,7 +198,7 @@ class DeviceCollate:
                 raise ValueError("additional_feats must be [N, A] with one row per box")
             A = int(addl_d.shape[1])
         out = _sample_and_collate(dev, self.cs, A, rows_d, addl_d, offs_d, None, pid_d, keep_d, keys_d, B, N,
-                                  stream_seed(self.seed, epoch))
+                                  stream_seed(self.seed, epoch), ks=self.ks)
         out["images"] = images
         return out
 
@@ -206,14 +241,17 @@ def epoch_plan(n_pages, batch_size, shuffle, seed, epoch, drop_last=False, rank=
 class DeviceDataset:
     """A whole split resident on the GPU: ``[P,H,W,3]`` uint8 pages, the x,y,w,h,label rows of every page back to back
     and (optionally) the additional features.  ``batches`` yields ``DeviceCollate``'s batch dict for the pages of every
-    step of ``epoch_plan``, plus ``page_ids`` (device int64 [B]) and ``img_ids`` (host array of names)."""
+    step of ``epoch_plan``, plus ``page_ids`` (device int64 [B]) and ``img_ids`` (host array of names).
+    ``spatial_k > 0``: ``context_indices`` is [N, 2*context_size + spatial_k], the window plus the nearest other boxes of
+    the page among the KEPT boxes (cova_context_knn, one launch behind the collation)."""
 
     STAGING_BYTES = 64 << 20           # pinned staging buffer of the one-off upload
 
-    def __init__(self, u8_pages, rows_per_page, context_size, device, additional_feats=None, img_ids=None):
+    def __init__(self, u8_pages, rows_per_page, context_size, device, additional_feats=None, img_ids=None, spatial_k=0):
         if int(context_size) < 0:
             raise ValueError("context_size must be >= 0")
-        self.cs, self.device = int(context_size), torch.device(device)
+        self.cs, self.ks = _check_graph(context_size, spatial_k)
+        self.device = torch.device(device)
         if isinstance(u8_pages, (list, tuple)):
             pages = [torch.as_tensor(np.ascontiguousarray(p) if isinstance(p, np.ndarray) else p) for p in u8_pages]
             if not pages or any(p.shape != pages[0].shape for p in pages):
@@ -284,6 +322,19 @@ class DeviceDataset:
     def __len__(self):
         return self.P
 
+    def with_context(self, context_size=None, spatial_k=None):
+        """The same resident split with another context graph (None keeps a value): the store, the rows, the additional
+        features and the names are SHARED -- nothing is uploaded, nothing is copied.  One resident split and one
+        features.FeatureCache (it stamps the conv stack and the boxes, not the graph) serve a sweep over graphs."""
+        cs = self.cs if context_size is None else int(context_size)
+        if cs < 0:
+            raise ValueError("context_size must be >= 0")
+        cs, ks = _check_graph(cs, self.ks if spatial_k is None else spatial_k)
+        other = object.__new__(type(self))
+        other.__dict__.update(self.__dict__)
+        other.cs, other.ks = cs, ks
+        return other
+
     def batches(self, batch_size, shuffle=False, sampling_fraction=1.0, seed=0, epoch=0, drop_last=False, rank=0,
                 world_size=1, order=None, prefetch=True, features=None):
         """One epoch of batches (a generator).  Train: ``shuffle=True, sampling_fraction=sf``; val / test: batch 10,
@@ -323,7 +374,8 @@ class DeviceDataset:
                 images = torch.empty((B, 3, self.H, self.W), dtype=torch.float32, device=dev)
                 call("cova_pages_u8_gather_f32", self.store, ids_d, self.P, B, self.H, self.W, images)
             out = _sample_and_collate(dev, self.cs, self.A, self.rows, self.addl, offs_d, starts_d, ids_d, keep_d, None,
-                                      B, N, sseed, n_out=N if sf == 1.0 else None, want_sel=features is not None)
+                                      B, N, sseed, n_out=N if sf == 1.0 else None, want_sel=features is not None,
+                                      ks=self.ks)
             if features is None:
                 out["images"] = images
             else:       # the sampler's kept SOURCE row ids are the table's row ids (with sf == 1 it keeps every row)

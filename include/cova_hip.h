@@ -569,6 +569,33 @@ int cova_collate_selected(const float *rows, const int *sel, const int *out_offs
                           float *bboxes, long long *labels, long long *ctx /*nullable if context_size==0*/,
                           const float *addl_in /*nullable if A==0*/, int A, float *addl_out /*nullable if A==0*/,
                           void *stream);
+/* ---- context graphs (graph.hip; pipeline.DeviceCollate / DeviceDataset(spatial_k=)) ----
+ * cova_context_knn: the context table with spatial neighbours, ctx [N, 2*context_size + k_spatial] int64 batch-global ids,
+ *   -1 pads.  bboxes [N,5] = page,x1,y1,x2,y2 exactly as cova_collate_boxes / cova_collate_selected wrote them (the page
+ *   column is not read); page p owns boxes page_offsets[p] .. page_offsets[p+1] (DEVICE int32 [B+1], page_offsets[B] = N:
+ *   the page_offsets of cova_collate_boxes, the out_offsets of cova_sample_boxes).  The graph runs over the boxes it is
+ *   given, i.e. over the KEPT boxes of a sampled page (the reference builds its window after sampling, datasets.py:117-128).
+ *   For box i (page-local index) of a page with n boxes:
+ *   columns 0 .. 2*context_size: the DOM-order window exactly as cova_collate_boxes writes it: max(0,i-cs) .. i-1, then
+ *     i+1 .. min(n-1,i+cs), page-local index + page_offsets[p], trailing -1.  The collate kernels are called with
+ *     context_size = 0 and ctx = NULL in this mode: this one launch writes the whole table.
+ *   the remaining k_spatial columns: the nearest other boxes of the same page, nearest first.  Box i itself and every j
+ *     with |i-j| <= context_size (the window's members) are excluded, so a row never names a neighbour twice; with fewer
+ *     than k_spatial candidates the tail is -1.  Candidates are ordered lexicographically by (gap2, ctr2, j), smallest
+ *     first, in float32 with EVERY operation rounded on its own (no fused multiply-add):
+ *       dx = max(0, max(x1_i,x1_j) - min(x2_i,x2_j)), dy likewise     the gap between the rectangles, 0 where they overlap
+ *       gap2 = (dx*dx) + (dy*dy)
+ *       sx = x1 + x2, sy = y1 + y2, ex = sx_i - sx_j, ey = sy_i - sy_j
+ *       ctr2 = (ex*ex) + (ey*ey)                                       four times the squared centre distance
+ *     Both keys are sums of squares: non-negative and, for finite boxes, not NaN, so their bit patterns order as unsigned
+ *     integers and the kernel compares ((bits(gap2) << 32) | bits(ctr2), j).  tests/graph_oracle.py is the numpy statement.
+ *   Any n is valid (0, 1, thousands).  N == 0 or a table of width 0 returns without a launch (no pointer is read).
+ *   context_size >= 0, k_spatial >= 0, 2*context_size + k_spatial <= 1024 (the K of cova_gat_fwd).  Non-finite
+ *   coordinates: the launch stays memory-safe and every id written is -1 or a valid id of the page, without repeats; the
+ *   order is unspecified (the host refuses such rows).  A page_offsets table that does not hold box g writes a row of -1.
+ *   One launch (one wave per box), no workspace, no atomics, no host read: capturable and bit-deterministic. */
+int cova_context_knn(const float *bboxes, const int *page_offsets, int B, int N, int context_size, int k_spatial,
+                     long long *ctx, void *stream);
 /* attention export rows (extract_attn_wts_and_visualize.py:104-135): out [N, 5+5K] =
  * x,y,w,h,label, K x (x,y,w,h) of the context boxes (0 for pads), K attention weights */
 int cova_attn_export_rows(const float *bboxes, const long long *ctx, const float *attn,

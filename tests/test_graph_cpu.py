@@ -1,0 +1,180 @@
+"""Host side of the spatial context graphs (no GPU): the numpy oracle (tests/graph_oracle.py) against an independent
+brute-force statement of the contract, the packed-bits order the kernel compares, a tie-heavy integer grid, the argument
+checks of DeviceCollate / DeviceDataset / with_context, the declared entry point and synthetic's generator."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import cova_amd  # noqa: F401
+from cova_web_object_detection_amd import _lib, engine, pipeline, synthetic
+
+import graph_oracle as GO
+
+
+def random_boxes(rs, n, size=300.0):
+    wh = rs.uniform(4, 80, (n, 2))
+    xy = rs.uniform(0, 1, (n, 2)) * (size - wh)
+    b = np.concatenate([xy, wh], 1).astype(np.float32)
+    b[:, 2:] = b[:, :2] + b[:, 2:]                            # float32 adds, as the collation does them
+    return b
+
+
+def brute_force(boxes, cs, k):
+    """The contract in Python scalars: one np.float32 operation per rounding, ``sorted`` over (gap2, ctr2, j) tuples."""
+    f = np.float32
+    b = [[f(v) for v in row] for row in np.asarray(boxes, dtype=np.float32).reshape(-1, 4)]
+    n = len(b)
+    out = np.full((n, 2 * cs + k), -1, dtype=np.int64)
+    for i in range(n):
+        w = [j for j in range(n) if j != i and abs(j - i) <= cs]
+        assert w == sorted(w)
+        out[i, :len(w)] = w
+        cand = []
+        for j in range(n):
+            if abs(j - i) <= cs:
+                continue
+            dx = max(f(0), f(max(b[i][0], b[j][0]) - min(b[i][2], b[j][2])))
+            dy = max(f(0), f(max(b[i][1], b[j][1]) - min(b[i][3], b[j][3])))
+            gap2 = f(f(dx * dx) + f(dy * dy))
+            ex = f(f(b[i][0] + b[i][2]) - f(b[j][0] + b[j][2]))
+            ey = f(f(b[i][1] + b[i][3]) - f(b[j][1] + b[j][3]))
+            ctr2 = f(f(ex * ex) + f(ey * ey))
+            cand.append((float(gap2), float(ctr2), j))
+        near = [c[2] for c in sorted(cand)[:k]]
+        out[i, 2 * cs:2 * cs + len(near)] = near
+    return out
+
+
+@pytest.mark.parametrize("cs,k", [(0, 24), (6, 12), (3, 0), (0, 200)])
+@pytest.mark.parametrize("n", [0, 1, 2, 5, 25, 65, 130])
+def test_oracle_equals_the_brute_force_statement(n, cs, k):
+    boxes = random_boxes(np.random.RandomState(n * 31 + cs), n)
+    got = GO.page_graph(boxes, cs, k)
+    assert got.dtype == np.int64 and got.shape == (n, 2 * cs + k)
+    assert np.array_equal(got, brute_force(boxes, cs, k))
+    assert np.array_equal(synthetic.context_graph_indices(boxes, cs, k), got)          # the package's own host formulation
+    assert np.array_equal(got[:, :2 * cs], synthetic.context_window_indices(n, cs))     # the window is the reference's
+    if n - 1 - 2 * cs < k and n:
+        assert (got[:, -1] == -1).all()                                                 # not enough candidates: pads
+
+
+@pytest.mark.parametrize("n", [2, 5, 25, 65, 130])
+def test_packed_bits_order_is_the_tuple_order(n):
+    boxes = random_boxes(np.random.RandomState(n), n)
+    boxes[n // 2] = boxes[0]                                  # an exact duplicate: both keys tie, the index decides
+    for i in range(n):
+        gap2, ctr2 = GO.pair_keys(boxes, i)
+        assert (gap2 >= 0).all() and (ctr2 >= 0).all() and not np.signbit(gap2).any() and not np.signbit(ctr2).any()
+        j = np.arange(n)
+        by_tuple = sorted(range(n), key=lambda t: (float(gap2[t]), float(ctr2[t]), t))
+        packed = GO.packed_keys(gap2, ctr2)
+        assert packed.dtype == np.uint64
+        by_bits = sorted(range(n), key=lambda t: (int(packed[t]), t))
+        assert by_bits == by_tuple == np.lexsort((j, ctr2, gap2)).tolist()
+
+
+def test_tie_grid_has_heavy_ties_and_a_hub():
+    boxes = GO.tie_grid()
+    n = boxes.shape[0]
+    assert n == 131 and np.array_equal(boxes, np.round(boxes))
+    zero_gap = sum(int((GO.pair_keys(boxes, i)[0][i + 1:] == 0).sum()) for i in range(n))
+    assert zero_gap == 130                                     # the covering box overlaps every cell; cells are 10 apart
+    g = GO.page_graph(boxes, 0, 8)
+    assert np.array_equal(g, brute_force(boxes, 0, 8))
+    assert np.array_equal(g, synthetic.context_graph_indices(boxes, 0, 8))
+    indeg = np.bincount(g[g >= 0], minlength=n)
+    assert indeg[130] == 130 > 64                              # a hub: every cell names it, more than a wave has lanes
+    assert (g >= 0).all() and all(len(set(r.tolist())) == 8 and i not in r for i, r in enumerate(g))
+    # ties in BOTH keys are there and go to the lower index
+    gap2, ctr2 = GO.pair_keys(boxes, 0)
+    pk = GO.packed_keys(gap2, ctr2)[1:]
+    assert len(set(pk.tolist())) < pk.shape[0]
+
+
+def test_hybrid_rows_exclude_the_window_and_batch_offsets_are_global():
+    rs = np.random.RandomState(5)
+    counts = [7, 0, 30, 1]
+    boxes = [random_boxes(rs, n) for n in counts]
+    ps = np.concatenate([[0], np.cumsum(counts)])
+    bb = np.concatenate([np.concatenate([np.full((n, 1), p, np.float32), b], 1) for p, (n, b) in enumerate(zip(counts, boxes))])
+    cs, k = 2, 5
+    g = GO.batch_graph(bb, ps, cs, k)
+    assert g.shape == (38, 9)
+    for p, n in enumerate(counts):
+        loc = g[ps[p]:ps[p + 1]]
+        assert np.array_equal(np.where(loc >= 0, loc - ps[p], -1), GO.page_graph(boxes[p], cs, k))
+        for i, row in enumerate(loc):
+            ids = row[row >= 0]
+            assert len(set(ids.tolist())) == ids.shape[0] and ((ids >= ps[p]) & (ids < ps[p + 1])).all()
+            assert all(abs(int(j) - ps[p] - i) > cs for j in row[2 * cs:] if j >= 0)
+    assert (g[37] == -1).all()                                 # the one-box page
+
+
+def test_graph_arguments_are_checked_on_the_host():
+    for cls_args in ((pipeline.DeviceCollate, (3, "cpu")),):
+        with pytest.raises(ValueError, match="spatial_k"):
+            cls_args[0](*cls_args[1], spatial_k=-1)
+    with pytest.raises(ValueError, match="neighbour slots"):
+        pipeline.DeviceCollate(500, "cpu", spatial_k=engine.GAT_MAX_K - 999)
+    c = pipeline.DeviceCollate(500, "cpu", spatial_k=engine.GAT_MAX_K - 1000)
+    assert (c.cs, c.ks) == (500, 24) and pipeline.DeviceCollate(3, "cpu").ks == 0
+    good = np.zeros((2, 4, 4, 3), np.uint8)
+    rows = [np.zeros((3, 5), np.float32), np.zeros((0, 5), np.float32)]
+    with pytest.raises(ValueError, match="spatial_k"):
+        pipeline.DeviceDataset(good, rows, 2, "cpu", spatial_k=-3)
+    with pytest.raises(ValueError, match="neighbour slots"):
+        pipeline.DeviceDataset(good, rows, 2, "cpu", spatial_k=engine.GAT_MAX_K - 3)
+    # a collate call with spatial neighbours refuses non-finite rows before anything reaches the device
+    bad = [np.zeros((3, 5), np.float32), np.zeros((1, 5), np.float32)]
+    bad[1][0, 2] = np.inf
+    with pytest.raises(ValueError, match="non-finite"):
+        pipeline.DeviceCollate(2, "cpu", spatial_k=4)(good, bad)
+    # with_context on a dataset shell (no device): shares every attribute, changes the graph alone
+    ds = object.__new__(pipeline.DeviceDataset)
+    ds.cs, ds.ks, ds.store, ds.rows = 12, 0, torch.zeros(4, dtype=torch.uint8), torch.zeros((3, 5))
+    sib = ds.with_context(0, 24)
+    assert (sib.cs, sib.ks) == (0, 24) and (ds.cs, ds.ks) == (12, 0)
+    assert sib.store is ds.store and sib.rows is ds.rows
+    assert (ds.with_context().cs, ds.with_context().ks) == (12, 0)
+    assert (sib.with_context(spatial_k=8).cs, sib.with_context(spatial_k=8).ks) == (0, 8)
+    assert (sib.with_context(context_size=6).cs, sib.with_context(context_size=6).ks) == (6, 24)
+    for kw, match in ((dict(spatial_k=-1), "spatial_k"), (dict(context_size=-1), "context_size"),
+                      (dict(context_size=512, spatial_k=1), "neighbour slots")):
+        with pytest.raises(ValueError, match=match):
+            ds.with_context(**kw)
+
+
+def test_context_knn_is_declared_and_exported():
+    cdll = ctypes.CDLL(_lib.LIB_PATH)
+    protos = _lib.parse_header()
+    assert "cova_context_knn" in protos and hasattr(cdll, "cova_context_knn")
+    assert protos["cova_context_knn"] == [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]      # ... ctx, stream
+    assert len(protos["cova_collate_boxes"]) == 9 and len(protos["cova_collate_selected"]) == 13       # unchanged
+    fn = cdll.cova_context_knn
+    fn.argtypes, fn.restype = protos["cova_context_knn"], ctypes.c_int
+    # nothing to do: returns without a launch and without reading a pointer
+    assert fn(None, None, 3, 0, 6, 12, None, None) == 0
+    assert fn(None, None, 3, 40, 0, 0, None, None) == 0
+    for cs, k in ((-1, 4), (2, -1), (500, 25), (0, engine.GAT_MAX_K + 1)):
+        assert fn(None, None, 3, 40, cs, k, None, None) == 10001
+    assert fn(None, None, 3, 40, 2, 4, None, None) == 10001                    # work to do and no pointers
+
+
+def test_synthetic_default_is_unchanged_and_spatial_k_carries_the_graph():
+    kw = dict(img_h=64, boxes_per_page=[9, 30, 1], context_size=3, seed=7)
+    a, b = synthetic.make_batch(3, **kw), synthetic.make_batch(3, spatial_k=0, **kw)
+    for key in a:
+        assert np.array_equal(np.asarray(a[key]), np.asarray(b[key])), key
+    ref = synthetic.collate_context([synthetic.context_window_indices(n, 3) for n in (9, 30, 1)])
+    assert np.array_equal(a["context_indices"].numpy(), ref)                  # the reference's window, as ever
+    c = synthetic.make_batch(3, spatial_k=5, **kw)
+    for key in a:
+        if key != "context_indices":
+            assert np.array_equal(np.asarray(a[key]), np.asarray(c[key])), key
+    assert c["context_indices"].dtype == torch.int64
+    assert np.array_equal(c["context_indices"].numpy(), GO.batch_graph(c["bboxes"].numpy(), [0, 9, 39, 40], 3, 5))
+    d = synthetic.make_boxes_only(3, 64, 64, boxes_per_page=[9, 30, 1], context_size=0, seed=7, spatial_k=4)
+    assert np.array_equal(d["context_indices"].numpy(), GO.batch_graph(d["bboxes"].numpy(), [0, 9, 39, 40], 0, 4))
