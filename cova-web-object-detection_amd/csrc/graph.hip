@@ -7,6 +7,8 @@
 //                        6-step wave min-reduction picks the winner and lane 0 stores it.  The first four candidates of a
 //                        lane keep their keys in registers (a page of the reference's data, 11-230 boxes, is covered);
 //                        the candidates behind them are recomputed every round, with no storage: any n.
+//   edge_geometry_kernel the eight relative-geometry features of every edge of a context table (cova_edge_geometry), one
+//                        thread per slot.
 // Integer compares of float bit patterns, every float operation rounded on its own: bit-deterministic, equal to numpy.
 #include "common.h"
 #include <limits.h>
@@ -113,7 +115,62 @@ __global__ __launch_bounds__(KNN_THREADS) void context_knn_kernel(
     }
 }
 
+// Relative geometry of one edge (include/cova_hip.h, cova_edge_geometry): box a = the node i, box b = its neighbour j, both
+// x1,y1,x2,y2; dj = j - i.  Every operation is rounded on its own (no contraction: tests/edge_oracle.py states the same
+// expressions in numpy float32, parenthesis for parenthesis) and `/` is the correctly rounded division.
+__device__ __forceinline__ void edge_features(const float4 a, const float4 b, float W, float H, int dj, float *f)
+{
+#pragma clang fp contract(off)
+    const float wi = a.z - a.x, hi = a.w - a.y, wj = b.z - b.x, hj = b.w - b.y;
+    f[0] = ((b.x + b.z) - (a.x + a.z)) / (2.f * W);
+    f[1] = ((b.y + b.w) - (a.y + a.w)) / (2.f * H);
+    f[2] = (wj - wi) / ((wj + wi) + 1.f);
+    f[3] = (hj - hi) / ((hj + hi) + 1.f);
+    f[4] = fmaxf(0.f, fmaxf(a.x, b.x) - fminf(a.z, b.z)) / W;      // the gap of knn_key
+    f[5] = fmaxf(0.f, fmaxf(a.y, b.y) - fminf(a.w, b.w)) / H;
+    const float iw = fmaxf(0.f, fminf(a.z, b.z) - fmaxf(a.x, b.x));
+    const float ih = fmaxf(0.f, fminf(a.w, b.w) - fmaxf(a.y, b.y));
+    const float inter = iw * ih;
+    const float ai = wi * hi, aj = wj * hj;
+    const float uni = (ai + aj) - inter;
+    f[6] = uni > 0.f ? inter / uni : 0.f;
+    f[7] = (float)max(-64, min(64, dj)) / 64.f;
+}
+
+// one thread per slot (i, k), grid-stride; a pad (j < 0 or j >= N) writes eight zeros and reads no box
+__global__ __launch_bounds__(256) void edge_geometry_kernel(const float *__restrict__ bboxes,
+                                                            const long long *__restrict__ ctx, int N, int K, float W,
+                                                            float H, float *__restrict__ phi)
+{
+    const long long E = (long long)N * K, step = (long long)gridDim.x * 256;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < E; e += step) {
+        const long long i = e / K, j = ctx[e];
+        float f[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (j >= 0 && j < N) {
+            const long long d = j - i;
+            edge_features(knn_box(bboxes, i), knn_box(bboxes, j), W, H, (int)d, f);
+        }
+        float4 *out = reinterpret_cast<float4 *>(phi + e * 8);
+        out[0] = make_float4(f[0], f[1], f[2], f[3]);
+        out[1] = make_float4(f[4], f[5], f[6], f[7]);
+    }
+}
+
 }  // namespace
+
+COVA_API int cova_edge_geometry(const float *bboxes, const long long *ctx, int N, int K, float img_w, float img_h,
+                                float *phi, void *stream)
+{
+    COVA_REQUIRE(N >= 0 && K >= 0 && K <= COVA_GAT_MAX_K);
+    if (N == 0 || K == 0) return COVA_OK;
+    COVA_REQUIRE(bboxes && ctx && phi && ((uintptr_t)phi & 15) == 0 && img_w > 0.f && img_h > 0.f);
+    long long blocks = ((long long)N * K + 255) / 256;
+    if (blocks > 64 * 1024) blocks = 64 * 1024;
+    hipLaunchKernelGGL(edge_geometry_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, bboxes, ctx, N, K,
+                       img_w, img_h, phi);
+    COVA_LAUNCH_CHECK();
+    return COVA_OK;
+}
 
 COVA_API int cova_context_knn(const float *bboxes, const int *page_offsets, int B, int N, int context_size, int k_spatial,
                               long long *ctx, void *stream)

@@ -634,13 +634,33 @@ __global__ __launch_bounds__(256) void gat_scores_kernel(const float *__restrict
     if (lane == 0) { s[n] = a + att_b[0]; t[n] = b; }
 }
 
+// Edge geometry (cova_gat_fwd_edge / cova_gat_bwd_edge): the additive score term of one slot, edge_w . phi[slot][0:8], as
+// one fma chain in feature order.  The forward and the source-side backward both call this, so the LeakyReLU slope the
+// backward takes is the one the forward took, bit for bit.  phi rows are 32 bytes: two 16-byte loads.
+__device__ __forceinline__ float gat_edge_term(const float *__restrict__ phi, size_t slot, const float *__restrict__ edge_w)
+{
+    const float4 p0 = *reinterpret_cast<const float4 *>(phi + slot * 8);
+    const float4 p1 = *reinterpret_cast<const float4 *>(phi + slot * 8 + 4);
+    float g = edge_w[0] * p0.x;
+    g = fmaf(edge_w[1], p0.y, g);
+    g = fmaf(edge_w[2], p0.z, g);
+    g = fmaf(edge_w[3], p0.w, g);
+    g = fmaf(edge_w[4], p1.x, g);
+    g = fmaf(edge_w[5], p1.y, g);
+    g = fmaf(edge_w[6], p1.z, g);
+    g = fmaf(edge_w[7], p1.w, g);
+    return g;
+}
+
 // KP = number of 64-slot passes a wave makes over the K neighbour slots (K <= 64 KP; KP = 1 is the reference's usual
 // range, -cs <= 32); slot k lives in lane k & 63 of pass k >> 6.  models.py:171-177 accepts any n_context.
-template <int KP>
+// EDGE: the pre-activation of a slot also takes gat_edge_term (phi [N,K,8], edge_w [8]); false reads neither pointer.
+template <int KP, bool EDGE = false>
 __global__ __launch_bounds__(256) void gat_fwd_kernel(
     const float *__restrict__ Wh, int ldw, const float *__restrict__ s, const float *__restrict__ t,
     const int64_t *__restrict__ ctx, int N, int K, int D, float slope, float *__restrict__ attn,
-    float *__restrict__ hprime, int ldh)
+    float *__restrict__ hprime, int ldh, const float *__restrict__ phi = nullptr,
+    const float *__restrict__ edge_w = nullptr)
 {
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (n >= N) return;
@@ -655,7 +675,8 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(
         if (k < K) {
             j = ctx[(size_t)n * K + k];
             if (j >= N) j = -1;                                 // out-of-range id: memory-safe, acts as a pad
-            const float u = s[n] + (j >= 0 ? t[j] : 0.f);
+            float u = s[n] + (j >= 0 ? t[j] : 0.f);
+            if (EDGE && j >= 0) u += gat_edge_term(phi, (size_t)n * K + k, edge_w);
             const float lr = u > 0.f ? u : slope * u;
             e[p] = j >= 0 ? lr : -9e15f;                       // models.py:202-203
         }
@@ -704,11 +725,12 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(
 // aggregation exchanged -- neighbour batches outside, the ND 64-channel chunks of a row inside -- so that one batch has
 // 8 ND loads in flight instead of 8 and a node makes ceil(K / 8) dependent round trips instead of ceil(K / 8) * D / 64
 // (18 -> 3 at configs[1]: 18.7 us of latency).  Every output still adds its neighbours in slot order: identical bits.
-template <int ND>
+template <int ND, bool EDGE = false>
 __global__ __launch_bounds__(256) void gat_fwd_wide_kernel(
     const float *__restrict__ Wh, int ldw, const float *__restrict__ s, const float *__restrict__ t,
     const int64_t *__restrict__ ctx, int N, int K, int D, float slope, float *__restrict__ attn,
-    float *__restrict__ hprime, int ldh)
+    float *__restrict__ hprime, int ldh, const float *__restrict__ phi = nullptr,
+    const float *__restrict__ edge_w = nullptr)
 {
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (n >= N) return;
@@ -717,7 +739,8 @@ __global__ __launch_bounds__(256) void gat_fwd_wide_kernel(
     if (lane < K) {
         j = ctx[(size_t)n * K + lane];
         if (j >= N) j = -1;                                 // out-of-range id: memory-safe, acts as a pad
-        const float u = s[n] + (j >= 0 ? t[j] : 0.f);
+        float u = s[n] + (j >= 0 ? t[j] : 0.f);
+        if (EDGE && j >= 0) u += gat_edge_term(phi, (size_t)n * K + lane, edge_w);
         const float lr = u > 0.f ? u : slope * u;
         e = j >= 0 ? lr : -9e15f;                           // models.py:202-203
     }
@@ -934,12 +957,13 @@ __global__ __launch_bounds__(256) void csr_count_scan_kernel(const int64_t *__re
 // backward, source side (one wave per node i): everything that stays with node i -- du [N,K] (0 on pads),
 // ds, dWh_i = ds * a_i.  The contributions to OTHER nodes (dt[ctx], dWh_j[ctx]) are gathered by
 // gat_bwd_dst_kernel from du / attn / g through the transposed index.
-template <int KP>
+template <int KP, bool EDGE = false>
 __global__ __launch_bounds__(256) void gat_bwd_src_kernel(
     const float *__restrict__ g, int ldg, const float *__restrict__ Wh, int ldw,
     const float *__restrict__ s, const float *__restrict__ t, const float *__restrict__ attn,
     const int64_t *__restrict__ ctx, const float *__restrict__ att_w, int N, int K, int D,
-    float slope, float *__restrict__ dWh, int lddw, float *__restrict__ ds, float *__restrict__ du_out)
+    float slope, float *__restrict__ dWh, int lddw, float *__restrict__ ds, float *__restrict__ du_out,
+    const float *__restrict__ phi = nullptr, const float *__restrict__ edge_w = nullptr)
 {
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (n >= N) return;
@@ -991,7 +1015,8 @@ __global__ __launch_bounds__(256) void gat_bwd_src_kernel(
         float du = 0.f;
         if (64 * p + lane < K && jj[p] >= 0) {
             const float de = alpha[p] * (dalpha[p] - dot);
-            const float u = s[n] + t[jj[p]];
+            float u = s[n] + t[jj[p]];
+            if (EDGE) u += gat_edge_term(phi, (size_t)n * K + 64 * p + lane, edge_w);      // (the forward's u, bit for bit)
             du = de * (u > 0.f ? 1.f : slope);
         }
         if (64 * p + lane < K) du_out[(size_t)n * K + 64 * p + lane] = du;
@@ -1045,12 +1070,13 @@ __global__ __launch_bounds__(256) void gat_bwd_dst_kernel(
 // gat_bwd_src_kernel<1> / gat_bwd_dst_kernel with every 64-channel chunk of a row in flight per neighbour batch (see
 // gat_fwd_wide_kernel): K <= 64, D <= 64 ND; identical bits (each sum keeps its order: channels ascending inside a dot
 // product, edges ascending inside a gathered row).
-template <int ND>
+template <int ND, bool EDGE = false>
 __global__ __launch_bounds__(256) void gat_bwd_src_wide_kernel(
     const float *__restrict__ g, int ldg, const float *__restrict__ Wh, int ldw,
     const float *__restrict__ s, const float *__restrict__ t, const float *__restrict__ attn,
     const int64_t *__restrict__ ctx, const float *__restrict__ att_w, int N, int K, int D,
-    float slope, float *__restrict__ dWh, int lddw, float *__restrict__ ds, float *__restrict__ du_out)
+    float slope, float *__restrict__ dWh, int lddw, float *__restrict__ ds, float *__restrict__ du_out,
+    const float *__restrict__ phi = nullptr, const float *__restrict__ edge_w = nullptr)
 {
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (n >= N) return;
@@ -1099,7 +1125,8 @@ __global__ __launch_bounds__(256) void gat_bwd_src_wide_kernel(
     float du = 0.f;
     if (lane < K && jj >= 0) {
         const float de = alpha * (dalpha - dot);
-        const float u = s[n] + t[jj];
+        float u = s[n] + t[jj];
+        if (EDGE) u += gat_edge_term(phi, (size_t)n * K + lane, edge_w);                   // (the forward's u, bit for bit)
         du = de * (u > 0.f ? 1.f : slope);
     }
     if (lane < K) du_out[(size_t)n * K + lane] = du;
@@ -1207,6 +1234,56 @@ __global__ __launch_bounds__(1024) void gat_bwd_att_kernel(const float *__restri
         for (int j = 0; j < NS; ++j) t += s_acc[j][threadIdx.x];
         if (oc == 2 * D) d_att_b[0] = t;
         else d_att_w[oc] = t;
+    }
+}
+
+// d_edge_w[e] = sum over the N*K slots of du[slot] * phi[slot][e] (du is 0 on pads and phi is 0 there too), in a fixed
+// association: block b owns the slots [b * EDGE_CHUNK, (b + 1) * EDGE_CHUNK) whatever the grid -- thread x takes x, x + 256,
+// ... in ascending order, the 64 lanes of a wave meet in wave_sum's butterfly, the four waves are added in wave order -- and
+// writes 8 partials; gat_edge_wgrad_final_kernel adds the partials of all blocks: thread group q takes b = q, q + 32, ...
+// ascending, the 32 groups are added in group order.  No atomics; the bits depend on (N*K, du, phi) alone.
+constexpr int EDGE_CHUNK = 4096;
+__global__ __launch_bounds__(256) void gat_edge_wgrad_partial_kernel(const float *__restrict__ du,
+                                                                     const float *__restrict__ phi, long long E,
+                                                                     float *__restrict__ partial)
+{
+    __shared__ float s_w[4][8];
+    const long long lo = (long long)blockIdx.x * EDGE_CHUNK;
+    const long long hi = lo + EDGE_CHUNK < E ? lo + EDGE_CHUNK : E;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (long long e = lo + threadIdx.x; e < hi; e += 256) {
+        const float d = du[e];
+        const float4 p0 = *reinterpret_cast<const float4 *>(phi + e * 8);
+        const float4 p1 = *reinterpret_cast<const float4 *>(phi + e * 8 + 4);
+        acc[0] = fmaf(d, p0.x, acc[0]); acc[1] = fmaf(d, p0.y, acc[1]);
+        acc[2] = fmaf(d, p0.z, acc[2]); acc[3] = fmaf(d, p0.w, acc[3]);
+        acc[4] = fmaf(d, p1.x, acc[4]); acc[5] = fmaf(d, p1.y, acc[5]);
+        acc[6] = fmaf(d, p1.z, acc[6]); acc[7] = fmaf(d, p1.w, acc[7]);
+    }
+#pragma unroll
+    for (int f = 0; f < 8; ++f) {
+        const float tot = wave_sum(acc[f]);
+        if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6][f] = tot;
+    }
+    __syncthreads();
+    if (threadIdx.x < 8)
+        partial[(size_t)blockIdx.x * 8 + threadIdx.x] =
+            ((s_w[0][threadIdx.x] + s_w[1][threadIdx.x]) + s_w[2][threadIdx.x]) + s_w[3][threadIdx.x];
+}
+
+__global__ __launch_bounds__(256) void gat_edge_wgrad_final_kernel(const float *__restrict__ partial, int nparts,
+                                                                   float *__restrict__ d_edge_w)
+{
+    __shared__ float s_q[32][8];
+    const int f = threadIdx.x & 7, q = threadIdx.x >> 3;
+    float acc = 0.f;
+    for (int b = q; b < nparts; b += 32) acc += partial[(size_t)b * 8 + f];
+    s_q[q][f] = acc;
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        float tot = 0.f;
+        for (int j = 0; j < 32; ++j) tot += s_q[j][threadIdx.x];
+        d_edge_w[threadIdx.x] = tot;
     }
 }
 
@@ -1438,19 +1515,21 @@ COVA_API int cova_bbox_linear_bwd(const float *dz, const float *raw, float *dW, 
 
 // Wh [N, 2D] (ld = ldw): first D columns W_i h, last D columns W_j h.
 // Outputs: s, t [N]; attn [N, K]; hprime rows at hprime + n*ldh (D entries).
-COVA_API int cova_gat_fwd(const float *Wh, int ldw, const float *att_w, const float *att_b,
-                          const int64_t *ctx, int N, int K, int D, float slope, float *s, float *t,
-                          float *attn, float *hprime, int ldh, void *stream)
+// EDGE = false is cova_gat_fwd (phi, edge_w unused: NULL); true is cova_gat_fwd_edge -- the same launches, the second one
+// on the EDGE instantiation of its kernel.
+namespace {
+template <bool EDGE>
+int gat_fwd_launch(const float *Wh, int ldw, const float *att_w, const float *att_b, const int64_t *ctx, int N, int K,
+                   int D, float slope, float *s, float *t, float *attn, float *hprime, int ldh, const float *phi,
+                   const float *edge_w, void *stream)
 {
-    COVA_REQUIRE(Wh && att_w && att_b && ctx && s && t && attn && hprime && K > 0 && K <= COVA_GAT_MAX_K && D > 0);
-    if (N == 0) return COVA_OK;
     hipLaunchKernelGGL(gat_scores_kernel, dim3(cdiv(N, 4)), dim3(256), 0, (hipStream_t)stream, Wh,
                        ldw, att_w, att_b, s, t, N, D);
     COVA_LAUNCH_CHECK();
     const dim3 grid(cdiv(N, 4)), blk(256);
     hipStream_t st = (hipStream_t)stream;
     if (K <= 64 && gat_wide_nd(D) > 0) {        // every 64-channel chunk of a neighbour row in flight (identical bits)
-#define COVA_GAT_FWD_WIDE(ND) hipLaunchKernelGGL(gat_fwd_wide_kernel<ND>, grid, blk, 0, st, Wh, ldw, s, t, ctx, N, K, D, slope, attn, hprime, ldh)
+#define COVA_GAT_FWD_WIDE(ND) hipLaunchKernelGGL((gat_fwd_wide_kernel<ND, EDGE>), grid, blk, 0, st, Wh, ldw, s, t, ctx, N, K, D, slope, attn, hprime, ldh, phi, edge_w)
         switch (gat_wide_nd(D)) {
         case 1: COVA_GAT_FWD_WIDE(1); break;
         case 2: COVA_GAT_FWD_WIDE(2); break;
@@ -1463,7 +1542,7 @@ COVA_API int cova_gat_fwd(const float *Wh, int ldw, const float *att_w, const fl
         COVA_LAUNCH_CHECK();
         return COVA_OK;
     }
-#define COVA_GAT_FWD(KP) hipLaunchKernelGGL(gat_fwd_kernel<KP>, grid, blk, 0, st, Wh, ldw, s, t, ctx, N, K, D, slope, attn, hprime, ldh)
+#define COVA_GAT_FWD(KP) hipLaunchKernelGGL((gat_fwd_kernel<KP, EDGE>), grid, blk, 0, st, Wh, ldw, s, t, ctx, N, K, D, slope, attn, hprime, ldh, phi, edge_w)
     switch ((K + 63) / 64) {        // one wave per node, K slots in ceil(K / 64) passes over the lanes
     case 1: COVA_GAT_FWD(1); break;
     case 2: COVA_GAT_FWD(2); break;
@@ -1479,6 +1558,28 @@ COVA_API int cova_gat_fwd(const float *Wh, int ldw, const float *att_w, const fl
 #undef COVA_GAT_FWD
     COVA_LAUNCH_CHECK();
     return COVA_OK;
+}
+}  // namespace
+
+COVA_API int cova_gat_fwd(const float *Wh, int ldw, const float *att_w, const float *att_b,
+                          const int64_t *ctx, int N, int K, int D, float slope, float *s, float *t,
+                          float *attn, float *hprime, int ldh, void *stream)
+{
+    COVA_REQUIRE(Wh && att_w && att_b && ctx && s && t && attn && hprime && K > 0 && K <= COVA_GAT_MAX_K && D > 0);
+    if (N == 0) return COVA_OK;
+    return gat_fwd_launch<false>(Wh, ldw, att_w, att_b, ctx, N, K, D, slope, s, t, attn, hprime, ldh, nullptr, nullptr,
+                                 stream);
+}
+
+// cova_gat_fwd with the edge term: u = s[i] + t[j] + edge_w . phi[i,k,:] (phi from cova_edge_geometry, 16-byte aligned)
+COVA_API int cova_gat_fwd_edge(const float *Wh, int ldw, const float *att_w, const float *att_b, const int64_t *ctx,
+                               const float *phi, const float *edge_w, int N, int K, int D, float slope, float *s,
+                               float *t, float *attn, float *hprime, int ldh, void *stream)
+{
+    COVA_REQUIRE(Wh && att_w && att_b && ctx && s && t && attn && hprime && K > 0 && K <= COVA_GAT_MAX_K && D > 0);
+    COVA_REQUIRE(phi && edge_w && ((uintptr_t)phi & 15) == 0);
+    if (N == 0) return COVA_OK;
+    return gat_fwd_launch<true>(Wh, ldw, att_w, att_b, ctx, N, K, D, slope, s, t, attn, hprime, ldh, phi, edge_w, stream);
 }
 
 // Transposed neighbour index of ctx [N,K]: csr[0..N] = row_ptr, csr[N+1 .. N+1+N*K) = the flat slots i*K+k that
@@ -1525,23 +1626,22 @@ COVA_API int cova_gat_transpose_reuse(const int64_t *ctx, int N, int K, int *csr
 
 // dWh [N, 2D] (ld = lddw) is fully written; ds, dt [N] scratch; d_att_w [2D], d_att_b [1].
 // csr (from cova_gat_transpose) + du [N,K] scratch: gather form, no float atomics, bit-identical reruns.
-// csr == NULL: the scatter form with float atomics (kept for A/B measurements).
-COVA_API int cova_gat_bwd(const float *g, int ldg, const float *Wh, int ldw, const float *s,
-                          const float *t, const float *attn, const int64_t *ctx, const float *att_w,
-                          int N, int K, int D, float slope, float *dWh, int lddw, float *ds, float *dt,
-                          float *d_att_w, float *d_att_b, const int *csr, float *du, void *stream)
-{
-    COVA_REQUIRE(g && Wh && s && t && attn && ctx && att_w && dWh && ds && dt && d_att_w && d_att_b);
-    COVA_REQUIRE(K > 0 && K <= COVA_GAT_MAX_K && D > 0 && N > 0);
-    COVA_REQUIRE(!csr || du);
-    hipStream_t st = (hipStream_t)stream;
+// csr == NULL: the scatter form with float atomics (kept for A/B measurements; not with EDGE).
+// EDGE = false is cova_gat_bwd (phi, edge_w, d_edge_w, edge_ws unused: NULL); true is cova_gat_bwd_edge.
+namespace {
+template <bool EDGE>
+int gat_bwd_launch(const float *g, int ldg, const float *Wh, int ldw, const float *s, const float *t, const float *attn,
+                   const int64_t *ctx, const float *att_w, int N, int K, int D, float slope, float *dWh, int lddw,
+                   float *ds, float *dt, float *d_att_w, float *d_att_b, const int *csr, float *du, const float *phi,
+                   const float *edge_w, float *d_edge_w, float *edge_ws, void *stream)
+{    hipStream_t st = (hipStream_t)stream;
     const int kp = (K + 63) / 64;
     if (csr != nullptr && K <= 64 && gat_wide_nd(D) > 0) {
         const dim3 grid(cdiv(N, 4)), blk(256);
 #define COVA_GAT_BWD_WIDE(ND)                                                                                               \
         do {                                                                                                                \
-            hipLaunchKernelGGL(gat_bwd_src_wide_kernel<ND>, grid, blk, 0, st, g, ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, \
-                               slope, dWh, lddw, ds, du);                                                                   \
+            hipLaunchKernelGGL((gat_bwd_src_wide_kernel<ND, EDGE>), grid, blk, 0, st, g, ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, \
+                               slope, dWh, lddw, ds, du, phi, edge_w);                                                      \
             hipLaunchKernelGGL(gat_bwd_dst_wide_kernel<ND>, grid, blk, 0, st, g, ldg, attn, du, csr, csr + N + 1, att_w, N, K, \
                                D, dWh, lddw, dt);                                                                           \
         } while (0)
@@ -1556,8 +1656,8 @@ COVA_API int cova_gat_bwd(const float *g, int ldg, const float *Wh, int ldw, con
 #undef COVA_GAT_BWD_WIDE
         COVA_LAUNCH_CHECK();
     } else if (csr != nullptr) {
-#define COVA_GAT_SRC(KP) hipLaunchKernelGGL(gat_bwd_src_kernel<KP>, dim3(cdiv(N, 4)), dim3(256), 0, st, g, ldg, Wh, ldw, s, t, \
-                                            attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, du)
+#define COVA_GAT_SRC(KP) hipLaunchKernelGGL((gat_bwd_src_kernel<KP, EDGE>), dim3(cdiv(N, 4)), dim3(256), 0, st, g, ldg, Wh, ldw, s, t, \
+                                            attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, du, phi, edge_w)
         switch (kp) {
         case 1: COVA_GAT_SRC(1); break;
         case 2: COVA_GAT_SRC(2); break;
@@ -1604,5 +1704,47 @@ COVA_API int cova_gat_bwd(const float *g, int ldg, const float *Wh, int ldw, con
     hipLaunchKernelGGL((v4 ? gat_bwd_att_kernel<4> : gat_bwd_att_kernel<1>), dim3(cdiv(2 * D + 1, 64)), dim3(1024), 0,
                        st, Wh, ldw, ds, dt, d_att_w, d_att_b, N, D);
     COVA_LAUNCH_CHECK();
+    if (EDGE) {                 // the edge weight's gradient from the du the source-side kernel wrote: two launches
+        const long long E = (long long)N * K;
+        const int nparts = (int)cdivll(E, EDGE_CHUNK);
+        hipLaunchKernelGGL(gat_edge_wgrad_partial_kernel, dim3(nparts), dim3(256), 0, st, du, phi, E, edge_ws);
+        COVA_LAUNCH_CHECK();
+        hipLaunchKernelGGL(gat_edge_wgrad_final_kernel, dim3(1), dim3(256), 0, st, edge_ws, nparts, d_edge_w);
+        COVA_LAUNCH_CHECK();
+    }
     return COVA_OK;
+}
+}  // namespace
+
+COVA_API int cova_gat_bwd(const float *g, int ldg, const float *Wh, int ldw, const float *s,
+                          const float *t, const float *attn, const int64_t *ctx, const float *att_w,
+                          int N, int K, int D, float slope, float *dWh, int lddw, float *ds, float *dt,
+                          float *d_att_w, float *d_att_b, const int *csr, float *du, void *stream)
+{
+    COVA_REQUIRE(g && Wh && s && t && attn && ctx && att_w && dWh && ds && dt && d_att_w && d_att_b);
+    COVA_REQUIRE(K > 0 && K <= COVA_GAT_MAX_K && D > 0 && N > 0);
+    COVA_REQUIRE(!csr || du);
+    return gat_bwd_launch<false>(g, ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, dt, d_att_w,
+                                 d_att_b, csr, du, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+// floats of cova_gat_bwd_edge's workspace: 8 partial sums per block of EDGE_CHUNK slots
+COVA_API int cova_gat_edge_workspace_floats(int N, int K)
+{
+    if (N <= 0 || K <= 0) return 0;
+    return 8 * (int)cdivll((long long)N * K, EDGE_CHUNK);
+}
+
+// cova_gat_bwd's gather form with the edge term in u, plus d_edge_w [8] = sum_slots du * phi (fixed order, no atomics)
+COVA_API int cova_gat_bwd_edge(const float *g, int ldg, const float *Wh, int ldw, const float *s, const float *t,
+                               const float *attn, const int64_t *ctx, const float *att_w, const float *phi,
+                               const float *edge_w, int N, int K, int D, float slope, float *dWh, int lddw, float *ds,
+                               float *dt, float *d_att_w, float *d_att_b, float *d_edge_w, const int *csr, float *du,
+                               float *workspace, void *stream)
+{
+    COVA_REQUIRE(g && Wh && s && t && attn && ctx && att_w && dWh && ds && dt && d_att_w && d_att_b);
+    COVA_REQUIRE(K > 0 && K <= COVA_GAT_MAX_K && D > 0 && N > 0);
+    COVA_REQUIRE(csr && du && phi && edge_w && d_edge_w && workspace && ((uintptr_t)phi & 15) == 0);
+    return gat_bwd_launch<true>(g, ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, dt, d_att_w,
+                                d_att_b, csr, du, phi, edge_w, d_edge_w, workspace, stream);
 }

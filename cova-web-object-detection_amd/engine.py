@@ -1293,11 +1293,35 @@ def _adjacent(a, b):
             a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr())
 
 
-def gat_fwd(h, ldh, N, F, ctx, params, hprime, ldo, prefix="gat."):
-    """models.py:171-212.  h rows at h + n*ldh (F values); hprime rows at hprime + n*ldo (D)."""
+def edge_geometry(bboxes, ctx, page_size):
+    """phi [N, K, 8]: the relative geometry of every edge of the context table (include/cova_hip.h, cova_edge_geometry).
+    ``page_size`` = (height, width) of the pages in pixels, as ``images.shape[2:]``.  One launch per batch; every head
+    and layer of the GAT stack shares the result."""
+    _check(bboxes)
+    _check(ctx, torch.int64)
+    try:
+        H, W = (float(v) for v in page_size)
+    except (TypeError, ValueError):
+        raise ValueError("page_size must be (height, width) in pixels, got %r" % (page_size,))
+    if not (H > 0 and W > 0):
+        raise ValueError("page_size must be positive, got %r" % (page_size,))
+    N, K = ctx.shape
+    phi = _empty((N, K, 8), bboxes)
+    call("cova_edge_geometry", bboxes, ctx, N, K, W, H, phi)
+    return phi
+
+
+def gat_fwd(h, ldh, N, F, ctx, params, hprime, ldo, prefix="gat.", phi=None):
+    """models.py:171-212.  h rows at h + n*ldh (F values); hprime rows at hprime + n*ldo (D).
+    ``phi`` (edge_geometry): the score takes the edge term ``edge_layer.weight . phi`` (cova_gat_fwd_edge); a head that
+    has an ``edge_layer.weight`` needs it."""
     _check(ctx, torch.int64)
     Wi, Wj = params[prefix + "W_i.weight"], params[prefix + "W_j.weight"]
     aw, ab = params[prefix + "attention_layer.weight"], params[prefix + "attention_layer.bias"]
+    ew = params.get(prefix + "edge_layer.weight")
+    if (ew is None) != (phi is None):
+        raise ValueError("%s: %s" % (prefix, "an edge-aware head needs the edge features phi (boxes and page size)"
+                                     if phi is None else "edge features given to a head without edge_layer.weight"))
     D, K = Wi.shape[0], ctx.shape[1]
     Wh = _empty((N, 2 * D), h)
     if _adjacent(Wi, Wj):        # one [2D, F] matrix (flat parameter bucket): both projections in one GEMM
@@ -1306,8 +1330,13 @@ def gat_fwd(h, ldh, N, F, ctx, params, hprime, ldo, prefix="gat."):
         call("cova_sgemm", 0, 1, N, D, F, h, ldh, Wi, F, Wh, 2 * D, None, 0)
         call("cova_sgemm", 0, 1, N, D, F, h, ldh, Wj, F, Wh[:, D:], 2 * D, None, 0)
     s, t, attn = _empty((N,), h), _empty((N,), h), _empty((N, K), h)
-    call("cova_gat_fwd", Wh, 2 * D, aw, ab, ctx, N, K, D, LEAKY_SLOPE, s, t, attn, hprime, ldo)
-    return dict(h=h, ldh=ldh, N=N, F=F, D=D, K=K, ctx=ctx, Wh=Wh, s=s, t=t, attn=attn, prefix=prefix)
+    if phi is None:
+        call("cova_gat_fwd", Wh, 2 * D, aw, ab, ctx, N, K, D, LEAKY_SLOPE, s, t, attn, hprime, ldo)
+    else:
+        assert tuple(phi.shape) == (N, K, 8), (tuple(phi.shape), N, K)
+        call("cova_gat_fwd_edge", Wh, 2 * D, aw, ab, ctx, _check(phi), _check(ew), N, K, D, LEAKY_SLOPE, s, t, attn,
+             hprime, ldo)
+    return dict(h=h, ldh=ldh, N=N, F=F, D=D, K=K, ctx=ctx, Wh=Wh, s=s, t=t, attn=attn, prefix=prefix, phi=phi)
 
 
 # Backward of the neighbour gather: a deterministic gather through the transposed index (no float atomics).
@@ -1346,8 +1375,16 @@ def gat_bwd(sv, g, ldg, params, dh, lddh, accumulate_dh, gout=None, csr=None):
     ds, dt = _empty((N,), g), _empty((N,), g)
     daw = _gbuf(gout, prefix + "attention_layer.weight", (1, 2 * D), g)
     dab = _gbuf(gout, prefix + "attention_layer.bias", (1,), g)
-    call("cova_gat_bwd", g, ldg, sv["Wh"], 2 * D, sv["s"], sv["t"], sv["attn"], sv["ctx"], aw, N, K, D,
-         LEAKY_SLOPE, dWh, 2 * D, ds, dt, daw, dab, csr, du)
+    phi, edge = sv.get("phi"), {}
+    if phi is None:
+        call("cova_gat_bwd", g, ldg, sv["Wh"], 2 * D, sv["s"], sv["t"], sv["attn"], sv["ctx"], aw, N, K, D,
+             LEAKY_SLOPE, dWh, 2 * D, ds, dt, daw, dab, csr, du)
+    else:
+        dew = _gbuf(gout, prefix + "edge_layer.weight", (1, 8), g)
+        ws = _empty((query("cova_gat_edge_workspace_floats", N, K),), g)
+        call("cova_gat_bwd_edge", g, ldg, sv["Wh"], 2 * D, sv["s"], sv["t"], sv["attn"], sv["ctx"], aw, phi,
+             params[prefix + "edge_layer.weight"], N, K, D, LEAKY_SLOPE, dWh, 2 * D, ds, dt, daw, dab, dew, csr, du, ws)
+        edge = {prefix + "edge_layer.weight": dew}
     dWi = _gbuf(gout, prefix + "W_i.weight", (D, F), g)
     dWj = _gbuf(gout, prefix + "W_j.weight", (D, F), g)
     if _adjacent(dWi, dWj):
@@ -1360,22 +1397,30 @@ def gat_bwd(sv, g, ldg, params, dh, lddh, accumulate_dh, gout=None, csr=None):
     else:
         call("cova_sgemm", 0, 0, N, F, D, dWh, 2 * D, Wi, F, dh, lddh, None, 1 if accumulate_dh else 0)
         call("cova_sgemm", 0, 0, N, F, D, dWh[:, D:], 2 * D, Wj, F, dh, lddh, None, 1)
-    return {prefix + "W_i.weight": dWi, prefix + "W_j.weight": dWj,
-            prefix + "attention_layer.weight": daw, prefix + "attention_layer.bias": dab}
+    return dict({prefix + "W_i.weight": dWi, prefix + "W_j.weight": dWj,
+                 prefix + "attention_layer.weight": daw, prefix + "attention_layer.bias": dab}, **edge)
 
 
-def gat_stack_fwd(comb, T, N, F, D, ctx, params, n_heads=1, n_gat_layers=1):
+def gat_stack_fwd(comb, T, N, F, D, ctx, params, n_heads=1, n_gat_layers=1, bboxes=None, page_size=None,
+                  edge_geometry_on=False):
     """The reference's single GraphAttentionLayer (models.py:114) or the multi-head / stacked extension:
     every layer concatenates its heads (hidden_dim/n_heads channels each, written side by side), layers
-    are chained; the last one writes the context columns comb[:, F:]."""
+    are chained; the last one writes the context columns comb[:, F:].
+    ``edge_geometry_on``: the edge features of the batch (``bboxes``, ``page_size`` = (height, width)) are computed once
+    and handed to every head."""
     from .weights import gat_prefixes
     prefixes = gat_prefixes(n_heads, n_gat_layers)
+    phi = None
+    if edge_geometry_on:
+        if bboxes is None or page_size is None:
+            raise ValueError("edge_geometry needs the boxes and the page size (height, width)")
+        phi = edge_geometry(bboxes, ctx, page_size)
     dh = D // n_heads
     layers, h, ldh, fin = [], comb, T, F
     for l, heads in enumerate(prefixes):
         last = l == len(prefixes) - 1
         out, ldo = (comb[:, F:], T) if last else (_empty((N, D), comb), D)
-        svs = [gat_fwd(h, ldh, N, fin, ctx, params, out[:, i * dh:], ldo, prefix=p)
+        svs = [gat_fwd(h, ldh, N, fin, ctx, params, out[:, i * dh:], ldo, prefix=p, phi=phi)
                for i, p in enumerate(heads)]
         layers.append(dict(heads=svs, out=out))
         h, ldh, fin = out, ldo, D
@@ -1466,8 +1511,10 @@ def decoder_bwd(sv, dlogits, params, gout=None):
 # ------------------------------------------------------------------------------- whole model
 @on_device_of(3)
 def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_indices, training,
-              seeds=(0, 0), masks=None, save=True, plan=None, visual_feats=None):
+              seeds=(0, 0), masks=None, save=True, plan=None, visual_feats=None, page_size=None):
     """CoVA.forward (models.py:94-122) -> (logits [N,n_classes], saved-for-backward or None).
+    ``page_size`` = (height, width) of the pages, read by cfg["edge_geometry"] only: by default ``images.shape[2:]``; a batch
+    without images (``visual_feats``) must name it (DeviceDataset batches carry it) or cfg["page_size"] must.
     ``training``: a bool (whole model) or per-layer modes {BatchNorm prefix / Dropout name: bool} (is_train).
     ``plan`` (grad_plan, with ``save``): without its "convstack" stage the conv stack keeps no activations.
     ``visual_feats`` = (table [R, n_vis], row_ids int32 [N]) (features.FeatureCache): the conv stack and the RoI op are
@@ -1475,7 +1522,7 @@ def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_in
     "convstack" (nothing is kept to run that backward from)."""
     if visual_feats is not None:
         return _model_fwd_cached(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks,
-                                 save, plan, visual_feats)
+                                 save, plan, visual_feats, page_size)
     N = bboxes.shape[0]
     PH, PW = cfg["roi_output_size"]
     n_vis = (C256 if is_bottleneck(params) else C128 if has_layer2(params) else C64) * PH * PW
@@ -1488,7 +1535,8 @@ def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_in
     feat, sv_conv = convstack_fwd(images, params, buffers, training, save_conv, lazy_out=not align)
     comb = _empty((N, T), images)
     scale = cfg.get("spatial_scale") or feat.shape[1] / images.shape[2]   # models.py:56
-    sv = dict(cfg=cfg, N=N, F=F, D=D, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=sv_conv, comb=comb)
+    sv = dict(cfg=cfg, N=N, F=F, D=D, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=sv_conv, comb=comb,
+              page_size=page_size or cfg.get("page_size") or tuple(images.shape[2:]))
     if align:
         sv["roi"] = roialign_fwd(feat, bboxes, (PH, PW), scale, cfg.get("sampling_ratio", 2),
                                  cfg.get("roi_aligned", False), comb, T)
@@ -1508,8 +1556,12 @@ def _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, t
         sv["addl"] = bn1d_fwd(additional_feats, A, N, A, "bn_additional_feat.", params, buffers,
                               training, comb[:, n_vis + Hd:], T, False)
     if D > 0:
+        edge = bool(cfg.get("edge_geometry", False))
+        if edge and sv.get("page_size") is None:
+            raise ValueError("edge_geometry: a batch without images must carry page_size = (height, width) "
+                             "(or the configuration a 'page_size')")
         sv["gat"] = gat_stack_fwd(comb, T, N, F, D, context_indices, params, cfg.get("n_heads", 1),
-                                  cfg.get("n_gat_layers", 1))
+                                  cfg.get("n_gat_layers", 1), bboxes if edge else None, sv.get("page_size"), edge)
     logits, sv["dec"] = decoder_fwd(comb, N, T, params, buffers, training, cfg["drop_prob"], seeds,
                                     masks)
     return logits, (sv if save else None)
@@ -1540,7 +1592,7 @@ def check_visual_feats(cfg, visual_feats, N):
 
 @on_device_of(3)
 def _model_fwd_cached(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks, save, plan,
-                      visual_feats):
+                      visual_feats, page_size=None):
     """model_fwd with the visual columns taken from a feature table: no conv stack, no RoI op."""
     N = bboxes.shape[0]
     table, row_ids = check_visual_feats(cfg, visual_feats, N)
@@ -1553,7 +1605,8 @@ def _model_fwd_cached(cfg, params, buffers, bboxes, additional_feats, context_in
     D = cfg["hidden_dim"] if cfg["use_context"] else 0
     T = F + D
     comb = _empty((N, T), bboxes)
-    sv = dict(cfg=cfg, N=N, F=F, D=D, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=None, roi=None, comb=comb)
+    sv = dict(cfg=cfg, N=N, F=F, D=D, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=None, roi=None, comb=comb,
+              page_size=page_size or cfg.get("page_size"))
     call("cova_feat_rows_gather", table, table.shape[0], n_vis, row_ids, N, comb, T)
     return _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks, save, sv)
 

@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import engine
-from .weights import backbone_channels, check_backbone_layers
+from .weights import EDGE_FEATURES, backbone_channels, check_backbone_layers
 
 GAT_MAX_K = engine.GAT_MAX_K
 LOSS_MAX_CLASSES = engine.LOSS_MAX_CLASSES
@@ -254,14 +254,16 @@ class _HipBatchNorm1d(nn.BatchNorm1d):
 
 class _GATFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, layer, h_i, context_indices, W_i, W_j, att_w, att_b):
+    def forward(ctx, layer, h_i, context_indices, W_i, W_j, att_w, att_b, edge_w=None, phi=None):
         h = _f32c(h_i)
         N, F = h.shape
         params = {"gat.W_i.weight": W_i.detach(), "gat.W_j.weight": W_j.detach(),
                   "gat.attention_layer.weight": att_w.detach(),
                   "gat.attention_layer.bias": att_b.detach()}
+        if edge_w is not None:
+            params["gat.edge_layer.weight"] = edge_w.detach().contiguous()
         hp = torch.empty((N, layer.hidden_dim), device=h.device)
-        ctx.sv = engine.gat_fwd(h, F, N, F, _i64c(context_indices), params, hp, layer.hidden_dim)
+        ctx.sv = engine.gat_fwd(h, F, N, F, _i64c(context_indices), params, hp, layer.hidden_dim, phi=phi)
         ctx.params = params
         ctx.mark_non_differentiable(ctx.sv["attn"])
         return hp, ctx.sv["attn"]
@@ -272,7 +274,8 @@ class _GATFn(torch.autograd.Function):
         dh = torch.empty((sv["N"], sv["F"]), device=g.device)
         grads = engine.gat_bwd(sv, g.contiguous(), sv["D"], ctx.params, dh, sv["F"], False)
         return (None, dh, None, grads["gat.W_i.weight"], grads["gat.W_j.weight"],
-                grads["gat.attention_layer.weight"], grads["gat.attention_layer.bias"])
+                grads["gat.attention_layer.weight"], grads["gat.attention_layer.bias"],
+                grads.get("gat.edge_layer.weight"), None)
 
 
 # ------------------------------------------------------------------------------------- modules
@@ -291,35 +294,60 @@ def _check_gat_inputs(h_i, context_indices, in_features):
                              % (GAT_MAX_K, GAT_MAX_K // 2))
 
 
-class GraphAttentionLayer(nn.Module):
-    """Single-head additive attention over K padded neighbours (reference models.py:151-212)."""
+def _edge_features(context_indices, bboxes, page_size):
+    """phi [N, K, 8] of one batch for the edge-aware layers (engine.edge_geometry); ValueError without boxes / page size."""
+    if bboxes is None or page_size is None:
+        raise ValueError("an edge-aware GraphAttentionLayer (edge_geometry=True) needs bboxes [N, 5] and "
+                         "page_size = (height, width)")
+    _require_cuda(bboxes)
+    if bboxes.dim() != 2 or bboxes.shape[1] != 5 or bboxes.shape[0] != context_indices.shape[0]:
+        raise RuntimeError("expected bboxes [%d, 5], got %s" % (context_indices.shape[0], tuple(bboxes.shape)))
+    return engine.edge_geometry(_f32c(bboxes), _i64c(context_indices), page_size)
 
-    def __init__(self, in_features, hidden_dim, alpha=0.2):
+
+class GraphAttentionLayer(nn.Module):
+    """Single-head additive attention over K padded neighbours (reference models.py:151-212).
+    ``edge_geometry=True`` (extension): the score of an edge also takes ``edge_layer`` (Linear(8, 1), no bias, zero at
+    construction) of its relative-geometry features (include/cova_hip.h, cova_edge_geometry)."""
+
+    def __init__(self, in_features, hidden_dim, alpha=0.2, edge_geometry=False):
         super(GraphAttentionLayer, self).__init__()
         if abs(alpha - engine.LEAKY_SLOPE) > 1e-12:
             raise ValueError("the HIP path is built for the reference's LeakyReLU slope 0.2")
         self.in_features = in_features
         self.hidden_dim = hidden_dim
+        self.edge_geometry = bool(edge_geometry)
         self.W_i = nn.Linear(self.in_features, self.hidden_dim, bias=False)
         self.W_j = nn.Linear(self.in_features, self.hidden_dim, bias=False)
         self.attention_layer = nn.Linear(2 * self.hidden_dim, 1)
         self.leakyrelu = nn.LeakyReLU(alpha)
+        if self.edge_geometry:
+            self.edge_layer = nn.Linear(EDGE_FEATURES, 1, bias=False)
+            nn.init.zeros_(self.edge_layer.weight)
 
-    def forward(self, h_i, context_indices, return_attn_wts=False):
-        """h_i [N, in_features]; context_indices int64 [N, n_context] with -1 pads."""
+    def forward(self, h_i, context_indices, return_attn_wts=False, bboxes=None, page_size=None, phi=None):
+        """h_i [N, in_features]; context_indices int64 [N, n_context] with -1 pads.  An edge-aware layer also needs
+        ``bboxes`` [N, 5] and ``page_size`` = (height, width), or the ``phi`` [N, n_context, 8] computed from them."""
         _require_cuda(h_i, context_indices)
         _check_gat_inputs(h_i, context_indices, self.in_features)
-        h_prime, attn = _GATFn.apply(self, h_i, context_indices, self.W_i.weight, self.W_j.weight,
-                                     self.attention_layer.weight, self.attention_layer.bias)
+        if not self.edge_geometry:
+            h_prime, attn = _GATFn.apply(self, h_i, context_indices, self.W_i.weight, self.W_j.weight,
+                                         self.attention_layer.weight, self.attention_layer.bias)
+        else:
+            if phi is None:
+                phi = _edge_features(context_indices, bboxes, page_size)
+            h_prime, attn = _GATFn.apply(self, h_i, context_indices, self.W_i.weight, self.W_j.weight,
+                                         self.attention_layer.weight, self.attention_layer.bias,
+                                         self.edge_layer.weight, phi)
         if return_attn_wts:
             return h_prime, attn
         return h_prime
 
 
 class _GATHeads(nn.Module):
-    def __init__(self, in_features, hidden_dim, n_heads):
+    def __init__(self, in_features, hidden_dim, n_heads, edge_geometry=False):
         super().__init__()
-        self.heads = nn.ModuleList([GraphAttentionLayer(in_features, hidden_dim // n_heads)
+        self.heads = nn.ModuleList([GraphAttentionLayer(in_features, hidden_dim // n_heads, edge_geometry=edge_geometry)
                                     for _ in range(n_heads)])
 
 
@@ -328,19 +356,23 @@ class MultiHeadGraphAttention(nn.Module):
     models.py:78-79): ``n_layers`` stacked layers, each the concatenation of ``n_heads``
     GraphAttentionLayers of hidden_dim/n_heads channels over the same neighbour table.  Same call
     contract as GraphAttentionLayer; the attention weights returned are the last layer's, per head
-    [N, n_heads, n_context]."""
+    [N, n_heads, n_context].  ``edge_geometry``: every head is edge-aware; the features are computed once per call."""
 
-    def __init__(self, in_features, hidden_dim, n_heads, n_layers):
+    def __init__(self, in_features, hidden_dim, n_heads, n_layers, edge_geometry=False):
         super().__init__()
         if hidden_dim % n_heads:
             raise ValueError("hidden_dim must be divisible by n_heads")
-        self.layers = nn.ModuleList([_GATHeads(in_features if l == 0 else hidden_dim, hidden_dim, n_heads)
+        self.edge_geometry = bool(edge_geometry)
+        self.layers = nn.ModuleList([_GATHeads(in_features if l == 0 else hidden_dim, hidden_dim, n_heads, edge_geometry)
                                      for l in range(n_layers)])
 
-    def forward(self, h_i, context_indices, return_attn_wts=False):
+    def forward(self, h_i, context_indices, return_attn_wts=False, bboxes=None, page_size=None, phi=None):
         h, attn = h_i, None
+        if self.edge_geometry and phi is None:
+            _require_cuda(h_i, context_indices)
+            phi = _edge_features(context_indices, bboxes, page_size)
         for layer in self.layers:
-            outs = [head(h, context_indices, True) for head in layer.heads]
+            outs = [head(h, context_indices, True, phi=phi) for head in layer.heads]
             h = torch.cat([o for o, _ in outs], dim=1)
             attn = torch.stack([a for _, a in outs], dim=1)
         return (h, attn) if return_attn_wts else h
@@ -350,7 +382,7 @@ class CoVA(nn.Module):
     def __init__(self, roi_output_size, img_H, n_classes, use_context=True, hidden_dim=384,
                  bbox_hidden_dim=32, n_additional_feat=0, drop_prob=0.2, class_names=None,
                  backbone="resnet18", n_heads=1, n_gat_layers=1, backbone_state_dict=None, roi_op="pool",
-                 sampling_ratio=2, roi_aligned=False, backbone_layers=1):
+                 sampling_ratio=2, roi_aligned=False, backbone_layers=1, edge_geometry=False):
         """The first nine arguments exactly as the reference's CoVA (models.py:10-34; called positionally
         at main.py:122-132).  Keyword-only-in-practice extensions, whose defaults are the reference's
         model: ``backbone`` 'resnet18' | 'resnet50' (torchvision ``children()[:-5]`` of either),
@@ -361,7 +393,10 @@ class CoVA(nn.Module):
         (``sampling_ratio``, ``roi_aligned`` as in ``torchvision.ops.RoIAlign``).
         ``img_H`` is only used for the RoIPool scale (models.py:53-56): pages may be any H x W.
         ``backbone_layers=2`` (resnet18 only) keeps torchvision's ``layer2`` after layer1 (``children()[:-4]``): 128
-        channels at stride 8, parameters under ``convnet.5.``."""
+        channels at stride 8, parameters under ``convnet.5.``.
+        ``edge_geometry=True``: every attention head scores an edge with its relative box geometry as well (one
+        ``edge_layer.weight`` [1, 8] per head, zero at construction: the fresh model computes the plain model's output);
+        the page size is taken from ``images``."""
         check_backbone_layers(backbone, backbone_layers)
         if roi_op not in ("pool", "align"):
             raise ValueError("roi_op must be 'pool' (the reference, models.py:58) or 'align'")
@@ -414,9 +449,9 @@ class CoVA(nn.Module):
 
         if self.use_context:
             if n_heads == 1 and n_gat_layers == 1:
-                self.gat = GraphAttentionLayer(self.n_feat, self.hidden_dim)
+                self.gat = GraphAttentionLayer(self.n_feat, self.hidden_dim, edge_geometry=edge_geometry)
             else:
-                self.gat = MultiHeadGraphAttention(self.n_feat, self.hidden_dim, n_heads, n_gat_layers)
+                self.gat = MultiHeadGraphAttention(self.n_feat, self.hidden_dim, n_heads, n_gat_layers, edge_geometry)
         self.n_total_feat = self.n_feat + (self.hidden_dim if self.use_context else 0)
         self.decoder = nn.Sequential(nn.Dropout(drop_prob),
                                      nn.Linear(self.n_total_feat, self.n_total_feat),
@@ -430,7 +465,7 @@ class CoVA(nn.Module):
                          spatial_scale=self.roi_pool.spatial_scale, backbone=backbone,
                          n_heads=n_heads, n_gat_layers=n_gat_layers, roi_op=roi_op,
                          sampling_ratio=int(sampling_ratio), roi_aligned=bool(roi_aligned),
-                         backbone_layers=backbone_layers)
+                         backbone_layers=backbone_layers, edge_geometry=bool(edge_geometry) and bool(use_context))
         self._param_keys = [k for k, _ in self.named_parameters()]
         self._conv_keys = [k for k in self._param_keys if k.startswith("convnet.")]
         self._bbox_keys = [k for k in self._param_keys if k.startswith("bbox_feat_encoder.")]

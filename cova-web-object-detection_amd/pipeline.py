@@ -380,6 +380,7 @@ class DeviceDataset:
                 out["images"] = images
             else:       # the sampler's kept SOURCE row ids are the table's row ids (with sf == 1 it keeps every row)
                 out["visual_feats"] = (features.table, out.pop("sel"))
+            out["page_size"] = (self.H, self.W)        # host ints (edge geometry on a batch without images reads them)
             out["page_ids"] = ids64[int(starts64[step]):int(starts64[step + 1])]
             out["img_ids"] = self.img_ids[plan[step]]
             return out
@@ -459,7 +460,7 @@ def attention_rows(trainer, batch):
     """float32 [M, 5+5K] rows for the boxes with label > 0, eval mode (running statistics)."""
     _, sv = engine.model_fwd(trainer.cfg, trainer.params, trainer.buffers, batch["images"],
                              batch["bboxes"], batch["additional_feats"], batch["context_indices"],
-                             False, save=True)
+                             False, save=True, page_size=batch.get("page_size"))
     attn, ctx = sv["gat"][-1]["heads"][0]["attn"], batch["context_indices"]
     N, K = ctx.shape
     out = torch.empty((N, 5 + 5 * K), dtype=torch.float32, device=attn.device)

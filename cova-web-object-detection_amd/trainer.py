@@ -199,7 +199,8 @@ class HotPathTrainer:
         self.device = torch.device(device)
         spec = state_dict_spec(**{k: cfg[k] for k in ("roi_output_size", "n_classes", "use_context",
                                                      "hidden_dim", "bbox_hidden_dim", "n_additional_feat",
-                                                     "backbone", "n_heads", "n_gat_layers", "backbone_layers")
+                                                     "backbone", "n_heads", "n_gat_layers", "backbone_layers",
+                                                     "edge_geometry")
                                   if k in cfg})
         pshapes = OrderedDict((k, s) for k, s in spec if is_param_key(k))
         self.pbucket = FlatBucket(pshapes, self.device)
@@ -540,7 +541,7 @@ class HotPathTrainer:
             logits, sv = engine.model_fwd(self.cfg, self.params, self.buffers, batch.get("images"),
                                           batch["bboxes"], batch["additional_feats"],
                                           batch["context_indices"], self.modes, (base, base + 1), masks,
-                                          plan=self.plan, visual_feats=vis)
+                                          plan=self.plan, visual_feats=vis, page_size=batch.get("page_size"))
             if opts is None:
                 loss, dl, pred = engine.ce_sum(logits, batch["labels"])
             else:
@@ -691,7 +692,8 @@ class HotPathTrainer:
                            batch["context_indices"], False, vis)
         logits, _ = engine.model_fwd(self.cfg, self.params, self.buffers, batch.get("images"),
                                      batch["bboxes"], batch["additional_feats"],
-                                     batch["context_indices"], False, save=False, visual_feats=vis)
+                                     batch["context_indices"], False, save=False, visual_feats=vis,
+                                     page_size=batch.get("page_size"))
         _, _, pred = engine.ce_sum(logits, None, want_grad=False)
         return logits, pred
 

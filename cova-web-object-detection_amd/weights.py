@@ -14,6 +14,7 @@ import torch
 
 BACKBONE_CHANNELS = 64  # ResNet-18 conv1/layer1 width (models.py:49-51 keeps conv1..layer1)
 BACKBONE_STRIDE = 4     # conv1 stride 2 * maxpool stride 2
+EDGE_FEATURES = 8       # relative-geometry features per edge (include/cova_hip.h, cova_edge_geometry)
 
 
 def _bn_entries(prefix, c):
@@ -56,7 +57,7 @@ def gat_prefixes(n_heads=1, n_gat_layers=1):
 
 def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=384,
                     bbox_hidden_dim=32, n_additional_feat=0, backbone="resnet18", n_heads=1,
-                    n_gat_layers=1, backbone_layers=1):
+                    n_gat_layers=1, backbone_layers=1, edge_geometry=False):
     """Ordered (key, shape) list, identical to ``reference CoVA(...).state_dict()`` for the defaults.
 
     Extensions (BASELINE.json configs[2], configs[4]; absent from the reference, defaults keep its
@@ -65,7 +66,9 @@ def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidde
     GraphAttentionLayer heads of hidden_dim/n_heads channels each, concatenated, stacked n_gat_layers
     times (layer 0 reads the n_feat own features, later layers the previous layer's hidden_dim);
     ``backbone_layers=2`` = resnet18 ``children()[:-4]``: layer2 (two BasicBlocks, 64 -> 128 channels at stride 2, block 0
-    with the 1x1 downsample) under ``convnet.5.`` with torchvision's key names."""
+    with the 1x1 downsample) under ``convnet.5.`` with torchvision's key names;
+    ``edge_geometry=True`` = one ``edge_layer.weight`` [1, 8] per attention head, behind its ``attention_layer.bias`` (W_i and
+    W_j stay adjacent): the weights of the relative-geometry term of the attention score (cova_edge_geometry)."""
     check_backbone_layers(backbone, backbone_layers)
     c = BACKBONE_CHANNELS
     spec = [("convnet.0.weight", (c, 3, 7, 7))]
@@ -122,6 +125,8 @@ def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidde
                          (p + "W_j.weight", (dh, fin)),
                          (p + "attention_layer.weight", (1, 2 * dh)),
                          (p + "attention_layer.bias", (1,))]
+                if edge_geometry:
+                    spec.append((p + "edge_layer.weight", (1, EDGE_FEATURES)))
         n_total += hidden_dim
     spec += [("decoder.1.weight", (n_total, n_total)), ("decoder.1.bias", (n_total,))]
     spec += _bn_entries("decoder.2.", n_total)
@@ -136,6 +141,8 @@ def seeded_state_dict(seed=123, logit_gain=1.0, **cfg):
     weights/biases ~ U(+-1/sqrt(fan_in)) (torch's default), BN affine/running stats away
     from their trivial values so that every BN term is exercised.  ``logit_gain`` scales
     the last Linear so that integer-prediction tests have decisive logit margins.
+    ``edge_layer.weight`` (edge_geometry=True) starts at ZERO without drawing from the stream: a fresh edge-aware model
+    computes what the plain model of the same seed computes.
     """
     rs = np.random.RandomState(seed)
     spec = state_dict_spec(**cfg)
@@ -146,6 +153,9 @@ def seeded_state_dict(seed=123, logit_gain=1.0, **cfg):
         is_bn = prefix in bn_prefixes
         if leaf == "num_batches_tracked":
             sd[key] = torch.tensor(0, dtype=torch.long)
+            continue
+        if prefix.endswith("edge_layer"):
+            sd[key] = torch.zeros(shape, dtype=torch.float32)
             continue
         if leaf == "running_mean":
             v = 0.1 * rs.standard_normal(shape)

@@ -426,6 +426,29 @@ int cova_gat_bwd(const float *g, int ldg, const float *Wh, int ldw, const float 
                  float slope, float *dWh /*[N,2D]*/, int lddw, float *ds /*[N]*/, float *dt /*[N]*/,
                  float *d_att_w /*[2D]*/, float *d_att_b /*[1]*/, const int *csr /*nullable*/,
                  float *du /*nullable [N,K]*/, void *stream);
+/* ---- edge geometry in the attention score (opt-in: CoVA(edge_geometry=True); the reference has no such term) ----
+ * cova_gat_fwd_edge: cova_gat_fwd with the pre-activation of slot k of node i extended by an additive edge term,
+ *   u = s[i] + t[j] + sum_e edge_w[e] * phi[i,k,e]   (one fma chain, e ascending, added to s[i] + t[j] last),
+ * phi [N,K,8] from cova_edge_geometry (16-byte aligned), edge_w [8] (`edge_layer.weight`, no bias: att_b is there).
+ * LeakyReLU, the -9e15 mask, softmax and aggregation are cova_gat_fwd's; pads and ids >= N read no phi.  With edge_w = 0
+ * every output has cova_gat_fwd's bits.  The same launches as cova_gat_fwd (scores, then the EDGE instantiation of the
+ * wave-per-node kernel): no LDS, no workspace, capturable. */
+int cova_gat_fwd_edge(const float *Wh, int ldw, const float *att_w /*[2D]*/, const float *att_b /*[1]*/,
+                      const int64_t *ctx /*[N,K]*/, const float *phi /*[N,K,8]*/, const float *edge_w /*[8]*/, int N,
+                      int K, int D, float slope, float *s /*[N]*/, float *t /*[N]*/, float *attn /*[N,K]*/,
+                      float *hprime, int ldh, void *stream);
+/* cova_gat_bwd_edge: cova_gat_bwd's gather form (csr and du are REQUIRED; the scatter form with float atomics is not
+ * extended) for a forward made by cova_gat_fwd_edge: the LeakyReLU slope of a slot follows the forward's u bit for bit.
+ * Also d_edge_w[e] = sum_{i,k} du[i,k] * phi[i,k,e] [8]: per-block partials of fixed 4096-slot chunks in `workspace`
+ * (cova_gat_edge_workspace_floats(N, K) floats), then summed in index order by one block -- no atomics, bits independent
+ * of timing and grid.  There is no gradient with respect to the boxes.  With edge_w = 0, dWh / d_att_w / d_att_b have
+ * cova_gat_bwd's bits. */
+int cova_gat_edge_workspace_floats(int N, int K);
+int cova_gat_bwd_edge(const float *g, int ldg, const float *Wh, int ldw, const float *s, const float *t,
+                      const float *attn, const int64_t *ctx, const float *att_w, const float *phi /*[N,K,8]*/,
+                      const float *edge_w /*[8]*/, int N, int K, int D, float slope, float *dWh /*[N,2D]*/, int lddw,
+                      float *ds /*[N]*/, float *dt /*[N]*/, float *d_att_w /*[2D]*/, float *d_att_b /*[1]*/,
+                      float *d_edge_w /*[8]*/, const int *csr, float *du /*[N,K]*/, float *workspace, void *stream);
 
 /* ------------------------------------------------------------------ decoder tail, loss, optimizer
  * replaces: nn.Dropout (models.py:84,88), nn.Linear(T, n_classes) (models.py:89),
@@ -596,6 +619,21 @@ int cova_collate_selected(const float *rows, const int *sel, const int *out_offs
  *   One launch (one wave per box), no workspace, no atomics, no host read: capturable and bit-deterministic. */
 int cova_context_knn(const float *bboxes, const int *page_offsets, int B, int N, int context_size, int k_spatial,
                      long long *ctx, void *stream);
+/* cova_edge_geometry: phi [N,K,8] float32 (16-byte aligned), the relative geometry of every edge of a context table; computed
+ *   once per batch and shared by every head and layer.  Slot k of box i, neighbour j = ctx[i,k] (batch-global id), boxes =
+ *   columns 1..4 of bboxes [N,5], w = x2 - x1, h = y2 - y1, W = img_w, H = img_h (pixels).  float32, EVERY operation rounded on
+ *   its own (no fused multiply-add), `/` correctly rounded:
+ *     phi0 = ((x1_j + x2_j) - (x1_i + x2_i)) / (2*W)           phi1 likewise in y with H     centre offset
+ *     phi2 = (w_j - w_i) / ((w_j + w_i) + 1)                   phi3 likewise with h          size contrast
+ *     phi4 = max(0, max(x1_i,x1_j) - min(x2_i,x2_j)) / W       phi5 likewise in y with H     the gap of cova_context_knn
+ *     phi6 = uni > 0 ? inter / uni : 0                                                       IoU, with
+ *            iw = max(0, min(x2_i,x2_j) - max(x1_i,x1_j)), ih likewise, inter = iw*ih, uni = ((w_i*h_i) + (w_j*h_j)) - inter
+ *     phi7 = clamp(j - i, -64, 64) / 64                                                      DOM-order offset (exact)
+ *   A pad (j < 0) or an id >= N (a pad to the GAT kernels too) gives eight zeros; no box is read for it.  Bit-equal to the
+ *   numpy float32 statement (tests/edge_oracle.py) for finite boxes with x2 >= x1, y2 >= y1; anything else is memory-safe and
+ *   deterministic.  One launch, one thread per slot: no LDS, no workspace, no atomics, no host read, capturable. */
+int cova_edge_geometry(const float *bboxes, const long long *ctx, int N, int K, float img_w, float img_h, float *phi,
+                       void *stream);
 /* attention export rows (extract_attn_wts_and_visualize.py:104-135): out [N, 5+5K] =
  * x,y,w,h,label, K x (x,y,w,h) of the context boxes (0 for pads), K attention weights */
 int cova_attn_export_rows(const float *bboxes, const long long *ctx, const float *attn,
