@@ -1720,3 +1720,42 @@ def ce_loss_bwd(logits, labels, class_weight, opts, acc, grad_scale=None, want_l
     call("cova_ce_loss_bwd", logits, labels, N, NC, class_weight, *_loss_args(opts), acc,
          1 if opts.get("reduction", "sum") == "mean" else 0, grad_scale, loss, dl)
     return loss, dl
+
+
+# ------------------------------------------------------------------------------------------- hard-negative mining
+MINED_OUT = -(1 << 63)      # drop label of a caller without an ignore label of its own: no class, no torch default
+
+
+def check_mining_options(ratio, min_keep=0):
+    """Host validation of the mining options (ValueError each) -> (ratio as float or None = off, min_keep as int)."""
+    import math
+    import numbers
+    if ratio is not None:
+        if isinstance(ratio, bool) or not isinstance(ratio, numbers.Real) or not math.isfinite(ratio) or ratio < 0:
+            raise ValueError("hard_negative_ratio must be None (off) or a finite number >= 0, got %r" % (ratio,))
+        ratio = float(ratio)
+    if isinstance(min_keep, bool) or not isinstance(min_keep, numbers.Integral) or min_keep < 0:
+        raise ValueError("hard_negative_min must be an integer >= 0, got %r" % (min_keep,))
+    return ratio, int(min_keep)
+
+
+def hard_negative_select(logits, labels, page_start, ratio, min_keep, drop_label, want_scores=False, want_counts=False):
+    """cova_hard_negative_select: per page (``page_start`` device int64 [B+1]) keep the positives and the
+    max(min_keep, floor(ratio * positives)) background rows with the highest lse - l[0]; the other background rows get
+    ``drop_label`` -> (labels_out int64 [N], scores f32 [N] or None, counts int32 [B, 3] = positives, background, kept
+    background, or None).  One launch, no host read."""
+    ratio, min_keep = check_mining_options(ratio, min_keep)
+    if ratio is None:
+        raise ValueError("hard_negative_select needs a ratio (None means that mining is off)")
+    N, NC = logits.shape
+    B = page_start.shape[0] - 1
+    if page_start.dim() != 1 or B < 1 or labels.shape != (N,):
+        raise ValueError("hard_negative_select takes logits [N, C], labels [N] and page_start [B + 1], B >= 1; got %s, %s, %s"
+                         % (tuple(logits.shape), tuple(labels.shape), tuple(page_start.shape)))
+    _check(logits), _check(labels, torch.int64), _check(page_start, torch.int64)
+    out = _empty((N,), logits, torch.int64)
+    scores = _empty((N,), logits) if want_scores else None
+    counts = _empty((B, 3), logits, torch.int32) if want_counts else None
+    call("cova_hard_negative_select", logits, labels, page_start, B, N, NC, ratio, min_keep, int(drop_label), out, scores,
+         counts)
+    return out, scores, counts

@@ -571,9 +571,15 @@ class CrossEntropyLoss(nn.Module):
     w[y] (1-p_y)^gamma (-log p_y); not together with label_smoothing).  ``forward(logits [N, C] f32, labels [N] int64)``
     returns the device scalar.  Differences from torch: reduction "none" and probability targets are
     not implemented; "mean" over a zero denominator (every box ignored) gives 0 with a zero gradient, not NaN; a label
-    outside [0, C) that is not ``ignore_index`` is skipped like an ignored one instead of raising a device assert."""
+    outside [0, C) that is not ``ignore_index`` is skipped like an ignored one instead of raising a device assert.
 
-    def __init__(self, weight=None, ignore_index=-100, reduction="mean", label_smoothing=0.0, focal_gamma=0.0):
+    ``hard_negative_ratio`` (None: off) and ``hard_negative_min`` add per-page hard-negative mining:
+    ``forward(logits, labels, page_start)`` with the pages' row offsets (device int64 [B + 1]) first relabels, without
+    gradient, every background row (label 0) outside its page's max(hard_negative_min, floor(ratio * positives)) hardest
+    as ``ignore_index`` (one cova_hard_negative_select launch) and scores the rest."""
+
+    def __init__(self, weight=None, ignore_index=-100, reduction="mean", label_smoothing=0.0, focal_gamma=0.0,
+                 hard_negative_ratio=None, hard_negative_min=0):
         super().__init__()
         if reduction == "none":
             raise ValueError('reduction="none" (per-box losses) is not implemented; use "mean" or "sum"')
@@ -588,8 +594,13 @@ class CrossEntropyLoss(nn.Module):
         ig = int(ignore_index)
         self.ignore_index, self.reduction = ig, reduction
         self.label_smoothing, self.focal_gamma = float(label_smoothing), float(focal_gamma)
+        self.hard_negative_ratio, self.hard_negative_min = engine.check_mining_options(hard_negative_ratio,
+                                                                                       hard_negative_min)
 
-    def forward(self, input, target):
+    def forward(self, input, target, page_start=None):
+        if self.hard_negative_ratio is not None and page_start is None:
+            raise ValueError("CrossEntropyLoss(hard_negative_ratio=...) needs page_start (the pages' row offsets, "
+                             "int64 [B + 1]) as the third argument of forward")
         _require_cuda(input, target)
         if input.dim() != 2 or target.dim() != 1 or target.shape[0] != input.shape[0]:
             raise ValueError("CrossEntropyLoss takes logits [N, C] and class labels [N], got %s and %s"
@@ -602,8 +613,17 @@ class CrossEntropyLoss(nn.Module):
                                          None, self.reduction)
         # torch's ignore_index may name a class (rows of that class are then skipped): no range check here
         opts["ignore_index"] = self.ignore_index
+        if self.hard_negative_ratio is not None:
+            _require_cuda(page_start)
+            with torch.no_grad():
+                target, _, _ = engine.hard_negative_select(_f32c(input.detach()), _i64c(target), _i64c(page_start),
+                                                           self.hard_negative_ratio, self.hard_negative_min,
+                                                           self.ignore_index)
         return _CELossFn.apply(input, target, self.weight, opts)
 
     def extra_repr(self):
-        return "ignore_index=%d, reduction=%r, label_smoothing=%g, focal_gamma=%g" % (
+        s = "ignore_index=%d, reduction=%r, label_smoothing=%g, focal_gamma=%g" % (
             self.ignore_index, self.reduction, self.label_smoothing, self.focal_gamma)
+        if self.hard_negative_ratio is not None:
+            s += ", hard_negative_ratio=%g, hard_negative_min=%d" % (self.hard_negative_ratio, self.hard_negative_min)
+        return s

@@ -184,13 +184,22 @@ class HotPathTrainer:
     ``focal_gamma`` (0 or >= 1), ``ignore_index`` (a label outside [0, n_classes): such boxes stay graph context but are
     not scored), ``loss_reduction`` "sum" | "mean" (under data parallelism the mean over the GLOBAL batch) and
     ``track_metrics`` (``trainer.metrics``: confusion counts and loss sums kept on the device).  Any of them takes the step
-    from cova_ce_sum to cova_ce_loss_fwd / cova_ce_loss_bwd; with none of them set the step is today's cova_ce_sum."""
+    from cova_ce_sum to cova_ce_loss_fwd / cova_ce_loss_bwd; with none of them set the step is today's cova_ce_sum.
+
+    Hard-negative mining ("Hard-negative mining"): ``hard_negative_ratio`` (None: off) and
+    ``hard_negative_min``: after the forward each page keeps its labelled boxes and the max(hard_negative_min,
+    floor(hard_negative_ratio * labelled boxes)) background boxes with the highest plain cross-entropy; the other
+    background boxes are not scored in this step (they stay graph context, ``pred`` still covers them, ``metrics`` count
+    the scored rows only).  One cova_hard_negative_select launch between the forward and the criterion, which then runs
+    through cova_ce_loss_fwd / cova_ce_loss_bwd; ``last_mined_labels`` / ``last_mining_counts`` hold the step's selection
+    on the device.  loss() and evaluation score every row."""
 
     def __init__(self, cfg, state_dict, device, lr=5e-4, weight_decay=1e-3, betas=(0.9, 0.999),
                  eps=1e-8, world_size=1, process_group=None, dropout_seed=123, sync_bn=False, frozen=(), bn_eval=(),
                  optimizer="adam", momentum=0.0, dampening=0.0, nesterov=False, param_groups=None,
                  max_grad_norm=None, norm_type=2.0, class_weight=None, label_smoothing=0.0, focal_gamma=0.0,
-                 ignore_index=None, loss_reduction="sum", track_metrics=False):
+                 ignore_index=None, loss_reduction="sum", track_metrics=False, hard_negative_ratio=None,
+                 hard_negative_min=0):
         if optimizer not in OPTIMIZERS:
             raise ValueError("optimizer must be one of %s, got %r" % (OPTIMIZERS, optimizer))
         if float(norm_type) != 2.0:
@@ -222,6 +231,7 @@ class HotPathTrainer:
         self._setup_finetune(tuple(frozen), tuple(bn_eval))
         self._setup_optimizer(optimizer, momentum, dampening, nesterov, param_groups, max_grad_norm)
         self._setup_criterion(class_weight, label_smoothing, focal_gamma, ignore_index, loss_reduction, track_metrics)
+        self._setup_mining(hard_negative_ratio, hard_negative_min)
         self._ar_events = []              # (start, end) HIP events around the collective waits of optimizer_step
         self.measure_allreduce = True     # record them (up to 4096 steps; exposed_allreduce_ms() drains the list)
         if world_size > 1:
@@ -332,10 +342,40 @@ class HotPathTrainer:
         self.metrics = LossMetrics(nc, self.device, self) if track_metrics else None
         self._loss_ws = None
 
-    def _criterion(self):
-        """None: the step's criterion is cova_ce_sum (no option set); else the checked options of this step."""
+    def _setup_mining(self, ratio, min_keep):
+        """The mining options join ``loss_options`` only when a ratio is given (a default trainer's dict stays as it
+        was); like the other scalar options they are read and checked at every step, so setting
+        ``loss_options["hard_negative_ratio"]`` between steps turns mining on or off."""
+        ratio, min_keep = engine.check_mining_options(ratio, min_keep)
+        if ratio is not None:
+            self.loss_options.update(hard_negative_ratio=ratio, hard_negative_min=min_keep)
+        self.last_mined_labels = self.last_mining_counts = None
+
+    def _mining(self):
+        """None: mining is off; else this step's checked (ratio, min_keep)."""
         o = self.loss_options
-        if (self.class_weight is None and self.metrics is None and o["label_smoothing"] == 0.0
+        ratio, min_keep = engine.check_mining_options(o.get("hard_negative_ratio"), o.get("hard_negative_min", 0))
+        return None if ratio is None else (ratio, min_keep)
+
+    def _mine(self, logits, batch, opts, mining):
+        """cova_hard_negative_select on this step's logits -> (labels for the criterion, its options with the drop
+        label as the ignore label).  No host read: page_start is the batch's, or comes from the page column of the
+        page-sorted bboxes."""
+        page_start = batch.get("page_start")
+        if page_start is None:
+            pages = torch.arange(int(batch["images"].shape[0]) + 1, dtype=torch.float32, device=logits.device)
+            page_start = torch.searchsorted(batch["bboxes"][:, 0].contiguous(), pages)
+        if opts["ignore_index"] is None:
+            opts = dict(opts, ignore_index=engine.MINED_OUT)
+        mined, _, counts = engine.hard_negative_select(logits, batch["labels"], page_start.contiguous(), mining[0],
+                                                       mining[1], opts["ignore_index"], want_counts=True)
+        self.last_mined_labels, self.last_mining_counts = mined, counts
+        return mined, opts
+
+    def _criterion(self):
+        """None: the step's criterion is cova_ce_sum (no option set, no mining); else the checked options of this step."""
+        o = self.loss_options
+        if (self._mining() is None and self.class_weight is None and self.metrics is None and o["label_smoothing"] == 0.0
                 and o["focal_gamma"] == 0.0 and o["ignore_index"] is None and o["loss_reduction"] == "sum"):
             return None
         return engine.check_loss_options(int(self.cfg["n_classes"]), None, o["label_smoothing"], o["focal_gamma"],
@@ -523,7 +563,9 @@ class HotPathTrainer:
         with criterion options the local sum ("sum") / the mean over the global batch ("mean").  A batch with
         ``visual_feats`` (DeviceDataset.batches(features=)) skips the conv stack and the RoI op; it raises ValueError
         unless the conv stack is frozen with its BatchNorms in eval mode."""
-        opts = self._criterion()
+        opts, mining = self._criterion(), self._mining()
+        if mining is not None and batch.get("page_start") is None and batch.get("images") is None:
+            raise ValueError("hard-negative mining needs the batch's page_start (or its images, for the page count)")
         # With SyncBN a one-box shard is legal (the statistics are over the whole batch, as torch.nn.SyncBatchNorm
         # accepts it): the train-mode "more than 1 value per channel" check then applies to the GLOBAL box count, which
         # _stat_sync has from its all-reduce -- every rank raises together instead of one rank leaving the others
@@ -545,7 +587,10 @@ class HotPathTrainer:
             if opts is None:
                 loss, dl, pred = engine.ce_sum(logits, batch["labels"])
             else:
-                loss, dl, pred = self._criterion_fwd_bwd(logits, batch["labels"], opts,
+                labels = batch["labels"]
+                if mining is not None:
+                    labels, opts = self._mine(logits, batch, opts, mining)
+                loss, dl, pred = self._criterion_fwd_bwd(logits, labels, opts,
                                                          None if self.metrics is None else self.metrics.buf)
             self._head_work = None
             overlap = self.world_size > 1 and engine.OPTIONS.overlap_allreduce

@@ -530,6 +530,27 @@ int cova_ce_loss_bwd(const float *logits, const int64_t *labels, int N, int NC, 
                      double label_smoothing, double focal_gamma, long long ignore_index, int has_ignore_index,
                      const double *acc_total, int reduction_mean, const float *grad_scale /*nullable*/,
                      float *loss_out /*nullable*/, float *dlogits /*nullable*/, void *stream);
+/* per-page hard-negative mining (mine.hip; HotPathTrainer(hard_negative_ratio=, hard_negative_min=) and
+ * models.CrossEntropyLoss(hard_negative_ratio=)): between the forward and cova_ce_loss_fwd, every page keeps its positives
+ * and its k hardest background rows; the other background rows get drop_label (the criterion's ignore label) in labels_out.
+ * Page p owns rows [s_p, e_p), s_p = clamp(page_start[p], 0, N), e_p = clamp(page_start[p+1], s_p, N) (page_start DEVICE
+ * int64 [B+1], non-decreasing by the caller's contract; otherwise the only guarantee is that no access is out of bounds).
+ * A row of a page is positive when 1 <= label < NC, background when label == 0; any other label (the caller's ignore
+ * label, a bad label) is neither and passes through.  Quota, in float64 on the device:
+ *   q = max((double)min_keep, floor(ratio * (double)n_pos)),  k_p = q >= n_bg ? n_bg : (int)q.
+ * Score of a row: its cross-entropy against background, s = lse - l[0], in f32 with cova_ce_loss_fwd's row arithmetic
+ * (max, expf sum, m + logf(se)); class weights, smoothing and the focal term play no part.  Key (uint32): 0x7FC00000 when
+ * s is NaN (above +inf: a NaN row is kept and surfaces in the loss), the bits of s when s > 0, else 0.
+ *   rank_n = #{background rows j of the page: key_j > key_n, or key_j == key_n and j < n}
+ *   labels_out[n] = drop_label for a background row with rank_n >= k_p, else labels[n].
+ * Every one of the N entries of labels_out is written; rows before page_start[0] or from page_start[B] on keep their label.
+ * score_out (nullable) receives s_n of every row n in [0, N), counts (nullable) DEVICE int32 [B,3] = n_pos, n_bg, k_p.
+ * 2 <= NC <= 16, B >= 1, N >= 1, ratio finite and >= 0, min_keep >= 0; any page size (0, 1, thousands of rows: a page of
+ * more than 2048 rows walks its keys in LDS tiles).  One launch, one block per page, no workspace, no atomics, no host
+ * read: bit-reproducible, a page's result does not depend on the batch around it. */
+int cova_hard_negative_select(const float *logits, const int64_t *labels, const int64_t *page_start, int B, int N, int NC,
+                              double ratio, int min_keep, long long drop_label, int64_t *labels_out /*[N]*/,
+                              float *score_out /*nullable [N]*/, int *counts /*nullable [B,3]*/, void *stream);
 /* evaluation decision (train.py:131-153): per page and class column, page-local indices of the k
  * highest-scoring boxes, best first; page_start [n_pages+1] are box offsets; out [n_pages,NC,k] */
 int cova_page_class_topk(const float *logits, const int64_t *page_start, int n_pages, int NC, int k,

@@ -1,0 +1,157 @@
+"""Host logic of per-page hard-negative mining (no GPU): tests/mining_oracle.py against a brute-force count, the key
+order and the quota of the contract, the refusals of engine.check_mining_options / HotPathTrainer / CrossEntropyLoss, what
+the defaults leave as before, and the declared entry point."""
+import ctypes
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.abspath(os.path.dirname(__file__)))
+import cova_amd  # noqa: E402,F401
+from cova_web_object_detection_amd import _lib, engine, weights  # noqa: E402
+from cova_web_object_detection_amd.models import CrossEntropyLoss  # noqa: E402
+from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
+import mining_oracle as MO  # noqa: E402
+
+CFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8,
+           n_additional_feat=0, drop_prob=0.0)
+SD = weights.seeded_state_dict(3, **{k: v for k, v in CFG.items() if k != "drop_prob"})
+
+
+def brute_force(scores, labels, page_start, nc, ratio, min_keep, drop):
+    """the contract's rank as an O(n^2) count, with keys compared as Python integers"""
+    key = [int(k) for k in MO.keys(scores)]
+    out = [int(v) for v in labels]
+    counts = []
+    for s, e in MO.page_bounds(page_start, len(out)):
+        bg = [n for n in range(s, e) if labels[n] == 0]
+        n_pos = sum(1 for n in range(s, e) if 1 <= labels[n] < nc)
+        k = MO.quota(ratio, min_keep, n_pos, len(bg))
+        counts.append((n_pos, len(bg), k))
+        for n in bg:
+            rank = sum(1 for j in bg if key[j] > key[n] or (key[j] == key[n] and j < n))
+            if rank >= k:
+                out[n] = drop
+    return np.asarray(out, dtype=np.int64), np.asarray(counts, dtype=np.int32).reshape(-1, 3)
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_oracle_equals_the_brute_force_count(seed):
+    rs = np.random.RandomState(seed)
+    nc, sizes = 4, [0, 1, 7, 40, 23, 2]
+    n = 3 + sum(sizes) + 4
+    page_start = 3 + np.concatenate([[0], np.cumsum(sizes)])
+    labels = np.where(rs.rand(n) < 0.8, 0, rs.randint(1, nc, n)).astype(np.int64)
+    labels[rs.rand(n) < 0.1] = -100
+    labels[rs.rand(n) < 0.05] = nc + 3
+    scores = (rs.randint(0, 6, n) * 0.5).astype(np.float32)          # few distinct values: many ties
+    scores[rs.rand(n) < 0.05] = np.nan
+    scores[rs.rand(n) < 0.05] = np.inf
+    scores[rs.rand(n) < 0.05] = -0.25
+    for ratio, min_keep in ((3, 2), (0, 0), (0.5, 1), (1e9, 0)):
+        got = MO.select_from_scores(scores, labels, page_start, nc, ratio, min_keep, -7)
+        want = brute_force(scores, labels, page_start, nc, ratio, min_keep, -7)
+        assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), (ratio, min_keep)
+        outside = np.r_[0:3, n - 4:n]
+        assert np.array_equal(got[0][outside], labels[outside])
+
+
+def test_key_order():
+    s = np.asarray([0.0, -0.0, 1e-45, 1.0, np.inf, np.nan, -3.0], dtype=np.float32)
+    k = MO.keys(s).tolist()
+    assert k == [0, 0, 1, 0x3F800000, 0x7F800000, 0x7FC00000, 0]
+    assert k[0] == k[1] == k[6] < k[2] < k[3] < k[4] < k[5]
+    # a NaN of any payload or sign gets the one key
+    odd = np.asarray([0xFFC00001, 0x7F800001], dtype=np.uint32).view(np.float32)
+    assert MO.keys(odd).tolist() == [0x7FC00000] * 2
+    k64 = MO.keys(s.astype(np.float64)).tolist()
+    assert k64[0] == k64[1] == k64[6] == 0 < k64[2] < k64[3] < k64[4] < k64[5]
+    # equal keys go to the lower index; NaN first, then inf
+    labels = np.zeros(7, dtype=np.int64)
+    out, counts = MO.select_from_scores(s, labels, [0, 7], 4, 0, 3, -1)
+    assert out.tolist() == [-1, -1, -1, 0, 0, 0, -1] and counts.tolist() == [[0, 7, 3]]
+    out, _ = MO.select_from_scores(s, labels, [0, 7], 4, 0, 5, -1)
+    assert out.tolist() == [0, -1, 0, 0, 0, 0, -1]               # ... 1, the denormal, then the first of the zeros
+
+
+def test_quota():
+    assert MO.quota(2.5, 0, 3, 100) == 7               # floor(7.5)
+    assert MO.quota(0.3, 0, 3, 100) == 0               # floor(0.9)
+    assert MO.quota(0.3, 2, 3, 100) == 2               # min_keep wins
+    assert MO.quota(0, 0, 3, 100) == 0
+    assert MO.quota(3, 0, 0, 100) == 0 and MO.quota(3, 4, 0, 100) == 4     # a page without a positive
+    assert MO.quota(3, 0, 50, 100) == 100 and MO.quota(3, 0, 50, 0) == 0   # more than there is
+    assert MO.quota(1e300, 0, 10, 5) == 5 and MO.quota(0, 10 ** 9, 0, 5) == 5
+    assert MO.quota(0.1, 0, 30, 100) == 3 and MO.quota(1 / 3, 0, 3, 100) == int(np.floor((1 / 3) * 3.0))
+
+
+def test_check_mining_options():
+    assert engine.check_mining_options(None, 0) == (None, 0)
+    assert engine.check_mining_options(3, 2) == (3.0, 2) and engine.check_mining_options(0.0) == (0.0, 0)
+    assert engine.check_mining_options(np.float32(1.5), np.int64(4)) == (1.5, 4)
+    for bad in (-1, -0.5, float("nan"), float("inf"), "3", True):
+        with pytest.raises(ValueError, match="hard_negative_ratio"):
+            engine.check_mining_options(bad, 0)
+    for bad in (-1, 1.5, None, "2", True):
+        with pytest.raises(ValueError, match="hard_negative_min"):
+            engine.check_mining_options(3.0, bad)
+    with pytest.raises(ValueError, match="hard_negative_min"):
+        engine.check_mining_options(None, -1)
+    assert engine.MINED_OUT == -(1 << 63) == torch.iinfo(torch.int64).min
+
+
+@pytest.mark.parametrize("kw, match", [
+    (dict(hard_negative_ratio=-1.0), "hard_negative_ratio"),
+    (dict(hard_negative_ratio=float("nan")), "hard_negative_ratio"),
+    (dict(hard_negative_ratio=float("inf")), "hard_negative_ratio"),
+    (dict(hard_negative_ratio=3.0, hard_negative_min=-1), "hard_negative_min"),
+    (dict(hard_negative_ratio=3.0, hard_negative_min=0.5), "hard_negative_min"),
+    (dict(hard_negative_min=-2), "hard_negative_min"),
+])
+def test_trainer_and_module_refuse_bad_mining_arguments(kw, match):
+    with pytest.raises(ValueError, match=match):
+        HotPathTrainer(CFG, SD, "cpu", **kw)
+    with pytest.raises(ValueError, match=match):
+        CrossEntropyLoss(**kw)
+
+
+def test_trainer_options():
+    plain = HotPathTrainer(CFG, SD, "cpu")
+    assert plain._mining() is None and plain._criterion() is None and plain.loss_path == "cova_ce_sum"
+    assert plain.loss_options == dict(label_smoothing=0.0, focal_gamma=0.0, ignore_index=None, loss_reduction="sum")
+    assert plain.last_mined_labels is None and plain.last_mining_counts is None
+    tr = HotPathTrainer(CFG, SD, "cpu", hard_negative_ratio=3, hard_negative_min=2)
+    assert tr._mining() == (3.0, 2) and tr.loss_path == "cova_ce_loss"
+    assert tr._criterion() == dict(label_smoothing=0.0, focal_gamma=0.0, ignore_index=None, reduction="sum")
+    assert tr.loss_options["hard_negative_ratio"] == 3.0 and tr.loss_options["hard_negative_min"] == 2
+    assert set(tr.optimizer_state_dict()) == set(plain.optimizer_state_dict())
+    # read and checked at every step, like the other scalar options
+    tr.loss_options["hard_negative_ratio"] = None
+    assert tr._mining() is None and tr.loss_path == "cova_ce_sum"
+    plain.loss_options["hard_negative_ratio"] = 0.0
+    assert plain._mining() == (0.0, 0) and plain.loss_path == "cova_ce_loss"
+    plain.loss_options["hard_negative_ratio"] = -2.0
+    with pytest.raises(ValueError, match="hard_negative_ratio"):
+        plain._criterion()
+
+
+def test_module_arguments():
+    m = CrossEntropyLoss()
+    assert m.hard_negative_ratio is None and m.hard_negative_min == 0 and "hard_negative" not in m.extra_repr()
+    m = CrossEntropyLoss(hard_negative_ratio=3, hard_negative_min=2)
+    assert (m.hard_negative_ratio, m.hard_negative_min) == (3.0, 2)
+    assert "hard_negative_ratio=3, hard_negative_min=2" in repr(m)
+    with pytest.raises(ValueError, match="page_start"):
+        m(torch.zeros(3, 4), torch.zeros(3, dtype=torch.int64))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        m(torch.zeros(3, 4), torch.zeros(3, dtype=torch.int64), torch.tensor([0, 3]))
+
+
+def test_entry_point_is_declared_and_exported():
+    protos = _lib.parse_header()
+    assert "cova_hard_negative_select" in protos and hasattr(ctypes.CDLL(_lib.LIB_PATH), "cova_hard_negative_select")
+    p, i, d, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_longlong
+    assert protos["cova_hard_negative_select"] == [p, p, p, i, i, i, d, i, ll, p, p, p, p]
