@@ -274,7 +274,7 @@ def _log(log_file, lines):
 
 def fit(trainer, train_set, val_set, n_epochs, batch_size, sampling_fraction=0.9, seed=0, eval_interval=3, patience=7,
         lr_schedule=None, checkpoint=None, log_file=None, k=1, rank=0, world_size=1, group=None, class_names=None,
-        train_features=None, val_features=None):
+        train_features=None, val_features=None, augment=None):
     """train.train_model: ``n_epochs`` epochs of ``trainer.train_step`` over ``train_set`` (shuffled, background boxes
     sampled), ``evaluate_split`` on ``val_set`` at epoch 1, every ``eval_interval`` epochs and at the last epoch,
     save-best / patience / reload-best -> FitResult.
@@ -287,7 +287,12 @@ def fit(trainer, train_set, val_set, n_epochs, batch_size, sampling_fraction=0.9
     reloaded at the end on every rank.  Every rank sees the same merged tables and takes the same decisions.
     ``train_features`` / ``val_features`` (features.FeatureCache over ``train_set`` / ``val_set``, for a trainer whose
     conv stack is frozen with its BatchNorms in eval mode): checked once on entry; the steps and the evaluations then
-    take the visual rows from the tables."""
+    take the visual rows from the tables.
+    ``augment`` (a pipeline.PageAugment): the TRAINING batches of every epoch are augmented (keyed by ``epoch``, so no two
+    epochs show a page alike); ``evaluate_split`` never is.  Not with ``train_features`` (ValueError)."""
+    if augment is not None and train_features is not None:
+        raise ValueError("augment cannot be combined with train_features: the cached rows were pooled from unaugmented "
+                         "pixels")
     if trainer.metrics is None:
         raise ValueError("fit needs a trainer built with track_metrics=True (the epoch's loss and accuracy are read "
                          "from trainer.metrics)")
@@ -300,11 +305,12 @@ def fit(trainer, train_set, val_set, n_epochs, batch_size, sampling_fraction=0.9
     names = _names(class_names, nc)
     base_lr = [g["lr"] for g in trainer.param_groups]
     best_state, history, epochs_run = None, [], 0
+    aug_kw = {} if augment is None else dict(augment=augment)
     trainer.metrics.reset()
     for epoch in range(1, ctl.n_epochs + 1):
         start = time.time()
         for batch in train_set.batches(batch_size, shuffle=True, sampling_fraction=sampling_fraction, seed=seed,
-                                       epoch=epoch, rank=rank, world_size=world_size, features=train_features):
+                                       epoch=epoch, rank=rank, world_size=world_size, features=train_features, **aug_kw):
             trainer.train_step(batch)
         m = trainer.metrics.read()
         trainer.metrics.reset()

@@ -18,6 +18,11 @@ the ``spatial_k`` nearest other boxes of the page, built by one cova_context_knn
 after the sampling, on the stream that collated them.  ``DeviceDataset.with_context`` gives the same resident split another
 graph.
 
+``PageAugment`` (opt-in, both classes and ``evaluation.fit``; the reference augments nothing) gives every page of every
+epoch an integer viewport shift with a constant fill colour and a 3x4 affine colour transform, a function of
+``(seed, epoch, page id)`` alone.  The page gather applies both in its one pass (cova_pages_u8_augment_f32) and one
+cova_boxes_translate launch moves the collated boxes with the pixels, before the spatial graph is built.
+
 ``attention_rows`` is the dump of extract_attn_wts_and_visualize.py:104-135.
 """
 import numpy as np
@@ -91,12 +96,121 @@ def _read_kept_total(out_offs, B):
     return int(out_offs[B].item())
 
 
+def _mix64_np(s, x):
+    """``mix64`` on uint64 arrays (arithmetic modulo 2**64)."""
+    with np.errstate(over="ignore"):
+        z = s + np.uint64(0x9E3779B97F4A7C15) * (x + np.uint64(1))
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+class PageAugment:
+    """Per-page augmentation parameters of cova_pages_u8_augment_f32 / cova_boxes_translate (host only, numpy).
+
+    ``max_shift=(sx, sy)``: the viewport moves by dx in [-sx, sx], dy in [-sy, sy] pixels (content and boxes move right /
+    down for positive values); what scrolls in has the colour ``fill`` (R, G, B bytes).  ``brightness`` (an offset in
+    [-b, b]), ``contrast``, ``saturation``, ``channel_gain`` (factors in [1-m, 1+m], m < 1) and ``invert_prob`` (light /
+    dark theme) fold into one 3x4 matrix per page.  Everything is a function of ``(seed, epoch, page id)``: a stream of
+    its own beside the box sampling's, so the kept boxes do not change when augmentation is switched on, and a page's
+    pixels do not depend on the batch it lands in, the batch size, the rank or the world size.  Zero magnitudes give zero
+    shifts and the exact identity matrix."""
+
+    LUMA = (0.299, 0.587, 0.114)
+
+    def __init__(self, max_shift=(0, 0), brightness=0.0, contrast=0.0, saturation=0.0, channel_gain=0.0, invert_prob=0.0,
+                 fill=(255, 255, 255), seed=0):
+        try:
+            sx, sy = (int(v) for v in max_shift)
+        except (TypeError, ValueError):
+            raise ValueError("max_shift must be a pair (sx, sy) of integers, got %r" % (max_shift,))
+        if sx < 0 or sy < 0 or sx >= 2 ** 31 or sy >= 2 ** 31:
+            raise ValueError("max_shift must be non-negative int32 values, got %r" % (max_shift,))
+        self.max_shift = (sx, sy)
+        self.brightness, self.contrast = float(brightness), float(contrast)
+        self.saturation, self.channel_gain = float(saturation), float(channel_gain)
+        self.invert_prob = float(invert_prob)
+        for name in ("brightness", "contrast", "saturation", "channel_gain"):
+            v = getattr(self, name)
+            if not (v >= 0.0) or not np.isfinite(v):
+                raise ValueError("%s must be a finite value >= 0, got %r" % (name, v))
+            if name != "brightness" and v >= 1.0:
+                raise ValueError("%s must be < 1 (the factor stays positive), got %r" % (name, v))
+        if not (0.0 <= self.invert_prob <= 1.0):
+            raise ValueError("invert_prob must be in [0, 1], got %r" % (invert_prob,))
+        try:
+            f = tuple(int(v) for v in fill)
+        except (TypeError, ValueError):
+            raise ValueError("fill must be three bytes (R, G, B), got %r" % (fill,))
+        if len(f) != 3 or any(v < 0 or v > 255 or v != w for v, w in zip(f, fill)):
+            raise ValueError("fill must be three bytes (R, G, B) in 0..255, got %r" % (fill,))
+        self.fill = f
+        self.seed = int(seed)
+
+    @property
+    def fill_rgb(self):
+        return (self.fill[0] << 16) | (self.fill[1] << 8) | self.fill[2]
+
+    @property
+    def shifts(self):
+        """Whether any page can move (then the boxes need their cova_boxes_translate launch)."""
+        return self.max_shift != (0, 0)
+
+    def check_page(self, W, H):
+        if self.max_shift[0] >= int(W) or self.max_shift[1] >= int(H):
+            raise ValueError("max_shift %r must be smaller than the page (W, H) = (%d, %d) in both directions"
+                             % (self.max_shift, W, H))
+
+    def params(self, page_ids, epoch):
+        """-> (shift int32 [n,2] = dx,dy, color float32 [n,12] = row-major 3x4, the offset last in a row).
+
+        aug_stream = mix64(stream_seed(seed, epoch), 1);  u(pid, slot) = (mix64(mix64(aug_stream, pid), slot) >> 11) * 2**-53,
+        then float64: slots 0, 1: d = floor(u * (2*s + 1)) - s;  2: beta = (2u-1)*brightness;  3: c = 1 + (2u-1)*contrast;
+        4: s = 1 + (2u-1)*saturation;  5-7: g_k = 1 + (2u-1)*channel_gain;  8: sigma = -1 if u < invert_prob else 1;
+        M[k][l] = sigma*c*g_k*(s*(k==l) + (1-s)*w[l]),  b_k = sigma*(0.5*(1-c) + beta) + (sigma < 0),  w = LUMA; rounded to
+        float32 at the end."""
+        pids = np.asarray(page_ids).reshape(-1)
+        if pids.size and (pids.dtype.kind not in "iu" or (pids < 0).any()):
+            raise ValueError("page ids must be non-negative integers")
+        n = pids.shape[0]
+        stream = np.uint64(mix64(stream_seed(self.seed, epoch), 1))
+        page = _mix64_np(stream, pids.astype(np.uint64))
+        u = np.empty((9, n), np.float64)
+        for slot in range(9):
+            u[slot] = (_mix64_np(page, np.uint64(slot)) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+        shift = np.empty((n, 2), np.int32)
+        for a, s in enumerate(self.max_shift):         # u < 1; the minimum keeps a product that rounds up to 2s+1 inside
+            shift[:, a] = np.minimum(np.floor(u[a] * (2 * s + 1)), 2 * s) - s
+        beta = (2.0 * u[2] - 1.0) * self.brightness
+        c = 1.0 + (2.0 * u[3] - 1.0) * self.contrast
+        sat = 1.0 + (2.0 * u[4] - 1.0) * self.saturation
+        gain = 1.0 + (2.0 * u[5:8] - 1.0) * self.channel_gain
+        sigma = np.where(u[8] < self.invert_prob, -1.0, 1.0)
+        color = np.empty((n, 3, 4), np.float64)
+        for k in range(3):
+            for l in range(3):
+                color[:, k, l] = sigma * c * gain[k] * (sat * float(k == l) + (1.0 - sat) * self.LUMA[l])
+            color[:, k, 3] = sigma * (0.5 * (1.0 - c) + beta) + np.where(sigma < 0, 1.0, 0.0)
+        return shift, color.reshape(n, 12).astype(np.float32)
+
+    def table(self, page_ids, epoch):
+        """``params`` as ONE int32 array [n*2 + n*12] = shifts, then the colour table's float32 bits (one upload)."""
+        shift, color = self.params(page_ids, epoch)
+        return np.concatenate([shift.reshape(-1), color.reshape(-1).view(np.int32)])
+
+
+def _split_aug_table(tab_d, n):
+    """(shift int32 [n,2], color float32 [n,12]) views of a device copy of ``PageAugment.table``."""
+    return tab_d[:2 * n].view(n, 2), tab_d[2 * n:14 * n].view(torch.float32).view(n, 12)
+
+
 def _sample_and_collate(dev, cs, A, rows_d, addl_d, offs_d, starts_d, pid_d, keep_d, keys_d, B, N, sseed, n_out=None,
-                        want_sel=False, ks=0):
+                        want_sel=False, ks=0, shift_d=None):
     """cova_sample_boxes + cova_collate_selected on the current stream.  ``n_out`` is the number of kept boxes when the
     host knows it (everything kept); None reads it back from the device: the one 4-byte host read of a sampled batch.
     ``want_sel``: also return the kept SOURCE row ids (int32 [n_out]) under "sel".  ``ks > 0``: the collation writes no
-    window; cova_context_knn builds the whole [n_out, 2*cs + ks] table over the kept boxes."""
+    window; cova_context_knn builds the whole [n_out, 2*cs + ks] table over the kept boxes.  ``shift_d`` (device int32
+    [B,2]): cova_boxes_translate moves the collated boxes before the graph is built."""
     ws = torch.empty((N + B,), dtype=torch.int32, device=dev)
     sel = torch.empty((N,), dtype=torch.int32, device=dev)
     out_offs = torch.empty((B + 1,), dtype=torch.int32, device=dev)
@@ -110,6 +224,8 @@ def _sample_and_collate(dev, cs, A, rows_d, addl_d, offs_d, starts_d, pid_d, kee
     addl = torch.empty((n_out, A), dtype=torch.float32, device=dev)
     call("cova_collate_selected", rows_d, sel, out_offs, B, n_out, K // 2, bboxes, labels, ctx if K else None,
          addl_d if A else None, A, addl if A else None)
+    if shift_d is not None:
+        call("cova_boxes_translate", bboxes, n_out, shift_d, B)
     if ks:
         ctx = _context_knn(bboxes, out_offs, B, cs, ks)
     out = dict(bboxes=bboxes, additional_feats=addl, context_indices=ctx, labels=labels,
@@ -120,12 +236,14 @@ def _sample_and_collate(dev, cs, A, rows_d, addl_d, offs_d, starts_d, pid_d, kee
 
 
 class DeviceCollate:
-    def __init__(self, context_size, device, n_additional_feat=0, pin=False, sampling_fraction=1.0, seed=0, spatial_k=0):
+    def __init__(self, context_size, device, n_additional_feat=0, pin=False, sampling_fraction=1.0, seed=0, spatial_k=0,
+                 augment=None):
         assert context_size >= 0
         self.cs, self.ks = _check_graph(context_size, spatial_k)
         self.device, self.A = torch.device(device), int(n_additional_feat)
         self.pin = bool(pin)            # stage host arrays in pinned memory: H2D copies become asynchronous
         self.sf, self.seed = _check_fraction(sampling_fraction), int(seed)
+        self.augment = augment          # a PageAugment: keyed by page_ids (default: the position) and epoch, as the sampler
 
     def __call__(self, u8_pages, rows_per_page, additional_feats=None, page_ids=None, epoch=0, keys=None):
         """u8_pages: uint8 [B,H,W,3] (numpy or torch, host or device); rows_per_page: list of
@@ -137,7 +255,11 @@ class DeviceCollate:
         instead: ``keys[perm[j]] = j`` per page reproduces the reference's ``np.random.permutation`` draw ``perm``.
 
         With ``spatial_k > 0`` ``context_indices`` is [N, 2*context_size + spatial_k] (cova_context_knn over the kept
-        boxes); the rows must be finite (ValueError)."""
+        boxes); the rows must be finite (ValueError).
+
+        With ``augment`` the pages go through cova_pages_u8_augment_f32 and the collated boxes through
+        cova_boxes_translate (before the spatial graph); the batch carries ``aug_shift`` (device int32 [B,2] = dx,dy).
+        Boxes are neither clipped nor dropped."""
         u8 = torch.as_tensor(np.ascontiguousarray(u8_pages) if isinstance(u8_pages, np.ndarray)
                              else u8_pages)
         assert u8.dtype == torch.uint8 and u8.dim() == 4 and u8.shape[3] == 3
@@ -155,25 +277,44 @@ class DeviceCollate:
         u8 = (host(u8) if u8.device.type == "cpu" else u8).to(dev, non_blocking=True).contiguous()
         rows_d = host(torch.from_numpy(rows)).to(dev, non_blocking=True)
         images = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
-        call("cova_images_u8_to_f32", u8, images, B, H, W)
+        shift_d = aug_shift = None
+        if self.augment is None:
+            call("cova_images_u8_to_f32", u8, images, B, H, W)
+        else:
+            self.augment.check_page(W, H)
+            aug_ids = np.arange(B, dtype=np.int64) if page_ids is None else np.asarray(page_ids, dtype=np.int64).reshape(-1)
+            if aug_ids.shape[0] != B:
+                raise ValueError("page_ids must hold one id in [0, 2**31) per page")
+            tab_d = host(torch.from_numpy(self.augment.table(aug_ids, epoch))).to(dev, non_blocking=True)
+            aug_shift, color_d = _split_aug_table(tab_d, B)
+            call("cova_pages_u8_augment_f32", u8, None, B, B, H, W, aug_shift, color_d, self.augment.fill_rgb, images)
+            shift_d = aug_shift if self.augment.shifts else None
         if self.sf < 1.0 or keys is not None:
-            return self._sampled(images, rows_d, counts, offs, additional_feats, page_ids, epoch, keys, host)
+            out = self._sampled(images, rows_d, counts, offs, additional_feats, page_ids, epoch, keys, host, shift_d)
+            if aug_shift is not None:
+                out["aug_shift"] = aug_shift
+            return out
         offs_d = host(torch.from_numpy(offs)).to(dev, non_blocking=True)
         bboxes = torch.empty((N, 5), dtype=torch.float32, device=dev)
         labels = torch.empty((N,), dtype=torch.int64, device=dev)
         K = 0 if self.ks else 2 * self.cs
         ctx = torch.empty((N, K) if K else (0, 0), dtype=torch.int64, device=dev)   # datasets.py:130
         call("cova_collate_boxes", rows_d, offs_d, B, N, K // 2, bboxes, labels, ctx if K else None)
+        if shift_d is not None:
+            call("cova_boxes_translate", bboxes, N, shift_d, B)
         if self.ks:
             ctx = _context_knn(bboxes, offs_d, B, self.cs, self.ks)
         if additional_feats is None:
             addl = torch.empty((N, 0), dtype=torch.float32, device=dev)
         else:
             addl = torch.as_tensor(additional_feats, dtype=torch.float32).to(dev).contiguous()
-        return dict(images=images, bboxes=bboxes, additional_feats=addl, context_indices=ctx,
-                    labels=labels, page_start=offs_d.to(torch.int64))
+        out = dict(images=images, bboxes=bboxes, additional_feats=addl, context_indices=ctx,
+                   labels=labels, page_start=offs_d.to(torch.int64))
+        if aug_shift is not None:
+            out["aug_shift"] = aug_shift
+        return out
 
-    def _sampled(self, images, rows_d, counts, offs, additional_feats, page_ids, epoch, keys, host):
+    def _sampled(self, images, rows_d, counts, offs, additional_feats, page_ids, epoch, keys, host, shift_d=None):
         dev, B, N = self.device, len(counts), int(offs[-1])
         if page_ids is None:
             pids = np.arange(B, dtype=np.int64)
@@ -198,7 +339,7 @@ class DeviceCollate:
                 raise ValueError("additional_feats must be [N, A] with one row per box")
             A = int(addl_d.shape[1])
         out = _sample_and_collate(dev, self.cs, A, rows_d, addl_d, offs_d, None, pid_d, keep_d, keys_d, B, N,
-                                  stream_seed(self.seed, epoch), ks=self.ks)
+                                  stream_seed(self.seed, epoch), ks=self.ks, shift_d=shift_d)
         out["images"] = images
         return out
 
@@ -336,20 +477,32 @@ class DeviceDataset:
         return other
 
     def batches(self, batch_size, shuffle=False, sampling_fraction=1.0, seed=0, epoch=0, drop_last=False, rank=0,
-                world_size=1, order=None, prefetch=True, features=None):
+                world_size=1, order=None, prefetch=True, features=None, augment=None):
         """One epoch of batches (a generator).  Train: ``shuffle=True, sampling_fraction=sf``; val / test: batch 10,
         no shuffle, no sampling (datasets.py:227-258).  With ``prefetch`` batch i+1 is assembled on a side stream while
         the consumer works on batch i.  With ``sampling_fraction == 1`` there is no host read at all; otherwise one
         4-byte read per batch (the number of kept boxes), on the side stream.
         ``features`` (a features.FeatureCache built over this dataset): the pages are not gathered; the batch has no
-        ``images`` and carries ``visual_feats`` = (the cache's table, the kept boxes' row ids) instead."""
+        ``images`` and carries ``visual_feats`` = (the cache's table, the kept boxes' row ids) instead.
+        ``augment`` (a PageAugment; None, the default, is exactly the path above): every page gets the shift and the colour
+        transform of ``augment.params(page id, epoch)``; the parameters of the whole epoch go up with the index tables, the
+        step's gather is one cova_pages_u8_augment_f32 launch and, when ``max_shift`` is not (0, 0), one
+        cova_boxes_translate launch moves the collated boxes before cova_context_knn.  Boxes are neither clipped nor
+        dropped: RoIPool / RoIAlign clamp, and a box pushed wholly off the page pools zeros and keeps its label and its
+        place in DOM order.  The batch gains ``aug_shift`` (device int32 [B,2] = dx,dy).  Not with ``features``
+        (ValueError): cached rows were pooled from unaugmented pixels."""
+        if augment is not None:
+            if features is not None:
+                raise ValueError("augment cannot be combined with features: the cached rows were pooled from unaugmented "
+                                 "pixels")
+            augment.check_page(self.W, self.H)
         sf = _check_fraction(sampling_fraction)
         if features is not None:
             features.check_dataset(self)
         plan = epoch_plan(self.P, batch_size, shuffle, seed, epoch, drop_last, rank, world_size, order)
-        return self._iterate(plan, sf, stream_seed(seed, epoch), bool(prefetch), features)
+        return self._iterate(plan, sf, stream_seed(seed, epoch), bool(prefetch), features, augment, epoch)
 
-    def _iterate(self, plan, sf, sseed, prefetch, features=None):
+    def _iterate(self, plan, sf, sseed, prefetch, features=None, augment=None, epoch=0):
         if not plan:
             return
         dev = self.device
@@ -362,20 +515,33 @@ class DeviceDataset:
             parts.append(part)
             where.append((pos, int(ids.shape[0]), int(n.sum())))
             pos += part.shape[0]
+        if augment is not None:     # behind the steps' tables, in the same copy: every page's shift, then the colour bits
+            parts.append(augment.table(np.concatenate(plan), epoch))
         table = torch.from_numpy(np.concatenate(parts)).to(dev)
         ids64 = torch.from_numpy(np.concatenate(plan)).to(dev)
         starts64 = np.concatenate([[0], np.cumsum([len(ids) for ids in plan])])
+        if augment is not None:
+            shifts_d, colors_d = _split_aug_table(table[pos:], int(starts64[-1]))
 
         def assemble(step):
             pos, B, N = where[step]
             ids_d, offs_d = table[pos:pos + B], table[pos + B:pos + 2 * B + 1]
             starts_d, keep_d = table[pos + 2 * B + 1:pos + 3 * B + 1], table[pos + 3 * B + 1:pos + 4 * B + 1]
+            aug_shift = None
             if features is None:
                 images = torch.empty((B, 3, self.H, self.W), dtype=torch.float32, device=dev)
-                call("cova_pages_u8_gather_f32", self.store, ids_d, self.P, B, self.H, self.W, images)
+                if augment is None:
+                    call("cova_pages_u8_gather_f32", self.store, ids_d, self.P, B, self.H, self.W, images)
+                else:
+                    lo = int(starts64[step])
+                    aug_shift = shifts_d[lo:lo + B]
+                    call("cova_pages_u8_augment_f32", self.store, ids_d, self.P, B, self.H, self.W, aug_shift,
+                         colors_d[lo:lo + B], augment.fill_rgb, images)
             out = _sample_and_collate(dev, self.cs, self.A, self.rows, self.addl, offs_d, starts_d, ids_d, keep_d, None,
                                       B, N, sseed, n_out=N if sf == 1.0 else None, want_sel=features is not None,
-                                      ks=self.ks)
+                                      ks=self.ks, shift_d=aug_shift if aug_shift is not None and augment.shifts else None)
+            if aug_shift is not None:
+                out["aug_shift"] = aug_shift
             if features is None:
                 out["images"] = images
             else:       # the sampler's kept SOURCE row ids are the table's row ids (with sf == 1 it keeps every row)

@@ -614,6 +614,34 @@ int cova_collate_selected(const float *rows, const int *sel, const int *out_offs
                           float *bboxes, long long *labels, long long *ctx /*nullable if context_size==0*/,
                           const float *addl_in /*nullable if A==0*/, int A, float *addl_out /*nullable if A==0*/,
                           void *stream);
+/* ---- page augmentation in the page gather (augment.hip; pipeline.PageAugment, DeviceDataset.batches(augment=)) ----
+ * The reference augments nothing: an opt-in extension.  The host draws, per page, an integer viewport shift (dx, dy) and a
+ * 3x4 affine colour transform as a function of (seed, epoch, page id) and uploads them once per epoch.
+ * cova_pages_u8_augment_f32: cova_pages_u8_gather_f32 with both applied; f32_nchw [B,3,H,W].  For output page b, channel c,
+ *   row y, column x:
+ *     source page = page_idx[b] (DEVICE int32 [B]), or b itself when page_idx is NULL (then P >= B, else a status); an index
+ *       outside [0,P) leaves the output page unwritten, as the gather does
+ *     sx = x - dx_b, sy = y - dy_b in 64 bits (shift DEVICE int32 [B,2] = dx,dy, any int32 value; NULL = 0,0)
+ *     v_k (k = R,G,B) = the source byte at (sy, sx) when 0 <= sx < W and 0 <= sy < H, else byte k of fill_rgb = 0xRRGGBB
+ *     t_k = (float)v_k / 255.f, correctly rounded: the arithmetic of cova_images_u8_to_f32
+ *     y_c = ((m[4c]*t_0 + m[4c+1]*t_1) + m[4c+2]*t_2) + m[4c+3],  m = color[b] (DEVICE f32 [B,12], row-major 3x4, m[4c+3] the
+ *       offset; NULL = the identity), float32 with EVERY multiply and add rounded on its own (no fused multiply-add)
+ *     out = y_c > 0 ? fminf(y_c, 1.f) : 0.f          in [0,1], never -0, 0 for a NaN
+ *   With the identity y_c is exactly t_c, so NULL / zero shift and NULL / identity colour give the bits of
+ *   cova_pages_u8_gather_f32.  tests/augment_oracle.py is the numpy statement.  Page offsets are 64-bit (the store may exceed
+ *   4 GiB); no thread reads a byte outside [store_u8, store_u8 + P*H*W*3).  With W % 4 == 0, store_u8 4-byte and f32_nchw
+ *   16-byte aligned a thread makes 4 pixels of a row from the aligned dwords that cover their 12 source bytes (any dx);
+ *   otherwise a pixel-per-thread kernel writes the same bytes.  H, W, P >= 1, store_u8 and f32_nchw non-NULL, else a status;
+ *   B == 0 returns without a launch.  One launch, no workspace, no atomics, no host read: capturable, bit-deterministic.
+ * cova_boxes_translate: boxes moved with the pixels, in place.  Row g of bboxes [N,5] = page,x1,y1,x2,y2: p = (int)bboxes[g,0];
+ *   if 0 <= p < B, columns 1 and 3 += (float)dx_p and columns 2 and 4 += (float)dy_p (one float32 add each), otherwise the row
+ *   is untouched.  Nothing is clipped or dropped: RoIPool / RoIAlign clamp, a box pushed off the page pools zeros.  N == 0
+ *   returns without a launch (no pointer is read); N < 0 or B < 0, and for N > 0 a NULL bboxes or shift or B == 0, return a
+ *   status.  One launch, one thread per box. */
+int cova_pages_u8_augment_f32(const uint8_t *store_u8, const int *page_idx /*nullable*/, int P, int B, int H, int W,
+                              const int *shift /*nullable [B,2]*/, const float *color /*nullable [B,12]*/, int fill_rgb,
+                              float *f32_nchw, void *stream);
+int cova_boxes_translate(float *bboxes, int N, const int *shift, int B, void *stream);
 /* ---- context graphs (graph.hip; pipeline.DeviceCollate / DeviceDataset(spatial_k=)) ----
  * cova_context_knn: the context table with spatial neighbours, ctx [N, 2*context_size + k_spatial] int64 batch-global ids,
  *   -1 pads.  bboxes [N,5] = page,x1,y1,x2,y2 exactly as cova_collate_boxes / cova_collate_selected wrote them (the page
