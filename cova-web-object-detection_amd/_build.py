@@ -16,11 +16,9 @@ def needs_build():
     return any(os.path.getmtime(s) > t for s in SOURCES + HEADERS)
 
 
-# per-file extra flags.  conv_wino: no SLP vectorisation -- on gfx950 packed f32 VALU ops cannot issue
-# in the shadow of an MFMA (LLVM unpacks them again and leaves the shuffle moves behind).
-FILE_FLAGS = {"conv_wino.hip": ["-fno-slp-vectorize"],
-              # conv_wgrad4: the same (packed transform arithmetic cost 210 register moves per K-step of the input role)
-              "conv_wgrad4.hip": ["-fno-slp-vectorize"]}
+# per-file extra flags.  conv_wgrad4: no SLP vectorisation -- on gfx950 packed f32 VALU ops cannot issue in the shadow
+# of an MFMA (LLVM unpacks them again and leaves the shuffle moves behind: 210 register moves per K-step of the input role).
+FILE_FLAGS = {"conv_wgrad4.hip": ["-fno-slp-vectorize"]}
 
 
 def build(force=False, verbose=False):
@@ -33,8 +31,6 @@ def build(force=False, verbose=False):
     common = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
               "-Wall", "-Wno-unused-function"]
     common += os.environ.get("COVA_EXTRA_FLAGS", "").split()
-    if os.environ.get("COVA_ABLATE"):          # tools/conv_bench.py ablation study builds
-        common.append("-DCOVA_ABLATE=1")
     procs, objs = [], []
     for src in SOURCES:                        # one hipcc per translation unit, in parallel
         obj = os.path.join(objdir, os.path.basename(src)[:-4] + ".o")

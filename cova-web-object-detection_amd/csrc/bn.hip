@@ -232,7 +232,7 @@ __global__ __launch_bounds__(1024) void bn_finalize_bwd_kernel(
 
 // finalize_bwd that also emits the affine form of the apply step,
 //   dz = scale*(dy - c1 - xhat*c2) = A*dy + B*z + C,   abc = [3][C] = A | B | C,
-// for the convolutions that apply it on load (cova_conv3x3_wino_pro / _wgrad_wino_pro).
+// for the convolutions that apply it on load (cova_conv3x3_wino4_full, cova_conv3x3_wgrad4_partial, cova_conv1x1).
 __global__ __launch_bounds__(1024) void bn_finalize_bwd_abc_kernel(
     const float *__restrict__ partial, int nparts, int C, double count,
     float *__restrict__ dgamma, float *__restrict__ dbeta, const float *__restrict__ mean,
@@ -411,7 +411,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
 // fetched from HBM once per strip instead of once per output row that touches it (round 2 measured 1.56x read
 // over-fetch with one thread per output: rows 2 oy - 1 / 2 oy + 1 were read by two blocks, usually on different XCDs).
 // Neighbouring columns are neighbouring 16-lane groups of the same wave (L1 hits).
-// STRIP / PRE (cova_set_option(13, v), tools/ew_bench.py): rows per strip; PRE: the two new input rows of output row
+// STRIP / PRE: rows per strip; PRE: the two new input rows of output row
 // oy + 1 are requested before output row oy is reduced and stored (12 instead of 6 loads of a thread in flight).
 template <int POOL_STRIP, bool PRE, bool XCD = false, bool TILE2D = false>
 __global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_kernel(

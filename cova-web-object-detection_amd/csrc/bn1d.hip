@@ -11,6 +11,7 @@
 // + bn_finalize_bwd + bn_bwd_apply (+ colsum) backward.  SyncBN and eval-mode BatchNorm keep the separate kernels
 // (bn.hip): a collective / a host decision sits between the sums and the parameters there.
 #include "bn_tail.h"
+#include "options.h"
 
 namespace {
 
@@ -346,14 +347,9 @@ __global__ __launch_bounds__(V4_THREADS) void bn1d_bwd_v4_kernel(
     }
 }
 
-int g_bn1d_variant = 1;
-
 inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
-
-int cova_internal_set_bn1d_variant(int v) { g_bn1d_variant = v; return COVA_OK; }
-int cova_internal_get_bn1d_variant() { return (int)g_bn1d_variant; }
 
 COVA_API int cova_bn1d_fwd(const float *x, int ldx, int R, int C, const float *gamma, const float *beta,
                            float *running_mean, float *running_var, long long *num_batches_tracked, float momentum,
@@ -364,7 +360,7 @@ COVA_API int cova_bn1d_fwd(const float *x, int ldx, int R, int C, const float *g
     COVA_REQUIRE(x && gamma && beta && out && scale && shift && mean && invstd && R > 0 && C > 0);
     COVA_REQUIRE((running_mean == nullptr) == (running_var == nullptr));
     COVA_REQUIRE(dropped == nullptr || (mask != nullptr && p >= 0.f && p < 1.f));
-    const bool v4 = g_bn1d_variant != 0 && C % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && al16(x) && al16(out) &&
+    const bool v4 = cova_options().bn1d_variant != 0 && C % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && al16(x) && al16(out) &&
                     (dropped == nullptr || (ld_dropped % 4 == 0 && al16(dropped) && ((uintptr_t)mask & 3) == 0)) &&
                     R <= 8 * V4_SLICES;
     if (v4) {
@@ -399,7 +395,7 @@ COVA_API int cova_bn1d_bwd(const float *dout, int ldg, const uint8_t *drop_mask,
 {
     COVA_REQUIRE(dout && z && mean && invstd && scale && dz && R > 0 && C > 0);
     COVA_REQUIRE(drop_mask == nullptr || (p >= 0.f && p < 1.f));
-    const bool v4 = g_bn1d_variant != 0 && C % 4 == 0 && ldg % 4 == 0 && ldz % 4 == 0 && lddz % 4 == 0 && al16(dout) &&
+    const bool v4 = cova_options().bn1d_variant != 0 && C % 4 == 0 && ldg % 4 == 0 && ldz % 4 == 0 && lddz % 4 == 0 && al16(dout) &&
                     al16(z) && al16(dz) && (act == nullptr || (lda % 4 == 0 && al16(act))) &&
                     (drop_mask == nullptr || ((uintptr_t)drop_mask & 3) == 0) && R <= 6 * V4_SLICES;   // (8 rows: 128 registers, spills)
     if (v4) {

@@ -22,14 +22,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
         if (!(cond)) return COVA_ERR_BAD_ARG;       \
     } while (0)
 
-// Ablation switches of the conv kernels (tools/conv_bench.py) exist only in builds made with
-// -DCOVA_ABLATE; in the production library the mask folds to 0 and the branches disappear.
-#ifdef COVA_ABLATE
-#define COVA_ABL(x) (x)
-#else
-#define COVA_ABL(x) 0
-#endif
-
 #define COVA_API extern "C" __attribute__((visibility("default")))
 
 // neighbour slots per node the wave-per-node GAT kernels hold in registers: up to sixteen 64-lane passes (-cs <= 512: far

@@ -12,9 +12,9 @@
 // Roofline bookkeeping: 2*64*64*9 = 73,728 FLOP per output pixel
 // for conv3x3 (fwd, dgrad and wgrad each), 2*64*147 = 18,816 FLOP per output pixel for conv1.
 #include "common.h"
-#include <stdlib.h>
 #include "bf3.h"
 #include "bn_tail.h"
+#include "options.h"
 #include <utility>
 #include <type_traits>
 
@@ -154,9 +154,8 @@ template <bool STATS>
 __global__ __launch_bounds__(c1::THREADS, 4) void conv1_7x7_v2_kernel(
     const float *__restrict__ img, const float *__restrict__ wk, float *__restrict__ out,
     float *__restrict__ stat_part, int H, int W, int H1, int W1, int tiles_x, int tiles_y, int ntiles,
-    int abl_arg, int w_oihw, const BnTail tail)
+    int w_oihw, const BnTail tail)
 {
-    const int abl = COVA_ABL(abl_arg);
     using namespace c1;
     __shared__ __attribute__((aligned(16))) float lds[IN_FLOATS + W_FLOATS + 8 * 128];
     float *s_in = lds;
@@ -251,7 +250,7 @@ __global__ __launch_bounds__(c1::THREADS, 4) void conv1_7x7_v2_kernel(
         // every LDS operand address is a per-lane base + a compile-time immediate (see pair_tap)
 #pragma unroll
         for (int p = 0; p < 49; ++p) {
-            if (p % 5 == 0 && p / 5 < NPRE && has_next && !(abl & 4)) issue_slot(p / 5, nimg, nty, ntx);
+            if (p % 5 == 0 && p / 5 < NPRE && has_next) issue_slot(p / 5, nimg, nty, ntx);
             const float a = a_set0[local_off(p)];
             acc0 = mfma32(a, b_base[p * 128], acc0);
             acc1 = mfma32(a, b_base[p * 128 + 32], acc1);
@@ -270,13 +269,10 @@ __global__ __launch_bounds__(c1::THREADS, 4) void conv1_7x7_v2_kernel(
         }
         const int oy = y0 + wave;
         float s0 = 0.f, s1 = 0.f, q0 = 0.f, q1 = 0.f;
-        if (abl & 1)
-            asm volatile("" ::"v"(acc0), "v"(acc1));
-        else
-            epilogue_store_stats(acc0, acc1, out, nullptr, ((size_t)b * H1 + oy) * W1 + x0, x0, W1,
-                                 oy < H1, lane, s0, s1, q0, q1);
+        epilogue_store_stats(acc0, acc1, out, nullptr, ((size_t)b * H1 + oy) * W1 + x0, x0, W1,
+                             oy < H1, lane, s0, s1, q0, q1);
         __syncthreads();                 // every wave is done reading the patch
-        if (has_next && !(abl & 2)) write_lds();
+        if (has_next) write_lds();
         if (STATS && lane < 32) {
             s_red[wave * 128 + lane] += s0;
             s_red[wave * 128 + 32 + lane] += s1;
@@ -1408,11 +1404,8 @@ __global__ __launch_bounds__(1024) void conv1_wgrad_reduce_kernel(const float *_
     }
 }
 
-extern int g_grid_cap;
-bool g_options_frozen = false;       // cova_set_option: the option state is fixed from the library's first query or launch on
 inline int persistent_grid(int ntiles, int blocks_per_cu = 1)
 {
-    g_options_frozen = true;             // every size query and every launch of the big kernels comes through here
     // compute units of the CURRENT device (the caller launches under the device guard of its tensors; the host
     // queries run under the same guard): cached per device id, not once per process
     static int cus_of[64] = {0};
@@ -1426,60 +1419,20 @@ inline int persistent_grid(int ntiles, int blocks_per_cu = 1)
         cus_of[dev] = cus;
     }
     int g = ntiles < cus * blocks_per_cu ? ntiles : cus * blocks_per_cu;
-    if (g_grid_cap > 0 && g > g_grid_cap) g = g_grid_cap;
+    const int cap = cova_options().grid_cap;
+    if (cap > 0 && g > cap) g = cap;
     return g;
 }
 
-int g_ablate = 0;            // conv3x3 v2 ablation mask (tools only)
-int g_grid_cap = 0;          // > 0: cap on persistent grids (tests force many tiles per block)
-int g_conv1_f32 = 0;         // 1: conv1 forward on the f32 MFMA kernel (v2) instead of the bf16-split one (A/B, tests)
-
 }  // namespace
 
-// shared with conv_wino.hip (same shared object; hidden visibility)
+// for the other translation units (options.h)
 int cova_internal_persistent_grid(int ntiles) { return persistent_grid(ntiles); }
 int cova_internal_persistent_grid2(int ntiles, int blocks_per_cu) { return persistent_grid(ntiles, blocks_per_cu); }
 
 // ====================================================================================
 // C ABI
 // ====================================================================================
-// test / tool hooks (not part of the path's contract): 2 = cap on persistent grids (tests force many tiles per
-// block), 5 = ablation mask of builds made with -DCOVA_ABLATE (tools/conv_bench.py), 6 = Winograd tile geometry
-int cova_internal_set_wino4_f32(int v);
-int cova_internal_set_bn1d_variant(int v);
-int cova_internal_set_gat_wide(int v);
-// The option state is a per-process constant: mutable until the first query or launch, fixed afterwards (include/cova_hip.h) --
-// unless the process opted in with COVA_ALLOW_OPTION_CHANGES=1 (tests, bench.py's A/B legs).
-int cova_internal_get_bn1d_variant();
-int cova_internal_get_gat_wide();
-int cova_internal_get_wino4_f32();
-int cova_internal_get_sgemm_dma();
-int cova_internal_set_sgemm_dma(int v);
-COVA_API int cova_set_option(int key, int value)
-{
-    static const bool allow = [] { const char *e = getenv("COVA_ALLOW_OPTION_CHANGES"); return e != nullptr && e[0] == '1'; }();
-    int cur;
-    switch (key) {
-    case 2: cur = g_grid_cap; break;
-    case 7: cur = g_conv1_f32; value = value != 0; break;
-    case 9: cur = cova_internal_get_wino4_f32(); value = value != 0; break;
-    case 14: cur = cova_internal_get_bn1d_variant(); break;
-    case 16: cur = cova_internal_get_gat_wide(); value = value != 0; break;
-    case 22: cur = cova_internal_get_sgemm_dma(); value = value != 0; break;
-    default: return COVA_ERR_BAD_ARG;
-    }
-    if (cur == value) return COVA_OK;
-    if (g_options_frozen && !allow) return COVA_ERR_BAD_ARG;
-    switch (key) {
-    case 2: g_grid_cap = value; return COVA_OK;
-    case 7: g_conv1_f32 = value; return COVA_OK;
-    case 9: return cova_internal_set_wino4_f32(value);
-    case 14: return cova_internal_set_bn1d_variant(value);
-    case 22: return cova_internal_set_sgemm_dma(value);
-    default: return cova_internal_set_gat_wide(value);
-    }
-}
-
 #ifdef C1B_TRACE
 COVA_API int cova_wg1b_trace_read(unsigned long long *host)
 {
@@ -1496,22 +1449,22 @@ COVA_API int cova_conv_out_size(int in_size, int kernel, int stride, int pad)
     return (in_size + 2 * pad - kernel) / stride + 1;
 }
 
-COVA_API int cova_conv1_num_tiles(int B, int H, int W);
-static int conv1_fwd_tiles(int B, int H, int W)
-{
-    const int H1 = cova_conv_out_size(H, 7, 2, 3), W1 = cova_conv_out_size(W, 7, 2, 3);
-    return g_conv1_f32 ? B * cdiv(H1, c1::TH) * cdiv(W1, c1::TW) : B * cdiv(H1, c1b::TH) * cdiv(W1, c1b::TW);
-}
-
-COVA_API int cova_conv1_num_partials(int B, int H, int W)
-{
-    return persistent_grid(conv1_fwd_tiles(B, H, W), g_conv1_f32 ? 2 : 1);
-}
-
 COVA_API int cova_conv1_num_tiles(int B, int H, int W)
 {
     const int H1 = cova_conv_out_size(H, 7, 2, 3), W1 = cova_conv_out_size(W, 7, 2, 3);
     return B * cdiv(H1, c1::TH) * cdiv(W1, c1::TW);
+}
+
+static int conv1_fwd_tiles(int B, int H, int W)
+{
+    if (cova_options().conv1_f32) return cova_conv1_num_tiles(B, H, W);
+    const int H1 = cova_conv_out_size(H, 7, 2, 3), W1 = cova_conv_out_size(W, 7, 2, 3);
+    return B * cdiv(H1, c1b::TH) * cdiv(W1, c1b::TW);
+}
+
+COVA_API int cova_conv1_num_partials(int B, int H, int W)
+{
+    return persistent_grid(conv1_fwd_tiles(B, H, W), cova_options().conv1_f32 ? 2 : 1);
 }
 
 COVA_API int cova_conv1_prep_weights(const float *w_oihw, float *w_k, void *stream)
@@ -1534,7 +1487,7 @@ static int conv1_fwd_launch(const float *img, const float *w_k, int w_oihw, floa
                      t.mean && t.invstd);
     }
     const int H1 = cova_conv_out_size(H, 7, 2, 3), W1 = cova_conv_out_size(W, 7, 2, 3);
-    if (!g_conv1_f32) {
+    if (!cova_options().conv1_f32) {
         const int tiles_x = cdiv(W1, c1b::TW), tiles_y = cdiv(H1, c1b::TH);
         const int ntiles = B * tiles_x * tiles_y;
         const dim3 pgrid(persistent_grid(ntiles, 1)), block(c1b::THREADS);
@@ -1553,10 +1506,10 @@ static int conv1_fwd_launch(const float *img, const float *w_k, int w_oihw, floa
     const dim3 pgrid(persistent_grid(ntiles, 2));
     if (stat_part)
         hipLaunchKernelGGL(conv1_7x7_v2_kernel<true>, pgrid, block, 0, (hipStream_t)stream, img,
-                           w_k, out, stat_part, H, W, H1, W1, tiles_x, tiles_y, ntiles, g_ablate, w_oihw, t);
+                           w_k, out, stat_part, H, W, H1, W1, tiles_x, tiles_y, ntiles, w_oihw, t);
     else
         hipLaunchKernelGGL(conv1_7x7_v2_kernel<false>, pgrid, block, 0, (hipStream_t)stream, img,
-                           w_k, out, stat_part, H, W, H1, W1, tiles_x, tiles_y, ntiles, g_ablate, w_oihw, t);
+                           w_k, out, stat_part, H, W, H1, W1, tiles_x, tiles_y, ntiles, w_oihw, t);
     COVA_LAUNCH_CHECK();
     return COVA_OK;
 }
@@ -1580,6 +1533,35 @@ COVA_API int cova_conv1_wgrad_workspace_floats(int B, int H, int W)
     return persistent_grid(cova_conv1_num_tiles(B, H, W)) * 8 * 64 * 160;
 }
 
+// POOL: gy = y1 and pb routes the pooled gradient through the BatchNorm+ReLU+MaxPool backward apply on load; else gy = dy
+template <bool POOL>
+static int conv1_wgrad_launch(const float *img, const float *gy, const PoolBwd pb, float *dw, float *ws, int B, int H, int W,
+                              void *stream)
+{
+    const int H1 = cova_conv_out_size(H, 7, 2, 3), W1 = cova_conv_out_size(W, 7, 2, 3);
+    const int tiles_x = cdiv(W1, wg1::TW), tiles_y = cdiv(H1, wg1::TH);
+    const int grid = persistent_grid(B * tiles_x * tiles_y);
+    if (!cova_options().conv1_f32) {
+        const int rtx = cdiv(W1, wg1r::TW), rty = cdiv(H1, wg1r::TH);
+        const int rgrid = persistent_grid(B * rtx * rty);
+        hipLaunchKernelGGL(conv1_wgrad_rs_kernel<POOL>, dim3(rgrid), dim3(wg1r::THREADS), 0, (hipStream_t)stream, img, gy,
+                           ws, H, W, H1, W1, rtx, rty, B * rtx * rty, pb);
+        COVA_LAUNCH_CHECK();
+        hipLaunchKernelGGL(conv1_wgrad_reduce_kernel, dim3(64 * 160 / 64), dim3(1024), 0, (hipStream_t)stream, ws,
+                           rgrid * 2, dw);
+        COVA_LAUNCH_CHECK();
+        return COVA_OK;
+    }
+    hipLaunchKernelGGL(conv1_wgrad_v2_kernel<POOL>, dim3(grid), dim3(wg1::THREADS), 0,
+                       (hipStream_t)stream, img, gy, ws, H, W, H1, W1, tiles_x, tiles_y,
+                       B * tiles_x * tiles_y, pb);
+    COVA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(conv1_wgrad_reduce_kernel, dim3(64 * 160 / 64), dim3(1024), 0,
+                       (hipStream_t)stream, ws, grid * 4, dw);
+    COVA_LAUNCH_CHECK();
+    return COVA_OK;
+}
+
 // conv1 weight gradient with the BatchNorm+ReLU+MaxPool backward apply folded into its operand:
 //   dy1 = abc[0]*route(dp, idx) + abc[1]*y1 + abc[2]   (what cova_bn_relu_maxpool_bwd_apply would write)
 // y1 NHWC [B,H1,W1,64] = conv1 output; dp NHWC [B,H2,W2,64] pooled gradient with the ReLU mask already
@@ -1592,27 +1574,7 @@ COVA_API int cova_conv1_wgrad_poolbwd(const float *img, const float *y1, const f
     COVA_REQUIRE((long long)H * W * 64 < (1ll << 31));            // 32-bit in-image offsets in the kernel
     const int H1 = cova_conv_out_size(H, 7, 2, 3), W1 = cova_conv_out_size(W, 7, 2, 3);
     const int H2 = cova_conv_out_size(H1, 3, 2, 1), W2 = cova_conv_out_size(W1, 3, 2, 1);
-    const int tiles_x = cdiv(W1, wg1::TW), tiles_y = cdiv(H1, wg1::TH);
-    const int grid = persistent_grid(B * tiles_x * tiles_y);
-    if (!g_conv1_f32) {
-        const int rtx = cdiv(W1, wg1r::TW), rty = cdiv(H1, wg1r::TH);
-        const int rgrid = persistent_grid(B * rtx * rty);
-        hipLaunchKernelGGL(conv1_wgrad_rs_kernel<true>, dim3(rgrid), dim3(wg1r::THREADS), 0, (hipStream_t)stream, img, y1,
-                           ws, H, W, H1, W1, rtx, rty, B * rtx * rty, PoolBwd{dp, idx, abc, H2, W2});
-        COVA_LAUNCH_CHECK();
-        hipLaunchKernelGGL(conv1_wgrad_reduce_kernel, dim3(64 * 160 / 64), dim3(1024), 0, (hipStream_t)stream, ws,
-                           rgrid * 2, dw);
-        COVA_LAUNCH_CHECK();
-        return COVA_OK;
-    }
-    hipLaunchKernelGGL(conv1_wgrad_v2_kernel<true>, dim3(grid), dim3(wg1::THREADS), 0,
-                       (hipStream_t)stream, img, y1, ws, H, W, H1, W1, tiles_x, tiles_y,
-                       B * tiles_x * tiles_y, PoolBwd{dp, idx, abc, H2, W2});
-    COVA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(conv1_wgrad_reduce_kernel, dim3(64 * 160 / 64), dim3(1024), 0,
-                       (hipStream_t)stream, ws, grid * 4, dw);
-    COVA_LAUNCH_CHECK();
-    return COVA_OK;
+    return conv1_wgrad_launch<true>(img, y1, PoolBwd{dp, idx, abc, H2, W2}, dw, ws, B, H, W, stream);
 }
 
 // img NCHW [B,3,H,W]; dy NHWC [B,H1,W1,64]; dw OIHW [64,3,7,7]
@@ -1621,26 +1583,5 @@ COVA_API int cova_conv1_wgrad(const float *img, const float *dy, float *dw, floa
 {
     COVA_REQUIRE(img && dy && dw && ws && B > 0 && H > 0 && W > 0);
     COVA_REQUIRE((long long)H * W * 64 < (1ll << 31));            // 32-bit in-image offsets in the kernel
-    const int H1 = cova_conv_out_size(H, 7, 2, 3), W1 = cova_conv_out_size(W, 7, 2, 3);
-    const int tiles_x = cdiv(W1, wg1::TW), tiles_y = cdiv(H1, wg1::TH);
-    const int grid = persistent_grid(B * tiles_x * tiles_y);
-    if (!g_conv1_f32) {
-        const int rtx = cdiv(W1, wg1r::TW), rty = cdiv(H1, wg1r::TH);
-        const int rgrid = persistent_grid(B * rtx * rty);
-        hipLaunchKernelGGL(conv1_wgrad_rs_kernel<false>, dim3(rgrid), dim3(wg1r::THREADS), 0, (hipStream_t)stream, img, dy,
-                           ws, H, W, H1, W1, rtx, rty, B * rtx * rty, PoolBwd{nullptr, nullptr, nullptr, 0, 0});
-        COVA_LAUNCH_CHECK();
-        hipLaunchKernelGGL(conv1_wgrad_reduce_kernel, dim3(64 * 160 / 64), dim3(1024), 0, (hipStream_t)stream, ws,
-                           rgrid * 2, dw);
-        COVA_LAUNCH_CHECK();
-        return COVA_OK;
-    }
-    hipLaunchKernelGGL(conv1_wgrad_v2_kernel<false>, dim3(grid), dim3(wg1::THREADS), 0,
-                       (hipStream_t)stream, img, dy, ws, H, W, H1, W1, tiles_x, tiles_y,
-                       B * tiles_x * tiles_y, PoolBwd{nullptr, nullptr, nullptr, 0, 0});
-    COVA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(conv1_wgrad_reduce_kernel, dim3(64 * 160 / 64), dim3(1024), 0,
-                       (hipStream_t)stream, ws, grid * 4, dw);
-    COVA_LAUNCH_CHECK();
-    return COVA_OK;
+    return conv1_wgrad_launch<false>(img, dy, PoolBwd{nullptr, nullptr, nullptr, 0, 0}, dw, ws, B, H, W, stream);
 }

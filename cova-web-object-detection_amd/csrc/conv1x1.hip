@@ -29,8 +29,7 @@
 // 64->256 / 256->64: 32,768 FLOP vs 1,280 B (25.6 FLOP/B: at the f32-MFMA / HBM ridge),
 // 64->64: 8,192 FLOP vs 512 B (HBM bound).
 #include "bf3.h"
-
-int cova_internal_persistent_grid2(int ntiles, int blocks_per_cu);
+#include "options.h"
 
 namespace {
 
@@ -826,7 +825,7 @@ COVA_API int cova_conv1x1_num_partials(long long R, int Cin, int Cout)
 
 // nn.Conv2d(Cin, Cout, 1, bias=False) on NHWC rows (torchvision Bottleneck conv1 / conv3 / downsample[0]
 // behind models.py:49-51 for the resnet50 extension), forward or -- with w_trans -- data gradient.
-// (Cin, Cout) in {(64,64), (64,256), (256,64)}.  Arguments as cova_conv3x3_wino_pro; stat_part rows =
+// (Cin, Cout) in {(64,64), (64,256), (256,64)}.  Arguments as cova_conv3x3_wino4_full; stat_part rows =
 // cova_conv1x1_num_partials, [2][Cout] each: (sum y, sum y^2) when z == NULL, else (sum dy, sum dy*xhat);
 // stat_part2 (with z2/mean2/invstd2): (sum dy, sum dy*xhat2) of a second BatchNorm fed by the same dy.
 COVA_API int cova_conv1x1(const float *in, const float *in2, const float *pro_abc, int pro_relu,

@@ -16,8 +16,7 @@
 // MFMA arithmetic; the result differs from the direct form by summation order only (measured against
 // fp64: 4e-7 relative, the direct form 1.4e-6).
 #include "bf3.h"
-
-int cova_internal_persistent_grid2(int ntiles, int blocks_per_cu);
+#include "options.h"
 
 namespace {
 

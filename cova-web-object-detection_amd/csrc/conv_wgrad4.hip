@@ -36,6 +36,7 @@
 // Operand prologues as the F(2x2) kernel's: activation = relu?(A*act + C) on load, gradient = A*dz + B*dz2 + C on load
 // (the BatchNorm+ReLU of the producer / the BatchNorm-backward apply, never materialised); zero padding stays zero.
 #include "common.h"
+#include "options.h"
 #include <type_traits>
 
 // Ablation builds of tools/wgrad4_bench.py (tools/wg4_abl_build.sh, -DWG4_ABL=<mask>; 0 in the product): 1 no MFMAs,
@@ -45,8 +46,6 @@
 #ifndef WG4_ABL
 #define WG4_ABL 0
 #endif
-
-int cova_internal_persistent_grid2(int ntiles, int blocks_per_cu);
 
 // 157,696 B of static LDS (operand buffers 83,968 + wave-private pixel buffers 73,728): only gfx950's 160 KB per CU holds it
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -661,8 +660,8 @@ COVA_API int cova_conv3x3_wgrad4_workspace_floats(int B, int H, int W)
     return grid * wg4::PART_FLOATS;          // <= 256 blocks x 36,864 floats
 }
 
-// Per-block partial sums of the weight gradient in the F(4x4,3x3) domain; operands transformed on load as
-// cova_conv3x3_wgrad_wino_partial: activation = relu?(A*act + C) (act_abc [3,64], B row ignored; NULL = plain),
+// Per-block partial sums of the weight gradient in the F(4x4,3x3) domain; operands transformed on load:
+// activation = relu?(A*act + C) (act_abc [3,64], B row ignored; NULL = plain),
 // gradient = A*dz + B*dz2 + C (dz_abc [3,64], dz2 nullable; NULL = plain).  ws: cova_conv3x3_wgrad4_workspace_floats.
 // dz_out (nullable, needs dz_abc): also writes the gradient operand as formed on load, NHWC [B,H,W,64] -- every pixel once.
 COVA_API int cova_conv3x3_wgrad4_partial(const float *act, const float *act_abc, int act_relu, const float *dz,

@@ -29,6 +29,7 @@
 #include "common.h"
 #include "bf3.h"
 #include "bn_tail.h"
+#include "options.h"
 #include <type_traits>
 
 // Ablation builds of tools/wino4_bench.py (COVA_EXTRA_FLAGS=-DW4_ABL=<mask>; 0 in the product): 1 no column stage,
@@ -603,8 +604,6 @@ __global__ void prep_wino4_kernel(const PrepW pw, float *__restrict__ u_fwd, flo
 
 }  // namespace
 
-int cova_internal_persistent_grid2(int ntiles, int blocks_per_cu);
-
 // ====================================================================================
 // C ABI
 // ====================================================================================
@@ -637,11 +636,6 @@ static int w4_grid(int B, int H, int W)
 
 COVA_API int cova_conv3x3_wino4_num_partials(int B, int H, int W) { return w4_grid(B, H, W); }
 
-// 1: every launch on the f32 main loop (A/B, tests); 0 (default): the split main loop wherever it exists (one input tensor)
-int g_w4_f32 = 0;
-int cova_internal_set_wino4_f32(int v) { g_w4_f32 = v != 0; return COVA_OK; }
-int cova_internal_get_wino4_f32() { return (int)g_w4_f32; }
-
 // floats per convolution and direction of the transformed-weight buffers: [f32 register image | bf16-piece register image]
 COVA_API int cova_conv3x3_wino4_u_floats(void) { return w4::U_TOTAL; }
 
@@ -669,7 +663,7 @@ template <bool STATS, int PRO, bool ADD, int BN>
 void launch_w4(const W4Args &a, int grid, hipStream_t st)
 {
     if constexpr (PRO != 2) {
-        if (!g_w4_f32) {             // split main loop: the piece image sits behind the f32 image
+        if (!cova_options().wino4_f32) {   // split main loop wherever it exists (one input tensor): the piece image sits behind the f32 image
             W4Args b = a;
             b.u = a.u + w4::U_FLOATS;
             hipLaunchKernelGGL((conv3x3_c64_wino4s_kernel<STATS, PRO, ADD, BN>), dim3(grid), dim3(w4::THREADS), 0, st, b);
@@ -734,7 +728,7 @@ COVA_API int cova_conv3x3_wino4(const float *in, const float *u, float *out, flo
 }
 
 // The same convolution on relu?(A[c]*in + C[c]) formed on load (pro_abc [3][64] = A | unused | C; zero padding stays
-// zero): a BatchNorm(+ReLU) folded into the consuming conv, as cova_conv3x3_wino_pro without a second tensor.
+// zero): a BatchNorm(+ReLU) folded into the consuming conv: cova_conv3x3_wino4_full without a second tensor.
 COVA_API int cova_conv3x3_wino4_pro(const float *in, const float *pro_abc, int pro_relu, const float *u, float *out,
                                     float *stat_part, int B, int H, int W, void *stream)
 {
@@ -743,7 +737,7 @@ COVA_API int cova_conv3x3_wino4_pro(const float *in, const float *pro_abc, int p
                   out, stat_part, B, H, W, stream);
 }
 
-// Full form, same contract as cova_conv3x3_wino_pro (conv_wino.hip): input f(A*in + B*in2 + C) on load (pro_abc / in2
+// Full form (the contract is spelled out in include/cova_hip.h): input f(A*in + B*in2 + C) on load (pro_abc / in2
 // nullable), epilogue  (+ addend) (x ReLU mask from act, or from fma(mask_scale, z, mask_shift) when act is NULL)
 // with the BatchNorm-backward sums (sum g, sum g*xhat(z)) in stat_part when z is given, else plain statistics.
 COVA_API int cova_conv3x3_wino4_full(const float *in, const float *in2, const float *pro_abc, int pro_relu,

@@ -17,6 +17,7 @@
 // barrier, stash, barrier -- and splitting a tile on its way into LDS lengthens exactly that), a register-direct form without LDS
 // tiles, operand tiles two k-tiles ahead, two LDS buffers per k-group.
 #include "common.h"
+#include "options.h"
 #include <type_traits>
 
 namespace {
@@ -353,8 +354,6 @@ __global__ __launch_bounds__(128 * WM * KS) void sgemm_dma_kernel(const float *_
     else epilogue(std::integral_constant<int, 0>{});
 }
 
-int g_sgemm_dma = 1;         // cova_set_option(22, .): 1 = the LDS-DMA kernel wherever the operands allow it (default), 0 = never
-
 inline int vec_ok(const float *p, int ld) { return (((uintptr_t)p & 15) == 0 && (ld & 3) == 0) ? 1 : 0; }
 
 }  // namespace
@@ -371,7 +370,7 @@ static int sgemm_launch(int transA, int transB, int M, int N, int K, const float
     // 16-byte pieces of both operands: aligned bases and leading dimensions, K a multiple of 4, a row-contiguous operand's row
     // count a multiple of 4 (a piece never straddles the edge); 32-bit byte offsets inside an operand
     const long long a_bytes = 4ll * (transA ? (long long)K * lda : (long long)M * lda), b_bytes = 4ll * (transB ? (long long)N * ldb : (long long)K * ldb);
-    const bool dma = g_sgemm_dma && va && vb && (K & 3) == 0 && K >= 4 && (!transA || ((M & 3) == 0 && M >= 4)) &&
+    const bool dma = cova_options().sgemm_dma && va && vb && (K & 3) == 0 && K >= 4 && (!transA || ((M & 3) == 0 && M >= 4)) &&
                      (transB || ((N & 3) == 0 && N >= 4)) && a_bytes < (1ll << 31) && b_bytes < (1ll << 31);
     if (dma) {
         // tile shape by the grid it makes (measured on the six products of the head, profiles/r06_gemm_bench.txt): 32 x 64 tiles with two
@@ -410,9 +409,6 @@ static int sgemm_launch(int transA, int transB, int M, int N, int K, const float
     COVA_LAUNCH_CHECK();
     return COVA_OK;
 }
-
-int cova_internal_get_sgemm_dma() { return g_sgemm_dma; }
-int cova_internal_set_sgemm_dma(int v) { g_sgemm_dma = v != 0; return COVA_OK; }
 
 COVA_API int cova_sgemm(int transA, int transB, int M, int N, int K, const float *A, int lda,
                         const float *B, int ldb, float *C, int ldc, const float *bias,

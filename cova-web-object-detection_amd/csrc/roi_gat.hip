@@ -12,8 +12,7 @@
 // One wavefront per node: the K neighbour slots live in lanes (ceil(K / 64) passes, K <= 1024) for the softmax (shuffle
 // reductions), the D hidden channels live in lanes for the gather (256-byte coalesced rows).
 #include "bn_tail.h"
-
-int cova_internal_persistent_grid2(int ntiles, int blocks_per_cu);
+#include "options.h"
 
 namespace {
 
@@ -781,77 +780,6 @@ __global__ __launch_bounds__(256) void gat_fwd_wide_kernel(
         if (64 * c + lane < D) hprime[(size_t)n * ldh + 64 * c + lane] = acc[c];
 }
 
-// backward of the sparse part.  g = dL/dh' [N, D] (ld = ldg).
-//   dalpha_k = g . Wh_j[ctx_k];  de = alpha*(dalpha - sum alpha*dalpha) (0 on masked slots);
-//   du = de * LeakyReLU'(u);  ds_i = sum_k du_k;  dt[ctx_k] += du_k;
-//   dWh_i[i] = ds_i * a_i;  dWh_j[ctx_k] += alpha_k*g_i (+ dt_j*a_j added by gat_bwd_finish)
-// dWh [N, 2D] must be zeroed in its second half (and dt zeroed) before the launch.
-template <int KP>
-__global__ __launch_bounds__(256) void gat_bwd_kernel(
-    const float *__restrict__ g, int ldg, const float *__restrict__ Wh, int ldw,
-    const float *__restrict__ s, const float *__restrict__ t, const float *__restrict__ attn,
-    const int64_t *__restrict__ ctx, const float *__restrict__ att_w, int N, int K, int D,
-    float slope, float *__restrict__ dWh, int lddw, float *__restrict__ ds, float *__restrict__ dt)
-{
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (n >= N) return;
-    int jj[KP];
-    float alpha[KP], dalpha[KP];
-#pragma unroll
-    for (int p = 0; p < KP; ++p) {
-        const int k = 64 * p + lane;
-        long long j = -1;
-        alpha[p] = 0.f;
-        dalpha[p] = 0.f;
-        if (k < K) {
-            j = ctx[(size_t)n * K + k];
-            if (j >= N) j = -1;
-            alpha[p] = attn[(size_t)n * K + k];
-        }
-        jj[p] = (int)j;
-    }
-    // dalpha for every slot: lanes over channels, one wave reduction per slot
-#pragma unroll
-    for (int p = 0; p < KP; ++p)
-        for (int k = 0; k < min(64, K - 64 * p); ++k) {
-            const int jk = __shfl(jj[p], k, 64);
-            float part = 0.f;
-            if (jk >= 0)
-                for (int d = lane; d < D; d += 64)
-                    part += g[(size_t)n * ldg + d] * Wh[(size_t)jk * ldw + D + d];
-            part = wave_sum(part);
-            if (lane == k) dalpha[p] = part;
-        }
-    float ad = 0.f;
-#pragma unroll
-    for (int p = 0; p < KP; ++p) ad += alpha[p] * dalpha[p];
-    const float dot = wave_sum(ad);
-    float dus = 0.f;
-#pragma unroll
-    for (int p = 0; p < KP; ++p) {
-        float du = 0.f;
-        if (64 * p + lane < K && jj[p] >= 0) {
-            const float de = alpha[p] * (dalpha[p] - dot);
-            const float u = s[n] + t[jj[p]];
-            du = de * (u > 0.f ? 1.f : slope);
-            atomicAdd(dt + jj[p], du);
-        }
-        dus += du;
-    }
-    const float dsn = wave_sum(dus);
-    if (lane == 0) ds[n] = dsn;
-    for (int d = lane; d < D; d += 64) dWh[(size_t)n * lddw + d] = dsn * att_w[d];
-#pragma unroll
-    for (int p = 0; p < KP; ++p)
-        for (int k = 0; k < min(64, K - 64 * p); ++k) {
-            const int jk = __shfl(jj[p], k, 64);
-            const float ak = __shfl(alpha[p], k, 64);
-            if (jk < 0) continue;
-            for (int d = lane; d < D; d += 64)
-                atomicAdd(dWh + (size_t)jk * lddw + D + d, ak * g[(size_t)n * ldg + d]);
-        }
-}
-
 // ---- transposed neighbour index (CSR over destination nodes): lets the backward GATHER what the
 // reference's autograd scatters (index_select backward), with a fixed summation order -> no float atomics,
 // bit-identical reruns, for ARBITRARY context_indices (models.py:171-177 accepts any ids), not only the
@@ -954,7 +882,11 @@ __global__ __launch_bounds__(256) void csr_count_scan_kernel(const int64_t *__re
     }
 }
 
-// backward, source side (one wave per node i): everything that stays with node i -- du [N,K] (0 on pads),
+// backward of the sparse part.  g = dL/dh' [N, D] (ld = ldg).
+//   dalpha_k = g . Wh_j[ctx_k];  de = alpha*(dalpha - sum alpha*dalpha) (0 on masked slots);
+//   du = de * LeakyReLU'(u);  ds_i = sum_k du_k;  dt[ctx_k] += du_k;
+//   dWh_i[i] = ds_i * a_i;  dWh_j[ctx_k] += alpha_k*g_i + dt_j*a_j
+// Source side (one wave per node i): everything that stays with node i -- du [N,K] (0 on pads),
 // ds, dWh_i = ds * a_i.  The contributions to OTHER nodes (dt[ctx], dWh_j[ctx]) are gathered by
 // gat_bwd_dst_kernel from du / attn / g through the transposed index.
 template <int KP, bool EDGE = false>
@@ -1186,17 +1118,8 @@ __global__ __launch_bounds__(256) void gat_bwd_dst_wide_kernel(
         if (64 * c + lane < D) dWh[(size_t)j * lddw + D + 64 * c + lane] = accv[c] + dtj * att_w[D + 64 * c + lane];
 }
 
-// dWh_j[n] += dt[n]*a_j  (elementwise), and the attention-vector gradients
+// the attention-vector gradients
 //   d att_w[d] = sum_n ds[n]*Wh[n][d] (d < D), sum_n dt[n]*Wh[n][d] (d >= D); d att_b = sum ds
-__global__ void gat_bwd_addt_kernel(float *__restrict__ dWh, int lddw, const float *__restrict__ dt,
-                                    const float *__restrict__ att_w, int N, int D)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N * D) return;
-    const int n = i / D, d = i - n * D;
-    dWh[(size_t)n * lddw + D + d] += dt[n] * att_w[D + d];
-}
-
 // block = 64 columns; V = 4: a thread owns 4 adjacent columns (float4 per row) and the block walks 64 row slices
 // (V = 1: 16 slices, any D); the extra block past the 2D columns sums ds (the bias gradient)
 template <int V>
@@ -1289,18 +1212,14 @@ __global__ __launch_bounds__(256) void gat_edge_wgrad_final_kernel(const float *
 
 // 64-channel chunks per row the wide GAT kernels are instantiated for (0: D too large, or switched off by
 // cova_set_option(16, 0): the chunk-at-a-time kernels)
-int g_gat_wide = 1;
 inline int gat_wide_nd(int D)
 {
     const int nd = (D + 63) / 64;
-    if (!g_gat_wide || nd > 8) return 0;
+    if (!cova_options().gat_wide || nd > 8) return 0;
     return nd <= 4 ? nd : (nd <= 6 ? 6 : 8);
 }
 
 }  // namespace
-
-int cova_internal_set_gat_wide(int v) { g_gat_wide = v != 0; return COVA_OK; }
-int cova_internal_get_gat_wide() { return (int)g_gat_wide; }
 
 // ====================================================================================
 // C ABI
@@ -1625,8 +1544,7 @@ COVA_API int cova_gat_transpose_reuse(const int64_t *ctx, int N, int K, int *csr
 }
 
 // dWh [N, 2D] (ld = lddw) is fully written; ds, dt [N] scratch; d_att_w [2D], d_att_b [1].
-// csr (from cova_gat_transpose) + du [N,K] scratch: gather form, no float atomics, bit-identical reruns.
-// csr == NULL: the scatter form with float atomics (kept for A/B measurements; not with EDGE).
+// csr (from cova_gat_transpose) + du [N,K] scratch, both required: gather form, no float atomics, bit-identical reruns.
 // EDGE = false is cova_gat_bwd (phi, edge_w, d_edge_w, edge_ws unused: NULL); true is cova_gat_bwd_edge.
 namespace {
 template <bool EDGE>
@@ -1636,7 +1554,7 @@ int gat_bwd_launch(const float *g, int ldg, const float *Wh, int ldw, const floa
                    const float *edge_w, float *d_edge_w, float *edge_ws, void *stream)
 {    hipStream_t st = (hipStream_t)stream;
     const int kp = (K + 63) / 64;
-    if (csr != nullptr && K <= 64 && gat_wide_nd(D) > 0) {
+    if (K <= 64 && gat_wide_nd(D) > 0) {
         const dim3 grid(cdiv(N, 4)), blk(256);
 #define COVA_GAT_BWD_WIDE(ND)                                                                                               \
         do {                                                                                                                \
@@ -1655,7 +1573,7 @@ int gat_bwd_launch(const float *g, int ldg, const float *Wh, int ldw, const floa
         }
 #undef COVA_GAT_BWD_WIDE
         COVA_LAUNCH_CHECK();
-    } else if (csr != nullptr) {
+    } else {
 #define COVA_GAT_SRC(KP) hipLaunchKernelGGL((gat_bwd_src_kernel<KP, EDGE>), dim3(cdiv(N, 4)), dim3(256), 0, st, g, ldg, Wh, ldw, s, t, \
                                             attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, du, phi, edge_w)
         switch (kp) {
@@ -1674,30 +1592,6 @@ int gat_bwd_launch(const float *g, int ldg, const float *Wh, int ldw, const floa
         COVA_LAUNCH_CHECK();
         hipLaunchKernelGGL(gat_bwd_dst_kernel, dim3(cdiv(N, 4)), dim3(256), 0, st, g, ldg, attn, du, csr,
                            csr + N + 1, att_w, N, K, D, dWh, lddw, dt);
-        COVA_LAUNCH_CHECK();
-    } else {
-        hipError_t e = hipMemsetAsync(dt, 0, sizeof(float) * (size_t)N, st);
-        if (e != hipSuccess) return (int)e;
-        e = hipMemset2DAsync(dWh + D, sizeof(float) * (size_t)lddw, 0, sizeof(float) * (size_t)D, (size_t)N, st);
-        if (e != hipSuccess) return (int)e;
-#define COVA_GAT_BWD(KP) hipLaunchKernelGGL(gat_bwd_kernel<KP>, dim3(cdiv(N, 4)), dim3(256), 0, st, g, ldg, Wh, ldw, s, t, attn, \
-                                            ctx, att_w, N, K, D, slope, dWh, lddw, ds, dt)
-        switch (kp) {
-        case 1: COVA_GAT_BWD(1); break;
-        case 2: COVA_GAT_BWD(2); break;
-        case 3: COVA_GAT_BWD(3); break;
-        case 4: COVA_GAT_BWD(4); break;
-        case 5: COVA_GAT_BWD(5); break;
-        case 6: COVA_GAT_BWD(6); break;
-        case 7: COVA_GAT_BWD(7); break;
-        case 8: COVA_GAT_BWD(8); break;
-        case 9: case 10: case 11: case 12: COVA_GAT_BWD(12); break;
-        default: COVA_GAT_BWD(16); break;
-        }
-#undef COVA_GAT_BWD
-        COVA_LAUNCH_CHECK();
-        hipLaunchKernelGGL(gat_bwd_addt_kernel, dim3(cdiv(N * D, 256)), dim3(256), 0, st, dWh, lddw, dt,
-                           att_w, N, D);
         COVA_LAUNCH_CHECK();
     }
     const bool v4 = (D % 4 == 0) && (ldw % 4 == 0) && (((uintptr_t)Wh & 15) == 0);
@@ -1723,7 +1617,7 @@ COVA_API int cova_gat_bwd(const float *g, int ldg, const float *Wh, int ldw, con
 {
     COVA_REQUIRE(g && Wh && s && t && attn && ctx && att_w && dWh && ds && dt && d_att_w && d_att_b);
     COVA_REQUIRE(K > 0 && K <= COVA_GAT_MAX_K && D > 0 && N > 0);
-    COVA_REQUIRE(!csr || du);
+    COVA_REQUIRE(csr && du);
     return gat_bwd_launch<false>(g, ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, dt, d_att_w,
                                  d_att_b, csr, du, nullptr, nullptr, nullptr, nullptr, stream);
 }

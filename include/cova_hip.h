@@ -64,8 +64,10 @@ int cova_conv_out_size(int in_size, int kernel, int stride, int pad);
  *   22 = cova_sgemm with the operand tiles brought in by global -> LDS copies (1, default: taken when both operands allow 16-byte
  *        pieces) or staged through registers (0: the kernel every other shape takes).
  * 14, 16 and 22 select between two kernels that both run by default (by alignment / by shape): the tests use them to compare the forms.
- * The option state is a PER-PROCESS CONSTANT: it may be set until the library's first query or launch and is fixed from then on
- * (launches captured into a hipGraph, workspace sizes already queried and a trainer's buffers all depend on it) -- a later
+ * The option state is a PER-PROCESS CONSTANT: it may be set until the first size query or launch that depends on ANY of the six
+ * options (every persistent-grid launch and *_num_partials / *_workspace_floats query reads the grid cap; cova_sgemm, cova_bn1d_*
+ * and cova_gat_* read theirs) and is fixed from then on, all six keys together -- launches captured into a hipGraph, workspace
+ * sizes already queried and a trainer's buffers all depend on it.  A later
  * cova_set_option that would CHANGE a value returns COVA_ERR_BAD_ARG (10001).  A process that sets COVA_ALLOW_OPTION_CHANGES=1
  * in its environment before the library is loaded keeps them mutable (the test suite and bench.py's `ab` legs, which re-query
  * every workspace size per step, do); options 7 and 9 change the result of the matching *_num_partials queries. */
@@ -114,9 +116,9 @@ int cova_conv1_wgrad_poolbwd(const float *img, const float *y1, const float *dp,
  * round 1 live in tools/csrc as well. */
 /* Weight gradient in Winograd F(4x4,3x3) form (csrc/conv_wgrad4.hip; 1.78x fewer MFMAs than the F(2x2,3x3) form,
  * fp32 error 3.7e-6 of the gradient's scale): replaces autograd's conv2d weight gradient of the four layer1 3x3
- * convolutions (torchvision BasicBlock conv1 / conv2, models.py:49-51; loss.backward() at train.py:59).  Same two-step
- * contract as cova_conv3x3_wgrad_wino_partial / _finish: activation = relu?(A*act + C) on load (act_abc nullable),
- * gradient = A*dz + B*dz2 + C on load (dz_abc, dz2 nullable), per-block partials into ws
+ * convolutions (torchvision BasicBlock conv1 / conv2, models.py:49-51; loss.backward() at train.py:59).  Two steps:
+ * activation = relu?(A*act + C) on load (act_abc nullable), gradient = A*dz + B*dz2 + C on load (dz_abc, dz2 nullable;
+ * the [3][64] = A | B | C coefficient layout of cova_conv3x3_wino4_full's prologue), per-block partials into ws
  * (cova_conv3x3_wgrad4_workspace_floats; each block applies G^T . G to its own sums in fp64 and writes [9][64][64]),
  * then the fp64 fold of up to four convolutions in one launch. */
 int cova_conv3x3_wgrad4_num_partials(int B, int H, int W);
@@ -135,8 +137,9 @@ int cova_conv3x3_wgrad4(const float *act, const float *dz, float *dw /*OIHW*/, f
 /* F(4x4,3x3) form of the same convolution (csrc/conv_wino4.hip; 1.78x fewer MFMAs than F(2x2,3x3), fp32 error 2.9e-6 of
  * the output scale): u_fwd / u_dgrad cova_conv3x3_wino4_u_floats() floats each per convolution (the per-wave register
  * images written by the prep kernel: the f32 image, its three-bf16-piece image, and the piece image of -U -- the tiles of odd
- * tile rows (ty) are multiplied with the negated weights and un-negated in the epilogue, so that the bf16 MFMA's sign-asymmetric
- * accumulation (7e-8 of the mean magnitude toward -inf on every output, tools/w4s_bias.py) cancels in sums over a map);
+ * tile row ty (rows of 8-pixel-high block tiles, counted per page) are multiplied with the negated weights and un-negated in the
+ * epilogue, so that the bf16 MFMA's sign-asymmetric accumulation (7e-8 of the mean magnitude toward -inf on every output,
+ * tools/w4s_bias.py) cancels in sums over a map; a map of one tile row (tiles_y == 1) has no negated tiles at all);
  * stat_part (nullable) [cova_conv3x3_wino4_num_partials][2][64] = (sum y, sum y^2).
  * Arithmetic: f32 in, f32 out, f32 transforms and accumulation; the transform-domain products run on the bf16 matrix pipe
  * with both f32 operands taken as three round-to-nearest bf16 pieces and the six products of order <= 2 (as conv1, see
@@ -155,9 +158,13 @@ int cova_conv3x3_wino4(const float *in, const float *u, float *out, float *stat_
 /* ... on relu?(A[c]*in + C[c]) formed on load (pro_abc [3][64] = A | unused | C), zero padding stays zero */
 int cova_conv3x3_wino4_pro(const float *in, const float *pro_abc, int pro_relu, const float *u, float *out,
                            float *stat_part /*nullable*/, int B, int H, int W, void *stream);
-/* ... full form, the contract of cova_conv3x3_wino_pro: input f(A*in + B*in2 + C) on load (in2, pro_abc nullable);
- * epilogue (+ addend) x ReLU mask (act > 0, or fma(mask_scale, z, mask_shift) > 0 when act is NULL) with the
- * BatchNorm-backward sums (sum g, sum g*xhat(z)) in stat_part when z is given, plain statistics otherwise */
+/* ... full form.  The prologue / epilogue contract (cova_conv1x1 and the wgrad4 operands follow it):
+ *   on load   x = f(A[c]*in + B[c]*in2 + C[c]), pro_abc [3][C] = A | B | C per input channel, f = ReLU if pro_relu; in2 NULL drops
+ *             the B term, pro_abc NULL takes in as it is; zero padding stays zero.
+ *   epilogue  g = (acc + addend) x ReLU mask; addend (nullable) has the output's shape; the mask is act > 0, or
+ *             fma(mask_scale[c], z, mask_shift[c]) > 0 when act is NULL, and absent when neither is given.
+ *   stat_part z given: the BatchNorm-backward sums (sum g, sum g*xhat(z)), xhat(z) = (z - mean[c]) * invstd[c];
+ *             z NULL: the plain statistics (sum y, sum y^2) of the output. */
 int cova_conv3x3_wino4_full(const float *in, const float *in2 /*nullable*/, const float *pro_abc /*nullable*/,
                             int pro_relu, const float *u, const float *addend /*nullable*/,
                             const float *act /*nullable*/, const float *mask_scale /*nullable*/,
@@ -186,7 +193,7 @@ int cova_conv3x3_wino4_bnact(const float *in, const float *pro_abc /*nullable*/,
  * models.py:49): 1x1 convolutions of torchvision's Bottleneck (conv1, conv3, downsample[0]) on NHWC rows.
  * out[r,co] = sum_ci f(A[ci]*in[r,ci] + B[ci]*in2[r,ci] + C[ci]) * w[co,ci], (Cin,Cout) in {(64,64),(64,256),
  * (256,64)}; w [Cout,Cin] row-major (= OIHW), or with w_trans [Cin,Cout] (data gradient of the conv whose
- * weight it is).  Prologue / epilogue arguments as cova_conv3x3_wino_pro; stat_part
+ * weight it is).  Prologue / epilogue arguments as cova_conv3x3_wino4_full; stat_part
  * [cova_conv1x1_num_partials][2][Cout] = (sum y, sum y^2) when z == NULL, else (sum dy, sum dy*xhat);
  * z2/mean2/invstd2 + stat_part2: a second BatchNorm (the downsample branch) fed by the same dy.
  * z == NULL with act != NULL (Cout = 256): (acc + addend) * [act > 0] without sums (taken by cova_conv1x1_vprod);
@@ -421,12 +428,12 @@ int cova_gat_transpose(const int64_t *ctx, int N, int K, int *csr /*[cova_gat_tr
 /* ... into a workspace kept from call to call (one per stream): the last 2N + 16 ints of csr must be zero on entry --
  * zero the buffer once when allocating it -- and are left zero: three launches, no memsets */
 int cova_gat_transpose_reuse(const int64_t *ctx, int N, int K, int *csr, void *stream);
-/* csr + du [N,K] scratch: deterministic gather form; csr == NULL: scatter form with float atomics */
+/* backward of cova_gat_fwd: gathers through csr (cova_gat_transpose) with du [N,K] as scratch -- fixed summation order, no
+ * float atomics, bit-identical reruns.  csr and du are REQUIRED: NULL returns COVA_ERR_BAD_ARG before anything is launched. */
 int cova_gat_bwd(const float *g, int ldg, const float *Wh, int ldw, const float *s, const float *t,
                  const float *attn, const int64_t *ctx, const float *att_w, int N, int K, int D,
                  float slope, float *dWh /*[N,2D]*/, int lddw, float *ds /*[N]*/, float *dt /*[N]*/,
-                 float *d_att_w /*[2D]*/, float *d_att_b /*[1]*/, const int *csr /*nullable*/,
-                 float *du /*nullable [N,K]*/, void *stream);
+                 float *d_att_w /*[2D]*/, float *d_att_b /*[1]*/, const int *csr, float *du /*[N,K]*/, void *stream);
 /* ---- edge geometry in the attention score (opt-in: CoVA(edge_geometry=True); the reference has no such term) ----
  * cova_gat_fwd_edge: cova_gat_fwd with the pre-activation of slot k of node i extended by an additive edge term,
  *   u = s[i] + t[j] + sum_e edge_w[e] * phi[i,k,e]   (one fma chain, e ascending, added to s[i] + t[j] last),
@@ -438,8 +445,8 @@ int cova_gat_fwd_edge(const float *Wh, int ldw, const float *att_w /*[2D]*/, con
                       const int64_t *ctx /*[N,K]*/, const float *phi /*[N,K,8]*/, const float *edge_w /*[8]*/, int N,
                       int K, int D, float slope, float *s /*[N]*/, float *t /*[N]*/, float *attn /*[N,K]*/,
                       float *hprime, int ldh, void *stream);
-/* cova_gat_bwd_edge: cova_gat_bwd's gather form (csr and du are REQUIRED; the scatter form with float atomics is not
- * extended) for a forward made by cova_gat_fwd_edge: the LeakyReLU slope of a slot follows the forward's u bit for bit.
+/* cova_gat_bwd_edge: cova_gat_bwd for a forward made by cova_gat_fwd_edge: the LeakyReLU slope of a slot follows the
+ * forward's u bit for bit.
  * Also d_edge_w[e] = sum_{i,k} du[i,k] * phi[i,k,e] [8]: per-block partials of fixed 4096-slot chunks in `workspace`
  * (cova_gat_edge_workspace_floats(N, K) floats), then summed in index order by one block -- no atomics, bits independent
  * of timing and grid.  There is no gradient with respect to the boxes.  With edge_w = 0, dWh / d_att_w / d_att_b have

@@ -243,3 +243,48 @@ def test_check_batch_host_contract():
     engine.check_batch(cfg, img, bb, af, torch.zeros(6, 100, dtype=torch.long), True)      # -cs 50: beyond one wavefront
     with pytest.raises(ValueError):
         engine.check_batch(cfg, img, bb, af, torch.zeros(6, engine.GAT_MAX_K + 1, dtype=torch.long), True)
+
+
+def _option_child(allow):
+    """Return codes of cova_set_option around a size query, and that query's results, from a fresh process (the option state
+    is per process; this suite's own process opted in to changes)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import json, sys; sys.path.insert(0, %r)\n"
+            "import cova_amd; from cova_web_object_detection_amd import _lib; q = _lib.query\n"
+            "dead = lambda: [q('cova_set_option', k, 1) for k in (3, 5, 6, 10, 13, 17)]\n"
+            "r = {'dead_before': dead(), 'set': q('cova_set_option', 7, 1)}\n"
+            "r['n1'], r['big1'] = q('cova_conv1_num_partials', 2, 64, 64), q('cova_conv1_num_partials', 2, 1024, 1024)\n"
+            "r['to0'] = q('cova_set_option', 7, 0)\n"
+            "r['n0'], r['big0'] = q('cova_conv1_num_partials', 2, 64, 64), q('cova_conv1_num_partials', 2, 1024, 1024)\n"
+            "r['to1'], r['dead_after'] = q('cova_set_option', 7, 1), dead()\n"
+            "print(json.dumps(r))" % root)
+    env = {k: v for k, v in os.environ.items() if k not in ("COVA_ALLOW_OPTION_CHANGES", "COVA_CONV1_F32")}
+    if allow:
+        env["COVA_ALLOW_OPTION_CHANGES"] = "1"
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    return json.loads(out.stdout.strip().splitlines()[-1])
+
+
+def test_size_query_freezes_the_option_state():
+    """A size query that depends on an option fixes the state: a changing write is refused (10001), a write of the current value
+    succeeds; the keys that left the library are refused before and after."""
+    r = _option_child(allow=False)
+    assert r["dead_before"] == [10001] * 6 and r["dead_after"] == [10001] * 6
+    assert r["set"] == 0 and r["to0"] == 10001 and r["to1"] == 0
+    assert r["n0"] == r["n1"] > 0 and r["big0"] == r["big1"] > 0         # the refused write changed nothing
+
+
+def test_option_changes_opt_in_keeps_the_state_mutable():
+    """COVA_ALLOW_OPTION_CHANGES=1 at load: the same sequence succeeds throughout, and option 7 changes cova_conv1_num_partials
+    wherever the map has more tiles than the device has compute units (the f32 kernel runs two blocks per compute unit, the
+    bf16-split one runs one; both cut the map into 8 x 32 tiles, so the 8 tiles of 2 x 64 x 64 give 8 rows either way and the
+    2048 tiles of 2 x 1024 x 1024 show the difference)."""
+    r = _option_child(allow=True)
+    assert r["dead_before"] == [10001] * 6 and r["dead_after"] == [10001] * 6
+    assert r["set"] == 0 and r["to0"] == 0 and r["to1"] == 0
+    assert r["n1"] == r["n0"] == 8
+    assert r["big1"] == 2 * r["big0"] > 0

@@ -1403,3 +1403,57 @@ def test_option_state_is_fixed_after_the_first_query():
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     assert out.stdout.strip().splitlines()[-1] == "[0, 0, 10001, 0, 10001, 10001, 0]", out.stdout
+
+
+_OPTION_CHILD = """
+import sys; sys.path.insert(0, %r)
+import torch, cova_amd
+from cova_web_object_detection_amd import _lib, engine
+z = lambda *s: torch.zeros(*s, device="cuda:0")
+def sgemm():
+    _lib.call("cova_sgemm", 0, 0, 8, 8, 8, z(8, 8), 8, z(8, 8), 8, z(8, 8), 8, None, 0)
+def bn1d():
+    _lib.call("cova_bn1d_fwd", z(8, 4), 4, 8, 4, z(4), z(4), None, None, None, 0.1, 1e-5, 0, z(8, 4), 4, None, 4, None, 0.0, 0, 0,
+              z(4), z(4), z(4), z(4))
+def gat():
+    p = {"gat.W_i.weight": z(64, 8), "gat.W_j.weight": z(64, 8), "gat.attention_layer.weight": z(1, 128),
+         "gat.attention_layer.bias": z(1)}
+    engine.gat_fwd(z(8, 8), 8, 8, 8, torch.zeros(8, 4, dtype=torch.int64, device="cuda:0"), p, z(8, 64), 64)
+{"sgemm": sgemm, "bn1d": bn1d, "gat": gat}[sys.argv[1]]()
+torch.cuda.synchronize()
+key, other, default = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
+print([_lib.query("cova_set_option", key, other), _lib.query("cova_set_option", key, default)])
+"""
+
+
+@pytest.mark.parametrize("first,key,other,default", [("sgemm", 22, 0, 1), ("bn1d", 14, 0, 1), ("gat", 16, 0, 1)])
+def test_options_freeze_with_the_launch_that_consumes_them(first, key, other, default):
+    """A process whose FIRST library call is cova_sgemm / cova_bn1d_fwd / engine.gat_fwd has consumed option 22 / 14 / 16: the
+    state is fixed from that launch on -- the non-default value is refused (10001), the value it has is accepted."""
+    import os
+    import subprocess
+    import sys
+    code = _OPTION_CHILD % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k != "COVA_ALLOW_OPTION_CHANGES"}
+    out = subprocess.run([sys.executable, "-c", code, first, str(key), str(other), str(default)], capture_output=True,
+                         text=True, timeout=300, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert out.stdout.strip().splitlines()[-1] == "[10001, 0]", out.stdout
+
+
+def test_gat_bwd_refuses_a_null_csr():
+    """cova_gat_bwd has the gather form only: csr == NULL is a bad argument (10001) reported before anything is launched -- the
+    outputs keep their sentinel -- and the same call with a transposed index succeeds."""
+    N, K, D = 8, 4, 64
+    z = lambda *s: torch.zeros(*s, device=DEV)
+    ctx = torch.zeros(N, K, dtype=torch.int64, device=DEV)
+    dWh, ds, dt = (torch.full(s, 7.5, device=DEV) for s in ((N, 2 * D), (N,), (N,)))
+    args = lambda csr: (z(N, D), D, z(N, 2 * D), 2 * D, z(N), z(N), z(N, K), ctx, z(1, 2 * D), N, K, D, 0.2, dWh, 2 * D, ds, dt,
+                        z(1, 2 * D), z(1), csr, z(N, K))
+    with pytest.raises(_lib.CovaHipError, match="status 10001"):
+        call("cova_gat_bwd", *args(None))
+    torch.cuda.synchronize()
+    assert all(bool((t == 7.5).all()) for t in (dWh, ds, dt))
+    call("cova_gat_bwd", *args(engine.gat_transpose(ctx)))
+    torch.cuda.synchronize()
+    assert all(bool((t == 0).all()) for t in (dWh, ds, dt))       # zero tensors in, zero gradients out: fully written

@@ -38,7 +38,7 @@ for r in range(rounds):
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / 10
         prof, _lib.PROFILE = _lib.PROFILE, None
-        ms = {n.replace("cova_", ""): (sum(a.elapsed_time(b) for a, b, _ in v) / len(v) if v else 0.0) for n, v in prof.items()}
+        ms = {n.replace("cova_", ""): (sum(p[0].elapsed_time(p[1]) for p in v) / len(v) if v else 0.0) for n, v in prof.items()}
         print("round %d option(%d)=%d: %.3f ms/step | " % (r, key, val, dt * 1e3) + "  ".join("%s %.3f" % kv for kv in ms.items()), flush=True)
 if key:
     _lib.query("cova_set_option", key, 0)

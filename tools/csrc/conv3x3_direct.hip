@@ -5,6 +5,14 @@
 // point of DESIGN.md section 4.1 (133 TFLOP/s = 0.85 of the f32-MFMA peak) and for tools/conv_bench.py.
 #include "../../cova-web-object-detection_amd/csrc/common.h"
 
+// Ablation switches (key 5) exist only in builds made with COVA_ABLATE=1 in the environment (-DCOVA_ABLATE); otherwise the mask
+// folds to 0 and the branches disappear.
+#ifdef COVA_ABLATE
+#define COVA_ABL(x) (x)
+#else
+#define COVA_ABL(x) 0
+#endif
+
 namespace {
 
 // ------------------------------------------------------------------------------------

@@ -22,6 +22,14 @@
 // Per tile: 16 chunks x (16 A reads + 32 adds + 32 B reads + 32 MFMAs) per wave.
 #include "../../cova-web-object-detection_amd/csrc/common.h"
 
+// Ablation switches (key 5) exist only in builds made with COVA_ABLATE=1 in the environment (-DCOVA_ABLATE); otherwise the mask
+// folds to 0 and the branches disappear.
+#ifdef COVA_ABLATE
+#define COVA_ABL(x) (x)
+#else
+#define COVA_ABL(x) 0
+#endif
+
 namespace {
 
 // 256 zero bytes in global memory: refill loads of halo pixels outside the image (and of idle
