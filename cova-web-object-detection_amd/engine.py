@@ -1759,3 +1759,64 @@ def hard_negative_select(logits, labels, page_start, ratio, min_keep, drop_label
     call("cova_hard_negative_select", logits, labels, page_start, B, N, NC, ratio, min_keep, int(drop_label), out, scores,
          counts)
     return out, scores, counts
+
+
+# ------------------------------------------------------------------------------------------- per-page ranking loss
+def check_rank_options(page_rank_weight):
+    """Host validation of the ranking term's weight (ValueError) -> float; 0 means that the term is off."""
+    import math
+    import numbers
+    w = page_rank_weight
+    if isinstance(w, bool) or not isinstance(w, numbers.Real) or not math.isfinite(w) or w < 0:
+        raise ValueError("page_rank_weight must be a finite number >= 0 (0: off), got %r" % (w,))
+    return float(w)
+
+
+def _rank_shapes(logits, labels, page_start):
+    N, NC = logits.shape
+    B = page_start.shape[0] - 1
+    if page_start.dim() != 1 or B < 1 or labels.shape != (N,):
+        raise ValueError("the page ranking loss takes logits [N, C], labels [N] and page_start [B + 1], B >= 1; got %s, %s, %s"
+                         % (tuple(logits.shape), tuple(labels.shape), tuple(page_start.shape)))
+    _check(logits), _check(labels, torch.int64), _check(page_start, torch.int64)
+    return B, N, NC
+
+
+def _rank_ignore(opts):
+    ig = opts.get("ignore_index")
+    return (0, 0) if ig is None else (int(ig), 1)
+
+
+def page_rank_loss_fwd(logits, labels, page_start, class_weight, opts):
+    """Phase 1 of the per-page ranking loss (cova_page_rank_loss_fwd): per page of ``page_start`` (device int64 [B + 1])
+    and class c >= 1 the list of the page's candidate rows in column c -> (lists float64 [B, NC-1, 4] = lse of the
+    candidates, lse of the targets, candidate count, target count; acc float64 [3] = sum w_c L_pc, sum w_c, scored
+    lists).  ``opts`` gives the ignore label ("ignore_index", None: none).  Two launches, no host read."""
+    B, N, NC = _rank_shapes(logits, labels, page_start)
+    lists = _empty((B, max(NC - 1, 0), 4), logits, torch.float64)
+    acc = _empty((3,), logits, torch.float64)
+    call("cova_page_rank_loss_fwd", logits, labels, page_start, B, N, NC, class_weight, *_rank_ignore(opts), lists, acc)
+    return lists, acc
+
+
+def page_rank_loss_bwd(logits, labels, page_start, class_weight, opts, lists, acc, rank_weight, grad_scale=None,
+                       want_loss=True, want_grad=True, into=None):
+    """Phase 2: ``lists`` and ``acc`` (device; all-reduced first under data parallelism with "mean") -> (loss f32 [1] =
+    rank_weight * R, dlogits).  ``into`` = (loss or None, dlogits or None): the term and its gradient are added to these
+    tensors (the outputs of ce_loss_bwd on the same stream) instead, and they are returned."""
+    B, N, NC = _rank_shapes(logits, labels, page_start)
+    rank_weight = float(rank_weight)
+    if into is None:
+        loss = _empty((1,), logits) if want_loss else None
+        dl = _empty((N, NC), logits) if want_grad else None
+    else:
+        loss, dl = into
+        for t, shape in ((loss, (1,)), (dl, (N, NC))):
+            if t is not None:
+                _check(t)
+                if tuple(t.shape) != shape:
+                    raise ValueError("page_rank_loss_bwd: cannot accumulate into a tensor of shape %s, expected %s"
+                                     % (tuple(t.shape), shape))
+    call("cova_page_rank_loss_bwd", logits, labels, page_start, B, N, NC, class_weight, *_rank_ignore(opts), lists, acc,
+         rank_weight, 1 if opts.get("reduction", "sum") == "mean" else 0, grad_scale, loss, dl, 0 if into is None else 1)
+    return loss, dl

@@ -566,6 +566,31 @@ class _CELossFn(torch.autograd.Function):
         return dl, None, None, None
 
 
+class _CERankLossFn(torch.autograd.Function):
+    """The criterion pair followed by cova_page_rank_loss_fwd + cova_page_rank_loss_bwd as one autograd node: the ranking
+    term and its gradient are added to the pair's loss and dlogits (gradient with respect to the logits only)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, rank_labels, page_start, weight, opts, rank_opts, rank_weight):
+        lg, lb, rl, ps = _f32c(logits), _i64c(labels), _i64c(rank_labels), _i64c(page_start)
+        acc, _ = engine.ce_loss_fwd(lg, lb, weight, opts, want_pred=False)
+        loss, _ = engine.ce_loss_bwd(lg, lb, weight, opts, acc, want_grad=False)
+        lists, racc = engine.page_rank_loss_fwd(lg, rl, ps, weight, rank_opts)
+        engine.page_rank_loss_bwd(lg, rl, ps, weight, rank_opts, lists, racc, rank_weight, into=(loss, None))
+        ctx.save_for_backward(lg, lb, rl, ps, acc, lists, racc)
+        ctx.weight, ctx.opts, ctx.rank_opts, ctx.rank_weight = weight, opts, rank_opts, rank_weight
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad):
+        lg, lb, rl, ps, acc, lists, racc = ctx.saved_tensors
+        gs = grad.detach().to(torch.float32).reshape(1).contiguous()      # stays on the device, as in _CELossFn
+        _, dl = engine.ce_loss_bwd(lg, lb, ctx.weight, ctx.opts, acc, grad_scale=gs, want_loss=False)
+        engine.page_rank_loss_bwd(lg, rl, ps, ctx.weight, ctx.rank_opts, lists, racc, ctx.rank_weight, grad_scale=gs,
+                                  into=(None, dl))
+        return dl, None, None, None, None, None, None, None
+
+
 class CrossEntropyLoss(nn.Module):
     """torch.nn.CrossEntropyLoss's arguments and defaults on the HIP criterion kernels, plus ``focal_gamma`` (0, or >= 1:
     w[y] (1-p_y)^gamma (-log p_y); not together with label_smoothing).  ``forward(logits [N, C] f32, labels [N] int64)``
@@ -576,10 +601,15 @@ class CrossEntropyLoss(nn.Module):
     ``hard_negative_ratio`` (None: off) and ``hard_negative_min`` add per-page hard-negative mining:
     ``forward(logits, labels, page_start)`` with the pages' row offsets (device int64 [B + 1]) first relabels, without
     gradient, every background row (label 0) outside its page's max(hard_negative_min, floor(ratio * positives)) hardest
-    as ``ignore_index`` (one cova_hard_negative_select launch) and scores the rest."""
+    as ``ignore_index`` (one cova_hard_negative_select launch) and scores the rest.
+
+    ``page_rank_weight`` (0: off) adds ``page_rank_weight * R``, the per-page listwise ranking loss of the labelled rows
+    among the rows of their page ("Page ranking loss"), with the module's ``weight``, ``ignore_index``
+    and ``reduction``; ``forward(logits, labels, page_start)`` is then one autograd node over cova_ce_loss_fwd / _bwd and
+    cova_page_rank_loss_fwd / _bwd.  The lists are read from the given labels, whatever mining relabels."""
 
     def __init__(self, weight=None, ignore_index=-100, reduction="mean", label_smoothing=0.0, focal_gamma=0.0,
-                 hard_negative_ratio=None, hard_negative_min=0):
+                 hard_negative_ratio=None, hard_negative_min=0, page_rank_weight=0.0):
         super().__init__()
         if reduction == "none":
             raise ValueError('reduction="none" (per-box losses) is not implemented; use "mean" or "sum"')
@@ -596,8 +626,12 @@ class CrossEntropyLoss(nn.Module):
         self.label_smoothing, self.focal_gamma = float(label_smoothing), float(focal_gamma)
         self.hard_negative_ratio, self.hard_negative_min = engine.check_mining_options(hard_negative_ratio,
                                                                                        hard_negative_min)
+        self.page_rank_weight = engine.check_rank_options(page_rank_weight)
 
     def forward(self, input, target, page_start=None):
+        if self.page_rank_weight != 0.0 and page_start is None:
+            raise ValueError("CrossEntropyLoss(page_rank_weight=...) needs page_start (the pages' row offsets, "
+                             "int64 [B + 1]) as the third argument of forward")
         if self.hard_negative_ratio is not None and page_start is None:
             raise ValueError("CrossEntropyLoss(hard_negative_ratio=...) needs page_start (the pages' row offsets, "
                              "int64 [B + 1]) as the third argument of forward")
@@ -613,12 +647,21 @@ class CrossEntropyLoss(nn.Module):
                                          None, self.reduction)
         # torch's ignore_index may name a class (rows of that class are then skipped): no range check here
         opts["ignore_index"] = self.ignore_index
+        given = target
         if self.hard_negative_ratio is not None:
             _require_cuda(page_start)
             with torch.no_grad():
                 target, _, _ = engine.hard_negative_select(_f32c(input.detach()), _i64c(target), _i64c(page_start),
                                                            self.hard_negative_ratio, self.hard_negative_min,
                                                            self.ignore_index)
+        if self.page_rank_weight != 0.0:
+            _require_cuda(page_start)
+            if page_start.dim() != 1 or page_start.shape[0] < 2 or page_start.is_floating_point():
+                raise ValueError("page_start must hold B + 1 integer row offsets, B >= 1, got shape %s"
+                                 % (tuple(page_start.shape),))
+            rank_opts = dict(ignore_index=self.ignore_index, reduction=self.reduction)
+            return _CERankLossFn.apply(input, target, given, page_start, self.weight, opts, rank_opts,
+                                       self.page_rank_weight)
         return _CELossFn.apply(input, target, self.weight, opts)
 
     def extra_repr(self):
@@ -626,4 +669,6 @@ class CrossEntropyLoss(nn.Module):
             self.ignore_index, self.reduction, self.label_smoothing, self.focal_gamma)
         if self.hard_negative_ratio is not None:
             s += ", hard_negative_ratio=%g, hard_negative_min=%d" % (self.hard_negative_ratio, self.hard_negative_min)
+        if self.page_rank_weight != 0.0:
+            s += ", page_rank_weight=%g" % self.page_rank_weight
         return s

@@ -192,14 +192,21 @@ class HotPathTrainer:
     background boxes are not scored in this step (they stay graph context, ``pred`` still covers them, ``metrics`` count
     the scored rows only).  One cova_hard_negative_select launch between the forward and the criterion, which then runs
     through cova_ce_loss_fwd / cova_ce_loss_bwd; ``last_mined_labels`` / ``last_mining_counts`` hold the step's selection
-    on the device.  loss() and evaluation score every row."""
+    on the device.  loss() and evaluation score every row.
+
+    Page ranking loss ("Page ranking loss"): ``page_rank_weight`` (0: off) adds ``page_rank_weight * R``
+    to the step's loss, R the listwise loss of the labelled boxes among the boxes of their page, per page and class
+    column: the quantity the page top-k evaluation ranks.  The criterion then runs through cova_ce_loss_fwd /
+    cova_ce_loss_bwd followed by cova_page_rank_loss_fwd / cova_page_rank_loss_bwd, which add the term and its gradient
+    to the pair's outputs; ``last_rank_lists`` / ``last_rank_acc`` hold the step's tables on the device.  loss()
+    includes the term; ``metrics`` and evaluate_split(with_loss=) count the cross-entropy alone."""
 
     def __init__(self, cfg, state_dict, device, lr=5e-4, weight_decay=1e-3, betas=(0.9, 0.999),
                  eps=1e-8, world_size=1, process_group=None, dropout_seed=123, sync_bn=False, frozen=(), bn_eval=(),
                  optimizer="adam", momentum=0.0, dampening=0.0, nesterov=False, param_groups=None,
                  max_grad_norm=None, norm_type=2.0, class_weight=None, label_smoothing=0.0, focal_gamma=0.0,
                  ignore_index=None, loss_reduction="sum", track_metrics=False, hard_negative_ratio=None,
-                 hard_negative_min=0):
+                 hard_negative_min=0, page_rank_weight=0.0):
         if optimizer not in OPTIMIZERS:
             raise ValueError("optimizer must be one of %s, got %r" % (OPTIMIZERS, optimizer))
         if float(norm_type) != 2.0:
@@ -232,6 +239,7 @@ class HotPathTrainer:
         self._setup_optimizer(optimizer, momentum, dampening, nesterov, param_groups, max_grad_norm)
         self._setup_criterion(class_weight, label_smoothing, focal_gamma, ignore_index, loss_reduction, track_metrics)
         self._setup_mining(hard_negative_ratio, hard_negative_min)
+        self._setup_rank(page_rank_weight)
         self._ar_events = []              # (start, end) HIP events around the collective waits of optimizer_step
         self.measure_allreduce = True     # record them (up to 4096 steps; exposed_allreduce_ms() drains the list)
         if world_size > 1:
@@ -357,25 +365,64 @@ class HotPathTrainer:
         ratio, min_keep = engine.check_mining_options(o.get("hard_negative_ratio"), o.get("hard_negative_min", 0))
         return None if ratio is None else (ratio, min_keep)
 
+    @staticmethod
+    def _check_paged(batch, what):
+        if batch.get("page_start") is None and batch.get("images") is None:
+            raise ValueError("%s needs the batch's page_start (or its images, for the page count)" % what)
+
+    @staticmethod
+    def _page_start(batch, device):
+        """The pages' row offsets (device int64 [B + 1]) without a host read: the batch's, or derived from the page
+        column of the page-sorted bboxes and the page count of the images."""
+        page_start = batch.get("page_start")
+        if page_start is None:
+            pages = torch.arange(int(batch["images"].shape[0]) + 1, dtype=torch.float32, device=device)
+            page_start = torch.searchsorted(batch["bboxes"][:, 0].contiguous(), pages)
+        return page_start.contiguous()
+
     def _mine(self, logits, batch, opts, mining):
         """cova_hard_negative_select on this step's logits -> (labels for the criterion, its options with the drop
         label as the ignore label).  No host read: page_start is the batch's, or comes from the page column of the
         page-sorted bboxes."""
-        page_start = batch.get("page_start")
-        if page_start is None:
-            pages = torch.arange(int(batch["images"].shape[0]) + 1, dtype=torch.float32, device=logits.device)
-            page_start = torch.searchsorted(batch["bboxes"][:, 0].contiguous(), pages)
         if opts["ignore_index"] is None:
             opts = dict(opts, ignore_index=engine.MINED_OUT)
-        mined, _, counts = engine.hard_negative_select(logits, batch["labels"], page_start.contiguous(), mining[0],
-                                                       mining[1], opts["ignore_index"], want_counts=True)
+        mined, _, counts = engine.hard_negative_select(logits, batch["labels"], self._page_start(batch, logits.device),
+                                                       mining[0], mining[1], opts["ignore_index"], want_counts=True)
         self.last_mined_labels, self.last_mining_counts = mined, counts
         return mined, opts
 
-    def _criterion(self):
-        """None: the step's criterion is cova_ce_sum (no option set, no mining); else the checked options of this step."""
+    def _setup_rank(self, weight):
+        """``page_rank_weight`` joins ``loss_options`` only when it is non-zero (a default trainer's dict stays as it
+        was); it is read and checked at every step, so it may be set, changed or zeroed between steps."""
+        weight = engine.check_rank_options(weight)
+        if weight != 0.0:
+            self.loss_options["page_rank_weight"] = weight
+        self.last_rank_lists = self.last_rank_acc = None
+
+    def _rank(self):
+        """This step's checked weight of the ranking term; 0.0: the term is off."""
+        return engine.check_rank_options(self.loss_options.get("page_rank_weight", 0.0))
+
+    def _rank_term(self, logits, batch, rank_weight, loss, dl):
+        """cova_page_rank_loss_fwd / _bwd on this step's logits: adds rank_weight * R to ``loss`` and its gradient to
+        ``dl`` (None: the loss alone), the outputs of the cova_ce_loss pair -> (lists, acc).  The lists are read from the batch's own
+        labels with the trainer's own ignore label, whatever mining relabelled for the cross-entropy."""
         o = self.loss_options
-        if (self._mining() is None and self.class_weight is None and self.metrics is None and o["label_smoothing"] == 0.0
+        ropts = dict(ignore_index=o["ignore_index"], reduction=o["loss_reduction"])
+        page_start = self._page_start(batch, logits.device)
+        lists, acc = engine.page_rank_loss_fwd(logits, batch["labels"], page_start, self.class_weight, ropts)
+        if self.world_size > 1 and ropts["reduction"] == "mean":
+            import torch.distributed as dist
+            dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=self.group)
+        engine.page_rank_loss_bwd(logits, batch["labels"], page_start, self.class_weight, ropts, lists, acc, rank_weight,
+                                  into=(loss, dl))
+        return lists, acc
+
+    def _criterion(self):
+        """None: the step's criterion is cova_ce_sum (no option set, no mining, no ranking term); else the checked
+        options of this step."""
+        o = self.loss_options
+        if (self._mining() is None and self._rank() == 0.0 and self.class_weight is None and self.metrics is None and o["label_smoothing"] == 0.0
                 and o["focal_gamma"] == 0.0 and o["ignore_index"] is None and o["loss_reduction"] == "sum"):
             return None
         return engine.check_loss_options(int(self.cfg["n_classes"]), None, o["label_smoothing"], o["focal_gamma"],
@@ -563,9 +610,11 @@ class HotPathTrainer:
         with criterion options the local sum ("sum") / the mean over the global batch ("mean").  A batch with
         ``visual_feats`` (DeviceDataset.batches(features=)) skips the conv stack and the RoI op; it raises ValueError
         unless the conv stack is frozen with its BatchNorms in eval mode."""
-        opts, mining = self._criterion(), self._mining()
-        if mining is not None and batch.get("page_start") is None and batch.get("images") is None:
-            raise ValueError("hard-negative mining needs the batch's page_start (or its images, for the page count)")
+        opts, mining, rank_weight = self._criterion(), self._mining(), self._rank()
+        if mining is not None:
+            self._check_paged(batch, "hard-negative mining")
+        if rank_weight != 0.0:
+            self._check_paged(batch, "the page ranking loss")
         # With SyncBN a one-box shard is legal (the statistics are over the whole batch, as torch.nn.SyncBatchNorm
         # accepts it): the train-mode "more than 1 value per channel" check then applies to the GLOBAL box count, which
         # _stat_sync has from its all-reduce -- every rank raises together instead of one rank leaving the others
@@ -592,6 +641,8 @@ class HotPathTrainer:
                     labels, opts = self._mine(logits, batch, opts, mining)
                 loss, dl, pred = self._criterion_fwd_bwd(logits, labels, opts,
                                                          None if self.metrics is None else self.metrics.buf)
+                if rank_weight != 0.0:
+                    self.last_rank_lists, self.last_rank_acc = self._rank_term(logits, batch, rank_weight, loss, dl)
             self._head_work = None
             overlap = self.world_size > 1 and engine.OPTIONS.overlap_allreduce
             engine.model_bwd(sv, dl, self.params, self.grads,
@@ -745,8 +796,14 @@ class HotPathTrainer:
     @torch.no_grad()
     def loss(self, batch):
         """Validation loss: eval-mode forward (running statistics, as predict) and the configured criterion (without
-        options CrossEntropyLoss(reduction="sum")).  Returns the device scalar; ``metrics`` is not touched."""
+        options CrossEntropyLoss(reduction="sum")), the page ranking term included when ``page_rank_weight`` is set.
+        Returns the device scalar; ``metrics`` is not touched."""
+        rank_weight = self._rank()
+        if rank_weight != 0.0:
+            self._check_paged(batch, "the page ranking loss")
         logits, _ = self.predict(batch)
         opts = self._criterion() or engine.check_loss_options(int(self.cfg["n_classes"]))
         loss, _, _ = self._criterion_fwd_bwd(logits, batch["labels"], opts, None, want_grad=False)
+        if rank_weight != 0.0:
+            self._rank_term(logits, batch, rank_weight, loss, None)
         return loss[0]

@@ -558,6 +558,40 @@ int cova_ce_loss_bwd(const float *logits, const int64_t *labels, int N, int NC, 
 int cova_hard_negative_select(const float *logits, const int64_t *labels, const int64_t *page_start, int B, int N, int NC,
                               double ratio, int min_keep, long long drop_label, int64_t *labels_out /*[N]*/,
                               float *score_out /*nullable [N]*/, int *counts /*nullable [B,3]*/, void *stream);
+/* per-page listwise ranking loss (rank.hip; HotPathTrainer(page_rank_weight=) and models.CrossEntropyLoss(page_rank_weight=)):
+ * the training term over the lists cova_eval_page_ranks ranks.  Page p owns rows [s_p, e_p), clamped as for
+ * cova_hard_negative_select above (page_start DEVICE int64 [B+1], non-decreasing by the caller's contract; otherwise the
+ * only guarantee is that no access is out of bounds).  A list is (page p, class c), c in 1..NC-1, with v_n = logits[n, c].
+ * A row of the page is a candidate when 0 <= label < NC and it does not carry the ignore label (has_ignore_index != 0 and
+ * label == ignore_index); a candidate is a target of the list when label == c.  Rows with the ignore label or a bad
+ * label, and rows outside [page_start[0], page_start[B]), take no part.  A list with at least one target is scored:
+ *   L_pc       = lse_candidates(v) - lse_targets(v)                     (one target t: lse - v_t)
+ *   dL_pc/dv_n = softmax_cand(v)_n - [n is a target] softmax_tgt(v)_n
+ * Arithmetic, so that a list's result is a function of its page's rows alone: per list one wave; the two maxima m are
+ * f32 compares (a NaN never wins); each term is expf(v - m) in f32; the terms are summed in float64, lane i taking the
+ * page's rows i, i + 64, ... in turn, then the xor butterfly (offsets 32, 16, .., 1); lse = (double)m + log(sum) in
+ * double.  lists DEVICE float64 [B, NC-1, 4] = lse of the candidates, lse of the targets, candidate count, target count;
+ * an unscored list writes its counts and zeros for the lse fields.  acc DEVICE float64 [3] = sum w_c L_pc, sum w_c and
+ * the number of scored lists, w_c = class_weight[c] (1 when NULL), folded from the table by one wave (lane i: lists i,
+ * i + 64, ...; then the butterfly).  The rank term is R = acc[0] ("sum") or acc[0] / acc[1] ("mean"; a zero denominator
+ * gives 0 and a zero gradient); under data parallelism acc is all-reduced between the two calls.
+ * cova_page_rank_loss_bwd, per candidate row n and class c >= 1 of a scored list:
+ *   x = (float)((double)v - lseA),  d = g * (expf(x) - [target] expf((float)((double)v - lseT))),
+ *   g = (float)(rank_weight * s * w_c), times grad_scale[0] when given (DEVICE [1]); s = 1 or 1 / acc[1].
+ * accumulate != 0: d is added to dlogits[n, c] and (float)(rank_weight * R) to loss_inout[0] (one f32 add each; every
+ * other entry keeps its bits; the call is stream-ordered after the cova_ce_loss_bwd that wrote them).  accumulate == 0:
+ * every entry of dlogits [N, NC] and the loss are written; column 0, non-candidates, rows outside the pages and unscored
+ * lists get zeros.  No multiply-add is fused.  2 <= NC <= 16, B >= 1, N >= 1, rank_weight finite and >= 0; at least
+ * one of loss_inout / dlogits.  Forward: two launches; backward: one, a thread per row.  No atomics, no workspace beyond
+ * lists, no host read; non-finite logits reach their own list only. */
+int cova_page_rank_loss_fwd(const float *logits, const int64_t *labels, const int64_t *page_start, int B, int N, int NC,
+                            const float *class_weight /*nullable*/, long long ignore_index, int has_ignore_index,
+                            double *lists /*[B,NC-1,4]*/, double *acc /*[3]*/, void *stream);
+int cova_page_rank_loss_bwd(const float *logits, const int64_t *labels, const int64_t *page_start, int B, int N, int NC,
+                            const float *class_weight /*nullable*/, long long ignore_index, int has_ignore_index,
+                            const double *lists, const double *acc_total, double rank_weight, int reduction_mean,
+                            const float *grad_scale /*nullable*/, float *loss_inout /*nullable*/,
+                            float *dlogits /*nullable*/, int accumulate, void *stream);
 /* evaluation decision (train.py:131-153): per page and class column, page-local indices of the k
  * highest-scoring boxes, best first; page_start [n_pages+1] are box offsets; out [n_pages,NC,k] */
 int cova_page_class_topk(const float *logits, const int64_t *page_start, int n_pages, int NC, int k,

@@ -1,0 +1,411 @@
+"""The per-page ranking loss on the GPU: cova_page_rank_loss_fwd / _bwd through the C ABI against tests/rank_oracle.py
+(float64; gates counted from the contract's arithmetic), the exact facts of the contract, reproducibility and page
+independence, the data-parallel "mean" in one process, refusals, HotPathTrainer(page_rank_weight=) (launches, no host
+synchronisation, the loss and the linearity of the wiring) and the drop-in CrossEntropyLoss."""
+import os
+import sys
+
+sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
+sys.path.insert(0, os.path.abspath(os.path.dirname(__file__)))
+import cova_amd  # noqa: E402,F401
+
+import numpy as np  # noqa: E402
+import pytest  # noqa: E402
+import torch  # noqa: E402
+
+from cova_web_object_detection_amd import _lib, engine  # noqa: E402
+from cova_web_object_detection_amd.models import CrossEntropyLoss  # noqa: E402
+from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
+import rank_oracle as RO  # noqa: E402
+from test_optim_gpu import CFG, _profiled, dev_batch, trainer_setup  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+EPS32 = float(np.finfo(np.float32).eps)
+FWD, BWD = "cova_page_rank_loss_fwd", "cova_page_rank_loss_bwd"
+PAIR = ("cova_ce_loss_fwd", "cova_ce_loss_bwd")
+SIZES = [0, 1, 2, 63, 64, 65, 230, 1025, 3000]
+HEAD, TAIL = 5, 7                                             # rows before page_start[0] and from page_start[B] on
+
+
+def dev(t, dtype=None):
+    return None if t is None else torch.as_tensor(t, dtype=dtype).to(DEV)
+
+
+def fwd(logits, labels, page_start, w=None, ignore=-100):
+    lists, acc = engine.page_rank_loss_fwd(dev(logits), dev(labels), dev(page_start, torch.int64), dev(w),
+                                           dict(ignore_index=ignore))
+    return lists, acc
+
+
+def bwd(logits, labels, page_start, lists, acc, weight, w=None, ignore=-100, reduction="sum", grad_scale=None, into=None):
+    """-> (loss f32 [1], dlogits) on the device"""
+    return engine.page_rank_loss_bwd(dev(logits), dev(labels), dev(page_start, torch.int64), dev(w),
+                                     dict(ignore_index=ignore, reduction=reduction), lists, acc, weight,
+                                     grad_scale=grad_scale, into=into)
+
+
+def bits(t):
+    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
+
+
+def labelled(n, nc, g, background=0.9):
+    return torch.where(torch.rand(n, generator=g) < background, torch.zeros(n, dtype=torch.int64),
+                       torch.randint(1, nc, (n,), generator=g))
+
+
+def mixed_batch(nc, seed):
+    """the issue's page sizes in one batch with rows outside the pages, ignored and bad labels, the pinned pages"""
+    g = torch.Generator().manual_seed(seed)
+    n = HEAD + sum(SIZES) + TAIL
+    page_start = HEAD + np.concatenate([[0], np.cumsum(SIZES)])
+    logits = torch.randn(n, nc, generator=g) * 4
+    labels = labelled(n, nc, g)
+    labels[torch.rand(n, generator=g) < 0.04] = -100
+    labels[torch.rand(n, generator=g) < 0.04] = nc + 3
+    start = {sz: int(page_start[i]) for i, sz in enumerate(SIZES)}
+    labels[start[1]] = 1                                                   # one class-1 row
+    labels[start[2]:start[2] + 2] = 0                                      # no positive
+    labels[start[64]:start[64] + 64] = nc - 1                              # every row a target of the last class
+    s = start[65]
+    labels[s:s + 65][labels[s:s + 65] == 1] = 0
+    labels[s + 7] = labels[s + 40] = 1                                     # two class-1 targets
+    labels[:HEAD] = torch.tensor([1, 0, nc - 1, -100, 1])                  # outside rows take no part
+    labels[n - TAIL:] = 1
+    return logits, labels, page_start, start
+
+
+# ------------------------------------------------------------------------------------ 1. against the float64 oracle
+@pytest.mark.parametrize("nc", [2, 4, 16])
+def test_against_the_float64_oracle(nc):
+    # The gates count the contract's f32 operations, they are not measured.  A list's lse is (double)m + log(sum of
+    # expf(v - m)) with a float64 sum: each term carries expf's error (within 2 ulp, on a term <= 1) and the rounding of
+    # v - m, eps |v - m| / 2 relative to the term, whose softmax-weighted sum is at most eps ln(n) / 2 (sum_i p_i (m -
+    # v_i) = m - lse + H(p) <= ln n); the float64 sum, log and add are below 1e-15.  Two such lse and one rounding at
+    # |L| stay below eps (8 + ln n_cand + |L|).  A gradient entry is expf(x) - [target] expf(x_t), x = f32(v - lseA): the
+    # error of lseA, the rounding at |x|, expf's 2 ulp on a value <= 1, the same for the target term (|x_t| <= |x|,
+    # fewer rows) and the subtraction's rounding stay below eps (8 + ln n_cand + |x|).
+    logits, labels, page_start, start = mixed_batch(nc, 300 + nc)
+    w = torch.linspace(0.5, 2.0, nc)
+    lg, lb = logits.numpy(), labels.numpy()
+    ref = RO.rank_loss(lg, lb, page_start, None, -100, 1.0, "sum")
+    refw = RO.rank_loss(lg, lb, page_start, w.numpy(), -100, 1.0, "sum")
+    lists, acc = fwd(logits, labels, page_start)
+    listsw, accw = fwd(logits, labels, page_start, w)
+    assert torch.equal(bits(lists), bits(listsw))                          # the table does not know the weights
+    loss, dl = bwd(logits, labels, page_start, lists, acc, 1.0)
+    torch.cuda.synchronize()
+    got, got_acc, got_accw, d = lists.cpu().numpy(), acc.cpu().numpy(), accw.cpu().numpy(), dl.cpu().numpy()
+    n = lb.shape[0]
+
+    assert np.array_equal(got[:, :, 2:], ref["lists"][:, :, 2:])           # the integer columns, exactly
+    scored = ref["scored"]
+    assert scored.any() and (~scored).any()
+    assert not got[:, :, :2][~scored].any()                                # unscored: zeros for the lse fields
+    L, L64 = got[:, :, 0] - got[:, :, 1], ref["L"]
+    n_cand = np.maximum(ref["lists"][:, :, 2], 1.0)
+    gate_L = EPS32 * (8 + np.log(n_cand) + np.abs(L64))
+    err_L = np.abs(L - L64)
+    print("NC %d: max |L - L64| / gate %.3f over %d scored lists" % (nc, (err_L / gate_L)[scored].max(), scored.sum()))
+    assert (err_L[scored] <= gate_L[scored]).all(), (err_L / gate_L)[scored].max()
+
+    # acc: the fold of the table, with the sum of the lists' gates; the denominator and the count exactly
+    for a, r, wc in ((got_acc, ref, np.ones(nc)), (got_accw, refw, w.double().numpy())):
+        wl = np.broadcast_to(wc[1:], scored.shape)
+        assert abs(a[0] - r["acc"][0]) <= (wl * gate_L)[scored].sum(), (a[0], r["acc"][0])
+        assert a[1] == r["acc"][1] and a[2] == r["acc"][2] == scored.sum()
+    assert abs(float(loss.item()) - ref["loss"]) <= (gate_L[scored].sum() + EPS32 * abs(ref["loss"]))
+
+    # the gradient for g = 1, entry by entry
+    page_of = np.full(n, -1)
+    for p, (s, e) in enumerate(RO.page_bounds(page_start, n)):
+        page_of[s:e] = p
+    live = (page_of >= 0) & ref["cand"]
+    x64 = np.zeros((n, nc))
+    gate_d = np.full((n, nc), EPS32 * 8)
+    rows = np.nonzero(live)[0]
+    for c in range(1, nc):
+        lseA, cnt = ref["lists"][page_of[rows], c - 1, 0], n_cand[page_of[rows], c - 1]
+        x64[rows, c] = lg[rows, c].astype(np.float64) - lseA
+        gate_d[rows, c] = EPS32 * (8 + np.log(cnt) + np.abs(x64[rows, c]))
+    err_d = np.abs(d.astype(np.float64) - ref["dlogits"])
+    print("NC %d: max |d - d64| / gate %.3f" % (nc, (err_d / gate_d).max()))
+    assert (err_d <= gate_d).all(), (err_d / gate_d).max()
+
+    # exact facts
+    p1 = SIZES.index(1)
+    assert scored[p1, 0] and L[p1, 0] == 0.0 and not d[start[1]].any()     # one candidate, its own target
+    assert got[SIZES.index(65), 0, 3] == 2 and got[SIZES.index(64), nc - 2, 3] == 64
+    assert not scored[SIZES.index(2)].any() and not scored[SIZES.index(0)].any()
+    zero = np.zeros((n, nc), dtype=bool)                                   # entries the term never touches
+    zero[:, 0] = True
+    zero[~live] = True
+    for c in range(1, nc):
+        zero[rows[~scored[page_of[rows], c - 1]], c] = True
+    assert zero[:HEAD].all() and zero[n - TAIL:].all() and (~zero).any()
+    assert not d[zero].any() and (d.view(np.uint32)[zero] == 0).all()
+    assert (d[~zero] != 0).mean() > 0.9
+
+    # accumulate: pre-fill + the result above, one f32 add each; untouched entries keep their bits
+    g = torch.Generator().manual_seed(5)
+    pre = torch.randn(n, nc, generator=g)
+    pre[::3] = -0.0
+    pre_loss = torch.tensor([1.25])
+    into = (pre_loss.to(DEV), pre.to(DEV))
+    loss2, dl2 = bwd(logits, labels, page_start, lists, acc, 1.0, into=into)
+    assert loss2 is into[0] and dl2 is into[1]
+    want = (pre + dl.cpu()).numpy()
+    want.view(np.uint32)[zero] = pre.numpy().view(np.uint32)[zero]
+    assert np.array_equal(dl2.cpu().numpy().view(np.uint32), want.view(np.uint32))
+    assert torch.equal(bits(loss2.cpu()), bits(pre_loss + loss.cpu()))
+
+
+# ----------------------------------------------------------------------- 2. reproducible and independent of the batch
+def test_reproducible_and_independent_of_the_batch_around_a_page():
+    g = torch.Generator().manual_seed(31)
+    sizes, nc = [0, 1, 17, 230, 300, 2500], 4
+    n = sum(sizes)
+    page_start = np.concatenate([[0], np.cumsum(sizes)])
+    logits = torch.randn(n, nc, generator=g) * 4
+    labels = labelled(n, nc, g, 0.95)
+    labels[1::29] = -100
+
+    def run(lg, lb, ps):
+        lists, acc = fwd(lg, lb, ps)
+        _, dl = bwd(lg, lb, ps, lists, acc, 0.5, reduction="sum")
+        return lists.cpu(), acc.cpu(), dl.cpu()
+
+    first, again = run(logits, labels, page_start), run(logits, labels, page_start)
+    for a, b in zip(first, again):
+        assert torch.equal(bits(a), bits(b))
+    assert float(first[1][2]) >= 6
+
+    def part(lo, hi):                                                      # pages lo .. hi-1 as a batch of their own
+        r0, r1 = int(page_start[lo]), int(page_start[hi])
+        if r1 == r0:                                                       # N >= 1: an empty page has nothing to compare
+            return
+        lists, _, dl = run(logits[r0:r1], labels[r0:r1], page_start[lo:hi + 1] - r0)
+        assert torch.equal(bits(lists), bits(first[0][lo:hi])), (lo, hi)
+        assert torch.equal(bits(dl), bits(first[2][r0:r1])), (lo, hi)
+
+    for p in range(len(sizes)):
+        part(p, p + 1)
+    part(0, 3)
+    part(3, len(sizes))
+
+
+# ------------------------------------------------------------------------------------------- 3. mean over two shards
+def test_mean_over_shards_equals_the_whole_batch():
+    g = torch.Generator().manual_seed(77)
+    sizes, nc, cut = [40, 230, 1, 90, 300, 64], 4, 3
+    n = sum(sizes)
+    page_start = np.concatenate([[0], np.cumsum(sizes)])
+    logits = torch.randn(n, nc, generator=g) * 4
+    labels = labelled(n, nc, g)
+    w = torch.tensor([1.0, 0.3, 2.7, 1.9])
+    lists, acc = fwd(logits, labels, page_start, w)
+    loss, whole = bwd(logits, labels, page_start, lists, acc, 0.5, w, reduction="mean")
+    r = int(page_start[cut])
+    shards = [(logits[:r], labels[:r], page_start[:cut + 1]), (logits[r:], labels[r:], page_start[cut:] - r)]
+    tables = [fwd(lg, lb, ps, w) for lg, lb, ps in shards]
+    total = tables[0][1] + tables[1][1]                                    # what the all-reduce leaves on every rank
+    parts = [bwd(lg, lb, ps, t[0], total, 0.5, w, reduction="mean") for (lg, lb, ps), t in zip(shards, tables)]
+    got = torch.cat([p[1] for p in parts])
+    assert float(acc[2]) == float(total[2]) > 0 and bool(whole.abs().sum() > 0)
+    assert torch.allclose(got, whole, rtol=1e-6, atol=0.0), float((got - whole).abs().max())
+    for p in parts:                                                        # every rank reports the global mean
+        assert torch.allclose(p[0], loss, rtol=1e-6, atol=0.0)
+
+
+# ---------------------------------------------------------------------------------------------------- 4. refusals
+def test_bad_arguments_are_refused():
+    lg, lb = torch.zeros(8, 4, device=DEV), torch.zeros(8, dtype=torch.int64, device=DEV)
+    ps = torch.tensor([0, 8], device=DEV)
+    lists, acc = torch.zeros(1, 3, 4, dtype=torch.float64, device=DEV), torch.zeros(3, dtype=torch.float64, device=DEV)
+    loss, dl = torch.zeros(1, device=DEV), torch.zeros(8, 4, device=DEV)
+
+    def call_fwd(logits=lg, labels=lb, page_start=ps, B=1, N=8, NC=4, lists=lists, acc=acc):
+        engine.call(FWD, logits, labels, page_start, B, N, NC, None, -100, 1, lists, acc)
+
+    def call_bwd(logits=lg, labels=lb, page_start=ps, B=1, N=8, NC=4, lists=lists, acc=acc, rank_weight=1.0, loss=loss,
+                 dlogits=dl):
+        engine.call(BWD, logits, labels, page_start, B, N, NC, None, -100, 1, lists, acc, rank_weight, 0, None, loss,
+                    dlogits, 0)
+
+    call_fwd(), call_bwd(), call_bwd(loss=None), call_bwd(dlogits=None)
+    common = (dict(logits=None), dict(labels=None), dict(page_start=None), dict(lists=None), dict(acc=None), dict(NC=1),
+              dict(NC=17), dict(B=0), dict(N=0))
+    for kw in common:
+        with pytest.raises(_lib.CovaHipError, match="10001"):
+            call_fwd(**kw)
+    for kw in common + (dict(rank_weight=-1.0), dict(rank_weight=float("nan")), dict(rank_weight=float("inf")),
+                        dict(loss=None, dlogits=None)):
+        with pytest.raises(_lib.CovaHipError, match="10001"):
+            call_bwd(**kw)
+    torch.cuda.synchronize()
+
+
+# ----------------------------------------------------------------------------------------------------- 5. the trainer
+def paged(batch, counts):
+    """a device batch that carries page_start, as DeviceCollate / DeviceDataset batches do"""
+    b = dev_batch(batch)
+    b["page_start"] = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int64, device=DEV)
+    return b
+
+
+def page_counts(i):
+    return [20 + 3 * i, 11 + 2 * i]                                         # trainer_setup's boxes_per_page
+
+
+def test_trainer_launches():
+    sd, batches = trainer_setup()
+    ref = HotPathTrainer(CFG, sd, DEV)
+    plain = _profiled(lambda: ref.forward_backward(dev_batch(batches[0])))
+    assert plain.get("cova_ce_sum") == 1 and not any(n in plain for n in PAIR + (FWD, BWD)), plain
+    tr = HotPathTrainer(CFG, sd, DEV, page_rank_weight=0.5)
+    assert tr.loss_path == "cova_ce_loss"
+    for b in (paged(batches[0], page_counts(0)), dev_batch(batches[0])):
+        prof = _profiled(lambda: tr.forward_backward(b))
+        assert [prof.pop(n, None) for n in PAIR + (FWD, BWD)] == [1, 1, 1, 1] and "cova_ce_sum" not in prof, prof
+        assert prof == {k: v for k, v in plain.items() if k != "cova_ce_sum"}
+    # weight 0: today's launches and today's bits
+    off = HotPathTrainer(CFG, sd, DEV, page_rank_weight=0.0)
+    ref2 = HotPathTrainer(CFG, sd, DEV)
+    assert off.loss_path == "cova_ce_sum" and off.loss_options == ref2.loss_options
+    b = dev_batch(batches[1])
+    prof = _profiled(lambda: off.forward_backward(b))
+    assert prof == _profiled(lambda: ref2.forward_backward(b)) and prof.get("cova_ce_sum") == 1
+    loss_off, _ = off.forward_backward(b)
+    loss_ref, _ = ref2.forward_backward(b)
+    assert torch.equal(bits(loss_off), bits(loss_ref)) and torch.equal(bits(off.gbucket.flat), bits(ref2.gbucket.flat))
+    assert off.last_rank_lists is None and off.last_rank_acc is None
+
+
+def test_train_step_makes_no_host_synchronisation_and_derives_page_start():
+    sd, batches = trainer_setup()
+    tr = HotPathTrainer(CFG, sd, DEV, page_rank_weight=0.5)
+    with_ps, without = paged(batches[1], page_counts(1)), dev_batch(batches[2])
+    assert "page_start" not in without
+    tr.train_step(dev_batch(batches[0]))
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        for b in (with_ps, without):
+            loss, pred = tr.train_step(b)
+    finally:
+        torch.cuda.set_sync_debug_mode(0)
+    assert loss.is_cuda and pred.shape == without["labels"].shape and bool(torch.isfinite(loss).all())
+    assert tr.last_rank_lists.is_cuda and tr.last_rank_lists.dtype == torch.float64
+    assert tr.last_rank_lists.shape == (2, 3, 4) and tr.last_rank_acc.shape == (3,) and tr.last_rank_acc.is_cuda
+    with pytest.raises(ValueError, match="page_start"):
+        tr.forward_backward({k: v for k, v in without.items() if k != "images"})
+    # the derived page_start gives the batch's own: the same tables, the same gradients
+    a, b = HotPathTrainer(CFG, sd, DEV, page_rank_weight=0.5), HotPathTrainer(CFG, sd, DEV, page_rank_weight=0.5)
+    a.forward_backward(paged(batches[0], page_counts(0)))
+    b.forward_backward(dev_batch(batches[0]))
+    assert torch.equal(bits(a.last_rank_lists), bits(b.last_rank_lists))
+    assert torch.equal(bits(a.last_rank_acc), bits(b.last_rank_acc)) and float(a.last_rank_acc[2]) > 0
+    assert int(a.last_rank_lists[:, 0, 2].sum()) == batches[0]["labels"].numel()
+    assert torch.equal(bits(a.gbucket.flat), bits(b.gbucket.flat))
+
+
+def test_trainer_loss_is_the_pairs_plus_the_rank_term():
+    sd, batches = trainer_setup()
+    a = HotPathTrainer(CFG, sd, DEV, page_rank_weight=0.5)
+    b = HotPathTrainer(CFG, sd, DEV, ignore_index=-100)                    # the pair alone, on the same forward bits
+    batch = dev_batch(batches[0])
+    # the validation loss first (the trainers hold the same state): the pair's plus f32(0.5 R) of the eval-mode logits
+    va, vb = a.loss(batch), b.loss(batch)
+    logits, _ = a.predict(batch)
+    ps = HotPathTrainer._page_start(batch, logits.device)
+    lists, acc = engine.page_rank_loss_fwd(logits, batch["labels"], ps, None, dict(ignore_index=None))
+    term = (0.5 * acc[0]).to(torch.float32)
+    assert float(term) > 0 and torch.equal(bits(va), bits(vb + term)), (va.item(), vb.item(), term.item())
+    assert a.last_rank_lists is None                                       # loss() leaves the step's tables alone
+    loss_a, pred_a = a.forward_backward(batch)
+    loss_b, pred_b = b.forward_backward(batch)
+    term = (0.5 * a.last_rank_acc[0]).to(torch.float32)
+    assert float(term) > 0 and torch.equal(pred_a, pred_b)
+    assert torch.equal(bits(loss_a), bits(loss_b + term)), (loss_a.item(), loss_b.item(), term.item())
+    assert not torch.equal(a.gbucket.flat, b.gbucket.flat)
+
+
+def test_trainer_gradient_is_linear_in_the_weight():
+    sd, batches = trainer_setup()
+    batch = dev_batch(batches[0])
+    grads = []
+    for kw in (dict(ignore_index=-100), dict(page_rank_weight=1.0), dict(page_rank_weight=2.0)):
+        tr = HotPathTrainer(CFG, sd, DEV, **kw)
+        assert tr.loss_path == "cova_ce_loss"
+        tr.forward_backward(batch)
+        grads.append({k: v.detach().clone() for k, v in tr.grads.items()})
+    g0, g1, g2 = grads
+    # g(w) = g0 + w r: the backward is linear in dlogits, so g2 - g1 and g1 - g0 are the same r up to the rounding of three
+    # backward passes.  Per parameter tensor, 1e-3 of max|g1 - g0| (gradients: rtol 1e-3); the scale of
+    # a tensor has the floor the project's gradient checks use, 1 % of the largest tensor's, because some tensors get exactly
+    # nothing from the term in exact arithmetic (a bias in front of a train-mode BatchNorm, terms that cancel in the
+    # attention softmax, the last layer's bias: a list's gradient sums to zero): their g1 - g0 is rounding noise alone
+    # and no implementation can hold a bound relative to it.
+    first = {k: float((g1[k] - g0[k]).abs().max()) for k in g0}
+    floor = 0.01 * max(first.values())
+    failed = []
+    for k in g0:
+        err = float(((g2[k] - g1[k]) - (g1[k] - g0[k])).abs().max())
+        scale = max(first[k], floor)
+        print("%-40s max|g1 - g0| %.3e  max|(g2 - g1) - (g1 - g0)| %.3e  ratio %.3e" % (k, first[k], err, err / scale))
+        if not err <= 1e-3 * scale:
+            failed.append((k, err, scale))
+    assert not failed, failed
+
+
+def test_mined_out_rows_stay_candidates():
+    sd, batches = trainer_setup()
+    a = HotPathTrainer(CFG, sd, DEV, page_rank_weight=0.5)
+    b = HotPathTrainer(CFG, sd, DEV, page_rank_weight=0.5, hard_negative_ratio=0, hard_negative_min=1)
+    batch = dev_batch(batches[0])
+    a.forward_backward(batch), b.forward_backward(batch)
+    assert bool((b.last_mined_labels == engine.MINED_OUT).any())
+    assert torch.equal(bits(a.last_rank_lists), bits(b.last_rank_lists))
+    assert torch.equal(bits(a.last_rank_acc), bits(b.last_rank_acc))
+    assert not torch.equal(a.gbucket.flat, b.gbucket.flat)                 # the cross-entropy did lose the mined rows
+
+
+# ------------------------------------------------------------------------------------------------------ 6. the module
+def test_module_equals_the_four_engine_calls():
+    g = torch.Generator().manual_seed(12)
+    sizes, nc = [11, 230, 64, 1, 90], 4
+    n = sum(sizes)
+    logits, labels = torch.randn(n, nc, generator=g) * 4, labelled(n, nc, g)
+    labels[2::17] = -100
+    lg, lb = logits.to(DEV), labels.to(DEV)
+    ps = torch.as_tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int64, device=DEV)
+    w = torch.tensor([1.0, 3.0, 2.0, 4.0])
+    for kw in (dict(), dict(weight=w, reduction="sum", label_smoothing=0.1)):
+        crit = CrossEntropyLoss(page_rank_weight=0.7, **kw).to(DEV)
+        x = lg.clone().requires_grad_(True)
+        loss = crit(x, lb, ps)
+        loss.backward()
+        opts = dict(label_smoothing=kw.get("label_smoothing", 0.0), focal_gamma=0.0, ignore_index=-100,
+                    reduction=kw.get("reduction", "mean"))
+        wd = None if "weight" not in kw else w.to(DEV)
+        one = torch.ones(1, device=DEV)
+        acc, _ = engine.ce_loss_fwd(lg, lb, wd, opts, want_pred=False)
+        ce_loss, ce_dl = engine.ce_loss_bwd(lg, lb, wd, opts, acc, grad_scale=one)
+        ce_only = ce_dl.clone()
+        lists, racc = engine.page_rank_loss_fwd(lg, lb, ps, wd, opts)
+        want_loss, want_dl = engine.page_rank_loss_bwd(lg, lb, ps, wd, opts, lists, racc, 0.7, grad_scale=one,
+                                                       into=(ce_loss, ce_dl))
+        assert torch.equal(bits(loss.detach().reshape(1)), bits(want_loss))
+        assert torch.equal(bits(x.grad), bits(want_dl))
+        assert float(racc[2]) > 0 and not torch.equal(x.grad, ce_only)
+        with pytest.raises(ValueError, match="page_start"):
+            crit(lg, lb)
+        # weight 0 is today's module, page_start or not
+        today = CrossEntropyLoss(page_rank_weight=0, **kw).to(DEV)
+        loss0, _ = engine.ce_loss_bwd(lg, lb, wd, opts, acc, want_grad=False)
+        assert torch.equal(bits(today(lg, lb).reshape(1)), bits(loss0))
+        assert torch.equal(bits(today(lg, lb, ps).reshape(1)), bits(loss0))
+        y = lg.clone().requires_grad_(True)
+        today(y, lb, ps).backward()
+        assert torch.equal(bits(y.grad), bits(ce_only))
