@@ -1,6 +1,7 @@
 // Parameter-group optimizers and the global gradient norm of HotPathTrainer (trainer.py): torch.optim.Adam (L2 added to the
 // gradient), AdamW and SGD (momentum, dampening, nesterov) over a table of flat-buffer segments with per-group
 // hyper-parameters, and torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) as two deterministic launches.
+// Also the averaged copy of the weights (EMA / equal-weight running mean, HotPathTrainer(average=)) over the same table.
 //
 // Segment table: int64 rows {lo, hi, group, start}.  Row r covers flat elements [lo, hi) of every buffer; `start` is the
 // sum of the lengths of the rows before it, so the rows tile one concatenated index space [0, total).  A block owns a
@@ -236,6 +237,54 @@ __global__ __launch_bounds__(OPT_THREADS) void grad_norm_finish_kernel(const dou
     }
 }
 
+// avg += w * (p - avg): the difference, the product and the sum each round to f32 on their own (no contraction), so the
+// update is a numpy float32 statement bit for bit and p == avg is a fixed point
+__device__ __forceinline__ float average(float av, float pv, float w)
+{
+#pragma clang fp contract(off)
+    const float d = pv - av;
+    const float t = w * d;
+    return av + t;
+}
+
+// flat elements [a, b) of one row piece
+__device__ __forceinline__ void average_range(float *__restrict__ avg, const float *__restrict__ p, long long a,
+                                              long long b, float w, bool vec4)
+{
+    if (vec4 && ((a | b) & 3) == 0) {
+        for (long long i = a + 4 * (long long)threadIdx.x; i < b; i += 4 * OPT_THREADS) {
+            float4 av = *reinterpret_cast<const float4 *>(avg + i);
+            const float4 pv = *reinterpret_cast<const float4 *>(p + i);
+            av.x = average(av.x, pv.x, w);
+            av.y = average(av.y, pv.y, w);
+            av.z = average(av.z, pv.z, w);
+            av.w = average(av.w, pv.w, w);
+            *reinterpret_cast<float4 *>(avg + i) = av;
+        }
+        return;
+    }
+    for (long long i = a + threadIdx.x; i < b; i += OPT_THREADS) avg[i] = average(avg[i], p[i], w);
+}
+
+// the slice-per-block walk of optim_step_kernel over the same table (group ignored)
+__global__ __launch_bounds__(OPT_THREADS) void weight_average_kernel(float *__restrict__ avg, const float *__restrict__ p,
+                                                                    long long n, const long long *__restrict__ seg,
+                                                                    int n_seg, long long total, float w, int vec4)
+{
+    __shared__ FirstRow s_first;
+    const long long v0 = (long long)blockIdx.x * OPT_SLICE;
+    const long long v1 = v0 + OPT_SLICE < total ? v0 + OPT_SLICE : total;
+    const int first = find_first_row(seg, n_seg, v0, &s_first);
+    for (long long pos = v0, r = first; pos < v1 && r < n_seg; ++r) {
+        const long long *row = row_at(seg, (int)r, first, s_first);
+        const long long lo = row[0], hi = row[1], st = row[3];
+        const long long end = st + (hi - lo) < v1 ? st + (hi - lo) : v1;
+        if (lo >= 0 && hi <= n && pos >= st)                 // a malformed row is skipped, never written out of bounds
+            average_range(avg, p, lo + (pos - st), lo + (end - st), w, vec4 != 0);
+        pos = end;
+    }
+}
+
 inline bool aligned16(const void *ptr) { return ((uintptr_t)ptr & 15) == 0; }
 
 }  // namespace
@@ -303,6 +352,20 @@ COVA_API int cova_grad_norm(const float *g, long long n, const long long *segs, 
     COVA_LAUNCH_CHECK();
     hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(OPT_THREADS), 0, s, workspace, n_part, (float)max_norm,
                        out);
+    COVA_LAUNCH_CHECK();
+    return COVA_OK;
+}
+
+COVA_API int cova_weight_average(float *avg, const float *p, long long n, const long long *segs, int n_seg,
+                                 long long total, double one_minus_decay, void *stream)
+{
+    COVA_REQUIRE(n_seg >= 0 && total >= 0);
+    if (n_seg == 0 || total == 0) return COVA_OK;
+    COVA_REQUIRE(avg && p && segs && n > 0 && total <= n);
+    const float w = (float)one_minus_decay;                  // converted once: the kernel multiplies by this f32
+    const dim3 grid((unsigned)cdivll(total, OPT_SLICE)), block(OPT_THREADS);
+    hipLaunchKernelGGL(weight_average_kernel, grid, block, 0, (hipStream_t)stream, avg, p, n, segs, n_seg, total, w,
+                       (int)(aligned16(avg) && aligned16(p)));
     COVA_LAUNCH_CHECK();
     return COVA_OK;
 }

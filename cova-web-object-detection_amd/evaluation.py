@@ -14,6 +14,7 @@ Table values: ``>= 0`` the rank of the labelled box (0 = best), ``-1`` the page 
 was not evaluated.
 """
 import collections
+import contextlib
 import time
 
 import numpy as np
@@ -274,7 +275,7 @@ def _log(log_file, lines):
 
 def fit(trainer, train_set, val_set, n_epochs, batch_size, sampling_fraction=0.9, seed=0, eval_interval=3, patience=7,
         lr_schedule=None, checkpoint=None, log_file=None, k=1, rank=0, world_size=1, group=None, class_names=None,
-        train_features=None, val_features=None, augment=None):
+        train_features=None, val_features=None, augment=None, use_average=False):
     """train.train_model: ``n_epochs`` epochs of ``trainer.train_step`` over ``train_set`` (shuffled, background boxes
     sampled), ``evaluate_split`` on ``val_set`` at epoch 1, every ``eval_interval`` epochs and at the last epoch,
     save-best / patience / reload-best -> FitResult.
@@ -289,7 +290,14 @@ def fit(trainer, train_set, val_set, n_epochs, batch_size, sampling_fraction=0.9
     conv stack is frozen with its BatchNorms in eval mode): checked once on entry; the steps and the evaluations then
     take the visual rows from the tables.
     ``augment`` (a pipeline.PageAugment): the TRAINING batches of every epoch are augmented (keyed by ``epoch``, so no two
-    epochs show a page alike); ``evaluate_split`` never is.  Not with ``train_features`` (ValueError)."""
+    epochs show a page alike); ``evaluate_split`` never is.  Not with ``train_features`` (ValueError).
+    ``use_average`` (a trainer built with ``average=``, else ValueError): every validation runs inside
+    ``trainer.averaged_weights()`` and the best state kept or saved is ``averaged_state_dict()``, so save-best and
+    patience follow the averaged model; an evaluation before the average has started (``n_averaged == 0``) uses the
+    live weights and state.  The history's ``averaged`` says which it was.  The final reload goes through
+    ``load_state_dict``, after which live parameters and average both hold the best state."""
+    if use_average and trainer.average is None:
+        raise ValueError("use_average needs a trainer built with average=\"ema\" or \"swa\"")
     if augment is not None and train_features is not None:
         raise ValueError("augment cannot be combined with train_features: the cached rows were pooled from unaugmented "
                          "pixels")
@@ -317,7 +325,8 @@ def fit(trainer, train_set, val_set, n_epochs, batch_size, sampling_fraction=0.9
         n, den = m["kept"], m["loss_denominator"]
         rec = dict(epoch=epoch, loss=m["loss_numerator"] / den if den > 0 else 0.0,
                    accuracy=100.0 * float(np.trace(m["confusion"])) / n if n else 0.0, boxes=n,
-                   lr=[g["lr"] for g in trainer.param_groups], eval_acc=None, class_acc=None, is_best=False)
+                   lr=[g["lr"] for g in trainer.param_groups], eval_acc=None, class_acc=None, is_best=False,
+                   averaged=False)
         rec["seconds"] = time.time() - start
         if rank == 0:
             _log(log_file, ["Epoch: %2d  Loss: %.4f  Accuracy: %.2f%%  (%.2fs)"
@@ -325,15 +334,17 @@ def fit(trainer, train_set, val_set, n_epochs, batch_size, sampling_fraction=0.9
         history.append(rec)
         epochs_run = epoch
         if ctl.should_evaluate(epoch):
-            report = evaluate_split(trainer, val_set, rank=rank, world_size=world_size, group=group,
-                                    features=val_features)
+            rec["averaged"] = bool(use_average) and trainer.average.n_averaged > 0
+            with trainer.averaged_weights() if rec["averaged"] else contextlib.nullcontext():
+                report = evaluate_split(trainer, val_set, rank=rank, world_size=world_size, group=group,
+                                        features=val_features)
             rec["class_acc"] = report.class_acc(k)
             rec["eval_acc"] = float(rec["class_acc"][1:].mean())
             if rank == 0:
                 _log(log_file, report.log_lines("VAL", k, names))
             rec["is_best"], stop = ctl.update(epoch, rec["eval_acc"])
             if rec["is_best"] and rank == 0:
-                best_state = trainer.state_dict()
+                best_state = trainer.averaged_state_dict() if rec["averaged"] else trainer.state_dict()
                 if checkpoint is not None:
                     torch.save(best_state, checkpoint)
                     best_state = None

@@ -12,8 +12,9 @@ switches on the exact large-batch mode: every BatchNorm statistic row is summed 
 (engine.StatSync, 2*C floats per message), after which a data-parallel step equals the
 single-device step on the concatenated batch.
 """
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
+import contextlib
 import os
 
 import torch
@@ -91,6 +92,48 @@ def group_runs(offsets, n, frozen, owner):
         else:
             runs.append([lo, hi, gid])
     return [tuple(r) for r in runs]
+
+
+AVERAGES = ("ema", "swa")
+# trainer.average: the averaging options as given and the number of parameter samples in the average so far
+AverageInfo = namedtuple("AverageInfo", "kind decay warmup start every buffers n_averaged")
+
+
+def average_weight(kind, decay, warmup, n_averaged):
+    """``one_minus_decay`` (a double) of the cova_weight_average launch that adds a sample to an average of ``n_averaged``:
+    "swa" 1 / (n_averaged + 1), the equal-weight running mean of torch's AveragedModel; "ema" 1 - d with d = ``decay``,
+    or with ``warmup`` min(decay, (1 + n_averaged) / (warmup + n_averaged)): early samples weigh more while the average
+    is young."""
+    n = int(n_averaged)
+    if kind == "swa":
+        return 1.0 / (n + 1)
+    d = float(decay)
+    if warmup is not None:
+        d = min(d, (1.0 + n) / (float(warmup) + n))
+    return 1.0 - d
+
+
+def check_average_options(average, decay, warmup, start, every, buffers):
+    """The checked averaging options of HotPathTrainer -> AverageInfo with n_averaged 0, or None when averaging is off."""
+    if average is None:
+        changed = [n for n, v, d in (("average_decay", decay, 0.999), ("average_warmup", warmup, None),
+                                     ("average_start", start, 0), ("average_every", every, 1),
+                                     ("average_buffers", buffers, True)) if v != d]
+        if changed:
+            raise ValueError("%s given without average= (\"ema\" or \"swa\")" % ", ".join(changed))
+        return None
+    if average not in AVERAGES:
+        raise ValueError("average must be None or one of %s, got %r" % (AVERAGES, average))
+    if not 0.0 <= float(decay) < 1.0:
+        raise ValueError("average_decay must be in [0, 1), got %r" % (decay,))
+    if warmup is not None and (int(warmup) != warmup or warmup < 1):
+        raise ValueError("average_warmup must be None or an integer >= 1, got %r" % (warmup,))
+    if int(start) != start or start < 0:
+        raise ValueError("average_start must be an integer >= 0, got %r" % (start,))
+    if int(every) != every or every < 1:
+        raise ValueError("average_every must be an integer >= 1, got %r" % (every,))
+    return AverageInfo(average, float(decay), None if warmup is None else int(warmup), int(start), int(every),
+                       bool(buffers), 0)
 
 
 def shard_pages(n_pages, rank, world_size):
@@ -199,14 +242,25 @@ class HotPathTrainer:
     column: the quantity the page top-k evaluation ranks.  The criterion then runs through cova_ce_loss_fwd /
     cova_ce_loss_bwd followed by cova_page_rank_loss_fwd / cova_page_rank_loss_bwd, which add the term and its gradient
     to the pair's outputs; ``last_rank_lists`` / ``last_rank_acc`` hold the step's tables on the device.  loss()
-    includes the term; ``metrics`` and evaluate_split(with_loss=) count the cross-entropy alone."""
+    includes the term; ``metrics`` and evaluate_split(with_loss=) count the cross-entropy alone.
+
+    Weight averaging ("Weight averaging"): ``average`` "ema" | "swa" (None: off) keeps an averaged copy
+    of the parameters in a second flat bucket, updated at the end of optimizer_step() by one cova_weight_average launch
+    over the trainable runs (a second one over the BatchNorm running statistics with ``average_buffers``), from step
+    ``average_start`` on, every ``average_every`` steps, with the weight average_weight() gives (``average_decay``,
+    ``average_warmup``).  ``trainer.average`` is the record, averaged_state_dict() the averaged model, and inside
+    ``with trainer.averaged_weights():`` predict / evaluate / loss / evaluate_split run on it without a copy.  The
+    schedule is host integers: no host read, and with ``average=None`` no tensor and no launch is added."""
 
     def __init__(self, cfg, state_dict, device, lr=5e-4, weight_decay=1e-3, betas=(0.9, 0.999),
                  eps=1e-8, world_size=1, process_group=None, dropout_seed=123, sync_bn=False, frozen=(), bn_eval=(),
                  optimizer="adam", momentum=0.0, dampening=0.0, nesterov=False, param_groups=None,
                  max_grad_norm=None, norm_type=2.0, class_weight=None, label_smoothing=0.0, focal_gamma=0.0,
                  ignore_index=None, loss_reduction="sum", track_metrics=False, hard_negative_ratio=None,
-                 hard_negative_min=0, page_rank_weight=0.0):
+                 hard_negative_min=0, page_rank_weight=0.0, average=None, average_decay=0.999, average_warmup=None,
+                 average_start=0, average_every=1, average_buffers=True):
+        self._avg = check_average_options(average, average_decay, average_warmup, average_start, average_every,
+                                          average_buffers)
         if optimizer not in OPTIMIZERS:
             raise ValueError("optimizer must be one of %s, got %r" % (OPTIMIZERS, optimizer))
         if float(norm_type) != 2.0:
@@ -225,10 +279,16 @@ class HotPathTrainer:
         self.exp_avg = torch.zeros_like(self.pbucket.flat)
         self.exp_avg_sq = torch.zeros_like(self.pbucket.flat)
         self.buffers = {}
+        # with averaging the running statistics live in one flat buffer, the batch counters in another (same keys, shapes
+        # and values): the average of the statistics is then one launch with a one-row table, the counters one copy
+        stat_views = self._flat_buffers(spec) if self._avg is not None else {}
         for k, _ in spec:
             v = state_dict[k]
             if is_param_key(k):
                 self.params[k].copy_(v)
+            elif k in stat_views:
+                self.buffers[k] = stat_views[k]
+                self.buffers[k].copy_(v)
             else:
                 self.buffers[k] = v.clone().to(self.device)
         self.hp = dict(lr=lr, weight_decay=weight_decay, betas=betas, eps=eps)
@@ -240,10 +300,126 @@ class HotPathTrainer:
         self._setup_criterion(class_weight, label_smoothing, focal_gamma, ignore_index, loss_reduction, track_metrics)
         self._setup_mining(hard_negative_ratio, hard_negative_min)
         self._setup_rank(page_rank_weight)
+        self._setup_average()
         self._ar_events = []              # (start, end) HIP events around the collective waits of optimizer_step
         self.measure_allreduce = True     # record them (up to 4096 steps; exposed_allreduce_ms() drains the list)
         if world_size > 1:
             self.broadcast_state(src=0)
+
+    def _flat_buffers(self, spec):
+        """Live BatchNorm buffers of an averaging trainer -> {key: view}: ``bbucket`` (float32, running_mean /
+        running_var in state_dict order) and ``tracked`` (int64, one num_batches_tracked per BatchNorm)."""
+        shapes = OrderedDict((k, s) for k, s in spec if k.endswith(("running_mean", "running_var")))
+        counters = [k for k, _ in spec if k.endswith("num_batches_tracked")]
+        self.bbucket = FlatBucket(shapes, self.device)
+        self.tracked = torch.zeros(len(counters), dtype=torch.int64, device=self.device)
+        views = dict(self.bbucket.views)
+        views.update((k, self.tracked[i]) for i, k in enumerate(counters))
+        return views
+
+    def _setup_average(self):
+        """The second flat bucket (and with ``average_buffers`` the second pair of buffer tensors), the device tables of
+        the averaging launches and the start of the schedule.  Nothing is allocated when averaging is off."""
+        self.n_averaged, self._avg_active = 0, False
+        if self._avg is None:
+            return
+        self.abucket = FlatBucket(OrderedDict((k, sh) for k, (_, _, sh) in self.pbucket.offsets.items()), self.device)
+        self._avg_buffers = self.buffers                    # average_buffers=False: the averaged model uses the live ones
+        self.abbucket = self.atracked = None
+        if self._avg.buffers:
+            self.abbucket = FlatBucket(OrderedDict((k, sh) for k, (_, _, sh) in self.bbucket.offsets.items()), self.device)
+            self.atracked = torch.zeros_like(self.tracked)
+            counters = [k for k in self.buffers if k.endswith("num_batches_tracked")]
+            views = dict(self.abbucket.views)
+            views.update((k, self.atracked[i]) for i, k in enumerate(counters))
+            self._avg_buffers = OrderedDict((k, views[k]) for k in self.buffers)
+        # trainable runs whatever their group: {lo, hi, 0, start} rows as cova_optim_step's; frozen tensors are left out
+        rows, start = [], 0
+        for lo, hi in self._adam_runs:
+            rows.append((lo, hi, 0, start))
+            start += hi - lo
+        self._avg_rows, self._avg_total = rows, start
+        self._avg_seg = torch.tensor(rows, dtype=torch.int64).view(-1, 4).to(self.device)
+        nb = self.bbucket.flat.numel()
+        self._avg_bseg = torch.tensor([(0, nb, 0, 0)], dtype=torch.int64).to(self.device) if nb else None
+        if self._avg.start == 0:
+            self.reset_average()
+
+    @property
+    def average(self):
+        """None when averaging is off; else the read-only record (kind, decay, warmup, start, every, buffers,
+        n_averaged)."""
+        return None if self._avg is None else self._avg._replace(n_averaged=self.n_averaged)
+
+    def _need_average(self, what):
+        if self._avg is None:
+            raise RuntimeError("%s needs a trainer built with average=\"ema\" or \"swa\"" % what)
+
+    def _not_averaged(self, what):
+        if self._avg_active:
+            raise RuntimeError("%s inside averaged_weights(): the trainer's views are the averaged model's" % what)
+
+    def reset_average(self):
+        """Restart the average from the current parameters and buffers (device copies): ``n_averaged`` 1 when the step
+        count has reached ``average_start``, else 0 (the average then starts at that step)."""
+        self._need_average("reset_average")
+        self._not_averaged("reset_average")
+        self.abucket.flat.copy_(self.pbucket.flat)
+        if self._avg.buffers:
+            self.abbucket.flat.copy_(self.bbucket.flat)
+            self.atracked.copy_(self.tracked)
+        self.n_averaged = 1 if self.step_count >= self._avg.start else 0
+
+    def _average_step(self):
+        """End of optimizer_step(): host integers decide, the device work is one launch per averaged flat buffer."""
+        a, s = self._avg, self.step_count
+        if s < a.start:
+            return
+        if self.n_averaged == 0:                            # step ``average_start``, or the first step after a resume past it
+            self.reset_average()
+            return
+        if (s - a.start) % a.every:
+            return
+        w = average_weight(a.kind, a.decay, a.warmup, self.n_averaged)
+        engine.call("cova_weight_average", self.abucket.flat, self.pbucket.flat, self.pbucket.flat.numel(), self._avg_seg,
+                    len(self._avg_rows), self._avg_total, w)
+        if a.buffers:
+            if self._avg_bseg is not None:
+                nb = self.bbucket.flat.numel()
+                engine.call("cova_weight_average", self.abbucket.flat, self.bbucket.flat, nb, self._avg_bseg, 1, nb, w)
+            self.atracked.copy_(self.tracked)               # copied, not averaged
+        self.n_averaged += 1
+
+    def averaged_state_dict(self):
+        """The averaged model in the keys and layout of state_dict() (clones); with ``average_buffers=False`` its buffers
+        are the live ones."""
+        self._need_average("averaged_state_dict")
+        if self.n_averaged == 0:
+            raise RuntimeError("the average has not started (average_start=%d, step %d)" % (self._avg.start, self.step_count))
+        sd = OrderedDict((k, v.detach().clone()) for k, v in self.abucket.views.items())
+        sd.update((k, v.detach().clone()) for k, v in self._avg_buffers.items())
+        return sd
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """Inside the block ``trainer.params`` (and with ``average_buffers`` ``trainer.buffers``) are the averaged
+        views, so predict / evaluate / loss / evaluate_split / FeatureCache.check run on the averaged model with no copy;
+        the live views are back on exit, also after an exception.  train_step, forward_backward, optimizer_step and
+        load_state_dict raise RuntimeError inside it, as does entering it before the average has started."""
+        self._need_average("averaged_weights")
+        self._not_averaged("averaged_weights")
+        if self.n_averaged == 0:
+            raise RuntimeError("the average has not started (average_start=%d, step %d)" % (self._avg.start, self.step_count))
+        live = self.params, self.buffers
+        self.params, self.buffers, self._avg_active = self.abucket.views, self._avg_buffers, True
+        try:
+            yield self
+        finally:
+            (self.params, self.buffers), self._avg_active = live, False
+
+    def _average_tensors(self):
+        """The tensors of the average that travel with broadcast_state / a broadcast optimizer state."""
+        return [self.abucket.flat] + ([self.abbucket.flat, self.atracked] if self._avg.buffers else [])
 
     def _setup_finetune(self, frozen, bn_eval):
         for what, entries, names in (("frozen", frozen, list(self.params)),
@@ -457,15 +633,21 @@ class HotPathTrainer:
         """Rank `src`'s parameters, BatchNorm buffers, Adam moments and step count to every rank: replicas start (and
         resume) from ONE state even when the ranks were built from rank-local checkpoints."""
         import torch.distributed as dist
+        self._not_averaged("broadcast_state")
         extra = [self.momentum_buffer] if self.momentum_buffer is not None else []
+        if self._avg is not None:
+            extra = extra + [t for t in self._average_tensors() if t.numel()]
         for t in [self.pbucket.flat, self.exp_avg, self.exp_avg_sq] + extra + [self.buffers[k] for k in sorted(self.buffers)]:
             dist.broadcast(t, src=src, group=self.group)
         flags = [int(b) for b in self._buf_exists] if self.momentum_buffer is not None else []
-        step = torch.tensor([self.step_count] + flags, dtype=torch.int64, device=self.device)
+        counter = [self.n_averaged] if self._avg is not None else []
+        step = torch.tensor([self.step_count] + flags + counter, dtype=torch.int64, device=self.device)
         dist.broadcast(step, src=src, group=self.group)
         got = step.tolist()
         self.step_count = int(got[0])
-        self._buf_exists = [bool(b) for b in got[1:]] if flags else self._buf_exists
+        self._buf_exists = [bool(b) for b in got[1:1 + len(flags)]] if flags else self._buf_exists
+        if counter:
+            self.n_averaged = int(got[-1])
 
     def exposed_allreduce_ms(self):
         """Mean time per step the stream spent in optimizer_step's gradient collectives (HIP events on the compute
@@ -500,7 +682,11 @@ class HotPathTrainer:
         Local by default: a rank-0-only reload ("reload best, evaluate on rank 0") involves no collective.  With
         `broadcast=True` the call IS a collective that EVERY rank must make: the keys are validated on all ranks first
         (one all-reduce of an ok flag, so a KeyError on one rank raises on all of them), then rank 0's parameters and
-        buffers -- what was loaded, not the Adam moments or the step count -- replace every rank's."""
+        buffers -- what was loaded, not the Adam moments or the step count -- replace every rank's.
+
+        With ``average=`` the average restarts from what was loaded, as reset_average() does; to resume an average,
+        load the state dict first and the optimizer state (which carries the average) after it."""
+        self._not_averaged("load_state_dict")
         missing = [k for k in list(self.params) + list(self.buffers) if k not in state_dict]
         # sizes are part of the validation every rank agrees on BEFORE any copy / broadcast: a tensor of the wrong size on
         # one rank raising inside copy_ would leave the other ranks blocked in dist.broadcast
@@ -521,6 +707,8 @@ class HotPathTrainer:
             import torch.distributed as dist
             for t in [self.pbucket.flat] + [self.buffers[k] for k in sorted(self.buffers)]:
                 dist.broadcast(t, src=0, group=self.group)
+        if self._avg is not None:
+            self.reset_average()
 
     def optimizer_state_dict(self):
         """Adam moments + step count (the reference keeps no optimizer state in its checkpoints, train.py:84;
@@ -532,6 +720,10 @@ class HotPathTrainer:
                       groups=[dict(params=list(g["params"]), **{k: g[k] for k in _GROUP_HP}) for g in self._groups],
                       momentum_buffer=None if self.momentum_buffer is None else self.momentum_buffer.detach().clone(),
                       momentum_buffer_exists=list(self._buf_exists))
+        if self._avg is not None:
+            st["average"] = dict(self.average._asdict(), flat=self.abucket.flat.detach().clone(),
+                                 buffers_flat=self.abbucket.flat.detach().clone() if self._avg.buffers else None,
+                                 num_batches_tracked=self.atracked.detach().clone() if self._avg.buffers else None)
         return st
 
     def _check_optimizer_state(self, state):
@@ -547,12 +739,29 @@ class HotPathTrainer:
             return "momentum buffer of the wrong size (expected %d elements)" % self.pbucket.flat.numel()
         if len(state.get("momentum_buffer_exists", self._buf_exists)) != len(self._groups):
             return "momentum_buffer_exists does not have one flag per group"
+        avg = state.get("average")
+        if avg is not None and self._avg is not None:       # (a trainer without averaging ignores the entry)
+            if avg.get("kind") != self._avg.kind:
+                return "average of kind %r, this trainer keeps %r" % (avg.get("kind"), self._avg.kind)
+            want = [("flat", self.abucket.flat)]
+            if self._avg.buffers:
+                want += [("buffers_flat", self.abbucket.flat), ("num_batches_tracked", self.atracked)]
+            for k, t in want:
+                if not (torch.is_tensor(avg.get(k)) and avg[k].numel() == t.numel()):
+                    return "average: %r of the wrong size (expected %d elements)" % (k, t.numel())
+            if int(avg.get("n_averaged", -1)) < 0:
+                return "average without n_averaged"
         return None
 
     def load_optimizer_state_dict(self, state, broadcast=False):
         """Moments (Adam) or momentum buffer (SGD), step count and hyper-parameters.  Local by default; `broadcast=True`
         makes it a collective every rank must call (validated on all ranks first) after which every rank holds rank 0's
-        moments, step count and hyper-parameters.  A state of another algorithm raises (on every rank when broadcasting)."""
+        moments, step count and hyper-parameters.  A state of another algorithm raises (on every rank when broadcasting).
+
+        With ``average=``: an "average" entry of this trainer's kind and size restores the average and ``n_averaged``
+        (another kind or size raises ValueError like another algorithm); without the entry the average stays as
+        load_state_dict() left it.  The averaging options stay the constructor's."""
+        self._not_averaged("load_optimizer_state_dict")
         ok = all(k in state for k in ("step", "exp_avg", "exp_avg_sq"))
         sized = ok and all(torch.is_tensor(state[k]) and state[k].numel() == self.exp_avg.numel() for k in ("exp_avg", "exp_avg_sq"))
         problem = self._check_optimizer_state(state)
@@ -577,10 +786,24 @@ class HotPathTrainer:
             else:
                 self.momentum_buffer.zero_()
             self._buf_exists = [bool(b) for b in state.get("momentum_buffer_exists", [False] * len(self._groups))]
+        avg = state.get("average") if self._avg is not None else None
+        if avg is not None:
+            self.abucket.flat.copy_(avg["flat"].to(self.device).view_as(self.abucket.flat))
+            if self._avg.buffers:
+                self.abbucket.flat.copy_(avg["buffers_flat"].to(self.device).view_as(self.abbucket.flat))
+                self.atracked.copy_(avg["num_batches_tracked"].to(self.device).view_as(self.atracked))
+            self.n_averaged = int(avg["n_averaged"])
         if broadcast and self.world_size > 1:
             import torch.distributed as dist
             for t in (self.exp_avg, self.exp_avg_sq):
                 dist.broadcast(t, src=0, group=self.group)
+            if self._avg is not None:
+                for t in self._average_tensors():
+                    if t.numel():
+                        dist.broadcast(t, src=0, group=self.group)
+                counter = torch.tensor([self.n_averaged], dtype=torch.int64, device=self.device)
+                dist.broadcast(counter, src=0, group=self.group)
+                self.n_averaged = int(counter.item())
             b1, b2 = self.hp["betas"]
             meta = torch.tensor([float(self.step_count), self.hp["lr"], self.hp["weight_decay"], b1, b2, self.hp["eps"]],
                                 dtype=torch.float64, device=self.device)
@@ -610,6 +833,7 @@ class HotPathTrainer:
         with criterion options the local sum ("sum") / the mean over the global batch ("mean").  A batch with
         ``visual_feats`` (DeviceDataset.batches(features=)) skips the conv stack and the RoI op; it raises ValueError
         unless the conv stack is frozen with its BatchNorms in eval mode."""
+        self._not_averaged("forward_backward")
         opts, mining, rank_weight = self._criterion(), self._mining(), self._rank()
         if mining is not None:
             self._check_paged(batch, "hard-negative mining")
@@ -684,6 +908,12 @@ class HotPathTrainer:
                                                         async_op=True)
 
     def optimizer_step(self):
+        self._not_averaged("optimizer_step")
+        self._update_parameters()
+        if self._avg is not None:
+            self._average_step()
+
+    def _update_parameters(self):
         if self.world_size > 1:
             timing = self.measure_allreduce and len(self._ar_events) < 4096
             if timing:                      # events on THIS trainer's device / stream (not the process' current device)
@@ -750,6 +980,7 @@ class HotPathTrainer:
     def train_step(self, batch, masks=None):
         """optimizer.zero_grad(); forward; loss; backward; optimizer.step()  (train.py:45-60).
         Gradients are fully overwritten each step, so zero_grad is implicit."""
+        self._not_averaged("train_step")
         loss, pred = self.forward_backward(batch, masks)
         self.optimizer_step()
         return loss, pred

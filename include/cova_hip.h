@@ -505,6 +505,19 @@ int cova_grad_norm_workspace_doubles(long long total);
  * it; a non-finite norm propagates (NaN -> NaN coefficient, inf -> 0), error_if_nonfinite=False. */
 int cova_grad_norm(const float *g, long long n, const long long *segs, int n_seg, long long total, double max_norm,
                    double *workspace, float *out, void *stream);
+/* ------------------------------------------------------------------ weight averaging (optim.hip)
+ * replaces: torch.optim.swa_utils.AveragedModel.update_parameters (equal-weight running mean, SWA) and timm's
+ * ModelEmaV2.update (exponential moving average) for HotPathTrainer(average=).
+ * Per element of the table's rows, with w = (float)one_minus_decay converted once on the host:
+ *   avg[i] = avg[i] + w * (p[i] - avg[i])
+ * the difference, the product and the sum each rounded to f32 on their own (no fused multiply-add): a numpy float32
+ * statement bit for bit, with p[i] == avg[i] a fixed point.  EMA: one_minus_decay = 1 - decay; SWA: 1 / (n_averaged + 1).
+ * segs: the table of cova_optim_step ({lo, hi, group, start}, group ignored) under the same rules: rows must not
+ * overlap; a row outside 0 <= lo <= hi <= n is skipped and never written; elements outside the rows (gaps, alignment
+ * padding, frozen tensors) are not touched.  n_seg == 0 or total == 0: no launch, returns 0.  One launch, no atomics, no
+ * workspace, no host read. */
+int cova_weight_average(float *avg, const float *p, long long n, const long long *segs, int n_seg, long long total,
+                        double one_minus_decay, void *stream);
 /* ------------------------------------------------------------------ configurable criterion (loss.hip)
  * replaces: F.cross_entropy(logits, labels, weight=, ignore_index=, label_smoothing=, reduction="sum" | "mean"), the focal
  * loss, and the per-step .item() reads of loss and accuracy (train.py:54,57), for HotPathTrainer(class_weight=,
