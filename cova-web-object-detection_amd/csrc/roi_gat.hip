@@ -520,8 +520,10 @@ __global__ __launch_bounds__(256) void roialign_bwd_rows_kernel(
             bool hit = false;
             if (n <= n_hi) {
                 const AlignGeo g = align_geo(rois + 5 * n, spatial_scale, PH, PW, sampling_ratio, aligned);
-                // rows / columns any sample of the box can touch (conservative: +-1 pixel around the roi)
-                const float ylo = g.sh, yhi = g.sh + (float)PH * g.bh, xlo = g.sw, xhi = g.sw + (float)PW * g.bw;
+                // rows / columns any sample of the box can touch (conservative: +-1 pixel around the roi); with `aligned` the
+                // extent is not clamped to >= 1, so an inverted box has its far corner below the near one
+                const float ya = g.sh, yb = g.sh + (float)PH * g.bh, xa = g.sw, xb = g.sw + (float)PW * g.bw;
+                const float ylo = fminf(ya, yb), yhi = fmaxf(ya, yb), xlo = fminf(xa, xb), xhi = fmaxf(xa, xb);
                 hit = g.b == b && (float)y >= ylo - 2.f && (float)y <= yhi + 2.f && (float)x1 >= xlo - 2.f &&
                       (float)x0 <= xhi + 2.f;
             }

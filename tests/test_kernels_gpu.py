@@ -1085,8 +1085,10 @@ def test_roipool_backward_rows_are_deterministic_and_cover_the_map():
 
 @pytest.mark.parametrize("ph,pw", [(1, 1), (2, 5), (7, 7)])
 def test_roipool_other_output_sizes(ph, pw):
-    """`-r` (roi_output_size, utils.py:20) other than the default 3: forward bit-exact vs the C oracle, backward
-    (generic bin loop of the row-owner kernel) vs its sequential scatter, masked variant consistent."""
+    """`-r` (roi_output_size, utils.py:20) other than the default 3: forward bit-exact vs the C oracle, cova_roipool_bwd
+    (generic bin loop of the row-owner kernel) vs its sequential scatter, then the whole model's eval logits vs the
+    oracle.  The masked entry points (cova_roipool_bwd_bn, _bwd_bn_tail) at these bin shapes are held to a float64
+    scatter in tests/test_roi_paths_gpu.py."""
     rs = np.random.RandomState(ph * 10 + pw)
     B, C, H, W = 2, 64, 30, 45
     feat = torch.from_numpy(rs.standard_normal((B, C, H, W)).astype(np.float32))
