@@ -1311,10 +1311,23 @@ def edge_geometry(bboxes, ctx, page_size):
     return phi
 
 
-def gat_fwd(h, ldh, N, F, ctx, params, hprime, ldo, prefix="gat.", phi=None):
+def check_attention_weight(prefix, aw, D, attention):
+    """The mode the caller asks for against the one the head's ``attention_layer.weight`` was built for."""
+    from .weights import attention_of, check_attention
+    check_attention(attention)
+    have = attention_of(aw, D, prefix)
+    if have != attention:
+        raise ValueError("attention=%r, but %sattention_layer.weight has shape %s: it belongs to attention=%r "
+                         "(a 'gat' head scores with [1, %d], a 'gatv2' head with [1, %d])"
+                         % (attention, prefix, tuple(aw.shape), have, 2 * D, D))
+
+
+def gat_fwd(h, ldh, N, F, ctx, params, hprime, ldo, prefix="gat.", phi=None, attention="gat"):
     """models.py:171-212.  h rows at h + n*ldh (F values); hprime rows at hprime + n*ldo (D).
     ``phi`` (edge_geometry): the score takes the edge term ``edge_layer.weight . phi`` (cova_gat_fwd_edge); a head that
-    has an ``edge_layer.weight`` needs it."""
+    has an ``edge_layer.weight`` needs it.
+    ``attention="gatv2"``: the score is ``a . LeakyReLU(Wh_i + Wh_j) + b`` (cova_gat2_fwd; the edge term is added outside
+    the non-linearity); the projections are the same GEMM(s), and the saved dict carries no ``s`` / ``t``."""
     _check(ctx, torch.int64)
     Wi, Wj = params[prefix + "W_i.weight"], params[prefix + "W_j.weight"]
     aw, ab = params[prefix + "attention_layer.weight"], params[prefix + "attention_layer.bias"]
@@ -1323,12 +1336,23 @@ def gat_fwd(h, ldh, N, F, ctx, params, hprime, ldo, prefix="gat.", phi=None):
         raise ValueError("%s: %s" % (prefix, "an edge-aware head needs the edge features phi (boxes and page size)"
                                      if phi is None else "edge features given to a head without edge_layer.weight"))
     D, K = Wi.shape[0], ctx.shape[1]
+    v2 = attention == "gatv2"
+    if aw.shape[-1] != (D if v2 else 2 * D) or not (v2 or attention == "gat"):
+        check_attention_weight(prefix, aw, D, attention)          # (raises)
     Wh = _empty((N, 2 * D), h)
     if _adjacent(Wi, Wj):        # one [2D, F] matrix (flat parameter bucket): both projections in one GEMM
         call("cova_sgemm", 0, 1, N, 2 * D, F, h, ldh, Wi, F, Wh, 2 * D, None, 0)
     else:
         call("cova_sgemm", 0, 1, N, D, F, h, ldh, Wi, F, Wh, 2 * D, None, 0)
         call("cova_sgemm", 0, 1, N, D, F, h, ldh, Wj, F, Wh[:, D:], 2 * D, None, 0)
+    if v2:
+        attn = _empty((N, K), h)
+        if phi is not None:
+            assert tuple(phi.shape) == (N, K, 8), (tuple(phi.shape), N, K)
+            _check(phi), _check(ew)
+        call("cova_gat2_fwd", Wh, 2 * D, aw, ab, ctx, phi, ew, N, K, D, LEAKY_SLOPE, attn, hprime, ldo)
+        return dict(h=h, ldh=ldh, N=N, F=F, D=D, K=K, ctx=ctx, Wh=Wh, attn=attn, prefix=prefix, phi=phi,
+                    attention="gatv2")
     s, t, attn = _empty((N,), h), _empty((N,), h), _empty((N, K), h)
     if phi is None:
         call("cova_gat_fwd", Wh, 2 * D, aw, ab, ctx, N, K, D, LEAKY_SLOPE, s, t, attn, hprime, ldo)
@@ -1372,19 +1396,29 @@ def gat_bwd(sv, g, ldg, params, dh, lddh, accumulate_dh, gout=None, csr=None):
     Wi, Wj = params[prefix + "W_i.weight"], params[prefix + "W_j.weight"]
     aw = params[prefix + "attention_layer.weight"]
     dWh = _empty((N, 2 * D), g)
-    ds, dt = _empty((N,), g), _empty((N,), g)
-    daw = _gbuf(gout, prefix + "attention_layer.weight", (1, 2 * D), g)
+    v2 = sv.get("attention", "gat") == "gatv2"
+    if aw.shape[-1] != (D if v2 else 2 * D):
+        check_attention_weight(prefix, aw, D, sv.get("attention", "gat"))          # (raises)
+    daw = _gbuf(gout, prefix + "attention_layer.weight", (1, D if v2 else 2 * D), g)
     dab = _gbuf(gout, prefix + "attention_layer.bias", (1,), g)
-    phi, edge = sv.get("phi"), {}
-    if phi is None:
-        call("cova_gat_bwd", g, ldg, sv["Wh"], 2 * D, sv["s"], sv["t"], sv["attn"], sv["ctx"], aw, N, K, D,
-             LEAKY_SLOPE, dWh, 2 * D, ds, dt, daw, dab, csr, du)
-    else:
+    phi, ew, dew, edge = sv.get("phi"), None, None, {}
+    if phi is not None:
+        ew = params[prefix + "edge_layer.weight"]
         dew = _gbuf(gout, prefix + "edge_layer.weight", (1, 8), g)
-        ws = _empty((query("cova_gat_edge_workspace_floats", N, K),), g)
-        call("cova_gat_bwd_edge", g, ldg, sv["Wh"], 2 * D, sv["s"], sv["t"], sv["attn"], sv["ctx"], aw, phi,
-             params[prefix + "edge_layer.weight"], N, K, D, LEAKY_SLOPE, dWh, 2 * D, ds, dt, daw, dab, dew, csr, du, ws)
         edge = {prefix + "edge_layer.weight": dew}
+    if v2:
+        ws = _empty((query("cova_gat2_workspace_floats", N, K, D),), g)
+        call("cova_gat2_bwd", g, ldg, sv["Wh"], 2 * D, sv["attn"], sv["ctx"], aw, phi, ew, N, K, D, LEAKY_SLOPE, dWh, 2 * D,
+             daw, dab, dew, csr, du, ws)
+    else:
+        ds, dt = _empty((N,), g), _empty((N,), g)
+        if phi is None:
+            call("cova_gat_bwd", g, ldg, sv["Wh"], 2 * D, sv["s"], sv["t"], sv["attn"], sv["ctx"], aw, N, K, D,
+                 LEAKY_SLOPE, dWh, 2 * D, ds, dt, daw, dab, csr, du)
+        else:
+            ws = _empty((query("cova_gat_edge_workspace_floats", N, K),), g)
+            call("cova_gat_bwd_edge", g, ldg, sv["Wh"], 2 * D, sv["s"], sv["t"], sv["attn"], sv["ctx"], aw, phi, ew, N, K,
+                 D, LEAKY_SLOPE, dWh, 2 * D, ds, dt, daw, dab, dew, csr, du, ws)
     dWi = _gbuf(gout, prefix + "W_i.weight", (D, F), g)
     dWj = _gbuf(gout, prefix + "W_j.weight", (D, F), g)
     if _adjacent(dWi, dWj):
@@ -1402,12 +1436,12 @@ def gat_bwd(sv, g, ldg, params, dh, lddh, accumulate_dh, gout=None, csr=None):
 
 
 def gat_stack_fwd(comb, T, N, F, D, ctx, params, n_heads=1, n_gat_layers=1, bboxes=None, page_size=None,
-                  edge_geometry_on=False):
+                  edge_geometry_on=False, attention="gat"):
     """The reference's single GraphAttentionLayer (models.py:114) or the multi-head / stacked extension:
     every layer concatenates its heads (hidden_dim/n_heads channels each, written side by side), layers
     are chained; the last one writes the context columns comb[:, F:].
     ``edge_geometry_on``: the edge features of the batch (``bboxes``, ``page_size`` = (height, width)) are computed once
-    and handed to every head."""
+    and handed to every head.  ``attention``: the scoring mode of every head ('gat' | 'gatv2', gat_fwd)."""
     from .weights import gat_prefixes
     prefixes = gat_prefixes(n_heads, n_gat_layers)
     phi = None
@@ -1420,7 +1454,7 @@ def gat_stack_fwd(comb, T, N, F, D, ctx, params, n_heads=1, n_gat_layers=1, bbox
     for l, heads in enumerate(prefixes):
         last = l == len(prefixes) - 1
         out, ldo = (comb[:, F:], T) if last else (_empty((N, D), comb), D)
-        svs = [gat_fwd(h, ldh, N, fin, ctx, params, out[:, i * dh:], ldo, prefix=p, phi=phi)
+        svs = [gat_fwd(h, ldh, N, fin, ctx, params, out[:, i * dh:], ldo, prefix=p, phi=phi, attention=attention)
                for i, p in enumerate(heads)]
         layers.append(dict(heads=svs, out=out))
         h, ldh, fin = out, ldo, D
@@ -1561,7 +1595,8 @@ def _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, t
             raise ValueError("edge_geometry: a batch without images must carry page_size = (height, width) "
                              "(or the configuration a 'page_size')")
         sv["gat"] = gat_stack_fwd(comb, T, N, F, D, context_indices, params, cfg.get("n_heads", 1),
-                                  cfg.get("n_gat_layers", 1), bboxes if edge else None, sv.get("page_size"), edge)
+                                  cfg.get("n_gat_layers", 1), bboxes if edge else None, sv.get("page_size"), edge,
+                                  cfg.get("attention", "gat"))
     logits, sv["dec"] = decoder_fwd(comb, N, T, params, buffers, training, cfg["drop_prob"], seeds,
                                     masks)
     return logits, (sv if save else None)

@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import engine
-from .weights import EDGE_FEATURES, backbone_channels, check_backbone_layers
+from .weights import EDGE_FEATURES, attention_of, backbone_channels, check_attention, check_backbone_layers
 
 GAT_MAX_K = engine.GAT_MAX_K
 LOSS_MAX_CLASSES = engine.LOSS_MAX_CLASSES
@@ -263,7 +263,8 @@ class _GATFn(torch.autograd.Function):
         if edge_w is not None:
             params["gat.edge_layer.weight"] = edge_w.detach().contiguous()
         hp = torch.empty((N, layer.hidden_dim), device=h.device)
-        ctx.sv = engine.gat_fwd(h, F, N, F, _i64c(context_indices), params, hp, layer.hidden_dim, phi=phi)
+        ctx.sv = engine.gat_fwd(h, F, N, F, _i64c(context_indices), params, hp, layer.hidden_dim, phi=phi,
+                                attention=layer.attention)
         ctx.params = params
         ctx.mark_non_differentiable(ctx.sv["attn"])
         return hp, ctx.sv["attn"]
@@ -308,22 +309,39 @@ def _edge_features(context_indices, bboxes, page_size):
 class GraphAttentionLayer(nn.Module):
     """Single-head additive attention over K padded neighbours (reference models.py:151-212).
     ``edge_geometry=True`` (extension): the score of an edge also takes ``edge_layer`` (Linear(8, 1), no bias, zero at
-    construction) of its relative-geometry features (include/cova_hip.h, cova_edge_geometry)."""
+    construction) of its relative-geometry features (include/cova_hip.h, cova_edge_geometry).
+    ``attention="gatv2"`` (extension): the dynamic score of Brody et al. (ICLR 2022), ``attention_layer(LeakyReLU(W_i h_i +
+    W_j h_j))`` with ``attention_layer`` a Linear(hidden_dim, 1), instead of the reference's static
+    ``LeakyReLU(attention_layer([W_i h_i ; W_j h_j]))``; the edge term is then added outside the non-linearity."""
 
-    def __init__(self, in_features, hidden_dim, alpha=0.2, edge_geometry=False):
+    def __init__(self, in_features, hidden_dim, alpha=0.2, edge_geometry=False, attention="gat"):
         super(GraphAttentionLayer, self).__init__()
         if abs(alpha - engine.LEAKY_SLOPE) > 1e-12:
             raise ValueError("the HIP path is built for the reference's LeakyReLU slope 0.2")
         self.in_features = in_features
         self.hidden_dim = hidden_dim
         self.edge_geometry = bool(edge_geometry)
+        self.attention = check_attention(attention)
         self.W_i = nn.Linear(self.in_features, self.hidden_dim, bias=False)
         self.W_j = nn.Linear(self.in_features, self.hidden_dim, bias=False)
-        self.attention_layer = nn.Linear(2 * self.hidden_dim, 1)
+        self.attention_layer = nn.Linear((1 if self.attention == "gatv2" else 2) * self.hidden_dim, 1)
         self.leakyrelu = nn.LeakyReLU(alpha)
         if self.edge_geometry:
             self.edge_layer = nn.Linear(EDGE_FEATURES, 1, bias=False)
             nn.init.zeros_(self.edge_layer.weight)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        w = state_dict.get(prefix + "attention_layer.weight")
+        if torch.is_tensor(w) and w.shape != self.attention_layer.weight.shape:
+            try:
+                theirs = "attention=%r" % attention_of(w, self.hidden_dim, prefix)
+            except ValueError:
+                theirs = "neither attention mode at hidden_dim %d" % self.hidden_dim
+            error_msgs.append("%sattention_layer.weight: this layer was built with attention=%r (weight %s), the "
+                              "checkpoint's %s belongs to %s; a checkpoint loads into the attention mode it was trained "
+                              "with only" % (prefix, self.attention, tuple(self.attention_layer.weight.shape),
+                                             tuple(w.shape), theirs))
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
 
     def forward(self, h_i, context_indices, return_attn_wts=False, bboxes=None, page_size=None, phi=None):
         """h_i [N, in_features]; context_indices int64 [N, n_context] with -1 pads.  An edge-aware layer also needs
@@ -345,10 +363,10 @@ class GraphAttentionLayer(nn.Module):
 
 
 class _GATHeads(nn.Module):
-    def __init__(self, in_features, hidden_dim, n_heads, edge_geometry=False):
+    def __init__(self, in_features, hidden_dim, n_heads, edge_geometry=False, attention="gat"):
         super().__init__()
-        self.heads = nn.ModuleList([GraphAttentionLayer(in_features, hidden_dim // n_heads, edge_geometry=edge_geometry)
-                                    for _ in range(n_heads)])
+        self.heads = nn.ModuleList([GraphAttentionLayer(in_features, hidden_dim // n_heads, edge_geometry=edge_geometry,
+                                                        attention=attention) for _ in range(n_heads)])
 
 
 class MultiHeadGraphAttention(nn.Module):
@@ -356,15 +374,17 @@ class MultiHeadGraphAttention(nn.Module):
     models.py:78-79): ``n_layers`` stacked layers, each the concatenation of ``n_heads``
     GraphAttentionLayers of hidden_dim/n_heads channels over the same neighbour table.  Same call
     contract as GraphAttentionLayer; the attention weights returned are the last layer's, per head
-    [N, n_heads, n_context].  ``edge_geometry``: every head is edge-aware; the features are computed once per call."""
+    [N, n_heads, n_context].  ``edge_geometry``: every head is edge-aware; the features are computed once per call.
+    ``attention``: the scoring mode of every head ('gat' | 'gatv2', GraphAttentionLayer)."""
 
-    def __init__(self, in_features, hidden_dim, n_heads, n_layers, edge_geometry=False):
+    def __init__(self, in_features, hidden_dim, n_heads, n_layers, edge_geometry=False, attention="gat"):
         super().__init__()
         if hidden_dim % n_heads:
             raise ValueError("hidden_dim must be divisible by n_heads")
         self.edge_geometry = bool(edge_geometry)
-        self.layers = nn.ModuleList([_GATHeads(in_features if l == 0 else hidden_dim, hidden_dim, n_heads, edge_geometry)
-                                     for l in range(n_layers)])
+        self.attention = check_attention(attention)
+        self.layers = nn.ModuleList([_GATHeads(in_features if l == 0 else hidden_dim, hidden_dim, n_heads, edge_geometry,
+                                               attention) for l in range(n_layers)])
 
     def forward(self, h_i, context_indices, return_attn_wts=False, bboxes=None, page_size=None, phi=None):
         h, attn = h_i, None
@@ -382,7 +402,7 @@ class CoVA(nn.Module):
     def __init__(self, roi_output_size, img_H, n_classes, use_context=True, hidden_dim=384,
                  bbox_hidden_dim=32, n_additional_feat=0, drop_prob=0.2, class_names=None,
                  backbone="resnet18", n_heads=1, n_gat_layers=1, backbone_state_dict=None, roi_op="pool",
-                 sampling_ratio=2, roi_aligned=False, backbone_layers=1, edge_geometry=False):
+                 sampling_ratio=2, roi_aligned=False, backbone_layers=1, edge_geometry=False, attention="gat"):
         """The first nine arguments exactly as the reference's CoVA (models.py:10-34; called positionally
         at main.py:122-132).  Keyword-only-in-practice extensions, whose defaults are the reference's
         model: ``backbone`` 'resnet18' | 'resnet50' (torchvision ``children()[:-5]`` of either),
@@ -396,8 +416,12 @@ class CoVA(nn.Module):
         channels at stride 8, parameters under ``convnet.5.``.
         ``edge_geometry=True``: every attention head scores an edge with its relative box geometry as well (one
         ``edge_layer.weight`` [1, 8] per head, zero at construction: the fresh model computes the plain model's output);
-        the page size is taken from ``images``."""
+        the page size is taken from ``images``.
+        ``attention="gatv2"``: every head scores with the GATv2 form ``a . LeakyReLU(W_i h_i + W_j h_j) + b`` (dynamic
+        attention: the ranking of a box's neighbours depends on the box); ``attention_layer.weight`` is then
+        [1, hidden_dim / n_heads], so checkpoints of the two modes do not load into each other."""
         check_backbone_layers(backbone, backbone_layers)
+        check_attention(attention)
         if roi_op not in ("pool", "align"):
             raise ValueError("roi_op must be 'pool' (the reference, models.py:58) or 'align'")
         super(CoVA, self).__init__()
@@ -449,9 +473,11 @@ class CoVA(nn.Module):
 
         if self.use_context:
             if n_heads == 1 and n_gat_layers == 1:
-                self.gat = GraphAttentionLayer(self.n_feat, self.hidden_dim, edge_geometry=edge_geometry)
+                self.gat = GraphAttentionLayer(self.n_feat, self.hidden_dim, edge_geometry=edge_geometry,
+                                               attention=attention)
             else:
-                self.gat = MultiHeadGraphAttention(self.n_feat, self.hidden_dim, n_heads, n_gat_layers, edge_geometry)
+                self.gat = MultiHeadGraphAttention(self.n_feat, self.hidden_dim, n_heads, n_gat_layers, edge_geometry,
+                                                   attention)
         self.n_total_feat = self.n_feat + (self.hidden_dim if self.use_context else 0)
         self.decoder = nn.Sequential(nn.Dropout(drop_prob),
                                      nn.Linear(self.n_total_feat, self.n_total_feat),
@@ -465,7 +491,8 @@ class CoVA(nn.Module):
                          spatial_scale=self.roi_pool.spatial_scale, backbone=backbone,
                          n_heads=n_heads, n_gat_layers=n_gat_layers, roi_op=roi_op,
                          sampling_ratio=int(sampling_ratio), roi_aligned=bool(roi_aligned),
-                         backbone_layers=backbone_layers, edge_geometry=bool(edge_geometry) and bool(use_context))
+                         backbone_layers=backbone_layers, edge_geometry=bool(edge_geometry) and bool(use_context),
+                         attention=attention)
         self._param_keys = [k for k, _ in self.named_parameters()]
         self._conv_keys = [k for k in self._param_keys if k.startswith("convnet.")]
         self._bbox_keys = [k for k in self._param_keys if k.startswith("bbox_feat_encoder.")]

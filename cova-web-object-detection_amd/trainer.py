@@ -270,7 +270,7 @@ class HotPathTrainer:
         spec = state_dict_spec(**{k: cfg[k] for k in ("roi_output_size", "n_classes", "use_context",
                                                      "hidden_dim", "bbox_hidden_dim", "n_additional_feat",
                                                      "backbone", "n_heads", "n_gat_layers", "backbone_layers",
-                                                     "edge_geometry")
+                                                     "edge_geometry", "attention")
                                   if k in cfg})
         pshapes = OrderedDict((k, s) for k, s in spec if is_param_key(k))
         self.pbucket = FlatBucket(pshapes, self.device)
@@ -282,6 +282,7 @@ class HotPathTrainer:
         # with averaging the running statistics live in one flat buffer, the batch counters in another (same keys, shapes
         # and values): the average of the statistics is then one launch with a one-row table, the counters one copy
         stat_views = self._flat_buffers(spec) if self._avg is not None else {}
+        self._check_attention_mode(state_dict)
         for k, _ in spec:
             v = state_dict[k]
             if is_param_key(k):
@@ -305,6 +306,19 @@ class HotPathTrainer:
         self.measure_allreduce = True     # record them (up to 4096 steps; exposed_allreduce_ms() drains the list)
         if world_size > 1:
             self.broadcast_state(src=0)
+
+    def _check_attention_mode(self, state_dict):
+        """A checkpoint of the other scoring mode differs in the width of every ``attention_layer.weight`` only: name the
+        mode instead of failing on a tensor size."""
+        mode = self.cfg.get("attention", "gat")
+        for k, p in self.params.items():
+            v = state_dict.get(k) if k.endswith("attention_layer.weight") else None
+            if torch.is_tensor(v) and v.numel() != p.numel():
+                other = "gatv2" if p.numel() == 2 * v.numel() else "gat" if 2 * p.numel() == v.numel() else None
+                raise ValueError("this trainer was configured with attention=%r (%s is %s), the state_dict holds %s%s: "
+                                 "a checkpoint loads into the attention mode it was trained with only"
+                                 % (mode, k, tuple(p.shape), tuple(v.shape),
+                                    " (attention=%r)" % other if other and other != mode else ""))
 
     def _flat_buffers(self, spec):
         """Live BatchNorm buffers of an averaging trainer -> {key: view}: ``bbucket`` (float32, running_mean /
@@ -698,6 +712,7 @@ class HotPathTrainer:
         if missing:
             raise KeyError("state_dict lacks %s" % missing[:4])
         if bad:
+            self._check_attention_mode(state_dict)
             raise ValueError("state_dict entries of the wrong size: %s" % bad[:4])
         for k, p in self.params.items():
             p.copy_(state_dict[k].to(p.device).view_as(p))

@@ -15,6 +15,24 @@ import torch
 BACKBONE_CHANNELS = 64  # ResNet-18 conv1/layer1 width (models.py:49-51 keeps conv1..layer1)
 BACKBONE_STRIDE = 4     # conv1 stride 2 * maxpool stride 2
 EDGE_FEATURES = 8       # relative-geometry features per edge (include/cova_hip.h, cova_edge_geometry)
+ATTENTION_MODES = ("gat", "gatv2")   # the reference's static score | a . LeakyReLU(Wh_i + Wh_j) + b (cova_gat2_fwd)
+
+
+def check_attention(attention):
+    if attention not in ATTENTION_MODES:
+        raise ValueError("attention must be one of %s, got %r" % (ATTENTION_MODES, attention))
+    return attention
+
+
+def attention_of(weight, D, prefix="gat."):
+    """The scoring mode an ``attention_layer.weight`` belongs to, by its width: [1, 2D] is 'gat', [1, D] is 'gatv2'."""
+    width = int(weight.shape[-1]) if weight.dim() else -1
+    if width == 2 * D:
+        return "gat"
+    if width == D:
+        return "gatv2"
+    raise ValueError("%sattention_layer.weight has shape %s: neither [1, %d] (attention='gat') nor [1, %d] "
+                     "(attention='gatv2')" % (prefix, tuple(weight.shape), 2 * D, D))
 
 
 def _bn_entries(prefix, c):
@@ -57,7 +75,7 @@ def gat_prefixes(n_heads=1, n_gat_layers=1):
 
 def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=384,
                     bbox_hidden_dim=32, n_additional_feat=0, backbone="resnet18", n_heads=1,
-                    n_gat_layers=1, backbone_layers=1, edge_geometry=False):
+                    n_gat_layers=1, backbone_layers=1, edge_geometry=False, attention="gat"):
     """Ordered (key, shape) list, identical to ``reference CoVA(...).state_dict()`` for the defaults.
 
     Extensions (BASELINE.json configs[2], configs[4]; absent from the reference, defaults keep its
@@ -68,8 +86,11 @@ def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidde
     ``backbone_layers=2`` = resnet18 ``children()[:-4]``: layer2 (two BasicBlocks, 64 -> 128 channels at stride 2, block 0
     with the 1x1 downsample) under ``convnet.5.`` with torchvision's key names;
     ``edge_geometry=True`` = one ``edge_layer.weight`` [1, 8] per attention head, behind its ``attention_layer.bias`` (W_i and
-    W_j stay adjacent): the weights of the relative-geometry term of the attention score (cova_edge_geometry)."""
+    W_j stay adjacent): the weights of the relative-geometry term of the attention score (cova_edge_geometry);
+    ``attention="gatv2"`` = every ``attention_layer.weight`` is [1, hidden_dim/n_heads] instead of [1, 2 hidden_dim/n_heads]
+    (the GATv2 score a . LeakyReLU(Wh_i + Wh_j) + b, cova_gat2_fwd): the shape only, keys and their order are unchanged."""
     check_backbone_layers(backbone, backbone_layers)
+    check_attention(attention)
     c = BACKBONE_CHANNELS
     spec = [("convnet.0.weight", (c, 3, 7, 7))]
     spec += _bn_entries("convnet.1.", c)
@@ -123,7 +144,7 @@ def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidde
             for p in heads:
                 spec += [(p + "W_i.weight", (dh, fin)),
                          (p + "W_j.weight", (dh, fin)),
-                         (p + "attention_layer.weight", (1, 2 * dh)),
+                         (p + "attention_layer.weight", (1, dh if attention == "gatv2" else 2 * dh)),
                          (p + "attention_layer.bias", (1,))]
                 if edge_geometry:
                     spec.append((p + "edge_layer.weight", (1, EDGE_FEATURES)))

@@ -457,6 +457,33 @@ int cova_gat_bwd_edge(const float *g, int ldg, const float *Wh, int ldw, const f
                       const float *edge_w /*[8]*/, int N, int K, int D, float slope, float *dWh /*[N,2D]*/, int lddw,
                       float *ds /*[N]*/, float *dt /*[N]*/, float *d_att_w /*[2D]*/, float *d_att_b /*[1]*/,
                       float *d_edge_w /*[8]*/, const int *csr, float *du /*[N,K]*/, float *workspace, void *stream);
+/* ---- GATv2 dynamic attention (gat_v2.hip; opt-in: CoVA(attention="gatv2"); Brody et al., ICLR 2022) ----
+ * The static score above is LeakyReLU(s[i] + t[j]): every node ranks a given set of neighbours alike.  cova_gat2_fwd scores
+ *   z[i,k,d] = Wh[i,d] + Wh[j,D+d]  (j = ctx[i,k]; one f32 add),   u[i,k] = att_b + sum_d att_w[d] * lrelu(z[i,k,d]),
+ *   lrelu(z) = z > 0 ? z : slope * z  (z == +-0 takes the slope branch),   att_w [D] (not [2D]),
+ * and, when phi [N,K,8] (16-byte aligned) and edge_w [8] are given (together or not at all), u += edge_w . phi[i,k,:], added
+ * LAST and OUTSIDE the non-linearity -- cova_gat_fwd_edge has its edge term inside the LeakyReLU.  Mask (-9e15 on pads and
+ * ids >= N), softmax over k and h'[i] = sum_k attn[i,k] * Wh[j, D:2D] are cova_gat_fwd's; an all-pad row gives 1/K and a zero
+ * h'.  edge_w = 0 gives the bits of the call without phi.  One launch: a wave per node, float4 lanes over channels when
+ * D % 4 == 0 and Wh / att_w / hprime (and ldw, ldh) are 16-byte aligned, else a scalar form; D <= 2048 (scalar form 1024).
+ * cova_gat2_bwd: g = dL/dh'; writes du [N,K] = attn * (dattn - sum attn * dattn) (pads exactly 0), all of dWh [N,2D]
+ *   dWh[i,d]   = att_w[d] * sum_k du[i,k] * gate(z[i,k,d])                             gate(z) = z > 0 ? 1 : slope
+ *   dWh[j,D+d] = sum_{(i,k): ctx[i,k] = j} attn[i,k] * g[i,d] + du[i,k] * att_w[d] * gate(z[i,k,d])   through csr, ascending
+ * (the gates re-formed by the forward's add and compare: identical decisions), and d_att_w[d] = sum du * lrelu(z),
+ * d_att_b = sum du, d_edge_w[e] = sum du * phi[..,e] (with phi / edge_w / d_edge_w: all three or none): partial sums of
+ * fixed blocks of four nodes in `workspace` (cova_gat2_workspace_floats(N, K, D) floats), folded in index order -- no float
+ * atomics, bit-identical reruns.  Three launches.  csr from cova_gat_transpose(_reuse).  Bad arguments (K outside
+ * [1, 1024], D outside the range above, ld* too small, a NULL operand, phi without edge_w) return COVA_ERR_BAD_ARG before
+ * anything is launched; N == 0 launches nothing. */
+int cova_gat2_fwd(const float *Wh, int ldw, const float *att_w /*[D]*/, const float *att_b /*[1]*/,
+                  const int64_t *ctx /*[N,K]*/, const float *phi /*[N,K,8] or NULL*/, const float *edge_w /*[8] or NULL*/,
+                  int N, int K, int D, float slope, float *attn /*[N,K]*/, float *hprime, int ldh, void *stream);
+int cova_gat2_workspace_floats(int N, int K, int D);
+int cova_gat2_bwd(const float *g, int ldg, const float *Wh, int ldw, const float *attn, const int64_t *ctx,
+                  const float *att_w /*[D]*/, const float *phi /*[N,K,8] or NULL*/, const float *edge_w /*[8] or NULL*/,
+                  int N, int K, int D, float slope, float *dWh /*[N,2D]*/, int lddw, float *d_att_w /*[D]*/,
+                  float *d_att_b /*[1]*/, float *d_edge_w /*[8] or NULL*/, const int *csr, float *du /*[N,K]*/,
+                  float *workspace, void *stream);
 
 /* ------------------------------------------------------------------ decoder tail, loss, optimizer
  * replaces: nn.Dropout (models.py:84,88), nn.Linear(T, n_classes) (models.py:89),

@@ -1,0 +1,641 @@
+"""GPU tests of the GATv2 scoring mode: cova_gat2_fwd / cova_gat2_bwd through the C ABI against the float64 torch oracle
+(tests/gatv2_oracle.py: autograd, no code shared with the hand-written backward), the anchor to the reference-pinned static
+kernels at slope 1, refusals and empty work, the modules and the whole model under autograd, and HotPathTrainer with the
+option on.
+
+Bounds: the project's own for this layer (tests/test_edge_gpu.py, tests/test_model_gpu.py::
+test_gat_layer_matches_reference_fixture): max-abs error over max-abs reference below 1e-5 for h' and attn, below 1e-4 for
+dWh, d_att_w and d_edge_w; d_att_b is analytically ~0 (every softmax row's du sums to zero) and is held on the d_att_w scale.
+The kernel tests feed Wh: the float64 oracle sees the same f32 values, so its gates are the kernel's (an f32 sum of two f32
+numbers never has the wrong sign).  The whole model on the cova_h64_n11 inputs keeps tests/test_model_gpu.py's
+LOGIT_TOL / LOSS_TOL / GRAD_TOL."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from cova_web_object_detection_amd import _lib, engine, weights  # noqa: E402
+from cova_web_object_detection_amd.evaluation import evaluate_split, fit  # noqa: E402
+from cova_web_object_detection_amd.features import FeatureCache  # noqa: E402
+from cova_web_object_detection_amd.models import CoVA, GraphAttentionLayer, MultiHeadGraphAttention  # noqa: E402
+from cova_web_object_detection_amd.pipeline import DeviceDataset, attention_rows  # noqa: E402
+from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
+from helpers import compare_grads, load_case, routing_from_saved  # noqa: E402
+from oracle import cova_oracle as O  # noqa: E402
+import edge_oracle as EO  # noqa: E402
+import gatv2_oracle as G2  # noqa: E402
+
+DEV = "cuda:0"
+GUARD = -7.0
+NAN = float("nan")
+LOGIT_TOL, LOSS_TOL, GRAD_TOL = 5e-5, 2e-5, 1e-4          # tests/test_model_gpu.py
+SGEMM_TOL = 2e-5                                          # tests/test_kernels_gpu.py
+NEW = ("cova_gat2_fwd", "cova_gat2_bwd", "cova_gat2_workspace_floats")
+EDGE_W = np.asarray([1.5, -2.0, 0.75, -0.5, 3.0, -1.25, 2.0, 0.6], np.float32)
+ZERO_ROW, DUP_NBR = 7, 9                                  # node 7 names node 9 twice, on channels where z is +0.0 / -0.0
+
+
+def relerr(got, ref, scale=None):
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    return np.abs(got - ref).max() / max(np.abs(ref).max() if scale is None else scale, 1e-6)
+
+
+# ---------------------------------------------------------------- 1. the kernels through the C ABI
+#        N    K    D  pad   (pad: extra floats per row of Wh / h' / g / dWh; odd = unaligned rows = the scalar form)
+SHAPES = {"one": (1, 1, 6, 0),              # a single self-loop; fewer channels than lanes, scalar form
+          "scalar": (37, 24, 6, 3),         # D % 4 != 0
+          "passes": (37, 65, 64, 4),        # K > 64: two lane passes; float4 form, one chunk
+          "unaligned": (37, 24, 64, 1),     # D % 4 == 0 but odd leading dimensions: the scalar form at 64 channels
+          "wide": (130, 24, 384, 8),        # the second 256-channel chunk part-filled; a hub of in-degree 129
+          "general": (130, 100, 96, 4)}     # K = 100, 24 float4 lanes of 64
+
+
+def random_boxes(rs, n, size):
+    """[n, 5] boxes of one page: some overlap, some lie apart (every edge feature takes values off zero)."""
+    wh = rs.uniform(4, 0.25 * size, (n, 2))
+    xy = rs.uniform(0, 1, (n, 2)) * (size - wh)
+    return np.concatenate([np.zeros((n, 1)), xy, xy + wh], 1).astype(np.float32)
+
+
+def make_table(rs, N, K, out_of_range=True):
+    """Arbitrary ids with: an all-pad row (3), a row with one valid slot (4), ids >= N, self-loops, one neighbour named
+    twice in a row, a node nobody names (N - 1) and a hub every other row names (5)."""
+    ctx = rs.randint(-1, N, (N, K)).astype(np.int64)
+    if N == 1:
+        return np.zeros((1, K), np.int64)
+    ctx[::5, 0] = np.arange(N)[::5]                           # self-loops
+    if K >= 4:
+        ctx[:, K - 1] = 5                                     # the hub
+        ctx[ZERO_ROW, 1:3] = DUP_NBR                          # the same neighbour twice
+        if out_of_range:
+            ctx[11, 1], ctx[12, 2] = N, N + 1000
+    ctx[3] = -1
+    ctx[4] = -1
+    ctx[4, K // 2] = 8
+    ctx[ctx == N - 1] = -1                                    # in-degree 0
+    return ctx
+
+
+@functools.lru_cache(maxsize=None)
+def gat_case(name, out_of_range=True):
+    N, K, D, pad = SHAPES[name]
+    rs = np.random.RandomState(sum(map(ord, name)))
+    ctx = make_table(rs, N, K, out_of_range)
+    Wh = rs.standard_normal((N, 2 * D)).astype(np.float32)
+    if N > DUP_NBR and K >= 4:                                # z exactly +0.0 on channels 0, 1 and -0.0 on channel 2
+        Wh[DUP_NBR, D:D + 2] = -Wh[ZERO_ROW, :2]
+        Wh[ZERO_ROW, 2] = Wh[DUP_NBR, D + 2] = -0.0
+    bb = random_boxes(rs, N, 1280.0)
+    aw = (rs.standard_normal(D) / np.sqrt(D)).astype(np.float32)
+    aw[:3] = [0.5, -0.5, 0.5]                                 # the channels of the zero sums weigh in the gradient
+    case = dict(name=name, N=N, K=K, D=D, pad=pad, ctx=ctx, Wh=Wh, phi=EO.edge_features(bb, ctx, 1280.0, 1280.0),
+                aw=aw, ab=rs.standard_normal(1).astype(np.float32), g=rs.standard_normal((N, D)).astype(np.float32))
+    case["ref"] = oracle64(case, None)
+    case["ref_edge"] = oracle64(case, EDGE_W)
+    return case
+
+
+def oracle64(case, edge_w, gate=None, slope=0.2):
+    D = case["D"]
+    f64 = lambda a: torch.from_numpy(np.asarray(a, np.float64))
+    Wh = f64(case["Wh"]).requires_grad_(True)
+    aw, ab = f64(case["aw"]).requires_grad_(True), f64(case["ab"]).requires_grad_(True)
+    ew = None if edge_w is None else f64(edge_w).view(1, 8).requires_grad_(True)
+    hp, attn = G2.attend(Wh[:, :D], Wh[:, D:], torch.from_numpy(case["ctx"]), aw, ab, slope, ew,
+                         None if edge_w is None else f64(case["phi"]), gate)
+    (hp * f64(case["g"])).sum().backward()
+    return dict(hp=hp.detach().numpy(), attn=attn.detach().numpy(), dWh=Wh.grad.numpy(), daw=aw.grad.numpy(),
+                dab=ab.grad.numpy(), dew=None if ew is None else ew.grad.numpy().reshape(-1))
+
+
+def framed(rows, cols, ld):
+    """A GUARD-filled [rows + 2, ld] buffer whose interior [1:rows+1, :cols] is NaN -> (buffer, interior view)."""
+    buf = torch.full((rows + 2, ld), GUARD, dtype=torch.float32, device=DEV)
+    buf[1:rows + 1, :cols] = NAN
+    return buf, buf[1:rows + 1]
+
+
+def padded(a, ld):
+    """The rows of ``a`` at leading dimension ld, the padding NaN: a kernel that reads past a row poisons its output."""
+    buf = torch.full((a.shape[0], ld), NAN, dtype=torch.float32, device=DEV)
+    buf[:, :a.shape[1]] = torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    return buf
+
+
+def survived(buf, rows, cols):
+    host = buf.cpu().numpy()
+    inner = host[1:rows + 1, :cols]
+    assert np.isfinite(inner).all(), "an output was not written"
+    host = host.copy()
+    host[1:rows + 1, :cols] = GUARD
+    assert (host == GUARD).all(), "a guard row or column was overwritten"
+    return inner
+
+
+def launch(case, edge_w=None, slope=0.2):
+    """cova_gat2_fwd + cova_gat2_bwd on framed buffers -> dict of host arrays (guards checked)."""
+    N, K, D, pad = case["N"], case["K"], case["D"], case["pad"]
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    Wh, g = padded(case["Wh"], 2 * D + pad), padded(case["g"], D + pad)
+    aw, ab, ctx = dev(case["aw"]), dev(case["ab"]), dev(case["ctx"])
+    phi = ew = dew_buf = None
+    if edge_w is not None:
+        phi, ew = dev(case["phi"]), dev(np.asarray(edge_w, np.float32))
+        dew_buf, dew = framed(1, 8, 8)
+    attn_b, attn = framed(N, K, K)
+    hp_b, hp = framed(N, D, D + pad)
+    du_b, du = framed(N, K, K)
+    dWh_b, dWh = framed(N, 2 * D, 2 * D + pad)
+    daw_b, daw = framed(1, D, D)
+    dab_b, dab = framed(1, 1, 1)
+    csr = torch.zeros((engine.query("cova_gat_transpose_ints", N, K),), dtype=torch.int32, device=DEV)
+    engine.call("cova_gat_transpose", ctx, N, K, csr)
+    nws = engine.query("cova_gat2_workspace_floats", N, K, D)
+    assert nws == -(-N // 4) * (D + 9)
+    ws = torch.full((nws + 16,), NAN, device=DEV)
+    ws[nws:] = GUARD
+    engine.call("cova_gat2_fwd", Wh, 2 * D + pad, aw, ab, ctx, phi, ew, N, K, D, slope, attn, hp, D + pad)
+    engine.call("cova_gat2_bwd", g, D + pad, Wh, 2 * D + pad, attn, ctx, aw, phi, ew, N, K, D, slope, dWh, 2 * D + pad, daw,
+                dab, None if edge_w is None else dew, csr, du, ws)
+    torch.cuda.synchronize()
+    assert (ws[nws:] == GUARD).all()
+    out = dict(attn=survived(attn_b, N, K), hp=survived(hp_b, N, D), du=survived(du_b, N, K),
+               dWh=survived(dWh_b, N, 2 * D), daw=survived(daw_b, 1, D).reshape(-1), dab=survived(dab_b, 1, 1).reshape(-1))
+    if edge_w is not None:
+        out["dew"] = survived(dew_buf, 1, 8).reshape(-1)
+    return out
+
+
+def check_against(got, ref, what):
+    errs = {k: relerr(got[k], ref[k]) for k in ("hp", "attn", "dWh", "daw")}
+    errs["dab"] = relerr(got["dab"], ref["dab"], scale=np.abs(ref["daw"]).max())
+    if ref.get("dew") is not None:
+        errs["dew"] = relerr(got["dew"], ref["dew"])
+    print(what, {k: "%.2e" % v for k, v in errs.items()})
+    for k, e in errs.items():
+        assert e < (1e-5 if k in ("hp", "attn") else 1e-4), (what, k, e)
+
+
+@pytest.mark.parametrize("name", list(SHAPES))
+def test_forward_and_backward_match_the_float64_oracle(name):
+    case = gat_case(name)
+    N, K = case["N"], case["K"]
+    plain, edge = launch(case), launch(case, EDGE_W)
+    check_against(plain, case["ref"], name)
+    check_against(edge, case["ref_edge"], name + " + edge")
+    if N > 1:
+        assert float(np.abs(case["ref_edge"]["dew"]).min()) > 0
+        assert relerr(plain["attn"], case["ref_edge"]["attn"]) > 1e-3                # the edge term is live
+        for got in (plain, edge):
+            assert np.allclose(got["attn"][3], 1.0 / K) and not got["hp"][3].any()  # the all-pad row
+            assert got["attn"][4, K // 2] == 1.0 and np.array_equal(got["hp"][4], case["Wh"][8, case["D"]:])
+            pads = (case["ctx"] < 0) | (case["ctx"] >= N)
+            assert not got["du"][pads].any() and not got["attn"][pads & ~pads.all(1, keepdims=True)].any()
+            assert not got["dWh"][N - 1, case["D"]:].any()                            # in-degree 0: zeros
+    else:
+        assert plain["attn"][0, 0] == 1.0 and np.array_equal(plain["hp"][0], case["Wh"][0, case["D"]:])
+
+
+@pytest.mark.parametrize("name", ["scalar", "unaligned", "wide"])
+def test_signed_zero_sums_take_the_slope_branch_in_all_three_kernels(name):
+    """z[7, slots 1 and 2, channels 0..2] is +0.0, +0.0, -0.0.  An oracle that took the other branch there (z >= 0) moves
+    dWh[7, 0:3] (source side) and dWh[9, D:D+3] (destination side) by far more than the bound; the kernels follow z > 0."""
+    case = gat_case(name)
+    N, K, D = case["N"], case["K"], case["D"]
+    Wh = torch.from_numpy(case["Wh"])
+    ctx = torch.from_numpy(case["ctx"])
+    ok = (ctx >= 0) & (ctx < N)
+    rows = torch.cat((Wh[:, D:], torch.zeros(1, D)))
+    z = Wh[:, :D].unsqueeze(1) + rows[torch.where(ok, ctx, torch.full_like(ctx, N))]
+    zs = z[ZERO_ROW, 1:3, :3]
+    assert not zs.any() and bool(torch.signbit(zs[:, 2]).all()) and not bool(torch.signbit(zs[:, :2]).any())
+    wrong = oracle64(case, None, gate=(z >= 0))
+    got, ref = launch(case), case["ref"]
+    scale = np.abs(ref["dWh"]).max()
+    for rows_, cols in ((ZERO_ROW, slice(0, 3)), (DUP_NBR, slice(D, D + 3))):
+        assert np.abs(got["dWh"][rows_, cols] - ref["dWh"][rows_, cols]).max() < 1e-4 * scale
+        assert np.abs(wrong["dWh"][rows_, cols] - ref["dWh"][rows_, cols]).min() > 1e-3 * scale
+
+
+@pytest.mark.parametrize("name", ["scalar", "passes", "wide", "general"])
+def test_zero_edge_weight_gives_the_plain_bits_and_reruns_are_bit_identical(name):
+    case = gat_case(name)
+    p, e = launch(case), launch(case, np.zeros(8, np.float32))
+    for k in p:
+        assert np.array_equal(p[k].view(np.uint32), e[k].view(np.uint32)), k
+    assert relerr(e["dew"], oracle64(case, np.zeros(8, np.float32))["dew"]) < 1e-4 and float(np.abs(e["dew"]).min()) > 0
+    a, b = launch(case, EDGE_W), launch(case, EDGE_W)
+    for k in a:
+        assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
+    p2 = launch(case)
+    for k in p:
+        assert np.array_equal(p[k].view(np.uint32), p2[k].view(np.uint32)), k
+
+
+@pytest.mark.parametrize("name", ["scalar", "passes", "wide"])
+def test_a_node_keeps_its_bits_inside_a_larger_batch(name):
+    """The same nodes as the first rows of a larger N (the added nodes name each other only): every per-node output has
+    the same bits -- a node's outputs depend on its own row, its neighbours and the edges that name it.  d_att_w, d_att_b
+    and d_edge_w are sums over all nodes and are left out."""
+    small = gat_case(name, False)
+    N, K, D = small["N"], small["K"], small["D"]
+    extra = 30
+    rs = np.random.RandomState(3)
+    big = dict(small, N=N + extra)
+    more = N + rs.randint(0, extra, (extra, K)).astype(np.int64)
+    more[2, :] = -1
+    big["ctx"] = np.concatenate([small["ctx"], more])
+    big["Wh"] = np.concatenate([small["Wh"], rs.standard_normal((extra, 2 * D)).astype(np.float32)])
+    big["g"] = np.concatenate([small["g"], rs.standard_normal((extra, D)).astype(np.float32)])
+    big["phi"] = np.concatenate([small["phi"], rs.standard_normal((extra, K, 8)).astype(np.float32)])
+    for ew in (None, EDGE_W):
+        a, b = launch(small, ew), launch(big, ew)
+        for k in ("attn", "hp", "du", "dWh"):
+            assert np.array_equal(a[k].view(np.uint32), b[k][:N].view(np.uint32)), (k, ew is not None)
+        assert np.isfinite(b["daw"]).all()
+
+
+def launch_static(case, aw2, edge_w, slope):
+    """cova_gat_fwd(_edge) + cova_gat_bwd(_edge), the reference-pinned kernels, on the same operands."""
+    N, D, K = case["N"], case["D"], case["K"]
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    Wh, g, aw, ab, ctx = dev(case["Wh"]), dev(case["g"]), dev(aw2), dev(case["ab"]), dev(case["ctx"])
+    new = lambda *shape: torch.full(shape, NAN, device=DEV)
+    s, t, attn, hp = new(N), new(N), new(N, K), new(N, D)
+    dWh, ds, dt, daw, dab, dew, du = new(N, 2 * D), new(N), new(N), new(2 * D), new(1), new(8), new(N, K)
+    csr = torch.zeros((engine.query("cova_gat_transpose_ints", N, K),), dtype=torch.int32, device=DEV)
+    engine.call("cova_gat_transpose", ctx, N, K, csr)
+    if edge_w is None:
+        engine.call("cova_gat_fwd", Wh, 2 * D, aw, ab, ctx, N, K, D, slope, s, t, attn, hp, D)
+        engine.call("cova_gat_bwd", g, D, Wh, 2 * D, s, t, attn, ctx, aw, N, K, D, slope, dWh, 2 * D, ds, dt, daw, dab, csr, du)
+    else:
+        phi, ew = dev(case["phi"]), dev(edge_w)
+        ws = new(engine.query("cova_gat_edge_workspace_floats", N, K))
+        engine.call("cova_gat_fwd_edge", Wh, 2 * D, aw, ab, ctx, phi, ew, N, K, D, slope, s, t, attn, hp, D)
+        engine.call("cova_gat_bwd_edge", g, D, Wh, 2 * D, s, t, attn, ctx, aw, phi, ew, N, K, D, slope, dWh, 2 * D, ds, dt,
+                    daw, dab, dew, csr, du, ws)
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in dict(attn=attn, hp=hp, dWh=dWh, daw=daw, dab=dab, dew=dew, du=du).items()}
+
+
+@pytest.mark.parametrize("name", ["scalar", "passes", "wide", "general"])
+def test_at_slope_one_the_kernels_agree_with_the_reference_pinned_static_kernels(name):
+    """slope = 1: a . lrelu(Wh_i + Wh_j) = a . Wh_i + a . Wh_j, the static score with att_w = [a ; a] (and the edge term
+    inside or outside the identity is the same term).  To the bounds, not bit for bit."""
+    case = gat_case(name, False)                              # (the static kernels are given in-range tables here too)
+    D = case["D"]
+    for ew in (None, EDGE_W):
+        v2 = launch(case, ew, slope=1.0)
+        st = launch_static(case, np.concatenate([case["aw"], case["aw"]]), ew, 1.0)
+        errs = {k: relerr(v2[k], st[k]) for k in ("hp", "attn", "dWh", "du")}
+        errs["daw"] = relerr(v2["daw"], st["daw"][:D] + st["daw"][D:])         # the two halves sum to the v2 gradient
+        errs["dab"] = relerr(v2["dab"], st["dab"], scale=np.abs(v2["daw"]).max())
+        if ew is not None:
+            errs["dew"] = relerr(v2["dew"], st["dew"])
+        print(name, ew is not None, {k: "%.2e" % v for k, v in errs.items()})
+        for k, e in errs.items():
+            assert e < (1e-5 if k in ("hp", "attn") else 1e-4), (name, k, e)
+
+
+def test_entry_points_refuse_bad_arguments_and_skip_empty_work():
+    N, K, D = 8, 6, 16
+    z = lambda *shape: torch.zeros(shape, device=DEV)
+    ctx = torch.zeros((N, K), dtype=torch.int64, device=DEV)
+    hp, attn = torch.full((N, D), GUARD, device=DEV), torch.full((N, K), GUARD, device=DEV)
+    Wh, aw, ab, phi, ew = z(N, 2 * D), z(D), z(1), z(N, K, 8), z(8)
+    fwd = lambda *a: engine.call("cova_gat2_fwd", *a)
+    good_f = [Wh, 2 * D, aw, ab, ctx, None, None, N, K, D, 0.2, attn, hp, D]
+
+    def bad(args, **changes):
+        a = list(args)
+        for i, v in changes.items():
+            a[int(i[1:])] = v
+        return a
+    for ch in (dict(_1=2 * D - 1), dict(_13=D - 1), dict(_8=0), dict(_8=1025), dict(_9=0), dict(_9=4096), dict(_7=-1),
+               dict(_5=phi), dict(_6=ew), dict(_5=phi.view(-1)[1:], _6=ew), dict(_0=None), dict(_2=None), dict(_3=None),
+               dict(_4=None), dict(_11=None), dict(_12=None)):
+        with pytest.raises(_lib.CovaHipError):
+            fwd(*bad(good_f, **ch))
+    g, du, dWh, daw, dab, dew = z(N, D), z(N, K), torch.full((N, 2 * D), GUARD, device=DEV), z(D), z(1), z(8)
+    csr = torch.zeros((engine.query("cova_gat_transpose_ints", N, K),), dtype=torch.int32, device=DEV)
+    engine.call("cova_gat_transpose", ctx, N, K, csr)
+    ws = z(engine.query("cova_gat2_workspace_floats", N, K, D))
+    good_b = [g, D, Wh, 2 * D, attn, ctx, aw, None, None, N, K, D, 0.2, dWh, 2 * D, daw, dab, None, csr, du, ws]
+    for ch in (dict(_1=D - 1), dict(_3=2 * D - 1), dict(_14=2 * D - 1), dict(_10=0), dict(_10=1025), dict(_11=0),
+               dict(_11=4096), dict(_9=-1), dict(_7=phi), dict(_8=ew), dict(_17=dew), dict(_7=phi, _8=ew),
+               dict(_7=phi, _17=dew), dict(_7=phi.view(-1)[1:], _8=ew, _17=dew), dict(_18=None), dict(_19=None),
+               dict(_20=None), dict(_0=None), dict(_4=None), dict(_13=None), dict(_15=None), dict(_16=None)):
+        with pytest.raises(_lib.CovaHipError):
+            engine.call("cova_gat2_bwd", *bad(good_b, **ch))
+    # N == 0: nothing is launched, no pointer is needed
+    fwd(None, 2 * D, None, None, None, None, None, 0, K, D, 0.2, None, None, D)
+    engine.call("cova_gat2_bwd", None, D, None, 2 * D, None, None, None, None, None, 0, K, D, 0.2, None, 2 * D, None, None,
+                None, None, None, None)
+    torch.cuda.synchronize()
+    assert (hp == GUARD).all() and (attn == GUARD).all() and (dWh == GUARD).all()
+    assert engine.query("cova_gat2_workspace_floats", 70, 100, 40) == 18 * 49
+    assert engine.query("cova_gat2_workspace_floats", 0, 24, 384) == 0
+    fwd(*good_f)                                                # and the good calls are good
+    engine.call("cova_gat2_bwd", *good_b)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(hp).all()) and (hp != GUARD).all()
+
+
+# ---------------------------------------------------------------- 2. the modules
+def device_gates(Wh, ctx):
+    """(Wh_i + Wh_j[ctx]) > 0 in float32 from a head's saved Wh [N, 2D]: the kernels' own decisions."""
+    N, D = Wh.shape[0], Wh.shape[1] // 2
+    ok = (ctx >= 0) & (ctx < N)
+    rows = torch.cat((Wh[:, D:], Wh.new_zeros(1, D)))
+    return ((Wh[:, :D].unsqueeze(1) + rows[torch.where(ok, ctx, torch.full_like(ctx, N))]) > 0).cpu()
+
+
+def recorded_heads(monkeypatch):
+    """Every engine.gat_fwd call's saved dict, in call order (layer-major, heads ascending)."""
+    svs, real = [], engine.gat_fwd
+
+    def fn(*a, **kw):
+        sv = real(*a, **kw)
+        svs.append(sv)
+        return sv
+    monkeypatch.setattr(engine, "gat_fwd", fn)
+    return svs
+
+
+def check_param_grads(module, sd):
+    """Every parameter gradient to 1e-4; a v2 ``attention_layer.bias`` shifts all scores of a row alike, so its gradient
+    is analytically zero (round-off in both implementations) and is held on the scale of its head's attention weight."""
+    for key, p in module.named_parameters():
+        ref = sd["gat." + key].grad
+        scale = None
+        if key.endswith("attention_layer.bias"):
+            scale = float(sd["gat." + key[:-len("bias")] + "weight"].grad.abs().max())
+            assert scale > 0
+        assert relerr(p.grad.cpu(), ref, scale) < 1e-4, key
+
+
+def test_v2_layer_under_autograd_matches_the_oracle(monkeypatch):
+    rs = np.random.RandomState(13)
+    N, Fd, D, K = 131, 24, 8, 9
+    ctx_np = make_table(rs, N, K)
+    bb = random_boxes(rs, N, 400.0)
+    torch.manual_seed(11)
+    for edge in (False, True):
+        layer = GraphAttentionLayer(Fd, D, edge_geometry=edge, attention="gatv2")
+        assert layer.attention_layer.weight.shape == (1, D)
+        if edge:
+            with torch.no_grad():
+                layer.edge_layer.weight.copy_(torch.from_numpy(EDGE_W).view(1, 8))
+        sd = {"gat." + k: v.detach().clone().double().requires_grad_(True) for k, v in layer.state_dict().items()}
+        h_host = torch.from_numpy(rs.standard_normal((N, Fd)).astype(np.float32))
+        g_host = torch.from_numpy(rs.standard_normal((N, D)).astype(np.float32))
+        layer = layer.to(DEV)
+        h, ctx, boxes = h_host.to(DEV).requires_grad_(True), torch.from_numpy(ctx_np).to(DEV), torch.from_numpy(bb).to(DEV)
+        svs = recorded_heads(monkeypatch)
+        kw = dict(bboxes=boxes, page_size=(400, 400)) if edge else {}
+        hp, attn = layer(h, ctx, return_attn_wts=True, **kw)
+        (hp * g_host.to(DEV)).sum().backward()
+        monkeypatch.undo()
+        sv = svs[0]
+        assert sv["attention"] == "gatv2" and "s" not in sv and "t" not in sv
+        h_ref = h_host.double().requires_grad_(True)
+        proj = torch.cat((h_ref @ sd["gat.W_i.weight"].T, h_ref @ sd["gat.W_j.weight"].T), 1).detach()
+        assert relerr(sv["Wh"].cpu(), proj) < SGEMM_TOL
+        phi = torch.from_numpy(EO.edge_features(bb, ctx_np, 400, 400)).double() if edge else None
+        hp_ref, attn_ref = G2.gat_v2(h_ref, torch.from_numpy(ctx_np), sd, phi, return_attn_wts=True,
+                                     gate=device_gates(sv["Wh"], ctx))
+        (hp_ref * g_host.double()).sum().backward()
+        assert relerr(hp.detach().cpu(), hp_ref.detach()) < 1e-5
+        assert relerr(attn.cpu(), attn_ref.detach()) < 1e-5
+        assert relerr(h.grad.cpu(), h_ref.grad) < 1e-4
+        check_param_grads(layer, sd)
+    # a static weight in a v2 call (and the reverse) is a ValueError that names both
+    params = {"gat." + k: v.detach() for k, v in GraphAttentionLayer(Fd, D).to(DEV).state_dict().items()}
+    with pytest.raises(ValueError, match=r"attention='gatv2'.*\(1, 16\).*attention='gat'"):
+        engine.gat_fwd(h.detach(), Fd, N, Fd, ctx, params, torch.empty((N, D), device=DEV), D, attention="gatv2")
+    params = {"gat." + k: v.detach() for k, v in layer.state_dict().items() if "edge" not in k}
+    with pytest.raises(ValueError, match=r"attention='gat'.*\(1, 8\).*attention='gatv2'"):
+        engine.gat_fwd(h.detach(), Fd, N, Fd, ctx, params, torch.empty((N, D), device=DEV), D)
+
+
+def test_two_heads_by_two_layers_under_autograd_match_the_oracle(monkeypatch):
+    rs = np.random.RandomState(17)
+    N, Fd, D, K = 70, 20, 16, 12
+    ctx_np = make_table(rs, N, K, out_of_range=False)
+    torch.manual_seed(5)
+    multi = MultiHeadGraphAttention(Fd, D, 2, 2, attention="gatv2")
+    sd = {"gat." + k: v.detach().clone().double().requires_grad_(True) for k, v in multi.state_dict().items()}
+    prefixes = [p for layer in weights.gat_prefixes(2, 2) for p in layer]
+    assert all(sd[p + "attention_layer.weight"].shape == (1, D // 2) for p in prefixes)
+    multi = multi.to(DEV)
+    h_host = torch.from_numpy(rs.standard_normal((N, Fd)).astype(np.float32))
+    g_host = torch.from_numpy(rs.standard_normal((N, D)).astype(np.float32))
+    h, ctx = h_host.to(DEV).requires_grad_(True), torch.from_numpy(ctx_np).to(DEV)
+    svs = recorded_heads(monkeypatch)
+    out = multi(h, ctx)
+    (out * g_host.to(DEV)).sum().backward()
+    monkeypatch.undo()
+    assert len(svs) == 4
+    routing = {"gate_" + p + "leaky": device_gates(sv["Wh"], ctx) for p, sv in zip(prefixes, svs)}
+    monkeypatch.setattr(O, "gat", G2.patched_gat())
+    h_ref = h_host.double().requires_grad_(True)
+    out_ref, _ = O.gat_stack(h_ref, torch.from_numpy(ctx_np), sd, routing=routing)
+    (out_ref * g_host.double()).sum().backward()
+    assert relerr(out.detach().cpu(), out_ref.detach()) < 1e-5
+    assert relerr(h.grad.cpu(), h_ref.grad) < 1e-4
+    check_param_grads(multi, sd)
+
+
+@pytest.mark.parametrize("edge", [False, True])
+def test_v2_model_matches_the_oracle_on_the_reference_inputs(monkeypatch, edge):
+    fx, cfg, _, batch = load_case("cova_h64_n11")
+    cfg = dict(cfg, n_heads=2, n_gat_layers=2, attention="gatv2", **(dict(edge_geometry=True) if edge else {}))
+    wcfg = {k: v for k, v in cfg.items() if k != "drop_prob"}
+    seed, gain = int(fx["meta/seed"]), float(fx["meta/logit_gain"])
+    sd = weights.seeded_state_dict(seed, logit_gain=gain, **wcfg)
+    rs = np.random.RandomState(19)
+    edge_keys = [k for k in sd if k.endswith("edge_layer.weight")]
+    for k in edge_keys:
+        sd[k] = torch.from_numpy(rs.uniform(-2, 2, (1, 8)).astype(np.float32))
+    img_h = int(fx["meta/img_h"])
+    b = batch
+    page = tuple(b["images"].shape[2:])
+    tap = {}
+    patched = G2.patched_gat(b["bboxes"], page)
+
+    def tapped(h_i, context_indices, sd_, alpha=0.2, return_attn_wts=False, prefix="gat.", routing=None):
+        tap[prefix] = torch.cat((h_i @ sd_[prefix + "W_i.weight"].T, h_i @ sd_[prefix + "W_j.weight"].T), 1).detach()
+        return patched(h_i, context_indices, sd_, alpha, return_attn_wts, prefix, routing)
+    monkeypatch.setattr(O, "gat", tapped)
+    args = [b[k].to(DEV) for k in ("images", "bboxes", "additional_feats", "context_indices")]
+
+    def build():
+        m = CoVA(cfg["roi_output_size"], img_h, cfg["n_classes"], cfg["use_context"], cfg["hidden_dim"],
+                 cfg["bbox_hidden_dim"], cfg["n_additional_feat"], cfg["drop_prob"], None, n_heads=2, n_gat_layers=2,
+                 edge_geometry=edge, attention="gatv2")
+        assert [k for k in m.state_dict()] == list(sd)
+        missing = m.load_state_dict(sd, strict=True)
+        assert not missing.missing_keys and not missing.unexpected_keys
+        return m.to(DEV)
+
+    m = build().eval()
+    with torch.no_grad():
+        logits = m(*args)
+    ref = O.forward(O.clone_state_dict(sd), b["images"], b["bboxes"], b["additional_feats"], b["context_indices"], cfg, False)
+    assert relerr(logits.cpu(), ref) < LOGIT_TOL
+    # the option does something: the static model of the same seed computes other logits
+    scfg = {k: v for k, v in cfg.items() if k != "attention"}
+    static_sd = weights.seeded_state_dict(seed, logit_gain=gain, **{k: v for k, v in scfg.items() if k != "drop_prob"})
+    for k in edge_keys:
+        static_sd[k] = sd[k].clone()
+    static_ref = O.forward(O.clone_state_dict(static_sd), b["images"], b["bboxes"], b["additional_feats"],
+                           b["context_indices"], scfg, False)
+    assert relerr(static_ref, ref) > 1e-3
+    m = build().train()
+    logits = m(*args)
+    sv = logits.grad_fn.sv
+    routing = routing_from_saved(dict(sv, gat=None))          # conv, RoI and decoder decisions; the v2 gates below
+    heads = [head for layer in sv["gat"] for head in layer["heads"]]
+    assert len(heads) == 4
+    for head in heads:
+        assert head["attention"] == "gatv2" and "s" not in head and "t" not in head
+        routing["gate_" + head["prefix"] + "leaky"] = device_gates(head["Wh"], head["ctx"])
+    loss = torch.nn.CrossEntropyLoss(reduction="sum")(logits, b["labels"].to(DEV))
+    loss.backward()
+    tap.clear()
+    loss_ref, logits_ref, grads_ref, _, _ = O.loss_and_grads(sd, b["images"], b["bboxes"], b["additional_feats"],
+                                                             b["context_indices"], b["labels"], cfg, None, routing)
+    for head in heads:                                        # a wrong projection cannot hide behind the forced gates
+        e = relerr(head["Wh"].cpu(), tap[head["prefix"]])
+        print(head["prefix"], "Wh against the oracle's projection: %.2e" % e)
+        assert e < SGEMM_TOL, (head["prefix"], e)
+    assert relerr(logits.detach().cpu(), logits_ref) < LOGIT_TOL
+    assert abs(loss.item() - float(loss_ref)) <= LOSS_TOL * abs(float(loss_ref))
+    grads = {k: p.grad for k, p in m.named_parameters()}
+    assert all(float(grads_ref[k].abs().max()) > 0 for k in edge_keys)
+    compare_grads(grads, grads_ref, rtol=GRAD_TOL, outlier_frac=0.0)
+    for k in edge_keys:                                       # (compare_grads floors the scale at 1 % of the largest gradient)
+        assert relerr(grads[k].cpu(), grads_ref[k]) < 1e-4, k
+
+
+# ---------------------------------------------------------------- 3. the trainer
+CFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8,
+           n_additional_feat=0, drop_prob=0.2)
+VCFG = dict(CFG, attention="gatv2")
+AW = "gat.attention_layer.weight"
+
+
+def page_set(P=15, img=96, seed=4):
+    rs = np.random.RandomState(seed)
+    u8 = rs.randint(0, 256, (P, img, img, 3)).astype(np.uint8)
+    rows = []
+    for _ in range(P):
+        n = int(rs.randint(11, 40))
+        wh = rs.uniform(6, 40, (n, 2))
+        xy = rs.uniform(0, 1, (n, 2)) * (img - wh)
+        lab = np.zeros((n, 1))
+        lab[rs.permutation(n)[:3], 0] = [1, 2, 3]
+        rows.append(np.concatenate([xy, wh, lab], 1).astype(np.float32))
+    return u8, rows
+
+
+def seeded(cfg):
+    return weights.seeded_state_dict(77, logit_gain=2.0, **{k: v for k, v in cfg.items() if k != "drop_prob"})
+
+
+def five_steps(tr, ds):
+    losses = [tr.train_step(batch)[0] for batch in ds.batches(3, shuffle=True, sampling_fraction=0.9, seed=12, epoch=0)]
+    assert len(losses) == 5 and all(np.isfinite(float(x)) for x in losses)
+    return [float(x) for x in losses], tr.state_dict()
+
+
+def profiled(fn):
+    _lib.PROFILE = {n: [] for n in _lib.lib().fn}
+    try:
+        out = fn()
+        torch.cuda.synchronize()
+    finally:
+        prof, _lib.PROFILE = _lib.PROFILE, None
+    return out, {n: len(v) for n, v in prof.items() if v}
+
+
+@pytest.mark.parametrize("kw", [dict(), dict(optimizer="adamw", max_grad_norm=1.0,
+                                             param_groups=[dict(params="gat.attention_layer.", lr=5e-3, weight_decay=0.0)]),
+                                dict(optimizer="sgd", momentum=0.9, lr=1e-3)])
+def test_five_v2_steps_move_the_attention_vector_and_are_reproducible(kw):
+    u8, rows = page_set()
+    ds = DeviceDataset(u8, rows, 2, DEV, spatial_k=6)
+    sd = seeded(VCFG)
+    assert sd[AW].shape == (1, 32)
+    a, b = HotPathTrainer(VCFG, sd, DEV, **kw), HotPathTrainer(VCFG, sd, DEV, **kw)
+    assert a.params[AW].shape == (1, 32) and a.grads[AW].shape == (1, 32)
+    assert engine._adjacent(a.params["gat.W_i.weight"], a.params["gat.W_j.weight"])
+    assert engine._adjacent(a.grads["gat.W_i.weight"], a.grads["gat.W_j.weight"])
+    la, sa = five_steps(a, ds)
+    lb, sb = five_steps(b, ds)
+    assert la == lb and list(sa) == list(sb)
+    for key in sa:
+        assert torch.equal(sa[key], sb[key]), key
+    assert sa[AW].shape == (1, 32) and bool(torch.isfinite(sa[AW]).all())
+    assert bool((sa[AW].cpu() != sd[AW]).all())                                 # every channel has moved
+    assert not torch.equal(sa["gat.W_i.weight"].cpu(), sd["gat.W_i.weight"])
+    # checkpoint round trip: parameters, moments and step count into a fresh trainer, then one more identical step
+    c = HotPathTrainer(VCFG, sd, DEV, **kw)
+    c.load_state_dict(a.state_dict())
+    c.load_optimizer_state_dict(a.optimizer_state_dict())
+    batch = next(iter(ds.batches(3, prefetch=False)))
+    assert float(a.train_step(batch)[0]) == float(c.train_step(batch)[0])
+    assert torch.equal(a.pbucket.flat, c.pbucket.flat)
+    with pytest.raises(ValueError, match="attention"):                          # a static checkpoint names the mode
+        c.load_state_dict(seeded(CFG))
+
+
+def test_default_step_issues_none_of_the_new_launches_and_a_v2_step_none_of_the_static_ones():
+    u8, rows = page_set(P=3)
+    batch = next(iter(DeviceDataset(u8, rows, 2, DEV, spatial_k=6).batches(3, prefetch=False)))
+    _, plain = profiled(lambda: HotPathTrainer(CFG, seeded(CFG), DEV).train_step(batch))
+    assert not any(n in plain for n in NEW)
+    assert plain["cova_gat_fwd"] == 1 and plain["cova_gat_bwd"] == 1 and plain["cova_gat_transpose_reuse"] == 1
+    _, v2 = profiled(lambda: HotPathTrainer(VCFG, seeded(VCFG), DEV).train_step(batch))
+    assert v2["cova_gat2_fwd"] == 1 and v2["cova_gat2_bwd"] == 1
+    assert not any(n in v2 for n in ("cova_gat_fwd", "cova_gat_bwd", "cova_gat_fwd_edge", "cova_gat_bwd_edge"))
+    # everything around the head is the same list of launches, the projection and gradient GEMMs included
+    rest = lambda d: {k: v for k, v in d.items() if "gat_fwd" not in k and "gat_bwd" not in k and "gat2_" not in k}
+    assert rest(v2) == rest(plain)
+    cfg22 = dict(CFG, n_heads=2, n_gat_layers=2, edge_geometry=True)
+    _, e22 = profiled(lambda: HotPathTrainer(cfg22, seeded(cfg22), DEV).train_step(batch))
+    v22 = dict(cfg22, attention="gatv2")
+    _, g22 = profiled(lambda: HotPathTrainer(v22, seeded(v22), DEV).train_step(batch))
+    assert g22["cova_gat2_fwd"] == 4 and g22["cova_gat2_bwd"] == 4 and g22["cova_edge_geometry"] == 1
+    assert e22["cova_gat_fwd_edge"] == 4 and not any(n in e22 for n in NEW)
+    rest = lambda d: {k: v for k, v in d.items() if "gat_fwd" not in k and "gat_bwd" not in k and "gat2_" not in k
+                      and k != "cova_gat_edge_workspace_floats"}
+    assert rest(g22) == rest(e22)
+
+
+def test_evaluate_split_fit_from_a_feature_cache_and_attention_rows_with_the_option_on():
+    u8, rows = page_set(P=9, seed=4)
+    v8, vrows = page_set(P=11, seed=9)
+    train, val = DeviceDataset(u8, rows, 2, DEV, spatial_k=6), DeviceDataset(v8, vrows, 2, DEV, spatial_k=6)
+    cfg = dict(VCFG, edge_geometry=True)
+    sd = seeded(cfg)
+    sd["gat.edge_layer.weight"] = torch.from_numpy(EDGE_W).view(1, 8).clone()
+    tr = HotPathTrainer(cfg, sd, DEV, track_metrics=True, frozen=("convnet.",), bn_eval=("convnet.",))
+    rep = evaluate_split(tr, val, with_loss=True)
+    assert rep.evaluated.all() and rep.ranks.shape == (11, 3) and np.isfinite(rep.loss)
+    tcache, vcache = FeatureCache.build(tr, train), FeatureCache.build(tr, val)
+    cached, full = next(iter(val.batches(11, features=vcache))), next(iter(val.batches(11, prefetch=False)))
+    assert torch.equal(tr.predict(cached)[0], tr.predict(full)[0])
+    static = HotPathTrainer(dict(CFG, edge_geometry=True), seeded(dict(CFG, edge_geometry=True)), DEV)
+    assert not torch.equal(tr.predict(full)[0], static.predict(full)[0])
+    before = tr.params[AW].clone()
+    out = fit(tr, train, val, 1, 3, sampling_fraction=0.9, seed=12, eval_interval=1, train_features=tcache,
+              val_features=vcache)
+    assert len(out.history) == 1 and out.history[0]["eval_acc"] is not None and tr.step_count == 3
+    assert not torch.equal(tr.params[AW], before)
+    rows_out = attention_rows(tr, full)
+    K = full["context_indices"].shape[1]
+    assert rows_out.shape == (int((full["labels"] > 0).sum()), 5 + 5 * K) and bool(torch.isfinite(rows_out).all())
