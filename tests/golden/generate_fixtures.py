@@ -2,6 +2,7 @@
 """Generate tests/golden/*.npz by running the REFERENCE's own code (dev container only).
 
     python tests/golden/generate_fixtures.py        # needs /root/reference (read-only)
+    python tests/golden/generate_fixtures.py case_cova_cs0 case_cova_roi5_odd     # only these (the others stay byte-identical)
 
 The reference (pure Python) cannot travel to the GPU box, so its outputs are captured here
 as data.  ``/root/reference`` is put first on sys.path (its ``datasets.py`` would otherwise be
@@ -62,8 +63,8 @@ def build_ref_model(cfg, img_h, sd):
 
 
 def case_full_model(name, n_pages, img_h, boxes, cs, seed, hidden_dim=384, bbox_hidden_dim=32,
-                    n_additional_feat=0, logit_gain=8.0):
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=hidden_dim,
+                    n_additional_feat=0, logit_gain=8.0, roi=(3, 3), use_context=True):
+    cfg = dict(roi_output_size=tuple(roi), n_classes=4, use_context=use_context, hidden_dim=hidden_dim,
                bbox_hidden_dim=bbox_hidden_dim, n_additional_feat=n_additional_feat, drop_prob=0.0)
     wcfg = {k: cfg[k] for k in ("roi_output_size", "n_classes", "use_context", "hidden_dim",
                                 "bbox_hidden_dim", "n_additional_feat")}
@@ -74,7 +75,8 @@ def case_full_model(name, n_pages, img_h, boxes, cs, seed, hidden_dim=384, bbox_
            "meta/boxes": np.asarray(boxes if not np.isscalar(boxes) else [boxes] * n_pages),
            "meta/context_size": cs, "meta/seed": seed, "meta/hidden_dim": hidden_dim,
            "meta/bbox_hidden_dim": bbox_hidden_dim, "meta/n_additional_feat": n_additional_feat,
-           "meta/logit_gain": logit_gain}
+           "meta/logit_gain": logit_gain, "meta/roi_output_size": np.asarray(roi, dtype=np.int64),
+           "meta/use_context": np.bool_(use_context)}
     args = (batch["images"], batch["bboxes"], batch["additional_feats"], batch["context_indices"])
 
     # ---- eval mode (running statistics), the mode predictions are taken in (train.py:112)
@@ -85,12 +87,16 @@ def case_full_model(name, n_pages, img_h, boxes, cs, seed, hidden_dim=384, bbox_
         visual = m._get_visual_features(batch["images"], batch["bboxes"])
         bbf = m._get_bbox_features(batch["bboxes"])
         own = torch.cat((visual, bbf, m.bn_additional_feat(batch["additional_feats"])), dim=1)
-        hp, attn = m.gat(own, batch["context_indices"], return_attn_wts=True)
+        if use_context:
+            hp, attn = m.gat(own, batch["context_indices"], return_attn_wts=True)
+            hp, attn = hp.numpy(), attn.numpy()
+        else:                          # `--context_size 0` (main.py:58-59): the model has no GAT
+            hp, attn = np.zeros((0,), np.float32), np.zeros((0, 0), np.float32)
     out["eval/logits"] = logits.numpy()
     out["eval/visual_sample"] = visual.numpy().reshape(-1)[::7].copy()
     out["eval/bbox_feats"] = bbf.numpy()
-    out["eval/attn"] = attn.numpy()
-    out["eval/context_sample"] = hp.numpy().reshape(-1)[::5].copy()
+    out["eval/attn"] = attn
+    out["eval/context_sample"] = hp.reshape(-1)[::5].copy()
     out["eval/argmax"] = logits.argmax(dim=1).numpy()
     dec = []
     for index in torch.unique(batch["bboxes"][:, 0]).long():
@@ -100,6 +106,9 @@ def case_full_model(name, n_pages, img_h, boxes, cs, seed, hidden_dim=384, bbox_
 
     # ---- train mode (batch statistics), Dropout(p=0) == identity: forward, CE-sum, backward
     m = build_ref_model(cfg, img_h, sd)
+    ref_sd = m.state_dict()            # names and shapes of the reference's own state_dict: data
+    out["meta/state_keys"] = np.asarray(list(ref_sd.keys()))
+    out["meta/state_shapes"] = np.asarray([",".join(str(d) for d in v.shape) for v in ref_sd.values()])
     m.train()
     logits = m(*args)
     loss = torch.nn.CrossEntropyLoss(reduction="sum")(logits, batch["labels"])   # main.py:139
@@ -113,6 +122,29 @@ def case_full_model(name, n_pages, img_h, boxes, cs, seed, hidden_dim=384, bbox_
             out["buf/" + k] = b.detach().numpy()
     np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
     print(name, "loss", loss.item(), "bytes", os.path.getsize(os.path.join(HERE, name + ".npz")))
+
+
+def case_cova_roi1_bare():
+    """smallest model: T = n_vis = 64, decoder only, a one-box page"""
+    case_full_model("cova_roi1_bare", 2, 64, [13, 1], 0, seed=105, hidden_dim=0, bbox_hidden_dim=0, roi=(1, 1),
+                    use_context=False)
+
+
+def case_cova_cs0():
+    """the `-cs 0` ablation (main.py:58-59 passes hidden_dim=0) at the standard widths, T = 608"""
+    case_full_model("cova_cs0", 2, 64, [40, 25], 0, seed=106, hidden_dim=0, bbox_hidden_dim=32, use_context=False)
+
+
+def case_cova_roi2x3_cs1():
+    """non-square bins, K = 2"""
+    case_full_model("cova_roi2x3_cs1", 2, 64, [30, 9], 1, seed=107, hidden_dim=64, bbox_hidden_dim=16, roi=(2, 3))
+
+
+def case_cova_roi5_odd():
+    """n_vis = 1600, F = 1610, T = 1710: no row of the [N, T] matrix and none of its column blocks (at 1600, 1607,
+    1610) starts on a 16-byte boundary"""
+    case_full_model("cova_roi5_odd", 3, 128, [11, 70, 2], 3, seed=108, hidden_dim=100, bbox_hidden_dim=7,
+                    n_additional_feat=3, roi=(5, 5))
 
 
 def case_gat(name="gat_layer", seed=7, N=13, K=6, Fd=40, D=16):
@@ -291,3 +323,7 @@ if __name__ == "__main__":
     case_full_model("cova_h128_ragged", 3, 128, [11, 230, 47], 12, seed=103, hidden_dim=128)
     case_full_model("cova_h64_addfeat", 2, 64, [40, 25], 4, seed=104, hidden_dim=64,
                     n_additional_feat=6)
+    case_cova_roi1_bare()
+    case_cova_cs0()
+    case_cova_roi2x3_cs1()
+    case_cova_roi5_odd()

@@ -8,15 +8,20 @@ import cova_amd  # noqa: F401
 from cova_web_object_detection_amd import synthetic, weights
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-FULL_CASES = ["cova_h64_n11", "cova_h64_n90", "cova_h128_ragged", "cova_h64_addfeat"]
+FULL_CASES = ["cova_h64_n11", "cova_h64_n90", "cova_h128_ragged", "cova_h64_addfeat",
+              # other points of the reference's hyper-parameter space (--roi, --context_size 0, head widths, -cs 1):
+              "cova_roi1_bare", "cova_cs0", "cova_roi2x3_cs1", "cova_roi5_odd"]
 SAMPLE_STRIDE = 97
 
 
 def load_case(name):
-    """Golden fixture -> (fixture dict, cfg, state_dict, batch) with inputs regenerated from seeds."""
+    """Golden fixture -> (fixture dict, cfg, state_dict, batch) with inputs regenerated from seeds.  The first four
+    fixtures predate ``meta/roi_output_size`` and ``meta/use_context``: they are (3, 3) models with a GAT."""
     fx = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
     boxes = [int(b) for b in fx["meta/boxes"]]
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True,
+    roi = tuple(int(v) for v in fx["meta/roi_output_size"]) if "meta/roi_output_size" in fx else (3, 3)
+    use_context = bool(fx["meta/use_context"]) if "meta/use_context" in fx else True
+    cfg = dict(roi_output_size=roi, n_classes=4, use_context=use_context,
                hidden_dim=int(fx["meta/hidden_dim"]), bbox_hidden_dim=int(fx["meta/bbox_hidden_dim"]),
                n_additional_feat=int(fx["meta/n_additional_feat"]), drop_prob=0.0)
     wcfg = {k: v for k, v in cfg.items() if k != "drop_prob"}

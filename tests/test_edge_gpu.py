@@ -179,8 +179,15 @@ EDGE_W = np.asarray([1.5, -2.0, 0.75, -0.5, 3.0, -1.25, 2.0, 0.6], np.float32)
 
 @functools.lru_cache(maxsize=None)
 def gat_case(name):
-    rs = np.random.RandomState({"wide": 41, "general": 42, "hub": 43}[name])
-    if name == "wide":               # K <= 64, D = 6 x 64: the wide kernels; a hybrid graph over two pages
+    rs = np.random.RandomState({"wide": 41, "general": 42, "hub": 43, "k2": 44}[name])
+    if name == "k2":                 # `-cs 1` at hidden_dim 100 (the GAT of tests/golden/cova_roi5_odd at K = 2): ldw = 200,
+        from cova_web_object_detection_amd import synthetic      # pages of 11, 70 and 2 boxes, the DOM-order window
+        counts = [11, 70, 2]
+        N, D, K = sum(counts), 100, 2
+        bb, ps = as_batch([random_boxes(rs, n) for n in counts])
+        ctx = synthetic.collate_context([synthetic.context_window_indices(n, 1) for n in counts])
+        assert int((ctx[:, 1] == -1).sum()) == 2 * len(counts) and (ctx[:, 0] >= 0).all()
+    elif name == "wide":              # K <= 64, D = 6 x 64: the wide kernels; a hybrid graph over two pages
         N, D, K = 130, 384, 24
         bb, ps = as_batch([random_boxes(rs, 65), random_boxes(rs, 65)])
         ctx = GO.batch_graph(bb, ps, 6, 12)
@@ -215,7 +222,7 @@ def check_against(got, ref, what):
         assert errs[k] < 1e-4, (what, k, errs[k])
 
 
-@pytest.mark.parametrize("name", ["wide", "general", "hub"])
+@pytest.mark.parametrize("name", ["wide", "general", "hub", "k2"])
 def test_forward_and_backward_match_the_float64_oracle(name):
     case = gat_case(name)
     assert float(np.abs(case["ref"]["dew"]).min()) > 0
@@ -224,7 +231,7 @@ def test_forward_and_backward_match_the_float64_oracle(name):
     assert relerr(launch(case, None, edge=False)["attn"].cpu().numpy(), case["ref"]["attn"]) > 1e-3
 
 
-@pytest.mark.parametrize("name", ["wide", "general", "hub"])
+@pytest.mark.parametrize("name", ["wide", "general", "hub", "k2"])
 def test_zero_edge_weight_is_the_plain_layer_bit_for_bit(name):
     case = gat_case(name)
     zero = np.zeros(8, np.float32)

@@ -136,9 +136,9 @@ def page_set(P=8, seed=4, A=0):
     return make_pages(counts, seed, A)
 
 
-def dataset(pages):
+def dataset(pages, cs=CS):
     u8, rows, addl = pages
-    return DeviceDataset(u8, rows, CS, DEV, additional_feats=addl)
+    return DeviceDataset(u8, rows, cs, DEV, additional_feats=addl)
 
 
 def seeded(cfg=CFG, seed=77):
@@ -151,11 +151,17 @@ def frozen_trainer(cfg=CFG, **kw):
 
 
 # ---------------------------------------------------------------- 3. build equals the direct forward
-@pytest.mark.parametrize("extra", [{}, dict(roi_op="align"), dict(backbone_layers=2), dict(backbone="resnet50")],
-                         ids=["resnet18-pool", "align", "layer2", "resnet50"])
-def test_build_equals_the_direct_forward(monkeypatch, extra):
+# the configurations of tests/golden/cova_roi2x3_cs1 (non-square bins, n_vis = 384, K = 2) and cova_cs0 (no GAT, T = F = 608)
+ROI2X3_CS1 = dict(roi_output_size=(2, 3), hidden_dim=64, bbox_hidden_dim=16)
+CS0 = dict(use_context=False, hidden_dim=0, bbox_hidden_dim=32)
+
+
+@pytest.mark.parametrize("extra,cs", [({}, CS), (dict(roi_op="align"), CS), (dict(backbone_layers=2), CS),
+                                      (dict(backbone="resnet50"), CS), (ROI2X3_CS1, 1), (CS0, 0)],
+                         ids=["resnet18-pool", "align", "layer2", "resnet50", "roi2x3-cs1", "cs0-no-context"])
+def test_build_equals_the_direct_forward(monkeypatch, extra, cs):
     cfg = dict(CFG, **extra)
-    tr, ds = frozen_trainer(cfg), dataset(make_pages(COUNTS7, 11))
+    tr, ds = frozen_trainer(cfg), dataset(make_pages(COUNTS7, 11), cs)
     n_vis = engine.backbone_feat(cfg)
     batch = next(iter(ds.batches(7, prefetch=False)))
     seen = []
@@ -171,6 +177,14 @@ def test_build_equals_the_direct_forward(monkeypatch, extra):
         assert cache.table.shape == ref.shape and cache.nbytes == ref.numel() * 4
         assert torch.equal(cache.table, ref), bs
         cache.check(tr, ds)
+    # the forward from the cached visual features is the full forward, bit for bit
+    order = np.asarray([6, 2, 4, 1])
+    full = next(iter(ds.batches(4, order=order, prefetch=False)))
+    cached = next(iter(ds.batches(4, order=order, features=cache)))
+    assert "images" not in cached and tuple(full["context_indices"].shape) == ((COUNTS7[6] + COUNTS7[2] + COUNTS7[4] + 1,
+                                                                               2 * cs) if cfg["use_context"] else (0, 0))
+    assert torch.equal(tr.predict(cached)[0], tr.predict(full)[0])
+    assert torch.equal(tr.loss(cached), tr.loss(full))
 
 
 # ---------------------------------------------------------------- 4. cached steps equal recomputed steps

@@ -38,7 +38,10 @@ def nchw(x):   # NHWC gpu -> NCHW cpu
 
 @pytest.mark.parametrize("ta,tb", [(0, 0), (0, 1), (1, 0), (1, 1)])
 @pytest.mark.parametrize("M,N,K", [(64, 64, 16), (45, 70, 33), (130, 992, 608), (1, 5, 3), (1440, 976, 976), (976, 976, 1440),
-                                   (64, 64, 1028), (70, 33, 640), (132, 100, 612), (4, 4, 4), (68, 36, 36), (256, 192, 96), (2100, 2048, 72)])
+                                   (64, 64, 1028), (70, 33, 640), (132, 100, 612), (4, 4, 4), (68, 36, 36), (256, 192, 96), (2100, 2048, 72),
+                                   # decoder.1 of a model whose T = 1710 is no multiple of 4 (RoI 5x5, bbox_hidden_dim 7, three
+                                   # additional features, hidden_dim 100): no operand row is 16-byte aligned
+                                   (83, 1710, 1710)])
 def test_sgemm(ta, tb, M, N, K):
     g = torch.Generator().manual_seed(M * 131 + N * 7 + K)
     A = torch.randn((K, M) if ta else (M, K), generator=g)
@@ -54,6 +57,37 @@ def test_sgemm(ta, tb, M, N, K):
     assert torch.equal(C2, C)                                  # deterministic
     call("cova_sgemm", ta, tb, M, N, K, A.to(DEV), A.shape[1], B.to(DEV), B.shape[1], C, N + 3, None, 1)
     close(C[:, :N], 2 * ref - bias, 2e-5, "sgemm accumulate")
+
+
+@pytest.mark.parametrize("ta,tb", [(0, 0), (0, 1), (1, 0), (1, 1)])
+@pytest.mark.parametrize("M,N,K,pa,pb,pc,off", [(83, 100, 1610, 100, 0, 100, 0),      # GAT projection: h = comb[:, :1610], ld 1710
+                                                (100, 1610, 83, 100, 100, 0, 0),      # its weight gradient: dWh^T h
+                                                (83, 1610, 100, 100, 0, 100, 0),      # its input gradient into dcomb, ld 1710
+                                                (83, 100, 1610, 100, 3, 100, 1607)])  # the same at an odd column offset
+def test_sgemm_sub_matrix_operands_with_unaligned_rows(ta, tb, M, N, K, pa, pb, pc, off):
+    """cova_sgemm on operands that are column blocks of wider matrices whose rows are not 16-byte aligned (the [N, T]
+    feature matrix at T = 1710): every transposition form, with bias and accumulating, against float64; nothing outside
+    the written block is touched."""
+    g = torch.Generator().manual_seed(M * 131 + N * 7 + K + off)
+    ra, ca = (K, M) if ta else (M, K)
+    rb, cb = (N, K) if tb else (K, N)
+    Aw = torch.randn(ra, off + ca + pa, generator=g).to(DEV)
+    Bw = torch.randn(rb, off + cb + pb, generator=g).to(DEV)
+    A, B = Aw[:, off:off + ca], Bw[:, off:off + cb]
+    bias = torch.randn(N, generator=g)
+    ref = ((A.t() if ta else A).cpu().double() @ (B.t() if tb else B).cpu().double() + bias.double()).float()
+    ldc = off + N + pc
+    Cw = torch.full((M, ldc), 7.0, device=DEV)
+    C = Cw[:, off:off + N]
+    call("cova_sgemm", ta, tb, M, N, K, A, Aw.shape[1], B, Bw.shape[1], C, ldc, bias.to(DEV), 0)
+    close(C, ref, 2e-5, "sgemm views")
+    assert (Cw[:, :off] == 7.0).all() and (Cw[:, off + N:] == 7.0).all()
+    C2w = torch.full((M, ldc), 7.0, device=DEV)
+    call("cova_sgemm", ta, tb, M, N, K, A, Aw.shape[1], B, Bw.shape[1], C2w[:, off:off + N], ldc, bias.to(DEV), 0)
+    assert torch.equal(C2w, Cw)                                # deterministic
+    call("cova_sgemm", ta, tb, M, N, K, A, Aw.shape[1], B, Bw.shape[1], C, ldc, None, 1)
+    close(C, 2 * ref - bias, 2e-5, "sgemm views accumulate")
+    assert (Cw[:, :off] == 7.0).all() and (Cw[:, off + N:] == 7.0).all()
 
 
 @pytest.mark.parametrize("ta,tb", [(0, 0), (0, 1), (1, 0), (1, 1)])
@@ -152,7 +186,10 @@ def test_batchnorm_train_fwd_bwd(R, C, relu, res):
                                                # 16-byte aligned rows: the float4 kernels (3 / 6 / 8 rows per thread; a
                                                # ragged last column block; no ReLU / no Dropout forms)
                                                (1440, 976, 1, 1, 8), (300, 64, 1, 1, 4), (77, 16, 1, 0, 0), (1440, 32, 1, 0, 8),
-                                               (2880, 100, 1, 1, 4), (3500, 36, 0, 1, 0), (1537, 12, 0, 0, 4)])
+                                               (2880, 100, 1, 1, 4), (3500, 36, 0, 1, 0), (1537, 12, 0, 0, 4),
+                                               # decoder.2 of whole models: T = 1710 (rows 8 bytes off a 16-byte boundary),
+                                               # with and without Dropout; the smallest model, 14 boxes at T = 64
+                                               (83, 1710, 1, 1, 0), (83, 1710, 1, 0, 0), (14, 64, 1, 0, 0), (14, 64, 1, 1, 0)])
 def test_batchnorm1d_single_launch_fwd_bwd(R, C, relu, drop, pad):
     """cova_bn1d_fwd / cova_bn1d_bwd (statistics + finalize + apply, with the Dropout behind the layer and the column sums
     of dz riding along) against torch autograd on the CPU, and against the separate-launch path they replace."""

@@ -82,15 +82,22 @@ def test_full_model_matches_reference_fixture(name):
     with torch.no_grad():
         logits = m(*args)
         visual = m._get_visual_features(args[0], args[1])
-        bbf = m._get_bbox_features(args[1])
-        own = torch.cat((visual, bbf, m.bn_additional_feat(args[2])), dim=1)
-        hp, attn = m.gat(own, args[3], return_attn_wts=True)
+        bbf = m._get_bbox_features(args[1])                 # [N, 0] without a positional encoder (models.py:129-131)
+        if cfg["use_context"]:
+            own = torch.cat((visual, bbf, m.bn_additional_feat(args[2])), dim=1)
+            hp, attn = m.gat(own, args[3], return_attn_wts=True)
     err = relerr(logits.cpu(), fx["eval/logits"])
+    print("%s: eval logits %.2e of the logit scale" % (name, err))
     assert err < LOGIT_TOL, err
     assert relerr(visual.cpu().numpy().reshape(-1)[::7], fx["eval/visual_sample"]) < LOGIT_TOL
-    assert relerr(bbf.cpu(), fx["eval/bbox_feats"]) < LOGIT_TOL
-    assert relerr(attn.cpu(), fx["eval/attn"]) < LOGIT_TOL
-    assert relerr(hp.cpu().numpy().reshape(-1)[::5], fx["eval/context_sample"]) < LOGIT_TOL
+    assert tuple(bbf.shape) == tuple(fx["eval/bbox_feats"].shape)
+    if cfg["bbox_hidden_dim"] > 0:
+        assert relerr(bbf.cpu(), fx["eval/bbox_feats"]) < LOGIT_TOL
+    if cfg["use_context"]:
+        assert relerr(attn.cpu(), fx["eval/attn"]) < LOGIT_TOL
+        assert relerr(hp.cpu().numpy().reshape(-1)[::5], fx["eval/context_sample"]) < LOGIT_TOL
+    else:                                                   # `--context_size 0`: no GAT to compare
+        assert not hasattr(m, "gat") and fx["eval/attn"].size == 0 and fx["eval/context_sample"].size == 0
     ref_logits = torch.from_numpy(fx["eval/logits"])
     tol = 10 * max(err, 1e-6) * float(ref_logits.abs().max())
     ok = margins_ok(ref_logits, tol)
@@ -101,6 +108,9 @@ def test_full_model_matches_reference_fixture(name):
     for p, row in enumerate(fx["eval/page_class_top1"]):
         o = ref_logits[batch["bboxes"][:, 0] == p]
         for c in range(o.shape[1]):
+            if o.shape[0] == 1:                              # a one-box page: no runner-up, the decision is that box
+                assert int(dec[p][0, c]) == int(row[c]) == 0
+                continue
             top2 = torch.topk(o[:, c], 2).values
             if (top2[0] - top2[1]) > tol:
                 assert int(dec[p][0, c]) == int(row[c])
@@ -111,7 +121,10 @@ def test_full_model_matches_reference_fixture(name):
     routing = routing_from_saved(logits.grad_fn.sv)      # the HIP forward's max-pool / RoIPool routing
     loss = torch.nn.CrossEntropyLoss(reduction="sum")(logits, batch["labels"].to(DEV))
     loss.backward()
-    assert relerr(logits.detach().cpu(), fx["train/logits"]) < LOGIT_TOL
+    terr = relerr(logits.detach().cpu(), fx["train/logits"])
+    print("%s: train logits %.2e of the logit scale, loss %.2e relative" % (
+        name, terr, abs(loss.item() - float(fx["train/loss"])) / abs(float(fx["train/loss"]))))
+    assert terr < LOGIT_TOL
     assert abs(loss.item() - float(fx["train/loss"])) <= LOSS_TOL * abs(float(fx["train/loss"]))
     grads = {k: p.grad for k, p in m.named_parameters()}
     # (1) the tight check: everything against the oracle forced to the HIP forward's discrete decisions (max-pool /
@@ -120,8 +133,9 @@ def test_full_model_matches_reference_fixture(name):
     b = batch
     _, _, grads_ref, after, inter = O.loss_and_grads(sd, b["images"], b["bboxes"], b["additional_feats"],
                                                      b["context_indices"], b["labels"], cfg, None, routing)
-    compare_grads(grads, grads_ref, rtol=GRAD_TOL, outlier_frac=0.0)
-    assert_routing_near_ties(routing, inter, b["bboxes"], (3, 3), m.roi_pool.spatial_scale)
+    worst_forced = compare_grads(grads, grads_ref, rtol=GRAD_TOL, outlier_frac=0.0)
+    print("%s: worst gradient against the forced oracle %s %.2e of its scale" % ((name,) + worst_forced))
+    assert_routing_near_ties(routing, inter, b["bboxes"], cfg["roi_output_size"], m.roi_pool.spatial_scale)
     # ... and the decisions that were forced are the oracle's own, up to pre-activations within round-off of
     # zero / exact ties: counted and bounded against the UNFORCED oracle
     tap = {}

@@ -99,7 +99,10 @@ def test_full_model_oracle_matches_reference(name):
         logits, inter = O.forward(O.clone_state_dict(sd), *args, cfg, False, None, True)
     assert np.allclose(logits.numpy(), fx["eval/logits"], atol=1e-5, rtol=1e-5)
     assert np.array_equal(logits.argmax(1).numpy(), fx["eval/argmax"])
-    assert np.allclose(inter["attn"].numpy(), fx["eval/attn"], atol=1e-6, rtol=1e-5)
+    if cfg["use_context"]:
+        assert np.allclose(inter["attn"].numpy(), fx["eval/attn"], atol=1e-6, rtol=1e-5)
+    else:                                                    # `--context_size 0`: the reference model has no GAT
+        assert "attn" not in inter and fx["eval/attn"].size == 0 and not any(k.startswith("gat.") for k in sd)
     assert np.allclose(inter["visual"].numpy().reshape(-1)[::7], fx["eval/visual_sample"], atol=1e-6)
     top1 = np.stack([v.numpy()[0] for _, v in sorted(O.page_class_decisions(logits, batch["bboxes"]).items())])
     assert np.array_equal(top1, fx["eval/page_class_top1"])
@@ -109,6 +112,26 @@ def test_full_model_oracle_matches_reference(name):
     check_grads(fx, grads, rtol=1e-3)
     for k in [k for k in fx if k.startswith("buf/")]:
         assert np.allclose(after[k[4:]].numpy(), fx[k], atol=1e-6, rtol=1e-5), k
+
+
+SPEC_CASES = [n for n in FULL_CASES if "meta/state_keys" in np.load(GOLDEN + "/%s.npz" % n).files]
+
+
+@pytest.mark.parametrize("name", SPEC_CASES)
+def test_state_dict_spec_is_the_reference_models_state_dict(name):
+    """weights.state_dict_spec(**cfg) against the names, order and shapes of the reference CoVA's own state_dict() at
+    that configuration (recorded by tests/golden/generate_fixtures.py): other RoI sizes, no GAT, odd head widths."""
+    fx, cfg, sd, _ = load_case(name)
+    spec = weights.state_dict_spec(**{k: v for k, v in cfg.items() if k != "drop_prob"})
+    assert [k for k, _ in spec] == [str(k) for k in fx["meta/state_keys"]]
+    shapes = [tuple(int(d) for d in str(s).split(",") if d) for s in fx["meta/state_shapes"]]
+    assert [tuple(s) for _, s in spec] == shapes
+    assert list(sd) == [k for k, _ in spec] and [tuple(v.shape) for v in sd.values()] == shapes
+    assert any(k.startswith("gat.") for k, _ in spec) == cfg["use_context"]
+
+
+def test_every_new_model_fixture_carries_the_reference_state_dict():
+    assert {"cova_roi1_bare", "cova_cs0", "cova_roi2x3_cs1", "cova_roi5_odd"} <= set(SPEC_CASES)
 
 
 def test_collate_restatement_matches_reference_on_raw_inputs():
