@@ -343,6 +343,8 @@ COVA_API int cova_conv_nhwc_fwd(const float *in, const float *w_fwd, float *out,
     hipStream_t stream = (hipStream_t)stream_;
     COVA_REQUIRE(in != nullptr && w_fwd != nullptr && out != nullptr && B >= 0 && H > 0 && W > 0);
     COVA_REQUIRE(shape_ok(Ci, Co, k, stride, pad));
+    // (integer division truncates towards zero: a map smaller than the kernel would pass as Ho = 1 at stride 2)
+    COVA_REQUIRE(H + 2 * pad >= k && W + 2 * pad >= k);
     const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
     COVA_REQUIRE(Ho > 0 && Wo > 0);
     if (B == 0) return COVA_OK;
@@ -364,6 +366,8 @@ COVA_API int cova_conv_nhwc_dgrad(const float *dy, const float *w_dgrad, const f
     COVA_REQUIRE(dy != nullptr && w_dgrad != nullptr && dx != nullptr && B >= 0 && H > 0 && W > 0);
     COVA_REQUIRE(shape_ok(Ci, Co, k, stride, pad));
     COVA_REQUIRE((dy2 == nullptr) == (w2_dgrad == nullptr));
+    // (integer division truncates towards zero: a map smaller than the kernel would pass as Ho = 1 at stride 2)
+    COVA_REQUIRE(H + 2 * pad >= k && W + 2 * pad >= k);
     const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
     COVA_REQUIRE(Ho > 0 && Wo > 0);
     // the second source is a 1x1 pad-0 convolution of the same stride: same output grid
@@ -412,6 +416,8 @@ COVA_API int cova_conv_nhwc_wgrad(const float *in, const float *dy, float *dw /*
     hipStream_t stream = (hipStream_t)stream_;
     COVA_REQUIRE(in != nullptr && dy != nullptr && dw != nullptr && ws != nullptr && B >= 0 && H > 0 && W > 0);
     COVA_REQUIRE(shape_ok(Ci, Co, k, stride, pad) && Co % WG_COLS == 0);
+    // (integer division truncates towards zero: a map smaller than the kernel would pass as Ho = 1 at stride 2)
+    COVA_REQUIRE(H + 2 * pad >= k && W + 2 * pad >= k);
     const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
     COVA_REQUIRE(Ho > 0 && Wo > 0);
     const int K = k * k * Ci;

@@ -2,7 +2,9 @@
 
 Kernel level: every entry point of csrc/conv_nhwc.hip (forward, data gradient, weight gradient of the 3x3 s2 64->128,
 3x3 s1 128->128 and 1x1 s2 64->128 convolutions) against float64 torch on the CPU, with an error no larger than that of
-a plain f32 multiply-add loop over the same operands, and bit-reproducible.  Module level: logits and every parameter
+a plain f32 multiply-add loop over the same operands, and bit-reproducible (every launch path of the contract, bit for
+bit on integer probes: tests/test_nhwc_paths_gpu.py).  Module level (square pages, a non-square page with an odd layer1
+map, a one-page batch): logits and every parameter
 gradient against the oracle composed in tests/layer2_oracle.py, with the HIP forward's discrete decisions forced into
 the oracle's backward as in tests/test_model_gpu.py.  Trainer and fine-tuning: Adam trajectory, reruns, launch counts."""
 import pytest
@@ -148,12 +150,13 @@ def test_stride2_dgrad_joins_the_downsample(B, H, W):
 
 
 # ----------------------------------------------------------------------------------------------------- module level
-def setup(img_h=64, roi_op="pool", seed=11, boxes=(13, 7)):
+def setup(img_h=64, roi_op="pool", seed=11, boxes=(13, 7), img_w=None):
     cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=48, bbox_hidden_dim=16,
                n_additional_feat=0, drop_prob=0.0)
     sd = weights.seeded_state_dict(seed, logit_gain=2.0, backbone_layers=2,
                                    **{k: v for k, v in cfg.items() if k != "drop_prob"})
-    batch = synthetic.make_batch(len(boxes), img_h=img_h, boxes_per_page=list(boxes), context_size=3, seed=seed + 1)
+    batch = synthetic.make_batch(len(boxes), img_h=img_h, img_w=img_w, boxes_per_page=list(boxes), context_size=3,
+                                 seed=seed + 1)
     m = CoVA((3, 3), img_h, 4, True, 48, 16, 0, 0.0, None, roi_op=roi_op, backbone_layers=2)
     m.load_state_dict(sd, strict=True)
     return dict(cfg, roi_op=roi_op), sd, batch, m.to(DEV)
@@ -169,9 +172,9 @@ def full_routing(sv, align):
     return r
 
 
-def module_case(monkeypatch, img_h, roi_op="pool", train=True, prepare=None, want_dimg=False):
+def module_case(monkeypatch, img_h, roi_op="pool", train=True, prepare=None, want_dimg=False, img_w=None, boxes=(13, 7)):
     L2O.patch(monkeypatch)
-    cfg, sd, batch, m = setup(img_h, roi_op)
+    cfg, sd, batch, m = setup(img_h, roi_op, boxes=boxes, img_w=img_w)
     m.train(train)
     if prepare is not None:
         prepare(m)
@@ -213,6 +216,21 @@ def module_case(monkeypatch, img_h, roi_op="pool", train=True, prepare=None, wan
 @pytest.mark.parametrize("train", [True, False])
 def test_module_matches_composed_oracle(monkeypatch, img_h, train):
     module_case(monkeypatch, img_h, train=train)
+
+
+@pytest.mark.parametrize("train", [True, False])
+def test_module_non_square_page_with_an_odd_layer1_map(monkeypatch, train):
+    """100 x 132 pixels: layer1's map is 25 x 33, odd on both sides (the four parity classes of the stride-2 data gradient
+    differ in size), layer2's 13 x 17"""
+    assert L2O.dummy_forward_size(100, 132) == (13, 17)
+    m, batch, _ = module_case(monkeypatch, 100, train=train, img_w=132)
+    assert batch["images"].shape == (2, 3, 100, 132)
+
+
+@pytest.mark.parametrize("train", [True, False])
+def test_module_one_page_batch(monkeypatch, train):
+    m, batch, _ = module_case(monkeypatch, 64, train=train, boxes=(17,))
+    assert batch["images"].shape[0] == 1
 
 
 def test_module_images_grad(monkeypatch):
