@@ -79,5 +79,22 @@ __device__ __forceinline__ float hash_uniform(unsigned long long seed, unsigned 
     return (float)(hash_mix64(seed, idx) >> 40) * (1.0f / 16777216.0f);   // 24 random bits -> [0,1)
 }
 
+// Attention dropout of the graph-attention kernels (roi_gat.hip, gat_v2.hip): rate p, inv = 1.f / (1.f - p), stream seed.
+// Slot e = i*K + k of the neighbour table is kept when its uniform is >= p (the convention of dropout_fwd_kernel); no mask
+// is stored, every kernel that needs it calls gat_dropped() on the same (seed, e).
+struct GatDrop {
+    float p, inv;
+    unsigned long long seed;
+};
+
+static inline GatDrop gat_drop_of(float p, unsigned long long seed) { return GatDrop{p, 1.f / (1.f - p), seed}; }
+
+// v * inv on a kept slot, 0 on a dropped one: ONE rounded f32 multiply (never contracted into a neighbouring add), so the
+// forward and both sides of the backward form the same dropped weight bit for bit
+__device__ __forceinline__ float gat_dropped(const GatDrop &dr, size_t e, float v)
+{
+    return hash_uniform(dr.seed, e) >= dr.p ? __fmul_rn(v, dr.inv) : 0.f;
+}
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline long long cdivll(long long a, long long b) { return (a + b - 1) / b; }

@@ -58,11 +58,13 @@ __device__ __forceinline__ float gat2_edge_term(const float *__restrict__ phi, s
 }
 
 // ------------------------------------------------------------------------------------------------ forward
-template <int NC, int V, bool EDGE>
+// DROP (all three kernels): attention dropout (common.h, GatDrop) -- attn keeps the softmax output, the aggregation and the
+// destination side weigh with gat_dropped(e, attn[e]), the source side scales dattn by keep * inv before the softmax backward.
+template <int NC, int V, bool EDGE, bool DROP = false>
 __global__ __launch_bounds__(256) void gat2_fwd_kernel(
     const float *__restrict__ Wh, int ldw, const float *__restrict__ att_w, const float *__restrict__ att_b,
     const int64_t *__restrict__ ctx, const float *__restrict__ phi, const float *__restrict__ edge_w, int N, int K, int D,
-    float slope, float *__restrict__ attn, float *__restrict__ hprime, int ldh)
+    float slope, float *__restrict__ attn, float *__restrict__ hprime, int ldh, GatDrop dr = GatDrop{})
 {
     constexpr int U = gat2_unroll<NC, V>();
     __shared__ float s_e[4][COVA_GAT_MAX_K];
@@ -153,6 +155,7 @@ __global__ __launch_bounds__(256) void gat2_fwd_kernel(
             const float alpha = se[p0 + lane] / denom;
             attn[(size_t)n * K + p0 + lane] = alpha;
             aw = j >= 0 ? alpha : 0.f;                         // pads: no weight, no row read
+            if (DROP && j >= 0) aw = gat_dropped(dr, (size_t)n * K + p0 + lane, alpha);    // (dropped slots: no row read)
         }
         const int jj = (int)j;
         for (int q0 = 0; q0 < cnt; q0 += U) {
@@ -193,11 +196,12 @@ __global__ __launch_bounds__(256) void gat2_fwd_kernel(
 // sum_k du[k] * lrelu(z[i,k,d]) (d_att_w), sum_k du[k] (d_att_b), sum_k du[k] * phi[i,k,:] (d_edge_w).  The four nodes of a
 // block are added in wave order and written as row blockIdx.x of the workspace: [0,D) d_att_w, D d_att_b, D+1 .. D+8
 // d_edge_w (row length P = D + 9); gat2_fold_kernel adds the rows.
-template <int NC, int V, bool EDGE>
+template <int NC, int V, bool EDGE, bool DROP = false>
 __global__ __launch_bounds__(256) void gat2_bwd_src_kernel(
     const float *__restrict__ g, int ldg, const float *__restrict__ Wh, int ldw, const float *__restrict__ attn,
     const int64_t *__restrict__ ctx, const float *__restrict__ att_w, const float *__restrict__ phi, int N, int K, int D,
-    float slope, float *__restrict__ dWh, int lddw, float *__restrict__ du_out, float *__restrict__ ws)
+    float slope, float *__restrict__ dWh, int lddw, float *__restrict__ du_out, float *__restrict__ ws,
+    GatDrop dr = GatDrop{})
 {
     constexpr int U = gat2_unroll<NC, V>();
     constexpr int ROW = NC * V * 64;                           // channels a wave covers
@@ -269,6 +273,7 @@ __global__ __launch_bounds__(256) void gat2_bwd_src_kernel(
                     if (lane == q0 + u) dalpha = tot;
                 }
             }
+            if (DROP && jj >= 0) dalpha = gat_dropped(dr, (size_t)n * K + p0 + lane, dalpha);
             sk[p0 + lane] = dalpha;
             float prod = alpha * dalpha;
             ad += prod;
@@ -374,11 +379,12 @@ __global__ __launch_bounds__(256) void gat2_bwd_src_kernel(
 // ------------------------------------------------------------------------------------------------ backward, destination side
 // One wave per node j over row j of the transposed index (flat slots e = i*K + k naming j, ascending):
 // dWh[j, D+d] = sum_e ( attn[e] * g[i_e, d] + du[e] * a[d] * gate(Wh[i_e, d] + Wh[j, D+d]) ); in-degree 0 writes zeros.
-template <int NC, int V>
+template <int NC, int V, bool DROP = false>
 __global__ __launch_bounds__(256) void gat2_bwd_dst_kernel(
     const float *__restrict__ g, int ldg, const float *__restrict__ Wh, int ldw, const float *__restrict__ attn,
     const float *__restrict__ du, const int *__restrict__ row_ptr, const int *__restrict__ edges,
-    const float *__restrict__ att_w, int N, int K, int D, float slope, float *__restrict__ dWh, int lddw)
+    const float *__restrict__ att_w, int N, int K, int D, float slope, float *__restrict__ dWh, int lddw,
+    GatDrop dr = GatDrop{})
 {
     constexpr int U = gat2_unroll<NC, V>();
     const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -401,7 +407,8 @@ __global__ __launch_bounds__(256) void gat2_bwd_dst_kernel(
     for (int c0 = 0; c0 < deg; c0 += 64) {
         const int cnt = min(64, deg - c0);
         const int e = lane < cnt ? edges[lo + c0 + lane] : 0;
-        const float al = lane < cnt ? attn[e] : 0.f;
+        float al = lane < cnt ? attn[e] : 0.f;
+        if (DROP && lane < cnt) al = gat_dropped(dr, (size_t)e, al);
         const float de = lane < cnt ? du[e] : 0.f;
         for (int q0 = 0; q0 < cnt; q0 += U) {
             bool on[U];
@@ -505,9 +512,11 @@ inline int gat2_chunks(int D, int V)
         }                                                                                                           \
     } while (0)
 
-COVA_API int cova_gat2_fwd(const float *Wh, int ldw, const float *att_w, const float *att_b, const int64_t *ctx,
-                           const float *phi, const float *edge_w, int N, int K, int D, float slope, float *attn,
-                           float *hprime, int ldh, void *stream)
+namespace {
+template <bool DROP>
+int gat2_fwd_launch(const float *Wh, int ldw, const float *att_w, const float *att_b, const int64_t *ctx,
+                    const float *phi, const float *edge_w, int N, int K, int D, float slope, float *attn,
+                    float *hprime, int ldh, void *stream, GatDrop dr = GatDrop{})
 {
     COVA_REQUIRE(N >= 0 && K > 0 && K <= COVA_GAT_MAX_K && D > 0 && ldw >= 2 * D && ldh >= D);
     COVA_REQUIRE((phi == nullptr) == (edge_w == nullptr) && (phi == nullptr || aligned16(phi)));
@@ -520,15 +529,34 @@ COVA_API int cova_gat2_fwd(const float *Wh, int ldw, const float *att_w, const f
     hipStream_t st = (hipStream_t)stream;
 #define COVA_GAT2_FWD(NC, V)                                                                                        \
     do {                                                                                                            \
-        if (phi) hipLaunchKernelGGL((gat2_fwd_kernel<NC, V, true>), grid, blk, 0, st, Wh, ldw, att_w, att_b, ctx, phi, \
-                                    edge_w, N, K, D, slope, attn, hprime, ldh);                                     \
-        else hipLaunchKernelGGL((gat2_fwd_kernel<NC, V, false>), grid, blk, 0, st, Wh, ldw, att_w, att_b, ctx, phi,  \
-                                edge_w, N, K, D, slope, attn, hprime, ldh);                                         \
+        if (phi) hipLaunchKernelGGL((gat2_fwd_kernel<NC, V, true, DROP>), grid, blk, 0, st, Wh, ldw, att_w, att_b, ctx, \
+                                    phi, edge_w, N, K, D, slope, attn, hprime, ldh, dr);                            \
+        else hipLaunchKernelGGL((gat2_fwd_kernel<NC, V, false, DROP>), grid, blk, 0, st, Wh, ldw, att_w, att_b, ctx, \
+                                phi, edge_w, N, K, D, slope, attn, hprime, ldh, dr);                                \
     } while (0)
     COVA_GAT2_DISPATCH(v4, nc, COVA_GAT2_FWD);
 #undef COVA_GAT2_FWD
     COVA_LAUNCH_CHECK();
     return COVA_OK;
+}
+}  // namespace
+
+COVA_API int cova_gat2_fwd(const float *Wh, int ldw, const float *att_w, const float *att_b, const int64_t *ctx,
+                           const float *phi, const float *edge_w, int N, int K, int D, float slope, float *attn,
+                           float *hprime, int ldh, void *stream)
+{
+    return gat2_fwd_launch<false>(Wh, ldw, att_w, att_b, ctx, phi, edge_w, N, K, D, slope, attn, hprime, ldh, stream);
+}
+
+// cova_gat2_fwd with attention dropout: slot e = i*K + k is kept when hash_uniform(seed, e) >= p and
+// then weighs attn * 1/(1-p) in h'; attn stays the softmax output.  p in [0, 1).
+COVA_API int cova_gat2_fwd_drop(const float *Wh, int ldw, const float *att_w, const float *att_b, const int64_t *ctx,
+                                const float *phi, const float *edge_w, int N, int K, int D, float slope, float p,
+                                unsigned long long seed, float *attn, float *hprime, int ldh, void *stream)
+{
+    COVA_REQUIRE(p >= 0.f && p < 1.f);                         // (NaN fails both)
+    return gat2_fwd_launch<true>(Wh, ldw, att_w, att_b, ctx, phi, edge_w, N, K, D, slope, attn, hprime, ldh, stream,
+                                 gat_drop_of(p, seed));
 }
 
 // floats of cova_gat2_bwd's workspace: one row of D + 9 partial sums per block of four nodes
@@ -539,10 +567,12 @@ COVA_API int cova_gat2_workspace_floats(int N, int K, int D)
     return n > 0x7fffffffLL ? -1 : (int)n;
 }
 
-COVA_API int cova_gat2_bwd(const float *g, int ldg, const float *Wh, int ldw, const float *attn, const int64_t *ctx,
-                           const float *att_w, const float *phi, const float *edge_w, int N, int K, int D, float slope,
-                           float *dWh, int lddw, float *d_att_w, float *d_att_b, float *d_edge_w, const int *csr,
-                           float *du, float *workspace, void *stream)
+namespace {
+template <bool DROP>
+int gat2_bwd_launch(const float *g, int ldg, const float *Wh, int ldw, const float *attn, const int64_t *ctx,
+                    const float *att_w, const float *phi, const float *edge_w, int N, int K, int D, float slope,
+                    float *dWh, int lddw, float *d_att_w, float *d_att_b, float *d_edge_w, const int *csr,
+                    float *du, float *workspace, void *stream, GatDrop dr = GatDrop{})
 {
     COVA_REQUIRE(N >= 0 && K > 0 && K <= COVA_GAT_MAX_K && D > 0 && ldg >= D && ldw >= 2 * D && lddw >= 2 * D);
     COVA_REQUIRE((phi == nullptr) == (edge_w == nullptr) && (phi == nullptr) == (d_edge_w == nullptr) &&
@@ -558,12 +588,12 @@ COVA_API int cova_gat2_bwd(const float *g, int ldg, const float *Wh, int ldw, co
     hipStream_t st = (hipStream_t)stream;
 #define COVA_GAT2_BWD(NC, V)                                                                                        \
     do {                                                                                                            \
-        if (phi) hipLaunchKernelGGL((gat2_bwd_src_kernel<NC, V, true>), grid, blk, 0, st, g, ldg, Wh, ldw, attn, ctx, \
-                                    att_w, phi, N, K, D, slope, dWh, lddw, du, workspace);                          \
-        else hipLaunchKernelGGL((gat2_bwd_src_kernel<NC, V, false>), grid, blk, 0, st, g, ldg, Wh, ldw, attn, ctx,   \
-                                att_w, phi, N, K, D, slope, dWh, lddw, du, workspace);                              \
-        hipLaunchKernelGGL((gat2_bwd_dst_kernel<NC, V>), grid, blk, 0, st, g, ldg, Wh, ldw, attn, du, csr,          \
-                           csr + N + 1, att_w, N, K, D, slope, dWh, lddw);                                          \
+        if (phi) hipLaunchKernelGGL((gat2_bwd_src_kernel<NC, V, true, DROP>), grid, blk, 0, st, g, ldg, Wh, ldw, attn, \
+                                    ctx, att_w, phi, N, K, D, slope, dWh, lddw, du, workspace, dr);                 \
+        else hipLaunchKernelGGL((gat2_bwd_src_kernel<NC, V, false, DROP>), grid, blk, 0, st, g, ldg, Wh, ldw, attn,  \
+                                ctx, att_w, phi, N, K, D, slope, dWh, lddw, du, workspace, dr);                     \
+        hipLaunchKernelGGL((gat2_bwd_dst_kernel<NC, V, DROP>), grid, blk, 0, st, g, ldg, Wh, ldw, attn, du, csr,    \
+                           csr + N + 1, att_w, N, K, D, slope, dWh, lddw, dr);                                      \
     } while (0)
     COVA_GAT2_DISPATCH(v4, nc, COVA_GAT2_BWD);
 #undef COVA_GAT2_BWD
@@ -573,4 +603,26 @@ COVA_API int cova_gat2_bwd(const float *g, int ldg, const float *Wh, int ldw, co
                        d_att_w, d_att_b, d_edge_w);
     COVA_LAUNCH_CHECK();
     return COVA_OK;
+}
+}  // namespace
+
+COVA_API int cova_gat2_bwd(const float *g, int ldg, const float *Wh, int ldw, const float *attn, const int64_t *ctx,
+                           const float *att_w, const float *phi, const float *edge_w, int N, int K, int D, float slope,
+                           float *dWh, int lddw, float *d_att_w, float *d_att_b, float *d_edge_w, const int *csr,
+                           float *du, float *workspace, void *stream)
+{
+    return gat2_bwd_launch<false>(g, ldg, Wh, ldw, attn, ctx, att_w, phi, edge_w, N, K, D, slope, dWh, lddw, d_att_w,
+                                  d_att_b, d_edge_w, csr, du, workspace, stream);
+}
+
+// cova_gat2_bwd behind cova_gat2_fwd_drop: the same (p, seed) regenerate the mask on both sides
+COVA_API int cova_gat2_bwd_drop(const float *g, int ldg, const float *Wh, int ldw, const float *attn, const int64_t *ctx,
+                                const float *att_w, const float *phi, const float *edge_w, int N, int K, int D,
+                                float slope, float p, unsigned long long seed, float *dWh, int lddw, float *d_att_w,
+                                float *d_att_b, float *d_edge_w, const int *csr, float *du, float *workspace,
+                                void *stream)
+{
+    COVA_REQUIRE(p >= 0.f && p < 1.f);
+    return gat2_bwd_launch<true>(g, ldg, Wh, ldw, attn, ctx, att_w, phi, edge_w, N, K, D, slope, dWh, lddw, d_att_w,
+                                 d_att_b, d_edge_w, csr, du, workspace, stream, gat_drop_of(p, seed));
 }

@@ -656,12 +656,13 @@ __device__ __forceinline__ float gat_edge_term(const float *__restrict__ phi, si
 // KP = number of 64-slot passes a wave makes over the K neighbour slots (K <= 64 KP; KP = 1 is the reference's usual
 // range, -cs <= 32); slot k lives in lane k & 63 of pass k >> 6.  models.py:171-177 accepts any n_context.
 // EDGE: the pre-activation of a slot also takes gat_edge_term (phi [N,K,8], edge_w [8]); false reads neither pointer.
-template <int KP, bool EDGE = false>
+// DROP: attention dropout (common.h, GatDrop) -- attn keeps the softmax output, the aggregation weighs with gat_dropped().
+template <int KP, bool EDGE = false, bool DROP = false>
 __global__ __launch_bounds__(256) void gat_fwd_kernel(
     const float *__restrict__ Wh, int ldw, const float *__restrict__ s, const float *__restrict__ t,
     const int64_t *__restrict__ ctx, int N, int K, int D, float slope, float *__restrict__ attn,
     float *__restrict__ hprime, int ldh, const float *__restrict__ phi = nullptr,
-    const float *__restrict__ edge_w = nullptr)
+    const float *__restrict__ edge_w = nullptr, GatDrop dr = GatDrop{})
 {
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (n >= N) return;
@@ -698,6 +699,7 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(
         const float alpha = pr[p] / denom;
         if (64 * p + lane < K) attn[(size_t)n * K + 64 * p + lane] = alpha;
         aw[p] = jj[p] >= 0 ? alpha : 0.f;                      // pads: weight 0 on a valid (clamped) row
+        if (DROP && jj[p] >= 0) aw[p] = gat_dropped(dr, (size_t)n * K + 64 * p + lane, alpha);
     }
     for (int d0 = 0; d0 < D; d0 += 64) {
         const int d = d0 + lane, dd = d < D ? d : 0;
@@ -726,12 +728,12 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(
 // aggregation exchanged -- neighbour batches outside, the ND 64-channel chunks of a row inside -- so that one batch has
 // 8 ND loads in flight instead of 8 and a node makes ceil(K / 8) dependent round trips instead of ceil(K / 8) * D / 64
 // (18 -> 3 at configs[1]: 18.7 us of latency).  Every output still adds its neighbours in slot order: identical bits.
-template <int ND, bool EDGE = false>
+template <int ND, bool EDGE = false, bool DROP = false>
 __global__ __launch_bounds__(256) void gat_fwd_wide_kernel(
     const float *__restrict__ Wh, int ldw, const float *__restrict__ s, const float *__restrict__ t,
     const int64_t *__restrict__ ctx, int N, int K, int D, float slope, float *__restrict__ attn,
     float *__restrict__ hprime, int ldh, const float *__restrict__ phi = nullptr,
-    const float *__restrict__ edge_w = nullptr)
+    const float *__restrict__ edge_w = nullptr, GatDrop dr = GatDrop{})
 {
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (n >= N) return;
@@ -753,7 +755,8 @@ __global__ __launch_bounds__(256) void gat_fwd_wide_kernel(
     const float denom = wave_sum(psum);
     const float alpha = pr / denom;
     if (lane < K) attn[(size_t)n * K + lane] = alpha;
-    const float aw = jj >= 0 ? alpha : 0.f;                 // pads: weight 0 on a valid (clamped) row
+    float aw = jj >= 0 ? alpha : 0.f;                       // pads: weight 0 on a valid (clamped) row
+    if (DROP && jj >= 0) aw = gat_dropped(dr, (size_t)n * K + lane, alpha);
     float acc[ND];
     int dd[ND];
 #pragma unroll
@@ -891,13 +894,15 @@ __global__ __launch_bounds__(256) void csr_count_scan_kernel(const int64_t *__re
 // Source side (one wave per node i): everything that stays with node i -- du [N,K] (0 on pads),
 // ds, dWh_i = ds * a_i.  The contributions to OTHER nodes (dt[ctx], dWh_j[ctx]) are gathered by
 // gat_bwd_dst_kernel from du / attn / g through the transposed index.
-template <int KP, bool EDGE = false>
+// DROP: dalpha of a slot is the gradient of its DROPPED weight times keep * inv (0 on a dropped slot, which still takes
+// -alpha * dot through the softmax); alpha stays the undropped softmax output.
+template <int KP, bool EDGE = false, bool DROP = false>
 __global__ __launch_bounds__(256) void gat_bwd_src_kernel(
     const float *__restrict__ g, int ldg, const float *__restrict__ Wh, int ldw,
     const float *__restrict__ s, const float *__restrict__ t, const float *__restrict__ attn,
     const int64_t *__restrict__ ctx, const float *__restrict__ att_w, int N, int K, int D,
     float slope, float *__restrict__ dWh, int lddw, float *__restrict__ ds, float *__restrict__ du_out,
-    const float *__restrict__ phi = nullptr, const float *__restrict__ edge_w = nullptr)
+    const float *__restrict__ phi = nullptr, const float *__restrict__ edge_w = nullptr, GatDrop dr = GatDrop{})
 {
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (n >= N) return;
@@ -939,6 +944,11 @@ __global__ __launch_bounds__(256) void gat_bwd_src_kernel(
             }
         }
     }
+    if (DROP) {
+#pragma unroll
+        for (int p = 0; p < KP; ++p)
+            if (jj[p] >= 0) dalpha[p] = gat_dropped(dr, (size_t)n * K + 64 * p + lane, dalpha[p]);
+    }
     float ad = 0.f;
 #pragma unroll
     for (int p = 0; p < KP; ++p) ad += alpha[p] * dalpha[p];
@@ -963,10 +973,12 @@ __global__ __launch_bounds__(256) void gat_bwd_src_kernel(
 
 // backward, destination side (one wave per node j): dt[j] = sum_e du[e];
 // dWh_j[j] = sum_e alpha[e] * g[i_e] + dt[j] * a_j, e over row j of the transposed index, ascending
+// DROP: alpha[e] is the dropped weight gat_dropped(e, attn[e]), the forward's expression on the forward's slot index.
+template <bool DROP = false>
 __global__ __launch_bounds__(256) void gat_bwd_dst_kernel(
     const float *__restrict__ g, int ldg, const float *__restrict__ attn, const float *__restrict__ du,
     const int *__restrict__ row_ptr, const int *__restrict__ edges, const float *__restrict__ att_w, int N,
-    int K, int D, float *__restrict__ dWh, int lddw, float *__restrict__ dt)
+    int K, int D, float *__restrict__ dWh, int lddw, float *__restrict__ dt, GatDrop dr = GatDrop{})
 {
     const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (j >= N) return;
@@ -981,7 +993,8 @@ __global__ __launch_bounds__(256) void gat_bwd_dst_kernel(
         float accv = 0.f;
         for (int c0 = 0; c0 < deg; c0 += 64) {
             const int e = c0 + lane < deg ? edges[lo + c0 + lane] : 0;
-            const float al = c0 + lane < deg ? attn[e] : 0.f;     // 0 weight on the padding lanes
+            float al = c0 + lane < deg ? attn[e] : 0.f;           // 0 weight on the padding lanes
+            if (DROP && c0 + lane < deg) al = gat_dropped(dr, (size_t)e, al);
             const int cnt = min(64, deg - c0);
             for (int q0 = 0; q0 < cnt; q0 += 8) {                  // 8 neighbour rows in flight, added in edge order
                 float gv[8], aq[8];
@@ -1004,13 +1017,13 @@ __global__ __launch_bounds__(256) void gat_bwd_dst_kernel(
 // gat_bwd_src_kernel<1> / gat_bwd_dst_kernel with every 64-channel chunk of a row in flight per neighbour batch (see
 // gat_fwd_wide_kernel): K <= 64, D <= 64 ND; identical bits (each sum keeps its order: channels ascending inside a dot
 // product, edges ascending inside a gathered row).
-template <int ND, bool EDGE = false>
+template <int ND, bool EDGE = false, bool DROP = false>
 __global__ __launch_bounds__(256) void gat_bwd_src_wide_kernel(
     const float *__restrict__ g, int ldg, const float *__restrict__ Wh, int ldw,
     const float *__restrict__ s, const float *__restrict__ t, const float *__restrict__ attn,
     const int64_t *__restrict__ ctx, const float *__restrict__ att_w, int N, int K, int D,
     float slope, float *__restrict__ dWh, int lddw, float *__restrict__ ds, float *__restrict__ du_out,
-    const float *__restrict__ phi = nullptr, const float *__restrict__ edge_w = nullptr)
+    const float *__restrict__ phi = nullptr, const float *__restrict__ edge_w = nullptr, GatDrop dr = GatDrop{})
 {
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (n >= N) return;
@@ -1053,6 +1066,7 @@ __global__ __launch_bounds__(256) void gat_bwd_src_wide_kernel(
     // (the sum below is gat_bwd_src_kernel's statement for statement: written as wave_sum(alpha * dalpha), hipcc's default
     // -ffp-contract=fast fuses the product into the first add of the reduction -- an unrounded product, and for K > 32,
     // where the partner lane holds a value, other bits than the chunk kernel's)
+    if (DROP && jj >= 0) dalpha = gat_dropped(dr, (size_t)n * K + lane, dalpha);
     float ad = 0.f;
     ad += alpha * dalpha;
     const float dot = wave_sum(ad);
@@ -1071,11 +1085,11 @@ __global__ __launch_bounds__(256) void gat_bwd_src_wide_kernel(
     for (int d = lane; d < D; d += 64) dWh[(size_t)n * lddw + d] = dsn * att_w[d];
 }
 
-template <int ND>
+template <int ND, bool DROP = false>
 __global__ __launch_bounds__(256) void gat_bwd_dst_wide_kernel(
     const float *__restrict__ g, int ldg, const float *__restrict__ attn, const float *__restrict__ du,
     const int *__restrict__ row_ptr, const int *__restrict__ edges, const float *__restrict__ att_w, int N,
-    int K, int D, float *__restrict__ dWh, int lddw, float *__restrict__ dt)
+    int K, int D, float *__restrict__ dWh, int lddw, float *__restrict__ dt, GatDrop dr = GatDrop{})
 {
     const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (j >= N) return;
@@ -1092,7 +1106,8 @@ __global__ __launch_bounds__(256) void gat_bwd_dst_wide_kernel(
     }
     for (int c0 = 0; c0 < deg; c0 += 64) {
         const int e = c0 + lane < deg ? edges[lo + c0 + lane] : 0;
-        const float al = c0 + lane < deg ? attn[e] : 0.f;         // 0 weight on the padding lanes
+        float al = c0 + lane < deg ? attn[e] : 0.f;               // 0 weight on the padding lanes
+        if (DROP && c0 + lane < deg) al = gat_dropped(dr, (size_t)e, al);
         const int cnt = min(64, deg - c0);
         for (int q0 = 0; q0 < cnt; q0 += 8) {                      // 8 neighbour rows x ND chunks in flight, added in edge order
             float gq[ND][8], aq[8];
@@ -1439,10 +1454,10 @@ COVA_API int cova_bbox_linear_bwd(const float *dz, const float *raw, float *dW, 
 // EDGE = false is cova_gat_fwd (phi, edge_w unused: NULL); true is cova_gat_fwd_edge -- the same launches, the second one
 // on the EDGE instantiation of its kernel.
 namespace {
-template <bool EDGE>
+template <bool EDGE, bool DROP = false>
 int gat_fwd_launch(const float *Wh, int ldw, const float *att_w, const float *att_b, const int64_t *ctx, int N, int K,
                    int D, float slope, float *s, float *t, float *attn, float *hprime, int ldh, const float *phi,
-                   const float *edge_w, void *stream)
+                   const float *edge_w, void *stream, GatDrop dr = GatDrop{})
 {
     hipLaunchKernelGGL(gat_scores_kernel, dim3(cdiv(N, 4)), dim3(256), 0, (hipStream_t)stream, Wh,
                        ldw, att_w, att_b, s, t, N, D);
@@ -1450,7 +1465,7 @@ int gat_fwd_launch(const float *Wh, int ldw, const float *att_w, const float *at
     const dim3 grid(cdiv(N, 4)), blk(256);
     hipStream_t st = (hipStream_t)stream;
     if (K <= 64 && gat_wide_nd(D) > 0) {        // every 64-channel chunk of a neighbour row in flight (identical bits)
-#define COVA_GAT_FWD_WIDE(ND) hipLaunchKernelGGL((gat_fwd_wide_kernel<ND, EDGE>), grid, blk, 0, st, Wh, ldw, s, t, ctx, N, K, D, slope, attn, hprime, ldh, phi, edge_w)
+#define COVA_GAT_FWD_WIDE(ND) hipLaunchKernelGGL((gat_fwd_wide_kernel<ND, EDGE, DROP>), grid, blk, 0, st, Wh, ldw, s, t, ctx, N, K, D, slope, attn, hprime, ldh, phi, edge_w, dr)
         switch (gat_wide_nd(D)) {
         case 1: COVA_GAT_FWD_WIDE(1); break;
         case 2: COVA_GAT_FWD_WIDE(2); break;
@@ -1463,7 +1478,7 @@ int gat_fwd_launch(const float *Wh, int ldw, const float *att_w, const float *at
         COVA_LAUNCH_CHECK();
         return COVA_OK;
     }
-#define COVA_GAT_FWD(KP) hipLaunchKernelGGL((gat_fwd_kernel<KP, EDGE>), grid, blk, 0, st, Wh, ldw, s, t, ctx, N, K, D, slope, attn, hprime, ldh, phi, edge_w)
+#define COVA_GAT_FWD(KP) hipLaunchKernelGGL((gat_fwd_kernel<KP, EDGE, DROP>), grid, blk, 0, st, Wh, ldw, s, t, ctx, N, K, D, slope, attn, hprime, ldh, phi, edge_w, dr)
     switch ((K + 63) / 64) {        // one wave per node, K slots in ceil(K / 64) passes over the lanes
     case 1: COVA_GAT_FWD(1); break;
     case 2: COVA_GAT_FWD(2); break;
@@ -1549,21 +1564,21 @@ COVA_API int cova_gat_transpose_reuse(const int64_t *ctx, int N, int K, int *csr
 // csr (from cova_gat_transpose) + du [N,K] scratch, both required: gather form, no float atomics, bit-identical reruns.
 // EDGE = false is cova_gat_bwd (phi, edge_w, d_edge_w, edge_ws unused: NULL); true is cova_gat_bwd_edge.
 namespace {
-template <bool EDGE>
+template <bool EDGE, bool DROP = false>
 int gat_bwd_launch(const float *g, int ldg, const float *Wh, int ldw, const float *s, const float *t, const float *attn,
                    const int64_t *ctx, const float *att_w, int N, int K, int D, float slope, float *dWh, int lddw,
                    float *ds, float *dt, float *d_att_w, float *d_att_b, const int *csr, float *du, const float *phi,
-                   const float *edge_w, float *d_edge_w, float *edge_ws, void *stream)
+                   const float *edge_w, float *d_edge_w, float *edge_ws, void *stream, GatDrop dr = GatDrop{})
 {    hipStream_t st = (hipStream_t)stream;
     const int kp = (K + 63) / 64;
     if (K <= 64 && gat_wide_nd(D) > 0) {
         const dim3 grid(cdiv(N, 4)), blk(256);
 #define COVA_GAT_BWD_WIDE(ND)                                                                                               \
         do {                                                                                                                \
-            hipLaunchKernelGGL((gat_bwd_src_wide_kernel<ND, EDGE>), grid, blk, 0, st, g, ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, \
-                               slope, dWh, lddw, ds, du, phi, edge_w);                                                      \
-            hipLaunchKernelGGL(gat_bwd_dst_wide_kernel<ND>, grid, blk, 0, st, g, ldg, attn, du, csr, csr + N + 1, att_w, N, K, \
-                               D, dWh, lddw, dt);                                                                           \
+            hipLaunchKernelGGL((gat_bwd_src_wide_kernel<ND, EDGE, DROP>), grid, blk, 0, st, g, ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, \
+                               slope, dWh, lddw, ds, du, phi, edge_w, dr);                                                  \
+            hipLaunchKernelGGL((gat_bwd_dst_wide_kernel<ND, DROP>), grid, blk, 0, st, g, ldg, attn, du, csr, csr + N + 1, att_w, N, K, \
+                               D, dWh, lddw, dt, dr);                                                                       \
         } while (0)
         switch (gat_wide_nd(D)) {
         case 1: COVA_GAT_BWD_WIDE(1); break;
@@ -1576,8 +1591,8 @@ int gat_bwd_launch(const float *g, int ldg, const float *Wh, int ldw, const floa
 #undef COVA_GAT_BWD_WIDE
         COVA_LAUNCH_CHECK();
     } else {
-#define COVA_GAT_SRC(KP) hipLaunchKernelGGL((gat_bwd_src_kernel<KP, EDGE>), dim3(cdiv(N, 4)), dim3(256), 0, st, g, ldg, Wh, ldw, s, t, \
-                                            attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, du, phi, edge_w)
+#define COVA_GAT_SRC(KP) hipLaunchKernelGGL((gat_bwd_src_kernel<KP, EDGE, DROP>), dim3(cdiv(N, 4)), dim3(256), 0, st, g, ldg, Wh, ldw, s, t, \
+                                            attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, du, phi, edge_w, dr)
         switch (kp) {
         case 1: COVA_GAT_SRC(1); break;
         case 2: COVA_GAT_SRC(2); break;
@@ -1592,8 +1607,8 @@ int gat_bwd_launch(const float *g, int ldg, const float *Wh, int ldw, const floa
         }
 #undef COVA_GAT_SRC
         COVA_LAUNCH_CHECK();
-        hipLaunchKernelGGL(gat_bwd_dst_kernel, dim3(cdiv(N, 4)), dim3(256), 0, st, g, ldg, attn, du, csr,
-                           csr + N + 1, att_w, N, K, D, dWh, lddw, dt);
+        hipLaunchKernelGGL(gat_bwd_dst_kernel<DROP>, dim3(cdiv(N, 4)), dim3(256), 0, st, g, ldg, attn, du, csr,
+                           csr + N + 1, att_w, N, K, D, dWh, lddw, dt, dr);
         COVA_LAUNCH_CHECK();
     }
     const bool v4 = (D % 4 == 0) && (ldw % 4 == 0) && (((uintptr_t)Wh & 15) == 0);
@@ -1643,4 +1658,46 @@ COVA_API int cova_gat_bwd_edge(const float *g, int ldg, const float *Wh, int ldw
     COVA_REQUIRE(csr && du && phi && edge_w && d_edge_w && workspace && ((uintptr_t)phi & 15) == 0);
     return gat_bwd_launch<true>(g, ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, dt, d_att_w,
                                 d_att_b, csr, du, phi, edge_w, d_edge_w, workspace, stream);
+}
+
+// ---- attention dropout: inverted dropout on the softmax output, rate p in [0, 1), stream `seed`.
+// Slot e = i*K + k is kept when hash_uniform(seed, e) >= p; its weight in h' (and in dWh_j) is attn * 1/(1-p), a dropped
+// slot weighs 0.  attn itself stays the softmax output; no mask is stored: forward, source side and destination side
+// each regenerate it from (seed, e).  phi / edge_w (and in the backward d_edge_w / workspace) are NULL as a group (the plain
+// score) or all given (the edge term of cova_gat_fwd_edge / cova_gat_bwd_edge).
+COVA_API int cova_gat_fwd_drop(const float *Wh, int ldw, const float *att_w, const float *att_b, const int64_t *ctx,
+                               const float *phi, const float *edge_w, int N, int K, int D, float slope, float p,
+                               unsigned long long seed, float *s, float *t, float *attn, float *hprime, int ldh,
+                               void *stream)
+{
+    COVA_REQUIRE(Wh && att_w && att_b && ctx && s && t && attn && hprime && K > 0 && K <= COVA_GAT_MAX_K && D > 0);
+    COVA_REQUIRE((phi == nullptr) == (edge_w == nullptr) && ((uintptr_t)phi & 15) == 0);
+    COVA_REQUIRE(p >= 0.f && p < 1.f);                         // (NaN fails both)
+    if (N == 0) return COVA_OK;
+    const GatDrop dr = gat_drop_of(p, seed);
+    if (phi)
+        return gat_fwd_launch<true, true>(Wh, ldw, att_w, att_b, ctx, N, K, D, slope, s, t, attn, hprime, ldh, phi, edge_w,
+                                          stream, dr);
+    return gat_fwd_launch<false, true>(Wh, ldw, att_w, att_b, ctx, N, K, D, slope, s, t, attn, hprime, ldh, nullptr,
+                                       nullptr, stream, dr);
+}
+
+COVA_API int cova_gat_bwd_drop(const float *g, int ldg, const float *Wh, int ldw, const float *s, const float *t,
+                               const float *attn, const int64_t *ctx, const float *att_w, const float *phi,
+                               const float *edge_w, int N, int K, int D, float slope, float p, unsigned long long seed,
+                               float *dWh, int lddw, float *ds, float *dt, float *d_att_w, float *d_att_b,
+                               float *d_edge_w, const int *csr, float *du, float *workspace, void *stream)
+{
+    COVA_REQUIRE(g && Wh && s && t && attn && ctx && att_w && dWh && ds && dt && d_att_w && d_att_b);
+    COVA_REQUIRE(K > 0 && K <= COVA_GAT_MAX_K && D > 0 && N > 0);
+    COVA_REQUIRE(csr && du && ((uintptr_t)phi & 15) == 0);
+    COVA_REQUIRE((phi == nullptr) == (edge_w == nullptr) && (phi == nullptr) == (d_edge_w == nullptr) &&
+                 (phi == nullptr) == (workspace == nullptr));
+    COVA_REQUIRE(p >= 0.f && p < 1.f);
+    const GatDrop dr = gat_drop_of(p, seed);
+    if (phi)
+        return gat_bwd_launch<true, true>(g, ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, dt,
+                                          d_att_w, d_att_b, csr, du, phi, edge_w, d_edge_w, workspace, stream, dr);
+    return gat_bwd_launch<false, true>(g, ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, dt, d_att_w,
+                                       d_att_b, csr, du, nullptr, nullptr, nullptr, nullptr, stream, dr);
 }

@@ -25,8 +25,10 @@ BN_MOMENTUM, BN_EPS, LEAKY_SLOPE = 0.1, 1e-5, 0.2   # nn.BatchNorm defaults; mod
 # {BatchNorm prefix ("convnet.1.", "convnet.4.0.bn1.", "decoder.2.", ...) or Dropout name ("decoder.0", "decoder.3"): bool}
 # (per-module .training, e.g. ``model.train(); model.convnet.eval()``); layers the mapping does not name are in train mode.
 # An eval-mode BatchNorm normalises with its running statistics and leaves its buffers alone; an eval-mode Dropout is the
-# identity.
+# identity.  A model built with ``attention_dropout`` > 0 also names the Dropout of every attention head, "<head prefix>attn_drop"
+# ("gat.attn_drop", "gat.layers.0.heads.1.attn_drop": ATTN_DROP_KEY behind weights.gat_prefixes).
 DROPOUT_KEYS = ("decoder.0", "decoder.3")
+ATTN_DROP_KEY = "attn_drop"
 
 
 def is_train(training, key):
@@ -1322,13 +1324,49 @@ def check_attention_weight(prefix, aw, D, attention):
                          % (attention, prefix, tuple(aw.shape), have, 2 * D, D))
 
 
-def gat_fwd(h, ldh, N, F, ctx, params, hprime, ldo, prefix="gat.", phi=None, attention="gat"):
+def dropout_base(seed, call):
+    """First dropout stream of forward number ``call`` (1, 2, ...) under ``seed``: CoVA._next_dropout_seeds' and
+    HotPathTrainer.forward_backward's rule.  The decoder draws from ``base`` and ``base + 1``; the next call's is ``base + 2``."""
+    return (int(seed) * 0x9E3779B1 + 2 * int(call)) & 0xFFFFFFFFFFFF
+
+
+def attention_dropout_seed(base, layer, head):
+    """Stream of the attention dropout of head ``head`` of layer ``layer`` in the step whose decoder Dropouts draw from
+    ``base`` and ``base + 1``: ``(layer + 1) << 56 | (head + 1) << 48 | base``.
+    Every ``base`` (CoVA._next_dropout_seeds, HotPathTrainer.forward_backward) is below 2**48 and ``base + 1`` at most
+    2**48, so the decoder streams of every step and seed have bits 49 .. 63 clear, while an attention stream has one of the
+    bits 48 .. 62 set and (head + 1) << 48 | base > 2**48: no attention stream is a decoder stream of any step, and two
+    attention streams are equal only for equal (base, layer, head).  The counter hash (csrc/common.h, hash_mix64)
+    finalises ``seed + golden * (idx + 1)`` with full avalanche: streams that differ in high bits only are unrelated."""
+    base, layer, head = int(base), int(layer), int(head)
+    if not (0 <= base < 1 << 48 and 0 <= layer < 127 and 0 <= head < 255):
+        raise ValueError("attention_dropout_seed: base in [0, 2**48), layer in [0, 127), head in [0, 255); got %r"
+                         % ((base, layer, head),))
+    return (layer + 1) << 56 | (head + 1) << 48 | base
+
+
+def check_gat_drop(drop):
+    """``drop`` of gat_fwd -> (p, seed) with p in (0, 1), or None when there is nothing to drop (None, or p == 0)."""
+    if drop is None:
+        return None
+    from .weights import check_attention_dropout
+    p, seed = drop
+    p, seed = check_attention_dropout(p), int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("attention dropout seed must fit 64 unsigned bits, got %r" % (seed,))
+    return (p, seed) if p > 0.0 else None
+
+
+def gat_fwd(h, ldh, N, F, ctx, params, hprime, ldo, prefix="gat.", phi=None, attention="gat", drop=None):
     """models.py:171-212.  h rows at h + n*ldh (F values); hprime rows at hprime + n*ldo (D).
     ``phi`` (edge_geometry): the score takes the edge term ``edge_layer.weight . phi`` (cova_gat_fwd_edge); a head that
     has an ``edge_layer.weight`` needs it.
     ``attention="gatv2"``: the score is ``a . LeakyReLU(Wh_i + Wh_j) + b`` (cova_gat2_fwd; the edge term is added outside
-    the non-linearity); the projections are the same GEMM(s), and the saved dict carries no ``s`` / ``t``."""
+    the non-linearity); the projections are the same GEMM(s), and the saved dict carries no ``s`` / ``t``.
+    ``drop`` = (p, seed): dropout on the attention coefficients (cova_gat_fwd_drop / cova_gat2_fwd_drop; ``attn`` stays the
+    softmax output); None or p == 0 issues exactly the calls above.  gat_bwd reads (p, seed) from the saved dict."""
     _check(ctx, torch.int64)
+    drop = check_gat_drop(drop)
     Wi, Wj = params[prefix + "W_i.weight"], params[prefix + "W_j.weight"]
     aw, ab = params[prefix + "attention_layer.weight"], params[prefix + "attention_layer.bias"]
     ew = params.get(prefix + "edge_layer.weight")
@@ -1350,17 +1388,27 @@ def gat_fwd(h, ldh, N, F, ctx, params, hprime, ldo, prefix="gat.", phi=None, att
         if phi is not None:
             assert tuple(phi.shape) == (N, K, 8), (tuple(phi.shape), N, K)
             _check(phi), _check(ew)
-        call("cova_gat2_fwd", Wh, 2 * D, aw, ab, ctx, phi, ew, N, K, D, LEAKY_SLOPE, attn, hprime, ldo)
+        if drop is None:
+            call("cova_gat2_fwd", Wh, 2 * D, aw, ab, ctx, phi, ew, N, K, D, LEAKY_SLOPE, attn, hprime, ldo)
+        else:
+            call("cova_gat2_fwd_drop", Wh, 2 * D, aw, ab, ctx, phi, ew, N, K, D, LEAKY_SLOPE, drop[0], drop[1], attn,
+                 hprime, ldo)
         return dict(h=h, ldh=ldh, N=N, F=F, D=D, K=K, ctx=ctx, Wh=Wh, attn=attn, prefix=prefix, phi=phi,
-                    attention="gatv2")
+                    attention="gatv2", drop=drop)
     s, t, attn = _empty((N,), h), _empty((N,), h), _empty((N, K), h)
-    if phi is None:
+    if drop is not None:
+        if phi is not None:
+            assert tuple(phi.shape) == (N, K, 8), (tuple(phi.shape), N, K)
+            _check(phi), _check(ew)
+        call("cova_gat_fwd_drop", Wh, 2 * D, aw, ab, ctx, phi, ew, N, K, D, LEAKY_SLOPE, drop[0], drop[1], s, t, attn,
+             hprime, ldo)
+    elif phi is None:
         call("cova_gat_fwd", Wh, 2 * D, aw, ab, ctx, N, K, D, LEAKY_SLOPE, s, t, attn, hprime, ldo)
     else:
         assert tuple(phi.shape) == (N, K, 8), (tuple(phi.shape), N, K)
         call("cova_gat_fwd_edge", Wh, 2 * D, aw, ab, ctx, _check(phi), _check(ew), N, K, D, LEAKY_SLOPE, s, t, attn,
              hprime, ldo)
-    return dict(h=h, ldh=ldh, N=N, F=F, D=D, K=K, ctx=ctx, Wh=Wh, s=s, t=t, attn=attn, prefix=prefix, phi=phi)
+    return dict(h=h, ldh=ldh, N=N, F=F, D=D, K=K, ctx=ctx, Wh=Wh, s=s, t=t, attn=attn, prefix=prefix, phi=phi, drop=drop)
 
 
 # Backward of the neighbour gather: a deterministic gather through the transposed index (no float atomics).
@@ -1401,18 +1449,26 @@ def gat_bwd(sv, g, ldg, params, dh, lddh, accumulate_dh, gout=None, csr=None):
         check_attention_weight(prefix, aw, D, sv.get("attention", "gat"))          # (raises)
     daw = _gbuf(gout, prefix + "attention_layer.weight", (1, D if v2 else 2 * D), g)
     dab = _gbuf(gout, prefix + "attention_layer.bias", (1,), g)
-    phi, ew, dew, edge = sv.get("phi"), None, None, {}
+    phi, ew, dew, edge, drop = sv.get("phi"), None, None, {}, sv.get("drop")
     if phi is not None:
         ew = params[prefix + "edge_layer.weight"]
         dew = _gbuf(gout, prefix + "edge_layer.weight", (1, 8), g)
         edge = {prefix + "edge_layer.weight": dew}
     if v2:
         ws = _empty((query("cova_gat2_workspace_floats", N, K, D),), g)
-        call("cova_gat2_bwd", g, ldg, sv["Wh"], 2 * D, sv["attn"], sv["ctx"], aw, phi, ew, N, K, D, LEAKY_SLOPE, dWh, 2 * D,
-             daw, dab, dew, csr, du, ws)
+        if drop is None:
+            call("cova_gat2_bwd", g, ldg, sv["Wh"], 2 * D, sv["attn"], sv["ctx"], aw, phi, ew, N, K, D, LEAKY_SLOPE, dWh,
+                 2 * D, daw, dab, dew, csr, du, ws)
+        else:
+            call("cova_gat2_bwd_drop", g, ldg, sv["Wh"], 2 * D, sv["attn"], sv["ctx"], aw, phi, ew, N, K, D, LEAKY_SLOPE,
+                 drop[0], drop[1], dWh, 2 * D, daw, dab, dew, csr, du, ws)
     else:
         ds, dt = _empty((N,), g), _empty((N,), g)
-        if phi is None:
+        if drop is not None:
+            ws = _empty((query("cova_gat_edge_workspace_floats", N, K),), g) if phi is not None else None
+            call("cova_gat_bwd_drop", g, ldg, sv["Wh"], 2 * D, sv["s"], sv["t"], sv["attn"], sv["ctx"], aw, phi, ew, N, K,
+                 D, LEAKY_SLOPE, drop[0], drop[1], dWh, 2 * D, ds, dt, daw, dab, dew, csr, du, ws)
+        elif phi is None:
             call("cova_gat_bwd", g, ldg, sv["Wh"], 2 * D, sv["s"], sv["t"], sv["attn"], sv["ctx"], aw, N, K, D,
                  LEAKY_SLOPE, dWh, 2 * D, ds, dt, daw, dab, csr, du)
         else:
@@ -1436,14 +1492,18 @@ def gat_bwd(sv, g, ldg, params, dh, lddh, accumulate_dh, gout=None, csr=None):
 
 
 def gat_stack_fwd(comb, T, N, F, D, ctx, params, n_heads=1, n_gat_layers=1, bboxes=None, page_size=None,
-                  edge_geometry_on=False, attention="gat"):
+                  edge_geometry_on=False, attention="gat", attention_dropout=0.0, seed_base=0, training=True):
     """The reference's single GraphAttentionLayer (models.py:114) or the multi-head / stacked extension:
     every layer concatenates its heads (hidden_dim/n_heads channels each, written side by side), layers
     are chained; the last one writes the context columns comb[:, F:].
     ``edge_geometry_on``: the edge features of the batch (``bboxes``, ``page_size`` = (height, width)) are computed once
-    and handed to every head.  ``attention``: the scoring mode of every head ('gat' | 'gatv2', gat_fwd)."""
-    from .weights import gat_prefixes
+    and handed to every head.  ``attention``: the scoring mode of every head ('gat' | 'gatv2', gat_fwd).
+    ``attention_dropout`` > 0: head (l, i) drops attention coefficients from its own stream
+    attention_dropout_seed(``seed_base``, l, i) while it is in train mode (``training``: a bool or per-layer modes, the
+    head's key is its prefix + ATTN_DROP_KEY); ``seed_base`` is the step's first decoder seed."""
+    from .weights import check_attention_dropout, gat_prefixes
     prefixes = gat_prefixes(n_heads, n_gat_layers)
+    attention_dropout = check_attention_dropout(attention_dropout)
     phi = None
     if edge_geometry_on:
         if bboxes is None or page_size is None:
@@ -1454,8 +1514,10 @@ def gat_stack_fwd(comb, T, N, F, D, ctx, params, n_heads=1, n_gat_layers=1, bbox
     for l, heads in enumerate(prefixes):
         last = l == len(prefixes) - 1
         out, ldo = (comb[:, F:], T) if last else (_empty((N, D), comb), D)
-        svs = [gat_fwd(h, ldh, N, fin, ctx, params, out[:, i * dh:], ldo, prefix=p, phi=phi, attention=attention)
-               for i, p in enumerate(heads)]
+        drops = [(attention_dropout, attention_dropout_seed(seed_base, l, i))
+                 if attention_dropout > 0 and is_train(training, p + ATTN_DROP_KEY) else None for i, p in enumerate(heads)]
+        svs = [gat_fwd(h, ldh, N, fin, ctx, params, out[:, i * dh:], ldo, prefix=p, phi=phi, attention=attention,
+                       drop=drops[i]) for i, p in enumerate(heads)]
         layers.append(dict(heads=svs, out=out))
         h, ldh, fin = out, ldo, D
     return layers
@@ -1596,7 +1658,7 @@ def _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, t
                              "(or the configuration a 'page_size')")
         sv["gat"] = gat_stack_fwd(comb, T, N, F, D, context_indices, params, cfg.get("n_heads", 1),
                                   cfg.get("n_gat_layers", 1), bboxes if edge else None, sv.get("page_size"), edge,
-                                  cfg.get("attention", "gat"))
+                                  cfg.get("attention", "gat"), cfg.get("attention_dropout", 0.0), seeds[0], training)
     logits, sv["dec"] = decoder_fwd(comb, N, T, params, buffers, training, cfg["drop_prob"], seeds,
                                     masks)
     return logits, (sv if save else None)

@@ -21,7 +21,8 @@ import torch
 import torch.nn as nn
 
 from . import engine
-from .weights import EDGE_FEATURES, attention_of, backbone_channels, check_attention, check_backbone_layers
+from .weights import (EDGE_FEATURES, attention_of, backbone_channels, check_attention, check_attention_dropout,
+                      check_backbone_layers)
 
 GAT_MAX_K = engine.GAT_MAX_K
 LOSS_MAX_CLASSES = engine.LOSS_MAX_CLASSES
@@ -254,7 +255,7 @@ class _HipBatchNorm1d(nn.BatchNorm1d):
 
 class _GATFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, layer, h_i, context_indices, W_i, W_j, att_w, att_b, edge_w=None, phi=None):
+    def forward(ctx, layer, h_i, context_indices, W_i, W_j, att_w, att_b, edge_w=None, phi=None, drop=None):
         h = _f32c(h_i)
         N, F = h.shape
         params = {"gat.W_i.weight": W_i.detach(), "gat.W_j.weight": W_j.detach(),
@@ -264,7 +265,7 @@ class _GATFn(torch.autograd.Function):
             params["gat.edge_layer.weight"] = edge_w.detach().contiguous()
         hp = torch.empty((N, layer.hidden_dim), device=h.device)
         ctx.sv = engine.gat_fwd(h, F, N, F, _i64c(context_indices), params, hp, layer.hidden_dim, phi=phi,
-                                attention=layer.attention)
+                                attention=layer.attention, drop=drop)
         ctx.params = params
         ctx.mark_non_differentiable(ctx.sv["attn"])
         return hp, ctx.sv["attn"]
@@ -276,7 +277,7 @@ class _GATFn(torch.autograd.Function):
         grads = engine.gat_bwd(sv, g.contiguous(), sv["D"], ctx.params, dh, sv["F"], False)
         return (None, dh, None, grads["gat.W_i.weight"], grads["gat.W_j.weight"],
                 grads["gat.attention_layer.weight"], grads["gat.attention_layer.bias"],
-                grads.get("gat.edge_layer.weight"), None)
+                grads.get("gat.edge_layer.weight"), None, None)
 
 
 # ------------------------------------------------------------------------------------- modules
@@ -312,9 +313,13 @@ class GraphAttentionLayer(nn.Module):
     construction) of its relative-geometry features (include/cova_hip.h, cova_edge_geometry).
     ``attention="gatv2"`` (extension): the dynamic score of Brody et al. (ICLR 2022), ``attention_layer(LeakyReLU(W_i h_i +
     W_j h_j))`` with ``attention_layer`` a Linear(hidden_dim, 1), instead of the reference's static
-    ``LeakyReLU(attention_layer([W_i h_i ; W_j h_j]))``; the edge term is then added outside the non-linearity."""
+    ``LeakyReLU(attention_layer([W_i h_i ; W_j h_j]))``; the edge term is then added outside the non-linearity.
+    ``attention_dropout=p`` (extension, 0 <= p < 1): inverted dropout on the normalised attention coefficients while the
+    layer (its ``attn_drop`` submodule) is in train mode (GAT paper, section 3.3; PyG ``GATConv(dropout=)``, DGL
+    ``attn_drop``).  The weights returned with ``return_attn_wts`` stay the distribution before dropout.  The masks are
+    regenerated in the kernels from a per-call seed (seed_dropout); with p = 0 no submodule is created."""
 
-    def __init__(self, in_features, hidden_dim, alpha=0.2, edge_geometry=False, attention="gat"):
+    def __init__(self, in_features, hidden_dim, alpha=0.2, edge_geometry=False, attention="gat", attention_dropout=0.0):
         super(GraphAttentionLayer, self).__init__()
         if abs(alpha - engine.LEAKY_SLOPE) > 1e-12:
             raise ValueError("the HIP path is built for the reference's LeakyReLU slope 0.2")
@@ -322,6 +327,8 @@ class GraphAttentionLayer(nn.Module):
         self.hidden_dim = hidden_dim
         self.edge_geometry = bool(edge_geometry)
         self.attention = check_attention(attention)
+        self.attention_dropout = check_attention_dropout(attention_dropout)
+        self._dropout_seed, self._dropout_calls = 0x5EED, 0
         self.W_i = nn.Linear(self.in_features, self.hidden_dim, bias=False)
         self.W_j = nn.Linear(self.in_features, self.hidden_dim, bias=False)
         self.attention_layer = nn.Linear((1 if self.attention == "gatv2" else 2) * self.hidden_dim, 1)
@@ -329,6 +336,13 @@ class GraphAttentionLayer(nn.Module):
         if self.edge_geometry:
             self.edge_layer = nn.Linear(EDGE_FEATURES, 1, bias=False)
             nn.init.zeros_(self.edge_layer.weight)
+        if self.attention_dropout > 0:
+            self.attn_drop = nn.Dropout(self.attention_dropout)     # rate and train / eval mode (no weights; never called)
+
+    def seed_dropout(self, seed):
+        """Seed of the attention-dropout masks of a layer called on its own (inside CoVA / MultiHeadGraphAttention the
+        owner's seed governs): call c (1, 2, ...) draws from engine.attention_dropout_seed(engine.dropout_base(seed, c), 0, 0)."""
+        self._dropout_seed, self._dropout_calls = int(seed), 0
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         w = state_dict.get(prefix + "attention_layer.weight")
@@ -343,30 +357,38 @@ class GraphAttentionLayer(nn.Module):
                                              tuple(w.shape), theirs))
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
 
-    def forward(self, h_i, context_indices, return_attn_wts=False, bboxes=None, page_size=None, phi=None):
+    def forward(self, h_i, context_indices, return_attn_wts=False, bboxes=None, page_size=None, phi=None, drop_seed=None):
         """h_i [N, in_features]; context_indices int64 [N, n_context] with -1 pads.  An edge-aware layer also needs
-        ``bboxes`` [N, 5] and ``page_size`` = (height, width), or the ``phi`` [N, n_context, 8] computed from them."""
+        ``bboxes`` [N, 5] and ``page_size`` = (height, width), or the ``phi`` [N, n_context, 8] computed from them.
+        ``drop_seed``: the attention-dropout stream of this call (MultiHeadGraphAttention hands each head its own)."""
         _require_cuda(h_i, context_indices)
         _check_gat_inputs(h_i, context_indices, self.in_features)
+        drop = None
+        if self.attention_dropout > 0 and self.attn_drop.training:
+            if drop_seed is None:
+                self._dropout_calls += 1
+                drop_seed = engine.attention_dropout_seed(engine.dropout_base(self._dropout_seed, self._dropout_calls), 0, 0)
+            drop = (self.attention_dropout, int(drop_seed))
         if not self.edge_geometry:
             h_prime, attn = _GATFn.apply(self, h_i, context_indices, self.W_i.weight, self.W_j.weight,
-                                         self.attention_layer.weight, self.attention_layer.bias)
+                                         self.attention_layer.weight, self.attention_layer.bias, None, None, drop)
         else:
             if phi is None:
                 phi = _edge_features(context_indices, bboxes, page_size)
             h_prime, attn = _GATFn.apply(self, h_i, context_indices, self.W_i.weight, self.W_j.weight,
                                          self.attention_layer.weight, self.attention_layer.bias,
-                                         self.edge_layer.weight, phi)
+                                         self.edge_layer.weight, phi, drop)
         if return_attn_wts:
             return h_prime, attn
         return h_prime
 
 
 class _GATHeads(nn.Module):
-    def __init__(self, in_features, hidden_dim, n_heads, edge_geometry=False, attention="gat"):
+    def __init__(self, in_features, hidden_dim, n_heads, edge_geometry=False, attention="gat", attention_dropout=0.0):
         super().__init__()
         self.heads = nn.ModuleList([GraphAttentionLayer(in_features, hidden_dim // n_heads, edge_geometry=edge_geometry,
-                                                        attention=attention) for _ in range(n_heads)])
+                                                        attention=attention, attention_dropout=attention_dropout)
+                                    for _ in range(n_heads)])
 
 
 class MultiHeadGraphAttention(nn.Module):
@@ -375,24 +397,37 @@ class MultiHeadGraphAttention(nn.Module):
     GraphAttentionLayers of hidden_dim/n_heads channels over the same neighbour table.  Same call
     contract as GraphAttentionLayer; the attention weights returned are the last layer's, per head
     [N, n_heads, n_context].  ``edge_geometry``: every head is edge-aware; the features are computed once per call.
-    ``attention``: the scoring mode of every head ('gat' | 'gatv2', GraphAttentionLayer)."""
+    ``attention``: the scoring mode of every head ('gat' | 'gatv2', GraphAttentionLayer).
+    ``attention_dropout``: every head drops attention coefficients (GraphAttentionLayer) from a stream of its own,
+    engine.attention_dropout_seed(base, layer, head), ``base`` = engine.dropout_base(seed, call) of seed_dropout()."""
 
-    def __init__(self, in_features, hidden_dim, n_heads, n_layers, edge_geometry=False, attention="gat"):
+    def __init__(self, in_features, hidden_dim, n_heads, n_layers, edge_geometry=False, attention="gat",
+                 attention_dropout=0.0):
         super().__init__()
         if hidden_dim % n_heads:
             raise ValueError("hidden_dim must be divisible by n_heads")
         self.edge_geometry = bool(edge_geometry)
         self.attention = check_attention(attention)
+        self.attention_dropout = check_attention_dropout(attention_dropout)
+        self._dropout_seed, self._dropout_calls = 0x5EED, 0
         self.layers = nn.ModuleList([_GATHeads(in_features if l == 0 else hidden_dim, hidden_dim, n_heads, edge_geometry,
-                                               attention) for l in range(n_layers)])
+                                               attention, self.attention_dropout) for l in range(n_layers)])
+
+    def seed_dropout(self, seed):
+        self._dropout_seed, self._dropout_calls = int(seed), 0
 
     def forward(self, h_i, context_indices, return_attn_wts=False, bboxes=None, page_size=None, phi=None):
-        h, attn = h_i, None
+        h, attn, base = h_i, None, None
+        if self.attention_dropout > 0:
+            self._dropout_calls += 1
+            base = engine.dropout_base(self._dropout_seed, self._dropout_calls)
         if self.edge_geometry and phi is None:
             _require_cuda(h_i, context_indices)
             phi = _edge_features(context_indices, bboxes, page_size)
-        for layer in self.layers:
-            outs = [head(h, context_indices, True, phi=phi) for head in layer.heads]
+        for l, layer in enumerate(self.layers):
+            outs = [head(h, context_indices, True, phi=phi,
+                         drop_seed=None if base is None else engine.attention_dropout_seed(base, l, i))
+                    for i, head in enumerate(layer.heads)]
             h = torch.cat([o for o, _ in outs], dim=1)
             attn = torch.stack([a for _, a in outs], dim=1)
         return (h, attn) if return_attn_wts else h
@@ -402,7 +437,8 @@ class CoVA(nn.Module):
     def __init__(self, roi_output_size, img_H, n_classes, use_context=True, hidden_dim=384,
                  bbox_hidden_dim=32, n_additional_feat=0, drop_prob=0.2, class_names=None,
                  backbone="resnet18", n_heads=1, n_gat_layers=1, backbone_state_dict=None, roi_op="pool",
-                 sampling_ratio=2, roi_aligned=False, backbone_layers=1, edge_geometry=False, attention="gat"):
+                 sampling_ratio=2, roi_aligned=False, backbone_layers=1, edge_geometry=False, attention="gat",
+                 attention_dropout=0.0):
         """The first nine arguments exactly as the reference's CoVA (models.py:10-34; called positionally
         at main.py:122-132).  Keyword-only-in-practice extensions, whose defaults are the reference's
         model: ``backbone`` 'resnet18' | 'resnet50' (torchvision ``children()[:-5]`` of either),
@@ -419,9 +455,13 @@ class CoVA(nn.Module):
         the page size is taken from ``images``.
         ``attention="gatv2"``: every head scores with the GATv2 form ``a . LeakyReLU(W_i h_i + W_j h_j) + b`` (dynamic
         attention: the ranking of a box's neighbours depends on the box); ``attention_layer.weight`` is then
-        [1, hidden_dim / n_heads], so checkpoints of the two modes do not load into each other."""
+        [1, hidden_dim / n_heads], so checkpoints of the two modes do not load into each other.
+        ``attention_dropout=p`` (0 <= p < 1): dropout on the attention coefficients of every head in train mode
+        (GraphAttentionLayer); the masks follow seed_dropout() like the decoder's, from streams of their own.  No weights:
+        the state_dict is unchanged; with p = 0 the module list is too."""
         check_backbone_layers(backbone, backbone_layers)
         check_attention(attention)
+        attention_dropout = check_attention_dropout(attention_dropout)
         if roi_op not in ("pool", "align"):
             raise ValueError("roi_op must be 'pool' (the reference, models.py:58) or 'align'")
         super(CoVA, self).__init__()
@@ -474,10 +514,10 @@ class CoVA(nn.Module):
         if self.use_context:
             if n_heads == 1 and n_gat_layers == 1:
                 self.gat = GraphAttentionLayer(self.n_feat, self.hidden_dim, edge_geometry=edge_geometry,
-                                               attention=attention)
+                                               attention=attention, attention_dropout=attention_dropout)
             else:
                 self.gat = MultiHeadGraphAttention(self.n_feat, self.hidden_dim, n_heads, n_gat_layers, edge_geometry,
-                                                   attention)
+                                                   attention, attention_dropout)
         self.n_total_feat = self.n_feat + (self.hidden_dim if self.use_context else 0)
         self.decoder = nn.Sequential(nn.Dropout(drop_prob),
                                      nn.Linear(self.n_total_feat, self.n_total_feat),
@@ -492,7 +532,7 @@ class CoVA(nn.Module):
                          n_heads=n_heads, n_gat_layers=n_gat_layers, roi_op=roi_op,
                          sampling_ratio=int(sampling_ratio), roi_aligned=bool(roi_aligned),
                          backbone_layers=backbone_layers, edge_geometry=bool(edge_geometry) and bool(use_context),
-                         attention=attention)
+                         attention=attention, attention_dropout=attention_dropout if use_context else 0.0)
         self._param_keys = [k for k, _ in self.named_parameters()]
         self._conv_keys = [k for k in self._param_keys if k.startswith("convnet.")]
         self._bbox_keys = [k for k in self._param_keys if k.startswith("bbox_feat_encoder.")]

@@ -20,7 +20,7 @@ import os
 import torch
 
 from . import engine
-from .weights import state_dict_spec
+from .weights import check_attention_dropout, state_dict_spec
 
 _BUF_SUFFIX = ("running_mean", "running_var", "num_batches_tracked")
 
@@ -266,6 +266,8 @@ class HotPathTrainer:
         if float(norm_type) != 2.0:
             raise ValueError("norm_type must be 2.0 (the only gradient norm implemented), got %r" % (norm_type,))
         self.cfg = dict(cfg)
+        if "attention_dropout" in cfg:          # (no weights: not an argument of state_dict_spec)
+            self.cfg["attention_dropout"] = check_attention_dropout(cfg["attention_dropout"])
         self.device = torch.device(device)
         spec = state_dict_spec(**{k: cfg[k] for k in ("roi_output_size", "n_classes", "use_context",
                                                      "hidden_dim", "bbox_hidden_dim", "n_additional_feat",

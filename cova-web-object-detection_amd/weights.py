@@ -24,6 +24,17 @@ def check_attention(attention):
     return attention
 
 
+def check_attention_dropout(p):
+    """Rate of the dropout on the attention coefficients (cova_gat_fwd_drop): a real number in [0, 1) -> float."""
+    try:
+        ok = not isinstance(p, bool) and 0.0 <= float(p) < 1.0          # (NaN fails both comparisons)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("attention_dropout must be a number in [0, 1), got %r" % (p,))
+    return float(p)
+
+
 def attention_of(weight, D, prefix="gat."):
     """The scoring mode an ``attention_layer.weight`` belongs to, by its width: [1, 2D] is 'gat', [1, D] is 'gatv2'."""
     width = int(weight.shape[-1]) if weight.dim() else -1

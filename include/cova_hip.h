@@ -484,6 +484,43 @@ int cova_gat2_bwd(const float *g, int ldg, const float *Wh, int ldw, const float
                   int N, int K, int D, float slope, float *dWh /*[N,2D]*/, int lddw, float *d_att_w /*[D]*/,
                   float *d_att_b /*[1]*/, float *d_edge_w /*[8] or NULL*/, const int *csr, float *du /*[N,K]*/,
                   float *workspace, void *stream);
+/* ---- attention dropout (opt-in: CoVA(attention_dropout=p); Velickovic et al., ICLR 2018, section 3.3) ----
+ * Inverted dropout on the softmax output of both scoring modes.  For the flat slot e = i*K + k:
+ *   keep[e]   = hash_uniform(seed, e) >= p     (f32 compare; the counter hash of cova_dropout_fwd, element e of stream seed)
+ *   alphad[e] = keep[e] ? attn[e] * inv : 0    inv = 1.f / (1.f - p), ONE rounded f32 multiply
+ *   h'[i]     = sum_k alphad[i,k] * Wh[ctx[i,k], D:2D]      (pads weigh 0, slot order as without dropout)
+ * attn [N,K] as written is the softmax output BEFORE dropout, bit-equal to the plain entry point's.  Backward:
+ *   dattn[e] = keep[e] ? (g[i] . Wh[j, D:2D]) * inv : 0;   du = attn * (dattn - sum_k attn * dattn) [* LeakyReLU'] -- a dropped
+ *   slot still takes -attn * sum through the softmax -- and the destination side weighs g[i] with alphad[e].
+ * No mask is stored: the forward, the source-side and the destination-side kernels regenerate keep from (seed, e) and form
+ * alphad by the same expression.  A row whose valid slots are all dropped has h' = 0 and passes no gradient.  The same
+ * launches as the plain entry points, on the DROP instantiations of the wave-per-node kernels: fixed summation orders, no
+ * float atomics, bit-identical reruns for one seed.
+ * cova_gat_fwd_drop / cova_gat_bwd_drop: cova_gat_fwd / cova_gat_bwd, or with phi and edge_w (backward: and d_edge_w and
+ * workspace) -- all of the group or none -- cova_gat_fwd_edge / cova_gat_bwd_edge.  cova_gat2_fwd_drop / cova_gat2_bwd_drop:
+ * cova_gat2_fwd / cova_gat2_bwd.  p outside [0, 1) (NaN included), a mismatched group and every bad argument of the plain
+ * entry points return COVA_ERR_BAD_ARG before anything is launched; N == 0 is COVA_OK where the plain entry point has it
+ * (not in cova_gat_bwd_drop). */
+int cova_gat_fwd_drop(const float *Wh, int ldw, const float *att_w /*[2D]*/, const float *att_b /*[1]*/,
+                      const int64_t *ctx /*[N,K]*/, const float *phi /*[N,K,8] or NULL*/, const float *edge_w /*[8] or NULL*/,
+                      int N, int K, int D, float slope, float p, unsigned long long seed, float *s /*[N]*/,
+                      float *t /*[N]*/, float *attn /*[N,K]*/, float *hprime, int ldh, void *stream);
+int cova_gat_bwd_drop(const float *g, int ldg, const float *Wh, int ldw, const float *s, const float *t,
+                      const float *attn, const int64_t *ctx, const float *att_w, const float *phi /*[N,K,8] or NULL*/,
+                      const float *edge_w /*[8] or NULL*/, int N, int K, int D, float slope, float p,
+                      unsigned long long seed, float *dWh /*[N,2D]*/, int lddw, float *ds /*[N]*/, float *dt /*[N]*/,
+                      float *d_att_w /*[2D]*/, float *d_att_b /*[1]*/, float *d_edge_w /*[8] or NULL*/, const int *csr,
+                      float *du /*[N,K]*/, float *workspace /*or NULL*/, void *stream);
+int cova_gat2_fwd_drop(const float *Wh, int ldw, const float *att_w /*[D]*/, const float *att_b /*[1]*/,
+                       const int64_t *ctx /*[N,K]*/, const float *phi /*[N,K,8] or NULL*/,
+                       const float *edge_w /*[8] or NULL*/, int N, int K, int D, float slope, float p,
+                       unsigned long long seed, float *attn /*[N,K]*/, float *hprime, int ldh, void *stream);
+int cova_gat2_bwd_drop(const float *g, int ldg, const float *Wh, int ldw, const float *attn, const int64_t *ctx,
+                       const float *att_w /*[D]*/, const float *phi /*[N,K,8] or NULL*/,
+                       const float *edge_w /*[8] or NULL*/, int N, int K, int D, float slope, float p,
+                       unsigned long long seed, float *dWh /*[N,2D]*/, int lddw, float *d_att_w /*[D]*/,
+                       float *d_att_b /*[1]*/, float *d_edge_w /*[8] or NULL*/, const int *csr, float *du /*[N,K]*/,
+                       float *workspace, void *stream);
 
 /* ------------------------------------------------------------------ decoder tail, loss, optimizer
  * replaces: nn.Dropout (models.py:84,88), nn.Linear(T, n_classes) (models.py:89),
