@@ -1,7 +1,8 @@
 // Parameter-group optimizers and the global gradient norm of HotPathTrainer (trainer.py): torch.optim.Adam (L2 added to the
 // gradient), AdamW and SGD (momentum, dampening, nesterov) over a table of flat-buffer segments with per-group
 // hyper-parameters, and torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) as two deterministic launches.
-// Also the averaged copy of the weights (EMA / equal-weight running mean, HotPathTrainer(average=)) over the same table.
+// Also the averaged copy of the weights (EMA / equal-weight running mean, HotPathTrainer(average=)) and the accumulation of
+// the gradient bucket over micro-batches (HotPathTrainer(accumulate_steps=)) over the same table.
 //
 // Segment table: int64 rows {lo, hi, group, start}.  Row r covers flat elements [lo, hi) of every buffer; `start` is the
 // sum of the lengths of the rows before it, so the rows tile one concatenated index space [0, total).  A block owns a
@@ -285,6 +286,73 @@ __global__ __launch_bounds__(OPT_THREADS) void weight_average_kernel(float *__re
     }
 }
 
+enum { ACC_OPEN = 0, ACC_ADD = 1, ACC_CLOSE = 2, ACC_ADD_CLOSE = 3 };
+
+// one element of cova_grad_accumulate: the sum and the product each round to f32 on their own (no contraction), so every
+// mode is a numpy float32 statement bit for bit and a scale of 1 leaves the sum's bits
+template <int MODE>
+__device__ __forceinline__ float accumulate(float av, float gv, float s)
+{
+#pragma clang fp contract(off)
+    if (MODE == ACC_OPEN) return gv;
+    if (MODE == ACC_ADD) return av + gv;
+    if (MODE == ACC_CLOSE) return av * s;
+    const float t = av + gv;
+    return t * s;
+}
+
+// flat elements [a, b) of one row piece, already cut to the clip range; open and add write acc and only read g, close and
+// add-close write g and only read acc (open does not read acc at all, close does not read g)
+template <int MODE>
+__device__ __forceinline__ void accumulate_range(float *__restrict__ acc, float *__restrict__ g, long long a, long long b,
+                                                 float s, bool vec4)
+{
+    constexpr bool reads_acc = MODE != ACC_OPEN, reads_g = MODE != ACC_CLOSE;
+    float *__restrict__ dst = MODE == ACC_OPEN || MODE == ACC_ADD ? acc : g;
+    if (vec4 && ((a | b) & 3) == 0) {
+        for (long long i = a + 4 * (long long)threadIdx.x; i < b; i += 4 * OPT_THREADS) {
+            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 av = reads_acc ? *reinterpret_cast<const float4 *>(acc + i) : z;
+            const float4 gv = reads_g ? *reinterpret_cast<const float4 *>(g + i) : z;
+            float4 o;
+            o.x = accumulate<MODE>(av.x, gv.x, s);
+            o.y = accumulate<MODE>(av.y, gv.y, s);
+            o.z = accumulate<MODE>(av.z, gv.z, s);
+            o.w = accumulate<MODE>(av.w, gv.w, s);
+            *reinterpret_cast<float4 *>(dst + i) = o;
+        }
+        return;
+    }
+    for (long long i = a + threadIdx.x; i < b; i += OPT_THREADS)
+        dst[i] = accumulate<MODE>(reads_acc ? acc[i] : 0.f, reads_g ? g[i] : 0.f, s);
+}
+
+// the slice-per-block walk of weight_average_kernel over the same table (group ignored); every piece is cut to the clip
+// range [c0, c1) of flat elements before it is touched
+template <int MODE>
+__global__ __launch_bounds__(OPT_THREADS) void grad_accumulate_kernel(float *__restrict__ acc, float *__restrict__ g,
+                                                                     long long n, const long long *__restrict__ seg,
+                                                                     int n_seg, long long total, long long c0,
+                                                                     long long c1, float s, int vec4)
+{
+    __shared__ FirstRow s_first;
+    const long long v0 = (long long)blockIdx.x * OPT_SLICE;
+    const long long v1 = v0 + OPT_SLICE < total ? v0 + OPT_SLICE : total;
+    const int first = find_first_row(seg, n_seg, v0, &s_first);
+    for (long long pos = v0, r = first; pos < v1 && r < n_seg; ++r) {
+        const long long *row = row_at(seg, (int)r, first, s_first);
+        const long long lo = row[0], hi = row[1], st = row[3];
+        const long long end = st + (hi - lo) < v1 ? st + (hi - lo) : v1;
+        if (lo >= 0 && hi <= n && pos >= st) {               // a malformed row is skipped, never written out of bounds
+            long long a = lo + (pos - st), b = lo + (end - st);
+            a = a > c0 ? a : c0;
+            b = b < c1 ? b : c1;
+            if (a < b) accumulate_range<MODE>(acc, g, a, b, s, vec4 != 0);
+        }
+        pos = end;
+    }
+}
+
 inline bool aligned16(const void *ptr) { return ((uintptr_t)ptr & 15) == 0; }
 
 }  // namespace
@@ -366,6 +434,35 @@ COVA_API int cova_weight_average(float *avg, const float *p, long long n, const 
     const dim3 grid((unsigned)cdivll(total, OPT_SLICE)), block(OPT_THREADS);
     hipLaunchKernelGGL(weight_average_kernel, grid, block, 0, (hipStream_t)stream, avg, p, n, segs, n_seg, total, w,
                        (int)(aligned16(avg) && aligned16(p)));
+    COVA_LAUNCH_CHECK();
+    return COVA_OK;
+}
+
+COVA_API int cova_grad_accumulate(int mode, float *acc, float *g, long long n, const long long *segs, int n_seg,
+                                  long long total, long long clip_lo, long long clip_hi, double scale, void *stream)
+{
+    COVA_REQUIRE(mode >= ACC_OPEN && mode <= ACC_ADD_CLOSE);
+    COVA_REQUIRE(n_seg >= 0 && total >= 0);
+    if (n_seg == 0 || total == 0) return COVA_OK;
+    COVA_REQUIRE(acc && g && segs && n > 0 && total <= n);
+    const long long c0 = clip_lo > 0 ? clip_lo : 0, c1 = clip_hi < n ? clip_hi : n;
+    if (c0 >= c1) return COVA_OK;                            // an empty clip touches nothing: no launch
+    const float s = (float)scale;                            // converted once: the kernel multiplies by this f32
+    const int vec4 = aligned16(acc) && aligned16(g);
+    const dim3 grid((unsigned)cdivll(total, OPT_SLICE)), block(OPT_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == ACC_OPEN)
+        hipLaunchKernelGGL(grad_accumulate_kernel<ACC_OPEN>, grid, block, 0, st, acc, g, n, segs, n_seg, total, c0, c1, s,
+                           vec4);
+    else if (mode == ACC_ADD)
+        hipLaunchKernelGGL(grad_accumulate_kernel<ACC_ADD>, grid, block, 0, st, acc, g, n, segs, n_seg, total, c0, c1, s,
+                           vec4);
+    else if (mode == ACC_CLOSE)
+        hipLaunchKernelGGL(grad_accumulate_kernel<ACC_CLOSE>, grid, block, 0, st, acc, g, n, segs, n_seg, total, c0, c1, s,
+                           vec4);
+    else
+        hipLaunchKernelGGL(grad_accumulate_kernel<ACC_ADD_CLOSE>, grid, block, 0, st, acc, g, n, segs, n_seg, total, c0,
+                           c1, s, vec4);
     COVA_LAUNCH_CHECK();
     return COVA_OK;
 }

@@ -295,7 +295,11 @@ def fit(trainer, train_set, val_set, n_epochs, batch_size, sampling_fraction=0.9
     ``trainer.averaged_weights()`` and the best state kept or saved is ``averaged_state_dict()``, so save-best and
     patience follow the averaged model; an evaluation before the average has started (``n_averaged == 0``) uses the
     live weights and state.  The history's ``averaged`` says which it was.  The final reload goes through
-    ``load_state_dict``, after which live parameters and average both hold the best state."""
+    ``load_state_dict``, after which live parameters and average both hold the best state.
+    A trainer built with ``accumulate_steps`` n > 1: ``trainer.flush()`` follows the last batch of every epoch, before the
+    metrics are read, before any evaluation and before ``lr_schedule`` applies, so an epoch whose batch count is no
+    multiple of n ends with a smaller update and no gradient crosses an epoch or an evaluation.  The history's ``updates``
+    is the number of parameter updates of the epoch."""
     if use_average and trainer.average is None:
         raise ValueError("use_average needs a trainer built with average=\"ema\" or \"swa\"")
     if augment is not None and train_features is not None:
@@ -315,18 +319,24 @@ def fit(trainer, train_set, val_set, n_epochs, batch_size, sampling_fraction=0.9
     best_state, history, epochs_run = None, [], 0
     aug_kw = {} if augment is None else dict(augment=augment)
     trainer.metrics.reset()
+    accumulating = getattr(trainer, "accumulate_steps", 1) > 1
     for epoch in range(1, ctl.n_epochs + 1):
-        start = time.time()
+        first_update = trainer.update_count if accumulating else 0
+        start, updates = time.time(), 0
         for batch in train_set.batches(batch_size, shuffle=True, sampling_fraction=sampling_fraction, seed=seed,
                                        epoch=epoch, rank=rank, world_size=world_size, features=train_features, **aug_kw):
             trainer.train_step(batch)
+            updates += 1                                  # (one update per batch unless the trainer accumulates)
+        if accumulating:
+            trainer.flush()
+            updates = trainer.update_count - first_update
         m = trainer.metrics.read()
         trainer.metrics.reset()
         n, den = m["kept"], m["loss_denominator"]
         rec = dict(epoch=epoch, loss=m["loss_numerator"] / den if den > 0 else 0.0,
                    accuracy=100.0 * float(np.trace(m["confusion"])) / n if n else 0.0, boxes=n,
                    lr=[g["lr"] for g in trainer.param_groups], eval_acc=None, class_acc=None, is_best=False,
-                   averaged=False)
+                   averaged=False, updates=updates)
         rec["seconds"] = time.time() - start
         if rank == 0:
             _log(log_file, ["Epoch: %2d  Loss: %.4f  Accuracy: %.2f%%  (%.2fs)"

@@ -15,6 +15,7 @@ single-device step on the concatenated batch.
 from collections import OrderedDict, namedtuple
 
 import contextlib
+import numbers
 import os
 
 import torch
@@ -136,6 +137,22 @@ def check_average_options(average, decay, warmup, start, every, buffers):
                        bool(buffers), 0)
 
 
+ACC_OPEN, ACC_ADD, ACC_CLOSE, ACC_ADD_CLOSE = range(4)          # the modes of cova_grad_accumulate
+
+
+def check_accumulate_steps(n):
+    """The checked ``accumulate_steps`` of HotPathTrainer: an integer >= 1 (not a bool, a float or a string)."""
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 1:
+        raise ValueError("accumulate_steps must be an integer >= 1, got %r" % (n,))
+    return int(n)
+
+
+def accumulate_scale(loss_reduction, m):
+    """``scale`` (a double) of the launch that closes an update made from ``m`` micro-batches: 1 for the "sum"
+    criterion, 1 / m for "mean" (the mean of the micro-batch means, the usual ``loss / accum_steps``)."""
+    return 1.0 if loss_reduction == "sum" else 1.0 / int(m)
+
+
 def shard_pages(n_pages, rank, world_size):
     """Contiguous page range [lo, hi) of this rank (whole pages only)."""
     base, rem = divmod(n_pages, world_size)
@@ -250,7 +267,17 @@ class HotPathTrainer:
     ``average_start`` on, every ``average_every`` steps, with the weight average_weight() gives (``average_decay``,
     ``average_warmup``).  ``trainer.average`` is the record, averaged_state_dict() the averaged model, and inside
     ``with trainer.averaged_weights():`` predict / evaluate / loss / evaluate_split run on it without a copy.  The
-    schedule is host integers: no host read, and with ``average=None`` no tensor and no launch is added."""
+    schedule is host integers: no host read, and with ``average=None`` no tensor and no launch is added.
+
+    Gradient accumulation ("Gradient accumulation"): ``accumulate_steps`` n > 1 makes one parameter
+    update from n micro-batches: train_step() folds the gradient bucket into a second flat bucket with one
+    cova_grad_accumulate launch over the trainable runs, and on the n-th micro-step closes the cycle into the gradient
+    bucket and runs optimizer_step()'s path (all-reduce, clipping, update, averaging) on the accumulated gradient;
+    flush() makes the update from the micro-batches pending (``accumulated``).  ``loss_reduction="sum"`` accumulates the
+    plain sum (exact: the gradient of the summed loss), "mean" scales by 1 / m, the mean of the m micro-batch means, which
+    is not the mean over the union when micro-batches score different numbers of boxes.  ``step_count`` counts
+    micro-batches (the dropout streams), ``update_count`` parameter updates (Adam's bias correction, the averaging
+    schedule).  With the default 1 no tensor and no launch is added and update_count is step_count."""
 
     def __init__(self, cfg, state_dict, device, lr=5e-4, weight_decay=1e-3, betas=(0.9, 0.999),
                  eps=1e-8, world_size=1, process_group=None, dropout_seed=123, sync_bn=False, frozen=(), bn_eval=(),
@@ -258,7 +285,8 @@ class HotPathTrainer:
                  max_grad_norm=None, norm_type=2.0, class_weight=None, label_smoothing=0.0, focal_gamma=0.0,
                  ignore_index=None, loss_reduction="sum", track_metrics=False, hard_negative_ratio=None,
                  hard_negative_min=0, page_rank_weight=0.0, average=None, average_decay=0.999, average_warmup=None,
-                 average_start=0, average_every=1, average_buffers=True):
+                 average_start=0, average_every=1, average_buffers=True, accumulate_steps=1):
+        self.accumulate_steps = check_accumulate_steps(accumulate_steps)
         self._avg = check_average_options(average, average_decay, average_warmup, average_start, average_every,
                                           average_buffers)
         if optimizer not in OPTIMIZERS:
@@ -303,6 +331,7 @@ class HotPathTrainer:
         self._setup_criterion(class_weight, label_smoothing, focal_gamma, ignore_index, loss_reduction, track_metrics)
         self._setup_mining(hard_negative_ratio, hard_negative_min)
         self._setup_rank(page_rank_weight)
+        self._setup_accumulate()
         self._setup_average()
         self._ar_events = []              # (start, end) HIP events around the collective waits of optimizer_step
         self.measure_allreduce = True     # record them (up to 4096 steps; exposed_allreduce_ms() drains the list)
@@ -384,11 +413,11 @@ class HotPathTrainer:
         if self._avg.buffers:
             self.abbucket.flat.copy_(self.bbucket.flat)
             self.atracked.copy_(self.tracked)
-        self.n_averaged = 1 if self.step_count >= self._avg.start else 0
+        self.n_averaged = 1 if self.update_count >= self._avg.start else 0
 
     def _average_step(self):
         """End of optimizer_step(): host integers decide, the device work is one launch per averaged flat buffer."""
-        a, s = self._avg, self.step_count
+        a, s = self._avg, self.update_count
         if s < a.start:
             return
         if self.n_averaged == 0:                            # step ``average_start``, or the first step after a resume past it
@@ -411,7 +440,7 @@ class HotPathTrainer:
         are the live ones."""
         self._need_average("averaged_state_dict")
         if self.n_averaged == 0:
-            raise RuntimeError("the average has not started (average_start=%d, step %d)" % (self._avg.start, self.step_count))
+            raise RuntimeError("the average has not started (average_start=%d, step %d)" % (self._avg.start, self.update_count))
         sd = OrderedDict((k, v.detach().clone()) for k, v in self.abucket.views.items())
         sd.update((k, v.detach().clone()) for k, v in self._avg_buffers.items())
         return sd
@@ -425,13 +454,59 @@ class HotPathTrainer:
         self._need_average("averaged_weights")
         self._not_averaged("averaged_weights")
         if self.n_averaged == 0:
-            raise RuntimeError("the average has not started (average_start=%d, step %d)" % (self._avg.start, self.step_count))
+            raise RuntimeError("the average has not started (average_start=%d, step %d)" % (self._avg.start, self.update_count))
         live = self.params, self.buffers
         self.params, self.buffers, self._avg_active = self.abucket.views, self._avg_buffers, True
         try:
             yield self
         finally:
             (self.params, self.buffers), self._avg_active = live, False
+
+    def _setup_accumulate(self):
+        """The accumulator bucket and the device table of the trainable runs ({lo, hi, 0, start} rows as
+        cova_optim_step's; frozen tensors are left out).  Nothing is allocated with ``accumulate_steps=1``."""
+        self.accumulated, self._update_count = 0, 0
+        self._close = None                   # the closing micro-step's scale while its forward_backward runs
+        if self.accumulate_steps == 1:
+            return
+        self.accbucket = FlatBucket(OrderedDict((k, sh) for k, (_, _, sh) in self.pbucket.offsets.items()), self.device)
+        runs = group_runs(self.pbucket.offsets, self.pbucket.flat.numel(), self.frozen, dict.fromkeys(self.params, 0))
+        rows, start = [], 0
+        for lo, hi, _ in runs:
+            rows.append((lo, hi, 0, start))
+            start += hi - lo
+        self._acc_rows, self._acc_total = rows, start
+        self._acc_seg = torch.tensor(rows, dtype=torch.int64).view(-1, 4).to(self.device)
+
+    @property
+    def update_count(self):
+        """Parameter updates made so far: what Adam's bias correction and the averaging schedule count.  With
+        ``accumulate_steps=1`` it is ``step_count``."""
+        return self._update_count if self.accumulate_steps > 1 else self.step_count
+
+    def _no_pending(self, what):
+        if self.accumulated:
+            raise ValueError("%s with %d micro-batch(es) accumulated: finish the cycle with train_step() or make the "
+                             "update with flush() first" % (what, self.accumulated))
+
+    def _accumulate(self, mode, scale=1.0, lo=0, hi=None):
+        """One cova_grad_accumulate launch over the trainable runs, cut to the flat range [lo, hi)."""
+        n = self.gbucket.flat.numel()
+        engine.call("cova_grad_accumulate", mode, self.accbucket.flat, self.gbucket.flat, n, self._acc_seg,
+                    len(self._acc_rows), self._acc_total, lo, n if hi is None else hi, scale)
+
+    def flush(self):
+        """Make the parameter update from the micro-batches pending (``accumulated`` = m >= 1, scale 1 / m with
+        ``loss_reduction="mean"``): one closing cova_grad_accumulate launch, then optimizer_step()'s path.  -> whether an
+        update happened; nothing is launched with none pending.  Under data parallelism a collective: every rank must
+        hold the same ``accumulated``."""
+        self._not_averaged("flush")
+        if not self.accumulated:
+            return False
+        self._accumulate(ACC_CLOSE, accumulate_scale(self.loss_options["loss_reduction"], self.accumulated))
+        self.accumulated = 0
+        self._optimizer_step()
+        return True
 
     def _average_tensors(self):
         """The tensors of the average that travel with broadcast_state / a broadcast optimizer state."""
@@ -650,6 +725,7 @@ class HotPathTrainer:
         resume) from ONE state even when the ranks were built from rank-local checkpoints."""
         import torch.distributed as dist
         self._not_averaged("broadcast_state")
+        self._no_pending("broadcast_state")
         extra = [self.momentum_buffer] if self.momentum_buffer is not None else []
         if self._avg is not None:
             extra = extra + [t for t in self._average_tensors() if t.numel()]
@@ -657,9 +733,12 @@ class HotPathTrainer:
             dist.broadcast(t, src=src, group=self.group)
         flags = [int(b) for b in self._buf_exists] if self.momentum_buffer is not None else []
         counter = [self.n_averaged] if self._avg is not None else []
-        step = torch.tensor([self.step_count] + flags + counter, dtype=torch.int64, device=self.device)
+        updates = [self._update_count] if self.accumulate_steps > 1 else []
+        step = torch.tensor(updates + [self.step_count] + flags + counter, dtype=torch.int64, device=self.device)
         dist.broadcast(step, src=src, group=self.group)
         got = step.tolist()
+        if updates:
+            self._update_count = int(got.pop(0))
         self.step_count = int(got[0])
         self._buf_exists = [bool(b) for b in got[1:1 + len(flags)]] if flags else self._buf_exists
         if counter:
@@ -724,12 +803,15 @@ class HotPathTrainer:
             import torch.distributed as dist
             for t in [self.pbucket.flat] + [self.buffers[k] for k in sorted(self.buffers)]:
                 dist.broadcast(t, src=0, group=self.group)
+        self.accumulated = 0                 # pending micro-batches belonged to the parameters just replaced
         if self._avg is not None:
             self.reset_average()
 
     def optimizer_state_dict(self):
         """Adam moments + step count (the reference keeps no optimizer state in its checkpoints, train.py:84;
-        with this a run can be resumed exactly)."""
+        with this a run can be resumed exactly).  With ``accumulate_steps`` > 1 also "updates", the parameter updates;
+        it is taken at a cycle boundary (ValueError while micro-batches are pending)."""
+        self._no_pending("optimizer_state_dict")
         st = dict(step=self.step_count, exp_avg=self.exp_avg.detach().clone(),
                   exp_avg_sq=self.exp_avg_sq.detach().clone(), hp={k: self.hp[k] for k in _ADAM_HP})
         if self._fused:     # (with no new option the format stays today's: an Adam checkpoint has no "algorithm")
@@ -737,6 +819,8 @@ class HotPathTrainer:
                       groups=[dict(params=list(g["params"]), **{k: g[k] for k in _GROUP_HP}) for g in self._groups],
                       momentum_buffer=None if self.momentum_buffer is None else self.momentum_buffer.detach().clone(),
                       momentum_buffer_exists=list(self._buf_exists))
+        if self.accumulate_steps > 1:
+            st["updates"] = self.update_count
         if self._avg is not None:
             st["average"] = dict(self.average._asdict(), flat=self.abucket.flat.detach().clone(),
                                  buffers_flat=self.abbucket.flat.detach().clone() if self._avg.buffers else None,
@@ -745,6 +829,10 @@ class HotPathTrainer:
 
     def _check_optimizer_state(self, state):
         """(what is wrong with `state` beyond the Adam fields, or None) -- a checkpoint without "algorithm" is Adam's."""
+        updates = state.get("updates")
+        if self.accumulate_steps == 1 and updates is not None and int(updates) != int(state.get("step", updates)):
+            return ("optimizer state of %d parameter updates in %d steps: it was written with accumulate_steps > 1 and "
+                    "loads into a trainer built with accumulate_steps > 1 only" % (int(updates), int(state["step"])))
         algorithm = state.get("algorithm", "adam")
         if algorithm != self.optimizer:
             return "optimizer state of algorithm %r, this trainer runs %r" % (algorithm, self.optimizer)
@@ -791,6 +879,8 @@ class HotPathTrainer:
         if problem is not None:
             raise ValueError(problem)
         self.step_count = int(state["step"])
+        self._update_count = int(state.get("updates", self.step_count))
+        self.accumulated = 0
         self.exp_avg.copy_(state["exp_avg"].to(self.device).view_as(self.exp_avg))
         self.exp_avg_sq.copy_(state["exp_avg_sq"].to(self.device).view_as(self.exp_avg_sq))
         self.hp.update(state.get("hp", {}))
@@ -822,11 +912,14 @@ class HotPathTrainer:
                 dist.broadcast(counter, src=0, group=self.group)
                 self.n_averaged = int(counter.item())
             b1, b2 = self.hp["betas"]
-            meta = torch.tensor([float(self.step_count), self.hp["lr"], self.hp["weight_decay"], b1, b2, self.hp["eps"]],
-                                dtype=torch.float64, device=self.device)
+            updates = [float(self._update_count)] if self.accumulate_steps > 1 else []
+            meta = torch.tensor([float(self.step_count), self.hp["lr"], self.hp["weight_decay"], b1, b2, self.hp["eps"]]
+                                + updates, dtype=torch.float64, device=self.device)
             dist.broadcast(meta, src=0, group=self.group)
             m = meta.tolist()
             self.step_count = int(m[0])
+            if updates:
+                self._update_count = int(m[6])
             self.hp.update(lr=m[1], weight_decay=m[2], betas=(m[3], m[4]), eps=m[5])
             if self._fused:
                 self._broadcast_groups()
@@ -885,7 +978,9 @@ class HotPathTrainer:
                 if rank_weight != 0.0:
                     self.last_rank_lists, self.last_rank_acc = self._rank_term(logits, batch, rank_weight, loss, dl)
             self._head_work = None
-            overlap = self.world_size > 1 and engine.OPTIONS.overlap_allreduce
+            # (an accumulating trainer exchanges gradients on the closing micro-step of train_step() only)
+            overlap = (self.world_size > 1 and engine.OPTIONS.overlap_allreduce
+                       and (self.accumulate_steps == 1 or self._close is not None))
             engine.model_bwd(sv, dl, self.params, self.grads,
                              after_head=self._reduce_head if overlap else None, plan=self.plan)
         finally:
@@ -921,11 +1016,19 @@ class HotPathTrainer:
         lo = self._head_offset()
         if lo >= self.gbucket.flat.numel():
             return
+        if self._close is not None:          # the head part of the cycle closes here, the conv part after model_bwd
+            self._accumulate(ACC_ADD_CLOSE, self._close, lo, self.gbucket.flat.numel())
         self._head_work = self.gbucket.all_reduce_range(lo, self.gbucket.flat.numel(), self.group,
                                                         async_op=True)
 
     def optimizer_step(self):
         self._not_averaged("optimizer_step")
+        self._no_pending("optimizer_step")
+        self._optimizer_step()
+
+    def _optimizer_step(self):
+        if self.accumulate_steps > 1:
+            self._update_count += 1
         self._update_parameters()
         if self._avg is not None:
             self._average_step()
@@ -957,12 +1060,12 @@ class HotPathTrainer:
         b1, b2 = self.hp["betas"]
         if not self.frozen:
             engine.call("cova_adam_step", self.pbucket.flat, self.gbucket.flat, self.exp_avg,
-                        self.exp_avg_sq, self.pbucket.flat.numel(), self.step_count, self.hp["lr"], b1, b2,
+                        self.exp_avg_sq, self.pbucket.flat.numel(), self.update_count, self.hp["lr"], b1, b2,
                         self.hp["eps"], self.hp["weight_decay"])
             return
         for lo, hi in self._adam_runs:          # frozen tensors: parameters and moments untouched
             engine.call("cova_adam_step", self.pbucket.flat[lo:hi], self.gbucket.flat[lo:hi], self.exp_avg[lo:hi],
-                        self.exp_avg_sq[lo:hi], hi - lo, self.step_count, self.hp["lr"], b1, b2,
+                        self.exp_avg_sq[lo:hi], hi - lo, self.update_count, self.hp["lr"], b1, b2,
                         self.hp["eps"], self.hp["weight_decay"])
 
     def _fused_step(self):
@@ -990,16 +1093,40 @@ class HotPathTrainer:
         sgd = self.optimizer == "sgd"
         engine.call("cova_optim_step", OPTIMIZERS.index(self.optimizer), flat, self.gbucket.flat,
                     self.momentum_buffer if sgd else self.exp_avg, None if sgd else self.exp_avg_sq, n, self._seg,
-                    len(self.optim_runs), self._seg_total, table.data_ptr(), len(self._groups), self.step_count, gscale)
+                    len(self.optim_runs), self._seg_total, table.data_ptr(), len(self._groups), self.update_count, gscale)
         if sgd:
             self._buf_exists = [b or g["momentum"] != 0 for g, b in zip(self._groups, self._buf_exists)]
 
     def train_step(self, batch, masks=None):
         """optimizer.zero_grad(); forward; loss; backward; optimizer.step()  (train.py:45-60).
-        Gradients are fully overwritten each step, so zero_grad is implicit."""
+        Gradients are fully overwritten each step, so zero_grad is implicit.
+
+        With ``accumulate_steps`` n > 1 this is one micro-step: forward and backward, then one cova_grad_accumulate launch
+        that opens (first micro-step of a cycle) or adds to the accumulator; the n-th closes the cycle into the gradient
+        bucket (scale 1 / n with ``loss_reduction="mean"``) and makes the update.  Only that one exchanges gradients
+        between ranks.  Returns the micro-batch's (loss, pred)."""
         self._not_averaged("train_step")
-        loss, pred = self.forward_backward(batch, masks)
-        self.optimizer_step()
+        if self.accumulate_steps == 1:
+            loss, pred = self.forward_backward(batch, masks)
+            self.optimizer_step()
+            return loss, pred
+        m = self.accumulated + 1
+        if m < self.accumulate_steps:
+            loss, pred = self.forward_backward(batch, masks)
+            self._accumulate(ACC_OPEN if m == 1 else ACC_ADD)
+            self.accumulated = m
+            return loss, pred
+        self._close = accumulate_scale(self.loss_options["loss_reduction"], m)
+        try:
+            loss, pred = self.forward_backward(batch, masks)
+            if self._head_work is None:
+                self._accumulate(ACC_ADD_CLOSE, self._close)
+            elif not self.conv_frozen:       # the head part was closed before its all-reduce started (_reduce_head)
+                self._accumulate(ACC_ADD_CLOSE, self._close, 0, self._head_offset())
+        finally:
+            self._close = None
+        self.accumulated = 0
+        self._optimizer_step()
         return loss, pred
 
     @torch.no_grad()

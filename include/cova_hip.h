@@ -582,6 +582,26 @@ int cova_grad_norm(const float *g, long long n, const long long *segs, int n_seg
  * workspace, no host read. */
 int cova_weight_average(float *avg, const float *p, long long n, const long long *segs, int n_seg, long long total,
                         double one_minus_decay, void *stream);
+/* ------------------------------------------------------------------ gradient accumulation (optim.hip)
+ * replaces: the implicit `.grad +=` of several loss.backward() calls between two optimizer.step() calls and the
+ * `loss / accum_steps` scaling that goes with it, for HotPathTrainer(accumulate_steps=).
+ * g is the gradient bucket the backward overwrites at every micro-batch, acc the accumulator of the same layout.  Per
+ * element i of the table's rows that also lies in the clip range [clip_lo, clip_hi) of flat elements, with
+ * s = (float)scale converted once on the host:
+ *   mode 0 (open):      acc[i] = g[i]                     acc is not read: no memset, garbage (NaN) in it is harmless
+ *   mode 1 (add):       acc[i] = acc[i] + g[i]
+ *   mode 2 (close):     g[i]   = acc[i] * s               g is not read
+ *   mode 3 (add-close): g[i]   = (acc[i] + g[i]) * s
+ * the sum and the product each rounded to f32 on their own (no fused multiply-add): a numpy float32 statement bit for
+ * bit in a fixed order, and with scale == 1.0 the result is the sum's bits.  g is only read in modes 0 and 1, acc only
+ * read in modes 2 and 3.
+ * segs: the table of cova_optim_step ({lo, hi, group, start}, group ignored) under the rules of cova_weight_average:
+ * rows must not overlap; a row outside 0 <= lo <= hi <= n is skipped and never written; elements outside the rows
+ * (gaps, alignment padding, frozen tensors) or outside the clip keep their bits in both buffers.  The clip may cut a row
+ * at any element, aligned or not (it is clamped to [0, n]); an empty clip launches nothing.  n_seg == 0 or total == 0: no
+ * launch, returns 0; total > n is an error.  One launch, no atomics, no workspace, no host read. */
+int cova_grad_accumulate(int mode, float *acc, float *g, long long n, const long long *segs, int n_seg, long long total,
+                         long long clip_lo, long long clip_hi, double scale, void *stream);
 /* ------------------------------------------------------------------ configurable criterion (loss.hip)
  * replaces: F.cross_entropy(logits, labels, weight=, ignore_index=, label_smoothing=, reduction="sum" | "mean"), the focal
  * loss, and the per-step .item() reads of loss and accuracy (train.py:54,57), for HotPathTrainer(class_weight=,
