@@ -8,6 +8,9 @@
 // sum of the lengths of the rows before it, so the rows tile one concatenated index space [0, total).  A block owns a
 // fixed slice of that space, finds the row its slice begins in with one parallel pass over the table and walks on from
 // there.  Frozen tensors are simply not in the table.
+//
+// Every kernel over the table is the one walk (for_each_piece) around the one element loop (for_each_element) around an
+// operation struct with a four(i) and a one(i) body: a new flat-bucket kernel is a new operation, not a new walk.
 #include "common.h"
 
 namespace {
@@ -97,49 +100,88 @@ __device__ __forceinline__ void update(float &pv, float gv, float &mv, float &vv
     }
 }
 
-template <int ALGO>
-__device__ __forceinline__ bool uses_m(const OptGroup &q)
+// The walk of a block over its slice of SLICE concatenated elements: start() behind the table scan, then f(a, b, group) per
+// valid flat piece [a, b) of a row, in table order.  A malformed row (outside [0, n), or behind the position reached) is skipped.
+template <int SLICE, class Start, class Piece>
+__device__ __forceinline__ void for_each_piece(const long long *__restrict__ seg, int n_seg, long long total, long long n,
+                                               FirstRow *s_first, Start start, Piece f)
 {
-    return ALGO != ALGO_SGD || q.momentum != 0.f;
+    const long long v0 = (long long)blockIdx.x * SLICE;
+    const long long v1 = v0 + SLICE < total ? v0 + SLICE : total;
+    const int first = find_first_row(seg, n_seg, v0, s_first);
+    start();
+    for (long long pos = v0, r = first; pos < v1 && r < n_seg; ++r) {
+        const long long *row = row_at(seg, (int)r, first, *s_first);
+        const long long lo = row[0], hi = row[1], st = row[3];
+        const long long end = st + (hi - lo) < v1 ? st + (hi - lo) : v1;
+        if (lo >= 0 && hi <= n && pos >= st) f(lo + (pos - st), lo + (end - st), (int)row[2]);
+        pos = end;
+    }
 }
 
-// flat elements [a, b) of one group; gscale (nullable) is the clip coefficient, multiplied into g on load
-template <int ALGO>
-__device__ __forceinline__ void update_range(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
-                                             float *__restrict__ v, long long a, long long b, const OptGroup &q,
-                                             const float *__restrict__ gscale, float gs, bool vec4)
+// Flat elements [a, b) of one piece: op.four(i) on float4s when the buffers are 16-byte aligned (vec4) and the piece begins
+// and ends on a multiple of four, else op.one(i); a thread's elements and their order are the same for every operation.
+template <class Op>
+__device__ __forceinline__ void for_each_element(long long a, long long b, bool vec4, Op &op)
 {
-#pragma clang fp contract(off)
-    const bool has_m = uses_m<ALGO>(q), has_v = ALGO != ALGO_SGD;
     if (vec4 && ((a | b) & 3) == 0) {
-        for (long long i = a + 4 * (long long)threadIdx.x; i < b; i += 4 * OPT_THREADS) {
-            float4 pv = *reinterpret_cast<const float4 *>(p + i);
-            float4 gv = *reinterpret_cast<const float4 *>(g + i);
-            float4 mv = has_m ? *reinterpret_cast<const float4 *>(m + i) : make_float4(0.f, 0.f, 0.f, 0.f);
-            float4 vv = has_v ? *reinterpret_cast<const float4 *>(v + i) : make_float4(0.f, 0.f, 0.f, 0.f);
-            if (gscale) {
-                gv.x = gv.x * gs; gv.y = gv.y * gs;
-                gv.z = gv.z * gs; gv.w = gv.w * gs;
-            }
-            update<ALGO>(pv.x, gv.x, mv.x, vv.x, q);
-            update<ALGO>(pv.y, gv.y, mv.y, vv.y, q);
-            update<ALGO>(pv.z, gv.z, mv.z, vv.z, q);
-            update<ALGO>(pv.w, gv.w, mv.w, vv.w, q);
-            *reinterpret_cast<float4 *>(p + i) = pv;
-            if (has_m) *reinterpret_cast<float4 *>(m + i) = mv;
-            if (has_v) *reinterpret_cast<float4 *>(v + i) = vv;
-        }
+        for (long long i = a + 4 * (long long)threadIdx.x; i < b; i += 4 * OPT_THREADS) op.four(i);
         return;
     }
-    for (long long i = a + threadIdx.x; i < b; i += OPT_THREADS) {
+    for (long long i = a + threadIdx.x; i < b; i += OPT_THREADS) op.one(i);
+}
+
+// update<ALGO> of one group over (p, g, m, v); gscale (nullable) is the clip coefficient, multiplied into g on load
+template <int ALGO>
+struct UpdateOp {
+    float *p, *m, *v;
+    const float *g;
+    const OptGroup &q;
+    bool has_m, scaled;              // has_m: every algorithm but sgd without momentum keeps a first moment / buffer
+    float gs;
+    static constexpr bool has_v = ALGO != ALGO_SGD;
+
+    __device__ __forceinline__ void four(long long i) const
+    {
+#pragma clang fp contract(off)
+        float4 pv = *reinterpret_cast<const float4 *>(p + i);
+        float4 gv = *reinterpret_cast<const float4 *>(g + i);
+        float4 mv = has_m ? *reinterpret_cast<const float4 *>(m + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 vv = has_v ? *reinterpret_cast<const float4 *>(v + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+        if (scaled) {
+            gv.x = gv.x * gs; gv.y = gv.y * gs;
+            gv.z = gv.z * gs; gv.w = gv.w * gs;
+        }
+        update<ALGO>(pv.x, gv.x, mv.x, vv.x, q);
+        update<ALGO>(pv.y, gv.y, mv.y, vv.y, q);
+        update<ALGO>(pv.z, gv.z, mv.z, vv.z, q);
+        update<ALGO>(pv.w, gv.w, mv.w, vv.w, q);
+        *reinterpret_cast<float4 *>(p + i) = pv;
+        if (has_m) *reinterpret_cast<float4 *>(m + i) = mv;
+        if (has_v) *reinterpret_cast<float4 *>(v + i) = vv;
+    }
+
+    __device__ __forceinline__ void one(long long i) const
+    {
+#pragma clang fp contract(off)
         float pv = p[i], gv = g[i];
         float mv = has_m ? m[i] : 0.f, vv = has_v ? v[i] : 0.f;
-        if (gscale) gv = gv * gs;
+        if (scaled) gv = gv * gs;
         update<ALGO>(pv, gv, mv, vv, q);
         p[i] = pv;
         if (has_m) m[i] = mv;
         if (has_v) v[i] = vv;
     }
+};
+
+// (the buffers as __restrict__ parameters: as struct members alone the qualifier is lost and the sgd loops compile longer)
+template <int ALGO>
+__device__ __forceinline__ void update_range(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                             float *__restrict__ v, long long a, long long b, const OptGroup &q,
+                                             bool scaled, float gs, bool vec4)
+{
+    UpdateOp<ALGO> op = {p, m, v, g, q, ALGO != ALGO_SGD || q.momentum != 0.f, scaled, gs};
+    for_each_element(a, b, vec4, op);
 }
 
 template <int ALGO>
@@ -150,20 +192,12 @@ __global__ __launch_bounds__(OPT_THREADS) void optim_step_kernel(float *__restri
                                                                 const float *__restrict__ gscale, int vec4)
 {
     __shared__ FirstRow s_first;
-    const long long v0 = (long long)blockIdx.x * OPT_SLICE;
-    const long long v1 = v0 + OPT_SLICE < total ? v0 + OPT_SLICE : total;
-    const int first = find_first_row(seg, n_seg, v0, &s_first);
-    const float gs = gscale ? *gscale : 1.f;
-    for (long long pos = v0, r = first; pos < v1 && r < n_seg; ++r) {
-        const long long *row = row_at(seg, (int)r, first, s_first);
-        const long long lo = row[0], hi = row[1], st = row[3];
-        int grp = (int)row[2];
+    float gs;     // read behind the table scan: ahead of it the load and its null test stand alone, +0.2 us on a 6 us launch
+    for_each_piece<OPT_SLICE>(seg, n_seg, total, n, &s_first, [&] { gs = gscale ? *gscale : 1.f; },
+                              [&](long long a, long long b, int grp) {
         grp = grp < 0 ? 0 : (grp >= n_groups ? n_groups - 1 : grp);
-        const long long end = st + (hi - lo) < v1 ? st + (hi - lo) : v1;
-        if (lo >= 0 && hi <= n && pos >= st)                 // a malformed row is skipped, never written out of bounds
-            update_range<ALGO>(p, g, m, v, lo + (pos - st), lo + (end - st), G.g[grp], gscale, gs, vec4 != 0);
-        pos = end;
-    }
+        update_range<ALGO>(p, g, m, v, a, b, G.g[grp], gscale != nullptr, gs, vec4 != 0);
+    });
 }
 
 // double-precision sum over the block in a fixed order (wave butterflies, then the waves in index order)
@@ -178,6 +212,27 @@ __device__ __forceinline__ double block_sum(double x, double *s_wave)
     return t;
 }
 
+// this thread's sum of g^2 in double, in the order for_each_element hands the elements out
+struct SumSqOp {
+    const float *g;
+    double acc;
+
+    __device__ __forceinline__ void four(long long i)
+    {
+        const float4 x = *reinterpret_cast<const float4 *>(g + i);
+        acc += (double)x.x * x.x;
+        acc += (double)x.y * x.y;
+        acc += (double)x.z * x.z;
+        acc += (double)x.w * x.w;
+    }
+
+    __device__ __forceinline__ void one(long long i)
+    {
+        const double x = g[i];
+        acc += x * x;
+    }
+};
+
 // stage 1: partial[b] = sum of g^2 (in double) over concatenated elements [b * NORM_SLICE, (b + 1) * NORM_SLICE)
 __global__ __launch_bounds__(OPT_THREADS) void grad_sumsq_kernel(const float *__restrict__ g, long long n,
                                                                 const long long *__restrict__ seg, int n_seg,
@@ -185,36 +240,10 @@ __global__ __launch_bounds__(OPT_THREADS) void grad_sumsq_kernel(const float *__
 {
     __shared__ FirstRow s_first;
     __shared__ double s_wave[OPT_THREADS / 64];
-    const long long v0 = (long long)blockIdx.x * NORM_SLICE;
-    const long long v1 = v0 + NORM_SLICE < total ? v0 + NORM_SLICE : total;
-    double acc = 0.0;
-    if (v0 < v1) {
-        const int first = find_first_row(seg, n_seg, v0, &s_first);
-        for (long long pos = v0, r = first; pos < v1 && r < n_seg; ++r) {
-            const long long *row = row_at(seg, (int)r, first, s_first);
-            const long long lo = row[0], hi = row[1], st = row[3];
-            const long long end = st + (hi - lo) < v1 ? st + (hi - lo) : v1;
-            if (lo >= 0 && hi <= n && pos >= st) {
-                const long long a = lo + (pos - st), b = lo + (end - st);
-                if (vec4 && ((a | b) & 3) == 0) {
-                    for (long long i = a + 4 * (long long)threadIdx.x; i < b; i += 4 * OPT_THREADS) {
-                        const float4 x = *reinterpret_cast<const float4 *>(g + i);
-                        acc += (double)x.x * x.x;
-                        acc += (double)x.y * x.y;
-                        acc += (double)x.z * x.z;
-                        acc += (double)x.w * x.w;
-                    }
-                } else {
-                    for (long long i = a + threadIdx.x; i < b; i += OPT_THREADS) {
-                        const double x = g[i];
-                        acc += x * x;
-                    }
-                }
-            }
-            pos = end;
-        }
-    }
-    const double t = block_sum(acc, s_wave);
+    SumSqOp op = {g, 0.0};
+    for_each_piece<NORM_SLICE>(seg, n_seg, total, n, &s_first, [] {},
+                               [&](long long a, long long b, int) { for_each_element(a, b, vec4 != 0, op); });
+    const double t = block_sum(op.acc, s_wave);
     if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
@@ -248,42 +277,33 @@ __device__ __forceinline__ float average(float av, float pv, float w)
     return av + t;
 }
 
-// flat elements [a, b) of one row piece
-__device__ __forceinline__ void average_range(float *__restrict__ avg, const float *__restrict__ p, long long a,
-                                              long long b, float w, bool vec4)
-{
-    if (vec4 && ((a | b) & 3) == 0) {
-        for (long long i = a + 4 * (long long)threadIdx.x; i < b; i += 4 * OPT_THREADS) {
-            float4 av = *reinterpret_cast<const float4 *>(avg + i);
-            const float4 pv = *reinterpret_cast<const float4 *>(p + i);
-            av.x = average(av.x, pv.x, w);
-            av.y = average(av.y, pv.y, w);
-            av.z = average(av.z, pv.z, w);
-            av.w = average(av.w, pv.w, w);
-            *reinterpret_cast<float4 *>(avg + i) = av;
-        }
-        return;
-    }
-    for (long long i = a + threadIdx.x; i < b; i += OPT_THREADS) avg[i] = average(avg[i], p[i], w);
-}
+struct AverageOp {
+    float *avg;
+    const float *p;
+    float w;
 
-// the slice-per-block walk of optim_step_kernel over the same table (group ignored)
+    __device__ __forceinline__ void four(long long i) const
+    {
+        float4 av = *reinterpret_cast<const float4 *>(avg + i);
+        const float4 pv = *reinterpret_cast<const float4 *>(p + i);
+        av.x = average(av.x, pv.x, w);
+        av.y = average(av.y, pv.y, w);
+        av.z = average(av.z, pv.z, w);
+        av.w = average(av.w, pv.w, w);
+        *reinterpret_cast<float4 *>(avg + i) = av;
+    }
+
+    __device__ __forceinline__ void one(long long i) const { avg[i] = average(avg[i], p[i], w); }
+};
+
 __global__ __launch_bounds__(OPT_THREADS) void weight_average_kernel(float *__restrict__ avg, const float *__restrict__ p,
                                                                     long long n, const long long *__restrict__ seg,
                                                                     int n_seg, long long total, float w, int vec4)
 {
     __shared__ FirstRow s_first;
-    const long long v0 = (long long)blockIdx.x * OPT_SLICE;
-    const long long v1 = v0 + OPT_SLICE < total ? v0 + OPT_SLICE : total;
-    const int first = find_first_row(seg, n_seg, v0, &s_first);
-    for (long long pos = v0, r = first; pos < v1 && r < n_seg; ++r) {
-        const long long *row = row_at(seg, (int)r, first, s_first);
-        const long long lo = row[0], hi = row[1], st = row[3];
-        const long long end = st + (hi - lo) < v1 ? st + (hi - lo) : v1;
-        if (lo >= 0 && hi <= n && pos >= st)                 // a malformed row is skipped, never written out of bounds
-            average_range(avg, p, lo + (pos - st), lo + (end - st), w, vec4 != 0);
-        pos = end;
-    }
+    AverageOp op = {avg, p, w};
+    for_each_piece<OPT_SLICE>(seg, n_seg, total, n, &s_first, [] {},
+                              [&](long long a, long long b, int) { for_each_element(a, b, vec4 != 0, op); });
 }
 
 enum { ACC_OPEN = 0, ACC_ADD = 1, ACC_CLOSE = 2, ACC_ADD_CLOSE = 3 };
@@ -301,34 +321,36 @@ __device__ __forceinline__ float accumulate(float av, float gv, float s)
     return t * s;
 }
 
-// flat elements [a, b) of one row piece, already cut to the clip range; open and add write acc and only read g, close and
-// add-close write g and only read acc (open does not read acc at all, close does not read g)
+// open and add write acc and only read g, close and add-close write g and only read acc (open does not read acc at all,
+// close does not read g)
 template <int MODE>
-__device__ __forceinline__ void accumulate_range(float *__restrict__ acc, float *__restrict__ g, long long a, long long b,
-                                                 float s, bool vec4)
-{
-    constexpr bool reads_acc = MODE != ACC_OPEN, reads_g = MODE != ACC_CLOSE;
-    float *__restrict__ dst = MODE == ACC_OPEN || MODE == ACC_ADD ? acc : g;
-    if (vec4 && ((a | b) & 3) == 0) {
-        for (long long i = a + 4 * (long long)threadIdx.x; i < b; i += 4 * OPT_THREADS) {
-            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 av = reads_acc ? *reinterpret_cast<const float4 *>(acc + i) : z;
-            const float4 gv = reads_g ? *reinterpret_cast<const float4 *>(g + i) : z;
-            float4 o;
-            o.x = accumulate<MODE>(av.x, gv.x, s);
-            o.y = accumulate<MODE>(av.y, gv.y, s);
-            o.z = accumulate<MODE>(av.z, gv.z, s);
-            o.w = accumulate<MODE>(av.w, gv.w, s);
-            *reinterpret_cast<float4 *>(dst + i) = o;
-        }
-        return;
-    }
-    for (long long i = a + threadIdx.x; i < b; i += OPT_THREADS)
-        dst[i] = accumulate<MODE>(reads_acc ? acc[i] : 0.f, reads_g ? g[i] : 0.f, s);
-}
+struct AccumulateOp {
+    float *acc, *g;
+    float s;
+    static constexpr bool reads_acc = MODE != ACC_OPEN, reads_g = MODE != ACC_CLOSE;
 
-// the slice-per-block walk of weight_average_kernel over the same table (group ignored); every piece is cut to the clip
-// range [c0, c1) of flat elements before it is touched
+    __device__ __forceinline__ float *dst() const { return MODE == ACC_OPEN || MODE == ACC_ADD ? acc : g; }
+
+    __device__ __forceinline__ void four(long long i) const
+    {
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 av = reads_acc ? *reinterpret_cast<const float4 *>(acc + i) : z;
+        const float4 gv = reads_g ? *reinterpret_cast<const float4 *>(g + i) : z;
+        float4 o;
+        o.x = accumulate<MODE>(av.x, gv.x, s);
+        o.y = accumulate<MODE>(av.y, gv.y, s);
+        o.z = accumulate<MODE>(av.z, gv.z, s);
+        o.w = accumulate<MODE>(av.w, gv.w, s);
+        *reinterpret_cast<float4 *>(dst() + i) = o;
+    }
+
+    __device__ __forceinline__ void one(long long i) const
+    {
+        dst()[i] = accumulate<MODE>(reads_acc ? acc[i] : 0.f, reads_g ? g[i] : 0.f, s);
+    }
+};
+
+// every piece is cut to the clip range [c0, c1) of flat elements before it is touched
 template <int MODE>
 __global__ __launch_bounds__(OPT_THREADS) void grad_accumulate_kernel(float *__restrict__ acc, float *__restrict__ g,
                                                                      long long n, const long long *__restrict__ seg,
@@ -336,21 +358,12 @@ __global__ __launch_bounds__(OPT_THREADS) void grad_accumulate_kernel(float *__r
                                                                      long long c1, float s, int vec4)
 {
     __shared__ FirstRow s_first;
-    const long long v0 = (long long)blockIdx.x * OPT_SLICE;
-    const long long v1 = v0 + OPT_SLICE < total ? v0 + OPT_SLICE : total;
-    const int first = find_first_row(seg, n_seg, v0, &s_first);
-    for (long long pos = v0, r = first; pos < v1 && r < n_seg; ++r) {
-        const long long *row = row_at(seg, (int)r, first, s_first);
-        const long long lo = row[0], hi = row[1], st = row[3];
-        const long long end = st + (hi - lo) < v1 ? st + (hi - lo) : v1;
-        if (lo >= 0 && hi <= n && pos >= st) {               // a malformed row is skipped, never written out of bounds
-            long long a = lo + (pos - st), b = lo + (end - st);
-            a = a > c0 ? a : c0;
-            b = b < c1 ? b : c1;
-            if (a < b) accumulate_range<MODE>(acc, g, a, b, s, vec4 != 0);
-        }
-        pos = end;
-    }
+    AccumulateOp<MODE> op = {acc, g, s};
+    for_each_piece<OPT_SLICE>(seg, n_seg, total, n, &s_first, [] {}, [&](long long a, long long b, int) {
+        a = a > c0 ? a : c0;
+        b = b < c1 ? b : c1;
+        if (a < b) for_each_element(a, b, vec4 != 0, op);
+    });
 }
 
 inline bool aligned16(const void *ptr) { return ((uintptr_t)ptr & 15) == 0; }
@@ -389,15 +402,10 @@ COVA_API int cova_optim_step(int algo, float *p, const float *g, float *m, float
     const int vec4 = aligned16(p) && aligned16(g) && (!m || aligned16(m)) && (!v || aligned16(v));
     const dim3 grid((unsigned)cdivll(total, OPT_SLICE)), block(OPT_THREADS);
     hipStream_t s = (hipStream_t)stream;
-    if (algo == ALGO_ADAM)
-        hipLaunchKernelGGL(optim_step_kernel<ALGO_ADAM>, grid, block, 0, s, p, g, m, v, n, segs, n_seg, total, G,
-                           n_groups, gscale, vec4);
-    else if (algo == ALGO_ADAMW)
-        hipLaunchKernelGGL(optim_step_kernel<ALGO_ADAMW>, grid, block, 0, s, p, g, m, v, n, segs, n_seg, total, G,
-                           n_groups, gscale, vec4);
-    else
-        hipLaunchKernelGGL(optim_step_kernel<ALGO_SGD>, grid, block, 0, s, p, g, m, v, n, segs, n_seg, total, G,
-                           n_groups, gscale, vec4);
+    static constexpr decltype(&optim_step_kernel<ALGO_ADAM>) kernels[] = {
+        optim_step_kernel<ALGO_ADAM>, optim_step_kernel<ALGO_ADAMW>, optim_step_kernel<ALGO_SGD>};   // by algorithm code
+    hipLaunchKernelGGL(kernels[algo], grid, block, 0, s, p, g, m, v, n, segs, n_seg, total, G, n_groups, gscale,
+                       vec4);
     COVA_LAUNCH_CHECK();
     return COVA_OK;
 }
@@ -415,8 +423,8 @@ COVA_API int cova_grad_norm(const float *g, long long n, const long long *segs, 
     COVA_REQUIRE(total == 0 || (segs && n_seg > 0));
     const int n_part = cova_grad_norm_workspace_doubles(total);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(n_part), dim3(OPT_THREADS), 0, s, g, n, segs, n_seg, total,
-                       (int)aligned16(g), workspace);
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(n_part), dim3(OPT_THREADS), 0, s, g, n, segs, total ? n_seg : 0, total,
+                       (int)aligned16(g), workspace);                    // (no element: no row is read, segs may be null)
     COVA_LAUNCH_CHECK();
     hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(OPT_THREADS), 0, s, workspace, n_part, (float)max_norm,
                        out);
@@ -450,19 +458,10 @@ COVA_API int cova_grad_accumulate(int mode, float *acc, float *g, long long n, c
     const float s = (float)scale;                            // converted once: the kernel multiplies by this f32
     const int vec4 = aligned16(acc) && aligned16(g);
     const dim3 grid((unsigned)cdivll(total, OPT_SLICE)), block(OPT_THREADS);
-    hipStream_t st = (hipStream_t)stream;
-    if (mode == ACC_OPEN)
-        hipLaunchKernelGGL(grad_accumulate_kernel<ACC_OPEN>, grid, block, 0, st, acc, g, n, segs, n_seg, total, c0, c1, s,
-                           vec4);
-    else if (mode == ACC_ADD)
-        hipLaunchKernelGGL(grad_accumulate_kernel<ACC_ADD>, grid, block, 0, st, acc, g, n, segs, n_seg, total, c0, c1, s,
-                           vec4);
-    else if (mode == ACC_CLOSE)
-        hipLaunchKernelGGL(grad_accumulate_kernel<ACC_CLOSE>, grid, block, 0, st, acc, g, n, segs, n_seg, total, c0, c1, s,
-                           vec4);
-    else
-        hipLaunchKernelGGL(grad_accumulate_kernel<ACC_ADD_CLOSE>, grid, block, 0, st, acc, g, n, segs, n_seg, total, c0,
-                           c1, s, vec4);
+    static constexpr decltype(&grad_accumulate_kernel<ACC_OPEN>) kernels[] = {                       // by mode
+        grad_accumulate_kernel<ACC_OPEN>, grad_accumulate_kernel<ACC_ADD>, grad_accumulate_kernel<ACC_CLOSE>,
+        grad_accumulate_kernel<ACC_ADD_CLOSE>};
+    hipLaunchKernelGGL(kernels[mode], grid, block, 0, (hipStream_t)stream, acc, g, n, segs, n_seg, total, c0, c1, s, vec4);
     COVA_LAUNCH_CHECK();
     return COVA_OK;
 }

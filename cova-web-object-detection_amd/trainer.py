@@ -43,6 +43,10 @@ class FlatBucket:
         self.views = OrderedDict((k, self.flat[o:o + m].view(shape))
                                  for k, (o, m, shape) in self.offsets.items())
 
+    def like(self):
+        """A zeroed bucket of the same layout on the same device."""
+        return FlatBucket(OrderedDict((k, shape) for k, (_, _, shape) in self.offsets.items()), self.flat.device)
+
     def all_reduce_sum(self, group=None):
         """One collective for the whole bucket."""
         import torch.distributed as dist
@@ -93,6 +97,32 @@ def group_runs(offsets, n, frozen, owner):
         else:
             runs.append([lo, hi, gid])
     return [tuple(r) for r in runs]
+
+
+class SegmentTable:
+    """The segment table of the flat-bucket kernels (csrc/optim.hip) from runs [(lo, hi, group)]: ``rows`` {lo, hi, group,
+    start} with ``start`` the running length, ``total`` their summed length and ``tensor``, the int64 [-1, 4] device
+    tensor the launches read: None until args() is first called, so a table nothing launches over holds no device memory."""
+
+    def __init__(self, runs, device):
+        self.rows, self.total, self.tensor, self._device = [], 0, None, device
+        for lo, hi, gid in runs:
+            self.rows.append((lo, hi, gid, self.total))
+            self.total += hi - lo
+
+    def args(self):
+        """(seg, n_seg, total) in the order every entry point over the table takes them."""
+        if self.tensor is None:
+            self.tensor = torch.tensor(self.rows, dtype=torch.int64).view(-1, 4).to(self._device)
+        return self.tensor, len(self.rows), self.total
+
+
+def group_rows(groups, buf_exists):
+    """Per parameter group the nine doubles lr, weight_decay, beta1, beta2, eps, momentum, dampening, nesterov, momentum
+    buffer exists.  The column order is the ABI of cova_optim_step's ``groups`` argument (include/cova_hip.h; csrc/optim.hip
+    reads h[0] .. h[8] of each row) and the message of HotPathTrainer._broadcast_groups: change it there too or not at all."""
+    return [[g["lr"], g["weight_decay"], g["betas"][0], g["betas"][1], g["eps"], g["momentum"], g["dampening"],
+             float(g["nesterov"]), float(b)] for g, b in zip(groups, buf_exists)]
 
 
 AVERAGES = ("ema", "swa")
@@ -368,25 +398,19 @@ class HotPathTrainer:
         self.n_averaged, self._avg_active = 0, False
         if self._avg is None:
             return
-        self.abucket = FlatBucket(OrderedDict((k, sh) for k, (_, _, sh) in self.pbucket.offsets.items()), self.device)
+        self.abucket = self.pbucket.like()
         self._avg_buffers = self.buffers                    # average_buffers=False: the averaged model uses the live ones
         self.abbucket = self.atracked = None
         if self._avg.buffers:
-            self.abbucket = FlatBucket(OrderedDict((k, sh) for k, (_, _, sh) in self.bbucket.offsets.items()), self.device)
+            self.abbucket = self.bbucket.like()
             self.atracked = torch.zeros_like(self.tracked)
             counters = [k for k in self.buffers if k.endswith("num_batches_tracked")]
             views = dict(self.abbucket.views)
             views.update((k, self.atracked[i]) for i, k in enumerate(counters))
             self._avg_buffers = OrderedDict((k, views[k]) for k in self.buffers)
-        # trainable runs whatever their group: {lo, hi, 0, start} rows as cova_optim_step's; frozen tensors are left out
-        rows, start = [], 0
-        for lo, hi in self._adam_runs:
-            rows.append((lo, hi, 0, start))
-            start += hi - lo
-        self._avg_rows, self._avg_total = rows, start
-        self._avg_seg = torch.tensor(rows, dtype=torch.int64).view(-1, 4).to(self.device)
-        nb = self.bbucket.flat.numel()
-        self._avg_bseg = torch.tensor([(0, nb, 0, 0)], dtype=torch.int64).to(self.device) if nb else None
+        self._stat_table = SegmentTable([(0, self.bbucket.flat.numel(), 0)], self.device)   # the running statistics
+        # the device tensors, made here (no step copies a table to the device) and held only while the feature is on
+        self._avg_seg, self._avg_bseg = self._run_table.args()[0], self._stat_table.args()[0]
         if self._avg.start == 0:
             self.reset_average()
 
@@ -426,12 +450,11 @@ class HotPathTrainer:
         if (s - a.start) % a.every:
             return
         w = average_weight(a.kind, a.decay, a.warmup, self.n_averaged)
-        engine.call("cova_weight_average", self.abucket.flat, self.pbucket.flat, self.pbucket.flat.numel(), self._avg_seg,
-                    len(self._avg_rows), self._avg_total, w)
+        engine.call("cova_weight_average", self.abucket.flat, self.pbucket.flat, self.pbucket.flat.numel(),
+                    *self._run_table.args(), w)
         if a.buffers:
-            if self._avg_bseg is not None:
-                nb = self.bbucket.flat.numel()
-                engine.call("cova_weight_average", self.abbucket.flat, self.bbucket.flat, nb, self._avg_bseg, 1, nb, w)
+            engine.call("cova_weight_average", self.abbucket.flat, self.bbucket.flat, self.bbucket.flat.numel(),
+                        *self._stat_table.args(), w)
             self.atracked.copy_(self.tracked)               # copied, not averaged
         self.n_averaged += 1
 
@@ -463,20 +486,13 @@ class HotPathTrainer:
             (self.params, self.buffers), self._avg_active = live, False
 
     def _setup_accumulate(self):
-        """The accumulator bucket and the device table of the trainable runs ({lo, hi, 0, start} rows as
-        cova_optim_step's; frozen tensors are left out).  Nothing is allocated with ``accumulate_steps=1``."""
+        """The accumulator bucket and the device table of the trainable runs: neither with ``accumulate_steps=1``."""
         self.accumulated, self._update_count = 0, 0
         self._close = None                   # the closing micro-step's scale while its forward_backward runs
         if self.accumulate_steps == 1:
             return
-        self.accbucket = FlatBucket(OrderedDict((k, sh) for k, (_, _, sh) in self.pbucket.offsets.items()), self.device)
-        runs = group_runs(self.pbucket.offsets, self.pbucket.flat.numel(), self.frozen, dict.fromkeys(self.params, 0))
-        rows, start = [], 0
-        for lo, hi, _ in runs:
-            rows.append((lo, hi, 0, start))
-            start += hi - lo
-        self._acc_rows, self._acc_total = rows, start
-        self._acc_seg = torch.tensor(rows, dtype=torch.int64).view(-1, 4).to(self.device)
+        self.accbucket = self.pbucket.like()
+        self._acc_seg = self._run_table.args()[0]            # made here if averaging has not: the same tensor
 
     @property
     def update_count(self):
@@ -492,8 +508,8 @@ class HotPathTrainer:
     def _accumulate(self, mode, scale=1.0, lo=0, hi=None):
         """One cova_grad_accumulate launch over the trainable runs, cut to the flat range [lo, hi)."""
         n = self.gbucket.flat.numel()
-        engine.call("cova_grad_accumulate", mode, self.accbucket.flat, self.gbucket.flat, n, self._acc_seg,
-                    len(self._acc_rows), self._acc_total, lo, n if hi is None else hi, scale)
+        engine.call("cova_grad_accumulate", mode, self.accbucket.flat, self.gbucket.flat, n, *self._run_table.args(),
+                    lo, n if hi is None else hi, scale)
 
     def flush(self):
         """Make the parameter update from the micro-batches pending (``accumulated`` = m >= 1, scale 1 / m with
@@ -526,19 +542,11 @@ class HotPathTrainer:
         self.modes = {p: False for p in eval_bns} if eval_bns else True
         self.plan = (engine.grad_plan([k for k in self.params if k not in self.frozen],
                                       layer2=engine.has_layer2(self.params)) if self.frozen else None)
-        # Adam over the runs of trainable tensors (a run spans the alignment padding between adjacent views)
-        keys, n = list(self.pbucket.offsets), self.pbucket.flat.numel()
-        ends = [self.pbucket.offsets[k][0] for k in keys[1:]] + [n]
-        runs = []
-        for k, hi in zip(keys, ends):
-            if k in self.frozen:
-                continue
-            lo = self.pbucket.offsets[k][0]
-            if runs and runs[-1][1] == lo:
-                runs[-1][1] = hi
-            else:
-                runs.append([lo, hi])
-        self._adam_runs = [tuple(r) for r in runs]
+        # the runs of trainable tensors whatever their group (frozen ones are left out): cova_adam_step's slices, and
+        # the one {lo, hi, 0, start} table that averaging and accumulation both launch over
+        runs = group_runs(self.pbucket.offsets, self.pbucket.flat.numel(), self.frozen, dict.fromkeys(self.params, 0))
+        self._adam_runs = [(lo, hi) for lo, hi, _ in runs]
+        self._run_table = SegmentTable(runs, self.device)
         self.conv_frozen = all(k in self.frozen for k in self.params if k.startswith("convnet."))
         conv_bns = [k[:-len("running_mean")] for k in self.buffers if k.startswith("convnet.") and k.endswith("running_mean")]
         self.conv_bn_eval = all(not engine.is_train(self.modes, p) for p in conv_bns)
@@ -597,12 +605,8 @@ class HotPathTrainer:
         self._buf_exists = [False] * len(groups)     # per group: torch creates the momentum buffer on its first step
         self.last_grad_norm = None
         self._norm_ws = None
-        rows, start = [], 0
-        for lo, hi, gid in self.optim_runs:
-            rows.append((lo, hi, gid, start))
-            start += hi - lo
-        self._seg_total = start
-        self._seg = torch.tensor(rows, dtype=torch.int64).view(-1, 4).to(self.device) if self._fused else None
+        self._optim_table = SegmentTable(self.optim_runs, self.device)
+        self._seg = self._optim_table.args()[0] if self._fused else None     # made here: no step copies it
 
     def _setup_criterion(self, class_weight, label_smoothing, focal_gamma, ignore_index, loss_reduction, track_metrics):
         """``class_weight`` becomes a device tensor that may be edited in place; the scalar options live in
@@ -927,9 +931,7 @@ class HotPathTrainer:
     def _broadcast_groups(self):
         """Rank 0's per-group hyper-parameters, momentum buffer and its per-group flags to every rank."""
         import torch.distributed as dist
-        rows = [[g["lr"], g["weight_decay"], g["betas"][0], g["betas"][1], g["eps"], g["momentum"], g["dampening"],
-                 float(g["nesterov"]), float(b)] for g, b in zip(self._groups, self._buf_exists)]
-        meta = torch.tensor(rows, dtype=torch.float64, device=self.device)
+        meta = torch.tensor(group_rows(self._groups, self._buf_exists), dtype=torch.float64, device=self.device)
         dist.broadcast(meta, src=0, group=self.group)
         for g, r in zip(self._groups, meta.tolist()):
             g.update(lr=r[0], weight_decay=r[1], betas=(r[2], r[3]), eps=r[4], momentum=r[5], dampening=r[6],
@@ -1077,23 +1079,20 @@ class HotPathTrainer:
         gscale = None
         if self.max_grad_norm is not None:
             if self._norm_ws is None:
-                n_ws = engine.query("cova_grad_norm_workspace_doubles", self._seg_total)
+                n_ws = engine.query("cova_grad_norm_workspace_doubles", self._optim_table.total)
                 self._norm_ws = torch.empty(n_ws, dtype=torch.float64, device=self.device)
             out = torch.empty(2, dtype=torch.float32, device=self.device)        # [norm, clip coefficient]
-            engine.call("cova_grad_norm", self.gbucket.flat, n, self._seg, len(self.optim_runs), self._seg_total,
-                        self.max_grad_norm, self._norm_ws, out)
+            engine.call("cova_grad_norm", self.gbucket.flat, n, *self._optim_table.args(), self.max_grad_norm,
+                        self._norm_ws, out)
             self.last_grad_norm, gscale = out[0], out[1:]
         if not self.optim_runs:
             return
-        # host table [groups][9], read by the launch itself (kernel arguments): lr, wd, beta1, beta2, eps, momentum,
-        # dampening, nesterov, momentum buffer exists
-        table = torch.tensor([[g["lr"], g["weight_decay"], g["betas"][0], g["betas"][1], g["eps"], g["momentum"],
-                               g["dampening"], float(g["nesterov"]), float(b)]
-                              for g, b in zip(self._groups, self._buf_exists)], dtype=torch.float64)
+        # host table [groups][9], read by the launch itself (kernel arguments)
+        table = torch.tensor(group_rows(self._groups, self._buf_exists), dtype=torch.float64)
         sgd = self.optimizer == "sgd"
         engine.call("cova_optim_step", OPTIMIZERS.index(self.optimizer), flat, self.gbucket.flat,
-                    self.momentum_buffer if sgd else self.exp_avg, None if sgd else self.exp_avg_sq, n, self._seg,
-                    len(self.optim_runs), self._seg_total, table.data_ptr(), len(self._groups), self.update_count, gscale)
+                    self.momentum_buffer if sgd else self.exp_avg, None if sgd else self.exp_avg_sq, n,
+                    *self._optim_table.args(), table.data_ptr(), len(self._groups), self.update_count, gscale)
         if sgd:
             self._buf_exists = [b or g["momentum"] != 0 for g, b in zip(self._groups, self._buf_exists)]
 

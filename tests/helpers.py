@@ -210,3 +210,45 @@ def assert_gate_flips_near_zero(routing, tap, rel_tol=2e-5, max_frac=1e-4):
             b = torch.gather(flat, 2, ref.reshape(B, C, -1))[diff.reshape(B, C, -1)]
             assert float((a - b).abs().max()) <= rel_tol * float(x.abs().max())
     return flips
+
+
+# The hard ragged segment table of the flat-bucket kernel tests (cova_optim_step, cova_grad_norm, cova_weight_average,
+# cova_grad_accumulate): rows (lo, hi) of a 9 000-element buffer; a block owns 2 048 concatenated elements (a norm block
+# 4 096).  It is the smallest table with a slice cut inside an unaligned row, an empty row, an odd two-element row, a
+# malformed row and a row behind the malformed one.
+#   (4, 3004)     4-aligned, concatenated [0, 3000): cut at 2048 -> flat 2052, both pieces on the float4 path
+#   (3005, 3007)  2 elements at an odd offset: scalar path
+#   (3010, 3010)  empty
+#   (3013, 6500)  unaligned, concatenated [3002, 6489): cut at 4096 and 6144, scalar pieces
+#   (8900, 9100)  malformed (hi > n): skipped, [8900, 9000) keeps what it held
+#   (6600, 8800)  behind the malformed row, concatenated [6689, 8889): cut at 8192
+# left out: [0, 4), the gaps between the rows, [6500, 6600) and the tail [8800, 9000)
+HARD_RAGGED = [(4, 3004), (3005, 3007), (3010, 3010), (3013, 6500), (8900, 9100), (6600, 8800)]
+N_RAGGED, N_BACKING = 9000, 9216           # the buffers are longer than n: a write past n would show, not fault
+
+
+def seg_table(rows, device="cuda:0"):
+    """Rows (lo, hi) or (lo, hi, group) -> (the int64 {lo, hi, group, start} device table, the summed length)."""
+    out, start = [], 0
+    for lo, hi, *group in rows:
+        out.append((lo, hi, group[0] if group else 0, start))
+        start += hi - lo
+    return torch.tensor(out, dtype=torch.int64, device=device).view(-1, 4), start
+
+
+def ragged_inside(rows=HARD_RAGGED, n=N_RAGGED, backing=N_BACKING):
+    """bool [backing]: the elements the valid rows cover (a malformed row covers none)."""
+    inside = torch.zeros(backing, dtype=torch.bool)
+    for lo, hi, *_ in rows:
+        if 0 <= lo and hi <= n:
+            inside[lo:hi] = True
+    return inside
+
+
+def on_device(host, offset, device="cuda:0"):
+    """A device copy whose base pointer is 16-byte aligned (offset 0) or one float behind that (offset 1)."""
+    backing = torch.empty(host.numel() + 4, dtype=torch.float32, device=device)
+    view = backing[offset:offset + host.numel()]
+    view.copy_(host)
+    assert view.data_ptr() % 16 == 4 * offset
+    return view

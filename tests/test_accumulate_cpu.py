@@ -169,7 +169,7 @@ def test_invalid_accumulate_steps_raise(n):
 def test_default_adds_nothing():
     tr = trainer()
     assert tr.accumulate_steps == 1 and tr.accumulated == 0
-    assert not any(hasattr(tr, n) for n in ("accbucket", "_acc_seg", "_acc_rows"))
+    assert not any(hasattr(tr, n) for n in ("accbucket", "_acc_seg", "_acc_rows")) and tr._run_table.tensor is None
     assert set(tr.optimizer_state_dict()) == {"step", "exp_avg", "exp_avg_sq", "hp"}
     assert tr.flush() is False
     tr.step_count = 7
@@ -182,7 +182,7 @@ def test_table_holds_the_trainable_runs_only():
     assert tr.accbucket.flat.numel() == tr.gbucket.flat.numel() and tr.accbucket.offsets == tr.gbucket.offsets
     seg = tr._acc_seg.tolist()
     lo_first = tr.pbucket.offsets["convnet.4.0.conv1.weight"][0]
-    assert seg == [[lo_first, tr.pbucket.flat.numel(), 0, 0]] and tr._acc_total == tr.pbucket.flat.numel() - lo_first
+    assert seg == [[lo_first, tr.pbucket.flat.numel(), 0, 0]] and tr._run_table.total == tr.pbucket.flat.numel() - lo_first
     assert all(tr.pbucket.offsets[k][0] + tr.pbucket.offsets[k][1] <= lo_first for k in tr.frozen)
     full = trainer(accumulate_steps=2)
     assert full._acc_seg.tolist() == [[0, full.pbucket.flat.numel(), 0, 0]]
@@ -191,7 +191,7 @@ def test_table_holds_the_trainable_runs_only():
     rows = mid._acc_seg.tolist()
     o, m, _ = mid.pbucket.offsets["bbox_feat_encoder.0.weight"]
     assert len(rows) == 2 and rows[0][:2] == [0, o] and rows[1][0] == (o + m + 3) // 4 * 4
-    assert rows[1][3] == o and mid._acc_total == sum(r[1] - r[0] for r in rows)
+    assert rows[1][3] == o and mid._run_table.total == sum(r[1] - r[0] for r in rows)
 
 
 # ---------------------------------------------------------------- 5. the cycle, launches recorded instead of issued

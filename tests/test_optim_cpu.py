@@ -50,6 +50,7 @@ def test_defaults_keep_todays_hyper_parameters_buffers_and_checkpoint():
     tr = trainer()
     assert not tr._fused and tr.optimizer == "adam" and tr.max_grad_norm is None and tr.last_grad_norm is None
     assert tr.momentum_buffer is None and tr._seg is None
+    assert tr._optim_table.tensor is None and tr._run_table.tensor is None     # no device table at all
     assert {k: tr.hp[k] for k in ("lr", "weight_decay", "betas", "eps")} == dict(lr=5e-4, weight_decay=1e-3,
                                                                                   betas=(0.9, 0.999), eps=1e-8)
     n = tr.pbucket.flat.numel()
@@ -100,7 +101,7 @@ def test_param_groups_resolve_to_merged_runs_of_the_flat_bucket():
     for (lo, hi, gid), row in zip(runs, seg):
         assert row == [lo, hi, gid, start]
         start += hi - lo
-    assert tr._seg_total == start
+    assert tr._optim_table.total == start and tr._seg is tr._optim_table.tensor
 
 
 def test_groups_naming_only_frozen_keys_and_claiming_everything():

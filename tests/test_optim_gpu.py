@@ -1,8 +1,12 @@
 """HotPathTrainer's optimizer options on the GPU: cova_optim_step (adam / adamw / sgd over a segment table with per-group
-hyper-parameters) and cova_grad_norm against torch.optim and torch.nn.utils.clip_grad_norm_ on the CPU, the trainer end to
-end against the oracle, and the launches of a default step."""
+hyper-parameters) and cova_grad_norm against torch.optim and torch.nn.utils.clip_grad_norm_ on the CPU, both over the hard
+ragged table of tests/helpers.py (a malformed row, slice cuts inside an unaligned row, both base-pointer alignments) bit
+for bit against the float32 statement (tests/optim_oracle.py), the trainer end to end against the oracle, and the launches
+of a default step."""
+import functools
 import math
 
+import numpy as np
 import pytest
 import torch
 
@@ -11,6 +15,8 @@ pytestmark = pytest.mark.gpu
 from cova_web_object_detection_amd import _lib, engine, synthetic, weights  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
 from oracle import cova_oracle as O  # noqa: E402
+import optim_oracle as OO  # noqa: E402
+from helpers import HARD_RAGGED, N_BACKING, N_RAGGED as N_HARD, on_device, ragged_inside, seg_table  # noqa: E402
 
 DEV = "cuda:0"
 F32_EPS = torch.finfo(torch.float32).eps
@@ -18,14 +24,6 @@ LOSS_TOL = 2e-5
 # ragged rows (lo, hi, group) of a 13 300-element buffer: sizes 1, 3, 4097, 4, 9000, 1 with gaps between them
 RAGGED = [(0, 1, 0), (2, 5, 1), (8, 8 + 4097, 0), (4112, 4116, 1), (4120, 13120, 1), (13200, 13201, 0)]
 N_RAGGED = 13300
-
-
-def seg_table(rows):
-    out, start = [], 0
-    for lo, hi, g in rows:
-        out.append((lo, hi, g, start))
-        start += hi - lo
-    return torch.tensor(out, dtype=torch.int64, device=DEV), start
 
 
 def group_table(groups, exists=None):
@@ -165,6 +163,111 @@ def test_grad_norm_matches_float64_is_deterministic_and_skips_gaps():
         gb[250_000] = bad                                                    # (inside row 3)
         norm, coef = grad_norm(gb, seg, total, 1.0).cpu().tolist()
         assert want[0](norm) and want[1](coef), (bad, norm, coef)
+
+
+# ------------------------------------------------------------------------------------- the hard ragged table
+SENTINEL = 0x7FC12345                      # a NaN with a payload: any arithmetic on it, or any store over it, shows
+HARD_GROUPS = {"adam": [dict(lr=5e-4, weight_decay=1e-3, betas=(0.9, 0.999), eps=1e-8),
+                        dict(lr=2e-3, weight_decay=0.0, betas=(0.8, 0.99), eps=1e-6)],
+               "adamw": [dict(lr=1e-2, weight_decay=0.05, betas=(0.9, 0.99), eps=1e-8),
+                         dict(lr=3e-3, weight_decay=0.0, betas=(0.8, 0.999), eps=1e-6)],
+               "sgd": [dict(lr=0.1, momentum=0.9, dampening=0.1, weight_decay=0.01),
+                       dict(lr=0.05, momentum=0.8, nesterov=True, weight_decay=0.0)]}
+
+
+def bits(t):
+    t = t.detach().cpu() if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t))
+    return t.contiguous().view(torch.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def hard_inputs():
+    """p, two gradients, m and v (>= 0) of N_BACKING floats: random inside the valid rows, the sentinel elsewhere."""
+    gen = torch.Generator().manual_seed(47)
+    inside = ragged_inside()
+    sentinel = torch.full((), SENTINEL, dtype=torch.int32).view(torch.float32)
+    draw = lambda scale: torch.where(inside, scale * torch.randn(N_BACKING, generator=gen), sentinel)
+    return dict(p=draw(1.0), g=[draw(0.3), draw(0.3)], m=draw(0.1), v=draw(0.05).abs(), inside=inside)
+
+
+def hard_reference(algo, rows, groups, x, offset):
+    """Two steps of the update over the valid rows -> bit patterns of (p, m, v).  adamw and sgd: the float32 statement;
+    adam: cova_adam_step on the same slices at the same base-pointer alignment."""
+    valid = [r for r in rows if 0 <= r[0] and r[1] <= N_HARD]
+    if algo == "adam":
+        p, m, v = (on_device(x[k], offset) for k in "pmv")
+        for step in (1, 2):
+            g = on_device(x["g"][step - 1], offset)
+            for lo, hi, k in valid:
+                if hi > lo:
+                    q = groups[k]
+                    engine.call("cova_adam_step", p[lo:hi], g[lo:hi], m[lo:hi], v[lo:hi], hi - lo, step, q["lr"],
+                                q["betas"][0], q["betas"][1], q["eps"], q["weight_decay"])
+        return bits(p), bits(m), bits(v)
+    p, m, v = (x[k].numpy().copy() for k in "pmv")
+    for step in (1, 2):
+        g = x["g"][step - 1].numpy()
+        for lo, hi, k in valid:
+            q, sl = groups[k], slice(lo, hi)
+            if algo == "adamw":
+                p[sl], m[sl], v[sl] = OO.adamw(p[sl], g[sl], m[sl], v[sl], step, **q)
+            else:
+                p[sl], m[sl] = OO.sgd(p[sl], g[sl], m[sl], step > 1, **dict(dict(dampening=0.0, nesterov=False), **q))
+    return bits(p), bits(m), bits(v)
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+@pytest.mark.parametrize("n_groups", [1, 2])
+@pytest.mark.parametrize("algo", list(HARD_GROUPS))
+def test_optim_step_over_the_hard_table_is_the_float32_statement_and_keeps_the_sentinel(algo, n_groups, offset):
+    x = hard_inputs()
+    rows = [(lo, hi, i % n_groups) for i, (lo, hi) in enumerate(HARD_RAGGED)]
+    groups = HARD_GROUPS[algo][:n_groups]
+    seg, total = seg_table(rows)
+    assert total == 8889 and total <= N_HARD               # (the malformed row's 200 elements count in the table)
+    code, sgd = list(HARD_GROUPS).index(algo), algo == "sgd"
+    runs = []
+    for _ in range(2):                                       # (the second run: a rerun gives the same bits)
+        p, m, v = (on_device(x[k], offset) for k in "pmv")
+        for step in (1, 2):
+            g = on_device(x["g"][step - 1], offset)
+            table = group_table(groups, [step > 1] * n_groups)                      # (alive until the call has read it)
+            engine.call("cova_optim_step", code, p, g, m, None if sgd else v, N_HARD, seg, len(rows), total,
+                        table.data_ptr(), n_groups, step, None)
+            assert torch.equal(bits(g), bits(x["g"][step - 1]))                     # the gradient is only read
+        runs.append((bits(p), bits(m), bits(v)))
+    assert all(torch.equal(a, b) for a, b in zip(*runs))
+    got, inside = runs[0], x["inside"]
+    for name, t, t0 in zip("pmv", got, (x["p"], x["m"], x["v"])):
+        assert bool((t[~inside] == SENTINEL).all()), name     # gaps, tail, the malformed row, past n
+        if name == "v" and sgd:
+            assert torch.equal(t, bits(t0))                   # sgd has no second moment
+        else:
+            assert (t != bits(t0))[inside].float().mean() > 0.9, name
+    for name, t, ref in zip("pmv", got, hard_reference(algo, rows, groups, x, offset)):
+        assert torch.equal(t, ref), (name, int((t != ref).sum()))
+
+
+def test_grad_norm_over_the_hard_table_skips_poison_and_ignores_the_alignment():
+    gen = torch.Generator().manual_seed(53)
+    inside = ragged_inside()
+    # huge and finite: one poisoned element in the sum would dominate it (an inf or a NaN would hide how many were read)
+    g0 = torch.where(inside, torch.randn(N_BACKING, generator=gen), torch.tensor(3e38))
+    seg, total = seg_table(HARD_RAGGED)
+    ref = math.sqrt(float((g0[inside].double() ** 2).sum()))
+    outs = []
+    for offset in (0, 1, 0, 1):                              # (twice each: a rerun gives the same bits)
+        g = on_device(g0, offset)
+        ws = torch.zeros(_lib.query("cova_grad_norm_workspace_doubles", total), dtype=torch.float64, device=DEV)
+        out = torch.empty(2, dtype=torch.float32, device=DEV)
+        engine.call("cova_grad_norm", g, N_HARD, seg, len(HARD_RAGGED), total, 1.0, ws, out)
+        outs.append(bits(out))
+        print("offset %d: partials %s, norm and coefficient %s (float64 norm %.9g)" % (offset, ws.tolist(), out.tolist(), ref))
+        assert torch.equal(bits(g), bits(g0))
+    assert all(torch.equal(outs[0], o) for o in outs[1:])
+    norm, coef = outs[0].view(torch.float32).tolist()
+    assert abs(norm - ref) <= 1e-6 * ref, (norm, ref)
+    assert coef == float(torch.clamp(1.0 / (torch.tensor(norm, dtype=torch.float32) + 1e-6), max=1.0))
 
 
 # ---------------------------------------------------------------------------------------------- the trainer

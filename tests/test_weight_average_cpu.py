@@ -87,6 +87,7 @@ def test_defaults_add_nothing():
     assert tr.average is None and tr.n_averaged == 0
     assert set(tr.optimizer_state_dict()) == {"step", "exp_avg", "exp_avg_sq", "hp"}
     assert not any(hasattr(tr, n) for n in ("abucket", "abbucket", "bbucket", "tracked", "atracked", "_avg_seg"))
+    assert not hasattr(tr, "_stat_table") and tr._run_table.tensor is None
     # the buffers are today's: separately allocated tensors
     ptrs = sorted((v.data_ptr(), v.numel() * v.element_size()) for v in tr.buffers.values())
     assert len({v.untyped_storage().data_ptr() for v in tr.buffers.values()}) == len(tr.buffers)
@@ -164,6 +165,7 @@ def test_counter_and_launch_weights_follow_the_schedule(launches, kind, kw):
             assert [c[-1] for c in launches] == [action] * len(launches)             # the double itself
             avg, p, n, seg, n_seg, total, _ = launches[0][1:]
             assert avg is tr.abucket.flat and p is tr.pbucket.flat and n == p.numel() == total and n_seg == 1
+            assert seg is tr._avg_seg
             if a.buffers:
                 avg, p, n, seg, n_seg, total, _ = launches[1][1:]
                 assert avg is tr.abbucket.flat and p is tr.bbucket.flat and seg.tolist() == [[0, n, 0, 0]]
@@ -184,12 +186,12 @@ def test_counter_and_launch_weights_follow_the_schedule(launches, kind, kw):
 def test_table_holds_the_trainable_runs_only():
     tr = trainer(average="swa", frozen=FROZEN, optimizer="adamw", param_groups=[{"params": "decoder.", "lr": 1e-3}])
     rows = tr._avg_seg.tolist()
-    assert tr.frozen and len(rows) == len(tr._avg_rows) >= 1
+    assert tr.frozen and len(rows) == len(tr._run_table.rows) >= 1
     start = 0
     for lo, hi, g, st in rows:
         assert 0 <= lo < hi <= tr.pbucket.flat.numel() and g == 0 and st == start
         start += hi - lo
-    assert start == tr._avg_total
+    assert start == tr._run_table.total
     covered = torch.zeros(tr.pbucket.flat.numel(), dtype=torch.bool)
     for lo, hi, _, _ in rows:
         assert not covered[lo:hi].any()
@@ -205,7 +207,7 @@ def test_table_holds_the_trainable_runs_only():
             merged.append([lo, hi])
     assert [r[:2] for r in rows] == merged
     everything = trainer(average="ema", frozen=tuple(trainer().params))
-    assert everything._avg_seg.shape == (0, 4) and everything._avg_total == 0
+    assert everything._avg_seg.shape == (0, 4) and everything._run_table.total == 0
 
 
 # ---------------------------------------------------------------- 6. state round trips

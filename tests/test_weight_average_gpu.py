@@ -16,28 +16,12 @@ from cova_web_object_detection_amd.evaluation import evaluate_split, fit  # noqa
 from cova_web_object_detection_amd.pipeline import DeviceDataset  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
 import average_oracle as AO  # noqa: E402
+from helpers import HARD_RAGGED as RAGGED, N_BACKING, N_RAGGED, ragged_inside, seg_table  # noqa: E402
 
 DEV = "cuda:0"
 SENTINEL = 0x7FC12345                      # a NaN with a payload: any arithmetic on it, or any store over it, shows
 
-# Ragged rows (lo, hi) of a 9 000-element buffer; a block owns 2 048 concatenated elements.
-#   (4, 3004)     4-aligned, concatenated [0, 3000): cut at 2048 -> flat 2052, both pieces on the float4 path
-#   (3005, 3007)  2 elements at an odd offset: scalar path
-#   (3010, 3010)  empty
-#   (3013, 6500)  unaligned, concatenated [3002, 6489): cut at 4096 and 6144, scalar pieces
-#   (8900, 9100)  malformed (hi > n): skipped, [8900, 9000) keeps the sentinel
-#   (6600, 8800)  behind the malformed row, concatenated [6689, 8889): cut at 8192
-# left out: [0, 4), the gaps between the rows, [6500, 6600) and the tail [8800, 9000)
-RAGGED = [(4, 3004), (3005, 3007), (3010, 3010), (3013, 6500), (8900, 9100), (6600, 8800)]
-N_RAGGED, N_BACKING = 9000, 9216           # the buffers are longer than n: a write past n would show, not fault
-
-
-def seg_table(rows):
-    out, start = [], 0
-    for lo, hi in rows:
-        out.append((lo, hi, 0, start))
-        start += hi - lo
-    return torch.tensor(out, dtype=torch.int64, device=DEV).view(-1, 4), start
+# RAGGED is the hard ragged table of tests/helpers.py (the malformed row's [8900, 9000) keeps the sentinel)
 
 
 def bits(t):
@@ -48,10 +32,7 @@ def bits(t):
 @functools.lru_cache(maxsize=None)
 def ragged_inputs():
     gen = torch.Generator().manual_seed(21)
-    inside = torch.zeros(N_BACKING, dtype=torch.bool)
-    for lo, hi in RAGGED:
-        if hi <= N_RAGGED:
-            inside[lo:hi] = True
+    inside = ragged_inside()
     avg = torch.randn(N_BACKING, generator=gen)
     p = avg + 0.1 * torch.randn(N_BACKING, generator=gen)
     p[5:40] = avg[5:40]                                       # some unchanged parameters: the fixed point

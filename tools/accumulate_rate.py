@@ -66,7 +66,7 @@ def window(fn):
 
 
 tr = trainers["n4"]
-n, seg, n_seg, total = tr.gbucket.flat.numel(), tr._acc_seg, len(tr._acc_rows), tr._acc_total
+n, (seg, n_seg, total) = tr.gbucket.flat.numel(), tr._run_table.args()
 g0 = torch.randn(n, device=dev) * 1e-3
 g = g0.clone()
 acc, avg, p = torch.zeros(n, device=dev), tr.pbucket.flat.clone(), tr.pbucket.flat.clone()

@@ -73,9 +73,9 @@ m, v2 = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
 p = tr.pbucket.flat.clone()
 avg, bavg = tr.abucket.flat.clone(), tr.abbucket.flat.clone()
 calls = (("cova_weight_average  parameters", n, lambda: engine.call(
-              "cova_weight_average", avg, p, n, tr._avg_seg, len(tr._avg_rows), tr._avg_total, w)),
+              "cova_weight_average", avg, p, n, *tr._run_table.args(), w)),
          ("cova_weight_average  statistics", nb, lambda: engine.call(
-              "cova_weight_average", bavg, tr.bbucket.flat, nb, tr._avg_bseg, 1, nb, w)),
+              "cova_weight_average", bavg, tr.bbucket.flat, nb, *tr._stat_table.args(), w)),
          ("cova_adam_step       parameters", n, lambda: engine.call(
               "cova_adam_step", p, g, m, v2, n, 1, 5e-4, 0.9, 0.999, 1e-8, 1e-3)))
 out.append("average_rate, launch: the configs[1] trainer's buckets; %d back-to-back calls per window, %d windows after one "
