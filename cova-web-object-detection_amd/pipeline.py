@@ -21,7 +21,9 @@ graph.
 ``PageAugment`` (opt-in, both classes and ``evaluation.fit``; the reference augments nothing) gives every page of every
 epoch an integer viewport shift with a constant fill colour and a 3x4 affine colour transform, a function of
 ``(seed, epoch, page id)`` alone.  The page gather applies both in its one pass (cova_pages_u8_augment_f32) and one
-cova_boxes_translate launch moves the collated boxes with the pixels, before the spatial graph is built.
+cova_boxes_translate launch moves the collated boxes with the pixels, before the spatial graph is built.  With
+``scale=(lo, hi)`` a page also zooms about the centre of its top edge: the gather becomes a fixed-point bilinear resample
+(cova_pages_u8_resample_f32) and the boxes take cova_boxes_affine, one launch each in the same places.
 
 ``attention_rows`` is the dump of extract_attn_wts_and_visualize.py:104-135.
 """
@@ -114,12 +116,24 @@ class PageAugment:
     dark theme) fold into one 3x4 matrix per page.  Everything is a function of ``(seed, epoch, page id)``: a stream of
     its own beside the box sampling's, so the kept boxes do not change when augmentation is switched on, and a page's
     pixels do not depend on the batch it lands in, the batch size, the rank or the world size.  Zero magnitudes give zero
-    shifts and the exact identity matrix."""
+    shifts and the exact identity matrix.
+
+    ``scale=(lo, hi)``, 0.5 <= lo <= hi <= 2: the page is also zoomed by a factor drawn from [lo, hi] (slot 9 of the same
+    stream, so no shift, colour or sampled box moves when it is switched on) about the centre of its top edge -- pages are
+    centred horizontally and grow downwards -- and ``max_shift`` keeps its meaning in output pixels.  The default (1, 1)
+    leaves every table and launch as without it (``scales`` is False); ``resample_params`` are the tables otherwise."""
 
     LUMA = (0.299, 0.587, 0.114)
 
     def __init__(self, max_shift=(0, 0), brightness=0.0, contrast=0.0, saturation=0.0, channel_gain=0.0, invert_prob=0.0,
-                 fill=(255, 255, 255), seed=0):
+                 fill=(255, 255, 255), seed=0, scale=(1.0, 1.0)):
+        try:
+            lo, hi = (float(v) for v in scale)
+        except (TypeError, ValueError):
+            raise ValueError("scale must be a pair (lo, hi) of numbers, got %r" % (scale,))
+        if not (np.isfinite(lo) and np.isfinite(hi) and 0.5 <= lo <= hi <= 2.0):
+            raise ValueError("scale must be finite with 0.5 <= lo <= hi <= 2.0, got %r" % (scale,))
+        self.scale = (lo, hi)
         try:
             sx, sy = (int(v) for v in max_shift)
         except (TypeError, ValueError):
@@ -161,6 +175,62 @@ class PageAugment:
             raise ValueError("max_shift %r must be smaller than the page (W, H) = (%d, %d) in both directions"
                              % (self.max_shift, W, H))
 
+    @property
+    def scales(self):
+        """Whether any page can zoom (then the gather is cova_pages_u8_resample_f32 and the boxes take cova_boxes_affine)."""
+        return self.scale != (1.0, 1.0)
+
+    def _uniforms(self, page_ids, epoch, slots):
+        """float64 [len(slots), n]: u(pid, slot) of the page stream (``params``), one row per requested slot."""
+        pids = np.asarray(page_ids).reshape(-1)
+        if pids.size and (pids.dtype.kind not in "iu" or (pids < 0).any()):
+            raise ValueError("page ids must be non-negative integers")
+        stream = np.uint64(mix64(stream_seed(self.seed, epoch), 1))
+        page = _mix64_np(stream, pids.astype(np.uint64))
+        u = np.empty((len(slots), pids.shape[0]), np.float64)
+        for k, slot in enumerate(slots):
+            u[k] = (_mix64_np(page, np.uint64(slot)) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+        return u
+
+    def _shifts(self, u):
+        """int32 [n,2] = dx,dy from the uniforms of slots 0 and 1 (``u[0]``, ``u[1]``)."""
+        shift = np.empty((u.shape[1], 2), np.int32)
+        for a, s in enumerate(self.max_shift):         # u < 1; the minimum keeps a product that rounds up to 2s+1 inside
+            shift[:, a] = np.minimum(np.floor(u[a] * (2 * s + 1)), 2 * s) - s
+        return shift
+
+    def resample_params(self, page_ids, epoch, W):
+        """-> (step int32 [n,2] = inv_x,inv_y, origin int64 [n,2] = org_x,org_y, affine float32 [n,4] = sx,sy,tx,ty): the
+        tables of cova_pages_u8_resample_f32 / cova_boxes_affine for pages of width ``W``.
+
+        Slot 9 of the page stream is the zoom: s = lo + u*(hi - lo) in float64 (slots 0-8 are ``params``'s, untouched).
+        inv = round(65536 / s) on both axes, s_eff = 65536 / inv.  The anchor is the horizontal centre of the top edge: it
+        maps to itself plus the viewport shift (dx, dy) of ``params``, in output pixels:
+        org_x = (W-1)*32768 + ((1 - W - 2*dx)*inv) // 2,  org_y = -32768 + ((1 - 2*dy)*inv) // 2  (integers, floor division);
+        boxes: sx = sy = s_eff, tx = W/2 + dx - (W/2)*s_eff, ty = dy, float64 rounded to float32 at the end.  With
+        scale == (1, 1): inv = 65536, org = -d*65536, sx = 1, (tx, ty) = (dx, dy)."""
+        W = int(W)
+        u = self._uniforms(page_ids, epoch, (0, 1, 9))
+        n = u.shape[1]
+        d = self._shifts(u).astype(np.int64)
+        lo, hi = self.scale
+        inv = np.rint(65536.0 / (lo + u[2] * (hi - lo))).astype(np.int64)
+        s_eff = 65536.0 / inv
+        origin = np.empty((n, 2), np.int64)
+        origin[:, 0] = (W - 1) * 32768 + ((1 - W - 2 * d[:, 0]) * inv) // 2
+        origin[:, 1] = -32768 + ((1 - 2 * d[:, 1]) * inv) // 2
+        affine = np.empty((n, 4), np.float64)
+        affine[:, 0] = affine[:, 1] = s_eff
+        affine[:, 2] = W / 2 + d[:, 0] - (W / 2) * s_eff
+        affine[:, 3] = d[:, 1]
+        return np.stack([inv, inv], 1).astype(np.int32), origin, affine.astype(np.float32)
+
+    def resample_table(self, page_ids, epoch, W):
+        """``resample_params`` as ONE int32 array [n*2 + n*4 + n*4] = steps, the origins' int64 as int32 pairs, the affine
+        rows' float32 bits: what goes up behind ``table`` when ``scales`` (the origins 8-byte aligned by the caller)."""
+        step, origin, affine = self.resample_params(page_ids, epoch, W)
+        return np.concatenate([step.reshape(-1), origin.reshape(-1).view(np.int32), affine.reshape(-1).view(np.int32)])
+
     def params(self, page_ids, epoch):
         """-> (shift int32 [n,2] = dx,dy, color float32 [n,12] = row-major 3x4, the offset last in a row).
 
@@ -169,18 +239,9 @@ class PageAugment:
         4: s = 1 + (2u-1)*saturation;  5-7: g_k = 1 + (2u-1)*channel_gain;  8: sigma = -1 if u < invert_prob else 1;
         M[k][l] = sigma*c*g_k*(s*(k==l) + (1-s)*w[l]),  b_k = sigma*(0.5*(1-c) + beta) + (sigma < 0),  w = LUMA; rounded to
         float32 at the end."""
-        pids = np.asarray(page_ids).reshape(-1)
-        if pids.size and (pids.dtype.kind not in "iu" or (pids < 0).any()):
-            raise ValueError("page ids must be non-negative integers")
-        n = pids.shape[0]
-        stream = np.uint64(mix64(stream_seed(self.seed, epoch), 1))
-        page = _mix64_np(stream, pids.astype(np.uint64))
-        u = np.empty((9, n), np.float64)
-        for slot in range(9):
-            u[slot] = (_mix64_np(page, np.uint64(slot)) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
-        shift = np.empty((n, 2), np.int32)
-        for a, s in enumerate(self.max_shift):         # u < 1; the minimum keeps a product that rounds up to 2s+1 inside
-            shift[:, a] = np.minimum(np.floor(u[a] * (2 * s + 1)), 2 * s) - s
+        u = self._uniforms(page_ids, epoch, range(9))
+        n = u.shape[1]
+        shift = self._shifts(u)
         beta = (2.0 * u[2] - 1.0) * self.brightness
         c = 1.0 + (2.0 * u[3] - 1.0) * self.contrast
         sat = 1.0 + (2.0 * u[4] - 1.0) * self.saturation
@@ -204,13 +265,21 @@ def _split_aug_table(tab_d, n):
     return tab_d[:2 * n].view(n, 2), tab_d[2 * n:14 * n].view(torch.float32).view(n, 12)
 
 
+def _split_resample_table(tab_d, n):
+    """(step int32 [n,2], origin int64 [n,2], affine float32 [n,4]) views of a device copy of ``PageAugment.resample_table``
+    that starts on an 8-byte boundary."""
+    return (tab_d[:2 * n].view(n, 2), tab_d[2 * n:6 * n].view(torch.int64).view(n, 2),
+            tab_d[6 * n:10 * n].view(torch.float32).view(n, 4))
+
+
 def _sample_and_collate(dev, cs, A, rows_d, addl_d, offs_d, starts_d, pid_d, keep_d, keys_d, B, N, sseed, n_out=None,
-                        want_sel=False, ks=0, shift_d=None):
+                        want_sel=False, ks=0, shift_d=None, affine_d=None):
     """cova_sample_boxes + cova_collate_selected on the current stream.  ``n_out`` is the number of kept boxes when the
     host knows it (everything kept); None reads it back from the device: the one 4-byte host read of a sampled batch.
     ``want_sel``: also return the kept SOURCE row ids (int32 [n_out]) under "sel".  ``ks > 0``: the collation writes no
     window; cova_context_knn builds the whole [n_out, 2*cs + ks] table over the kept boxes.  ``shift_d`` (device int32
-    [B,2]): cova_boxes_translate moves the collated boxes before the graph is built."""
+    [B,2]): cova_boxes_translate moves the collated boxes before the graph is built; ``affine_d`` (device float32 [B,4],
+    a zooming augmentation): cova_boxes_affine does, in its place."""
     ws = torch.empty((N + B,), dtype=torch.int32, device=dev)
     sel = torch.empty((N,), dtype=torch.int32, device=dev)
     out_offs = torch.empty((B + 1,), dtype=torch.int32, device=dev)
@@ -224,7 +293,9 @@ def _sample_and_collate(dev, cs, A, rows_d, addl_d, offs_d, starts_d, pid_d, kee
     addl = torch.empty((n_out, A), dtype=torch.float32, device=dev)
     call("cova_collate_selected", rows_d, sel, out_offs, B, n_out, K // 2, bboxes, labels, ctx if K else None,
          addl_d if A else None, A, addl if A else None)
-    if shift_d is not None:
+    if affine_d is not None:
+        call("cova_boxes_affine", bboxes, n_out, affine_d, B)
+    elif shift_d is not None:
         call("cova_boxes_translate", bboxes, n_out, shift_d, B)
     if ks:
         ctx = _context_knn(bboxes, out_offs, B, cs, ks)
@@ -259,7 +330,8 @@ class DeviceCollate:
 
         With ``augment`` the pages go through cova_pages_u8_augment_f32 and the collated boxes through
         cova_boxes_translate (before the spatial graph); the batch carries ``aug_shift`` (device int32 [B,2] = dx,dy).
-        Boxes are neither clipped nor dropped."""
+        With ``augment.scales`` the two launches are cova_pages_u8_resample_f32 and cova_boxes_affine and the batch also
+        carries ``aug_affine`` (device float32 [B,4] = sx,sy,tx,ty).  Boxes are neither clipped nor dropped."""
         u8 = torch.as_tensor(np.ascontiguousarray(u8_pages) if isinstance(u8_pages, np.ndarray)
                              else u8_pages)
         assert u8.dtype == torch.uint8 and u8.dim() == 4 and u8.shape[3] == 3
@@ -277,7 +349,7 @@ class DeviceCollate:
         u8 = (host(u8) if u8.device.type == "cpu" else u8).to(dev, non_blocking=True).contiguous()
         rows_d = host(torch.from_numpy(rows)).to(dev, non_blocking=True)
         images = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
-        shift_d = aug_shift = None
+        shift_d = aug_shift = aug_affine = None
         if self.augment is None:
             call("cova_images_u8_to_f32", u8, images, B, H, W)
         else:
@@ -285,14 +357,25 @@ class DeviceCollate:
             aug_ids = np.arange(B, dtype=np.int64) if page_ids is None else np.asarray(page_ids, dtype=np.int64).reshape(-1)
             if aug_ids.shape[0] != B:
                 raise ValueError("page_ids must hold one id in [0, 2**31) per page")
-            tab_d = host(torch.from_numpy(self.augment.table(aug_ids, epoch))).to(dev, non_blocking=True)
+            tab = self.augment.table(aug_ids, epoch)
+            if self.augment.scales:             # 14*B ints so far: the zoom tables start on an 8-byte boundary
+                tab = np.concatenate([tab, self.augment.resample_table(aug_ids, epoch, W)])
+            tab_d = host(torch.from_numpy(tab)).to(dev, non_blocking=True)
             aug_shift, color_d = _split_aug_table(tab_d, B)
-            call("cova_pages_u8_augment_f32", u8, None, B, B, H, W, aug_shift, color_d, self.augment.fill_rgb, images)
-            shift_d = aug_shift if self.augment.shifts else None
+            if self.augment.scales:
+                step_d, origin_d, aug_affine = _split_resample_table(tab_d[14 * B:], B)
+                call("cova_pages_u8_resample_f32", u8, None, B, B, H, W, step_d, origin_d, color_d, self.augment.fill_rgb,
+                     images)
+            else:
+                call("cova_pages_u8_augment_f32", u8, None, B, B, H, W, aug_shift, color_d, self.augment.fill_rgb, images)
+                shift_d = aug_shift if self.augment.shifts else None
         if self.sf < 1.0 or keys is not None:
-            out = self._sampled(images, rows_d, counts, offs, additional_feats, page_ids, epoch, keys, host, shift_d)
+            out = self._sampled(images, rows_d, counts, offs, additional_feats, page_ids, epoch, keys, host, shift_d,
+                                aug_affine)
             if aug_shift is not None:
                 out["aug_shift"] = aug_shift
+            if aug_affine is not None:
+                out["aug_affine"] = aug_affine
             return out
         offs_d = host(torch.from_numpy(offs)).to(dev, non_blocking=True)
         bboxes = torch.empty((N, 5), dtype=torch.float32, device=dev)
@@ -300,7 +383,9 @@ class DeviceCollate:
         K = 0 if self.ks else 2 * self.cs
         ctx = torch.empty((N, K) if K else (0, 0), dtype=torch.int64, device=dev)   # datasets.py:130
         call("cova_collate_boxes", rows_d, offs_d, B, N, K // 2, bboxes, labels, ctx if K else None)
-        if shift_d is not None:
+        if aug_affine is not None:
+            call("cova_boxes_affine", bboxes, N, aug_affine, B)
+        elif shift_d is not None:
             call("cova_boxes_translate", bboxes, N, shift_d, B)
         if self.ks:
             ctx = _context_knn(bboxes, offs_d, B, self.cs, self.ks)
@@ -312,9 +397,12 @@ class DeviceCollate:
                    labels=labels, page_start=offs_d.to(torch.int64))
         if aug_shift is not None:
             out["aug_shift"] = aug_shift
+        if aug_affine is not None:
+            out["aug_affine"] = aug_affine
         return out
 
-    def _sampled(self, images, rows_d, counts, offs, additional_feats, page_ids, epoch, keys, host, shift_d=None):
+    def _sampled(self, images, rows_d, counts, offs, additional_feats, page_ids, epoch, keys, host, shift_d=None,
+                 affine_d=None):
         dev, B, N = self.device, len(counts), int(offs[-1])
         if page_ids is None:
             pids = np.arange(B, dtype=np.int64)
@@ -339,7 +427,7 @@ class DeviceCollate:
                 raise ValueError("additional_feats must be [N, A] with one row per box")
             A = int(addl_d.shape[1])
         out = _sample_and_collate(dev, self.cs, A, rows_d, addl_d, offs_d, None, pid_d, keep_d, keys_d, B, N,
-                                  stream_seed(self.seed, epoch), ks=self.ks, shift_d=shift_d)
+                                  stream_seed(self.seed, epoch), ks=self.ks, shift_d=shift_d, affine_d=affine_d)
         out["images"] = images
         return out
 
@@ -489,7 +577,10 @@ class DeviceDataset:
         step's gather is one cova_pages_u8_augment_f32 launch and, when ``max_shift`` is not (0, 0), one
         cova_boxes_translate launch moves the collated boxes before cova_context_knn.  Boxes are neither clipped nor
         dropped: RoIPool / RoIAlign clamp, and a box pushed wholly off the page pools zeros and keeps its label and its
-        place in DOM order.  The batch gains ``aug_shift`` (device int32 [B,2] = dx,dy).  Not with ``features``
+        place in DOM order.  The batch gains ``aug_shift`` (device int32 [B,2] = dx,dy).  With ``augment.scales`` the zoom
+        tables ride behind the others in the same copy, the gather is one cova_pages_u8_resample_f32 launch, the boxes take
+        one cova_boxes_affine launch in cova_boxes_translate's place and the batch also gains ``aug_affine`` (device float32
+        [B,4] = sx,sy,tx,ty: x' = x*sx + tx, y' = y*sy + ty).  Not with ``features``
         (ValueError): cached rows were pooled from unaugmented pixels."""
         if augment is not None:
             if features is not None:
@@ -517,17 +608,26 @@ class DeviceDataset:
             pos += part.shape[0]
         if augment is not None:     # behind the steps' tables, in the same copy: every page's shift, then the colour bits
             parts.append(augment.table(np.concatenate(plan), epoch))
+            if augment.scales:      # and the zoom tables behind those, on an 8-byte boundary (the origins are int64)
+                zoom_at = pos + parts[-1].shape[0]
+                if zoom_at % 2:
+                    parts.append(np.zeros(1, np.int32))
+                    zoom_at += 1
+                parts.append(augment.resample_table(np.concatenate(plan), epoch, self.W))
         table = torch.from_numpy(np.concatenate(parts)).to(dev)
         ids64 = torch.from_numpy(np.concatenate(plan)).to(dev)
         starts64 = np.concatenate([[0], np.cumsum([len(ids) for ids in plan])])
+        zooms = augment is not None and augment.scales
         if augment is not None:
             shifts_d, colors_d = _split_aug_table(table[pos:], int(starts64[-1]))
+        if zooms:
+            steps_d, origins_d, affines_d = _split_resample_table(table[zoom_at:], int(starts64[-1]))
 
         def assemble(step):
             pos, B, N = where[step]
             ids_d, offs_d = table[pos:pos + B], table[pos + B:pos + 2 * B + 1]
             starts_d, keep_d = table[pos + 2 * B + 1:pos + 3 * B + 1], table[pos + 3 * B + 1:pos + 4 * B + 1]
-            aug_shift = None
+            aug_shift = aug_affine = None
             if features is None:
                 images = torch.empty((B, 3, self.H, self.W), dtype=torch.float32, device=dev)
                 if augment is None:
@@ -535,13 +635,21 @@ class DeviceDataset:
                 else:
                     lo = int(starts64[step])
                     aug_shift = shifts_d[lo:lo + B]
-                    call("cova_pages_u8_augment_f32", self.store, ids_d, self.P, B, self.H, self.W, aug_shift,
-                         colors_d[lo:lo + B], augment.fill_rgb, images)
+                    if zooms:
+                        aug_affine = affines_d[lo:lo + B]
+                        call("cova_pages_u8_resample_f32", self.store, ids_d, self.P, B, self.H, self.W, steps_d[lo:lo + B],
+                             origins_d[lo:lo + B], colors_d[lo:lo + B], augment.fill_rgb, images)
+                    else:
+                        call("cova_pages_u8_augment_f32", self.store, ids_d, self.P, B, self.H, self.W, aug_shift,
+                             colors_d[lo:lo + B], augment.fill_rgb, images)
             out = _sample_and_collate(dev, self.cs, self.A, self.rows, self.addl, offs_d, starts_d, ids_d, keep_d, None,
                                       B, N, sseed, n_out=N if sf == 1.0 else None, want_sel=features is not None,
-                                      ks=self.ks, shift_d=aug_shift if aug_shift is not None and augment.shifts else None)
+                                      ks=self.ks, shift_d=aug_shift if aug_shift is not None and augment.shifts else None,
+                                      affine_d=aug_affine)
             if aug_shift is not None:
                 out["aug_shift"] = aug_shift
+            if aug_affine is not None:
+                out["aug_affine"] = aug_affine
             if features is None:
                 out["images"] = images
             else:       # the sampler's kept SOURCE row ids are the table's row ids (with sf == 1 it keeps every row)

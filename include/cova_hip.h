@@ -780,6 +780,35 @@ int cova_pages_u8_augment_f32(const uint8_t *store_u8, const int *page_idx /*nul
                               const int *shift /*nullable [B,2]*/, const float *color /*nullable [B,12]*/, int fill_rgb,
                               float *f32_nchw, void *stream);
 int cova_boxes_translate(float *bboxes, int N, const int *shift, int B, void *stream);
+/* ---- page zoom in the page gather (augment.hip; pipeline.PageAugment(scale=)) ----
+ * cova_pages_u8_resample_f32: cova_pages_u8_augment_f32 with the integer shift replaced by a bilinear resample in 16.16 fixed
+ *   point with 8-bit weights; integer arithmetic up to one correctly rounded division.  step DEVICE int32 [B,2] = inv_x, inv_y
+ *   (source pixels per output pixel, times 65536), origin DEVICE int64 [B,2] = org_x, org_y (the source position of output
+ *   pixel (0,0), times 65536; fraction 0 = exactly pixel i).  For output page b, row y, column x, channel c:
+ *     p_x = org_x + x*inv_x, p_y = org_y + y*inv_y                       in int64
+ *     i = p >> 16 (arithmetic: the floor), f = (p >> 8) & 255           per axis
+ *     the taps i and i+1 of an axis carry the integer weights 256 - f and f
+ *     a tap (ix, iy) with 0 <= ix < W and 0 <= iy < H is the page's byte v_c, any other tap byte c of fill_rgb = 0xRRGGBB
+ *     q_c = sum over the four taps of wy*wx*byte_c                      an integer <= 255*65536 = 16711680 < 2^24
+ *     t_c = (float)q_c / 16711680.f, correctly rounded
+ *     then color[b] (nullable: the identity) and the clamp exactly as cova_pages_u8_augment_f32 (unfused, never -0, NaN -> 0)
+ *   A tap of weight 0 changes nothing, wherever it lies.  With inv = 65536 on both axes and org = (-dx*65536, -dy*65536) the
+ *   output is bit-equal to cova_pages_u8_augment_f32 with shift = (dx, dy) (q_c = 65536*v_c, and the quotient is v_c/255's).
+ *   page_idx, P, B, an index outside [0,P) (the page stays unwritten), the 64-bit page offsets and the statuses are those of
+ *   cova_pages_u8_augment_f32; step and origin are required (NULL with B > 0 is a status).  Every address is formed from
+ *   a position already tested against (or clipped to) the page, so no table contents make a thread read outside the store;
+ *   the arithmetic above holds for 1 <= inv <= 2^22 and |org| < 2^62.  With W % 4 == 0, store_u8 4-byte and f32_nchw 16-byte
+ *   aligned a thread makes 4 pixels of a row; a page with 1 <= inv_x <= 131072 then takes its taps from the row segments its
+ *   wave staged in LDS (clipped to the page, the fill colour beside them), any other inv_x one by one from the store.  Otherwise a pixel-per-thread kernel writes the same bytes.  tests/resample_oracle.py is
+ *   the numpy statement.  One launch, no workspace, no atomics, no host read: capturable, bit-deterministic.
+ * cova_boxes_affine: cova_boxes_translate with a scale.  affine DEVICE f32 [B,4] = sx, sy, tx, ty; under the same guard on the
+ *   page column (NaN, negative, >= B: the row stays) x' = x*sx + tx for columns 1 and 3, y' = y*sy + ty for columns 2 and 4,
+ *   one float32 multiply then one float32 add, not fused.  With sx = sy = 1 and integer tx, ty: the bits of
+ *   cova_boxes_translate.  N == 0 returns without a launch; N < 0 or B < 0, and for N > 0 a NULL pointer or B == 0, a status. */
+int cova_pages_u8_resample_f32(const uint8_t *store_u8, const int *page_idx /*nullable*/, int P, int B, int H, int W,
+                               const int *step /*[B,2]*/, const long long *origin /*[B,2]*/,
+                               const float *color /*nullable [B,12]*/, int fill_rgb, float *f32_nchw, void *stream);
+int cova_boxes_affine(float *bboxes, int N, const float *affine /*[B,4]*/, int B, void *stream);
 /* ---- context graphs (graph.hip; pipeline.DeviceCollate / DeviceDataset(spatial_k=)) ----
  * cova_context_knn: the context table with spatial neighbours, ctx [N, 2*context_size + k_spatial] int64 batch-global ids,
  *   -1 pads.  bboxes [N,5] = page,x1,y1,x2,y2 exactly as cova_collate_boxes / cova_collate_selected wrote them (the page
