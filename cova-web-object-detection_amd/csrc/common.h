@@ -96,5 +96,32 @@ __device__ __forceinline__ float gat_dropped(const GatDrop &dr, size_t e, float 
     return hash_uniform(dr.seed, e) >= dr.p ? __fmul_rn(v, dr.inv) : 0.f;
 }
 
+// Neighbour id of one slot of the table ctx [N,K] (slot = i*K + k), as every wave-per-node GAT kernel reads it: an id >= N
+// is memory-safe and acts as a pad (-1), like the table's own -1 entries; ids fit an int (N does).
+__device__ __forceinline__ int gat_slot_id(const int64_t *__restrict__ ctx, size_t slot, int N)
+{
+    const long long j = ctx[slot];
+    return j >= N ? -1 : (int)j;
+}
+
+// Edge geometry (cova_gat_fwd_edge / cova_gat_bwd_edge, cova_gat2_*): the additive score term of one slot,
+// edge_w . phi[slot][0:8], as one fma chain in feature order.  A forward and its source-side backward both call this, so
+// the LeakyReLU slope the backward takes is the one the forward took, bit for bit.  phi rows are 32 bytes, 16-byte aligned:
+// two 16-byte loads.
+__device__ __forceinline__ float gat_edge_term(const float *__restrict__ phi, size_t slot, const float *__restrict__ edge_w)
+{
+    const float4 p0 = *reinterpret_cast<const float4 *>(phi + slot * 8);
+    const float4 p1 = *reinterpret_cast<const float4 *>(phi + slot * 8 + 4);
+    float g = edge_w[0] * p0.x;
+    g = fmaf(edge_w[1], p0.y, g);
+    g = fmaf(edge_w[2], p0.z, g);
+    g = fmaf(edge_w[3], p0.w, g);
+    g = fmaf(edge_w[4], p1.x, g);
+    g = fmaf(edge_w[5], p1.y, g);
+    g = fmaf(edge_w[6], p1.z, g);
+    g = fmaf(edge_w[7], p1.w, g);
+    return g;
+}
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline long long cdivll(long long a, long long b) { return (a + b - 1) / b; }

@@ -41,22 +41,6 @@ __device__ __forceinline__ void stv(float *__restrict__ p, const float (&r)[V])
     else p[0] = r[0];
 }
 
-// edge_w . phi[slot][0:8]: one fma chain in feature order (phi rows are 32 bytes, 16-byte aligned)
-__device__ __forceinline__ float gat2_edge_term(const float *__restrict__ phi, size_t slot, const float *__restrict__ edge_w)
-{
-    const float4 p0 = *reinterpret_cast<const float4 *>(phi + slot * 8);
-    const float4 p1 = *reinterpret_cast<const float4 *>(phi + slot * 8 + 4);
-    float g = edge_w[0] * p0.x;
-    g = fmaf(edge_w[1], p0.y, g);
-    g = fmaf(edge_w[2], p0.z, g);
-    g = fmaf(edge_w[3], p0.w, g);
-    g = fmaf(edge_w[4], p1.x, g);
-    g = fmaf(edge_w[5], p1.y, g);
-    g = fmaf(edge_w[6], p1.z, g);
-    g = fmaf(edge_w[7], p1.w, g);
-    return g;
-}
-
 // ------------------------------------------------------------------------------------------------ forward
 // DROP (all three kernels): attention dropout (common.h, GatDrop) -- attn keeps the softmax output, the aggregation and the
 // destination side weigh with gat_dropped(e, attn[e]), the source side scales dattn by keep * inv before the softmax backward.
@@ -89,12 +73,7 @@ __global__ __launch_bounds__(256) void gat2_fwd_kernel(
     float m = -INFINITY;
     for (int p0 = 0; p0 < K; p0 += 64) {                       // scores: slot p0 + q ends in lane q
         const int cnt = min(64, K - p0);
-        long long j = -1;
-        if (lane < cnt) {
-            j = ctx[(size_t)n * K + p0 + lane];
-            if (j >= N) j = -1;                                // out-of-range id: memory-safe, acts as a pad
-        }
-        const int jj = (int)j;
+        const int jj = lane < cnt ? gat_slot_id(ctx, (size_t)n * K + p0 + lane, N) : -1;
         float e = lane < cnt ? -9e15f : -INFINITY;             // pads keep the mask value (models.py:202-203)
         for (int q0 = 0; q0 < cnt; q0 += U) {
             int jk[U];
@@ -125,7 +104,7 @@ __global__ __launch_bounds__(256) void gat2_fwd_kernel(
                     }
                 }
                 float sc = wave_sum(part) + b;
-                if (EDGE) sc += gat2_edge_term(phi, (size_t)n * K + p0 + q0 + u, edge_w);
+                if (EDGE) sc += gat_edge_term(phi, (size_t)n * K + p0 + q0 + u, edge_w);
                 if (lane == q0 + u) e = sc;
             }
         }
@@ -147,17 +126,15 @@ __global__ __launch_bounds__(256) void gat2_fwd_kernel(
         for (int v = 0; v < V; ++v) acc[c][v] = 0.f;
     for (int p0 = 0; p0 < K; p0 += 64) {                       // aggregation, neighbours added in slot order
         const int cnt = min(64, K - p0);
-        long long j = -1;
+        int jj = -1;
         float aw = 0.f;
         if (lane < cnt) {
-            j = ctx[(size_t)n * K + p0 + lane];
-            if (j >= N) j = -1;
+            jj = gat_slot_id(ctx, (size_t)n * K + p0 + lane, N);
             const float alpha = se[p0 + lane] / denom;
             attn[(size_t)n * K + p0 + lane] = alpha;
-            aw = j >= 0 ? alpha : 0.f;                         // pads: no weight, no row read
-            if (DROP && j >= 0) aw = gat_dropped(dr, (size_t)n * K + p0 + lane, alpha);    // (dropped slots: no row read)
+            aw = jj >= 0 ? alpha : 0.f;                        // pads: no weight, no row read
+            if (DROP && jj >= 0) aw = gat_dropped(dr, (size_t)n * K + p0 + lane, alpha);   // (dropped slots: no row read)
         }
-        const int jj = (int)j;
         for (int q0 = 0; q0 < cnt; q0 += U) {
             float au[U], wj[U][NC][V];
 #pragma unroll
@@ -237,14 +214,12 @@ __global__ __launch_bounds__(256) void gat2_bwd_src_kernel(
         float ad = 0.f;
         for (int p0 = 0; p0 < K; p0 += 64) {                   // dattn of slot p0 + q ends in lane q
             const int cnt = min(64, K - p0);
-            long long j = -1;
+            int jj = -1;
             float alpha = 0.f, dalpha = 0.f;
             if (lane < cnt) {
-                j = ctx[(size_t)n * K + p0 + lane];
-                if (j >= N) j = -1;
+                jj = gat_slot_id(ctx, (size_t)n * K + p0 + lane, N);
                 alpha = attn[(size_t)n * K + p0 + lane];
             }
-            const int jj = (int)j;
             for (int q0 = 0; q0 < cnt; q0 += U) {
                 int jk[U];
                 float wj[U][NC][V];
@@ -284,15 +259,14 @@ __global__ __launch_bounds__(256) void gat2_bwd_src_kernel(
         for (int f = 0; f < 8; ++f) dphi[f] = 0.f;
         for (int p0 = 0; p0 < K; p0 += 64) {                   // du, then the gated sums over the slots in slot order
             const int cnt = min(64, K - p0);
-            long long j = -1;
+            int jj = -1;
             float du = 0.f;
             if (lane < cnt) {
-                j = ctx[(size_t)n * K + p0 + lane];
-                if (j >= N) j = -1;
-                if (j >= 0) du = attn[(size_t)n * K + p0 + lane] * (sk[p0 + lane] - dot);
+                jj = gat_slot_id(ctx, (size_t)n * K + p0 + lane, N);
+                if (jj >= 0) du = attn[(size_t)n * K + p0 + lane] * (sk[p0 + lane] - dot);
                 du_out[(size_t)n * K + p0 + lane] = du;
                 dus += du;
-                if (EDGE && j >= 0) {
+                if (EDGE && jj >= 0) {
                     const size_t slot = (size_t)n * K + p0 + lane;
                     const float4 f0 = *reinterpret_cast<const float4 *>(phi + slot * 8);
                     const float4 f1 = *reinterpret_cast<const float4 *>(phi + slot * 8 + 4);
@@ -302,7 +276,6 @@ __global__ __launch_bounds__(256) void gat2_bwd_src_kernel(
                     dphi[6] = fmaf(du, f1.z, dphi[6]); dphi[7] = fmaf(du, f1.w, dphi[7]);
                 }
             }
-            const int jj = (int)j;
             for (int q0 = 0; q0 < cnt; q0 += U) {
                 int jk[U];
                 float dk[U], wj[U][NC][V];

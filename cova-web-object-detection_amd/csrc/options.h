@@ -7,7 +7,7 @@ struct CovaOptions {
     int conv1_f32 = 0;       // key 7: 1 = conv1 forward and weight gradient on the f32 MFMA kernels instead of the bf16-split ones
     int wino4_f32 = 0;       // key 9: 1 = the F(4x4,3x3) main loop in f32 instead of the bf16 split
     int bn1d_variant = 1;    // key 14: != 0 = the float4 row kernels where the operands allow it, 0 = the 128-slice form
-    int gat_wide = 1;        // key 16: 1 = every 64-channel chunk of a neighbour row in flight (K <= 64, D <= 512), 0 = chunk by chunk
+    int gat_wide = 1;        // key 16: 1 = the GAT kernels' wide form <KP = 1, ND> where it applies (K <= 64, D <= 512: every 64-channel chunk of a neighbour row in flight), 0 = always the chunk form <KP, ND = 1> (roi_gat.hip, gat_form)
     int sgemm_dma = 1;       // key 22: 1 = the LDS-DMA sgemm kernel wherever the operands allow it
     std::atomic<bool> frozen{false};
 };

@@ -11,6 +11,7 @@
 // -1 pad row), mask -> -9e15, softmax over the K slots, h'_i = sum_k alpha_ik Wh_j[ctx(i,k)].
 // One wavefront per node: the K neighbour slots live in lanes (ceil(K / 64) passes, K <= 1024) for the softmax (shuffle
 // reductions), the D hidden channels live in lanes for the gather (256-byte coalesced rows).
+#include <type_traits>
 #include "bn_tail.h"
 #include "options.h"
 
@@ -635,35 +636,27 @@ __global__ __launch_bounds__(256) void gat_scores_kernel(const float *__restrict
     if (lane == 0) { s[n] = a + att_b[0]; t[n] = b; }
 }
 
-// Edge geometry (cova_gat_fwd_edge / cova_gat_bwd_edge): the additive score term of one slot, edge_w . phi[slot][0:8], as
-// one fma chain in feature order.  The forward and the source-side backward both call this, so the LeakyReLU slope the
-// backward takes is the one the forward took, bit for bit.  phi rows are 32 bytes: two 16-byte loads.
-__device__ __forceinline__ float gat_edge_term(const float *__restrict__ phi, size_t slot, const float *__restrict__ edge_w)
-{
-    const float4 p0 = *reinterpret_cast<const float4 *>(phi + slot * 8);
-    const float4 p1 = *reinterpret_cast<const float4 *>(phi + slot * 8 + 4);
-    float g = edge_w[0] * p0.x;
-    g = fmaf(edge_w[1], p0.y, g);
-    g = fmaf(edge_w[2], p0.z, g);
-    g = fmaf(edge_w[3], p0.w, g);
-    g = fmaf(edge_w[4], p1.x, g);
-    g = fmaf(edge_w[5], p1.y, g);
-    g = fmaf(edge_w[6], p1.z, g);
-    g = fmaf(edge_w[7], p1.w, g);
-    return g;
-}
-
-// KP = number of 64-slot passes a wave makes over the K neighbour slots (K <= 64 KP; KP = 1 is the reference's usual
-// range, -cs <= 32); slot k lives in lane k & 63 of pass k >> 6.  models.py:171-177 accepts any n_context.
+// The wave-per-node kernels below (forward, backward source side, backward destination side) are one template each over
+// the loop nest
+//     for d0 (64 ND channels a trip)  /  for p < KP  /  for neighbour batches: load batch x ND chunks, add in slot order
+// KP = number of 64-slot passes a wave makes over the K neighbour slots (K <= 64 KP; KP = 1 is the reference's usual range,
+// -cs <= 32); slot k lives in lane k & 63 of pass k >> 6.  models.py:171-177 accepts any n_context.
+// ND = 64-channel chunks of a row a lane holds per neighbour.  ND = 1 is the chunk-at-a-time form: any D, the d0 loop walks
+// the row.  ND > 1 (KP = 1, D <= 64 ND: gat_form) is the wide form: the d0 loop makes one trip, a batch has 8 ND (source
+// side: 4 ND) loads in flight, and a node makes ceil(K / 8) dependent round trips instead of ceil(K / 8) * D / 64 (18 -> 3
+// at configs[1]: 18.7 us of latency).  Every output adds its neighbours in slot / edge order and its channels ascending
+// whatever (KP, ND): identical bits.
+// Padding: a channel past D and a padding slot read a valid address (channel 0, row 0) with weight 0.
 // EDGE: the pre-activation of a slot also takes gat_edge_term (phi [N,K,8], edge_w [8]); false reads neither pointer.
 // DROP: attention dropout (common.h, GatDrop) -- attn keeps the softmax output, the aggregation weighs with gat_dropped().
-template <int KP, bool EDGE = false, bool DROP = false>
+template <int KP, int ND, bool EDGE = false, bool DROP = false>
 __global__ __launch_bounds__(256) void gat_fwd_kernel(
     const float *__restrict__ Wh, int ldw, const float *__restrict__ s, const float *__restrict__ t,
     const int64_t *__restrict__ ctx, int N, int K, int D, float slope, float *__restrict__ attn,
     float *__restrict__ hprime, int ldh, const float *__restrict__ phi = nullptr,
     const float *__restrict__ edge_w = nullptr, GatDrop dr = GatDrop{})
 {
+    static_assert(KP == 1 || ND == 1, "several passes over the slots: one 64-channel chunk at a time");
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (n >= N) return;
     int jj[KP];
@@ -672,17 +665,15 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(
 #pragma unroll
     for (int p = 0; p < KP; ++p) {
         const int k = 64 * p + lane;
-        long long j = -1;
+        jj[p] = -1;
         e[p] = -INFINITY;
         if (k < K) {
-            j = ctx[(size_t)n * K + k];
-            if (j >= N) j = -1;                                 // out-of-range id: memory-safe, acts as a pad
-            float u = s[n] + (j >= 0 ? t[j] : 0.f);
-            if (EDGE && j >= 0) u += gat_edge_term(phi, (size_t)n * K + k, edge_w);
+            jj[p] = gat_slot_id(ctx, (size_t)n * K + k, N);
+            float u = s[n] + (jj[p] >= 0 ? t[jj[p]] : 0.f);
+            if (EDGE && jj[p] >= 0) u += gat_edge_term(phi, (size_t)n * K + k, edge_w);
             const float lr = u > 0.f ? u : slope * u;
-            e[p] = j >= 0 ? lr : -9e15f;                       // models.py:202-203
+            e[p] = jj[p] >= 0 ? lr : -9e15f;                   // models.py:202-203
         }
-        jj[p] = (int)j;
         m = fmaxf(m, e[p]);
     }
     m = wave_max(m);
@@ -701,88 +692,39 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(
         aw[p] = jj[p] >= 0 ? alpha : 0.f;                      // pads: weight 0 on a valid (clamped) row
         if (DROP && jj[p] >= 0) aw[p] = gat_dropped(dr, (size_t)n * K + 64 * p + lane, alpha);
     }
-    for (int d0 = 0; d0 < D; d0 += 64) {
-        const int d = d0 + lane, dd = d < D ? d : 0;
-        float acc = 0.f;
+    int d0 = 0;
+    do {                                                       // 64 ND channels a trip: the chunk form walks the row
+        float acc[ND];
+        int dd[ND];
+#pragma unroll
+        for (int c = 0; c < ND; ++c) {
+            acc[c] = 0.f;
+            dd[c] = d0 + 64 * c + lane < D ? d0 + 64 * c + lane : 0;
+        }
 #pragma unroll
         for (int p = 0; p < KP; ++p) {
             const int Kp = min(64, K - 64 * p);                 // slots of this pass
-            for (int k0 = 0; k0 < Kp; k0 += 8) {                // 8 neighbour rows in flight, added in slot order
-                float v[8], a[8];
+            for (int k0 = 0; k0 < Kp; k0 += 8) {                // 8 neighbour rows x ND chunks in flight, added in slot order
+                float v[ND][8], a[8];
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     const int kk = min(k0 + u, Kp - 1);
                     const int jk = __shfl(jj[p], kk, 64);
                     a[u] = k0 + u < Kp ? __shfl(aw[p], kk, 64) : 0.f;
-                    v[u] = Wh[(size_t)(jk >= 0 ? jk : 0) * ldw + D + dd];
+                    const float *row = Wh + (size_t)(jk >= 0 ? jk : 0) * ldw + D;
+#pragma unroll
+                    for (int c = 0; c < ND; ++c) v[c][u] = row[dd[c]];
                 }
 #pragma unroll
-                for (int u = 0; u < 8; ++u) acc = a[u] != 0.f ? fmaf(a[u], v[u], acc) : acc;
+                for (int c = 0; c < ND; ++c)
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) acc[c] = a[u] != 0.f ? fmaf(a[u], v[c][u], acc[c]) : acc[c];
             }
-        }
-        if (d < D) hprime[(size_t)n * ldh + d] = acc;
-    }
-}
-
-// K <= 64 (the reference's range), D <= 64 ND: the same wave-per-node arithmetic as gat_fwd_kernel<1> with the loops of the
-// aggregation exchanged -- neighbour batches outside, the ND 64-channel chunks of a row inside -- so that one batch has
-// 8 ND loads in flight instead of 8 and a node makes ceil(K / 8) dependent round trips instead of ceil(K / 8) * D / 64
-// (18 -> 3 at configs[1]: 18.7 us of latency).  Every output still adds its neighbours in slot order: identical bits.
-template <int ND, bool EDGE = false, bool DROP = false>
-__global__ __launch_bounds__(256) void gat_fwd_wide_kernel(
-    const float *__restrict__ Wh, int ldw, const float *__restrict__ s, const float *__restrict__ t,
-    const int64_t *__restrict__ ctx, int N, int K, int D, float slope, float *__restrict__ attn,
-    float *__restrict__ hprime, int ldh, const float *__restrict__ phi = nullptr,
-    const float *__restrict__ edge_w = nullptr, GatDrop dr = GatDrop{})
-{
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (n >= N) return;
-    long long j = -1;
-    float e = -INFINITY;
-    if (lane < K) {
-        j = ctx[(size_t)n * K + lane];
-        if (j >= N) j = -1;                                 // out-of-range id: memory-safe, acts as a pad
-        float u = s[n] + (j >= 0 ? t[j] : 0.f);
-        if (EDGE && j >= 0) u += gat_edge_term(phi, (size_t)n * K + lane, edge_w);
-        const float lr = u > 0.f ? u : slope * u;
-        e = j >= 0 ? lr : -9e15f;                           // models.py:202-203
-    }
-    const int jj = (int)j;
-    const float m = wave_max(e);
-    const float pr = lane < K ? expf(e - m) : 0.f;
-    float psum = 0.f;
-    psum += pr;
-    const float denom = wave_sum(psum);
-    const float alpha = pr / denom;
-    if (lane < K) attn[(size_t)n * K + lane] = alpha;
-    float aw = jj >= 0 ? alpha : 0.f;                       // pads: weight 0 on a valid (clamped) row
-    if (DROP && jj >= 0) aw = gat_dropped(dr, (size_t)n * K + lane, alpha);
-    float acc[ND];
-    int dd[ND];
-#pragma unroll
-    for (int c = 0; c < ND; ++c) {
-        acc[c] = 0.f;
-        dd[c] = 64 * c + lane < D ? 64 * c + lane : 0;
-    }
-    for (int k0 = 0; k0 < K; k0 += 8) {                     // 8 neighbour rows x ND chunks in flight, added in slot order
-        float v[ND][8], a[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int kk = min(k0 + u, K - 1);
-            const int jk = __shfl(jj, kk, 64);
-            a[u] = k0 + u < K ? __shfl(aw, kk, 64) : 0.f;
-            const float *row = Wh + (size_t)(jk >= 0 ? jk : 0) * ldw + D;
-#pragma unroll
-            for (int c = 0; c < ND; ++c) v[c][u] = row[dd[c]];
         }
 #pragma unroll
         for (int c = 0; c < ND; ++c)
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc[c] = a[u] != 0.f ? fmaf(a[u], v[c][u], acc[c]) : acc[c];
-    }
-#pragma unroll
-    for (int c = 0; c < ND; ++c)
-        if (64 * c + lane < D) hprime[(size_t)n * ldh + 64 * c + lane] = acc[c];
+            if (d0 + 64 * c + lane < D) hprime[(size_t)n * ldh + d0 + 64 * c + lane] = acc[c];
+    } while (ND == 1 && (d0 += 64) < D);                       // (wide form: D <= 64 ND, one trip)
 }
 
 // ---- transposed neighbour index (CSR over destination nodes): lets the backward GATHER what the
@@ -894,9 +836,13 @@ __global__ __launch_bounds__(256) void csr_count_scan_kernel(const int64_t *__re
 // Source side (one wave per node i): everything that stays with node i -- du [N,K] (0 on pads),
 // ds, dWh_i = ds * a_i.  The contributions to OTHER nodes (dt[ctx], dWh_j[ctx]) are gathered by
 // gat_bwd_dst_kernel from du / attn / g through the transposed index.
+// (KP, ND) as in gat_fwd_kernel; four neighbour rows x ND chunks in flight.  The dot products g . Wh_j are the one place
+// where the two forms are two loops: the chunk form walks the row lane by lane (a lane past D leaves the loop) and reads a
+// chunk of the node's own gradient row beside the neighbours' chunks; the wide form reads that row once, ahead of the
+// neighbour loop, and forms and reduces one neighbour's partial sum before the next.  Prologue and epilogue are shared.
 // DROP: dalpha of a slot is the gradient of its DROPPED weight times keep * inv (0 on a dropped slot, which still takes
 // -alpha * dot through the softmax); alpha stays the undropped softmax output.
-template <int KP, bool EDGE = false, bool DROP = false>
+template <int KP, int ND, bool EDGE = false, bool DROP = false>
 __global__ __launch_bounds__(256) void gat_bwd_src_kernel(
     const float *__restrict__ g, int ldg, const float *__restrict__ Wh, int ldw,
     const float *__restrict__ s, const float *__restrict__ t, const float *__restrict__ attn,
@@ -904,6 +850,7 @@ __global__ __launch_bounds__(256) void gat_bwd_src_kernel(
     float slope, float *__restrict__ dWh, int lddw, float *__restrict__ ds, float *__restrict__ du_out,
     const float *__restrict__ phi = nullptr, const float *__restrict__ edge_w = nullptr, GatDrop dr = GatDrop{})
 {
+    static_assert(KP == 1 || ND == 1, "several passes over the slots: one 64-channel chunk at a time");
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (n >= N) return;
     int jj[KP];
@@ -911,34 +858,56 @@ __global__ __launch_bounds__(256) void gat_bwd_src_kernel(
 #pragma unroll
     for (int p = 0; p < KP; ++p) {
         const int k = 64 * p + lane;
-        long long j = -1;
+        jj[p] = -1;
         alpha[p] = 0.f;
         dalpha[p] = 0.f;
         if (k < K) {
-            j = ctx[(size_t)n * K + k];
-            if (j >= N) j = -1;
+            jj[p] = gat_slot_id(ctx, (size_t)n * K + k, N);
             alpha[p] = attn[(size_t)n * K + k];
         }
-        jj[p] = (int)j;
+    }
+    [[maybe_unused]] float gw[ND];                             // wide form: the node's own gradient row, read once
+    [[maybe_unused]] int dd[ND];
+    if constexpr (ND > 1) {
+#pragma unroll
+        for (int c = 0; c < ND; ++c) {
+            dd[c] = 64 * c + lane < D ? 64 * c + lane : 0;
+            gw[c] = g[(size_t)n * ldg + dd[c]];
+        }
     }
 #pragma unroll
     for (int p = 0; p < KP; ++p) {
         const int Kp = min(64, K - 64 * p);
-        for (int k0 = 0; k0 < Kp; k0 += 4) {                   // four neighbour rows in flight per channel slice
+        for (int k0 = 0; k0 < Kp; k0 += 4) {
             int jk[4];
             float part[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int u = 0; u < 4; ++u) jk[u] = __shfl(jj[p], min(k0 + u, Kp - 1), 64);
-            for (int d = lane; d < D; d += 64) {
-                const float gv = g[(size_t)n * ldg + d];
-                float w[4];
+            [[maybe_unused]] float wq[ND][4];
+            if constexpr (ND == 1) {                           // chunk form: the lanes walk the row, four rows in flight
+                for (int d = lane; d < D; d += 64) {
+                    const float gv = g[(size_t)n * ldg + d];
+                    float w[4];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) w[u] = Wh[(size_t)(jk[u] >= 0 ? jk[u] : 0) * ldw + D + d];
+                    for (int u = 0; u < 4; ++u) w[u] = Wh[(size_t)(jk[u] >= 0 ? jk[u] : 0) * ldw + D + d];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) part[u] = fmaf(gv, w[u], part[u]);
+                    for (int u = 0; u < 4; ++u) part[u] = fmaf(gv, w[u], part[u]);
+                }
+            } else {                                           // wide form: four rows x ND chunks in flight
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const float *row = Wh + (size_t)(jk[u] >= 0 ? jk[u] : 0) * ldw + D;
+#pragma unroll
+                    for (int c = 0; c < ND; ++c) wq[c][u] = row[dd[c]];
+                }
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
+                if constexpr (ND > 1) {                        // (one partial sum formed and reduced before the next)
+#pragma unroll
+                    for (int c = 0; c < ND; ++c)           // (a chunk past D holds channel 0's operands: not added)
+                        part[u] = 64 * c + lane < D ? fmaf(gw[c], wq[c][u], part[u]) : part[u];
+                }
                 const float tot = wave_sum(part[u]);
                 if (lane == k0 + u && jk[u] >= 0) dalpha[p] = tot;
             }
@@ -949,7 +918,7 @@ __global__ __launch_bounds__(256) void gat_bwd_src_kernel(
         for (int p = 0; p < KP; ++p)
             if (jj[p] >= 0) dalpha[p] = gat_dropped(dr, (size_t)n * K + 64 * p + lane, dalpha[p]);
     }
-    float ad = 0.f;
+    float ad = 0.f;                                            // (a rounded product, then the add: DESIGN 12.9)
 #pragma unroll
     for (int p = 0; p < KP; ++p) ad += alpha[p] * dalpha[p];
     const float dot = wave_sum(ad);
@@ -972,9 +941,9 @@ __global__ __launch_bounds__(256) void gat_bwd_src_kernel(
 }
 
 // backward, destination side (one wave per node j): dt[j] = sum_e du[e];
-// dWh_j[j] = sum_e alpha[e] * g[i_e] + dt[j] * a_j, e over row j of the transposed index, ascending
+// dWh_j[j] = sum_e alpha[e] * g[i_e] + dt[j] * a_j, e over row j of the transposed index, ascending; ND as in gat_fwd_kernel.
 // DROP: alpha[e] is the dropped weight gat_dropped(e, attn[e]), the forward's expression on the forward's slot index.
-template <bool DROP = false>
+template <int ND, bool DROP = false>
 __global__ __launch_bounds__(256) void gat_bwd_dst_kernel(
     const float *__restrict__ g, int ldg, const float *__restrict__ attn, const float *__restrict__ du,
     const int *__restrict__ row_ptr, const int *__restrict__ edges, const float *__restrict__ att_w, int N,
@@ -987,152 +956,47 @@ __global__ __launch_bounds__(256) void gat_bwd_dst_kernel(
     float dtj = 0.f;
     for (int c0 = 0; c0 < deg; c0 += 64) dtj += wave_sum(c0 + lane < deg ? du[edges[lo + c0 + lane]] : 0.f);
     if (lane == 0) dt[j] = dtj;
-    for (int d0 = 0; d0 < D; d0 += 64) {
-        const int d = d0 + lane;
-        const int dd = d < D ? d : 0;
-        float accv = 0.f;
+    int d0 = 0;
+    do {                                                       // 64 ND channels a trip: the chunk form walks the row
+        float accv[ND];
+        int dd[ND];
+#pragma unroll
+        for (int c = 0; c < ND; ++c) {
+            accv[c] = 0.f;
+            dd[c] = d0 + 64 * c + lane < D ? d0 + 64 * c + lane : 0;
+        }
         for (int c0 = 0; c0 < deg; c0 += 64) {
             const int e = c0 + lane < deg ? edges[lo + c0 + lane] : 0;
             float al = c0 + lane < deg ? attn[e] : 0.f;           // 0 weight on the padding lanes
             if (DROP && c0 + lane < deg) al = gat_dropped(dr, (size_t)e, al);
             const int cnt = min(64, deg - c0);
-            for (int q0 = 0; q0 < cnt; q0 += 8) {                  // 8 neighbour rows in flight, added in edge order
-                float gv[8], aq[8];
+            for (int q0 = 0; q0 < cnt; q0 += 8) {                  // 8 neighbour rows x ND chunks in flight, added in edge order
+                float gq[ND][8], aq[8];
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     const int qq = min(q0 + u, 63);
                     const int i = __shfl(e, qq, 64) / K;
-                    aq[u] = q0 + u < cnt ? __shfl(al, qq, 64) : 0.f;
-                    const float gl = g[(size_t)i * ldg + dd];      // (unconditional load; padding slots read row 0 ...)
-                    gv[u] = q0 + u < cnt ? gl : 0.f;               // ... and must not turn a non-finite g[0] into NaN: 0 * inf
+                    const bool in = q0 + u < cnt;
+                    aq[u] = in ? __shfl(al, qq, 64) : 0.f;
+                    const float *row = g + (size_t)i * ldg;
+#pragma unroll
+                    for (int c = 0; c < ND; ++c) {
+                        const float gl = row[dd[c]];               // (unconditional load; padding slots read row 0 ...)
+                        gq[c][u] = in ? gl : 0.f;                  // ... and must not turn a non-finite g[0] into NaN: 0 * inf
+                    }
                 }
 #pragma unroll
-                for (int u = 0; u < 8; ++u) accv = fmaf(aq[u], gv[u], accv);
+                for (int c = 0; c < ND; ++c)
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) accv[c] = fmaf(aq[u], gq[c][u], accv[c]);
             }
         }
-        if (d < D) dWh[(size_t)j * lddw + D + d] = accv + dtj * att_w[D + d];
-    }
-}
-
-// gat_bwd_src_kernel<1> / gat_bwd_dst_kernel with every 64-channel chunk of a row in flight per neighbour batch (see
-// gat_fwd_wide_kernel): K <= 64, D <= 64 ND; identical bits (each sum keeps its order: channels ascending inside a dot
-// product, edges ascending inside a gathered row).
-template <int ND, bool EDGE = false, bool DROP = false>
-__global__ __launch_bounds__(256) void gat_bwd_src_wide_kernel(
-    const float *__restrict__ g, int ldg, const float *__restrict__ Wh, int ldw,
-    const float *__restrict__ s, const float *__restrict__ t, const float *__restrict__ attn,
-    const int64_t *__restrict__ ctx, const float *__restrict__ att_w, int N, int K, int D,
-    float slope, float *__restrict__ dWh, int lddw, float *__restrict__ ds, float *__restrict__ du_out,
-    const float *__restrict__ phi = nullptr, const float *__restrict__ edge_w = nullptr, GatDrop dr = GatDrop{})
-{
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (n >= N) return;
-    long long j = -1;
-    float alpha = 0.f, dalpha = 0.f;
-    if (lane < K) {
-        j = ctx[(size_t)n * K + lane];
-        if (j >= N) j = -1;
-        alpha = attn[(size_t)n * K + lane];
-    }
-    const int jj = (int)j;
-    float gv[ND];
-    int dd[ND];
 #pragma unroll
-    for (int c = 0; c < ND; ++c) {
-        const bool in = 64 * c + lane < D;
-        dd[c] = in ? 64 * c + lane : 0;
-        gv[c] = in ? g[(size_t)n * ldg + dd[c]] : 0.f;       // (channels past D: weight 0 on a valid address)
-    }
-    for (int k0 = 0; k0 < K; k0 += 4) {                      // four neighbour rows x ND chunks in flight
-        int jk[4];
-        float w[ND][4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            jk[u] = __shfl(jj, min(k0 + u, K - 1), 64);
-            const float *row = Wh + (size_t)(jk[u] >= 0 ? jk[u] : 0) * ldw + D;
-#pragma unroll
-            for (int c = 0; c < ND; ++c) w[c][u] = row[dd[c]];
+        for (int c = 0; c < ND; ++c) {
+            const int d = d0 + 64 * c + lane;
+            if (d < D) dWh[(size_t)j * lddw + D + d] = accv[c] + dtj * att_w[D + d];
         }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            float part = 0.f;
-#pragma unroll
-            for (int c = 0; c < ND; ++c)
-                part = 64 * c + lane < D ? fmaf(gv[c], w[c][u], part) : part;      // (the channels gat_bwd_src_kernel's loop visits)
-            const float tot = wave_sum(part);
-            if (lane == k0 + u && jk[u] >= 0) dalpha = tot;
-        }
-    }
-    // (the sum below is gat_bwd_src_kernel's statement for statement: written as wave_sum(alpha * dalpha), hipcc's default
-    // -ffp-contract=fast fuses the product into the first add of the reduction -- an unrounded product, and for K > 32,
-    // where the partner lane holds a value, other bits than the chunk kernel's)
-    if (DROP && jj >= 0) dalpha = gat_dropped(dr, (size_t)n * K + lane, dalpha);
-    float ad = 0.f;
-    ad += alpha * dalpha;
-    const float dot = wave_sum(ad);
-    float du = 0.f;
-    if (lane < K && jj >= 0) {
-        const float de = alpha * (dalpha - dot);
-        float u = s[n] + t[jj];
-        if (EDGE) u += gat_edge_term(phi, (size_t)n * K + lane, edge_w);                   // (the forward's u, bit for bit)
-        du = de * (u > 0.f ? 1.f : slope);
-    }
-    if (lane < K) du_out[(size_t)n * K + lane] = du;
-    float dus = 0.f;
-    dus += du;
-    const float dsn = wave_sum(dus);
-    if (lane == 0) ds[n] = dsn;
-    for (int d = lane; d < D; d += 64) dWh[(size_t)n * lddw + d] = dsn * att_w[d];
-}
-
-template <int ND, bool DROP = false>
-__global__ __launch_bounds__(256) void gat_bwd_dst_wide_kernel(
-    const float *__restrict__ g, int ldg, const float *__restrict__ attn, const float *__restrict__ du,
-    const int *__restrict__ row_ptr, const int *__restrict__ edges, const float *__restrict__ att_w, int N,
-    int K, int D, float *__restrict__ dWh, int lddw, float *__restrict__ dt, GatDrop dr = GatDrop{})
-{
-    const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (j >= N) return;
-    const int lo = row_ptr[j], deg = row_ptr[j + 1] - lo;
-    float dtj = 0.f;
-    for (int c0 = 0; c0 < deg; c0 += 64) dtj += wave_sum(c0 + lane < deg ? du[edges[lo + c0 + lane]] : 0.f);
-    if (lane == 0) dt[j] = dtj;
-    float accv[ND];
-    int dd[ND];
-#pragma unroll
-    for (int c = 0; c < ND; ++c) {
-        accv[c] = 0.f;
-        dd[c] = 64 * c + lane < D ? 64 * c + lane : 0;
-    }
-    for (int c0 = 0; c0 < deg; c0 += 64) {
-        const int e = c0 + lane < deg ? edges[lo + c0 + lane] : 0;
-        float al = c0 + lane < deg ? attn[e] : 0.f;               // 0 weight on the padding lanes
-        if (DROP && c0 + lane < deg) al = gat_dropped(dr, (size_t)e, al);
-        const int cnt = min(64, deg - c0);
-        for (int q0 = 0; q0 < cnt; q0 += 8) {                      // 8 neighbour rows x ND chunks in flight, added in edge order
-            float gq[ND][8], aq[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int qq = min(q0 + u, 63);
-                const int i = __shfl(e, qq, 64) / K;
-                const bool in = q0 + u < cnt;
-                aq[u] = in ? __shfl(al, qq, 64) : 0.f;
-                const float *row = g + (size_t)i * ldg;
-#pragma unroll
-                for (int c = 0; c < ND; ++c) {
-                    const float gl = row[dd[c]];                   // (unconditional load; padding slots read row 0 ...)
-                    gq[c][u] = in ? gl : 0.f;                      // ... and must not turn a non-finite g[0] into NaN: 0 * inf
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < ND; ++c)
-#pragma unroll
-                for (int u = 0; u < 8; ++u) accv[c] = fmaf(aq[u], gq[c][u], accv[c]);
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < ND; ++c)
-        if (64 * c + lane < D) dWh[(size_t)j * lddw + D + 64 * c + lane] = accv[c] + dtj * att_w[D + 64 * c + lane];
+    } while (ND == 1 && (d0 += 64) < D);                       // (wide form: D <= 64 ND, one trip)
 }
 
 // the attention-vector gradients
@@ -1227,13 +1091,35 @@ __global__ __launch_bounds__(256) void gat_edge_wgrad_final_kernel(const float *
     }
 }
 
-// 64-channel chunks per row the wide GAT kernels are instantiated for (0: D too large, or switched off by
-// cova_set_option(16, 0): the chunk-at-a-time kernels)
-inline int gat_wide_nd(int D)
+// (K, D, options) -> the instantiation <KP, ND> of the three wave-per-node kernels.  K <= 64 and D <= 512: the wide form
+// <1, ND>, ND = 64-channel chunks of a row rounded up to 1, 2, 3, 4, 6, 8.  Otherwise, or with cova_set_option(16, 0): the
+// chunk form <KP, 1>, KP = ceil(K / 64) rounded up to 1 .. 8, 12, 16.
+struct GatForm {
+    int kp, nd;
+};
+
+inline GatForm gat_form(int K, int D)
 {
-    const int nd = (D + 63) / 64;
-    if (!cova_options().gat_wide || nd > 8) return 0;
-    return nd <= 4 ? nd : (nd <= 6 ? 6 : 8);
+    const int kp = (K + 63) / 64, nd = (D + 63) / 64;
+    if (kp == 1 && nd <= 8 && cova_options().gat_wide) return GatForm{1, nd <= 4 ? nd : (nd <= 6 ? 6 : 8)};
+    return GatForm{kp <= 8 ? kp : (kp <= 12 ? 12 : 16), 1};
+}
+
+// launch(KP, ND) with the form's values as compile-time constants: the one table of instantiations (a form outside it
+// launches nothing and is an error)
+template <class Launch>
+int gat_dispatch(GatForm f, Launch launch)
+{
+#define COVA_GAT_FORM(KP, ND)                                                                   \
+    case 100 * ND + KP: launch(std::integral_constant<int, KP>{}, std::integral_constant<int, ND>{}); break
+    switch (100 * f.nd + f.kp) {
+    COVA_GAT_FORM(1, 1); COVA_GAT_FORM(2, 1); COVA_GAT_FORM(3, 1); COVA_GAT_FORM(4, 1); COVA_GAT_FORM(5, 1);
+    COVA_GAT_FORM(6, 1); COVA_GAT_FORM(7, 1); COVA_GAT_FORM(8, 1); COVA_GAT_FORM(12, 1); COVA_GAT_FORM(16, 1);
+    COVA_GAT_FORM(1, 2); COVA_GAT_FORM(1, 3); COVA_GAT_FORM(1, 4); COVA_GAT_FORM(1, 6); COVA_GAT_FORM(1, 8);
+    default: return COVA_ERR_BAD_ARG;
+    }
+#undef COVA_GAT_FORM
+    return COVA_OK;
 }
 
 }  // namespace
@@ -1451,47 +1337,25 @@ COVA_API int cova_bbox_linear_bwd(const float *dz, const float *raw, float *dW, 
 
 // Wh [N, 2D] (ld = ldw): first D columns W_i h, last D columns W_j h.
 // Outputs: s, t [N]; attn [N, K]; hprime rows at hprime + n*ldh (D entries).
-// EDGE = false is cova_gat_fwd (phi, edge_w unused: NULL); true is cova_gat_fwd_edge -- the same launches, the second one
-// on the EDGE instantiation of its kernel.
+// The checks every forward entry point shares, then two launches.  EDGE = false is cova_gat_fwd (phi, edge_w unused: NULL);
+// true is cova_gat_fwd_edge -- the same launches, the second one on the EDGE instantiation of its kernel.
 namespace {
 template <bool EDGE, bool DROP = false>
 int gat_fwd_launch(const float *Wh, int ldw, const float *att_w, const float *att_b, const int64_t *ctx, int N, int K,
                    int D, float slope, float *s, float *t, float *attn, float *hprime, int ldh, const float *phi,
                    const float *edge_w, void *stream, GatDrop dr = GatDrop{})
 {
-    hipLaunchKernelGGL(gat_scores_kernel, dim3(cdiv(N, 4)), dim3(256), 0, (hipStream_t)stream, Wh,
-                       ldw, att_w, att_b, s, t, N, D);
-    COVA_LAUNCH_CHECK();
+    COVA_REQUIRE(Wh && att_w && att_b && ctx && s && t && attn && hprime && K > 0 && K <= COVA_GAT_MAX_K && D > 0);
+    if (N == 0) return COVA_OK;
     const dim3 grid(cdiv(N, 4)), blk(256);
     hipStream_t st = (hipStream_t)stream;
-    if (K <= 64 && gat_wide_nd(D) > 0) {        // every 64-channel chunk of a neighbour row in flight (identical bits)
-#define COVA_GAT_FWD_WIDE(ND) hipLaunchKernelGGL((gat_fwd_wide_kernel<ND, EDGE, DROP>), grid, blk, 0, st, Wh, ldw, s, t, ctx, N, K, D, slope, attn, hprime, ldh, phi, edge_w, dr)
-        switch (gat_wide_nd(D)) {
-        case 1: COVA_GAT_FWD_WIDE(1); break;
-        case 2: COVA_GAT_FWD_WIDE(2); break;
-        case 3: COVA_GAT_FWD_WIDE(3); break;
-        case 4: COVA_GAT_FWD_WIDE(4); break;
-        case 6: COVA_GAT_FWD_WIDE(6); break;
-        default: COVA_GAT_FWD_WIDE(8); break;
-        }
-#undef COVA_GAT_FWD_WIDE
-        COVA_LAUNCH_CHECK();
-        return COVA_OK;
-    }
-#define COVA_GAT_FWD(KP) hipLaunchKernelGGL((gat_fwd_kernel<KP, EDGE, DROP>), grid, blk, 0, st, Wh, ldw, s, t, ctx, N, K, D, slope, attn, hprime, ldh, phi, edge_w, dr)
-    switch ((K + 63) / 64) {        // one wave per node, K slots in ceil(K / 64) passes over the lanes
-    case 1: COVA_GAT_FWD(1); break;
-    case 2: COVA_GAT_FWD(2); break;
-    case 3: COVA_GAT_FWD(3); break;
-    case 4: COVA_GAT_FWD(4); break;
-    case 5: COVA_GAT_FWD(5); break;
-    case 6: COVA_GAT_FWD(6); break;
-    case 7: COVA_GAT_FWD(7); break;
-    case 8: COVA_GAT_FWD(8); break;
-    case 9: case 10: case 11: case 12: COVA_GAT_FWD(12); break;
-    default: COVA_GAT_FWD(16); break;
-    }
-#undef COVA_GAT_FWD
+    hipLaunchKernelGGL(gat_scores_kernel, grid, blk, 0, st, Wh, ldw, att_w, att_b, s, t, N, D);
+    COVA_LAUNCH_CHECK();
+    const int rc = gat_dispatch(gat_form(K, D), [&](auto kp, auto nd) {
+        hipLaunchKernelGGL((gat_fwd_kernel<decltype(kp)::value, decltype(nd)::value, EDGE, DROP>), grid, blk, 0, st, Wh,
+                           ldw, s, t, ctx, N, K, D, slope, attn, hprime, ldh, phi, edge_w, dr);
+    });
+    if (rc != COVA_OK) return rc;
     COVA_LAUNCH_CHECK();
     return COVA_OK;
 }
@@ -1501,8 +1365,6 @@ COVA_API int cova_gat_fwd(const float *Wh, int ldw, const float *att_w, const fl
                           const int64_t *ctx, int N, int K, int D, float slope, float *s, float *t,
                           float *attn, float *hprime, int ldh, void *stream)
 {
-    COVA_REQUIRE(Wh && att_w && att_b && ctx && s && t && attn && hprime && K > 0 && K <= COVA_GAT_MAX_K && D > 0);
-    if (N == 0) return COVA_OK;
     return gat_fwd_launch<false>(Wh, ldw, att_w, att_b, ctx, N, K, D, slope, s, t, attn, hprime, ldh, nullptr, nullptr,
                                  stream);
 }
@@ -1512,9 +1374,7 @@ COVA_API int cova_gat_fwd_edge(const float *Wh, int ldw, const float *att_w, con
                                const float *phi, const float *edge_w, int N, int K, int D, float slope, float *s,
                                float *t, float *attn, float *hprime, int ldh, void *stream)
 {
-    COVA_REQUIRE(Wh && att_w && att_b && ctx && s && t && attn && hprime && K > 0 && K <= COVA_GAT_MAX_K && D > 0);
     COVA_REQUIRE(phi && edge_w && ((uintptr_t)phi & 15) == 0);
-    if (N == 0) return COVA_OK;
     return gat_fwd_launch<true>(Wh, ldw, att_w, att_b, ctx, N, K, D, slope, s, t, attn, hprime, ldh, phi, edge_w, stream);
 }
 
@@ -1562,55 +1422,27 @@ COVA_API int cova_gat_transpose_reuse(const int64_t *ctx, int N, int K, int *csr
 
 // dWh [N, 2D] (ld = lddw) is fully written; ds, dt [N] scratch; d_att_w [2D], d_att_b [1].
 // csr (from cova_gat_transpose) + du [N,K] scratch, both required: gather form, no float atomics, bit-identical reruns.
-// EDGE = false is cova_gat_bwd (phi, edge_w, d_edge_w, edge_ws unused: NULL); true is cova_gat_bwd_edge.
+// The checks every backward entry point shares, then the launches.  EDGE = false is cova_gat_bwd (phi, edge_w, d_edge_w,
+// edge_ws unused: NULL); true is cova_gat_bwd_edge.
 namespace {
 template <bool EDGE, bool DROP = false>
 int gat_bwd_launch(const float *g, int ldg, const float *Wh, int ldw, const float *s, const float *t, const float *attn,
                    const int64_t *ctx, const float *att_w, int N, int K, int D, float slope, float *dWh, int lddw,
                    float *ds, float *dt, float *d_att_w, float *d_att_b, const int *csr, float *du, const float *phi,
                    const float *edge_w, float *d_edge_w, float *edge_ws, void *stream, GatDrop dr = GatDrop{})
-{    hipStream_t st = (hipStream_t)stream;
-    const int kp = (K + 63) / 64;
-    if (K <= 64 && gat_wide_nd(D) > 0) {
-        const dim3 grid(cdiv(N, 4)), blk(256);
-#define COVA_GAT_BWD_WIDE(ND)                                                                                               \
-        do {                                                                                                                \
-            hipLaunchKernelGGL((gat_bwd_src_wide_kernel<ND, EDGE, DROP>), grid, blk, 0, st, g, ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, \
-                               slope, dWh, lddw, ds, du, phi, edge_w, dr);                                                  \
-            hipLaunchKernelGGL((gat_bwd_dst_wide_kernel<ND, DROP>), grid, blk, 0, st, g, ldg, attn, du, csr, csr + N + 1, att_w, N, K, \
-                               D, dWh, lddw, dt, dr);                                                                       \
-        } while (0)
-        switch (gat_wide_nd(D)) {
-        case 1: COVA_GAT_BWD_WIDE(1); break;
-        case 2: COVA_GAT_BWD_WIDE(2); break;
-        case 3: COVA_GAT_BWD_WIDE(3); break;
-        case 4: COVA_GAT_BWD_WIDE(4); break;
-        case 6: COVA_GAT_BWD_WIDE(6); break;
-        default: COVA_GAT_BWD_WIDE(8); break;
-        }
-#undef COVA_GAT_BWD_WIDE
-        COVA_LAUNCH_CHECK();
-    } else {
-#define COVA_GAT_SRC(KP) hipLaunchKernelGGL((gat_bwd_src_kernel<KP, EDGE, DROP>), dim3(cdiv(N, 4)), dim3(256), 0, st, g, ldg, Wh, ldw, s, t, \
-                                            attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, du, phi, edge_w, dr)
-        switch (kp) {
-        case 1: COVA_GAT_SRC(1); break;
-        case 2: COVA_GAT_SRC(2); break;
-        case 3: COVA_GAT_SRC(3); break;
-        case 4: COVA_GAT_SRC(4); break;
-        case 5: COVA_GAT_SRC(5); break;
-        case 6: COVA_GAT_SRC(6); break;
-        case 7: COVA_GAT_SRC(7); break;
-        case 8: COVA_GAT_SRC(8); break;
-        case 9: case 10: case 11: case 12: COVA_GAT_SRC(12); break;
-        default: COVA_GAT_SRC(16); break;
-        }
-#undef COVA_GAT_SRC
-        COVA_LAUNCH_CHECK();
-        hipLaunchKernelGGL(gat_bwd_dst_kernel<DROP>, dim3(cdiv(N, 4)), dim3(256), 0, st, g, ldg, attn, du, csr,
+{
+    COVA_REQUIRE(g && Wh && s && t && attn && ctx && att_w && dWh && ds && dt && d_att_w && d_att_b && csr && du);
+    COVA_REQUIRE(K > 0 && K <= COVA_GAT_MAX_K && D > 0 && N > 0);
+    const dim3 grid(cdiv(N, 4)), blk(256);
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = gat_dispatch(gat_form(K, D), [&](auto kp, auto nd) {
+        hipLaunchKernelGGL((gat_bwd_src_kernel<decltype(kp)::value, decltype(nd)::value, EDGE, DROP>), grid, blk, 0, st, g,
+                           ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, du, phi, edge_w, dr);
+        hipLaunchKernelGGL((gat_bwd_dst_kernel<decltype(nd)::value, DROP>), grid, blk, 0, st, g, ldg, attn, du, csr,
                            csr + N + 1, att_w, N, K, D, dWh, lddw, dt, dr);
-        COVA_LAUNCH_CHECK();
-    }
+    });
+    if (rc != COVA_OK) return rc;
+    COVA_LAUNCH_CHECK();
     const bool v4 = (D % 4 == 0) && (ldw % 4 == 0) && (((uintptr_t)Wh & 15) == 0);
     hipLaunchKernelGGL((v4 ? gat_bwd_att_kernel<4> : gat_bwd_att_kernel<1>), dim3(cdiv(2 * D + 1, 64)), dim3(1024), 0,
                        st, Wh, ldw, ds, dt, d_att_w, d_att_b, N, D);
@@ -1632,9 +1464,6 @@ COVA_API int cova_gat_bwd(const float *g, int ldg, const float *Wh, int ldw, con
                           int N, int K, int D, float slope, float *dWh, int lddw, float *ds, float *dt,
                           float *d_att_w, float *d_att_b, const int *csr, float *du, void *stream)
 {
-    COVA_REQUIRE(g && Wh && s && t && attn && ctx && att_w && dWh && ds && dt && d_att_w && d_att_b);
-    COVA_REQUIRE(K > 0 && K <= COVA_GAT_MAX_K && D > 0 && N > 0);
-    COVA_REQUIRE(csr && du);
     return gat_bwd_launch<false>(g, ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, dt, d_att_w,
                                  d_att_b, csr, du, nullptr, nullptr, nullptr, nullptr, stream);
 }
@@ -1653,9 +1482,7 @@ COVA_API int cova_gat_bwd_edge(const float *g, int ldg, const float *Wh, int ldw
                                float *dt, float *d_att_w, float *d_att_b, float *d_edge_w, const int *csr, float *du,
                                float *workspace, void *stream)
 {
-    COVA_REQUIRE(g && Wh && s && t && attn && ctx && att_w && dWh && ds && dt && d_att_w && d_att_b);
-    COVA_REQUIRE(K > 0 && K <= COVA_GAT_MAX_K && D > 0 && N > 0);
-    COVA_REQUIRE(csr && du && phi && edge_w && d_edge_w && workspace && ((uintptr_t)phi & 15) == 0);
+    COVA_REQUIRE(phi && edge_w && d_edge_w && workspace && ((uintptr_t)phi & 15) == 0);
     return gat_bwd_launch<true>(g, ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, dt, d_att_w,
                                 d_att_b, csr, du, phi, edge_w, d_edge_w, workspace, stream);
 }
@@ -1670,16 +1497,10 @@ COVA_API int cova_gat_fwd_drop(const float *Wh, int ldw, const float *att_w, con
                                unsigned long long seed, float *s, float *t, float *attn, float *hprime, int ldh,
                                void *stream)
 {
-    COVA_REQUIRE(Wh && att_w && att_b && ctx && s && t && attn && hprime && K > 0 && K <= COVA_GAT_MAX_K && D > 0);
     COVA_REQUIRE((phi == nullptr) == (edge_w == nullptr) && ((uintptr_t)phi & 15) == 0);
     COVA_REQUIRE(p >= 0.f && p < 1.f);                         // (NaN fails both)
-    if (N == 0) return COVA_OK;
-    const GatDrop dr = gat_drop_of(p, seed);
-    if (phi)
-        return gat_fwd_launch<true, true>(Wh, ldw, att_w, att_b, ctx, N, K, D, slope, s, t, attn, hprime, ldh, phi, edge_w,
-                                          stream, dr);
-    return gat_fwd_launch<false, true>(Wh, ldw, att_w, att_b, ctx, N, K, D, slope, s, t, attn, hprime, ldh, nullptr,
-                                       nullptr, stream, dr);
+    return (phi ? gat_fwd_launch<true, true> : gat_fwd_launch<false, true>)(
+        Wh, ldw, att_w, att_b, ctx, N, K, D, slope, s, t, attn, hprime, ldh, phi, edge_w, stream, gat_drop_of(p, seed));
 }
 
 COVA_API int cova_gat_bwd_drop(const float *g, int ldg, const float *Wh, int ldw, const float *s, const float *t,
@@ -1688,16 +1509,10 @@ COVA_API int cova_gat_bwd_drop(const float *g, int ldg, const float *Wh, int ldw
                                float *dWh, int lddw, float *ds, float *dt, float *d_att_w, float *d_att_b,
                                float *d_edge_w, const int *csr, float *du, float *workspace, void *stream)
 {
-    COVA_REQUIRE(g && Wh && s && t && attn && ctx && att_w && dWh && ds && dt && d_att_w && d_att_b);
-    COVA_REQUIRE(K > 0 && K <= COVA_GAT_MAX_K && D > 0 && N > 0);
-    COVA_REQUIRE(csr && du && ((uintptr_t)phi & 15) == 0);
     COVA_REQUIRE((phi == nullptr) == (edge_w == nullptr) && (phi == nullptr) == (d_edge_w == nullptr) &&
-                 (phi == nullptr) == (workspace == nullptr));
+                 (phi == nullptr) == (workspace == nullptr) && ((uintptr_t)phi & 15) == 0);
     COVA_REQUIRE(p >= 0.f && p < 1.f);
-    const GatDrop dr = gat_drop_of(p, seed);
-    if (phi)
-        return gat_bwd_launch<true, true>(g, ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, dt,
-                                          d_att_w, d_att_b, csr, du, phi, edge_w, d_edge_w, workspace, stream, dr);
-    return gat_bwd_launch<false, true>(g, ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, dt, d_att_w,
-                                       d_att_b, csr, du, nullptr, nullptr, nullptr, nullptr, stream, dr);
+    return (phi ? gat_bwd_launch<true, true> : gat_bwd_launch<false, true>)(
+        g, ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, dt, d_att_w, d_att_b, csr, du, phi, edge_w,
+        d_edge_w, workspace, stream, gat_drop_of(p, seed));
 }

@@ -1093,6 +1093,55 @@ def test_gat_wide_kernels_equal_the_chunk_kernels_bit_for_bit(D, K):
     assert bool(torch.isfinite(res[1][0]).all()) and bool(torch.isfinite(res[1][2]).all())
 
 
+@pytest.mark.parametrize("mode", ["edge", "drop", "edge+drop"])
+@pytest.mark.parametrize("D,K", [(40, 13), (330, 48), (512, 64)])
+def test_gat_wide_form_equals_the_chunk_form_with_edge_term_and_dropout(D, K, mode):
+    """cova_set_option(16, .) through the EDGE and DROP instantiations (cova_gat_fwd_edge / _drop, cova_gat_bwd_edge / _drop):
+    a partial single chunk, five-and-a-bit chunks on the ND = 6 instantiation, the last wide shape on both axes; one all-pad
+    row, a hub column, ids >= N (pads).  The two forms are instantiations of one template, so this holds the loop exchange
+    and the dispatch, not the arithmetic they share: that is held to the float64 oracles by tests/test_edge_gpu.py and
+    tests/test_attn_dropout_gpu.py.  At D <= 64 both settings reach <KP = 1, ND = 1>, so (40, 13) holds only that the
+    option changes nothing there."""
+    N, Fd = 37, 24
+    rs = np.random.RandomState(100 * D + K)
+    c = rs.randint(-1, N, (N, K))
+    c[:, 0] = 17                                             # a hub
+    c[rs.randint(0, N, 6), rs.randint(1, K, 6)] = N + rs.randint(0, 5, 6)
+    c[5, K - 1] = N
+    c[3] = -1                                                # (after the hub column: the whole row)
+    ctx = torch.from_numpy(c.astype(np.int64))
+    h, sd, g = _gat_case(N, K, Fd, D, ctx, 6)
+    phi, drop = None, None
+    if "edge" in mode:
+        sd["gat.edge_layer.weight"] = torch.from_numpy(rs.uniform(-1.5, 1.5, (1, 8)).astype(np.float32))
+        pad = (ctx < 0) | (ctx >= N)
+        phi = torch.from_numpy(rs.standard_normal((N, K, 8)).astype(np.float32)).masked_fill(pad[:, :, None], 0.0).to(DEV)
+    if "drop" in mode:
+        drop = (0.5, 20241 + D)
+    params = {k: v.to(DEV) for k, v in sd.items()}
+    res = []
+    for wide in (0, 1):
+        query("cova_set_option", 16, wide)
+        try:
+            hp = torch.empty(N, D, device=DEV)
+            sv = engine.gat_fwd(h.to(DEV), Fd, N, Fd, ctx.to(DEV), params, hp, D, phi=phi, drop=drop)
+            dh = torch.empty(N, Fd, device=DEV)
+            grads = engine.gat_bwd(sv, g.to(DEV), D, params, dh, Fd, False)
+            res.append((hp, sv["attn"], dh, grads))
+        finally:
+            query("cova_set_option", 16, 1)
+    assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1]) and torch.equal(res[0][2], res[1][2])
+    assert set(res[0][3]) == set(sd) and set(res[1][3]) == set(sd)         # d_edge_w included
+    for k in res[0][3]:
+        assert torch.equal(res[0][3][k], res[1][3][k]), k
+    assert bool(torch.isfinite(res[1][0]).all()) and bool(torch.isfinite(res[1][2]).all())
+    assert float(res[1][0][3].abs().max()) == 0.0                          # the all-pad row gathers nothing
+    if drop is not None:                                                   # the mask is live: h' is not the undropped one
+        hp = torch.empty(N, D, device=DEV)
+        engine.gat_fwd(h.to(DEV), Fd, N, Fd, ctx.to(DEV), params, hp, D, phi=phi)
+        assert not torch.equal(hp, res[1][0])
+
+
 def test_roipool_backward_rows_are_deterministic_and_cover_the_map():
     """Heavily nested boxes (every box inside the previous one: maximal arg-max collisions), C = 256, a map
     wider than one LDS segment: equals the oracle's sequential scatter, no element left unwritten, reruns equal."""
