@@ -1756,6 +1756,28 @@ def ce_sum(logits, labels, want_grad=True, gscale=1.0):
     return loss, dl, pred
 
 
+# ------------------------------------------------------------------------------------------- page decoding
+DECODE_MODES = ("column", "joint")
+DECODE_SCORES = ("logit", "map")                     # the score_mode of cova_page_joint_decode is the index
+JOINT_MAX_CLASSES = 7
+
+
+def check_decode(decode, score, n_classes, k=1):
+    """Host validation of a page decoding mode (ValueError each) -> the score_mode of cova_page_joint_decode.
+    "column": the arg-max of every class column on its own; "joint": one distinct box per class (k must be 1, at most
+    7 classes: the kernel enumerates up to 7^6 assignments a page)."""
+    if decode not in DECODE_MODES:
+        raise ValueError("decode must be one of %s, got %r" % (DECODE_MODES, decode))
+    if score not in DECODE_SCORES:
+        raise ValueError("the decoding score must be one of %s, got %r" % (DECODE_SCORES, score))
+    if decode == "joint":
+        if int(k) != 1:
+            raise ValueError("decode=\"joint\" decides one box per class: k must be 1, got %r" % (k,))
+        if not 2 <= int(n_classes) <= JOINT_MAX_CLASSES:
+            raise ValueError("decode=\"joint\" takes 2..%d classes, got %r" % (JOINT_MAX_CLASSES, n_classes))
+    return DECODE_SCORES.index(score)
+
+
 # ------------------------------------------------------------------------------------------- configurable criterion
 LOSS_MAX_CLASSES = 16
 LOSS_REDUCTIONS = ("sum", "mean")

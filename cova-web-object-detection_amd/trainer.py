@@ -1129,14 +1129,24 @@ class HotPathTrainer:
         return loss, pred
 
     @torch.no_grad()
-    def evaluate(self, batch, page_start, k=1):
+    def evaluate(self, batch, page_start, k=1, decode="column", score="map"):
         """Eval-mode decisions of train.py:131-154 for one batch.  ``page_start`` int64 [n_pages+1]
         box offsets.  Returns (topk [n_pages, n_classes, k] page-local box indices, best first;
-        correct [n_pages, n_classes-1] bool = the labelled box of class c is among the top k)."""
+        correct [n_pages, n_classes-1] bool = the labelled box of class c is among the top k).
+        ``decode="joint"`` (k must be 1, at most 7 classes, else ValueError): ``topk[:, 1:, 0]`` is the joint choice of
+        cova_page_joint_decode -- one distinct box per class, scored by ``score`` ("map": logit minus the background
+        logit, "logit") -- and ``correct`` its hit table (== 1); column 0 stays the arg-max of the background column."""
+        mode = engine.check_decode(decode, score, int(self.cfg["n_classes"]), k)
         logits, _ = self.predict(batch)
         n_pages, nc = page_start.numel() - 1, logits.shape[1]
         topk = torch.empty((n_pages, nc, k), dtype=torch.int64, device=logits.device)
         engine.call("cova_page_class_topk", logits, page_start.contiguous(), n_pages, nc, k, topk)
+        if decode == "joint":
+            tab = torch.full((2, n_pages, nc - 1), -2, dtype=torch.int32, device=logits.device)
+            engine.call("cova_page_joint_decode", logits, batch["labels"], page_start.contiguous(), None, n_pages, nc,
+                        n_pages, mode, tab[0], tab[1], None)
+            topk[:, 1:, 0] = tab[0]
+            return topk, tab[1] == 1
         # train.py:146: the labelled box of class c is the FIRST box of that class within the page;
         # a page without one scores False (the reference would raise an IndexError there)
         labels = batch["labels"]

@@ -706,6 +706,34 @@ int cova_page_class_topk(const float *logits, const int64_t *page_start, int n_p
 int cova_eval_page_ranks(const float *logits, const int64_t *labels, const int64_t *page_start,
                          const int *page_ids /*nullable [B]*/, int B, int NC, int P, int *rank,
                          int *top1 /*nullable [P,NC-1]*/, void *stream);
+/* joint page decoding (decode.hip; evaluate_split / predict_split / HotPathTrainer.evaluate / fit with decode="joint"): one
+ * DISTINCT box per non-background class, the most probable labelling of a page that holds exactly one box of each class.
+ * Page p of the batch owns rows [page_start[p], page_start[p+1]) as for cova_eval_page_ranks (DEVICE int64 [B+1],
+ * non-decreasing by the caller's contract; a negative start counts as 0, an end below its start as an empty page).  n is
+ * its box count, C = NC - 1, i the page-local index.
+ *   score of box i for class c in 1..C, float32: score_mode 0 ("logit") logits[i, c]; score_mode 1 ("map")
+ *     logits[i, c] - logits[i, 0], one float32 subtraction.  A NaN score counts as -inf.
+ *   order of a column: score descending, ties to the lower index (cova_page_class_topk's order).
+ *   candidates of class c: the first m = min(n, C + 1) boxes of its column in that order.
+ *   assignment: a tuple of ranks (r_1..r_C), each in [0, m), whose candidate boxes are pairwise distinct.
+ *   total: the float64 sum of the C float32 scores, added in class order ((s_1 + s_2) + s_3) ...; a NaN total counts as -inf.
+ *   result: the assignment with the greatest total, among equal totals the lexicographically smallest rank tuple;
+ *     choice[row, c-1] = page-local index of class c's box.
+ *   gap[row] (nullable, float64) = the best total minus the greatest total of any other assignment: +inf when there is no
+ *     other assignment, 0 on a tie (also when both totals are -inf, or both +inf).
+ *   0 < n < C (the classes cannot all be served): choice is the column decision (the first of each column's order),
+ *     gap = +inf.  n = 0: choice = -1, gap = +inf.
+ *   hit[row, c-1] (nullable; needs labels): 1 when labels[choice] == c, 0 when not, -1 when the page has no box labelled c.
+ * labels is nullable when hit is NULL.  row = page_ids[p] (DEVICE int32 [B]), or p when page_ids is NULL; a row outside
+ * [0, P) is skipped, rows of pages not in the batch are not written (the caller pre-fills choice and hit with -2 and gap
+ * with -1.0, so one all-reduce(MAX) merges the tables of several ranks).  Any page size (0, 1, thousands of boxes);
+ * 2 <= NC <= 7 (7^6 = 117649 tuples at most) and score_mode in {0, 1}, else a status and no launch.  Only additions and
+ * compares, none contracted or reordered; tests/decode_oracle.py is the numpy statement.  One launch, one block per page,
+ * no workspace, no atomics, no host read: a page's result does not depend on the batch around it. */
+int cova_page_joint_decode(const float *logits, const int64_t *labels /*nullable*/, const int64_t *page_start,
+                           const int *page_ids /*nullable [B]*/, int B, int NC, int P, int score_mode,
+                           int *choice /*[P,NC-1]*/, int *hit /*nullable [P,NC-1]*/, double *gap /*nullable [P]*/,
+                           void *stream);
 
 /* ---- device-side input pipeline --------------------------------------
  * ToTensor of datasets.py:41-45,96-97: u8 [B,H,W,3] -> f32 [B,3,H,W], value/255 (bit-exact) */

@@ -1,0 +1,245 @@
+"""GPU tests of joint page decoding: cova_page_joint_decode against the numpy oracle (tests/decode_oracle.py) bit for bit on
+the case table of tests/decode_cases.py, its refused arguments, and the decision through evaluate_split, predict_split,
+HotPathTrainer.evaluate and fit on a small resident split."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from cova_web_object_detection_amd import engine, evaluation, weights  # noqa: E402
+from cova_web_object_detection_amd.evaluation import EvalReport, evaluate_split, fit, predict_split  # noqa: E402
+from cova_web_object_detection_amd.pipeline import DeviceDataset  # noqa: E402
+from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
+import decode_cases as DC  # noqa: E402
+import decode_oracle as DO  # noqa: E402
+
+DEV = "cuda:0"
+
+
+def run_kernel(logits, labels, page_start, nc, score_mode, page_ids=None, P=None, want_hit=True, want_gap=True):
+    """cova_page_joint_decode on one batch -> (choice, hit, gap) numpy, the tables pre-filled with -2 / -2 / -1.0."""
+    B = len(page_start) - 1
+    P = B if P is None else P
+    lg = torch.as_tensor(np.ascontiguousarray(logits, dtype=np.float32)).to(DEV).reshape(-1, nc)
+    lb = None if labels is None else torch.as_tensor(np.ascontiguousarray(labels, dtype=np.int64)).to(DEV)
+    ps = torch.as_tensor(np.asarray(page_start, dtype=np.int64)).to(DEV)
+    ids = None if page_ids is None else torch.as_tensor(np.asarray(page_ids, dtype=np.int32)).to(DEV)
+    choice = torch.full((P, nc - 1), -2, dtype=torch.int32, device=DEV)
+    hit = torch.full((P, nc - 1), -2, dtype=torch.int32, device=DEV) if want_hit else None
+    gap = torch.full((P,), -1.0, dtype=torch.float64, device=DEV) if want_gap else None
+    engine.call("cova_page_joint_decode", lg, lb, ps, ids, B, nc, P, score_mode, choice, hit, gap)
+    torch.cuda.synchronize()
+    return tuple(None if t is None else t.cpu().numpy() for t in (choice, hit, gap))
+
+
+def assert_same_bytes(got, ref, what):
+    for name, g, r in zip(("choice", "hit", "gap"), got, ref):
+        assert g.dtype == r.dtype and g.shape == r.shape, (what, name)
+        if g.tobytes() != r.tobytes():
+            bad = np.nonzero((g != r).reshape(g.shape[0], -1).any(axis=1))[0]
+            raise AssertionError("%s: %s differs in rows %s: got %s, oracle %s"
+                                 % (what, name, bad[:8].tolist(), g[bad[:8]].tolist(), r[bad[:8]].tolist()))
+
+
+# ---------------------------------------------------------------- 1. the kernel against the oracle
+@pytest.mark.parametrize("name", ["nc4_mode0", "nc4_mode1", "special_mode0", "special_mode1", "nc2", "nc7", "nc4_2500"])
+def test_kernel_equals_the_oracle_bit_for_bit(name):
+    c = DC.gpu_cases()[name]
+    got = run_kernel(c["logits"], c["labels"], c["page_start"], c["nc"], c["score_mode"])
+    assert_same_bytes(got, DC.oracle_tables(name), name)
+    if name == "nc2":                                  # one class: the joint decision is the column decision
+        for p, (logits, _) in enumerate(DC.pages_of(c)):
+            assert got[0][p].tolist() == DO.column_page(logits, c["score_mode"])
+
+
+def test_scattered_rows_bad_ids_and_untouched_rows_keep_their_prefill():
+    c = DC.gpu_cases()["nc4_mode1"]
+    B = len(c["sizes"])
+    P = B + 6
+    ids = np.random.RandomState(3).permutation(P)[:B].astype(np.int32)
+    ids[2], ids[8] = -1, P                             # a page of 2 boxes and one of 65: both skipped
+    got = run_kernel(c["logits"], c["labels"], c["page_start"], 4, 1, page_ids=ids, P=P)
+    ref = DO.joint_decode(c["logits"], c["labels"], c["page_start"], 4, 1, page_ids=ids, P=P)
+    assert_same_bytes(got, ref, "scattered")
+    written = sorted(int(i) for i in ids if 0 <= i < P)
+    untouched = [r for r in range(P) if r not in written]
+    assert len(written) == B - 2 and len(untouched) == 8
+    assert (got[0][untouched] == -2).all() and (got[1][untouched] == -2).all() and (got[2][untouched] == -1.0).all()
+    whole = DC.oracle_tables("nc4_mode1")
+    for p in range(B):
+        if 0 <= ids[p] < P:
+            assert got[0][ids[p]].tolist() == whole[0][p].tolist() and got[2][ids[p]] == whole[2][p]
+
+
+def test_nullable_outputs():
+    c = DC.gpu_cases()["nc4_mode1"]
+    ref = DC.oracle_tables("nc4_mode1")
+    choice, hit, gap = run_kernel(c["logits"], None, c["page_start"], 4, 1, want_hit=False)
+    assert hit is None and choice.tobytes() == ref[0].tobytes() and gap.tobytes() == ref[2].tobytes()
+    choice, hit, gap = run_kernel(c["logits"], c["labels"], c["page_start"], 4, 1, want_gap=False)
+    assert gap is None and choice.tobytes() == ref[0].tobytes() and hit.tobytes() == ref[1].tobytes()
+    choice, hit, gap = run_kernel(c["logits"], None, c["page_start"], 4, 1, want_hit=False, want_gap=False)
+    assert choice.tobytes() == ref[0].tobytes()
+
+
+def test_a_page_does_not_depend_on_the_batch_around_it():
+    c = DC.gpu_cases()["nc4_mode0"]
+    pages = DC.pages_of(c)
+    order = np.random.RandomState(5).permutation(len(pages))
+    shuffled = DC.batch_of([pages[p] for p in order], 4)
+    got = run_kernel(shuffled["logits"], shuffled["labels"], shuffled["page_start"], 4, 0, page_ids=order)
+    assert_same_bytes(got, DC.oracle_tables("nc4_mode0"), "shuffled batch")
+    alone = run_kernel(pages[10][0], pages[10][1], [0, 300], 4, 0)             # and a page on its own
+    assert [t[0].tolist() for t in alone] == [t[10].tolist() for t in DC.oracle_tables("nc4_mode0")]
+
+
+def test_refused_arguments_return_the_status_without_a_launch():
+    c = DC.gpu_cases()["nc2"]
+    for nc, mode in ((8, 1), (2, 2), (2, -1), (1, 0)):
+        lg = torch.zeros((16, max(nc, 2)), device=DEV)
+        ps = torch.tensor([0, 16], dtype=torch.int64, device=DEV)
+        choice = torch.full((1, 8), -2, dtype=torch.int32, device=DEV)
+        with pytest.raises(engine._lib.CovaHipError, match="status 10001"):
+            engine.call("cova_page_joint_decode", lg, None, ps, None, 1, nc, 1, mode, choice, None, None)
+        torch.cuda.synchronize()
+        assert (choice == -2).all()
+    lg = torch.as_tensor(c["logits"]).to(DEV)
+    ps = torch.as_tensor(c["page_start"]).to(DEV)
+    hit = torch.full((4, 1), -2, dtype=torch.int32, device=DEV)
+    with pytest.raises(engine._lib.CovaHipError, match="status 10001"):         # a hit table needs labels
+        engine.call("cova_page_joint_decode", lg, None, ps, None, 4, 2, 4, 1, hit.clone(), hit, None)
+
+
+# ---------------------------------------------------------------- 2. through the trainer
+CFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8,
+           n_additional_feat=0, drop_prob=0.2)
+CS = 6
+BOXES = [14, 2, 23, 11, 30, 17]                        # page 1 has fewer boxes than classes
+
+
+def page_set(img=96, seed=4):
+    rs = np.random.RandomState(seed)
+    u8 = rs.randint(0, 256, (len(BOXES), img, img, 3)).astype(np.uint8)
+    rows = []
+    for n in BOXES:
+        wh = rs.uniform(6, 40, (n, 2))
+        xy = rs.uniform(0, 1, (n, 2)) * (img - wh)
+        lab = np.zeros((n, 1))
+        k = min(n, 3)
+        lab[rs.permutation(n)[:k], 0] = np.arange(1, k + 1)
+        rows.append(np.concatenate([xy, wh, lab], 1).astype(np.float32))
+    return u8, rows
+
+
+def seeded(seed=77):
+    return weights.seeded_state_dict(seed, logit_gain=2.0, **{k: v for k, v in CFG.items() if k != "drop_prob"})
+
+
+@functools.lru_cache(maxsize=None)
+def split():
+    """(dataset, trainer, the joint and the column report of the whole split, both at batch size 4)."""
+    u8, rows = page_set()
+    ds, tr = DeviceDataset(u8, rows, CS, DEV), HotPathTrainer(CFG, seeded(), DEV)
+    return ds, tr, evaluate_split(tr, ds, batch_size=4, decode="joint"), evaluate_split(tr, ds, batch_size=4)
+
+
+def oracle_of_split(ds, tr, score_mode, batch_size=4):
+    """The oracle applied to trainer.predict's logits of the same batches."""
+    out = []
+    for batch in ds.batches(batch_size):
+        logits, _ = tr.predict(batch)
+        out.append(DO.joint_decode(logits.cpu().numpy(), batch["labels"].cpu().numpy(),
+                                   batch["page_start"].cpu().numpy(), 4, score_mode))
+    return [np.concatenate([o[i] for o in out]) for i in range(3)]
+
+
+@pytest.mark.parametrize("score", ["map", "logit"])
+def test_evaluate_split_tables_equal_the_oracle_on_the_trainers_logits(score):
+    ds, tr, joint, column = split()
+    rep = joint if score == "map" else evaluate_split(tr, ds, batch_size=4, decode="joint", score=score)
+    ref = oracle_of_split(ds, tr, engine.DECODE_SCORES.index(score))
+    assert_same_bytes((rep.joint_top1, rep.joint_hit, rep.joint_gap), ref, "evaluate_split " + score)
+    assert rep.ranks.tobytes() == column.ranks.tobytes() and rep.top1.tobytes() == column.top1.tobytes()
+    assert column.joint_hit is None and column.joint_top1 is None and column.joint_gap is None
+    assert rep.evaluated.all() and rep.joint_gap[1] == np.inf and rep.joint_hit[1, 2] == -1     # two boxes: no class 3
+    assert np.array_equal(rep.hits(1, "joint"), ref[1] == 1)
+    for p, n in enumerate(BOXES):
+        if n >= 3:
+            assert len(set(rep.joint_top1[p].tolist())) == 3 and 0 <= rep.joint_gap[p] < np.inf
+
+
+def test_rank_shards_merge_to_the_single_rank_report():
+    ds, tr, joint, _ = split()
+    parts = [evaluate_split(tr, ds, batch_size=4, rank=r, world_size=2, merge=False, decode="joint") for r in (0, 1)]
+    assert parts[0].evaluated.tolist() == [p < 3 for p in range(6)] and (parts[0].joint_gap[3:] == -1.0).all()
+    assert (parts[1].joint_hit[:3] == -2).all() and (parts[1].joint_top1[:3] == -2).all()
+    merged = EvalReport.merge(parts)
+    for name in ("ranks", "top1", "joint_top1", "joint_hit", "joint_gap"):
+        assert getattr(merged, name).tobytes() == getattr(joint, name).tobytes(), name
+
+
+def test_predict_split_and_trainer_evaluate_agree_with_the_report(monkeypatch):
+    ds, tr, joint, column = split()
+    copies = []
+    read = evaluation._read_tables
+    monkeypatch.setattr(evaluation, "_read_tables", lambda blob: copies.append(1) or read(blob))
+    boxes, gap = predict_split(tr, ds, batch_size=4)
+    assert len(copies) == 1                                                    # one copy at the end
+    assert boxes.dtype == np.int32 and gap.dtype == np.float64
+    assert boxes.tobytes() == joint.joint_top1.tobytes() and gap.tobytes() == joint.joint_gap.tobytes()
+    boxes, gap = predict_split(tr, ds, batch_size=4, decode="column")
+    assert gap is None and boxes.tobytes() == column.top1.tobytes()
+    again, _ = predict_split(tr, ds, batch_size=5)                               # another batch size: the same pages
+    assert again.shape == (6, 3) and (again >= 0).all() and (again < np.asarray(BOXES)[:, None]).all()
+    pos = 0
+    for batch in ds.batches(4):
+        topk, ok = tr.evaluate(batch, batch["page_start"], decode="joint")
+        plain, _ = tr.evaluate(batch, batch["page_start"])
+        B = ok.shape[0]
+        assert topk.dtype == torch.int64 and topk.shape == (B, 4, 1) and ok.dtype == torch.bool
+        assert np.array_equal(topk[:, 1:, 0].cpu().numpy(), joint.joint_top1[pos:pos + B])
+        assert np.array_equal(ok.cpu().numpy(), joint.hits(1, "joint")[pos:pos + B])
+        assert torch.equal(topk[:, 0], plain[:, 0])                            # the background column is as before
+        pos += B
+    with pytest.raises(ValueError, match="k must be 1"):
+        tr.evaluate(batch, batch["page_start"], k=2, decode="joint")
+
+
+PARENT_KEYS = {"epoch", "loss", "accuracy", "boxes", "lr", "eval_acc", "class_acc", "is_best", "averaged", "updates",
+               "seconds"}
+
+
+def test_fit_follows_the_joint_hits_and_the_default_is_unchanged(tmp_path):
+    u8, rows = page_set()
+    ds = DeviceDataset(u8, rows, CS, DEV)
+    kw = dict(lr=2e-3, track_metrics=True)
+    a, b, c = (HotPathTrainer(CFG, seeded(), DEV, **kw) for _ in range(3))
+    log = str(tmp_path / "log.txt")
+    res = fit(a, ds, ds, 2, 3, sampling_fraction=1.0, seed=5, eval_interval=1, log_file=log, decode="joint")
+    assert [h["decode"] for h in res.history] == ["joint", "joint"] and res.epochs_run == 2
+    # the weights fit leaves: the best epoch's (reloaded), or the last epoch's when no evaluation scored above zero
+    at = res.best_epoch if res.best_epoch is not None else 2
+    rep = evaluate_split(a, ds, decode="joint")
+    assert np.array_equal(res.history[at - 1]["class_acc"], rep.class_acc(1, "joint"))
+    assert res.history[at - 1]["eval_acc"] == float(rep.class_acc(1, "joint")[1:].mean())
+    lines = open(log).read().splitlines()
+    vals = [l for l in lines if l.startswith("[VAL]")]
+    assert [l.split("%")[0] for l in vals] == ["[VAL] Avg_class_Accuracy: %.2f" % h["eval_acc"] for h in res.history]
+    with pytest.raises(ValueError, match="k must be 1"):
+        fit(a, ds, ds, 1, 3, k=3, decode="joint")
+    # the default: the history of a call that names no mode, key for key
+    plain = fit(b, ds, ds, 2, 3, sampling_fraction=1.0, seed=5, eval_interval=1)
+    named = fit(c, ds, ds, 2, 3, sampling_fraction=1.0, seed=5, eval_interval=1, decode="column", decode_score="logit")
+    for h, g in zip(plain.history, named.history):
+        assert set(h) == PARENT_KEYS | {"decode"} == set(g) and h["decode"] == "column"
+        for key in PARENT_KEYS - {"seconds", "class_acc"}:
+            assert h[key] == g[key], key
+        assert np.array_equal(h["class_acc"], g["class_acc"])
+    column = evaluate_split(b, ds)
+    at = plain.best_epoch if plain.best_epoch is not None else 2
+    assert np.array_equal(plain.history[at - 1]["class_acc"], column.class_acc(1))
+    for h, g in zip(plain.history, res.history):                               # the same training, another validation
+        assert (h["loss"], h["accuracy"], h["boxes"]) == (g["loss"], g["accuracy"], g["boxes"])
