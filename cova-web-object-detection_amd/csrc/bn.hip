@@ -407,24 +407,18 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
 // which is where torch's max_pool2d backward routes the gradient.
 // ------------------------------------------------------------------------------------
 // A thread owns (output column ox, channel quad c4) and walks DOWN a strip of POOL_STRIP output rows, keeping the input
-// row it shares with the next window (2 oy + 1) in registers: 6 float4 loads per output instead of 9, and a map row is
-// fetched from HBM once per strip instead of once per output row that touches it (round 2 measured 1.56x read
-// over-fetch with one thread per output: rows 2 oy - 1 / 2 oy + 1 were read by two blocks, usually on different XCDs).
-// Neighbouring columns are neighbouring 16-lane groups of the same wave (L1 hits).
-// STRIP / PRE: rows per strip; PRE: the two new input rows of output row
-// oy + 1 are requested before output row oy is reduced and stored (12 instead of 6 loads of a thread in flight).
-template <int POOL_STRIP, bool PRE, bool XCD = false, bool TILE2D = false>
+// row it shares with the next window (2 oy + 1) in registers.  Neighbouring columns are neighbouring 16-lane groups of the
+// same wave (L1 hits).  POOL_STRIP = 1, one output row per thread, was the fastest of the launch shapes measured in round 5
+// (longer strips, the next rows requested ahead, 4 x 4 output tiles: DESIGN.md 12.9); the walk is written for any strip.
+template <bool XCD>
 __global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_kernel(
     const float *__restrict__ y, const float *__restrict__ scale, const float *__restrict__ shift,
     float *__restrict__ out, uint8_t *__restrict__ idx, float *__restrict__ ymax, int B, int H1, int W1,
     int H2, int W2)
 {
-    // TILE2D (POOL_STRIP = 1): a block is 4 x 4 outputs x 16 channel quads (a wave = 4 adjacent columns of one output row)
-    // instead of 16 adjacent columns of one row: 81 instead of 99 input pixels per block, the rest are L1 hits
-    static_assert(!TILE2D || POOL_STRIP == 1, "TILE2D: one output row per thread");
+    constexpr int POOL_STRIP = 1;
     const int nstrips = (H2 + POOL_STRIP - 1) / POOL_STRIP;
-    const int tiles_x = (W2 + 3) / 4, tiles_y = (H2 + 3) / 4;
-    const long long total = TILE2D ? (long long)B * tiles_y * tiles_x * 256 : (long long)B * nstrips * W2 * 16;
+    const long long total = (long long)B * nstrips * W2 * 16;
     // XCD: consecutive blocks go to the eight XCDs in turn -- block b takes work block (b % 8) * (grid / 8) + b / 8, so that
     // an XCD walks ONE contiguous eighth of the maps and the input row two neighbouring strips share is met in its own L2
     long long wb = blockIdx.x;
@@ -435,22 +429,9 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_kernel(
     for (long long i = wb * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int c4 = (int)(i & 15);
         long long p = i >> 4;
-        int ox, strip, b;
-        if (TILE2D) {
-            const int px = (int)(p & 3), py = (int)((p >> 2) & 3);
-            p >>= 4;                                               // tile index
-            const int tx = (int)(p % tiles_x);
-            p /= tiles_x;
-            ox = 4 * tx + px;
-            strip = 4 * (int)(p % tiles_y) + py;                   // (= the output row)
-            b = (int)(p / tiles_y);
-            if (ox >= W2 || strip >= H2) continue;
-        } else {
-            ox = (int)(p % W2);
-            p /= W2;
-            strip = (int)(p % nstrips);
-            b = (int)(p / nstrips);
-        }
+        const int ox = (int)(p % W2);
+        p /= W2;
+        const int strip = (int)(p % nstrips), b = (int)(p / nstrips);
         const float4 sc = *reinterpret_cast<const float4 *>(scale + c4 * 4);
         const float4 sh = *reinterpret_cast<const float4 *>(shift + c4 * 4);
         const float scv[4] = {sc.x, sc.y, sc.z, sc.w}, shv[4] = {sh.x, sh.y, sh.z, sh.w};
@@ -465,18 +446,11 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_kernel(
             }
         };
         const int oy0 = strip * POOL_STRIP, oy1 = min(oy0 + POOL_STRIP, H2);
-        float4 top[3], mid[3], bot[3], nmid[3], nbot[3];
+        float4 top[3], mid[3], bot[3];
         load_row(2 * oy0 - 1, top);
-        if (PRE) { load_row(2 * oy0, nmid); load_row(2 * oy0 + 1, nbot); }
         for (int oy = oy0; oy < oy1; ++oy) {
-            if (PRE) {
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) { mid[kx] = nmid[kx]; bot[kx] = nbot[kx]; }
-                if (oy + 1 < oy1) { load_row(2 * oy + 2, nmid); load_row(2 * oy + 3, nbot); }      // (rows clamped in load_row)
-            } else {
-                load_row(2 * oy, mid);
-                load_row(2 * oy + 1, bot);
-            }
+            load_row(2 * oy, mid);
+            load_row(2 * oy + 1, bot);
             const bool oky[3] = {2 * oy - 1 >= 0, true, 2 * oy + 1 < H1};
             float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
             float my[4] = {0.f, 0.f, 0.f, 0.f};          // raw conv output at the arg-max position
@@ -506,102 +480,9 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_kernel(
     }
 }
 
-// Gradient w.r.t. the bn output before relu at input pixel (b, Y, X): gather from the <= 4
-// pooling windows that contain the pixel, then apply the relu mask.
-__device__ __forceinline__ void pool_relu_gather(const float *__restrict__ dp,
-                                                 const uint8_t *__restrict__ idx,
-                                                 const float t[4], int b, int Y, int X, int H2,
-                                                 int W2, int c4, float dy[4])
-{
-    dy[0] = dy[1] = dy[2] = dy[3] = 0.f;
-    const int oy_lo = Y >> 1, oy_hi = (Y + 1) >> 1;     // equal when Y is even
-    const int ox_lo = X >> 1, ox_hi = (X + 1) >> 1;
-    for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-        if (oy >= H2) continue;
-        const int ky = Y - (2 * oy - 1);
-        for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-            if (ox >= W2) continue;
-            const int kx = X - (2 * ox - 1);
-            const int pos = ky * 3 + kx;
-            const size_t o = (((size_t)b * H2 + oy) * W2 + ox) * 64 + c4 * 4;
-            const uchar4 id = *reinterpret_cast<const uchar4 *>(idx + o);
-            const float4 g = *reinterpret_cast<const float4 *>(dp + o);
-            if (id.x == pos) dy[0] += g.x;
-            if (id.y == pos) dy[1] += g.y;
-            if (id.z == pos) dy[2] += g.z;
-            if (id.w == pos) dy[3] += g.w;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (!(t[j] > 0.f)) dy[j] = 0.f;
-}
-
-// PASS 0: per-block partial sums of dy and dy*xhat ([block][2][64]);
-// PASS 1: dz = scale*(dy - c1 - xhat*c2) written NHWC.
-template <int PASS>
-__global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_kernel(
-    const float *__restrict__ dp, const uint8_t *__restrict__ idx, const float *__restrict__ y,
-    const float *__restrict__ scale, const float *__restrict__ shift,
-    const float *__restrict__ mean, const float *__restrict__ invstd,
-    const float *__restrict__ coef, float *__restrict__ dz, float *__restrict__ partial, int B,
-    int H1, int W1, int H2, int W2)
-{
-    __shared__ float s_s[16][64], s_q[16][64];
-    const int c4 = threadIdx.x & 15, prow = threadIdx.x >> 4;   // 16 pixels per block pass
-    const float4 sc = *reinterpret_cast<const float4 *>(scale + c4 * 4);
-    const float4 sh = *reinterpret_cast<const float4 *>(shift + c4 * 4);
-    const float4 mu = *reinterpret_cast<const float4 *>(mean + c4 * 4);
-    const float4 is = *reinterpret_cast<const float4 *>(invstd + c4 * 4);
-    float c1[4] = {0, 0, 0, 0}, c2[4] = {0, 0, 0, 0};
-    if (PASS == 1) {
-        *reinterpret_cast<float4 *>(c1) = *reinterpret_cast<const float4 *>(coef + c4 * 4);
-        *reinterpret_cast<float4 *>(c2) = *reinterpret_cast<const float4 *>(coef + 64 + c4 * 4);
-    }
-    const float scv[4] = {sc.x, sc.y, sc.z, sc.w}, shv[4] = {sh.x, sh.y, sh.z, sh.w};
-    const float muv[4] = {mu.x, mu.y, mu.z, mu.w}, isv[4] = {is.x, is.y, is.z, is.w};
-    float s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
-    const long long npix = (long long)B * H1 * W1;
-    for (long long p = (long long)blockIdx.x * 16 + prow; p < npix; p += (long long)gridDim.x * 16) {
-        const int X = (int)(p % W1);
-        const long long pr = p / W1;
-        const int Y = (int)(pr % H1);
-        const int b = (int)(pr / H1);
-        const float4 v = *reinterpret_cast<const float4 *>(y + (size_t)p * 64 + c4 * 4);
-        const float vv[4] = {v.x, v.y, v.z, v.w};
-        float t[4], dy[4], xh[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            t[j] = vv[j] * scv[j] + shv[j];
-            xh[j] = (vv[j] - muv[j]) * isv[j];
-        }
-        pool_relu_gather(dp, idx, t, b, Y, X, H2, W2, c4, dy);
-        if (PASS == 0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { s[j] += dy[j]; q[j] += dy[j] * xh[j]; }
-        } else {
-            float o[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = scv[j] * (dy[j] - c1[j] - xh[j] * c2[j]);
-            *reinterpret_cast<float4 *>(dz + (size_t)p * 64 + c4 * 4) =
-                make_float4(o[0], o[1], o[2], o[3]);
-        }
-    }
-    if (PASS == 0) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { s_s[prow][c4 * 4 + j] = s[j]; s_q[prow][c4 * 4 + j] = q[j]; }
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            float a = 0.f, bq = 0.f;
-            for (int r = 0; r < 16; ++r) { a += s_s[r][threadIdx.x]; bq += s_q[r][threadIdx.x]; }
-            partial[((size_t)blockIdx.x * 2 + 0) * 64 + threadIdx.x] = a;
-            partial[((size_t)blockIdx.x * 2 + 1) * 64 + threadIdx.x] = bq;
-        }
-    }
-}
-
-// Window-based form of the PASS 0 reduction: every pooling window routes its gradient to exactly
-// one input pixel (its argmax), so sum_pixels dy = sum_windows dp*[bn(y_argmax) > 0] and likewise
+// BatchNorm-backward sums of the conv1 tail, per-block partials of dy and dy*xhat ([block][2][64]), by window: every
+// pooling window routes its gradient to exactly one input pixel (its argmax), so
+// sum_pixels dy = sum_windows dp*[bn(y_argmax) > 0] and likewise
 // for dy*xhat: one gather of y per (window, channel) instead of a sweep over the 4x larger input.
 __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_reduce_win_kernel(
     const float *__restrict__ dp, const uint8_t *__restrict__ idx, const float *__restrict__ y,
@@ -650,7 +531,7 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_reduce_win_kernel(
     }
 }
 
-// Quad form of the PASS 1 kernel: one thread per (pooling window, 4 channels) produces the 2x2 input
+// The apply pass, dz = scale*(dy - c1 - xhat*c2) written NHWC: one thread per (pooling window, 4 channels) produces the 2x2 input
 // pixels (2oy..2oy+1, 2ox..2ox+1).  Those four pixels only receive gradient from the windows
 // (oy..oy+1, ox..ox+1), so 4 dp + 4 idx + 4 y loads (all independent) serve 4 outputs, instead of
 // up to 9 dependent loads per output pixel.
@@ -729,19 +610,6 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_apply_quad_kernel(
             }
         }
     }
-}
-
-inline int ew_grid(long long total_threads)
-{
-    long long g = cdivll(total_threads, 256);
-    if (g > 256 * 16) g = 256 * 16;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
-inline bool vec4_ok(const void *p, int ld)
-{
-    return p == nullptr || (((uintptr_t)p & 15) == 0 && (ld & 3) == 0);
 }
 
 }  // namespace
@@ -945,15 +813,11 @@ COVA_API int cova_bn_relu_maxpool_fwd(const float *y, const float *scale, const 
 {
     COVA_REQUIRE(y && scale && shift && out && idx && B > 0 && H1 > 0 && W1 > 0);
     const int H2 = (H1 + 2 - 3) / 2 + 1, W2 = (W1 + 2 - 3) / 2 + 1;
-    auto launch = [&](auto kern, int strip, bool capped) {
-        const long long threads = (long long)B * cdiv(H2, strip) * W2 * 16;
-        long long g = capped ? ew_grid(threads) : cdivll(threads, 256);
-        if (g > 0x7fffffffll) g = 0x7fffffffll;                      // (the kernel strides over what is left)
-        hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, y, scale, shift, out, idx, ymax, B,
-                           H1, W1, H2, W2);
-    };
     // one output row per thread on XCD-contiguous work blocks: the fastest of 17 launch shapes measured in round 5
-    launch(bn_relu_maxpool_fwd_kernel<1, false, true>, 1, false);
+    long long g = cdivll((long long)B * H2 * W2 * 16, 256);
+    if (g > 0x7fffffffll) g = 0x7fffffffll;                          // (the kernel strides over what is left)
+    hipLaunchKernelGGL(bn_relu_maxpool_fwd_kernel<true>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, y, scale, shift,
+                       out, idx, ymax, B, H1, W1, H2, W2);
     COVA_LAUNCH_CHECK();
     return COVA_OK;
 }

@@ -347,8 +347,6 @@ __global__ __launch_bounds__(V4_THREADS) void bn1d_bwd_v4_kernel(
     }
 }
 
-inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 COVA_API int cova_bn1d_fwd(const float *x, int ldx, int R, int C, const float *gamma, const float *beta,
@@ -360,8 +358,8 @@ COVA_API int cova_bn1d_fwd(const float *x, int ldx, int R, int C, const float *g
     COVA_REQUIRE(x && gamma && beta && out && scale && shift && mean && invstd && R > 0 && C > 0);
     COVA_REQUIRE((running_mean == nullptr) == (running_var == nullptr));
     COVA_REQUIRE(dropped == nullptr || (mask != nullptr && p >= 0.f && p < 1.f));
-    const bool v4 = cova_options().bn1d_variant != 0 && C % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && al16(x) && al16(out) &&
-                    (dropped == nullptr || (ld_dropped % 4 == 0 && al16(dropped) && ((uintptr_t)mask & 3) == 0)) &&
+    const bool v4 = cova_options().bn1d_variant != 0 && C % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && aligned16(x) && aligned16(out) &&
+                    (dropped == nullptr || (ld_dropped % 4 == 0 && aligned16(dropped) && ((uintptr_t)mask & 3) == 0)) &&
                     R <= 8 * V4_SLICES;
     if (v4) {
         const dim3 g4(cdiv(C, V4_COLS));
@@ -395,8 +393,8 @@ COVA_API int cova_bn1d_bwd(const float *dout, int ldg, const uint8_t *drop_mask,
 {
     COVA_REQUIRE(dout && z && mean && invstd && scale && dz && R > 0 && C > 0);
     COVA_REQUIRE(drop_mask == nullptr || (p >= 0.f && p < 1.f));
-    const bool v4 = cova_options().bn1d_variant != 0 && C % 4 == 0 && ldg % 4 == 0 && ldz % 4 == 0 && lddz % 4 == 0 && al16(dout) &&
-                    al16(z) && al16(dz) && (act == nullptr || (lda % 4 == 0 && al16(act))) &&
+    const bool v4 = cova_options().bn1d_variant != 0 && C % 4 == 0 && ldg % 4 == 0 && ldz % 4 == 0 && lddz % 4 == 0 && aligned16(dout) &&
+                    aligned16(z) && aligned16(dz) && (act == nullptr || (lda % 4 == 0 && aligned16(act))) &&
                     (drop_mask == nullptr || ((uintptr_t)drop_mask & 3) == 0) && R <= 6 * V4_SLICES;   // (8 rows: 128 registers, spills)
     if (v4) {
         const dim3 g4(cdiv(C, V4_COLS));

@@ -57,10 +57,46 @@ __device__ __forceinline__ float row16_sum(float v)
     return v;
 }
 
+// fmaxf form: a NaN operand is dropped, whichever side it is on
 __device__ __forceinline__ float wave_max(float v)
 {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// compare form (f32 compares): an incoming NaN never wins and a lane's own value is kept unless a greater one arrives.
+// Not wave_max: the two differ on NaN and on the sign of zero; rank.hip's maxima are defined by this one.
+__device__ __forceinline__ float wave_max_gt(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float u = __shfl_xor(v, o, 64);
+        if (u > v) v = u;
+    }
+    return v;
+}
+
+// the xor butterfly in float64 and in integers: every lane ends with the same bits (loss.hip, rank.hip, optim.hip; the
+// counts of eval.hip, mine.hip, sample.hip)
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ int wave_sum_i(int v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ int wave_min_i(int v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
     return v;
 }
 
@@ -125,3 +161,18 @@ __device__ __forceinline__ float gat_edge_term(const float *__restrict__ phi, si
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline long long cdivll(long long a, long long b) { return (a + b - 1) / b; }
+
+// ---- host-side launch helpers
+static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// 16-byte accesses of a row-major operand: aligned base, leading dimension a multiple of 4 floats (an absent operand passes)
+static inline bool vec4_ok(const void *p, int ld) { return p == nullptr || (aligned16(p) && (ld & 3) == 0); }
+
+// blocks of 256 threads for a grid-stride kernel over n items, at most `cap` blocks and at least one
+static inline int capped_grid(long long n, long long cap)
+{
+    const long long g = cdivll(n, 256);
+    return (int)(g > cap ? cap : g < 1 ? 1 : g);
+}
+static inline int ew_grid(long long n) { return capped_grid(n, 256 * 16); }      // the elementwise kernels of bn.hip and head.hip
+static inline int grid_for(long long n) { return capped_grid(n, 256 * 32); }     // the thread-per-item kernels of input.hip and sample.hip

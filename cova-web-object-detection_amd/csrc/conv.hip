@@ -12,7 +12,7 @@
 // Roofline bookkeeping: 2*64*64*9 = 73,728 FLOP per output pixel
 // for conv3x3 (fwd, dgrad and wgrad each), 2*64*147 = 18,816 FLOP per output pixel for conv1.
 #include "common.h"
-#include "bf3.h"
+#include "mma.h"
 #include "bn_tail.h"
 #include "options.h"
 #include <utility>
@@ -353,14 +353,6 @@ constexpr int RF0 = 7;                         // K-step at which the prefetched
 __host__ __device__ constexpr int row_off(int t) { return t < 21 ? ((t / 7) * PR + t % 7) * SEGW : 0; }
 }  // namespace c1b
 
-__device__ __forceinline__ f32x16 mfma32bf(u32x4 a, u32x4 b, f32x16 c)
-{
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// barrier over LDS traffic only (global stores and loads stay in flight across it)
-__device__ __forceinline__ void c1b_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // compile-time loop: f(std::integral_constant<int, 0>) ... f(std::integral_constant<int, N-1>)
 template <class F, int... I>
 __device__ __forceinline__ void c1b_static_for_impl(F &&f, std::integer_sequence<int, I...>)
@@ -618,7 +610,7 @@ __global__ __launch_bounds__(c1b::THREADS) void conv1_7x7_bf3_kernel(
         pend = false;
         C1B_STAMP(1);
         C1B_STAMP(2);
-        c1b_lds_barrier();               // the next patch is complete; every wave is done reading this one
+        lds_barrier();               // the next patch is complete; every wave is done reading this one
         C1B_STAMP(3);
         cur ^= 1;
         // output rows y0 + 2q, + 1: D register r of lane l = pixel mfma32_row(r, l), channel cb*32 + (l & 31)
@@ -1217,7 +1209,7 @@ __global__ __launch_bounds__(wg1r::THREADS) void conv1_wgrad_rs_kernel(
                 });
             });
             WG1R_STAMP(1);
-            c1b_lds_barrier();
+            lds_barrier();
             WG1R_STAMP(2);
             cur ^= 1;
 #ifdef C1B_TRACE
@@ -1363,7 +1355,7 @@ __global__ __launch_bounds__(wg1r::THREADS) void conv1_wgrad_rs_kernel(
             WG1R_STAMP(3);                                                                       \
             load_tile(B_, coords(tile + (K_) * tstep));                                          \
             WG1R_STAMP(1);                                                                       \
-            c1b_lds_barrier();                                                                   \
+            lds_barrier();                                                                   \
             WG1R_STAMP(2);                                                                       \
             nb ^= 1;                                                                             \
             WG1R_TRIT();

@@ -28,15 +28,10 @@
 // Roofline bookkeeping: 2*Cin*Cout FLOP and 4*(Cin+Cout) compulsory bytes per pixel --
 // 64->256 / 256->64: 32,768 FLOP vs 1,280 B (25.6 FLOP/B: at the f32-MFMA / HBM ridge),
 // 64->64: 8,192 FLOP vs 512 B (HBM bound).
-#include "bf3.h"
+#include "mma.h"
 #include "options.h"
 
 namespace {
-
-__device__ __forceinline__ f32x16 c11_mfma_bf(u32x4 a, u32x4 b, f32x16 c)
-{
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 struct C11Args {
     const float *in, *in2, *pro;          // pro [3][Cin] = A | B | C (nullable)
@@ -441,7 +436,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv1x1_kernel(const
                                 b[pc] = Wp[(pc * COUT + (ps * NTP + n) * 32 + p) * (G::WROW / 4) + wcol / 8 + s4];
                             // the six products of order <= 2, smallest first: x2 w0, x0 w2, x1 w1, x1 w0, x0 w1, x0 w0
                             auto mf = [&](int xi, int wi) __attribute__((always_inline)) {
-                                acc[n] = TR ? c11_mfma_bf(b[wi], xp[xi][s4], acc[n]) : c11_mfma_bf(xp[xi][s4], b[wi], acc[n]);
+                                acc[n] = TR ? mfma32bf(b[wi], xp[xi][s4], acc[n]) : mfma32bf(xp[xi][s4], b[wi], acc[n]);
                             };
                             mf(2, 0); mf(0, 2); mf(1, 1); mf(1, 0); mf(0, 1); mf(0, 0);
                         }

@@ -15,7 +15,7 @@
 // maps per Bottleneck, at +25 % MFMA work (the Gram matrix / the 64 extra K channels).  Same exact-f32
 // MFMA arithmetic; the result differs from the direct form by summation order only (measured against
 // fp64: 4e-7 relative, the direct form 1.4e-6).
-#include "bf3.h"
+#include "mma.h"
 #include "options.h"
 
 namespace {
@@ -40,11 +40,6 @@ struct VPArgs {
 // 64u .. 64u+63; the Gram matrix of a (the same operand on both sides) is taken by wave (K-step & 3), as are the sums of a.
 // The bf16 MFMA drops low product bits toward -infinity (tools/probe/mfma_round_probe.hip): odd blocks multiply with the
 // NEGATED a on the B side and negate their partial sums back, so that the bias has no common sign over the blocks.
-__device__ __forceinline__ f32x16 vp_mfma(u32x4 a, u32x4 b, f32x16 c)
-{
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
 // (one instantiation: without act_abc the prologue runs with A = 1, C = 0 -- exact; the variant without it made the register
 // allocator spill the Gram accumulators)
 __global__ __launch_bounds__(256, 2) void conv1x1_vprod_kernel(const VPArgs a)
@@ -131,12 +126,12 @@ __global__ __launch_bounds__(256, 2) void conv1x1_vprod_kernel(const VPArgs a)
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 f32x16 c = acc[i][j];
-                c = vp_mfma(ap[i][2], bp[j][0], c);
-                c = vp_mfma(ap[i][0], bp[j][2], c);
-                c = vp_mfma(ap[i][1], bp[j][1], c);
-                c = vp_mfma(ap[i][1], bp[j][0], c);
-                c = vp_mfma(ap[i][0], bp[j][1], c);
-                c = vp_mfma(ap[i][0], bp[j][0], c);
+                c = mfma32bf(ap[i][2], bp[j][0], c);
+                c = mfma32bf(ap[i][0], bp[j][2], c);
+                c = mfma32bf(ap[i][1], bp[j][1], c);
+                c = mfma32bf(ap[i][1], bp[j][0], c);
+                c = mfma32bf(ap[i][0], bp[j][1], c);
+                c = mfma32bf(ap[i][0], bp[j][0], c);
                 acc[i][j] = c;
             }
         {                                                      // Gram quadrant; A side: the pieces of +a (= the B pieces with the block's sign undone)
@@ -147,12 +142,12 @@ __global__ __launch_bounds__(256, 2) void conv1x1_vprod_kernel(const VPArgs a)
                 for (int e = 0; e < 4; ++e) ag[pc][e] = (gi ? bp[1][pc][e] : bp[0][pc][e]) ^ flip;
             const u32x4 b0 = gj ? bp[1][0] : bp[0][0], b1 = gj ? bp[1][1] : bp[0][1], b2 = gj ? bp[1][2] : bp[0][2];
             f32x16 c = accg;
-            c = vp_mfma(ag[2], b0, c);
-            c = vp_mfma(ag[0], b2, c);
-            c = vp_mfma(ag[1], b1, c);
-            c = vp_mfma(ag[1], b0, c);
-            c = vp_mfma(ag[0], b1, c);
-            c = vp_mfma(ag[0], b0, c);
+            c = mfma32bf(ag[2], b0, c);
+            c = mfma32bf(ag[0], b2, c);
+            c = mfma32bf(ag[1], b1, c);
+            c = mfma32bf(ag[1], b0, c);
+            c = mfma32bf(ag[0], b1, c);
+            c = mfma32bf(ag[0], b0, c);
             accg = c;
         }
     };

@@ -35,7 +35,7 @@
 // gradient launch of the same convolution.
 // Operand prologues as the F(2x2) kernel's: activation = relu?(A*act + C) on load, gradient = A*dz + B*dz2 + C on load
 // (the BatchNorm+ReLU of the producer / the BatchNorm-backward apply, never materialised); zero padding stays zero.
-#include "common.h"
+#include "mma.h"
 #include "options.h"
 #include <type_traits>
 
@@ -84,23 +84,6 @@ struct Wg4Args {
     int act_relu;
     int H, W, tiles_y, strips, nseg_y, seg_rows, nsegs;
 };
-
-typedef __attribute__((address_space(3))) void wg4_lds_void;
-
-__device__ __forceinline__ f32x4 wg4_mfma(float a, float b, f32x4 c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// barrier over LDS traffic only: global -> LDS copies (the next K-step's pixels) stay in flight across it
-__device__ __forceinline__ void wg4_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// global -> LDS copy of 16 bytes per lane (lane i lands at lds_base + 16 i; lds_base wave-uniform), as inline asm: the
-// compiler neither tracks nor waits for it -- the one wait is the explicit vmcnt(0) in front of the transform's reads
-__device__ __forceinline__ void wg4_copy16(const char *base, unsigned off_bytes, unsigned lds_base_bytes)
-{
-    asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_base_bytes), "v"(off_bytes), "s"(base) : "memory", "m0");
-}
 
 // B^T x for one 6-vector (second stage of the input transform; 12 operations)
 __device__ __forceinline__ void wg4_bt6(const float (&d)[6], float (&o)[6])
@@ -239,17 +222,17 @@ __global__ __launch_bounds__(wg4::THREADS, 1) void conv3x3_wgrad4_kernel(const W
             pair(pb + 16 * ROW + q0, b1);
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
-                acc[q0 + q][0] = wg4_mfma(a0[q], b0[q], acc[q0 + q][0]);
-                acc[q0 + q][1] = wg4_mfma(a0[q], b1[q], acc[q0 + q][1]);
-                acc[q0 + q][2] = wg4_mfma(a1[q], b0[q], acc[q0 + q][2]);
-                acc[q0 + q][3] = wg4_mfma(a1[q], b1[q], acc[q0 + q][3]);
+                acc[q0 + q][0] = mfma16x4(a0[q], b0[q], acc[q0 + q][0]);
+                acc[q0 + q][1] = mfma16x4(a0[q], b1[q], acc[q0 + q][1]);
+                acc[q0 + q][2] = mfma16x4(a1[q], b0[q], acc[q0 + q][2]);
+                acc[q0 + q][3] = mfma16x4(a1[q], b1[q], acc[q0 + q][3]);
             }
         }
         const float a0 = pa[8], a1 = pa[16 * ROW + 8], b0 = pb[8], b1 = pb[16 * ROW + 8];
-        acc[8][0] = wg4_mfma(a0, b0, acc[8][0]);
-        acc[8][1] = wg4_mfma(a0, b1, acc[8][1]);
-        acc[8][2] = wg4_mfma(a1, b0, acc[8][2]);
-        acc[8][3] = wg4_mfma(a1, b1, acc[8][3]);
+        acc[8][0] = mfma16x4(a0, b0, acc[8][0]);
+        acc[8][1] = mfma16x4(a0, b1, acc[8][1]);
+        acc[8][2] = mfma16x4(a1, b0, acc[8][2]);
+        acc[8][3] = mfma16x4(a1, b1, acc[8][3]);
     };
 
     // The whole pipeline of one (role, position half): specialised bodies, chosen once per wave (the role and the half are
@@ -277,7 +260,7 @@ __global__ __launch_bounds__(wg4::THREADS, 1) void conv3x3_wgrad4_kernel(const W
         const int sub = lane >> 4, c4 = lane & 15;
         const unsigned laneoff = (unsigned)((((sub >> 1) * W + (sub & 1)) * 64 + c4 * 4) * 4);
         float *raw = s_raw + wave * RAW_FLOATS;
-        const unsigned raw_lds = (unsigned)(size_t)(wg4_lds_void *)raw;
+        const unsigned raw_lds = (unsigned)(size_t)(lds_void *)raw;
         const float *raw_r = raw + lane;                     // slot s, this lane's channel: raw_r[64 s]
         // pixel validity of a patch: bit r of the row mask / bit c of the column mask (wave-uniform; a few scalar operations:
         // the valid rows / columns of a patch are a contiguous range)
@@ -310,14 +293,14 @@ __global__ __launch_bounds__(wg4::THREADS, 1) void conv3x3_wgrad4_kernel(const W
             const unsigned dst = raw_lds + (VROLE ? 3072u * (unsigned)ps : 2048u * (unsigned)br) + 1024u * (unsigned)bc;
             if (!edge) {                                         // scalar base of the row pair + the block column
                 const unsigned off = (unsigned)(((gy0 + 2 * br) * W + gx0) * 256 + 512 * bc);     // (a page < 4 GB: host check)
-                wg4_copy16(src + off, laneoff, dst);
-                if (TWO) wg4_copy16(src2 + off, laneoff, dst + 4096);
+                copy16_to_lds(src + off, laneoff, dst);
+                if (TWO) copy16_to_lds(src2 + off, laneoff, dst + 4096);
             } else {
                 const int r = 2 * br + (sub >> 1), c = 2 * bc + (sub & 1);
                 const int gy = min(max(gy0 + r, 0), H - 1), gx = min(max(gx0 + c, 0), W - 1);
                 const unsigned eo = (unsigned)((gy * W + gx) * 256 + c4 * 16);
-                wg4_copy16(src, eo, dst);
-                if (TWO) wg4_copy16(src2, eo, dst + 4096);
+                copy16_to_lds(src, eo, dst);
+                if (TWO) copy16_to_lds(src2, eo, dst + 4096);
             }
         };
         // a continued walk of the input role keeps row pair 0 (wave-uniform)
@@ -447,7 +430,7 @@ __global__ __launch_bounds__(wg4::THREADS, 1) void conv3x3_wgrad4_kernel(const W
         crm = nrm; ccm = ncm;
         cur_org = origin(nxt);
         advance(nxt);
-        wg4_lds_barrier();
+        lds_barrier();
         // The two waves of a SIMD (wave w: input role, wave w + 4: gradient role) run the iteration in OPPOSITE order --
         // transform then MFMAs / MFMAs then transform: one wave's pixel wait and transform arithmetic sit beside the
         // other's matrix phase instead of all eight waves idling the matrix pipe together.  (Within an iteration every wave
@@ -469,7 +452,7 @@ __global__ __launch_bounds__(wg4::THREADS, 1) void conv3x3_wgrad4_kernel(const W
                 cur_org = origin(nxt);
                 advance(nxt);
             }
-            wg4_lds_barrier();
+            lds_barrier();
             WG4_STAMP(6);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the last request, never consumed, has landed before the LDS is released)

@@ -27,7 +27,7 @@
 // LDS traffic per 8-channel chunk and 16 tiles: 74 KB of V operand reads + 73 KB of stage traffic + 11 KB of copies
 // (round 2: 147 + 73 + 47 KB per 4 channels x 32 tiles).
 #include "common.h"
-#include "bf3.h"
+#include "mma.h"
 #include "bn_tail.h"
 #include "options.h"
 #include <type_traits>
@@ -71,11 +71,6 @@ constexpr int U_FLOATS = 8 * 8 * 9 * 64 * 4;   // [chunk 8][wave 8][quad 9][lane
 constexpr int U_SPLIT_DWORDS = 2 * 8 * 18 * 3 * 256;     // the bf16-piece image of the split main loop (conv_wino4_split.h): 221,184
 constexpr int U_TOTAL = U_FLOATS + 2 * U_SPLIT_DWORDS;    // one convolution, one direction: [f32 image | piece image | piece image of -U] = 589,824 floats
 }  // namespace w4
-
-__device__ __forceinline__ f32x4 mfma16x4(float a, float b, f32x4 c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // B^T x for one 6-vector (12 operations)
 __device__ __forceinline__ void bt6(const float (&d)[6], float (&o)[6])
@@ -123,8 +118,6 @@ struct W4Args {
 // 256 zero bytes in global memory: halo pixels outside the image are fetched from here
 __device__ __attribute__((aligned(256))) float g_w4_zero_page[64];
 
-typedef __attribute__((address_space(3))) void lds_void;
-
 // Sum over the 16 lanes of a wave that share (lane & 3); every lane ends up with its class's total.  Two v_add_f32 with
 // DPP operands inside the 16-lane rows (row_ror:4, row_ror:8), two cross-row exchanges.
 __device__ __forceinline__ float quad_class_sum(float v)
@@ -135,22 +128,6 @@ __device__ __forceinline__ float quad_class_sum(float v)
     v += __shfl_xor(v, 32, 64);
     return v;
 }
-
-// global -> LDS copy of 16 bytes per lane (lane i lands at lds_base + 16 i; lds_base wave-uniform) as inline asm:
-// the compiler then neither knows the copy (no conservative vmcnt(0) in front of every later LDS read, which the
-// builtin gets unless each buffer is its own __shared__ object) nor waits for it -- every wait on these copies is
-// an explicit s_waitcnt in the kernel.
-// Address = wave-uniform base (scalar register pair) + this lane's unsigned 32-bit byte offset: no 64-bit per-lane
-// pointers (which the compiler otherwise precomputes per pixel and keeps -- or spills -- across the whole loop).
-__device__ __forceinline__ void copy16_to_lds(const float *base, unsigned off_bytes, unsigned lds_base_bytes)
-{
-    asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_base_bytes), "v"(off_bytes), "s"(base) : "memory", "m0");
-}
-
-// Barrier that orders LDS accesses only: this wave's ds_writes are complete (lgkmcnt(0)) while global -> LDS copies
-// and weight loads stay in flight.  __syncthreads() is a release fence over LDS, and a pending copy IS an LDS store:
-// it waits vmcnt(0).
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Software pipeline, one iteration = one 8-channel chunk g of the block's chunk stream (8 chunks per tile, the stream
 // runs across tiles):

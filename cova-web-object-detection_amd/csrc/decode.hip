@@ -89,11 +89,11 @@ __global__ __launch_bounds__(decode_threads<C>()) void page_joint_decode_kernel(
             int bi = NONE;
             for (int i = lane; i < n; i += 64) {
                 const float v = score_of(rows + (size_t)i * NC, c, score_mode);
-                const bool after = j == 0 || v < pv || (v == pv && i > pi);
+                const bool after = j == 0 || v < pv || (v == pv && i > pi);   // ranks_before(pv, pi, v, i) of rows.h
                 if (after && (bi == NONE || v > bv)) { bv = v; bi = i; }   // ascending i per lane: a tie keeps the lower index
             }
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
+            for (int o = 32; o > 0; o >>= 1) {              // wave_ranked_first (rows.h), written out: these statements must match it
                 const float ov = __shfl_xor(bv, o, 64);
                 const int oi = __shfl_xor(bi, o, 64);
                 if (oi != NONE && (bi == NONE || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }

@@ -1,27 +1,11 @@
 // Evaluation of a whole split on the device (train.py:131-154 over every batch of a loader): the rank of the labelled box.
 //   cova_eval_page_ranks: per page of the batch and class c >= 1, the position of the FIRST box labelled c in the order
-//   cova_page_class_topk uses (score descending, ties to the lower page-local index), scattered into a split-resident
-//   table by page id.  "Among the top k" is then 0 <= rank < k for every k, and the per-batch host fold of
-//   HotPathTrainer.evaluate's booleans becomes one device-to-host copy per split.
-#include "common.h"
+//   cova_page_class_topk uses (ranks_before in rows.h: score descending, ties to the lower page-local index), scattered
+//   into a split-resident table by page id.  "Among the top k" is then 0 <= rank < k for every k, and the per-batch host
+//   fold of HotPathTrainer.evaluate's booleans becomes one device-to-host copy per split.
+#include "rows.h"
 
 namespace {
-
-constexpr int MAXNC = 16;
-
-__device__ __forceinline__ int wave_min_i(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum_i(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // One wave per (page of the batch, class 1..NC-1); a wave owns its table entries, so there is no atomic and no workspace.
 // Pass 1 finds the first labelled box (lowest index) and the best box of the column; pass 2 counts the boxes that come
@@ -38,36 +22,31 @@ __global__ __launch_bounds__(256) void eval_page_ranks_kernel(const float *__res
     const int row = page_ids ? page_ids[page] : page;
     if (row < 0 || row >= P) return;                       // the host validates ids; an id outside the table is skipped
     const int64_t lo = page_start[page], hi = page_start[page + 1];
-    int t = 0x7fffffff, bi = 0x7fffffff;
+    int t = RANK_NONE, bi = RANK_NONE;
     float bv = -INFINITY;
     for (int64_t n = lo + lane; n < hi; n += 64) {
         const int i = (int)(n - lo);
         if (labels[n] == (int64_t)c) t = min(t, i);
         const float v = logits[(size_t)n * NC + c];
-        if (bi == 0x7fffffff || v > bv) { bv = v; bi = i; }   // ascending i per lane: a tie keeps the lower index
+        if (bi == RANK_NONE || v > bv) { bv = v; bi = i; }   // ascending i per lane: a tie keeps the lower index
     }
     t = wave_min_i(t);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
-    }
+    wave_ranked_first(bv, bi);
     int r = -1;
-    if (t != 0x7fffffff) {
+    if (t != RANK_NONE) {
         const float vt = logits[(size_t)(lo + t) * NC + c];
         int before = 0;
         for (int64_t n = lo + lane; n < hi; n += 64) {
             const float v = logits[(size_t)n * NC + c];
             const int i = (int)(n - lo);
-            before += (v > vt || (v == vt && i < t)) ? 1 : 0;
+            before += ranks_before(v, i, vt, t) ? 1 : 0;
         }
         r = wave_sum_i(before);
     }
     if (lane == 0) {
         const size_t at = (size_t)row * (NC - 1) + (c - 1);
         rank[at] = r;
-        if (top1) top1[at] = (bi == 0x7fffffff) ? -1 : bi;
+        if (top1) top1[at] = (bi == RANK_NONE) ? -1 : bi;
     }
 }
 
@@ -76,7 +55,7 @@ __global__ __launch_bounds__(256) void eval_page_ranks_kernel(const float *__res
 COVA_API int cova_eval_page_ranks(const float *logits, const int64_t *labels, const int64_t *page_start,
                                   const int *page_ids, int B, int NC, int P, int *rank, int *top1, void *stream)
 {
-    COVA_REQUIRE(logits && labels && page_start && rank && B > 0 && NC >= 2 && NC <= MAXNC && P > 0);
+    COVA_REQUIRE(logits && labels && page_start && rank && B > 0 && NC >= 2 && NC <= COVA_MAX_CLASSES && P > 0);
     hipLaunchKernelGGL(eval_page_ranks_kernel, dim3(cdiv(B * (NC - 1), 4)), dim3(256), 0, (hipStream_t)stream, logits,
                        labels, page_start, page_ids, B, NC, P, rank, top1);
     COVA_LAUNCH_CHECK();

@@ -449,8 +449,6 @@ __global__ __launch_bounds__(1024) void gat2_fold_kernel(const float *__restrict
     }
 }
 
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 // chunks per row the kernels are instantiated for: 1, 2, 4, 8 (and 16 in the scalar form); 0 = D too large
 inline int gat2_chunks(int D, int V)
 {

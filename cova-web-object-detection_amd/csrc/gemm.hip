@@ -16,7 +16,7 @@
 // product on the bf16 matrix pipe with three-piece operands (slower: these launches are bound by the k-tile round trip -- fetch,
 // barrier, stash, barrier -- and splitting a tile on its way into LDS lengthens exactly that), a register-direct form without LDS
 // tiles, operand tiles two k-tiles ahead, two LDS buffers per k-group.
-#include "common.h"
+#include "mma.h"
 #include "options.h"
 #include <type_traits>
 
@@ -184,13 +184,6 @@ __global__ __launch_bounds__(256 * KS) void sgemm_kernel(const float *__restrict
 //     accumulator issues every ~128 cycles, two chains keep the pipe busy from one wave;
 //   * rows past M / N are clamped (their outputs are never stored); a k past K is clamped and both of its operands are zeroed
 //     in registers (last k-tile only).
-typedef __attribute__((address_space(3))) void gd_lds_void;
-
-__device__ __forceinline__ void gd_copy16(const char *base, unsigned off_bytes, unsigned lds_base_bytes)
-{
-    asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_base_bytes), "v"(off_bytes), "s"(base) : "memory", "m0");
-}
-
 template <int N_>
 __device__ __forceinline__ void gd_wait_vm()
 {
@@ -222,7 +215,7 @@ __global__ __launch_bounds__(128 * WM * KS) void sgemm_dma_kernel(const float *_
     const int wm = wave >> 1, wn = wave & 1;
     const int m0 = blockIdx.y * RA, n0 = blockIdx.x * RB;
     const int li = lane & 31, kh = lane >> 5;
-    const unsigned lds0 = (unsigned)(size_t)(gd_lds_void *)&s_t[grp][0][0];
+    const unsigned lds0 = (unsigned)(size_t)(lds_void *)&s_t[grp][0][0];
 
     // ---- copy pieces.  k-contiguous tile: piece c = (rb = c >> 1, kb = c & 1), lane = s * 16 + r -> row 16 rb + r, k = 16 kb + 4 s.
     // Row-contiguous tile of R rows: R / 4 lanes per k-row, 256 / R k-rows per piece: k = c * (256 / R) + lane / (R / 4), rows 4 (lane % (R / 4)) ...
@@ -242,7 +235,7 @@ __global__ __launch_bounds__(128 * WM * KS) void sgemm_dma_kernel(const float *_
             unsigned o;
             if (AK) o = (unsigned)(a_row[i] * lda + min(k0 + 16 * (c & 1) + 4 * (lane >> 4), K - 4)) * 4u;
             else o = (unsigned)(min(k0 + c * (256 / RA) + lane / (RA / 4), K - 1) * lda + a_row[i]) * 4u;
-            gd_copy16(reinterpret_cast<const char *>(A), o, dst + (unsigned)c * 1024u);
+            copy16_to_lds(A, o, dst + (unsigned)c * 1024u);
         }
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
@@ -250,7 +243,7 @@ __global__ __launch_bounds__(128 * WM * KS) void sgemm_dma_kernel(const float *_
             unsigned o;
             if (BKC) o = (unsigned)(b_row[i] * ldb + min(k0 + 16 * (c & 1) + 4 * (lane >> 4), K - 4)) * 4u;
             else o = (unsigned)(min(k0 + c * (256 / RB) + lane / (RB / 4), K - 1) * ldb + b_row[i]) * 4u;
-            gd_copy16(reinterpret_cast<const char *>(Bm), o, dst + (unsigned)(A_FLOATS * 4) + (unsigned)c * 1024u);
+            copy16_to_lds(Bm, o, dst + (unsigned)(A_FLOATS * 4) + (unsigned)c * 1024u);
         }
     };
 
@@ -270,7 +263,7 @@ __global__ __launch_bounds__(128 * WM * KS) void sgemm_dma_kernel(const float *_
     for (int it = 0; it < nit; ++it) {
         const int t = grp + KS * it;
         gd_wait_vm<(NA + NB) * (DS - 2)>();             // this wave's copies of k-tile t have landed (the DS - 2 younger groups may be in flight) ...
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // ... and everybody's; the slot of the k-tile before has been read by all
+        lds_barrier();                                                        // ... and everybody's; the slot of the k-tile before has been read by all
                                                        // (LDS-only barrier: __syncthreads() would wait for the copies in flight)
         issue(grp + KS * (it + DS - 1), (it + DS - 1) % DS);                 // (past the end: clamped addresses, never read)
         const float *st = &s_t[grp][it % DS][0];
@@ -354,8 +347,6 @@ __global__ __launch_bounds__(128 * WM * KS) void sgemm_dma_kernel(const float *_
     else epilogue(std::integral_constant<int, 0>{});
 }
 
-inline int vec_ok(const float *p, int ld) { return (((uintptr_t)p & 15) == 0 && (ld & 3) == 0) ? 1 : 0; }
-
 }  // namespace
 
 static int sgemm_launch(int transA, int transB, int M, int N, int K, const float *A, int lda,
@@ -366,7 +357,7 @@ static int sgemm_launch(int transA, int transB, int M, int N, int K, const float
     if (M == 0 || N == 0) return COVA_OK;
     const dim3 grid(cdiv(N, BN), cdiv(M, BM));
     hipStream_t st = (hipStream_t)stream;
-    const int va = vec_ok(A, lda), vb = vec_ok(B, ldb);
+    const int va = vec4_ok(A, lda), vb = vec4_ok(B, ldb);
     // 16-byte pieces of both operands: aligned bases and leading dimensions, K a multiple of 4, a row-contiguous operand's row
     // count a multiple of 4 (a piece never straddles the edge); 32-bit byte offsets inside an operand
     const long long a_bytes = 4ll * (transA ? (long long)K * lda : (long long)M * lda), b_bytes = 4ll * (transB ? (long long)N * ldb : (long long)K * ldb);

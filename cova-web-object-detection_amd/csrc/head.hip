@@ -2,7 +2,7 @@
 // n_classes-wide last Linear (models.py:89) fwd/bwd, CrossEntropyLoss(reduction="sum") with its
 // gradient and the per-box argmax (main.py:139, train.py:53,56), and the Adam update as
 // configured at main.py:133-135 (L2 weight decay added to the gradient, bias-corrected).
-#include "common.h"
+#include "rows.h"
 
 namespace {
 
@@ -41,8 +41,6 @@ __global__ __launch_bounds__(256) void dropout_bwd_kernel(const float *__restric
     }
 }
 
-constexpr int MAXNC = 16;
-
 // y[n][k] = x[n] . W[k] + b[k]; one wave per row.  V = 4: a lane takes four adjacent input columns per step (one
 // float4 of x and of every weight row: a 976-column row is four steps instead of sixteen dependent round trips).
 template <int V>
@@ -54,9 +52,9 @@ __global__ __launch_bounds__(256) void linear_small_fwd_kernel(const float *__re
 {
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (n >= N) return;
-    float acc[MAXNC];
+    float acc[COVA_MAX_CLASSES];
 #pragma unroll
-    for (int k = 0; k < MAXNC; ++k) acc[k] = 0.f;
+    for (int k = 0; k < COVA_MAX_CLASSES; ++k) acc[k] = 0.f;
     for (int c = lane * V; c < Cin; c += 64 * V) {
         float xv[V];
         if (V == 4) {
@@ -66,7 +64,7 @@ __global__ __launch_bounds__(256) void linear_small_fwd_kernel(const float *__re
             xv[0] = x[(size_t)n * ldx + c];
         }
 #pragma unroll
-        for (int k = 0; k < MAXNC; ++k)
+        for (int k = 0; k < COVA_MAX_CLASSES; ++k)
             if (k < NC) {
                 if (V == 4) {
                     const float4 w = *reinterpret_cast<const float4 *>(W + (size_t)k * Cin + c);
@@ -77,7 +75,7 @@ __global__ __launch_bounds__(256) void linear_small_fwd_kernel(const float *__re
             }
     }
 #pragma unroll
-    for (int k = 0; k < MAXNC; ++k)
+    for (int k = 0; k < COVA_MAX_CLASSES; ++k)
         if (k < NC) {
             const float t = wave_sum(acc[k]);
             if (lane == 0) y[(size_t)n * NC + k] = t + b[k];
@@ -102,7 +100,7 @@ __device__ __forceinline__ void linear_small_bwd_x_body(const float *__restrict_
 // dW[k][c] = sum_n dy[n][k]*x[n][c]; block = 64 columns x 16 row slices; db by block 0
 // V = 4: a thread owns 4 adjacent input columns (one float4 per row): 16 threads cover the block's 64 columns and a
 // wave walks 4 row slices, the block 64 (V = 1: 16 slices, any alignment) -- see colsum_kernel.
-// KN: compile-time bound of the class count (4: the reference's; MAXNC otherwise) -- the register budget of the row batches
+// KN: compile-time bound of the class count (4: the reference's; COVA_MAX_CLASSES otherwise) -- the register budget of the row batches
 template <int V, int KN>
 __global__ __launch_bounds__(1024) void linear_small_bwd_w_kernel(const float *__restrict__ dy,
                                                                   const float *__restrict__ x, int ldx,
@@ -218,7 +216,7 @@ __global__ __launch_bounds__(1024) void ce_sum_kernel(const float *__restrict__ 
     double local = 0.0;
     for (int n = threadIdx.x; n < N; n += 1024) {
         const float *l = logits + (size_t)n * NC;
-        float m = l[0];
+        float m = l[0];                                     // row_lse (rows.h), written out: these statements must match it
         int am = 0;
         for (int k = 1; k < NC; ++k)
             if (l[k] > m) { m = l[k]; am = k; }
@@ -312,31 +310,23 @@ __global__ __launch_bounds__(256) void page_class_topk_kernel(const float *__res
     for (int j = 0; j < k; ++j) {
         // best (value, lowest index) strictly after (prev_v, prev_i) in the order (v desc, i asc)
         float bv = -INFINITY;
-        int bi = 0x7fffffff;
+        int bi = RANK_NONE;
         for (int n = lo + lane; n < hi; n += 64) {
             const float v = logits[(size_t)n * NC + c];
             const int i = n - lo;
-            const bool after = (v < prev_v) || (v == prev_v && i > prev_i);
-            if (after && (v > bv || (v == bv && i < bi))) { bv = v; bi = i; }
+            const bool after = ranks_before(prev_v, prev_i, v, i);
+            if (after && ranks_before(v, i, bv, bi)) { bv = v; bi = i; }
         }
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
+        for (int o = 32; o > 0; o >>= 1) {                  // (not wave_ranked_first: no RANK_NONE tests, see rows.h)
             const float ov = __shfl_xor(bv, o, 64);
             const int oi = __shfl_xor(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+            if (ranks_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
         }
-        if (lane == 0) out[((size_t)page * NC + c) * k + j] = (bi == 0x7fffffff) ? -1 : bi;
+        if (lane == 0) out[((size_t)page * NC + c) * k + j] = (bi == RANK_NONE) ? -1 : bi;
         prev_v = bv;
         prev_i = bi;
     }
-}
-
-inline int ew_grid(long long total)
-{
-    long long g = cdivll(total, 256);
-    if (g > 4096) g = 4096;
-    if (g < 1) g = 1;
-    return (int)g;
 }
 
 }  // namespace
@@ -365,7 +355,7 @@ COVA_API int cova_dropout_bwd(const float *g, int ldg, const uint8_t *mask, floa
 COVA_API int cova_linear_small_fwd(const float *x, int ldx, const float *W, const float *b, float *y,
                                    int N, int Cin, int NC, void *stream)
 {
-    COVA_REQUIRE(x && W && b && y && NC > 0 && NC <= MAXNC && Cin > 0);
+    COVA_REQUIRE(x && W && b && y && NC > 0 && NC <= COVA_MAX_CLASSES && Cin > 0);
     if (N == 0) return COVA_OK;
     const bool v4 = (Cin % 4 == 0) && (ldx % 4 == 0) && (((uintptr_t)x & 15) == 0) && (((uintptr_t)W & 15) == 0);
     hipLaunchKernelGGL((v4 ? linear_small_fwd_kernel<4> : linear_small_fwd_kernel<1>), dim3(cdiv(N, 4)), dim3(256), 0,
@@ -378,7 +368,7 @@ COVA_API int cova_linear_small_bwd(const float *dy, const float *x, int ldx, con
                                    float *dx, int lddx, float *dW, float *db, int N, int Cin, int NC,
                                    void *stream)
 {
-    COVA_REQUIRE(dy && x && W && dx && dW && db && NC > 0 && NC <= MAXNC && Cin > 0 && N > 0);
+    COVA_REQUIRE(dy && x && W && dx && dW && db && NC > 0 && NC <= COVA_MAX_CLASSES && Cin > 0 && N > 0);
     hipStream_t st = (hipStream_t)stream;
     const bool v4 = (Cin % 4 == 0) && (ldx % 4 == 0) && (((uintptr_t)x & 15) == 0);
     // one launch: cdiv(Cin, 64) weight-gradient blocks, then the blocks of the input gradient (same arithmetic per element
@@ -388,7 +378,7 @@ COVA_API int cova_linear_small_bwd(const float *dy, const float *x, int ldx, con
     if (nx > 1024) nx = 1024;
     const dim3 wgrid(nw + (int)nx), wblock(1024);
     if (NC <= 4) hipLaunchKernelGGL((v4 ? linear_small_bwd_w_kernel<4, 4> : linear_small_bwd_w_kernel<1, 4>), wgrid, wblock, 0, st, dy, x, ldx, dW, db, N, Cin, NC, W, dx, lddx, nw);
-    else hipLaunchKernelGGL((v4 ? linear_small_bwd_w_kernel<4, MAXNC> : linear_small_bwd_w_kernel<1, MAXNC>), wgrid, wblock, 0, st, dy, x, ldx, dW, db, N, Cin, NC, W, dx, lddx, nw);
+    else hipLaunchKernelGGL((v4 ? linear_small_bwd_w_kernel<4, COVA_MAX_CLASSES> : linear_small_bwd_w_kernel<1, COVA_MAX_CLASSES>), wgrid, wblock, 0, st, dy, x, ldx, dW, db, N, Cin, NC, W, dx, lddx, nw);
     COVA_LAUNCH_CHECK();
     return COVA_OK;
 }

@@ -106,13 +106,6 @@ __global__ __launch_bounds__(256) void collate_boxes_kernel(
     }
 }
 
-inline int grid_for(long long n)
-{
-    long long g = (n + 255) / 256;
-    if (g > 256 * 32) g = 256 * 32;
-    return (int)(g < 1 ? 1 : g);
-}
-
 }  // namespace
 
 // u8 [B,H,W,3] -> f32 [B,3,H,W], value/255 (torchvision ToTensor as used at datasets.py:41-45)

@@ -6,11 +6,10 @@
 // Per-row arithmetic is ce_sum_kernel's (f32, expf / logf, first maximum wins); sums over rows are float64 over fixed
 // slices of LOSS_SLICE rows folded in a fixed order, so the results depend on N alone: no float atomics, no host read.
 // With no option set the rows' terms are ce_sum_kernel's bits (1.0f factors and +0 terms only).
-#include "common.h"
+#include "rows.h"
 
 namespace {
 
-constexpr int LOSS_MAXNC = 16;        // = the head's MAXNC (head.hip)
 constexpr int LOSS_THREADS = 1024;
 constexpr int LOSS_ROWS = 2;          // rows per thread of the forward: a slice is one block's rows
 constexpr int LOSS_SLICE = LOSS_THREADS * LOSS_ROWS;
@@ -24,26 +23,6 @@ struct LossOpt {
     long long ignore_index;
     int has_ignore;
 };
-
-// 0: kept, 1: ignored, 2: outside [0, NC) and not the ignore label
-__device__ __forceinline__ int label_state(long long lab, int NC, const LossOpt &o)
-{
-    if (o.has_ignore && lab == o.ignore_index) return 1;
-    return (lab < 0 || lab >= NC) ? 2 : 0;
-}
-
-// max / first argmax / logsumexp of one row, exactly as ce_sum_kernel
-__device__ __forceinline__ float row_lse(const float *__restrict__ l, int NC, int *am_out)
-{
-    float m = l[0];
-    int am = 0;
-    for (int k = 1; k < NC; ++k)
-        if (l[k] > m) { m = l[k]; am = k; }
-    float se = 0.f;
-    for (int k = 0; k < NC; ++k) se += expf(l[k] - m);
-    *am_out = am;
-    return m + logf(se);
-}
 
 // 1 - p_y as the sum of the other classes' probabilities: a saturated row gives 0, never a negative or a NaN
 __device__ __forceinline__ float others_prob(const float *__restrict__ l, int NC, int y, float lse)
@@ -59,13 +38,6 @@ __device__ __forceinline__ float others_prob(const float *__restrict__ l, int NC
 __device__ __forceinline__ float focal_pow_m1(float q, float gamma)
 {
     return gamma == 1.f ? 1.f : gamma == 2.f ? q : powf(q, gamma - 1.f);
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // metrics (int64 words, M = NC*NC): [0, M) confusion[label][pred], [M] kept, [M+1] bad labels, [M+2], [M+3] the float64
@@ -92,8 +64,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void ce_loss_fwd_kernel(const float *
                                                                    double *__restrict__ acc, int64_t *__restrict__ pred,
                                                                    int64_t *__restrict__ metrics)
 {
-    __shared__ float s_w[LOSS_MAXNC];
-    __shared__ int s_conf[LOSS_MAXNC * LOSS_MAXNC];
+    __shared__ float s_w[COVA_MAX_CLASSES];
+    __shared__ int s_conf[COVA_MAX_CLASSES * COVA_MAX_CLASSES];
     __shared__ double s_part[LOSS_THREADS / 64][N_ACC];
     if (threadIdx.x < NC) s_w[threadIdx.x] = weight ? weight[threadIdx.x] : 1.f;
     if (threadIdx.x < NC * NC) s_conf[threadIdx.x] = 0;
@@ -109,7 +81,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void ce_loss_fwd_kernel(const float *
         const float lse = row_lse(l, NC, &am);
         if (pred) pred[n] = am;
         const long long lab = labels[n];
-        const int state = label_state(lab, NC, o);
+        const int state = label_state(lab, NC, o.ignore_index, o.has_ignore);
         if (state == 2) t[3] += 1.0;
         if (state != 0) continue;
         const int y = (int)lab;
@@ -177,7 +149,7 @@ __global__ __launch_bounds__(LOSS_BWD_THREADS) void ce_loss_bwd_kernel(const flo
                                                                        float *__restrict__ loss,
                                                                        float *__restrict__ dlogits)
 {
-    __shared__ float s_w[LOSS_MAXNC];
+    __shared__ float s_w[COVA_MAX_CLASSES];
     if (threadIdx.x < NC) s_w[threadIdx.x] = weight ? weight[threadIdx.x] : 1.f;
     __syncthreads();
     const double num = acc[0], den = acc[1];
@@ -190,7 +162,7 @@ __global__ __launch_bounds__(LOSS_BWD_THREADS) void ce_loss_bwd_kernel(const flo
     const float *l = logits + (size_t)n * NC;
     float *d = dlogits + (size_t)n * NC;
     const long long lab = labels[n];
-    if (label_state(lab, NC, o) != 0) {
+    if (label_state(lab, NC, o.ignore_index, o.has_ignore) != 0) {
         for (int k = 0; k < NC; ++k) d[k] = 0.f;
         return;
     }
@@ -224,7 +196,7 @@ __global__ __launch_bounds__(LOSS_BWD_THREADS) void ce_loss_bwd_kernel(const flo
 inline bool loss_options(int NC, double label_smoothing, double focal_gamma, long long ignore_index,
                          int has_ignore_index, LossOpt *o)
 {
-    if (!(NC > 0 && NC <= LOSS_MAXNC)) return false;
+    if (!(NC > 0 && NC <= COVA_MAX_CLASSES)) return false;
     if (!(label_smoothing >= 0.0 && label_smoothing < 1.0)) return false;
     if (!(focal_gamma == 0.0 || focal_gamma >= 1.0)) return false;
     if (focal_gamma != 0.0 && label_smoothing != 0.0) return false;

@@ -1,36 +1,25 @@
 // Per-page hard-negative mining for the criterion: after the forward every page keeps its
 // positives and the k hardest background boxes, k = max(min_keep, floor(ratio * positives)); the other background boxes
 // get the criterion's ignore label and stay graph context.  The score is the plain cross-entropy against background,
-// lse - l[0], with row_lse's arithmetic (loss.hip); it becomes an integer key and the rank is a count, as in eval.hip and
+// lse - l[0], with row_lse (rows.h); it becomes an integer key and the rank is a count, as in eval.hip and
 // sample.hip: no atomics, no host read, one launch, a function of the inputs alone.
 //   mine_select_kernel  one block per page: scores and keys of the page's rows (keys in an LDS tile), the page's counts
 //                       and quota, then one thread per background row counts the rows that rank before it with broadcast
 //                       reads of the tile.  A page of more than MINE_TILE rows walks its keys tile by tile, recomputing
 //                       them from the logits (n / MINE_THREADS passes: the counting itself stays the larger cost).
-#include "common.h"
+#include "rows.h"
 
 namespace {
 
-constexpr int MINE_MAXNC = 16;            // = LOSS_MAXNC (loss.hip)
 constexpr int MINE_THREADS = 256;
 constexpr int MINE_TILE = 2048;           // keys per LDS tile (8 KiB); a page of the reference's data (11-230 boxes) is one tile
 constexpr unsigned MINE_NAN_KEY = 0x7FC00000u;
 
-// logsumexp of one row with the statement order of loss.hip's row_lse (max, expf sum, m + logf(se))
-__device__ __forceinline__ float mine_row_lse(const float *__restrict__ l, int NC)
-{
-    float m = l[0];
-    for (int k = 1; k < NC; ++k)
-        if (l[k] > m) m = l[k];
-    float se = 0.f;
-    for (int k = 0; k < NC; ++k) se += expf(l[k] - m);
-    return m + logf(se);
-}
-
 __device__ __forceinline__ float mine_score(const float *__restrict__ logits, int row, int NC)
 {
     const float *l = logits + (size_t)row * NC;
-    return mine_row_lse(l, NC) - l[0];
+    int am;
+    return row_lse(l, NC, &am) - l[0];
 }
 
 // NaN ranks above +inf (a broken forward stays in the loss), s <= 0 (rounding, -0) is the easiest
@@ -62,8 +51,6 @@ __device__ __forceinline__ void mine_pass_through(const float *__restrict__ logi
     }
 }
 
-__device__ __forceinline__ int mine_clamp(long long v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : (int)v; }
-
 __global__ __launch_bounds__(MINE_THREADS) void mine_select_kernel(
     const float *__restrict__ logits, const int64_t *__restrict__ labels, const int64_t *__restrict__ page_start, int B,
     int N, int NC, double ratio, int min_keep, long long drop_label, int64_t *__restrict__ labels_out,
@@ -72,7 +59,8 @@ __global__ __launch_bounds__(MINE_THREADS) void mine_select_kernel(
     __shared__ __attribute__((aligned(16))) unsigned tile[MINE_TILE];
     __shared__ int wave_cnt[MINE_THREADS / 64][2];
     const int p = blockIdx.x, tid = threadIdx.x;
-    const int base = mine_clamp(page_start[p], 0, N), end = mine_clamp(page_start[p + 1], base, N), n = end - base;
+    const PageRows pr = page_rows(page_start, p, N);
+    const int base = pr.base, end = pr.end, n = end - base;
     if (p == 0) mine_pass_through(logits, labels, 0, base, NC, labels_out, score_out);
     if (p == B - 1) mine_pass_through(logits, labels, end, N, NC, labels_out, score_out);
     const bool one_tile = n <= MINE_TILE;
@@ -89,11 +77,8 @@ __global__ __launch_bounds__(MINE_THREADS) void mine_select_kernel(
         if (one_tile) tile[i] = mine_word(s, lab);
     }
     if (one_tile && tid < 4 && n + tid < ((n + 3) & ~3)) tile[n + tid] = 0u;           // pad to whole uint4 reads
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        n_pos += __shfl_xor(n_pos, o, 64);
-        n_bg += __shfl_xor(n_bg, o, 64);
-    }
+    n_pos = wave_sum_i(n_pos);
+    n_bg = wave_sum_i(n_bg);
     if ((tid & 63) == 0) {
         wave_cnt[tid >> 6][0] = n_pos;
         wave_cnt[tid >> 6][1] = n_bg;
@@ -152,7 +137,7 @@ COVA_API int cova_hard_negative_select(const float *logits, const int64_t *label
                                        float *score_out, int *counts, void *stream)
 {
     COVA_REQUIRE(logits && labels && page_start && labels_out && B >= 1 && N >= 1);
-    COVA_REQUIRE(NC >= 2 && NC <= MINE_MAXNC);
+    COVA_REQUIRE(NC >= 2 && NC <= COVA_MAX_CLASSES);
     COVA_REQUIRE(ratio >= 0.0 && ratio <= DBL_MAX && min_keep >= 0);
     hipLaunchKernelGGL(mine_select_kernel, dim3(B), dim3(MINE_THREADS), 0, (hipStream_t)stream, logits, labels, page_start,
                        B, N, NC, ratio, min_keep, drop_label, labels_out, score_out, counts);

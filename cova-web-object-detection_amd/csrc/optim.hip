@@ -203,8 +203,7 @@ __global__ __launch_bounds__(OPT_THREADS) void optim_step_kernel(float *__restri
 // double-precision sum over the block in a fixed order (wave butterflies, then the waves in index order)
 __device__ __forceinline__ double block_sum(double x, double *s_wave)
 {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    x = wave_sum_f64(x);
     if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = x;
     __syncthreads();
     double t = 0.0;
@@ -365,8 +364,6 @@ __global__ __launch_bounds__(OPT_THREADS) void grad_accumulate_kernel(float *__r
         if (a < b) for_each_element(a, b, vec4 != 0, op);
     });
 }
-
-inline bool aligned16(const void *ptr) { return ((uintptr_t)ptr & 15) == 0; }
 
 }  // namespace
 

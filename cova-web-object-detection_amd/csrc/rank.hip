@@ -3,12 +3,12 @@
 // ignore label); its targets are the rows labelled c, and a list with a target is scored:
 //   L_pc = lse_candidates(v) - lse_targets(v),   dL_pc/dv_n = softmax_cand(v)_n - [n is a target] softmax_tgt(v)_n.
 //   rank_lists_kernel  one wave per list, as eval.hip: f32 maxima, expf(v - m) terms in f32 summed in float64 (lane-
-//                      strided over the page's rows, then loss.hip's xor butterfly), lse = (double)m + log(sum) -> lists.
+//                      strided over the page's rows, then the xor butterfly wave_sum_f64), lse = (double)m + log(sum) -> lists.
 //   rank_fold_kernel   one wave folds the table into acc = {sum w_c L_pc, sum w_c, scored lists} in a fixed order.
 //   rank_bwd_kernel    one thread per row: finds the row's page, reads the lists' lse values, writes or accumulates
 //                      dlogits[n, 1..NC-1]; thread 0 writes or accumulates the loss.
 // No atomics, no workspace beyond the table, no host read; a list's result is a function of its page's rows alone.
-#include "common.h"
+#include "rows.h"
 
 // the contract counts one rounding per operation (accumulate = pre-fill + the accumulate == 0 result, in f32): no fused
 // multiply-adds in this file
@@ -16,42 +16,8 @@
 
 namespace {
 
-constexpr int RANK_MAXNC = 16;            // = LOSS_MAXNC (loss.hip)
 constexpr int RANK_THREADS = 256;
 constexpr int RANK_LIST = 4;              // doubles per list: lse of the candidates, lse of the targets, the two counts
-
-__device__ __forceinline__ int rank_clamp(long long v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : (int)v; }
-
-// loss.hip's wave_sum_f64: the xor butterfly, every lane ends with the same bits
-__device__ __forceinline__ double rank_wave_sum_f64(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ int rank_wave_sum_i(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// f32 compares; a NaN never wins, so it reaches the sum through expf(NaN - m)
-__device__ __forceinline__ float rank_wave_max(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float u = __shfl_xor(v, o, 64);
-        if (u > v) v = u;
-    }
-    return v;
-}
-
-__device__ __forceinline__ bool rank_candidate(long long lab, int NC, long long ignore_index, int has_ignore)
-{
-    return lab >= 0 && lab < NC && !(has_ignore && lab == ignore_index);
-}
 
 __global__ __launch_bounds__(RANK_THREADS) void rank_lists_kernel(const float *__restrict__ logits,
                                                                   const int64_t *__restrict__ labels,
@@ -62,12 +28,13 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_lists_kernel(const float *_
     const int task = blockIdx.x * (RANK_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (task >= B * (NC - 1)) return;                     // wave-uniform
     const int p = task / (NC - 1), c = 1 + task - p * (NC - 1);
-    const int base = rank_clamp(page_start[p], 0, N), end = rank_clamp(page_start[p + 1], base, N);
+    const PageRows pr = page_rows(page_start, p, N);
+    const int base = pr.base, end = pr.end;
     float mA = -INFINITY, mT = -INFINITY;
     int nA = 0, nT = 0;
     for (int n = base + lane; n < end; n += 64) {
         const long long lab = labels[n];
-        if (!rank_candidate(lab, NC, ignore_index, has_ignore)) continue;
+        if (label_state(lab, NC, ignore_index, has_ignore) != 0) continue;
         const float v = logits[(size_t)n * NC + c];
         ++nA;
         if (v > mA) mA = v;
@@ -76,8 +43,8 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_lists_kernel(const float *_
             if (v > mT) mT = v;
         }
     }
-    nA = rank_wave_sum_i(nA);
-    nT = rank_wave_sum_i(nT);
+    nA = wave_sum_i(nA);
+    nT = wave_sum_i(nT);
     double *out = lists + (size_t)task * RANK_LIST;
     if (nT == 0) {                                        // unscored: counts only
         if (lane == 0) {
@@ -88,18 +55,18 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_lists_kernel(const float *_
         }
         return;
     }
-    mA = rank_wave_max(mA);
-    mT = rank_wave_max(mT);
+    mA = wave_max_gt(mA);
+    mT = wave_max_gt(mT);
     double sA = 0.0, sT = 0.0;
     for (int n = base + lane; n < end; n += 64) {
         const long long lab = labels[n];
-        if (!rank_candidate(lab, NC, ignore_index, has_ignore)) continue;
+        if (label_state(lab, NC, ignore_index, has_ignore) != 0) continue;
         const float v = logits[(size_t)n * NC + c];
         sA += (double)expf(v - mA);
         if (lab == c) sT += (double)expf(v - mT);
     }
-    sA = rank_wave_sum_f64(sA);
-    sT = rank_wave_sum_f64(sT);
+    sA = wave_sum_f64(sA);
+    sT = wave_sum_f64(sT);
     if (lane == 0) {
         out[0] = (double)mA + log(sA);
         out[1] = (double)mT + log(sT);
@@ -122,9 +89,9 @@ __global__ __launch_bounds__(64) void rank_fold_kernel(const double *__restrict_
             cnt += 1.0;
         }
     }
-    num = rank_wave_sum_f64(num);
-    den = rank_wave_sum_f64(den);
-    cnt = rank_wave_sum_f64(cnt);
+    num = wave_sum_f64(num);
+    den = wave_sum_f64(den);
+    cnt = wave_sum_f64(cnt);
     if (threadIdx.x == 0) {
         acc[0] = num;
         acc[1] = den;
@@ -157,7 +124,7 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_bwd_kernel(
         else lo = mid + 1;
     }
     const long long lab = labels[n];
-    const bool live = lo < B && page_start[lo] <= (int64_t)n && rank_candidate(lab, NC, ignore_index, has_ignore);
+    const bool live = lo < B && page_start[lo] <= (int64_t)n && label_state(lab, NC, ignore_index, has_ignore) == 0;
     if (!live) {
         if (!accumulate)
             for (int k = 0; k < NC; ++k) d[k] = 0.f;
@@ -191,7 +158,7 @@ COVA_API int cova_page_rank_loss_fwd(const float *logits, const int64_t *labels,
                                      double *lists, double *acc, void *stream)
 {
     COVA_REQUIRE(logits && labels && page_start && lists && acc && B >= 1 && N >= 1);
-    COVA_REQUIRE(NC >= 2 && NC <= RANK_MAXNC);
+    COVA_REQUIRE(NC >= 2 && NC <= COVA_MAX_CLASSES);
     const long long n_lists = (long long)B * (NC - 1);
     COVA_REQUIRE(n_lists <= INT32_MAX);
     hipStream_t s = (hipStream_t)stream;
@@ -210,7 +177,7 @@ COVA_API int cova_page_rank_loss_bwd(const float *logits, const int64_t *labels,
                                      void *stream)
 {
     COVA_REQUIRE(logits && labels && page_start && lists && acc_total && (loss_inout || dlogits) && B >= 1 && N >= 1);
-    COVA_REQUIRE(NC >= 2 && NC <= RANK_MAXNC);
+    COVA_REQUIRE(NC >= 2 && NC <= COVA_MAX_CLASSES);
     COVA_REQUIRE((long long)B * (NC - 1) <= INT32_MAX);
     COVA_REQUIRE(rank_weight >= 0.0 && rank_weight <= DBL_MAX);
     const int grid = dlogits ? cdiv(N, RANK_THREADS) : 1;

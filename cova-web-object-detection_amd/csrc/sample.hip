@@ -94,8 +94,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_compact_kernel(
     const int p = blockIdx.x, tid = threadIdx.x;
     int s = 0;
     for (int q = tid; q < p; q += SAMPLE_THREADS) s += counts[q];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = wave_sum_i(s);
     if ((tid & 63) == 0) wave_tot[tid >> 6] = s;
     __syncthreads();
     int start = 0;
@@ -146,13 +145,6 @@ __global__ __launch_bounds__(256) void collate_selected_kernel(
             ctx[(long long)g * K + slot] = v;
         }
     }
-}
-
-inline int grid_for(long long n)
-{
-    long long g = (n + 255) / 256;
-    if (g > 256 * 32) g = 256 * 32;
-    return (int)(g < 1 ? 1 : g);
 }
 
 }  // namespace

@@ -1779,7 +1779,7 @@ def check_decode(decode, score, n_classes, k=1):
 
 
 # ------------------------------------------------------------------------------------------- configurable criterion
-LOSS_MAX_CLASSES = 16
+LOSS_MAX_CLASSES = 16                               # = COVA_MAX_CLASSES (csrc/rows.h), the one class limit of the row and page kernels
 LOSS_REDUCTIONS = ("sum", "mean")
 
 

@@ -25,7 +25,7 @@ CANARY = 7.0
 
 # ------------------------------------------------------------------------------------------------ dispatch
 def _vec4_ok(off, ld):
-    """bn.hip vec4_ok: a NULL pointer passes; otherwise 16-byte aligned and ld % 4 == 0"""
+    """common.h vec4_ok: a NULL pointer passes; otherwise 16-byte aligned and ld % 4 == 0"""
     return off is None or (off % 4 == 0 and ld % 4 == 0)
 
 
