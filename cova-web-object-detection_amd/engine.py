@@ -165,7 +165,8 @@ def check_batch(cfg, images, bboxes, additional_feats, context_indices, training
                              % (GAT_MAX_K, GAT_MAX_K // 2))
     if N == 1:
         # torch.nn.functional.batch_norm's _verify_batch_size, hit by the first train-mode BatchNorm1d of the forward
-        T = backbone_feat(cfg) + cfg["bbox_hidden_dim"] + A + (cfg["hidden_dim"] if cfg["use_context"] else 0)
+        T = (backbone_feat(cfg) + cfg["bbox_hidden_dim"] + A + (cfg["hidden_dim"] if cfg["use_context"] else 0)
+             + cfg.get("page_context_dim", 0))
         for width, prefix in ((cfg["bbox_hidden_dim"], "bbox_feat_encoder.1."), (A, "bn_additional_feat."),
                               (T, "decoder.2.")):
             if width and is_train(training, prefix):
@@ -1541,6 +1542,53 @@ def gat_stack_bwd(layers, dcomb, T, N, F, D, params, gout=None):
     return grads
 
 
+# ------------------------------------------------------------------------------- page readout
+def page_start_of(bboxes, images, page_start=None):
+    """The pages' row offsets (device int64 [B + 1]) without a host read: the batch's table when given, else from the
+    page column of the page-sorted boxes and the page count of the images (HotPathTrainer._page_start's rule)."""
+    if page_start is not None:
+        return _check(page_start.contiguous(), torch.int64)
+    if images is None:
+        raise ValueError("page_context_dim: a batch without images must carry page_start (the pages' row offsets, "
+                         "int64 [B + 1])")
+    pages = torch.arange(int(images.shape[0]) + 1, dtype=torch.float32, device=bboxes.device)
+    return torch.searchsorted(bboxes[:, 0].contiguous(), pages)
+
+
+def page_readout_fwd(h, ldh, N, F, page_start, params, out, ldo, prefix="page_readout."):
+    """The page readout (cova_page_readout_fwd): P = h W^T by cova_sgemm, then per page the softmax of
+    LeakyReLU(a . P_i + b) over its rows and r_p = sum beta_i P_i, written to the row out + n*ldo of every box of the page.
+    h rows at h + n*ldh (F values); ``page_start`` device int64 [B + 1].  -> saved dict for page_readout_bwd."""
+    _check(page_start, torch.int64)
+    W = params[prefix + "W.weight"]
+    aw, ab = params[prefix + "attention_layer.weight"], params[prefix + "attention_layer.bias"]
+    G, B = W.shape[0], page_start.shape[0] - 1
+    if W.shape[1] != F or aw.numel() != G:
+        raise ValueError("%sW.weight %s / attention_layer.weight %s do not fit %d own features"
+                         % (prefix, tuple(W.shape), tuple(aw.shape), F))
+    P = _empty((N, G), h)
+    call("cova_sgemm", 0, 1, N, G, F, h, ldh, W, F, P, G, None, 0)
+    u, beta, r = _empty((N,), h), _empty((N,), h), _empty((B, G), h)
+    call("cova_page_readout_fwd", P, G, aw, ab, page_start, B, N, G, LEAKY_SLOPE, u, beta, r, out, ldo)
+    return dict(h=h, ldh=ldh, N=N, F=F, G=G, B=B, P=P, u=u, beta=beta, r=r, page_start=page_start, prefix=prefix)
+
+
+def page_readout_bwd(sv, g, ldg, params, dh, lddh, gout=None):
+    """g = dL/d(readout columns) (rows at g + n*ldg).  ACCUMULATES dL/dh into dh; returns the three parameter gradients."""
+    N, F, G, B, prefix = sv["N"], sv["F"], sv["G"], sv["B"], sv["prefix"]
+    W, aw = params[prefix + "W.weight"], params[prefix + "attention_layer.weight"]
+    dP = _empty((N, G), g)
+    daw = _gbuf(gout, prefix + "attention_layer.weight", (1, G), g)
+    dab = _gbuf(gout, prefix + "attention_layer.bias", (1,), g)
+    ws = _empty((query("cova_page_readout_workspace_floats", B, G),), g)
+    call("cova_page_readout_bwd", g, ldg, sv["P"], G, sv["u"], sv["beta"], sv["r"], aw, sv["page_start"], B, N, G,
+         LEAKY_SLOPE, dP, G, daw, dab, ws)
+    dW = _gbuf(gout, prefix + "W.weight", (G, F), g)
+    call("cova_sgemm", 1, 0, G, F, N, dP, G, sv["h"], sv["ldh"], dW, F, None, 0)
+    call("cova_sgemm", 0, 0, N, F, G, dP, G, W, F, dh, lddh, None, 1)
+    return {prefix + "W.weight": dW, prefix + "attention_layer.weight": daw, prefix + "attention_layer.bias": dab}
+
+
 # ------------------------------------------------------------------------------- decoder
 def dropout_fwd(x, ld, N, C, p, seed, mask=None):
     out = _empty((N, C), x)
@@ -1607,8 +1655,11 @@ def decoder_bwd(sv, dlogits, params, gout=None):
 # ------------------------------------------------------------------------------- whole model
 @on_device_of(3)
 def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_indices, training,
-              seeds=(0, 0), masks=None, save=True, plan=None, visual_feats=None, page_size=None):
+              seeds=(0, 0), masks=None, save=True, plan=None, visual_feats=None, page_size=None, page_start=None):
     """CoVA.forward (models.py:94-122) -> (logits [N,n_classes], saved-for-backward or None).
+    ``page_start`` (device int64 [B + 1], the pages' row offsets) is read by cfg["page_context_dim"] only: the batch's table
+    when given, else derived on the device from the page column of ``bboxes`` and the page count of ``images``
+    (page_start_of); a batch without either raises ValueError.
     ``page_size`` = (height, width) of the pages, read by cfg["edge_geometry"] only: by default ``images.shape[2:]``; a batch
     without images (``visual_feats``) must name it (DeviceDataset batches carry it) or cfg["page_size"] must.
     ``training``: a bool (whole model) or per-layer modes {BatchNorm prefix / Dropout name: bool} (is_train).
@@ -1618,21 +1669,24 @@ def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_in
     "convstack" (nothing is kept to run that backward from)."""
     if visual_feats is not None:
         return _model_fwd_cached(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks,
-                                 save, plan, visual_feats, page_size)
+                                 save, plan, visual_feats, page_size, page_start)
     N = bboxes.shape[0]
     PH, PW = cfg["roi_output_size"]
     n_vis = (C256 if is_bottleneck(params) else C128 if has_layer2(params) else C64) * PH * PW
     Hd, A = cfg["bbox_hidden_dim"], cfg["n_additional_feat"]
     F = n_vis + Hd + A
     D = cfg["hidden_dim"] if cfg["use_context"] else 0
-    T = F + D
+    G = cfg.get("page_context_dim", 0)
+    T = F + D + G
+    if G > 0:
+        page_start = page_start_of(bboxes, images, page_start)
     align = cfg.get("roi_op", "pool") == "align"
     save_conv = save and (plan is None or "convstack" in plan)
     feat, sv_conv = convstack_fwd(images, params, buffers, training, save_conv, lazy_out=not align)
     comb = _empty((N, T), images)
     scale = cfg.get("spatial_scale") or feat.shape[1] / images.shape[2]   # models.py:56
-    sv = dict(cfg=cfg, N=N, F=F, D=D, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=sv_conv, comb=comb,
-              page_size=page_size or cfg.get("page_size") or tuple(images.shape[2:]))
+    sv = dict(cfg=cfg, N=N, F=F, D=D, G=G, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=sv_conv, comb=comb,
+              page_size=page_size or cfg.get("page_size") or tuple(images.shape[2:]), page_start=page_start)
     if align:
         sv["roi"] = roialign_fwd(feat, bboxes, (PH, PW), scale, cfg.get("sampling_ratio", 2),
                                  cfg.get("roi_aligned", False), comb, T)
@@ -1644,6 +1698,7 @@ def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_in
 def _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks, save, sv):
     """Everything behind the visual columns of ``sv["comb"]``: positional encoder, additional features, GAT, decoder."""
     N, F, D, T, n_vis, Hd, A, comb = (sv[k] for k in ("N", "F", "D", "T", "n_vis", "Hd", "A", "comb"))
+    G = sv.get("G", 0)
     if Hd > 0:
         sv["bbox"] = bbox_fwd(bboxes, params, buffers, training, comb[:, n_vis:], T)
     if A > 0:
@@ -1659,6 +1714,8 @@ def _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, t
         sv["gat"] = gat_stack_fwd(comb, T, N, F, D, context_indices, params, cfg.get("n_heads", 1),
                                   cfg.get("n_gat_layers", 1), bboxes if edge else None, sv.get("page_size"), edge,
                                   cfg.get("attention", "gat"), cfg.get("attention_dropout", 0.0), seeds[0], training)
+    if G > 0:
+        sv["readout"] = page_readout_fwd(comb, T, N, F, sv["page_start"], params, comb[:, F + D:], T)
     logits, sv["dec"] = decoder_fwd(comb, N, T, params, buffers, training, cfg["drop_prob"], seeds,
                                     masks)
     return logits, (sv if save else None)
@@ -1689,7 +1746,7 @@ def check_visual_feats(cfg, visual_feats, N):
 
 @on_device_of(3)
 def _model_fwd_cached(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks, save, plan,
-                      visual_feats, page_size=None):
+                      visual_feats, page_size=None, page_start=None):
     """model_fwd with the visual columns taken from a feature table: no conv stack, no RoI op."""
     N = bboxes.shape[0]
     table, row_ids = check_visual_feats(cfg, visual_feats, N)
@@ -1700,10 +1757,13 @@ def _model_fwd_cached(cfg, params, buffers, bboxes, additional_feats, context_in
     Hd, A = cfg["bbox_hidden_dim"], cfg["n_additional_feat"]
     F = n_vis + Hd + A
     D = cfg["hidden_dim"] if cfg["use_context"] else 0
-    T = F + D
+    G = cfg.get("page_context_dim", 0)
+    T = F + D + G
+    if G > 0:
+        page_start = page_start_of(bboxes, None, page_start)
     comb = _empty((N, T), bboxes)
-    sv = dict(cfg=cfg, N=N, F=F, D=D, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=None, roi=None, comb=comb,
-              page_size=page_size or cfg.get("page_size"))
+    sv = dict(cfg=cfg, N=N, F=F, D=D, G=G, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=None, roi=None, comb=comb,
+              page_size=page_size or cfg.get("page_size"), page_start=page_start)
     call("cova_feat_rows_gather", table, table.shape[0], n_vis, row_ids, N, comb, T)
     return _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks, save, sv)
 
@@ -1722,6 +1782,8 @@ def model_bwd(sv, dlogits, params, gout=None, after_head=None, want_dimg=False, 
     dcomb, grads = decoder_bwd(sv["dec"], dlogits, params, gout)
     if D > 0:
         grads.update(gat_stack_bwd(sv["gat"], dcomb, T, N, F, D, params, gout))
+    if sv.get("G", 0) > 0:               # after the GAT's: both accumulate into dcomb[:, :F], in this order
+        grads.update(page_readout_bwd(sv["readout"], dcomb[:, F + D:], T, params, dcomb, T, gout))
     if A > 0 and (plan is None or "addl" in plan):
         st = sv["addl"]
         dz = _empty((N, A), dcomb)

@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from . import engine
 from .weights import (EDGE_FEATURES, attention_of, backbone_channels, check_attention, check_attention_dropout,
-                      check_backbone_layers)
+                      check_backbone_layers, check_page_context_dim)
 
 GAT_MAX_K = engine.GAT_MAX_K
 LOSS_MAX_CLASSES = engine.LOSS_MAX_CLASSES
@@ -433,12 +433,64 @@ class MultiHeadGraphAttention(nn.Module):
         return (h, attn) if return_attn_wts else h
 
 
+class _PageReadoutFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, layer, h, page_start, W, att_w, att_b):
+        h = _f32c(h)
+        N, F = h.shape
+        params = {"page_readout.W.weight": W.detach(), "page_readout.attention_layer.weight": att_w.detach(),
+                  "page_readout.attention_layer.bias": att_b.detach()}
+        out = torch.empty((N, layer.dim), device=h.device)
+        ctx.sv = engine.page_readout_fwd(h, F, N, F, _i64c(page_start), params, out, layer.dim)
+        ctx.params = params
+        ctx.mark_non_differentiable(ctx.sv["beta"])
+        return out, ctx.sv["beta"]
+
+    @staticmethod
+    def backward(ctx, g, _gbeta):
+        sv = ctx.sv
+        dh = torch.zeros((sv["N"], sv["F"]), device=g.device)          # page_readout_bwd accumulates
+        grads = engine.page_readout_bwd(sv, g.contiguous(), sv["G"], ctx.params, dh, sv["F"])
+        return (None, dh, None, grads["page_readout.W.weight"], grads["page_readout.attention_layer.weight"],
+                grads["page_readout.attention_layer.bias"])
+
+
+class PageReadout(nn.Module):
+    """Extension: the global-attention readout of Li et al. 2016 (gated graph networks; PyG ``AttentionalAggregation``)
+    over the boxes of each page.  ``P = W h`` (Linear(in_features, dim), no bias), ``beta`` = softmax over the page's boxes
+    of ``LeakyReLU(attention_layer(P))`` (Linear(dim, 1)), ``r_p = sum beta_i P_i``; every box of a page receives its
+    page's ``r_p``.  ``forward(h [N, in_features], page_start int64 [B + 1])`` -> ``r_rows [N, dim]`` (and ``beta [N]`` with
+    ``return_attn_wts``); one autograd node over cova_page_readout_fwd / cova_page_readout_bwd."""
+
+    def __init__(self, in_features, dim, alpha=0.2):
+        super().__init__()
+        if abs(alpha - engine.LEAKY_SLOPE) > 1e-12:
+            raise ValueError("the HIP path is built for the reference's LeakyReLU slope 0.2")
+        self.in_features, self.dim = in_features, check_page_context_dim(dim)
+        if self.dim < 1:
+            raise ValueError("PageReadout needs dim >= 1")
+        self.W = nn.Linear(in_features, self.dim, bias=False)
+        self.attention_layer = nn.Linear(self.dim, 1)
+
+    def forward(self, h, page_start, return_attn_wts=False):
+        _require_cuda(h, page_start)
+        if h.dim() != 2 or h.shape[1] != self.in_features:
+            raise RuntimeError("expected h [N, %d], got %s" % (self.in_features, tuple(h.shape)))
+        if page_start.dim() != 1 or page_start.shape[0] < 1 or page_start.is_floating_point():
+            raise ValueError("page_start must hold B + 1 integer row offsets, got shape %s" % (tuple(page_start.shape),))
+        if h.shape[0] == 0:
+            return (h.new_empty((0, self.dim)), h.new_empty((0,))) if return_attn_wts else h.new_empty((0, self.dim))
+        out, beta = _PageReadoutFn.apply(self, h, page_start, self.W.weight, self.attention_layer.weight,
+                                         self.attention_layer.bias)
+        return (out, beta) if return_attn_wts else out
+
+
 class CoVA(nn.Module):
     def __init__(self, roi_output_size, img_H, n_classes, use_context=True, hidden_dim=384,
                  bbox_hidden_dim=32, n_additional_feat=0, drop_prob=0.2, class_names=None,
                  backbone="resnet18", n_heads=1, n_gat_layers=1, backbone_state_dict=None, roi_op="pool",
                  sampling_ratio=2, roi_aligned=False, backbone_layers=1, edge_geometry=False, attention="gat",
-                 attention_dropout=0.0):
+                 attention_dropout=0.0, page_context_dim=0):
         """The first nine arguments exactly as the reference's CoVA (models.py:10-34; called positionally
         at main.py:122-132).  Keyword-only-in-practice extensions, whose defaults are the reference's
         model: ``backbone`` 'resnet18' | 'resnet50' (torchvision ``children()[:-5]`` of either),
@@ -458,7 +510,12 @@ class CoVA(nn.Module):
         [1, hidden_dim / n_heads], so checkpoints of the two modes do not load into each other.
         ``attention_dropout=p`` (0 <= p < 1): dropout on the attention coefficients of every head in train mode
         (GraphAttentionLayer); the masks follow seed_dropout() like the decoder's, from streams of their own.  No weights:
-        the state_dict is unchanged; with p = 0 the module list is too."""
+        the state_dict is unchanged; with p = 0 the module list is too.
+        ``page_context_dim=G`` (0 <= G <= 512; independent of ``use_context``): a PageReadout of the own features gives every
+        box G more columns, the attention-pooled vector of its page (``page_readout.*``, between ``gat`` and ``decoder``
+        in the state_dict); the pages are read off the page column of ``bboxes`` and the page count of ``images``.  With 0 the
+        module list, the state_dict and every launch are unchanged."""
+        page_context_dim = check_page_context_dim(page_context_dim)
         check_backbone_layers(backbone, backbone_layers)
         check_attention(attention)
         attention_dropout = check_attention_dropout(attention_dropout)
@@ -518,7 +575,10 @@ class CoVA(nn.Module):
             else:
                 self.gat = MultiHeadGraphAttention(self.n_feat, self.hidden_dim, n_heads, n_gat_layers, edge_geometry,
                                                    attention, attention_dropout)
-        self.n_total_feat = self.n_feat + (self.hidden_dim if self.use_context else 0)
+        self.page_context_dim = page_context_dim
+        if page_context_dim > 0:
+            self.page_readout = PageReadout(self.n_feat, page_context_dim)
+        self.n_total_feat = self.n_feat + (self.hidden_dim if self.use_context else 0) + page_context_dim
         self.decoder = nn.Sequential(nn.Dropout(drop_prob),
                                      nn.Linear(self.n_total_feat, self.n_total_feat),
                                      nn.BatchNorm1d(self.n_total_feat), nn.ReLU(),
@@ -532,7 +592,8 @@ class CoVA(nn.Module):
                          n_heads=n_heads, n_gat_layers=n_gat_layers, roi_op=roi_op,
                          sampling_ratio=int(sampling_ratio), roi_aligned=bool(roi_aligned),
                          backbone_layers=backbone_layers, edge_geometry=bool(edge_geometry) and bool(use_context),
-                         attention=attention, attention_dropout=attention_dropout if use_context else 0.0)
+                         attention=attention, attention_dropout=attention_dropout if use_context else 0.0,
+                         page_context_dim=page_context_dim)
         self._param_keys = [k for k, _ in self.named_parameters()]
         self._conv_keys = [k for k in self._param_keys if k.startswith("convnet.")]
         self._bbox_keys = [k for k in self._param_keys if k.startswith("bbox_feat_encoder.")]

@@ -21,7 +21,7 @@ import os
 import torch
 
 from . import engine
-from .weights import check_attention_dropout, state_dict_spec
+from .weights import PAGE_READOUT_KEYS, check_attention_dropout, check_page_context_dim, state_dict_spec
 
 _BUF_SUFFIX = ("running_mean", "running_var", "num_batches_tracked")
 
@@ -326,11 +326,14 @@ class HotPathTrainer:
         self.cfg = dict(cfg)
         if "attention_dropout" in cfg:          # (no weights: not an argument of state_dict_spec)
             self.cfg["attention_dropout"] = check_attention_dropout(cfg["attention_dropout"])
+        if "page_context_dim" in cfg:
+            self.cfg["page_context_dim"] = check_page_context_dim(cfg["page_context_dim"])
+        self._check_page_readout(state_dict)        # (before any device work)
         self.device = torch.device(device)
         spec = state_dict_spec(**{k: cfg[k] for k in ("roi_output_size", "n_classes", "use_context",
                                                      "hidden_dim", "bbox_hidden_dim", "n_additional_feat",
                                                      "backbone", "n_heads", "n_gat_layers", "backbone_layers",
-                                                     "edge_geometry", "attention")
+                                                     "edge_geometry", "attention", "page_context_dim")
                                   if k in cfg})
         pshapes = OrderedDict((k, s) for k, s in spec if is_param_key(k))
         self.pbucket = FlatBucket(pshapes, self.device)
@@ -380,6 +383,24 @@ class HotPathTrainer:
                                  "a checkpoint loads into the attention mode it was trained with only"
                                  % (mode, k, tuple(p.shape), tuple(v.shape),
                                     " (attention=%r)" % other if other and other != mode else ""))
+
+    def _check_page_readout(self, state_dict):
+        """A checkpoint trained without the page readout lacks the ``page_readout.*`` entries (and its decoder is narrower),
+        one trained with it carries them: name the option instead of failing on a key or a tensor size."""
+        G = self.cfg.get("page_context_dim", 0)
+        have = [k for k in PAGE_READOUT_KEYS if k in state_dict]
+        if G > 0 and len(have) < len(PAGE_READOUT_KEYS):
+            raise ValueError("this trainer was configured with page_context_dim=%d, the state_dict lacks %s: a checkpoint "
+                             "loads into the page_context_dim it was trained with only"
+                             % (G, [k for k in PAGE_READOUT_KEYS if k not in have]))
+        if G == 0 and have:
+            raise ValueError("this trainer was configured without a page readout (page_context_dim=0), the state_dict "
+                             "holds %s: a checkpoint loads into the page_context_dim it was trained with only" % have)
+        w = state_dict.get(PAGE_READOUT_KEYS[0]) if G > 0 else None
+        if torch.is_tensor(w) and (w.dim() != 2 or w.shape[0] != G):
+            raise ValueError("this trainer was configured with page_context_dim=%d, the state_dict's %s has shape %s "
+                             "(page_context_dim=%s)" % (G, PAGE_READOUT_KEYS[0], tuple(w.shape),
+                                                        w.shape[0] if w.dim() == 2 else "?"))
 
     def _flat_buffers(self, spec):
         """Live BatchNorm buffers of an averaging trainer -> {key: view}: ``bbucket`` (float32, running_mean /
@@ -786,6 +807,7 @@ class HotPathTrainer:
         With ``average=`` the average restarts from what was loaded, as reset_average() does; to resume an average,
         load the state dict first and the optimizer state (which carries the average) after it."""
         self._not_averaged("load_state_dict")
+        self._check_page_readout(state_dict)
         missing = [k for k in list(self.params) + list(self.buffers) if k not in state_dict]
         # sizes are part of the validation every rank agrees on BEFORE any copy / broadcast: a tensor of the wrong size on
         # one rank raising inside copy_ would leave the other ranks blocked in dist.broadcast
@@ -968,7 +990,8 @@ class HotPathTrainer:
             logits, sv = engine.model_fwd(self.cfg, self.params, self.buffers, batch.get("images"),
                                           batch["bboxes"], batch["additional_feats"],
                                           batch["context_indices"], self.modes, (base, base + 1), masks,
-                                          plan=self.plan, visual_feats=vis, page_size=batch.get("page_size"))
+                                          plan=self.plan, visual_feats=vis, page_size=batch.get("page_size"),
+                                          page_start=batch.get("page_start"))
             if opts is None:
                 loss, dl, pred = engine.ce_sum(logits, batch["labels"])
             else:
@@ -1173,7 +1196,7 @@ class HotPathTrainer:
         logits, _ = engine.model_fwd(self.cfg, self.params, self.buffers, batch.get("images"),
                                      batch["bboxes"], batch["additional_feats"],
                                      batch["context_indices"], False, save=False, visual_feats=vis,
-                                     page_size=batch.get("page_size"))
+                                     page_size=batch.get("page_size"), page_start=batch.get("page_start"))
         _, _, pred = engine.ce_sum(logits, None, want_grad=False)
         return logits, pred
 

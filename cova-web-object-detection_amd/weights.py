@@ -35,6 +35,18 @@ def check_attention_dropout(p):
     return float(p)
 
 
+PAGE_CONTEXT_MAX = 512               # channels of the page readout's vector (RO_MAX_G of csrc/readout.hip)
+PAGE_READOUT_KEYS = ("page_readout.W.weight", "page_readout.attention_layer.weight", "page_readout.attention_layer.bias")
+
+
+def check_page_context_dim(g):
+    """Width of the page readout's vector (cova_page_readout_fwd): an int in [0, 512], 0 = no readout -> int."""
+    if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or not 0 <= g <= PAGE_CONTEXT_MAX:
+        raise ValueError("page_context_dim must be an integer in [0, %d] (0: no page readout), got %r"
+                         % (PAGE_CONTEXT_MAX, g))
+    return int(g)
+
+
 def attention_of(weight, D, prefix="gat."):
     """The scoring mode an ``attention_layer.weight`` belongs to, by its width: [1, 2D] is 'gat', [1, D] is 'gatv2'."""
     width = int(weight.shape[-1]) if weight.dim() else -1
@@ -86,7 +98,7 @@ def gat_prefixes(n_heads=1, n_gat_layers=1):
 
 def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=384,
                     bbox_hidden_dim=32, n_additional_feat=0, backbone="resnet18", n_heads=1,
-                    n_gat_layers=1, backbone_layers=1, edge_geometry=False, attention="gat"):
+                    n_gat_layers=1, backbone_layers=1, edge_geometry=False, attention="gat", page_context_dim=0):
     """Ordered (key, shape) list, identical to ``reference CoVA(...).state_dict()`` for the defaults.
 
     Extensions (BASELINE.json configs[2], configs[4]; absent from the reference, defaults keep its
@@ -99,9 +111,13 @@ def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidde
     ``edge_geometry=True`` = one ``edge_layer.weight`` [1, 8] per attention head, behind its ``attention_layer.bias`` (W_i and
     W_j stay adjacent): the weights of the relative-geometry term of the attention score (cova_edge_geometry);
     ``attention="gatv2"`` = every ``attention_layer.weight`` is [1, hidden_dim/n_heads] instead of [1, 2 hidden_dim/n_heads]
-    (the GATv2 score a . LeakyReLU(Wh_i + Wh_j) + b, cova_gat2_fwd): the shape only, keys and their order are unchanged."""
+    (the GATv2 score a . LeakyReLU(Wh_i + Wh_j) + b, cova_gat2_fwd): the shape only, keys and their order are unchanged;
+    ``page_context_dim=G`` > 0 = the page readout (cova_page_readout_fwd; independent of ``use_context``): behind the GAT's
+    entries and in front of the decoder's, ``page_readout.W.weight`` [G, n_feat], ``page_readout.attention_layer.weight``
+    [1, G] and ``page_readout.attention_layer.bias`` [1]; the decoder is G columns wider."""
     check_backbone_layers(backbone, backbone_layers)
     check_attention(attention)
+    page_context_dim = check_page_context_dim(page_context_dim)
     c = BACKBONE_CHANNELS
     spec = [("convnet.0.weight", (c, 3, 7, 7))]
     spec += _bn_entries("convnet.1.", c)
@@ -160,6 +176,10 @@ def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidde
                 if edge_geometry:
                     spec.append((p + "edge_layer.weight", (1, EDGE_FEATURES)))
         n_total += hidden_dim
+    if page_context_dim > 0:
+        spec += [(PAGE_READOUT_KEYS[0], (page_context_dim, n_feat)), (PAGE_READOUT_KEYS[1], (1, page_context_dim)),
+                 (PAGE_READOUT_KEYS[2], (1,))]
+        n_total += page_context_dim
     spec += [("decoder.1.weight", (n_total, n_total)), ("decoder.1.bias", (n_total,))]
     spec += _bn_entries("decoder.2.", n_total)
     spec += [("decoder.5.weight", (n_classes, n_total)), ("decoder.5.bias", (n_classes,))]

@@ -689,6 +689,37 @@ int cova_page_rank_loss_bwd(const float *logits, const int64_t *labels, const in
                             const double *lists, const double *acc_total, double rank_weight, int reduction_mean,
                             const float *grad_scale /*nullable*/, float *loss_inout /*nullable*/,
                             float *dlogits /*nullable*/, int accumulate, void *stream);
+/* ---- page readout (readout.hip; opt-in: CoVA(page_context_dim=G); Li et al. 2016, PyG AttentionalAggregation) ----
+ * One attention-pooled vector per page, handed to every box of the page.  P [N, G] (rows at P + n*ldp) are the projected
+ * own features; page p owns rows [s_p, e_p), clamped as for cova_hard_negative_select above (page_start DEVICE int64 [B+1]).
+ *   u_i = att_w . P_i + att_b[0],  e_i = u_i > 0 ? u_i : alpha * u_i   (u == +-0 takes the alpha branch, as cova_gat2_fwd)
+ *   beta_i = exp(e_i - max_p e) / sum_p exp(e_j - max_p e),  r_p = sum_{i in p} beta_i P_i,  out[i, 0:G] = r_page(i)
+ * cova_page_readout_fwd writes u [N], beta [N], r [B, G] and the rows out + n*ldo of every box of a page; an empty page
+ * writes nothing (its row of r included), rows outside [page_start[0], page_start[B]) are not written.
+ * cova_page_readout_bwd, given g = dL/dout (rows at g + n*ldg) and gr_p = sum_{i in p} g_i:
+ *   de_i = beta_i (gr_p . P_i - gr_p . r_p),  du_i = de_i * (u_i > 0 ? 1 : alpha),  dP_i = beta_i gr_p + du_i att_w,
+ *   d_att_w = sum_i du_i P_i [G],  d_att_b = sum_i du_i [1]
+ * writes dP (rows at dP + n*lddp) of every box of a page and d_att_w / d_att_b through per-page partials in ws
+ * (cova_page_readout_workspace_floats(B, G) = B * (G + 1) floats; 0 for B <= 0 or G outside [1, 512]), folded over pages in
+ * ascending order by a second launch.
+ * A block of sixteen waves per page; waves stride over the page's rows, lanes over channels: float4 chunks when G % 4 == 0
+ * and every base and leading dimension is 16-byte aligned, scalar otherwise.  All sums are f32 in a fixed order that is a
+ * function of the page's own row count and G alone: a dot product is a lane's channels ascending as one fma chain, then
+ * the xor butterfly (offsets 32 .. 1); the maximum is per wave over rows w, w + 16, ... (f32 compares), then waves 0..15;
+ * the softmax denominator is thread t over rows t, t + 1024, ..., the butterfly, then the tree of adjacent pairs over the
+ * waves, ((w0 + w1) + (w2 + w3)) + ((w4 + w5) + (w6 + w7)) ...; r_p, gr_p and the d_att partials are per wave over rows w,
+ * w + 16, ... in turn, then the same tree.  So reruns are bit-identical,
+ * a page's u, beta, r, out and dP keep their bits whatever other pages share the batch, and nothing depends on an atomic
+ * or a host read.  LDS is bounded by G and the block size: a page of any length runs.
+ * 1 <= G <= 512, N >= 0, B >= 0, ld* >= G, else COVA_ERR_BAD_ARG before anything is launched; N == 0 or B == 0 launches
+ * nothing and needs no pointer; otherwise a NULL operand is COVA_ERR_BAD_ARG.  Forward: one launch; backward: two. */
+int cova_page_readout_workspace_floats(int B, int G);
+int cova_page_readout_fwd(const float *P, int ldp, const float *att_w /*[G]*/, const float *att_b /*[1]*/,
+                          const int64_t *page_start /*[B+1]*/, int B, int N, int G, float alpha, float *u /*[N]*/,
+                          float *beta /*[N]*/, float *r /*[B,G]*/, float *out, int ldo, void *stream);
+int cova_page_readout_bwd(const float *g, int ldg, const float *P, int ldp, const float *u, const float *beta,
+                          const float *r, const float *att_w, const int64_t *page_start, int B, int N, int G, float alpha,
+                          float *dP, int lddp, float *d_att_w /*[G]*/, float *d_att_b /*[1]*/, float *ws, void *stream);
 /* evaluation decision (train.py:131-153): per page and class column, page-local indices of the k
  * highest-scoring boxes, best first; page_start [n_pages+1] are box offsets; out [n_pages,NC,k] */
 int cova_page_class_topk(const float *logits, const int64_t *page_start, int n_pages, int NC, int k,
