@@ -1,5 +1,6 @@
-// Helpers of the matrix-pipe kernels (conv.hip, conv1x1.hip, conv1x1_lin.hip, conv_wino4.hip, conv_wgrad4.hip, gemm.hip):
-// the MFMA wrappers next to common.h's mfma32, the global -> LDS copy and the LDS-only barrier.  One definition each.
+// Helpers of the matrix-pipe kernels (conv.hip, conv1x1.hip, conv1x1_lin.hip, conv_wino4.hip, conv_wgrad4.hip, gemm.hip,
+// page_attn.hip): the MFMA wrappers next to common.h's mfma32, the global -> LDS copy and the LDS-only barrier.  One
+// definition each.
 #pragma once
 #include "bf3.h"
 

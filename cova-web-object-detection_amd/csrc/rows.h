@@ -1,7 +1,7 @@
-// What the row and page kernels (head.hip, loss.hip, rank.hip, mine.hip, eval.hip, decode.hip, readout.hip) promise each
-// other bit for bit: the class limit, the logsumexp of a row, the label predicate, the rows of a page and the ranking order.
-// One definition each; none of them holds a product that feeds a sum, so a file-level fp-contract pragma of the including
-// file has nothing to reach here.
+// What the row and page kernels (head.hip, loss.hip, rank.hip, mine.hip, eval.hip, decode.hip, readout.hip, page_attn.hip)
+// promise each other bit for bit: the class limit, the logsumexp of a row, the label predicate, the rows of a page and the
+// ranking order.  One definition each; none of them holds a product that feeds a sum, so a file-level fp-contract pragma of
+// the including file has nothing to reach here.
 #pragma once
 #include "common.h"
 
@@ -34,7 +34,8 @@ __device__ __forceinline__ int label_state(long long lab, int NC, long long igno
 }
 
 // The rows [base, end) of page p in a flat batch of N rows, from page_start [B + 1].  Who does what with a malformed table:
-//   mine_select_kernel, rank_lists_kernel, readout_fwd_kernel, readout_bwd_kernel (readout.hip)
+//   mine_select_kernel, rank_lists_kernel, readout_fwd_kernel, readout_bwd_kernel (readout.hip), the kernels of
+//   page_attn.hip (pa_block)
 //                                              page_rows(): both ends clamped into [0, N], end >= base
 //   page_joint_decode_kernel                   its own clamp without N: lo >= 0, hi >= lo
 //   eval_page_ranks_kernel, page_class_topk_kernel, rank_bwd_kernel's page search    page_start as it is

@@ -166,7 +166,7 @@ def check_batch(cfg, images, bboxes, additional_feats, context_indices, training
     if N == 1:
         # torch.nn.functional.batch_norm's _verify_batch_size, hit by the first train-mode BatchNorm1d of the forward
         T = (backbone_feat(cfg) + cfg["bbox_hidden_dim"] + A + (cfg["hidden_dim"] if cfg["use_context"] else 0)
-             + cfg.get("page_context_dim", 0))
+             + cfg.get("page_context_dim", 0) + cfg.get("page_attention_dim", 0))
         for width, prefix in ((cfg["bbox_hidden_dim"], "bbox_feat_encoder.1."), (A, "bn_additional_feat."),
                               (T, "decoder.2.")):
             if width and is_train(training, prefix):
@@ -1543,14 +1543,15 @@ def gat_stack_bwd(layers, dcomb, T, N, F, D, params, gout=None):
 
 
 # ------------------------------------------------------------------------------- page readout
-def page_start_of(bboxes, images, page_start=None):
+def page_start_of(bboxes, images, page_start=None, option="page_context_dim"):
     """The pages' row offsets (device int64 [B + 1]) without a host read: the batch's table when given, else from the
-    page column of the page-sorted boxes and the page count of the images (HotPathTrainer._page_start's rule)."""
+    page column of the page-sorted boxes and the page count of the images (HotPathTrainer._page_start's rule).
+    ``option`` names the cfg entry that needs the table in the error of a batch that has neither."""
     if page_start is not None:
         return _check(page_start.contiguous(), torch.int64)
     if images is None:
-        raise ValueError("page_context_dim: a batch without images must carry page_start (the pages' row offsets, "
-                         "int64 [B + 1])")
+        raise ValueError("%s: a batch without images must carry page_start (the pages' row offsets, "
+                         "int64 [B + 1])" % option)
     pages = torch.arange(int(images.shape[0]) + 1, dtype=torch.float32, device=bboxes.device)
     return torch.searchsorted(bboxes[:, 0].contiguous(), pages)
 
@@ -1587,6 +1588,38 @@ def page_readout_bwd(sv, g, ldg, params, dh, lddh, gout=None):
     call("cova_sgemm", 1, 0, G, F, N, dP, G, sv["h"], sv["ldh"], dW, F, None, 0)
     call("cova_sgemm", 0, 0, N, F, G, dP, G, W, F, dh, lddh, None, 1)
     return {prefix + "W.weight": dW, prefix + "attention_layer.weight": daw, prefix + "attention_layer.bias": dab}
+
+
+# ------------------------------------------------------------------------------- page self-attention
+def page_attn_fwd(h, ldh, N, F, page_start, params, heads, out, ldo, prefix="page_attention."):
+    """The page self-attention (cova_page_attn_fwd): [Q | K | V] = h qkv.weight^T by cova_sgemm, then per page and head the
+    softmax of Q_i . K_j / sqrt(dh) over ALL rows j of the page and O_i = sum_j A_ij V_j, written to the rows out + n*ldo
+    (E columns).  h rows at h + n*ldh (F values); ``page_start`` device int64 [B + 1].  -> saved dict for page_attn_bwd
+    (qkv, lse [N, heads] and the output's place: the probabilities are recomputed)."""
+    _check(page_start, torch.int64)
+    W = params[prefix + "qkv.weight"]
+    E, B = W.shape[0] // 3, page_start.shape[0] - 1
+    if W.shape[1] != F or W.shape[0] != 3 * E or E < 1:
+        raise ValueError("%sqkv.weight %s does not fit %d own features" % (prefix, tuple(W.shape), F))
+    qkv = _empty((N, 3 * E), h)
+    call("cova_sgemm", 0, 1, N, 3 * E, F, h, ldh, W, F, qkv, 3 * E, None, 0)
+    lse = _empty((N, heads), h)
+    call("cova_page_attn_fwd", qkv, 3 * E, page_start, B, N, E, heads, out, ldo, lse)
+    return dict(h=h, ldh=ldh, N=N, F=F, E=E, B=B, heads=heads, qkv=qkv, lse=lse, out=out, ldo=ldo, page_start=page_start,
+                prefix=prefix)
+
+
+def page_attn_bwd(sv, g, ldg, params, dh, lddh, gout=None):
+    """g = dL/d(attention columns) (rows at g + n*ldg).  ACCUMULATES dL/dh into dh; returns the weight gradient."""
+    N, F, E, B, prefix = sv["N"], sv["F"], sv["E"], sv["B"], sv["prefix"]
+    W = params[prefix + "qkv.weight"]
+    dqkv = _empty((N, 3 * E), g)
+    call("cova_page_attn_bwd", g, ldg, sv["qkv"], 3 * E, sv["out"], sv["ldo"], sv["lse"], sv["page_start"], B, N, E,
+         sv["heads"], dqkv, 3 * E)
+    dW = _gbuf(gout, prefix + "qkv.weight", (3 * E, F), g)
+    call("cova_sgemm", 1, 0, 3 * E, F, N, dqkv, 3 * E, sv["h"], sv["ldh"], dW, F, None, 0)
+    call("cova_sgemm", 0, 0, N, F, 3 * E, dqkv, 3 * E, W, F, dh, lddh, None, 1)
+    return {prefix + "qkv.weight": dW}
 
 
 # ------------------------------------------------------------------------------- decoder
@@ -1657,7 +1690,8 @@ def decoder_bwd(sv, dlogits, params, gout=None):
 def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_indices, training,
               seeds=(0, 0), masks=None, save=True, plan=None, visual_feats=None, page_size=None, page_start=None):
     """CoVA.forward (models.py:94-122) -> (logits [N,n_classes], saved-for-backward or None).
-    ``page_start`` (device int64 [B + 1], the pages' row offsets) is read by cfg["page_context_dim"] only: the batch's table
+    ``page_start`` (device int64 [B + 1], the pages' row offsets) is read by cfg["page_context_dim"] and
+    cfg["page_attention_dim"] only: the batch's table
     when given, else derived on the device from the page column of ``bboxes`` and the page count of ``images``
     (page_start_of); a batch without either raises ValueError.
     ``page_size`` = (height, width) of the pages, read by cfg["edge_geometry"] only: by default ``images.shape[2:]``; a batch
@@ -1676,16 +1710,16 @@ def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_in
     Hd, A = cfg["bbox_hidden_dim"], cfg["n_additional_feat"]
     F = n_vis + Hd + A
     D = cfg["hidden_dim"] if cfg["use_context"] else 0
-    G = cfg.get("page_context_dim", 0)
-    T = F + D + G
-    if G > 0:
-        page_start = page_start_of(bboxes, images, page_start)
+    G, E = cfg.get("page_context_dim", 0), cfg.get("page_attention_dim", 0)
+    T = F + D + G + E
+    if G > 0 or E > 0:
+        page_start = page_start_of(bboxes, images, page_start, "page_context_dim" if G > 0 else "page_attention_dim")
     align = cfg.get("roi_op", "pool") == "align"
     save_conv = save and (plan is None or "convstack" in plan)
     feat, sv_conv = convstack_fwd(images, params, buffers, training, save_conv, lazy_out=not align)
     comb = _empty((N, T), images)
     scale = cfg.get("spatial_scale") or feat.shape[1] / images.shape[2]   # models.py:56
-    sv = dict(cfg=cfg, N=N, F=F, D=D, G=G, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=sv_conv, comb=comb,
+    sv = dict(cfg=cfg, N=N, F=F, D=D, G=G, E=E, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=sv_conv, comb=comb,
               page_size=page_size or cfg.get("page_size") or tuple(images.shape[2:]), page_start=page_start)
     if align:
         sv["roi"] = roialign_fwd(feat, bboxes, (PH, PW), scale, cfg.get("sampling_ratio", 2),
@@ -1698,7 +1732,7 @@ def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_in
 def _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks, save, sv):
     """Everything behind the visual columns of ``sv["comb"]``: positional encoder, additional features, GAT, decoder."""
     N, F, D, T, n_vis, Hd, A, comb = (sv[k] for k in ("N", "F", "D", "T", "n_vis", "Hd", "A", "comb"))
-    G = sv.get("G", 0)
+    G, E = sv.get("G", 0), sv.get("E", 0)
     if Hd > 0:
         sv["bbox"] = bbox_fwd(bboxes, params, buffers, training, comb[:, n_vis:], T)
     if A > 0:
@@ -1716,6 +1750,9 @@ def _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, t
                                   cfg.get("attention", "gat"), cfg.get("attention_dropout", 0.0), seeds[0], training)
     if G > 0:
         sv["readout"] = page_readout_fwd(comb, T, N, F, sv["page_start"], params, comb[:, F + D:], T)
+    if E > 0:
+        sv["page_attn"] = page_attn_fwd(comb, T, N, F, sv["page_start"], params, cfg.get("page_attention_heads", 1),
+                                        comb[:, F + D + G:], T)
     logits, sv["dec"] = decoder_fwd(comb, N, T, params, buffers, training, cfg["drop_prob"], seeds,
                                     masks)
     return logits, (sv if save else None)
@@ -1757,12 +1794,12 @@ def _model_fwd_cached(cfg, params, buffers, bboxes, additional_feats, context_in
     Hd, A = cfg["bbox_hidden_dim"], cfg["n_additional_feat"]
     F = n_vis + Hd + A
     D = cfg["hidden_dim"] if cfg["use_context"] else 0
-    G = cfg.get("page_context_dim", 0)
-    T = F + D + G
-    if G > 0:
-        page_start = page_start_of(bboxes, None, page_start)
+    G, E = cfg.get("page_context_dim", 0), cfg.get("page_attention_dim", 0)
+    T = F + D + G + E
+    if G > 0 or E > 0:
+        page_start = page_start_of(bboxes, None, page_start, "page_context_dim" if G > 0 else "page_attention_dim")
     comb = _empty((N, T), bboxes)
-    sv = dict(cfg=cfg, N=N, F=F, D=D, G=G, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=None, roi=None, comb=comb,
+    sv = dict(cfg=cfg, N=N, F=F, D=D, G=G, E=E, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=None, roi=None, comb=comb,
               page_size=page_size or cfg.get("page_size"), page_start=page_start)
     call("cova_feat_rows_gather", table, table.shape[0], n_vis, row_ids, N, comb, T)
     return _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks, save, sv)
@@ -1784,6 +1821,8 @@ def model_bwd(sv, dlogits, params, gout=None, after_head=None, want_dimg=False, 
         grads.update(gat_stack_bwd(sv["gat"], dcomb, T, N, F, D, params, gout))
     if sv.get("G", 0) > 0:               # after the GAT's: both accumulate into dcomb[:, :F], in this order
         grads.update(page_readout_bwd(sv["readout"], dcomb[:, F + D:], T, params, dcomb, T, gout))
+    if sv.get("E", 0) > 0:               # after the readout's: the third to accumulate into dcomb[:, :F], in this order
+        grads.update(page_attn_bwd(sv["page_attn"], dcomb[:, F + D + sv.get("G", 0):], T, params, dcomb, T, gout))
     if A > 0 and (plan is None or "addl" in plan):
         st = sv["addl"]
         dz = _empty((N, A), dcomb)

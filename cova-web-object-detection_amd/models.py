@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from . import engine
 from .weights import (EDGE_FEATURES, attention_of, backbone_channels, check_attention, check_attention_dropout,
-                      check_backbone_layers, check_page_context_dim)
+                      check_backbone_layers, check_page_attention, check_page_context_dim)
 
 GAT_MAX_K = engine.GAT_MAX_K
 LOSS_MAX_CLASSES = engine.LOSS_MAX_CLASSES
@@ -485,12 +485,61 @@ class PageReadout(nn.Module):
         return (out, beta) if return_attn_wts else out
 
 
+class _PageAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, layer, h, page_start, W):
+        h = _f32c(h)
+        N, F = h.shape
+        params = {"page_attention.qkv.weight": W.detach()}
+        out = torch.empty((N, layer.dim), device=h.device)
+        ctx.sv = engine.page_attn_fwd(h, F, N, F, _i64c(page_start), params, layer.heads, out, layer.dim)
+        ctx.params = params
+        ctx.mark_non_differentiable(ctx.sv["lse"])
+        return out, ctx.sv["lse"]
+
+    @staticmethod
+    def backward(ctx, g, _glse):
+        sv = ctx.sv
+        dh = torch.zeros((sv["N"], sv["F"]), device=g.device)          # page_attn_bwd accumulates
+        grads = engine.page_attn_bwd(sv, g.contiguous(), sv["E"], ctx.params, dh, sv["F"])
+        return None, dh, None, grads["page_attention.qkv.weight"]
+
+
+class PageAttention(nn.Module):
+    """Extension: multi-head scaled dot-product self-attention (Vaswani et al. 2017) restricted to pages.  ``[Q | K | V] =
+    qkv(h)`` (Linear(in_features, 3 dim), no bias); for a box i and a head of ``dim / heads`` columns, ``A_ij`` = softmax
+    over ALL boxes j of i's page of ``Q_i . K_j / sqrt(dim / heads)`` and ``O_i = sum_j A_ij V_j``.  No output projection
+    (the decoder's first Linear follows), no dropout, no geometry term.  ``forward(h [N, in_features], page_start int64
+    [B + 1])`` -> ``O [N, dim]`` (and ``lse [N, heads]``, the log-sum-exp of each row's scores, with ``return_lse``); one
+    autograd node over cova_page_attn_fwd / cova_page_attn_bwd."""
+
+    def __init__(self, in_features, dim, heads=1):
+        super().__init__()
+        self.in_features = in_features
+        self.dim, self.heads = check_page_attention(dim, heads)
+        if self.dim < 1:
+            raise ValueError("PageAttention needs dim >= 4")
+        self.qkv = nn.Linear(in_features, 3 * self.dim, bias=False)
+
+    def forward(self, h, page_start, return_lse=False):
+        _require_cuda(h, page_start)
+        if h.dim() != 2 or h.shape[1] != self.in_features:
+            raise RuntimeError("expected h [N, %d], got %s" % (self.in_features, tuple(h.shape)))
+        if page_start.dim() != 1 or page_start.shape[0] < 1 or page_start.is_floating_point():
+            raise ValueError("page_start must hold B + 1 integer row offsets, got shape %s" % (tuple(page_start.shape),))
+        if h.shape[0] == 0:
+            out, lse = h.new_empty((0, self.dim)), h.new_empty((0, self.heads))
+        else:
+            out, lse = _PageAttentionFn.apply(self, h, page_start, self.qkv.weight)
+        return (out, lse) if return_lse else out
+
+
 class CoVA(nn.Module):
     def __init__(self, roi_output_size, img_H, n_classes, use_context=True, hidden_dim=384,
                  bbox_hidden_dim=32, n_additional_feat=0, drop_prob=0.2, class_names=None,
                  backbone="resnet18", n_heads=1, n_gat_layers=1, backbone_state_dict=None, roi_op="pool",
                  sampling_ratio=2, roi_aligned=False, backbone_layers=1, edge_geometry=False, attention="gat",
-                 attention_dropout=0.0, page_context_dim=0):
+                 attention_dropout=0.0, page_context_dim=0, page_attention_dim=0, page_attention_heads=1):
         """The first nine arguments exactly as the reference's CoVA (models.py:10-34; called positionally
         at main.py:122-132).  Keyword-only-in-practice extensions, whose defaults are the reference's
         model: ``backbone`` 'resnet18' | 'resnet50' (torchvision ``children()[:-5]`` of either),
@@ -514,8 +563,14 @@ class CoVA(nn.Module):
         ``page_context_dim=G`` (0 <= G <= 512; independent of ``use_context``): a PageReadout of the own features gives every
         box G more columns, the attention-pooled vector of its page (``page_readout.*``, between ``gat`` and ``decoder``
         in the state_dict); the pages are read off the page column of ``bboxes`` and the page count of ``images``.  With 0 the
-        module list, the state_dict and every launch are unchanged."""
+        module list, the state_dict and every launch are unchanged.
+        ``page_attention_dim=E`` with ``page_attention_heads=Hh`` (0 <= E <= 512, Hh divides E, E / Hh a multiple of 4 in
+        [4, 128]; independent of ``use_context`` and of ``page_context_dim``): a PageAttention of the own features gives
+        every box E more columns behind the readout's, its own attention-weighted view of ALL boxes of its page
+        (``page_attention.qkv.weight``, between ``page_readout`` and ``decoder`` in the state_dict).  ``edge_geometry`` and
+        ``attention_dropout`` belong to the GAT and do not reach this layer.  With 0 nothing changes."""
         page_context_dim = check_page_context_dim(page_context_dim)
+        page_attention_dim, page_attention_heads = check_page_attention(page_attention_dim, page_attention_heads)
         check_backbone_layers(backbone, backbone_layers)
         check_attention(attention)
         attention_dropout = check_attention_dropout(attention_dropout)
@@ -578,7 +633,11 @@ class CoVA(nn.Module):
         self.page_context_dim = page_context_dim
         if page_context_dim > 0:
             self.page_readout = PageReadout(self.n_feat, page_context_dim)
-        self.n_total_feat = self.n_feat + (self.hidden_dim if self.use_context else 0) + page_context_dim
+        self.page_attention_dim, self.page_attention_heads = page_attention_dim, page_attention_heads
+        if page_attention_dim > 0:
+            self.page_attention = PageAttention(self.n_feat, page_attention_dim, page_attention_heads)
+        self.n_total_feat = (self.n_feat + (self.hidden_dim if self.use_context else 0) + page_context_dim
+                             + page_attention_dim)
         self.decoder = nn.Sequential(nn.Dropout(drop_prob),
                                      nn.Linear(self.n_total_feat, self.n_total_feat),
                                      nn.BatchNorm1d(self.n_total_feat), nn.ReLU(),
@@ -593,7 +652,8 @@ class CoVA(nn.Module):
                          sampling_ratio=int(sampling_ratio), roi_aligned=bool(roi_aligned),
                          backbone_layers=backbone_layers, edge_geometry=bool(edge_geometry) and bool(use_context),
                          attention=attention, attention_dropout=attention_dropout if use_context else 0.0,
-                         page_context_dim=page_context_dim)
+                         page_context_dim=page_context_dim, page_attention_dim=page_attention_dim,
+                         page_attention_heads=page_attention_heads)
         self._param_keys = [k for k, _ in self.named_parameters()]
         self._conv_keys = [k for k in self._param_keys if k.startswith("convnet.")]
         self._bbox_keys = [k for k in self._param_keys if k.startswith("bbox_feat_encoder.")]

@@ -21,7 +21,8 @@ import os
 import torch
 
 from . import engine
-from .weights import PAGE_READOUT_KEYS, check_attention_dropout, check_page_context_dim, state_dict_spec
+from .weights import (PAGE_ATTENTION_KEY, PAGE_READOUT_KEYS, check_attention_dropout, check_page_attention,
+                      check_page_context_dim, state_dict_spec)
 
 _BUF_SUFFIX = ("running_mean", "running_var", "num_batches_tracked")
 
@@ -328,12 +329,17 @@ class HotPathTrainer:
             self.cfg["attention_dropout"] = check_attention_dropout(cfg["attention_dropout"])
         if "page_context_dim" in cfg:
             self.cfg["page_context_dim"] = check_page_context_dim(cfg["page_context_dim"])
+        if "page_attention_dim" in cfg or "page_attention_heads" in cfg:
+            self.cfg["page_attention_dim"], self.cfg["page_attention_heads"] = check_page_attention(
+                cfg.get("page_attention_dim", 0), cfg.get("page_attention_heads", 1))
         self._check_page_readout(state_dict)        # (before any device work)
+        self._check_page_attention(state_dict)
         self.device = torch.device(device)
         spec = state_dict_spec(**{k: cfg[k] for k in ("roi_output_size", "n_classes", "use_context",
                                                      "hidden_dim", "bbox_hidden_dim", "n_additional_feat",
                                                      "backbone", "n_heads", "n_gat_layers", "backbone_layers",
-                                                     "edge_geometry", "attention", "page_context_dim")
+                                                     "edge_geometry", "attention", "page_context_dim",
+                                                     "page_attention_dim", "page_attention_heads")
                                   if k in cfg})
         pshapes = OrderedDict((k, s) for k, s in spec if is_param_key(k))
         self.pbucket = FlatBucket(pshapes, self.device)
@@ -401,6 +407,22 @@ class HotPathTrainer:
             raise ValueError("this trainer was configured with page_context_dim=%d, the state_dict's %s has shape %s "
                              "(page_context_dim=%s)" % (G, PAGE_READOUT_KEYS[0], tuple(w.shape),
                                                         w.shape[0] if w.dim() == 2 else "?"))
+
+    def _check_page_attention(self, state_dict):
+        """As _check_page_readout, for ``page_attention.qkv.weight``: a checkpoint of the other kind names the option."""
+        E = self.cfg.get("page_attention_dim", 0)
+        w = state_dict.get(PAGE_ATTENTION_KEY)
+        if E > 0 and w is None:
+            raise ValueError("this trainer was configured with page_attention_dim=%d, the state_dict lacks %s: a checkpoint "
+                             "loads into the page_attention_dim it was trained with only" % (E, PAGE_ATTENTION_KEY))
+        if E == 0 and w is not None:
+            raise ValueError("this trainer was configured without page attention (page_attention_dim=0), the state_dict "
+                             "holds %s: a checkpoint loads into the page_attention_dim it was trained with only"
+                             % PAGE_ATTENTION_KEY)
+        if E > 0 and torch.is_tensor(w) and (w.dim() != 2 or w.shape[0] != 3 * E):
+            raise ValueError("this trainer was configured with page_attention_dim=%d, the state_dict's %s has shape %s "
+                             "(page_attention_dim=%s)" % (E, PAGE_ATTENTION_KEY, tuple(w.shape),
+                                                          w.shape[0] // 3 if w.dim() == 2 else "?"))
 
     def _flat_buffers(self, spec):
         """Live BatchNorm buffers of an averaging trainer -> {key: view}: ``bbucket`` (float32, running_mean /
@@ -808,6 +830,7 @@ class HotPathTrainer:
         load the state dict first and the optimizer state (which carries the average) after it."""
         self._not_averaged("load_state_dict")
         self._check_page_readout(state_dict)
+        self._check_page_attention(state_dict)
         missing = [k for k in list(self.params) + list(self.buffers) if k not in state_dict]
         # sizes are part of the validation every rank agrees on BEFORE any copy / broadcast: a tensor of the wrong size on
         # one rank raising inside copy_ would leave the other ranks blocked in dist.broadcast

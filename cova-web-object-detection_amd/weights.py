@@ -47,6 +47,33 @@ def check_page_context_dim(g):
     return int(g)
 
 
+PAGE_ATTENTION_MAX = 512             # channels of the page attention's output (PA_MAX_E of csrc/page_attn.hip)
+PAGE_ATTENTION_MAX_HEAD = 128        # columns of one head (PA_MAX_DH)
+PAGE_ATTENTION_KEY = "page_attention.qkv.weight"
+
+
+def check_page_attention(e, heads=1):
+    """Width and head count of the page self-attention (cova_page_attn_fwd): E an int in [0, 512] (0 = off), Hh an int >= 1
+    that divides E, the head width E / Hh a multiple of 4 in [4, 128] -> (E, Hh)."""
+    for name, v in (("page_attention_dim", e), ("page_attention_heads", heads)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+    e, heads = int(e), int(heads)
+    if not 0 <= e <= PAGE_ATTENTION_MAX:
+        raise ValueError("page_attention_dim must be an integer in [0, %d] (0: no page attention), got %r"
+                         % (PAGE_ATTENTION_MAX, e))
+    if heads < 1:
+        raise ValueError("page_attention_heads must be at least 1, got %r" % (heads,))
+    if e > 0:
+        if e % heads:
+            raise ValueError("page_attention_heads=%d does not divide page_attention_dim=%d" % (heads, e))
+        dh = e // heads
+        if dh % 4 or not 4 <= dh <= PAGE_ATTENTION_MAX_HEAD:
+            raise ValueError("page_attention_dim / page_attention_heads = %d: the head width must be a multiple of 4 in "
+                             "[4, %d]" % (dh, PAGE_ATTENTION_MAX_HEAD))
+    return e, heads
+
+
 def attention_of(weight, D, prefix="gat."):
     """The scoring mode an ``attention_layer.weight`` belongs to, by its width: [1, 2D] is 'gat', [1, D] is 'gatv2'."""
     width = int(weight.shape[-1]) if weight.dim() else -1
@@ -98,7 +125,8 @@ def gat_prefixes(n_heads=1, n_gat_layers=1):
 
 def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=384,
                     bbox_hidden_dim=32, n_additional_feat=0, backbone="resnet18", n_heads=1,
-                    n_gat_layers=1, backbone_layers=1, edge_geometry=False, attention="gat", page_context_dim=0):
+                    n_gat_layers=1, backbone_layers=1, edge_geometry=False, attention="gat", page_context_dim=0,
+                    page_attention_dim=0, page_attention_heads=1):
     """Ordered (key, shape) list, identical to ``reference CoVA(...).state_dict()`` for the defaults.
 
     Extensions (BASELINE.json configs[2], configs[4]; absent from the reference, defaults keep its
@@ -114,10 +142,14 @@ def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidde
     (the GATv2 score a . LeakyReLU(Wh_i + Wh_j) + b, cova_gat2_fwd): the shape only, keys and their order are unchanged;
     ``page_context_dim=G`` > 0 = the page readout (cova_page_readout_fwd; independent of ``use_context``): behind the GAT's
     entries and in front of the decoder's, ``page_readout.W.weight`` [G, n_feat], ``page_readout.attention_layer.weight``
-    [1, G] and ``page_readout.attention_layer.bias`` [1]; the decoder is G columns wider."""
+    [1, G] and ``page_readout.attention_layer.bias`` [1]; the decoder is G columns wider;
+    ``page_attention_dim=E`` > 0 = the page self-attention (cova_page_attn_fwd; independent of ``use_context`` and of
+    ``page_context_dim``): behind the readout's entries and in front of the decoder's, ``page_attention.qkv.weight``
+    [3E, n_feat], the same shape for every ``page_attention_heads``; the decoder is E columns wider."""
     check_backbone_layers(backbone, backbone_layers)
     check_attention(attention)
     page_context_dim = check_page_context_dim(page_context_dim)
+    page_attention_dim, page_attention_heads = check_page_attention(page_attention_dim, page_attention_heads)
     c = BACKBONE_CHANNELS
     spec = [("convnet.0.weight", (c, 3, 7, 7))]
     spec += _bn_entries("convnet.1.", c)
@@ -180,6 +212,9 @@ def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidde
         spec += [(PAGE_READOUT_KEYS[0], (page_context_dim, n_feat)), (PAGE_READOUT_KEYS[1], (1, page_context_dim)),
                  (PAGE_READOUT_KEYS[2], (1,))]
         n_total += page_context_dim
+    if page_attention_dim > 0:
+        spec.append((PAGE_ATTENTION_KEY, (3 * page_attention_dim, n_feat)))
+        n_total += page_attention_dim
     spec += [("decoder.1.weight", (n_total, n_total)), ("decoder.1.bias", (n_total,))]
     spec += _bn_entries("decoder.2.", n_total)
     spec += [("decoder.5.weight", (n_classes, n_total)), ("decoder.5.bias", (n_classes,))]

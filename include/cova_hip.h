@@ -720,6 +720,32 @@ int cova_page_readout_fwd(const float *P, int ldp, const float *att_w /*[G]*/, c
 int cova_page_readout_bwd(const float *g, int ldg, const float *P, int ldp, const float *u, const float *beta,
                           const float *r, const float *att_w, const int64_t *page_start, int B, int N, int G, float alpha,
                           float *dP, int lddp, float *d_att_w /*[G]*/, float *d_att_b /*[1]*/, float *ws, void *stream);
+/* ---- page self-attention (page_attn.hip; opt-in: CoVA(page_attention_dim=E, page_attention_heads=Hh)) ----
+ * Multi-head scaled dot-product self-attention restricted to pages.  qkv [N, 3E] (rows at qkv + n*ldq) holds [Q | K | V];
+ * head a owns the columns a*dh .. a*dh + dh of each third, dh = E / Hh.  Page p owns rows [s_p, e_p), clamped as for
+ * cova_page_readout_fwd above (page_start DEVICE int64 [B+1]).  For a row i of page p and a head a:
+ *   s_ij = (Q_i . K_j) * (1 / sqrt(dh)) over ALL rows j of page p (i included),  A_ij = softmax_j s_ij,  O_i = sum_j A_ij V_j
+ * cova_page_attn_fwd writes O (out + n*ldo, E columns) and lse [N, Hh] = max_j s_ij + log sum_j exp(s_ij - max) of every row
+ * of a page; an empty page writes nothing, rows outside [page_start[0], page_start[B]) are not written.  No probability is
+ * stored: cova_page_attn_bwd, given g = dL/dO (rows at g + n*ldg), recomputes A_ij = exp(s_ij - lse_i) and writes
+ *   delta_i = g_i . O_i,  dA_ij = g_i . V_j,  ds_ij = A_ij (dA_ij - delta_i)
+ *   dQ_i = sum_j ds_ij K_j / sqrt(dh),  dK_j = sum_i ds_ij Q_i / sqrt(dh),  dV_j = sum_i A_ij g_i
+ * as [dQ | dK | dV] into dqkv (rows at dqkv + n*lddq) for every row of a page.
+ * Both products of every kernel run on the f32 matrix pipe (v_mfma_f32_16x16x4_f32); a block of four waves per (page, head,
+ * tile of 64 rows) walks the page's other rows through LDS in ascending tiles (two passes in the forward: maximum, then
+ * sums), so a page of any length runs.  Every summation order is a function of the page's own row count, E and Hh alone
+ * (page_attn.hip's header lists them): reruns are bit-identical, a page's rows keep their bits whatever other pages share
+ * the batch, and nothing depends on an atomic, a host read or a workspace.
+ * out, g and dqkv rows may sit at any leading dimension and alignment (16-byte stores where aligned, scalar otherwise); qkv
+ * must be 16-byte aligned with ldq % 4 == 0.  1 <= Hh, Hh divides E, E <= 512, dh a multiple of 4 in [4, 128], N >= 0,
+ * B >= 0, ldq >= 3E, lddq >= 3E, ldo >= E, ldg >= E, else COVA_ERR_BAD_ARG before anything is launched; N == 0 or B == 0
+ * launches nothing and needs no pointer; otherwise a NULL operand is COVA_ERR_BAD_ARG.  Forward: one launch; backward: two
+ * (query side, key side). */
+int cova_page_attn_fwd(const float *qkv, int ldq, const int64_t *page_start /*[B+1]*/, int B, int N, int E, int Hh,
+                       float *out, int ldo, float *lse /*[N,Hh]*/, void *stream);
+int cova_page_attn_bwd(const float *g, int ldg, const float *qkv, int ldq, const float *out, int ldo,
+                       const float *lse /*[N,Hh]*/, const int64_t *page_start /*[B+1]*/, int B, int N, int E, int Hh,
+                       float *dqkv, int lddq, void *stream);
 /* evaluation decision (train.py:131-153): per page and class column, page-local indices of the k
  * highest-scoring boxes, best first; page_start [n_pages+1] are box offsets; out [n_pages,NC,k] */
 int cova_page_class_topk(const float *logits, const int64_t *page_start, int n_pages, int NC, int k,
