@@ -10,7 +10,8 @@
 //   edge_geometry_kernel the eight relative-geometry features of every edge of a context table (cova_edge_geometry), one
 //                        thread per slot.
 // Integer compares of float bit patterns, every float operation rounded on its own: bit-deterministic, equal to numpy.
-#include "common.h"
+// knn_box and edge_features live in geometry.h: page_attn.hip forms the same feature bits for its geometry bias.
+#include "geometry.h"
 #include <limits.h>
 
 namespace {
@@ -34,12 +35,6 @@ __device__ __forceinline__ unsigned long long knn_key(const float4 a, const floa
     const float ex2 = ex * ex, ey2 = ey * ey;
     const float ctr2 = ex2 + ey2;
     return ((unsigned long long)__float_as_uint(gap2) << 32) | (unsigned long long)__float_as_uint(ctr2);
-}
-
-__device__ __forceinline__ float4 knn_box(const float *__restrict__ bboxes, long long g)
-{
-    const float *r = bboxes + g * 5;
-    return make_float4(r[1], r[2], r[3], r[4]);
 }
 
 __global__ __launch_bounds__(KNN_THREADS) void context_knn_kernel(
@@ -113,28 +108,6 @@ __global__ __launch_bounds__(KNN_THREADS) void context_knn_kernel(
         }
         for (int s = r + lane; s < ks; s += 64) row[2 * cs + s] = -1;
     }
-}
-
-// Relative geometry of one edge (include/cova_hip.h, cova_edge_geometry): box a = the node i, box b = its neighbour j, both
-// x1,y1,x2,y2; dj = j - i.  Every operation is rounded on its own (no contraction: tests/edge_oracle.py states the same
-// expressions in numpy float32, parenthesis for parenthesis) and `/` is the correctly rounded division.
-__device__ __forceinline__ void edge_features(const float4 a, const float4 b, float W, float H, int dj, float *f)
-{
-#pragma clang fp contract(off)
-    const float wi = a.z - a.x, hi = a.w - a.y, wj = b.z - b.x, hj = b.w - b.y;
-    f[0] = ((b.x + b.z) - (a.x + a.z)) / (2.f * W);
-    f[1] = ((b.y + b.w) - (a.y + a.w)) / (2.f * H);
-    f[2] = (wj - wi) / ((wj + wi) + 1.f);
-    f[3] = (hj - hi) / ((hj + hi) + 1.f);
-    f[4] = fmaxf(0.f, fmaxf(a.x, b.x) - fminf(a.z, b.z)) / W;      // the gap of knn_key
-    f[5] = fmaxf(0.f, fmaxf(a.y, b.y) - fminf(a.w, b.w)) / H;
-    const float iw = fmaxf(0.f, fminf(a.z, b.z) - fmaxf(a.x, b.x));
-    const float ih = fmaxf(0.f, fminf(a.w, b.w) - fmaxf(a.y, b.y));
-    const float inter = iw * ih;
-    const float ai = wi * hi, aj = wj * hj;
-    const float uni = (ai + aj) - inter;
-    f[6] = uni > 0.f ? inter / uni : 0.f;
-    f[7] = (float)max(-64, min(64, dj)) / 64.f;
 }
 
 // one thread per slot (i, k), grid-stride; a pad (j < 0 or j >= N) writes eight zeros and reads no box

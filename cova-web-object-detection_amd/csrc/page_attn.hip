@@ -32,6 +32,26 @@
 //                          (part_0 + part_1) + (part_2 + part_3) by shuffles (pa_delta_part: both sides call it)
 // A row's own tile-mates never enter its sums, so O, lse and dqkv rows keep their bits whatever other pages share the batch,
 // and reruns are bit-identical.
+//
+// The GEO instantiations (cova_page_attn_fwd_geo / cova_page_attn_bwd_geo) add a relative-geometry
+// bias to every score, formed on the fly from the two boxes of the pair, per head a with eight weights w[a][0..7]:
+//   phi_ij = edge_features(box of the QUERY i, box of the KEY j, W, H, dj = j - i)    geometry.h: cova_edge_geometry's bits
+//   b_ij   = fma chain from +0 over e = 0..7 of w[a][e] * phi_ij[e]
+//   s_ij   = (Q_i . K_j) * rs + b_ij                  one rounded multiply, then one rounded add
+// A lane keeps the box of its own row in four registers; the boxes of the staged other rows lie in LDS beside the tile
+// (KT x 4 floats, staged in the same phase); the head's eight weights are block-uniform.  On the key side own = key and
+// other = query, and the call is still edge_features(query box, key box, key index - query index): five of the eight
+// features are antisymmetric.  Everything GEO sits behind `if constexpr`: the plain instantiations are what they were.
+//   d w[a][e] = sum over pages, i, j of ds_ij * phi_ij[e], on the QUERY side:
+//     lane (l16, grp)   eight partials, fmaf(ds, phi[e], partial) in turn: tiles ascending, sub-tiles ascending, r
+//                       ascending (own row l16, other rows 16 sub + 4 grp + r); a masked pair enters with ds = +0
+//     wave              v += shfl_xor(v, o) for o = 32, 16, 8, 4, 2, 1
+//     block             ((w0 + w1) + w2) + w3 over its four waves through LDS, written to workspace[block][e]; a block whose
+//                       own tile lies behind its page's end writes eight zeros
+//     fold launch       per (a, e) one thread, from +0: pages ascending, inside a page its own tiles ascending (the blocks
+//                       behind the page's end hold zeros and are passed over: the sum's bits are the same)
+// No atomics, no host read: d w is bit-identical between reruns.  phi has no gradient (the boxes are data).
+#include "geometry.h"
 #include "mma.h"
 #include "rows.h"
 
@@ -162,15 +182,54 @@ __device__ __forceinline__ PaBlock pa_block(const int64_t *__restrict__ page_sta
     return PaBlock{t, a, pr.base, t * PA_OWN < n ? n : 0};
 }
 
+// operands of the geometry bias; the plain instantiations carry the empty form
+template <bool GEO>
+struct PaGeo {};
+
+template <>
+struct PaGeo<true> {
+    const float *bboxes;                   // [N, 5] = page, x1, y1, x2, y2
+    const float *w;                        // [Hh, 8]
+    float W, H;                            // page width and height in pixels
+    float *ws;                             // query side of the backward: [blocks][8] partial sums of d w
+};
+
+// the boxes of a tile's rows [0, KT) into LDS; rows >= rows_valid are zeros.  row0 = batch row of the tile's row 0.
 template <int DHB>
+__device__ __forceinline__ void pa_stage_boxes(float4 *__restrict__ lds, const float *__restrict__ bboxes, int row0,
+                                               int rows_valid, int tid)
+{
+    if (tid < PaCfg<DHB>::KT)
+        lds[tid] = tid < rows_valid ? knn_box(bboxes, (long long)row0 + tid) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+__device__ __forceinline__ void pa_geo_weights(const float *__restrict__ w, int head, float (&wt)[8])
+{
+#pragma unroll
+    for (int e = 0; e < 8; ++e) wt[e] = w[head * 8 + e];
+}
+
+// phi of (query box, key box, dj = key index - query index) and the bias w . phi as one fma chain from +0
+__device__ __forceinline__ float pa_bias(const float4 qbox, const float4 kbox, float W, float H, int dj, const float (&wt)[8],
+                                         float (&phi)[8])
+{
+    edge_features(qbox, kbox, W, H, dj, phi);
+    float b = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) b = fmaf(wt[e], phi[e], b);
+    return b;
+}
+
+template <int DHB, bool GEO>
 __global__ __launch_bounds__(PA_THREADS) void pa_fwd_kernel(const float *__restrict__ qkv, int ldq,
                                                             const int64_t *__restrict__ page_start, int N, int E, int Hh,
                                                             int tiles, float *__restrict__ out, int ldo,
-                                                            float *__restrict__ lse, int vo)
+                                                            float *__restrict__ lse, int vo, PaGeo<GEO> geo)
 {
     using C = PaCfg<DHB>;
     __shared__ __attribute__((aligned(16))) float Ks[C::KT * C::LD];
     __shared__ __attribute__((aligned(16))) float Vs[C::KT * C::LD];
+    __shared__ float4 Bs[GEO ? C::KT : 1];                               // boxes of the staged keys (GEO)
     const PaBlock b = pa_block(page_start, N, Hh, tiles);
     const int n = b.n;
     if (n == 0) return;
@@ -183,6 +242,12 @@ __global__ __launch_bounds__(PA_THREADS) void pa_fwd_kernel(const float *__restr
     f32x4 Qf[DHB];
     pa_frag<DHB>(qok ? qh + (size_t)q * ldq : nullptr, dh, grp, true, Qf);
     const int nkt = (n + C::KT - 1) / C::KT;
+    float4 qbox = make_float4(0.f, 0.f, 0.f, 0.f);
+    [[maybe_unused]] float wt[8], phi[8];
+    if constexpr (GEO) {
+        if (qok) qbox = knn_box(geo.bboxes, (long long)b.base + q);
+        pa_geo_weights(geo.w, b.head, wt);
+    }
 
     // pass 1: the row maximum
     float m = -INFINITY;
@@ -190,12 +255,17 @@ __global__ __launch_bounds__(PA_THREADS) void pa_fwd_kernel(const float *__restr
         const int k0 = kt * C::KT;
         __syncthreads();
         pa_stage<DHB>(Ks, qh + E + (size_t)k0 * ldq, ldq, n - k0, dh, true, tid);
+        if constexpr (GEO) pa_stage_boxes<DHB>(Bs, geo.bboxes, b.base + k0, n - k0, tid);
         __syncthreads();
         for (int sub = 0; sub < C::KT / 16 && k0 + sub * 16 < n; ++sub) {
             const f32x4 s = pa_dot<DHB>(Ks, sub, Qf, l16, grp);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float v = s[r] * rs;
+                float v = s[r] * rs;
+                if constexpr (GEO) {
+                    const int o = sub * 16 + 4 * grp + r;
+                    v = v + pa_bias(qbox, Bs[o], geo.W, geo.H, k0 + o - q, wt, phi);
+                }
                 if (k0 + sub * 16 + 4 * grp + r < n && v > m) m = v;
             }
         }
@@ -213,13 +283,18 @@ __global__ __launch_bounds__(PA_THREADS) void pa_fwd_kernel(const float *__restr
         __syncthreads();
         pa_stage<DHB>(Ks, qh + E + (size_t)k0 * ldq, ldq, n - k0, dh, true, tid);
         pa_stage<DHB>(Vs, qh + 2 * E + (size_t)k0 * ldq, ldq, n - k0, dh, true, tid);
+        if constexpr (GEO) pa_stage_boxes<DHB>(Bs, geo.bboxes, b.base + k0, n - k0, tid);
         __syncthreads();
         for (int sub = 0; sub < C::KT / 16 && k0 + sub * 16 < n; ++sub) {
             const f32x4 s = pa_dot<DHB>(Ks, sub, Qf, l16, grp);
             f32x4 pw;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float v = s[r] * rs;
+                float v = s[r] * rs;
+                if constexpr (GEO) {
+                    const int o = sub * 16 + 4 * grp + r;
+                    v = v + pa_bias(qbox, Bs[o], geo.W, geo.H, k0 + o - q, wt, phi);
+                }
                 pw[r] = k0 + sub * 16 + 4 * grp + r < n ? expf(v - m) : 0.f;
                 l += pw[r];
             }
@@ -239,21 +314,27 @@ __global__ __launch_bounds__(PA_THREADS) void pa_fwd_kernel(const float *__restr
 }
 
 // query side of the backward: dQ_i = rs * sum_j ds_ij K_j, keys in ascending tiles
-template <int DHB>
+template <int DHB, bool GEO>
 __global__ __launch_bounds__(PA_THREADS) void pa_bwd_q_kernel(const float *__restrict__ g, int ldg,
                                                               const float *__restrict__ qkv, int ldq,
                                                               const float *__restrict__ out, int ldo,
                                                               const float *__restrict__ lse,
                                                               const int64_t *__restrict__ page_start, int N, int E, int Hh,
                                                               int tiles, float *__restrict__ dqkv, int lddq, int vg, int vo,
-                                                              int vd)
+                                                              int vd, PaGeo<GEO> geo)
 {
     using C = PaCfg<DHB>;
     __shared__ __attribute__((aligned(16))) float Ks[C::KT * C::LD];
     __shared__ __attribute__((aligned(16))) float Vs[C::KT * C::LD];
+    __shared__ float4 Bs[GEO ? C::KT : 1];                               // boxes of the staged keys (GEO)
+    __shared__ float wred[GEO ? PA_THREADS / 64 * 8 : 1];                // the waves' partial sums of d w (GEO)
     const PaBlock b = pa_block(page_start, N, Hh, tiles);
     const int n = b.n;
-    if (n == 0) return;
+    if (n == 0) {
+        if constexpr (GEO)
+            if (threadIdx.x < 8) geo.ws[(size_t)blockIdx.x * 8 + threadIdx.x] = 0.f;
+        return;
+    }
     const int dh = E / Hh, tid = threadIdx.x, lane = tid & 63, l16 = lane & 15, grp = lane >> 4;
     const float rs = 1.f / sqrtf((float)dh);
     const int q = b.own_tile * PA_OWN + (tid >> 6) * 16 + l16;
@@ -267,6 +348,14 @@ __global__ __launch_bounds__(PA_THREADS) void pa_bwd_q_kernel(const float *__res
     pa_frag<DHB>(qok ? grow : nullptr, dh, grp, vg != 0, Gf);
     const float lse_q = qok ? lse[(size_t)(b.base + q) * Hh + b.head] : 0.f;
     const float delta = pa_grp_sum(qok ? pa_delta_part(grow, orow, dh, grp, vg != 0, vo != 0) : 0.f);
+    float4 qbox = make_float4(0.f, 0.f, 0.f, 0.f);
+    [[maybe_unused]] float wt[8], phi[8], dw[8];
+    if constexpr (GEO) {
+        if (qok) qbox = knn_box(geo.bboxes, (long long)b.base + q);
+        pa_geo_weights(geo.w, b.head, wt);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dw[e] = 0.f;
+    }
 
     f32x4 acc[DHB];
 #pragma unroll
@@ -277,6 +366,7 @@ __global__ __launch_bounds__(PA_THREADS) void pa_bwd_q_kernel(const float *__res
         __syncthreads();
         pa_stage<DHB>(Ks, qh + E + (size_t)k0 * ldq, ldq, n - k0, dh, true, tid);
         pa_stage<DHB>(Vs, qh + 2 * E + (size_t)k0 * ldq, ldq, n - k0, dh, true, tid);
+        if constexpr (GEO) pa_stage_boxes<DHB>(Bs, geo.bboxes, b.base + k0, n - k0, tid);
         __syncthreads();
         for (int sub = 0; sub < C::KT / 16 && k0 + sub * 16 < n; ++sub) {
             const f32x4 s = pa_dot<DHB>(Ks, sub, Qf, l16, grp);
@@ -284,11 +374,35 @@ __global__ __launch_bounds__(PA_THREADS) void pa_bwd_q_kernel(const float *__res
             f32x4 ds;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float v = s[r] * rs;
+                float v = s[r] * rs;
+                if constexpr (GEO) {
+                    const int o = sub * 16 + 4 * grp + r;
+                    v = v + pa_bias(qbox, Bs[o], geo.W, geo.H, k0 + o - q, wt, phi);
+                }
                 const bool ok = qok && k0 + sub * 16 + 4 * grp + r < n;
                 ds[r] = ok ? expf(v - lse_q) * (dA[r] - delta) : 0.f;
+                if constexpr (GEO) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) dw[e] = fmaf(ds[r], phi[e], dw[e]);
+                }
             }
             pa_acc<DHB>(Ks, sub, ds, acc, l16, grp);
+        }
+    }
+
+    if constexpr (GEO) {                   // lane partials -> wave (fixed butterfly) -> block (wave order) -> workspace
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float v = dw[e];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+            if (lane == 0) wred[(tid >> 6) * 8 + e] = v;
+        }
+        __syncthreads();
+        if (tid < 8) {
+            float v = wred[tid];
+            for (int w = 1; w < PA_THREADS / 64; ++w) v += wred[w * 8 + tid];
+            geo.ws[(size_t)blockIdx.x * 8 + tid] = v;
         }
     }
 
@@ -302,19 +416,20 @@ __global__ __launch_bounds__(PA_THREADS) void pa_bwd_q_kernel(const float *__res
 }
 
 // key side of the backward: dK_j = rs * sum_i ds_ij Q_i, dV_j = sum_i A_ij g_i, queries in ascending tiles
-template <int DHB>
+template <int DHB, bool GEO>
 __global__ __launch_bounds__(PA_THREADS) void pa_bwd_k_kernel(const float *__restrict__ g, int ldg,
                                                               const float *__restrict__ qkv, int ldq,
                                                               const float *__restrict__ out, int ldo,
                                                               const float *__restrict__ lse,
                                                               const int64_t *__restrict__ page_start, int N, int E, int Hh,
                                                               int tiles, float *__restrict__ dqkv, int lddq, int vg, int vo,
-                                                              int vd)
+                                                              int vd, PaGeo<GEO> geo)
 {
     using C = PaCfg<DHB>;
     __shared__ __attribute__((aligned(16))) float Qs[C::KT * C::LD];
     __shared__ __attribute__((aligned(16))) float Gs[C::KT * C::LD];
     __shared__ float lse_s[C::KT], del_s[C::KT];
+    __shared__ float4 Bs[GEO ? C::KT : 1];                               // boxes of the staged queries (GEO)
     const PaBlock b = pa_block(page_start, N, Hh, tiles);
     const int n = b.n;
     if (n == 0) return;
@@ -330,6 +445,13 @@ __global__ __launch_bounds__(PA_THREADS) void pa_bwd_k_kernel(const float *__res
     pa_frag<DHB>(kok ? qh + E + (size_t)k * ldq : nullptr, dh, grp, true, Kf);
     pa_frag<DHB>(kok ? qh + 2 * E + (size_t)k * ldq : nullptr, dh, grp, true, Vf);
 
+    float4 kbox = make_float4(0.f, 0.f, 0.f, 0.f);
+    [[maybe_unused]] float wt[8], phi[8];
+    if constexpr (GEO) {
+        if (kok) kbox = knn_box(geo.bboxes, (long long)b.base + k);
+        pa_geo_weights(geo.w, b.head, wt);
+    }
+
     f32x4 dK[DHB], dV[DHB];
 #pragma unroll
     for (int c = 0; c < DHB; ++c) dK[c] = dV[c] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -339,6 +461,7 @@ __global__ __launch_bounds__(PA_THREADS) void pa_bwd_k_kernel(const float *__res
         __syncthreads();
         pa_stage<DHB>(Qs, qh + (size_t)q0 * ldq, ldq, n - q0, dh, true, tid);
         pa_stage<DHB>(Gs, gh + (size_t)q0 * ldg, ldg, n - q0, dh, vg != 0, tid);
+        if constexpr (GEO) pa_stage_boxes<DHB>(Bs, geo.bboxes, b.base + q0, n - q0, tid);
         {   // four threads per query: its delta (the query side's bits) and its lse
             const int qq = tid >> 2, j = tid & 3;
             const bool ok = qq < C::KT && q0 + qq < n;
@@ -360,7 +483,9 @@ __global__ __launch_bounds__(PA_THREADS) void pa_bwd_k_kernel(const float *__res
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int qi = sub * 16 + 4 * grp + r;
-                const float v = s[r] * rs;
+                float v = s[r] * rs;
+                if constexpr (GEO)          // own = key, other = query: still (query box, key box, key - query)
+                    v = v + pa_bias(Bs[qi], kbox, geo.W, geo.H, k - (q0 + qi), wt, phi);
                 if (kok && q0 + qi < n) {
                     pw[r] = expf(v - lse_s[qi]);
                     ds[r] = pw[r] * (dA[r] - del_s[qi]);
@@ -394,20 +519,39 @@ static bool pa_shape_ok(int B, int N, int E, int Hh)
     return (long long)B * Hh * cdiv(N > 0 ? N : 1, PA_OWN) <= 0x7fffffffLL;
 }
 
+// d w[a][e] from the query side's block partials: one thread per (a, e), pages ascending, a page's own tiles ascending
+__global__ __launch_bounds__(64) void pa_geo_fold_kernel(const float *__restrict__ ws, const int64_t *__restrict__ page_start,
+                                                         int B, int N, int Hh, int tiles, float *__restrict__ d_w)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= Hh * 8) return;
+    const int a = i >> 3, e = i & 7;
+    float v = 0.f;
+    for (int p = 0; p < B; ++p) {
+        const PageRows pr = page_rows(page_start, p, N);
+        const int nt = (pr.end - pr.base + PA_OWN - 1) / PA_OWN;
+        const float *src = ws + ((size_t)p * Hh + a) * tiles * 8 + e;
+        for (int t = 0; t < nt; ++t) v += src[(size_t)t * 8];
+    }
+    d_w[i] = v;
+}
+
 }  // namespace
 
-#define PA_DISPATCH(KERNEL, ...)                                                                           \
-    do {                                                                                                   \
-        if (dh <= 16) hipLaunchKernelGGL(KERNEL<1>, dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__);   \
-        else if (dh <= 32) hipLaunchKernelGGL(KERNEL<2>, dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
-        else if (dh <= 64) hipLaunchKernelGGL(KERNEL<4>, dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
-        else if (dh <= 96) hipLaunchKernelGGL(KERNEL<6>, dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
-        else hipLaunchKernelGGL(KERNEL<8>, dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__);            \
-        COVA_LAUNCH_CHECK();                                                                               \
+#define PA_DISPATCH(KERNEL, GEO, ...)                                                                                      \
+    do {                                                                                                                   \
+        if (dh <= 16) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<1, GEO>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
+        else if (dh <= 32) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<2, GEO>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
+        else if (dh <= 64) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<4, GEO>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
+        else if (dh <= 96) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<6, GEO>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<8, GEO>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__);       \
+        COVA_LAUNCH_CHECK();                                                                                               \
     } while (0)
 
-COVA_API int cova_page_attn_fwd(const float *qkv, int ldq, const int64_t *page_start, int B, int N, int E, int Hh, float *out,
-                                int ldo, float *lse, void *stream)
+// the checks and launches both forms share; the GEO entry points check their own operands first
+template <bool GEO>
+static int pa_fwd(const float *qkv, int ldq, const int64_t *page_start, int B, int N, int E, int Hh, float *out, int ldo,
+                  float *lse, PaGeo<GEO> geo, void *stream)
 {
     COVA_REQUIRE(pa_shape_ok(B, N, E, Hh) && ldq >= 3 * E && ldo >= E);
     if (N == 0 || B == 0) return COVA_OK;
@@ -416,13 +560,14 @@ COVA_API int cova_page_attn_fwd(const float *qkv, int ldq, const int64_t *page_s
     const int dh = E / Hh, tiles = cdiv(N, PA_OWN), blocks = B * Hh * tiles;
     const int vo = vec4_ok(out, ldo);
     hipStream_t st = (hipStream_t)stream;
-    PA_DISPATCH(pa_fwd_kernel, qkv, ldq, page_start, N, E, Hh, tiles, out, ldo, lse, vo);
+    PA_DISPATCH(pa_fwd_kernel, GEO, qkv, ldq, page_start, N, E, Hh, tiles, out, ldo, lse, vo, geo);
     return COVA_OK;
 }
 
-COVA_API int cova_page_attn_bwd(const float *g, int ldg, const float *qkv, int ldq, const float *out, int ldo,
-                                const float *lse, const int64_t *page_start, int B, int N, int E, int Hh, float *dqkv,
-                                int lddq, void *stream)
+template <bool GEO>
+static int pa_bwd(const float *g, int ldg, const float *qkv, int ldq, const float *out, int ldo, const float *lse,
+                  const int64_t *page_start, int B, int N, int E, int Hh, float *dqkv, int lddq, PaGeo<GEO> geo,
+                  void *stream)
 {
     COVA_REQUIRE(pa_shape_ok(B, N, E, Hh) && ldg >= E && ldq >= 3 * E && ldo >= E && lddq >= 3 * E);
     if (N == 0 || B == 0) return COVA_OK;
@@ -431,7 +576,60 @@ COVA_API int cova_page_attn_bwd(const float *g, int ldg, const float *qkv, int l
     const int dh = E / Hh, tiles = cdiv(N, PA_OWN), blocks = B * Hh * tiles;
     const int vg = vec4_ok(g, ldg), vo = vec4_ok(out, ldo), vd = vec4_ok(dqkv, lddq);
     hipStream_t st = (hipStream_t)stream;
-    PA_DISPATCH(pa_bwd_q_kernel, g, ldg, qkv, ldq, out, ldo, lse, page_start, N, E, Hh, tiles, dqkv, lddq, vg, vo, vd);
-    PA_DISPATCH(pa_bwd_k_kernel, g, ldg, qkv, ldq, out, ldo, lse, page_start, N, E, Hh, tiles, dqkv, lddq, vg, vo, vd);
+    PA_DISPATCH(pa_bwd_q_kernel, GEO, g, ldg, qkv, ldq, out, ldo, lse, page_start, N, E, Hh, tiles, dqkv, lddq, vg, vo, vd,
+                geo);
+    PA_DISPATCH(pa_bwd_k_kernel, GEO, g, ldg, qkv, ldq, out, ldo, lse, page_start, N, E, Hh, tiles, dqkv, lddq, vg, vo, vd,
+                geo);
+    return COVA_OK;
+}
+
+COVA_API int cova_page_attn_fwd(const float *qkv, int ldq, const int64_t *page_start, int B, int N, int E, int Hh, float *out,
+                                int ldo, float *lse, void *stream)
+{
+    return pa_fwd<false>(qkv, ldq, page_start, B, N, E, Hh, out, ldo, lse, PaGeo<false>{}, stream);
+}
+
+COVA_API int cova_page_attn_bwd(const float *g, int ldg, const float *qkv, int ldq, const float *out, int ldo,
+                                const float *lse, const int64_t *page_start, int B, int N, int E, int Hh, float *dqkv,
+                                int lddq, void *stream)
+{
+    return pa_bwd<false>(g, ldg, qkv, ldq, out, ldo, lse, page_start, B, N, E, Hh, dqkv, lddq, PaGeo<false>{}, stream);
+}
+
+COVA_API int cova_page_attn_geo_workspace_floats(int B, int N, int Hh)
+{
+    if (B <= 0 || N <= 0 || Hh < 1) return 0;
+    const long long v = 8LL * B * Hh * cdiv(N, PA_OWN);
+    return v <= 0x7fffffffLL ? (int)v : 0;
+}
+
+COVA_API int cova_page_attn_fwd_geo(const float *qkv, int ldq, const int64_t *page_start, const float *bboxes,
+                                    const float *geo_w, float img_w, float img_h, int B, int N, int E, int Hh, float *out,
+                                    int ldo, float *lse, void *stream)
+{
+    COVA_REQUIRE(img_w > 0.f && img_h > 0.f);
+    if (N > 0 && B > 0) {
+        COVA_REQUIRE(bboxes && geo_w);
+    }
+    return pa_fwd<true>(qkv, ldq, page_start, B, N, E, Hh, out, ldo, lse, PaGeo<true>{bboxes, geo_w, img_w, img_h, nullptr},
+                        stream);
+}
+
+COVA_API int cova_page_attn_bwd_geo(const float *g, int ldg, const float *qkv, int ldq, const float *out, int ldo,
+                                    const float *lse, const int64_t *page_start, const float *bboxes, const float *geo_w,
+                                    float img_w, float img_h, int B, int N, int E, int Hh, float *dqkv, int lddq,
+                                    float *d_geo_w, float *workspace, void *stream)
+{
+    COVA_REQUIRE(img_w > 0.f && img_h > 0.f);
+    if (N > 0 && B > 0) {
+        COVA_REQUIRE(bboxes && geo_w && d_geo_w && workspace);
+        COVA_REQUIRE(Hh < 1 || cova_page_attn_geo_workspace_floats(B, N, Hh) > 0);      // the workspace's size fits an int
+    }
+    const int rc = pa_bwd<true>(g, ldg, qkv, ldq, out, ldo, lse, page_start, B, N, E, Hh, dqkv, lddq,
+                                PaGeo<true>{bboxes, geo_w, img_w, img_h, workspace}, stream);
+    if (rc != COVA_OK || N == 0 || B == 0) return rc;
+    hipLaunchKernelGGL(pa_geo_fold_kernel, dim3(cdiv(Hh * 8, 64)), dim3(64), 0, (hipStream_t)stream, workspace, page_start, B,
+                       N, Hh, cdiv(N, PA_OWN), d_geo_w);
+    COVA_LAUNCH_CHECK();
     return COVA_OK;
 }

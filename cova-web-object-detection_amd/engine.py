@@ -1591,35 +1591,67 @@ def page_readout_bwd(sv, g, ldg, params, dh, lddh, gout=None):
 
 
 # ------------------------------------------------------------------------------- page self-attention
-def page_attn_fwd(h, ldh, N, F, page_start, params, heads, out, ldo, prefix="page_attention."):
+def page_attn_fwd(h, ldh, N, F, page_start, params, heads, out, ldo, prefix="page_attention.", bboxes=None,
+                  page_size=None):
     """The page self-attention (cova_page_attn_fwd): [Q | K | V] = h qkv.weight^T by cova_sgemm, then per page and head the
     softmax of Q_i . K_j / sqrt(dh) over ALL rows j of the page and O_i = sum_j A_ij V_j, written to the rows out + n*ldo
     (E columns).  h rows at h + n*ldh (F values); ``page_start`` device int64 [B + 1].  -> saved dict for page_attn_bwd
-    (qkv, lse [N, heads] and the output's place: the probabilities are recomputed)."""
+    (qkv, lse [N, heads] and the output's place: the probabilities are recomputed).
+    With ``geometry.weight`` [heads, 8] among the parameters the scores carry the box-geometry bias
+    (cova_page_attn_fwd_geo): ``bboxes`` [N, 5] and ``page_size`` = (height, width) in pixels are then required."""
     _check(page_start, torch.int64)
     W = params[prefix + "qkv.weight"]
     E, B = W.shape[0] // 3, page_start.shape[0] - 1
     if W.shape[1] != F or W.shape[0] != 3 * E or E < 1:
         raise ValueError("%sqkv.weight %s does not fit %d own features" % (prefix, tuple(W.shape), F))
+    geo = params.get(prefix + "geometry.weight")
+    if geo is not None:
+        if tuple(geo.shape) != (heads, 8):
+            raise ValueError("%sgeometry.weight %s does not fit %d heads" % (prefix, tuple(geo.shape), heads))
+        if bboxes is None or tuple(bboxes.shape) != (N, 5):
+            raise ValueError("%sgeometry.weight: the geometry bias needs bboxes [%d, 5]" % (prefix, N))
+        _check(bboxes)
+        try:
+            img_h, img_w = (float(v) for v in page_size)
+        except (TypeError, ValueError):
+            raise ValueError("page_size must be (height, width) in pixels, got %r" % (page_size,))
+        if not (img_h > 0 and img_w > 0):
+            raise ValueError("page_size must be positive, got %r" % (page_size,))
     qkv = _empty((N, 3 * E), h)
     call("cova_sgemm", 0, 1, N, 3 * E, F, h, ldh, W, F, qkv, 3 * E, None, 0)
     lse = _empty((N, heads), h)
-    call("cova_page_attn_fwd", qkv, 3 * E, page_start, B, N, E, heads, out, ldo, lse)
-    return dict(h=h, ldh=ldh, N=N, F=F, E=E, B=B, heads=heads, qkv=qkv, lse=lse, out=out, ldo=ldo, page_start=page_start,
-                prefix=prefix)
+    sv = dict(h=h, ldh=ldh, N=N, F=F, E=E, B=B, heads=heads, qkv=qkv, lse=lse, out=out, ldo=ldo, page_start=page_start,
+              prefix=prefix)
+    if geo is not None:
+        call("cova_page_attn_fwd_geo", qkv, 3 * E, page_start, bboxes, geo, img_w, img_h, B, N, E, heads, out, ldo, lse)
+        sv.update(bboxes=bboxes, img_w=img_w, img_h=img_h)
+    else:
+        call("cova_page_attn_fwd", qkv, 3 * E, page_start, B, N, E, heads, out, ldo, lse)
+    return sv
 
 
 def page_attn_bwd(sv, g, ldg, params, dh, lddh, gout=None):
-    """g = dL/d(attention columns) (rows at g + n*ldg).  ACCUMULATES dL/dh into dh; returns the weight gradient."""
+    """g = dL/d(attention columns) (rows at g + n*ldg).  ACCUMULATES dL/dh into dh; returns the weight gradient (and
+    the geometry weight's, where the forward took the bias: cova_page_attn_bwd_geo, its workspace from the allocator)."""
     N, F, E, B, prefix = sv["N"], sv["F"], sv["E"], sv["B"], sv["prefix"]
     W = params[prefix + "qkv.weight"]
     dqkv = _empty((N, 3 * E), g)
-    call("cova_page_attn_bwd", g, ldg, sv["qkv"], 3 * E, sv["out"], sv["ldo"], sv["lse"], sv["page_start"], B, N, E,
-         sv["heads"], dqkv, 3 * E)
+    grads = {}
+    if "bboxes" in sv:                    # the forward took the geometry bias
+        Hh = sv["heads"]
+        dgeo = _gbuf(gout, prefix + "geometry.weight", (Hh, 8), g)
+        ws = _empty((query("cova_page_attn_geo_workspace_floats", B, N, Hh),), g)
+        call("cova_page_attn_bwd_geo", g, ldg, sv["qkv"], 3 * E, sv["out"], sv["ldo"], sv["lse"], sv["page_start"],
+             sv["bboxes"], params[prefix + "geometry.weight"], sv["img_w"], sv["img_h"], B, N, E, Hh, dqkv, 3 * E, dgeo, ws)
+        grads[prefix + "geometry.weight"] = dgeo
+    else:
+        call("cova_page_attn_bwd", g, ldg, sv["qkv"], 3 * E, sv["out"], sv["ldo"], sv["lse"], sv["page_start"], B, N, E,
+             sv["heads"], dqkv, 3 * E)
     dW = _gbuf(gout, prefix + "qkv.weight", (3 * E, F), g)
     call("cova_sgemm", 1, 0, 3 * E, F, N, dqkv, 3 * E, sv["h"], sv["ldh"], dW, F, None, 0)
     call("cova_sgemm", 0, 0, N, F, 3 * E, dqkv, 3 * E, W, F, dh, lddh, None, 1)
-    return {prefix + "qkv.weight": dW}
+    grads[prefix + "qkv.weight"] = dW
+    return grads
 
 
 # ------------------------------------------------------------------------------- decoder
@@ -1751,8 +1783,16 @@ def _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, t
     if G > 0:
         sv["readout"] = page_readout_fwd(comb, T, N, F, sv["page_start"], params, comb[:, F + D:], T)
     if E > 0:
+        geo = bool(cfg.get("page_attention_geometry", False))
+        if geo and sv.get("page_size") is None:
+            raise ValueError("page_attention_geometry: a batch without images must carry page_size = (height, width) "
+                             "(or the configuration a 'page_size')")
+        if geo != ("page_attention.geometry.weight" in params):
+            raise ValueError("page_attention_geometry=%r, but the parameters %s page_attention.geometry.weight"
+                             % (geo, "lack" if geo else "hold"))
         sv["page_attn"] = page_attn_fwd(comb, T, N, F, sv["page_start"], params, cfg.get("page_attention_heads", 1),
-                                        comb[:, F + D + G:], T)
+                                        comb[:, F + D + G:], T, bboxes=bboxes if geo else None,
+                                        page_size=sv.get("page_size"))
     logits, sv["dec"] = decoder_fwd(comb, N, T, params, buffers, training, cfg["drop_prob"], seeds,
                                     masks)
     return logits, (sv if save else None)

@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from . import engine
 from .weights import (EDGE_FEATURES, attention_of, backbone_channels, check_attention, check_attention_dropout,
-                      check_backbone_layers, check_page_attention, check_page_context_dim)
+                      check_backbone_layers, check_page_attention, check_page_attention_geometry, check_page_context_dim)
 
 GAT_MAX_K = engine.GAT_MAX_K
 LOSS_MAX_CLASSES = engine.LOSS_MAX_CLASSES
@@ -487,12 +487,16 @@ class PageReadout(nn.Module):
 
 class _PageAttentionFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, layer, h, page_start, W):
+    def forward(ctx, layer, h, page_start, bboxes, page_size, W, Wgeo):
         h = _f32c(h)
         N, F = h.shape
         params = {"page_attention.qkv.weight": W.detach()}
+        if Wgeo is not None:
+            params["page_attention.geometry.weight"] = _f32c(Wgeo.detach())
+            bboxes = _f32c(bboxes)
         out = torch.empty((N, layer.dim), device=h.device)
-        ctx.sv = engine.page_attn_fwd(h, F, N, F, _i64c(page_start), params, layer.heads, out, layer.dim)
+        ctx.sv = engine.page_attn_fwd(h, F, N, F, _i64c(page_start), params, layer.heads, out, layer.dim,
+                                      bboxes=bboxes, page_size=page_size)
         ctx.params = params
         ctx.mark_non_differentiable(ctx.sv["lse"])
         return out, ctx.sv["lse"]
@@ -502,27 +506,43 @@ class _PageAttentionFn(torch.autograd.Function):
         sv = ctx.sv
         dh = torch.zeros((sv["N"], sv["F"]), device=g.device)          # page_attn_bwd accumulates
         grads = engine.page_attn_bwd(sv, g.contiguous(), sv["E"], ctx.params, dh, sv["F"])
-        return None, dh, None, grads["page_attention.qkv.weight"]
+        return (None, dh, None, None, None, grads["page_attention.qkv.weight"],
+                grads.get("page_attention.geometry.weight"))
 
 
 class PageAttention(nn.Module):
     """Extension: multi-head scaled dot-product self-attention (Vaswani et al. 2017) restricted to pages.  ``[Q | K | V] =
     qkv(h)`` (Linear(in_features, 3 dim), no bias); for a box i and a head of ``dim / heads`` columns, ``A_ij`` = softmax
     over ALL boxes j of i's page of ``Q_i . K_j / sqrt(dim / heads)`` and ``O_i = sum_j A_ij V_j``.  No output projection
-    (the decoder's first Linear follows), no dropout, no geometry term.  ``forward(h [N, in_features], page_start int64
+    (the decoder's first Linear follows), no dropout.  ``forward(h [N, in_features], page_start int64
     [B + 1])`` -> ``O [N, dim]`` (and ``lse [N, heads]``, the log-sum-exp of each row's scores, with ``return_lse``); one
-    autograd node over cova_page_attn_fwd / cova_page_attn_bwd."""
+    autograd node over cova_page_attn_fwd / cova_page_attn_bwd.
+    ``geometry=True`` (extension; the relative 2-D bias of LayoutLMv2, Xu et al. 2021, on this project's own features):
+    the score of a pair also takes ``geometry`` (Linear(8, heads), no bias, zero at construction: the fresh layer computes
+    the plain layer's output) of the eight relative-geometry features of cova_edge_geometry, query box against key box,
+    formed inside the kernels (cova_page_attn_fwd_geo / cova_page_attn_bwd_geo).  ``forward`` then needs ``bboxes``
+    [N, 5] and ``page_size`` = (height, width) in pixels; the boxes get no gradient."""
 
-    def __init__(self, in_features, dim, heads=1):
+    def __init__(self, in_features, dim, heads=1, geometry=False):
         super().__init__()
         self.in_features = in_features
         self.dim, self.heads = check_page_attention(dim, heads)
         if self.dim < 1:
             raise ValueError("PageAttention needs dim >= 4")
         self.qkv = nn.Linear(in_features, 3 * self.dim, bias=False)
+        self.geometry_bias = bool(geometry)
+        if self.geometry_bias:
+            self.geometry = nn.Linear(8, self.heads, bias=False)
+            nn.init.zeros_(self.geometry.weight)
 
-    def forward(self, h, page_start, return_lse=False):
+    def forward(self, h, page_start, bboxes=None, page_size=None, return_lse=False):
         _require_cuda(h, page_start)
+        wgeo = None
+        if self.geometry_bias:
+            if bboxes is None or page_size is None or bboxes.dim() != 2 or tuple(bboxes.shape) != (h.shape[0], 5):
+                raise ValueError("a PageAttention with geometry=True needs bboxes [N, 5] and page_size = (height, width)")
+            _require_cuda(bboxes)
+            wgeo = self.geometry.weight
         if h.dim() != 2 or h.shape[1] != self.in_features:
             raise RuntimeError("expected h [N, %d], got %s" % (self.in_features, tuple(h.shape)))
         if page_start.dim() != 1 or page_start.shape[0] < 1 or page_start.is_floating_point():
@@ -530,7 +550,7 @@ class PageAttention(nn.Module):
         if h.shape[0] == 0:
             out, lse = h.new_empty((0, self.dim)), h.new_empty((0, self.heads))
         else:
-            out, lse = _PageAttentionFn.apply(self, h, page_start, self.qkv.weight)
+            out, lse = _PageAttentionFn.apply(self, h, page_start, bboxes, page_size, self.qkv.weight, wgeo)
         return (out, lse) if return_lse else out
 
 
@@ -539,7 +559,8 @@ class CoVA(nn.Module):
                  bbox_hidden_dim=32, n_additional_feat=0, drop_prob=0.2, class_names=None,
                  backbone="resnet18", n_heads=1, n_gat_layers=1, backbone_state_dict=None, roi_op="pool",
                  sampling_ratio=2, roi_aligned=False, backbone_layers=1, edge_geometry=False, attention="gat",
-                 attention_dropout=0.0, page_context_dim=0, page_attention_dim=0, page_attention_heads=1):
+                 attention_dropout=0.0, page_context_dim=0, page_attention_dim=0, page_attention_heads=1,
+                 page_attention_geometry=False):
         """The first nine arguments exactly as the reference's CoVA (models.py:10-34; called positionally
         at main.py:122-132).  Keyword-only-in-practice extensions, whose defaults are the reference's
         model: ``backbone`` 'resnet18' | 'resnet50' (torchvision ``children()[:-5]`` of either),
@@ -568,9 +589,13 @@ class CoVA(nn.Module):
         [4, 128]; independent of ``use_context`` and of ``page_context_dim``): a PageAttention of the own features gives
         every box E more columns behind the readout's, its own attention-weighted view of ALL boxes of its page
         (``page_attention.qkv.weight``, between ``page_readout`` and ``decoder`` in the state_dict).  ``edge_geometry`` and
-        ``attention_dropout`` belong to the GAT and do not reach this layer.  With 0 nothing changes."""
+        ``attention_dropout`` belong to the GAT and do not reach this layer.  With 0 nothing changes.
+        ``page_attention_geometry=True`` (needs ``page_attention_dim`` > 0, else ValueError): the page attention's scores
+        take a bias from the relative geometry of the two boxes (``page_attention.geometry.weight`` [Hh, 8], zero at
+        construction, directly behind ``page_attention.qkv.weight``); the page size is taken from ``images``."""
         page_context_dim = check_page_context_dim(page_context_dim)
         page_attention_dim, page_attention_heads = check_page_attention(page_attention_dim, page_attention_heads)
+        page_attention_geometry = check_page_attention_geometry(page_attention_geometry, page_attention_dim)
         check_backbone_layers(backbone, backbone_layers)
         check_attention(attention)
         attention_dropout = check_attention_dropout(attention_dropout)
@@ -635,7 +660,8 @@ class CoVA(nn.Module):
             self.page_readout = PageReadout(self.n_feat, page_context_dim)
         self.page_attention_dim, self.page_attention_heads = page_attention_dim, page_attention_heads
         if page_attention_dim > 0:
-            self.page_attention = PageAttention(self.n_feat, page_attention_dim, page_attention_heads)
+            self.page_attention = PageAttention(self.n_feat, page_attention_dim, page_attention_heads,
+                                                geometry=page_attention_geometry)
         self.n_total_feat = (self.n_feat + (self.hidden_dim if self.use_context else 0) + page_context_dim
                              + page_attention_dim)
         self.decoder = nn.Sequential(nn.Dropout(drop_prob),
@@ -653,7 +679,7 @@ class CoVA(nn.Module):
                          backbone_layers=backbone_layers, edge_geometry=bool(edge_geometry) and bool(use_context),
                          attention=attention, attention_dropout=attention_dropout if use_context else 0.0,
                          page_context_dim=page_context_dim, page_attention_dim=page_attention_dim,
-                         page_attention_heads=page_attention_heads)
+                         page_attention_heads=page_attention_heads, page_attention_geometry=page_attention_geometry)
         self._param_keys = [k for k, _ in self.named_parameters()]
         self._conv_keys = [k for k in self._param_keys if k.startswith("convnet.")]
         self._bbox_keys = [k for k in self._param_keys if k.startswith("bbox_feat_encoder.")]

@@ -21,8 +21,8 @@ import os
 import torch
 
 from . import engine
-from .weights import (PAGE_ATTENTION_KEY, PAGE_READOUT_KEYS, check_attention_dropout, check_page_attention,
-                      check_page_context_dim, state_dict_spec)
+from .weights import (PAGE_ATTENTION_GEO_KEY, PAGE_ATTENTION_KEY, PAGE_READOUT_KEYS, check_attention_dropout,
+                      check_page_attention, check_page_attention_geometry, check_page_context_dim, state_dict_spec)
 
 _BUF_SUFFIX = ("running_mean", "running_var", "num_batches_tracked")
 
@@ -332,6 +332,9 @@ class HotPathTrainer:
         if "page_attention_dim" in cfg or "page_attention_heads" in cfg:
             self.cfg["page_attention_dim"], self.cfg["page_attention_heads"] = check_page_attention(
                 cfg.get("page_attention_dim", 0), cfg.get("page_attention_heads", 1))
+        if "page_attention_geometry" in cfg:
+            self.cfg["page_attention_geometry"] = check_page_attention_geometry(
+                cfg["page_attention_geometry"], self.cfg.get("page_attention_dim", 0))
         self._check_page_readout(state_dict)        # (before any device work)
         self._check_page_attention(state_dict)
         self.device = torch.device(device)
@@ -339,7 +342,8 @@ class HotPathTrainer:
                                                      "hidden_dim", "bbox_hidden_dim", "n_additional_feat",
                                                      "backbone", "n_heads", "n_gat_layers", "backbone_layers",
                                                      "edge_geometry", "attention", "page_context_dim",
-                                                     "page_attention_dim", "page_attention_heads")
+                                                     "page_attention_dim", "page_attention_heads",
+                                                     "page_attention_geometry")
                                   if k in cfg})
         pshapes = OrderedDict((k, s) for k, s in spec if is_param_key(k))
         self.pbucket = FlatBucket(pshapes, self.device)
@@ -423,6 +427,19 @@ class HotPathTrainer:
             raise ValueError("this trainer was configured with page_attention_dim=%d, the state_dict's %s has shape %s "
                              "(page_attention_dim=%s)" % (E, PAGE_ATTENTION_KEY, tuple(w.shape),
                                                           w.shape[0] // 3 if w.dim() == 2 else "?"))
+        geo, gw = bool(self.cfg.get("page_attention_geometry", False)), state_dict.get(PAGE_ATTENTION_GEO_KEY)
+        if geo and gw is None:
+            raise ValueError("this trainer was configured with page_attention_geometry=True, the state_dict lacks %s: a "
+                             "checkpoint loads into the page_attention_geometry it was trained with only"
+                             % PAGE_ATTENTION_GEO_KEY)
+        if not geo and gw is not None:
+            raise ValueError("this trainer was configured without the page attention's geometry bias "
+                             "(page_attention_geometry=False), the state_dict holds %s: a checkpoint loads into the "
+                             "page_attention_geometry it was trained with only" % PAGE_ATTENTION_GEO_KEY)
+        Hh = self.cfg.get("page_attention_heads", 1)
+        if geo and torch.is_tensor(gw) and tuple(gw.shape) != (Hh, 8):
+            raise ValueError("this trainer was configured with page_attention_geometry=True and page_attention_heads=%d, "
+                             "the state_dict's %s has shape %s" % (Hh, PAGE_ATTENTION_GEO_KEY, tuple(gw.shape)))
 
     def _flat_buffers(self, spec):
         """Live BatchNorm buffers of an averaging trainer -> {key: view}: ``bbucket`` (float32, running_mean /

@@ -74,6 +74,19 @@ def check_page_attention(e, heads=1):
     return e, heads
 
 
+PAGE_ATTENTION_GEO_KEY = "page_attention.geometry.weight"
+
+
+def check_page_attention_geometry(geometry, e):
+    """``page_attention_geometry`` (cova_page_attn_fwd_geo) against the layer's width: the option needs the layer -> bool."""
+    if not isinstance(geometry, (bool, np.bool_)):
+        raise ValueError("page_attention_geometry must be a bool, got %r" % (geometry,))
+    if geometry and e <= 0:
+        raise ValueError("page_attention_geometry=True needs page_attention_dim > 0 (the bias belongs to the page "
+                         "attention's scores), got page_attention_dim=%r" % (e,))
+    return bool(geometry)
+
+
 def attention_of(weight, D, prefix="gat."):
     """The scoring mode an ``attention_layer.weight`` belongs to, by its width: [1, 2D] is 'gat', [1, D] is 'gatv2'."""
     width = int(weight.shape[-1]) if weight.dim() else -1
@@ -126,7 +139,7 @@ def gat_prefixes(n_heads=1, n_gat_layers=1):
 def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=384,
                     bbox_hidden_dim=32, n_additional_feat=0, backbone="resnet18", n_heads=1,
                     n_gat_layers=1, backbone_layers=1, edge_geometry=False, attention="gat", page_context_dim=0,
-                    page_attention_dim=0, page_attention_heads=1):
+                    page_attention_dim=0, page_attention_heads=1, page_attention_geometry=False):
     """Ordered (key, shape) list, identical to ``reference CoVA(...).state_dict()`` for the defaults.
 
     Extensions (BASELINE.json configs[2], configs[4]; absent from the reference, defaults keep its
@@ -145,11 +158,15 @@ def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidde
     [1, G] and ``page_readout.attention_layer.bias`` [1]; the decoder is G columns wider;
     ``page_attention_dim=E`` > 0 = the page self-attention (cova_page_attn_fwd; independent of ``use_context`` and of
     ``page_context_dim``): behind the readout's entries and in front of the decoder's, ``page_attention.qkv.weight``
-    [3E, n_feat], the same shape for every ``page_attention_heads``; the decoder is E columns wider."""
+    [3E, n_feat], the same shape for every ``page_attention_heads``; the decoder is E columns wider;
+    ``page_attention_geometry=True`` (needs ``page_attention_dim`` > 0) = ``page_attention.geometry.weight``
+    [page_attention_heads, 8] directly behind ``page_attention.qkv.weight``: per head the weights of the relative-geometry
+    bias of the attention scores (cova_page_attn_fwd_geo); the decoder's width is unchanged."""
     check_backbone_layers(backbone, backbone_layers)
     check_attention(attention)
     page_context_dim = check_page_context_dim(page_context_dim)
     page_attention_dim, page_attention_heads = check_page_attention(page_attention_dim, page_attention_heads)
+    page_attention_geometry = check_page_attention_geometry(page_attention_geometry, page_attention_dim)
     c = BACKBONE_CHANNELS
     spec = [("convnet.0.weight", (c, 3, 7, 7))]
     spec += _bn_entries("convnet.1.", c)
@@ -214,6 +231,8 @@ def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidde
         n_total += page_context_dim
     if page_attention_dim > 0:
         spec.append((PAGE_ATTENTION_KEY, (3 * page_attention_dim, n_feat)))
+        if page_attention_geometry:
+            spec.append((PAGE_ATTENTION_GEO_KEY, (page_attention_heads, EDGE_FEATURES)))
         n_total += page_attention_dim
     spec += [("decoder.1.weight", (n_total, n_total)), ("decoder.1.bias", (n_total,))]
     spec += _bn_entries("decoder.2.", n_total)
@@ -229,7 +248,8 @@ def seeded_state_dict(seed=123, logit_gain=1.0, **cfg):
     from their trivial values so that every BN term is exercised.  ``logit_gain`` scales
     the last Linear so that integer-prediction tests have decisive logit margins.
     ``edge_layer.weight`` (edge_geometry=True) starts at ZERO without drawing from the stream: a fresh edge-aware model
-    computes what the plain model of the same seed computes.
+    computes what the plain model of the same seed computes.  ``page_attention.geometry.weight``
+    (page_attention_geometry=True) starts at zero in the same way.
     """
     rs = np.random.RandomState(seed)
     spec = state_dict_spec(**cfg)
@@ -241,7 +261,7 @@ def seeded_state_dict(seed=123, logit_gain=1.0, **cfg):
         if leaf == "num_batches_tracked":
             sd[key] = torch.tensor(0, dtype=torch.long)
             continue
-        if prefix.endswith("edge_layer"):
+        if prefix.endswith("edge_layer") or key == PAGE_ATTENTION_GEO_KEY:
             sd[key] = torch.zeros(shape, dtype=torch.float32)
             continue
         if leaf == "running_mean":

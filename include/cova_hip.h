@@ -746,6 +746,39 @@ int cova_page_attn_fwd(const float *qkv, int ldq, const int64_t *page_start /*[B
 int cova_page_attn_bwd(const float *g, int ldg, const float *qkv, int ldq, const float *out, int ldo,
                        const float *lse /*[N,Hh]*/, const int64_t *page_start /*[B+1]*/, int B, int N, int E, int Hh,
                        float *dqkv, int lddq, void *stream);
+/* ---- box-geometry bias of the page self-attention (page_attn.hip, the GEO instantiations; opt-in:
+ * CoVA(page_attention_geometry=True)) ----
+ * The pair above with a relative-geometry term on every score, formed inside the kernels from the two boxes of the pair
+ * (no [n, n, 8] table exists).  bboxes [N,5] = page,x1,y1,x2,y2 as cova_edge_geometry reads them; geo_w [Hh, 8], one row of
+ * weights per head; img_w, img_h the page size in pixels.  For rows i, j of one page and head a:
+ *   phi_ij = the eight f32 features of cova_edge_geometry with box a = the QUERY i, box b = the KEY j, dj = j - i
+ *            (one definition, csrc/geometry.h: the same bits, correctly rounded divisions included)
+ *   b_ij   = fma chain from +0 over e = 0..7 of geo_w[a][e] * phi_ij[e]
+ *   s_ij   = (Q_i . K_j) * (1 / sqrt(dh)) + b_ij          one rounded multiply, then one rounded add
+ * and A, O, lse as for cova_page_attn_fwd on these s_ij.  The diagonal i = j is a pair like any other (phi_ii has IoU 1
+ * for a box with area).  With geo_w == 0 every output has the plain pair's bits.  The boxes have no gradient.
+ * cova_page_attn_bwd_geo: ds_ij = A_ij (dA_ij - delta_i) with A recomputed from the biased scores against lse; dQ, dK, dV
+ * keep their expressions; d_geo_w[a][e] = sum over pages, i, j of ds_ij * phi_ij[e], every entry of [Hh, 8] written.  Its
+ * order (page_attn.hip's header): on the query side a lane's fma chain over its pairs (tiles, sub-tiles, r ascending), the
+ * xor butterfly 32 .. 1 over the wave, the block's four waves in wave order, eight sums per block into workspace
+ * [blocks][8] (blocks = B * Hh * ceil(N / 64), block = (page * Hh + head) * ceil(N / 64) + tile; a block behind its page's
+ * end writes zeros), then one fold launch per (head, e) over pages ascending and a page's tiles ascending.  No atomics, no
+ * host read: reruns are bit-identical, d_geo_w included; O, lse and dqkv rows of a page keep their bits whatever other
+ * pages share the batch.  Every workspace entry is written before it is read; the caller need not clear it.
+ * cova_page_attn_geo_workspace_floats(B, N, Hh) = 8 * B * Hh * ceil(N / 64) floats; 0 for B <= 0, N <= 0, Hh < 1 or a
+ * count beyond an int.
+ * Refusals are those of the plain pair, plus img_w <= 0 or img_h <= 0 (always), and, where N > 0 and B > 0, a NULL bboxes,
+ * geo_w, d_geo_w or workspace or a workspace count beyond an int: COVA_ERR_BAD_ARG before anything is launched.  N == 0
+ * or B == 0 launches nothing, needs no pointer and leaves d_geo_w unwritten.  Forward: one launch; backward: three (query
+ * side, key side, fold). */
+int cova_page_attn_geo_workspace_floats(int B, int N, int Hh);
+int cova_page_attn_fwd_geo(const float *qkv, int ldq, const int64_t *page_start /*[B+1]*/, const float *bboxes /*[N,5]*/,
+                           const float *geo_w /*[Hh,8]*/, float img_w, float img_h, int B, int N, int E, int Hh, float *out,
+                           int ldo, float *lse /*[N,Hh]*/, void *stream);
+int cova_page_attn_bwd_geo(const float *g, int ldg, const float *qkv, int ldq, const float *out, int ldo,
+                           const float *lse /*[N,Hh]*/, const int64_t *page_start /*[B+1]*/, const float *bboxes /*[N,5]*/,
+                           const float *geo_w /*[Hh,8]*/, float img_w, float img_h, int B, int N, int E, int Hh, float *dqkv,
+                           int lddq, float *d_geo_w /*[Hh,8]*/, float *workspace, void *stream);
 /* evaluation decision (train.py:131-153): per page and class column, page-local indices of the k
  * highest-scoring boxes, best first; page_start [n_pages+1] are box offsets; out [n_pages,NC,k] */
 int cova_page_class_topk(const float *logits, const int64_t *page_start, int n_pages, int NC, int k,
