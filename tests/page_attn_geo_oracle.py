@@ -80,7 +80,10 @@ def page_attention(h, sd, page_start, heads, phi, return_all=False):
 
 def patched_gat_stack(page_start, heads, bboxes, page_size):
     """page_attn_oracle.patched_gat_stack with the geometry bias of this batch: [own | GAT context | O].  ``page_size`` =
-    (height, width)."""
+    (height, width).
+    Not for stacking: without heads in the state dict the hook this one replaced is never called, so the columns of another
+    page layer hooked beneath it would be dropped without a word; several page layers at once are stated by
+    tests/combined_oracle.py."""
     plain = O.gat_stack
     phi = page_features(bboxes.detach().numpy(), page_start, page_size[1], page_size[0])
 

@@ -57,7 +57,10 @@ def patched_gat_stack(page_start, heads):
     """A replacement for oracle.cova_oracle.gat_stack (monkeypatch) that appends the attention columns to the context, so
     that O.forward / O.loss_and_grads state the whole model with ``page_attention_dim``: [own | GAT context | O].  The
     decoder reads its widths from the state dict.  A state dict without attention heads of the GAT (a ``use_context=False``
-    model, stated to O.forward with ``use_context=True`` so that this function is reached at all) gets [own | O]."""
+    model, stated to O.forward with ``use_context=True`` so that this function is reached at all) gets [own | O].
+    Not for stacking: without heads in the state dict the hook this one replaced is never called, so the columns of another
+    page layer hooked beneath it would be dropped without a word; several page layers at once are stated by
+    tests/combined_oracle.py."""
     plain = O.gat_stack
 
     def fn(h_i, context_indices, sd, alpha=0.2, routing=None):

@@ -74,7 +74,10 @@ def patched_gat_stack(page_start):
     that O.forward / O.loss_and_grads state the whole model with ``page_context_dim``: [own | GAT context | r_page].  The
     decoder reads its widths from the state dict.  ``routing["gate_page_readout.leaky"]`` [N] forces the readout's gates.
     A state dict without attention heads (a ``use_context=False`` model, stated to O.forward with ``use_context=True`` so
-    that this function is reached at all) gets the readout columns alone: [own | r_page]."""
+    that this function is reached at all) gets the readout columns alone: [own | r_page].
+    Not for stacking: without heads in the state dict the hook this one replaced is never called, so the columns of another
+    page layer hooked beneath it would be dropped without a word; several page layers at once are stated by
+    tests/combined_oracle.py."""
     plain = O.gat_stack
 
     def fn(h_i, context_indices, sd, alpha=0.2, routing=None):
