@@ -26,24 +26,6 @@ constexpr int RO_THREADS = 1024;          // 16 waves: a page is one block, its 
 constexpr int RO_WAVES = RO_THREADS / 64;
 constexpr int RO_MAX_G = 512;
 
-template <int V>
-__device__ __forceinline__ void ro_load(const float *__restrict__ p, float (&v)[V])
-{
-    if constexpr (V == 4) {
-        const float4 t = *reinterpret_cast<const float4 *>(p);
-        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    } else {
-        v[0] = p[0];
-    }
-}
-
-template <int V>
-__device__ __forceinline__ void ro_store(float *__restrict__ p, const float (&v)[V])
-{
-    if constexpr (V == 4) *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else p[0] = v[0];
-}
-
 // x . y over the wave's channels; absent chunks hold zeros in x
 template <int V, int NCH>
 __device__ __forceinline__ float ro_dot(const float (&x)[NCH][V], const float *__restrict__ row, int lane, int G)

@@ -1,7 +1,7 @@
-// What the row and page kernels (head.hip, loss.hip, rank.hip, mine.hip, eval.hip, decode.hip, readout.hip, page_attn.hip)
-// promise each other bit for bit: the class limit, the logsumexp of a row, the label predicate, the rows of a page and the
-// ranking order.  One definition each; none of them holds a product that feeds a sum, so a file-level fp-contract pragma of
-// the including file has nothing to reach here.
+// What the row and page kernels (head.hip, loss.hip, rank.hip, mine.hip, eval.hip, decode.hip, readout.hip, page_attn.hip,
+// page_encoder.hip) promise each other bit for bit: the class limit, the logsumexp of a row, the label predicate, the rows of
+// a page, the chunk access of a row whose lanes sit over channels and the ranking order.  One definition each; none of them
+// holds a product that feeds a sum, so a file-level fp-contract pragma of the including file has nothing to reach here.
 #pragma once
 #include "common.h"
 
@@ -49,6 +49,26 @@ __device__ __forceinline__ PageRows page_rows(const int64_t *__restrict__ page_s
 {
     const int base = page_clamp(page_start[p], 0, N);
     return PageRows{base, page_clamp(page_start[p + 1], base, N)};
+}
+
+// One chunk of a row whose lanes sit over channels (readout.hip, page_encoder.hip): V = 4 is a 16-byte access (the caller has
+// checked C % 4 == 0 and the alignment of every base and leading dimension), V = 1 a scalar one.
+template <int V>
+__device__ __forceinline__ void ro_load(const float *__restrict__ p, float (&v)[V])
+{
+    if constexpr (V == 4) {
+        const float4 t = *reinterpret_cast<const float4 *>(p);
+        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+    } else {
+        v[0] = p[0];
+    }
+}
+
+template <int V>
+__device__ __forceinline__ void ro_store(float *__restrict__ p, const float (&v)[V])
+{
+    if constexpr (V == 4) *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    else p[0] = v[0];
 }
 
 // The ranking order of a class column: score descending, ties to the lower page-local index.  "a comes before b":

@@ -4,7 +4,9 @@ evaluate.py:9, extract_attn_wts_and_visualize.py:10) resolves to the MI355X impl
 ``CrossEntropyLoss`` is the criterion of main.py:139 on the same kernels (``from models import CrossEntropyLoss``).
 The extensions are defaulted trailing arguments of the same classes (``CoVA(..., attention="gatv2", attention_dropout=0.6)``,
 ``GraphAttentionLayer(..., attention_dropout=)``, ``CoVA(..., page_context_dim=128)`` with its ``PageReadout`` module,
-``CoVA(..., page_attention_dim=128, page_attention_heads=4)`` with its ``PageAttention`` module, and
-``page_attention_geometry=True`` for the box-geometry bias of its scores): the reference's 9-argument call is unchanged."""
+``CoVA(..., page_attention_dim=128, page_attention_heads=4)`` with its ``PageAttention`` module,
+``page_attention_geometry=True`` for the box-geometry bias of its scores, and ``CoVA(..., page_encoder_dim=128,
+page_encoder_heads=4, page_encoder_layers=2)`` with its ``PageEncoder`` module): the reference's 9-argument call is
+unchanged."""
 import cova_amd  # noqa: F401  (registers cova_web_object_detection_amd)
-from cova_web_object_detection_amd.models import CoVA, CrossEntropyLoss, GraphAttentionLayer, PageAttention, PageReadout  # noqa: F401
+from cova_web_object_detection_amd.models import CoVA, CrossEntropyLoss, GraphAttentionLayer, PageAttention, PageEncoder, PageReadout  # noqa: F401

@@ -166,7 +166,7 @@ def check_batch(cfg, images, bboxes, additional_feats, context_indices, training
     if N == 1:
         # torch.nn.functional.batch_norm's _verify_batch_size, hit by the first train-mode BatchNorm1d of the forward
         T = (backbone_feat(cfg) + cfg["bbox_hidden_dim"] + A + (cfg["hidden_dim"] if cfg["use_context"] else 0)
-             + cfg.get("page_context_dim", 0) + cfg.get("page_attention_dim", 0))
+             + cfg.get("page_context_dim", 0) + cfg.get("page_attention_dim", 0) + cfg.get("page_encoder_dim", 0))
         for width, prefix in ((cfg["bbox_hidden_dim"], "bbox_feat_encoder.1."), (A, "bn_additional_feat."),
                               (T, "decoder.2.")):
             if width and is_train(training, prefix):
@@ -1556,6 +1556,11 @@ def page_start_of(bboxes, images, page_start=None, option="page_context_dim"):
     return torch.searchsorted(bboxes[:, 0].contiguous(), pages)
 
 
+def _page_option(G, E):
+    """The cfg entry a missing page table is reported under: the first page layer that is on."""
+    return "page_context_dim" if G > 0 else "page_attention_dim" if E > 0 else "page_encoder_dim"
+
+
 def page_readout_fwd(h, ldh, N, F, page_start, params, out, ldo, prefix="page_readout."):
     """The page readout (cova_page_readout_fwd): P = h W^T by cova_sgemm, then per page the softmax of
     LeakyReLU(a . P_i + b) over its rows and r_p = sum beta_i P_i, written to the row out + n*ldo of every box of the page.
@@ -1654,6 +1659,157 @@ def page_attn_bwd(sv, g, ldg, params, dh, lddh, gout=None):
     return grads
 
 
+# ------------------------------------------------------------------------------- page encoder
+LN_EPS = 1e-5                         # nn.LayerNorm's default (weights.PAGE_ENCODER_EPS)
+
+
+def layernorm_fwd(x, ldx, N, C, weight, bias, out, ldo):
+    """cova_layernorm_fwd over the rows x + n*ldx -> (mean [N], rstd [N]); ``out`` rows at out + n*ldo."""
+    mean, rstd = _empty((N,), x), _empty((N,), x)
+    call("cova_layernorm_fwd", x, ldx, N, C, weight, bias, LN_EPS, out, ldo, mean, rstd)
+    return mean, rstd
+
+
+def layernorm_bwd(g, ldg, x, ldx, mean, rstd, weight, N, C, res, dx, lddx, dweight, dbias):
+    """cova_layernorm_bwd: dx = (res or 0) + dL/dx (``res`` may be ``dx``: the stream gradient updated in place), dweight
+    and dbias written; the workspace comes from the allocator."""
+    ws = _empty((query("cova_layernorm_workspace_floats", N, C),), g)
+    call("cova_layernorm_bwd", g, ldg, x, ldx, mean, rstd, weight, N, C, res, lddx if res is not None else 0, dx, lddx,
+         dweight, dbias, ws)
+
+
+def page_encoder_fwd(h, ldh, N, F, page_start, params, heads, layers, out, ldo, prefix="page_encoder.", bboxes=None,
+                     page_size=None):
+    """The page encoder: x = h input.weight^T, then ``layers`` pre-LN transformer blocks restricted to pages,
+        a = LN1(x); qkv = a qkv.weight^T; O = page attention of qkv; x += O out.weight^T + out.bias
+        m = LN2(x); z = m ffn1.weight^T + ffn1.bias; f = GELU(z); x += f ffn2.weight^T + ffn2.bias
+    and the final LN, written to the rows out + n*ldo (P columns).  The GEMMs are cova_sgemm (a residual add is its bias +
+    accumulate form into a copy of the stream), the attention is cova_page_attn_fwd on the layer's qkv, or with
+    ``geometry.weight`` [heads, 8] among a layer's parameters cova_page_attn_fwd_geo (``bboxes`` [N, 5] and ``page_size`` =
+    (height, width) are then required); LayerNorm and GELU are cova_layernorm_fwd / cova_gelu_fwd.  There is no dropout in
+    the encoder; attention_dropout and edge_geometry belong to the GAT and do not reach it.
+    h rows at h + n*ldh (F values); ``page_start`` device int64 [B + 1].  -> saved dict for page_encoder_bwd: per layer the
+    stream ``x`` at both LayerNorm inputs with their ``mean`` / ``rstd`` and outputs, ``qkv``, ``lse``, ``O``, ``z``, ``f``."""
+    _check(page_start, torch.int64)
+    W_in = params[prefix + "input.weight"]
+    P, B = W_in.shape[0], page_start.shape[0] - 1
+    if W_in.shape[1] != F or P < 1:
+        raise ValueError("%sinput.weight %s does not fit %d own features" % (prefix, tuple(W_in.shape), F))
+    geo = (prefix + "layers.0.geometry.weight") in params
+    geo_args = None
+    if geo:
+        if bboxes is None or tuple(bboxes.shape) != (N, 5):
+            raise ValueError("%slayers.*.geometry.weight: the geometry bias needs bboxes [%d, 5]" % (prefix, N))
+        _check(bboxes)
+        try:
+            img_h, img_w = (float(v) for v in page_size)
+        except (TypeError, ValueError):
+            raise ValueError("page_size must be (height, width) in pixels, got %r" % (page_size,))
+        if not (img_h > 0 and img_w > 0):
+            raise ValueError("page_size must be positive, got %r" % (page_size,))
+        geo_args = (bboxes, img_w, img_h)
+    x = _empty((N, P), h)
+    call("cova_sgemm", 0, 1, N, P, F, h, ldh, W_in, F, x, P, None, 0)
+    blocks = []
+    for l in range(layers):
+        p = "%slayers.%d." % (prefix, l)
+        Wqkv, W1 = params[p + "qkv.weight"], params[p + "ffn1.weight"]
+        M = W1.shape[0]
+        if tuple(Wqkv.shape) != (3 * P, P) or W1.shape[1] != P or tuple(params[p + "ffn2.weight"].shape) != (P, M):
+            raise ValueError("%s*: the layer's weights do not fit page_encoder_dim=%d" % (p, P))
+        b = dict(prefix=p, M=M, x1=x)
+        b["a"] = a = _empty((N, P), h)
+        b["mean1"], b["rstd1"] = layernorm_fwd(x, P, N, P, params[p + "norm1.weight"], params[p + "norm1.bias"], a, P)
+        b["qkv"] = qkv = _empty((N, 3 * P), h)
+        call("cova_sgemm", 0, 1, N, 3 * P, P, a, P, Wqkv, P, qkv, 3 * P, None, 0)
+        b["lse"] = lse = _empty((N, heads), h)
+        # rows outside every page are written by no attention kernel: they stay zero
+        b["O"] = O = torch.zeros((N, P), dtype=torch.float32, device=h.device)
+        if geo:
+            gw = params[p + "geometry.weight"]
+            if tuple(gw.shape) != (heads, 8):
+                raise ValueError("%sgeometry.weight %s does not fit %d heads" % (p, tuple(gw.shape), heads))
+            call("cova_page_attn_fwd_geo", qkv, 3 * P, page_start, geo_args[0], gw, geo_args[1], geo_args[2], B, N, P,
+                 heads, O, P, lse)
+        else:
+            call("cova_page_attn_fwd", qkv, 3 * P, page_start, B, N, P, heads, O, P, lse)
+        x2 = _empty((N, P), h)
+        x2.copy_(x)                                   # (a device copy: the stream at LN1's input is kept for its backward)
+        call("cova_sgemm", 0, 1, N, P, P, O, P, params[p + "out.weight"], P, x2, P, params[p + "out.bias"], 1)
+        b["x2"] = x2
+        b["m"] = m = _empty((N, P), h)
+        b["mean2"], b["rstd2"] = layernorm_fwd(x2, P, N, P, params[p + "norm2.weight"], params[p + "norm2.bias"], m, P)
+        b["z"] = z = _empty((N, M), h)
+        call("cova_sgemm", 0, 1, N, M, P, m, P, W1, P, z, M, params[p + "ffn1.bias"], 0)
+        b["f"] = f = _empty((N, M), h)
+        call("cova_gelu_fwd", z, M, N, M, f, M)
+        x = _empty((N, P), h)
+        x.copy_(x2)
+        call("cova_sgemm", 0, 1, N, P, M, f, M, params[p + "ffn2.weight"], M, x, P, params[p + "ffn2.bias"], 1)
+        blocks.append(b)
+    mean, rstd = layernorm_fwd(x, P, N, P, params[prefix + "norm.weight"], params[prefix + "norm.bias"], out, ldo)
+    sv = dict(h=h, ldh=ldh, N=N, F=F, P=P, B=B, heads=heads, layers=layers, blocks=blocks, x=x, mean=mean, rstd=rstd,
+              page_start=page_start, prefix=prefix)
+    if geo:
+        sv.update(bboxes=bboxes, img_w=geo_args[1], img_h=geo_args[2])
+    return sv
+
+
+def page_encoder_bwd(sv, g, ldg, params, dh, lddh, gout=None):
+    """g = dL/d(encoder columns) (rows at g + n*ldg).  Walks the blocks backwards: per Linear the two cova_sgemm (weight
+    gradient, data gradient), cova_colsum for out.bias / ffn1.bias / ffn2.bias, cova_gelu_bwd, cova_page_attn_bwd(_geo) and
+    cova_layernorm_bwd with ``res`` = the stream gradient, which is so read and written once per LayerNorm.  ACCUMULATES
+    dL/dh into dh; returns every parameter gradient."""
+    N, F, P, B, Hh, prefix = sv["N"], sv["F"], sv["P"], sv["B"], sv["heads"], sv["prefix"]
+    grads = {}
+
+    def buf(key, shape):
+        grads[key] = t = _gbuf(gout, key, shape, g)
+        return t
+
+    gx = _empty((N, P), g)                 # the gradient on the residual stream
+    layernorm_bwd(g, ldg, sv["x"], P, sv["mean"], sv["rstd"], params[prefix + "norm.weight"], N, P, None, gx, P,
+                  buf(prefix + "norm.weight", (P,)), buf(prefix + "norm.bias", (P,)))
+    for b in reversed(sv["blocks"]):
+        p, M = b["prefix"], b["M"]
+        # x3 = x2 + f ffn2.weight^T + ffn2.bias
+        call("cova_colsum", gx, P, N, P, buf(p + "ffn2.bias", (P,)))
+        call("cova_sgemm", 1, 0, P, M, N, gx, P, b["f"], M, buf(p + "ffn2.weight", (P, M)), M, None, 0)
+        df = _empty((N, M), g)
+        call("cova_sgemm", 0, 0, N, M, P, gx, P, params[p + "ffn2.weight"], M, df, M, None, 0)
+        dz = _empty((N, M), g)
+        call("cova_gelu_bwd", df, M, b["z"], M, N, M, dz, M)
+        call("cova_colsum", dz, M, N, M, buf(p + "ffn1.bias", (M,)))
+        call("cova_sgemm", 1, 0, M, P, N, dz, M, b["m"], P, buf(p + "ffn1.weight", (M, P)), P, None, 0)
+        dm = _empty((N, P), g)
+        call("cova_sgemm", 0, 0, N, P, M, dz, M, params[p + "ffn1.weight"], P, dm, P, None, 0)
+        layernorm_bwd(dm, P, b["x2"], P, b["mean2"], b["rstd2"], params[p + "norm2.weight"], N, P, gx, gx, P,
+                      buf(p + "norm2.weight", (P,)), buf(p + "norm2.bias", (P,)))
+        # x2 = x1 + O out.weight^T + out.bias
+        call("cova_colsum", gx, P, N, P, buf(p + "out.bias", (P,)))
+        call("cova_sgemm", 1, 0, P, P, N, gx, P, b["O"], P, buf(p + "out.weight", (P, P)), P, None, 0)
+        dO = dm                                # (dead by now: reuse)
+        call("cova_sgemm", 0, 0, N, P, P, gx, P, params[p + "out.weight"], P, dO, P, None, 0)
+        # rows outside every page are written by no attention kernel: their dqkv stays zero
+        dqkv = torch.zeros((N, 3 * P), dtype=torch.float32, device=g.device)
+        if "bboxes" in sv:                    # the forward took the geometry bias
+            ws = _empty((query("cova_page_attn_geo_workspace_floats", B, N, Hh),), g)
+            call("cova_page_attn_bwd_geo", dO, P, b["qkv"], 3 * P, b["O"], P, b["lse"], sv["page_start"], sv["bboxes"],
+                 params[p + "geometry.weight"], sv["img_w"], sv["img_h"], B, N, P, Hh, dqkv, 3 * P,
+                 buf(p + "geometry.weight", (Hh, 8)), ws)
+        else:
+            call("cova_page_attn_bwd", dO, P, b["qkv"], 3 * P, b["O"], P, b["lse"], sv["page_start"], B, N, P, Hh, dqkv,
+                 3 * P)
+        call("cova_sgemm", 1, 0, 3 * P, P, N, dqkv, 3 * P, b["a"], P, buf(p + "qkv.weight", (3 * P, P)), P, None, 0)
+        da = _empty((N, P), g)
+        call("cova_sgemm", 0, 0, N, P, 3 * P, dqkv, 3 * P, params[p + "qkv.weight"], P, da, P, None, 0)
+        layernorm_bwd(da, P, b["x1"], P, b["mean1"], b["rstd1"], params[p + "norm1.weight"], N, P, gx, gx, P,
+                      buf(p + "norm1.weight", (P,)), buf(p + "norm1.bias", (P,)))
+    call("cova_sgemm", 1, 0, P, F, N, gx, P, sv["h"], sv["ldh"], buf(prefix + "input.weight", (P, F)), F, None, 0)
+    call("cova_sgemm", 0, 0, N, F, P, gx, P, params[prefix + "input.weight"], F, dh, lddh, None, 1)
+    return grads
+
+
 # ------------------------------------------------------------------------------- decoder
 def dropout_fwd(x, ld, N, C, p, seed, mask=None):
     out = _empty((N, C), x)
@@ -1722,8 +1878,8 @@ def decoder_bwd(sv, dlogits, params, gout=None):
 def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_indices, training,
               seeds=(0, 0), masks=None, save=True, plan=None, visual_feats=None, page_size=None, page_start=None):
     """CoVA.forward (models.py:94-122) -> (logits [N,n_classes], saved-for-backward or None).
-    ``page_start`` (device int64 [B + 1], the pages' row offsets) is read by cfg["page_context_dim"] and
-    cfg["page_attention_dim"] only: the batch's table
+    ``page_start`` (device int64 [B + 1], the pages' row offsets) is read by cfg["page_context_dim"],
+    cfg["page_attention_dim"] and cfg["page_encoder_dim"] only: the batch's table
     when given, else derived on the device from the page column of ``bboxes`` and the page count of ``images``
     (page_start_of); a batch without either raises ValueError.
     ``page_size`` = (height, width) of the pages, read by cfg["edge_geometry"] only: by default ``images.shape[2:]``; a batch
@@ -1742,16 +1898,16 @@ def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_in
     Hd, A = cfg["bbox_hidden_dim"], cfg["n_additional_feat"]
     F = n_vis + Hd + A
     D = cfg["hidden_dim"] if cfg["use_context"] else 0
-    G, E = cfg.get("page_context_dim", 0), cfg.get("page_attention_dim", 0)
-    T = F + D + G + E
-    if G > 0 or E > 0:
-        page_start = page_start_of(bboxes, images, page_start, "page_context_dim" if G > 0 else "page_attention_dim")
+    G, E, P = cfg.get("page_context_dim", 0), cfg.get("page_attention_dim", 0), cfg.get("page_encoder_dim", 0)
+    T = F + D + G + E + P
+    if G > 0 or E > 0 or P > 0:
+        page_start = page_start_of(bboxes, images, page_start, _page_option(G, E))
     align = cfg.get("roi_op", "pool") == "align"
     save_conv = save and (plan is None or "convstack" in plan)
     feat, sv_conv = convstack_fwd(images, params, buffers, training, save_conv, lazy_out=not align)
     comb = _empty((N, T), images)
     scale = cfg.get("spatial_scale") or feat.shape[1] / images.shape[2]   # models.py:56
-    sv = dict(cfg=cfg, N=N, F=F, D=D, G=G, E=E, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=sv_conv, comb=comb,
+    sv = dict(cfg=cfg, N=N, F=F, D=D, G=G, E=E, P=P, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=sv_conv, comb=comb,
               page_size=page_size or cfg.get("page_size") or tuple(images.shape[2:]), page_start=page_start)
     if align:
         sv["roi"] = roialign_fwd(feat, bboxes, (PH, PW), scale, cfg.get("sampling_ratio", 2),
@@ -1764,7 +1920,7 @@ def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_in
 def _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks, save, sv):
     """Everything behind the visual columns of ``sv["comb"]``: positional encoder, additional features, GAT, decoder."""
     N, F, D, T, n_vis, Hd, A, comb = (sv[k] for k in ("N", "F", "D", "T", "n_vis", "Hd", "A", "comb"))
-    G, E = sv.get("G", 0), sv.get("E", 0)
+    G, E, P = sv.get("G", 0), sv.get("E", 0), sv.get("P", 0)
     if Hd > 0:
         sv["bbox"] = bbox_fwd(bboxes, params, buffers, training, comb[:, n_vis:], T)
     if A > 0:
@@ -1793,6 +1949,17 @@ def _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, t
         sv["page_attn"] = page_attn_fwd(comb, T, N, F, sv["page_start"], params, cfg.get("page_attention_heads", 1),
                                         comb[:, F + D + G:], T, bboxes=bboxes if geo else None,
                                         page_size=sv.get("page_size"))
+    if P > 0:
+        geo = bool(cfg.get("page_encoder_geometry", False))
+        if geo and sv.get("page_size") is None:
+            raise ValueError("page_encoder_geometry: a batch without images must carry page_size = (height, width) "
+                             "(or the configuration a 'page_size')")
+        if geo != ("page_encoder.layers.0.geometry.weight" in params):
+            raise ValueError("page_encoder_geometry=%r, but the parameters %s page_encoder.layers.0.geometry.weight"
+                             % (geo, "lack" if geo else "hold"))
+        sv["page_enc"] = page_encoder_fwd(comb, T, N, F, sv["page_start"], params, cfg.get("page_encoder_heads", 1),
+                                          cfg.get("page_encoder_layers", 1), comb[:, F + D + G + E:], T,
+                                          bboxes=bboxes if geo else None, page_size=sv.get("page_size"))
     logits, sv["dec"] = decoder_fwd(comb, N, T, params, buffers, training, cfg["drop_prob"], seeds,
                                     masks)
     return logits, (sv if save else None)
@@ -1834,12 +2001,12 @@ def _model_fwd_cached(cfg, params, buffers, bboxes, additional_feats, context_in
     Hd, A = cfg["bbox_hidden_dim"], cfg["n_additional_feat"]
     F = n_vis + Hd + A
     D = cfg["hidden_dim"] if cfg["use_context"] else 0
-    G, E = cfg.get("page_context_dim", 0), cfg.get("page_attention_dim", 0)
-    T = F + D + G + E
-    if G > 0 or E > 0:
-        page_start = page_start_of(bboxes, None, page_start, "page_context_dim" if G > 0 else "page_attention_dim")
+    G, E, P = cfg.get("page_context_dim", 0), cfg.get("page_attention_dim", 0), cfg.get("page_encoder_dim", 0)
+    T = F + D + G + E + P
+    if G > 0 or E > 0 or P > 0:
+        page_start = page_start_of(bboxes, None, page_start, _page_option(G, E))
     comb = _empty((N, T), bboxes)
-    sv = dict(cfg=cfg, N=N, F=F, D=D, G=G, E=E, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=None, roi=None, comb=comb,
+    sv = dict(cfg=cfg, N=N, F=F, D=D, G=G, E=E, P=P, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=None, roi=None, comb=comb,
               page_size=page_size or cfg.get("page_size"), page_start=page_start)
     call("cova_feat_rows_gather", table, table.shape[0], n_vis, row_ids, N, comb, T)
     return _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks, save, sv)
@@ -1863,6 +2030,9 @@ def model_bwd(sv, dlogits, params, gout=None, after_head=None, want_dimg=False, 
         grads.update(page_readout_bwd(sv["readout"], dcomb[:, F + D:], T, params, dcomb, T, gout))
     if sv.get("E", 0) > 0:               # after the readout's: the third to accumulate into dcomb[:, :F], in this order
         grads.update(page_attn_bwd(sv["page_attn"], dcomb[:, F + D + sv.get("G", 0):], T, params, dcomb, T, gout))
+    if sv.get("P", 0) > 0:               # after the page attention's: the fourth to accumulate into dcomb[:, :F], in this order
+        grads.update(page_encoder_bwd(sv["page_enc"], dcomb[:, F + D + sv.get("G", 0) + sv.get("E", 0):], T, params, dcomb,
+                                      T, gout))
     if A > 0 and (plan is None or "addl" in plan):
         st = sv["addl"]
         dz = _empty((N, A), dcomb)

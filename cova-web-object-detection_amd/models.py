@@ -22,7 +22,8 @@ import torch.nn as nn
 
 from . import engine
 from .weights import (EDGE_FEATURES, attention_of, backbone_channels, check_attention, check_attention_dropout,
-                      check_backbone_layers, check_page_attention, check_page_attention_geometry, check_page_context_dim)
+                      check_backbone_layers, check_page_attention, check_page_attention_geometry, check_page_context_dim,
+                      check_page_encoder)
 
 GAT_MAX_K = engine.GAT_MAX_K
 LOSS_MAX_CLASSES = engine.LOSS_MAX_CLASSES
@@ -554,13 +555,98 @@ class PageAttention(nn.Module):
         return (out, lse) if return_lse else out
 
 
+class _PageEncoderFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, layer, h, page_start, bboxes, page_size, *values):
+        h = _f32c(h)
+        N, F = h.shape
+        params = {"page_encoder." + k: _f32c(v) for k, v in zip(layer._keys, values)}
+        if layer.geometry_bias:
+            bboxes = _f32c(bboxes)
+        out = torch.empty((N, layer.dim), device=h.device)
+        ctx.sv = engine.page_encoder_fwd(h, F, N, F, _i64c(page_start), params, layer.heads, layer.n_layers, out, layer.dim,
+                                         bboxes=bboxes if layer.geometry_bias else None, page_size=page_size)
+        ctx.params, ctx.keys = params, layer._keys
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        sv = ctx.sv
+        dh = torch.zeros((sv["N"], sv["F"]), device=g.device)          # page_encoder_bwd accumulates
+        grads = engine.page_encoder_bwd(sv, g.contiguous(), sv["P"], ctx.params, dh, sv["F"])
+        return (None, dh, None, None, None) + tuple(grads["page_encoder." + k] for k in ctx.keys)
+
+
+class _PageEncoderBlock(nn.Module):
+    """Parameter holder of one pre-LN block: norm1, qkv, (geometry,) out, norm2, ffn1, ffn2 in state_dict order."""
+
+    def __init__(self, dim, heads, ffn_dim, geometry):
+        super().__init__()
+        self.norm1 = nn.LayerNorm(dim)
+        self.qkv = nn.Linear(dim, 3 * dim, bias=False)
+        if geometry:
+            self.geometry = nn.Linear(8, heads, bias=False)
+            nn.init.zeros_(self.geometry.weight)
+        self.out = nn.Linear(dim, dim)
+        self.norm2 = nn.LayerNorm(dim)
+        self.ffn1 = nn.Linear(dim, ffn_dim)
+        self.ffn2 = nn.Linear(ffn_dim, dim)
+
+    def forward(self, x):
+        raise RuntimeError("parameter container only; the block runs in libcova_hip.so (PageEncoder.forward)")
+
+
+class PageEncoder(nn.Module):
+    """Extension: an L-layer pre-LN transformer encoder (Vaswani et al. 2017; the pre-LN form of Xiong et al. 2020) over
+    the boxes of each page -- torch's ``nn.TransformerEncoderLayer(norm_first=True, activation="gelu", dropout=0)`` per
+    page with a zero ``in_proj_bias``, behind an input projection and in front of a final LayerNorm:
+        x = input(h)                                  Linear(in_features, dim), no bias (a LayerNorm follows)
+        per layer:  x = x + out(page attention of qkv(norm1(x)));   x = x + ffn2(GELU(ffn1(norm2(x))))
+        return norm(x)
+    The attention is PageAttention's (every box attends to ALL boxes of its page, ``heads`` heads, cova_page_attn_fwd);
+    ``geometry=True`` gives every layer the box-geometry bias of PageAttention(geometry=True) (``layers.<l>.geometry``,
+    Linear(8, heads), no bias, zero at construction; ``forward`` then needs ``bboxes`` [N, 5] and ``page_size`` = (height,
+    width)).  GELU is the exact (erf) form, eps = 1e-5.  There is no dropout inside the encoder, and the GAT's
+    ``attention_dropout`` and ``edge_geometry`` do not reach it.  ``forward(h [N, in_features], page_start int64 [B + 1])``
+    -> ``[N, dim]``; one autograd node over engine.page_encoder_fwd / page_encoder_bwd (cova_layernorm_*, cova_gelu_*,
+    cova_page_attn_*, cova_sgemm, cova_colsum)."""
+
+    def __init__(self, in_features, dim, heads=1, layers=1, ffn_dim=None, geometry=False):
+        super().__init__()
+        self.in_features = in_features
+        self.dim, self.heads, self.n_layers, self.ffn_dim, self.geometry_bias = check_page_encoder(dim, heads, layers,
+                                                                                                   ffn_dim, geometry)
+        if self.dim < 1:
+            raise ValueError("PageEncoder needs dim >= 4")
+        self.input = nn.Linear(in_features, self.dim, bias=False)
+        self.layers = nn.ModuleList(_PageEncoderBlock(self.dim, self.heads, self.ffn_dim, self.geometry_bias)
+                                    for _ in range(self.n_layers))
+        self.norm = nn.LayerNorm(self.dim)
+        self._keys = [k for k, _ in self.named_parameters()]
+
+    def forward(self, h, page_start, bboxes=None, page_size=None):
+        _require_cuda(h, page_start)
+        if self.geometry_bias:
+            if bboxes is None or page_size is None or bboxes.dim() != 2 or tuple(bboxes.shape) != (h.shape[0], 5):
+                raise ValueError("a PageEncoder with geometry=True needs bboxes [N, 5] and page_size = (height, width)")
+            _require_cuda(bboxes)
+        if h.dim() != 2 or h.shape[1] != self.in_features:
+            raise RuntimeError("expected h [N, %d], got %s" % (self.in_features, tuple(h.shape)))
+        if page_start.dim() != 1 or page_start.shape[0] < 1 or page_start.is_floating_point():
+            raise ValueError("page_start must hold B + 1 integer row offsets, got shape %s" % (tuple(page_start.shape),))
+        if h.shape[0] == 0:
+            return h.new_empty((0, self.dim))
+        return _PageEncoderFn.apply(self, h, page_start, bboxes, page_size, *[p for _, p in self.named_parameters()])
+
+
 class CoVA(nn.Module):
     def __init__(self, roi_output_size, img_H, n_classes, use_context=True, hidden_dim=384,
                  bbox_hidden_dim=32, n_additional_feat=0, drop_prob=0.2, class_names=None,
                  backbone="resnet18", n_heads=1, n_gat_layers=1, backbone_state_dict=None, roi_op="pool",
                  sampling_ratio=2, roi_aligned=False, backbone_layers=1, edge_geometry=False, attention="gat",
                  attention_dropout=0.0, page_context_dim=0, page_attention_dim=0, page_attention_heads=1,
-                 page_attention_geometry=False):
+                 page_attention_geometry=False, page_encoder_dim=0, page_encoder_heads=1, page_encoder_layers=1,
+                 page_encoder_ffn_dim=None, page_encoder_geometry=False):
         """The first nine arguments exactly as the reference's CoVA (models.py:10-34; called positionally
         at main.py:122-132).  Keyword-only-in-practice extensions, whose defaults are the reference's
         model: ``backbone`` 'resnet18' | 'resnet50' (torchvision ``children()[:-5]`` of either),
@@ -592,10 +678,21 @@ class CoVA(nn.Module):
         ``attention_dropout`` belong to the GAT and do not reach this layer.  With 0 nothing changes.
         ``page_attention_geometry=True`` (needs ``page_attention_dim`` > 0, else ValueError): the page attention's scores
         take a bias from the relative geometry of the two boxes (``page_attention.geometry.weight`` [Hh, 8], zero at
-        construction, directly behind ``page_attention.qkv.weight``); the page size is taken from ``images``."""
+        construction, directly behind ``page_attention.qkv.weight``); the page size is taken from ``images``.
+        ``page_encoder_dim=P`` (0 <= P <= 512, 0 = off; independent of ``use_context``, ``page_context_dim`` and
+        ``page_attention_dim``): a PageEncoder of the own features -- ``page_encoder_layers`` (1..8) pre-LN transformer
+        blocks of ``page_encoder_heads`` heads (the page attention's rule for P / Hh) and a feed-forward width
+        ``page_encoder_ffn_dim`` (a multiple of 4 in [4, 2048]; None: 2 P) -- gives every box P more columns behind the page
+        attention's (``page_encoder.*``, between ``page_attention`` and ``decoder`` in the state_dict).
+        ``page_encoder_geometry=True`` (needs P > 0) gives every layer's scores the box-geometry bias
+        (``page_encoder.layers.<l>.geometry.weight`` [Hh, 8], zero at construction).  No dropout inside the encoder;
+        ``edge_geometry`` and ``attention_dropout`` belong to the GAT and do not reach it.  With 0 nothing changes."""
         page_context_dim = check_page_context_dim(page_context_dim)
         page_attention_dim, page_attention_heads = check_page_attention(page_attention_dim, page_attention_heads)
         page_attention_geometry = check_page_attention_geometry(page_attention_geometry, page_attention_dim)
+        (page_encoder_dim, page_encoder_heads, page_encoder_layers, page_encoder_ffn_dim,
+         page_encoder_geometry) = check_page_encoder(page_encoder_dim, page_encoder_heads, page_encoder_layers,
+                                                     page_encoder_ffn_dim, page_encoder_geometry)
         check_backbone_layers(backbone, backbone_layers)
         check_attention(attention)
         attention_dropout = check_attention_dropout(attention_dropout)
@@ -662,8 +759,12 @@ class CoVA(nn.Module):
         if page_attention_dim > 0:
             self.page_attention = PageAttention(self.n_feat, page_attention_dim, page_attention_heads,
                                                 geometry=page_attention_geometry)
+        self.page_encoder_dim = page_encoder_dim
+        if page_encoder_dim > 0:
+            self.page_encoder = PageEncoder(self.n_feat, page_encoder_dim, page_encoder_heads, page_encoder_layers,
+                                            page_encoder_ffn_dim, page_encoder_geometry)
         self.n_total_feat = (self.n_feat + (self.hidden_dim if self.use_context else 0) + page_context_dim
-                             + page_attention_dim)
+                             + page_attention_dim + page_encoder_dim)
         self.decoder = nn.Sequential(nn.Dropout(drop_prob),
                                      nn.Linear(self.n_total_feat, self.n_total_feat),
                                      nn.BatchNorm1d(self.n_total_feat), nn.ReLU(),
@@ -679,7 +780,10 @@ class CoVA(nn.Module):
                          backbone_layers=backbone_layers, edge_geometry=bool(edge_geometry) and bool(use_context),
                          attention=attention, attention_dropout=attention_dropout if use_context else 0.0,
                          page_context_dim=page_context_dim, page_attention_dim=page_attention_dim,
-                         page_attention_heads=page_attention_heads, page_attention_geometry=page_attention_geometry)
+                         page_attention_heads=page_attention_heads, page_attention_geometry=page_attention_geometry,
+                         page_encoder_dim=page_encoder_dim, page_encoder_heads=page_encoder_heads,
+                         page_encoder_layers=page_encoder_layers, page_encoder_ffn_dim=page_encoder_ffn_dim,
+                         page_encoder_geometry=page_encoder_geometry)
         self._param_keys = [k for k, _ in self.named_parameters()]
         self._conv_keys = [k for k in self._param_keys if k.startswith("convnet.")]
         self._bbox_keys = [k for k in self._param_keys if k.startswith("bbox_feat_encoder.")]

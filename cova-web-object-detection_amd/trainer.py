@@ -21,8 +21,12 @@ import os
 import torch
 
 from . import engine
-from .weights import (PAGE_ATTENTION_GEO_KEY, PAGE_ATTENTION_KEY, PAGE_READOUT_KEYS, check_attention_dropout,
-                      check_page_attention, check_page_attention_geometry, check_page_context_dim, state_dict_spec)
+from .weights import (PAGE_ATTENTION_GEO_KEY, PAGE_ATTENTION_KEY, PAGE_ENCODER_INPUT_KEY, PAGE_READOUT_KEYS,
+                      check_attention_dropout, check_page_attention, check_page_attention_geometry, check_page_context_dim,
+                      check_page_encoder, page_encoder_layer_prefix, state_dict_spec)
+
+_PAGE_ENCODER_OPTIONS = ("page_encoder_dim", "page_encoder_heads", "page_encoder_layers", "page_encoder_ffn_dim",
+                         "page_encoder_geometry")
 
 _BUF_SUFFIX = ("running_mean", "running_var", "num_batches_tracked")
 
@@ -335,8 +339,13 @@ class HotPathTrainer:
         if "page_attention_geometry" in cfg:
             self.cfg["page_attention_geometry"] = check_page_attention_geometry(
                 cfg["page_attention_geometry"], self.cfg.get("page_attention_dim", 0))
+        if any(k in cfg for k in _PAGE_ENCODER_OPTIONS):
+            self.cfg.update(zip(_PAGE_ENCODER_OPTIONS, check_page_encoder(
+                cfg.get("page_encoder_dim", 0), cfg.get("page_encoder_heads", 1), cfg.get("page_encoder_layers", 1),
+                cfg.get("page_encoder_ffn_dim"), cfg.get("page_encoder_geometry", False))))
         self._check_page_readout(state_dict)        # (before any device work)
         self._check_page_attention(state_dict)
+        self._check_page_encoder(state_dict)
         self.device = torch.device(device)
         spec = state_dict_spec(**{k: cfg[k] for k in ("roi_output_size", "n_classes", "use_context",
                                                      "hidden_dim", "bbox_hidden_dim", "n_additional_feat",
@@ -344,7 +353,8 @@ class HotPathTrainer:
                                                      "edge_geometry", "attention", "page_context_dim",
                                                      "page_attention_dim", "page_attention_heads",
                                                      "page_attention_geometry")
-                                  if k in cfg})
+                                  if k in cfg},
+                               **{k: self.cfg[k] for k in _PAGE_ENCODER_OPTIONS if k in self.cfg})
         pshapes = OrderedDict((k, s) for k, s in spec if is_param_key(k))
         self.pbucket = FlatBucket(pshapes, self.device)
         self.gbucket = FlatBucket(pshapes, self.device)
@@ -440,6 +450,48 @@ class HotPathTrainer:
         if geo and torch.is_tensor(gw) and tuple(gw.shape) != (Hh, 8):
             raise ValueError("this trainer was configured with page_attention_geometry=True and page_attention_heads=%d, "
                              "the state_dict's %s has shape %s" % (Hh, PAGE_ATTENTION_GEO_KEY, tuple(gw.shape)))
+
+    def _check_page_encoder(self, state_dict):
+        """As _check_page_attention, for the ``page_encoder.*`` entries: a checkpoint loads only into the width, depth,
+        feed-forward width and geometry option it was trained with, and the message names the option."""
+        P, L = self.cfg.get("page_encoder_dim", 0), self.cfg.get("page_encoder_layers", 1)
+        have = [k for k in state_dict if isinstance(k, str) and k.startswith("page_encoder.")]
+        tail = ": a checkpoint loads into the page encoder it was trained with only"
+        if P == 0:
+            if have:
+                raise ValueError("this trainer was configured without a page encoder (page_encoder_dim=0), the state_dict "
+                                 "holds %s%s" % (have[:2], tail))
+            return
+        w = state_dict.get(PAGE_ENCODER_INPUT_KEY)
+        if w is None:
+            raise ValueError("this trainer was configured with page_encoder_dim=%d, the state_dict lacks %s%s"
+                             % (P, PAGE_ENCODER_INPUT_KEY, tail))
+        if torch.is_tensor(w) and (w.dim() != 2 or w.shape[0] != P):
+            raise ValueError("this trainer was configured with page_encoder_dim=%d, the state_dict's %s has shape %s "
+                             "(page_encoder_dim=%s)" % (P, PAGE_ENCODER_INPUT_KEY, tuple(w.shape),
+                                                        w.shape[0] if w.dim() == 2 else "?"))
+        depth = 0
+        while page_encoder_layer_prefix(depth) + "qkv.weight" in state_dict:
+            depth += 1
+        if depth != L:
+            raise ValueError("this trainer was configured with page_encoder_layers=%d, the state_dict holds %d layer(s) "
+                             "under page_encoder.layers (page_encoder_layers=%d)%s" % (L, depth, depth, tail))
+        M, Hh = self.cfg["page_encoder_ffn_dim"], self.cfg.get("page_encoder_heads", 1)
+        geo = bool(self.cfg.get("page_encoder_geometry", False))
+        for l in range(L):
+            k = page_encoder_layer_prefix(l) + "ffn1.weight"
+            w = state_dict.get(k)
+            if torch.is_tensor(w) and (w.dim() != 2 or w.shape[0] != M):
+                raise ValueError("this trainer was configured with page_encoder_ffn_dim=%d, the state_dict's %s has shape "
+                                 "%s (page_encoder_ffn_dim=%s)" % (M, k, tuple(w.shape), w.shape[0] if w.dim() == 2 else "?"))
+            k = page_encoder_layer_prefix(l) + "geometry.weight"
+            gw = state_dict.get(k)
+            if geo != (gw is not None):
+                raise ValueError("this trainer was configured with page_encoder_geometry=%r, the state_dict %s %s%s"
+                                 % (geo, "lacks" if geo else "holds", k, tail))
+            if geo and torch.is_tensor(gw) and tuple(gw.shape) != (Hh, 8):
+                raise ValueError("this trainer was configured with page_encoder_geometry=True and page_encoder_heads=%d, "
+                                 "the state_dict's %s has shape %s" % (Hh, k, tuple(gw.shape)))
 
     def _flat_buffers(self, spec):
         """Live BatchNorm buffers of an averaging trainer -> {key: view}: ``bbucket`` (float32, running_mean /
@@ -848,6 +900,7 @@ class HotPathTrainer:
         self._not_averaged("load_state_dict")
         self._check_page_readout(state_dict)
         self._check_page_attention(state_dict)
+        self._check_page_encoder(state_dict)
         missing = [k for k in list(self.params) + list(self.buffers) if k not in state_dict]
         # sizes are part of the validation every rank agrees on BEFORE any copy / broadcast: a tensor of the wrong size on
         # one rank raising inside copy_ would leave the other ranks blocked in dist.broadcast

@@ -52,26 +52,31 @@ PAGE_ATTENTION_MAX_HEAD = 128        # columns of one head (PA_MAX_DH)
 PAGE_ATTENTION_KEY = "page_attention.qkv.weight"
 
 
-def check_page_attention(e, heads=1):
-    """Width and head count of the page self-attention (cova_page_attn_fwd): E an int in [0, 512] (0 = off), Hh an int >= 1
-    that divides E, the head width E / Hh a multiple of 4 in [4, 128] -> (E, Hh)."""
-    for name, v in (("page_attention_dim", e), ("page_attention_heads", heads)):
+def _check_width_and_heads(e, heads, dim_name, heads_name, off):
+    """The rule the page attention kernels set for a width and its head count (cova_page_attn_fwd), shared by every layer
+    that runs them: E an int in [0, 512] (0 = off), Hh an int >= 1 that divides E, E / Hh a multiple of 4 in [4, 128]."""
+    for name, v in ((dim_name, e), (heads_name, heads)):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
             raise ValueError("%s must be an integer, got %r" % (name, v))
     e, heads = int(e), int(heads)
     if not 0 <= e <= PAGE_ATTENTION_MAX:
-        raise ValueError("page_attention_dim must be an integer in [0, %d] (0: no page attention), got %r"
-                         % (PAGE_ATTENTION_MAX, e))
+        raise ValueError("%s must be an integer in [0, %d] (0: %s), got %r" % (dim_name, PAGE_ATTENTION_MAX, off, e))
     if heads < 1:
-        raise ValueError("page_attention_heads must be at least 1, got %r" % (heads,))
+        raise ValueError("%s must be at least 1, got %r" % (heads_name, heads))
     if e > 0:
         if e % heads:
-            raise ValueError("page_attention_heads=%d does not divide page_attention_dim=%d" % (heads, e))
+            raise ValueError("%s=%d does not divide %s=%d" % (heads_name, heads, dim_name, e))
         dh = e // heads
         if dh % 4 or not 4 <= dh <= PAGE_ATTENTION_MAX_HEAD:
-            raise ValueError("page_attention_dim / page_attention_heads = %d: the head width must be a multiple of 4 in "
-                             "[4, %d]" % (dh, PAGE_ATTENTION_MAX_HEAD))
+            raise ValueError("%s / %s = %d: the head width must be a multiple of 4 in "
+                             "[4, %d]" % (dim_name, heads_name, dh, PAGE_ATTENTION_MAX_HEAD))
     return e, heads
+
+
+def check_page_attention(e, heads=1):
+    """Width and head count of the page self-attention (cova_page_attn_fwd): E an int in [0, 512] (0 = off), Hh an int >= 1
+    that divides E, the head width E / Hh a multiple of 4 in [4, 128] -> (E, Hh)."""
+    return _check_width_and_heads(e, heads, "page_attention_dim", "page_attention_heads", "no page attention")
 
 
 PAGE_ATTENTION_GEO_KEY = "page_attention.geometry.weight"
@@ -85,6 +90,59 @@ def check_page_attention_geometry(geometry, e):
         raise ValueError("page_attention_geometry=True needs page_attention_dim > 0 (the bias belongs to the page "
                          "attention's scores), got page_attention_dim=%r" % (e,))
     return bool(geometry)
+
+
+PAGE_ENCODER_MAX_LAYERS = 8
+PAGE_ENCODER_MAX_FFN = 2048          # columns of the feed-forward part (a multiple of 4: the float4 rows of cova_gelu_fwd)
+PAGE_ENCODER_EPS = 1e-5              # nn.LayerNorm's default
+PAGE_ENCODER_INPUT_KEY = "page_encoder.input.weight"
+PAGE_ENCODER_NORM_KEYS = ("page_encoder.norm.weight", "page_encoder.norm.bias")
+
+
+def check_page_encoder(dim, heads=1, layers=1, ffn_dim=None, geometry=False):
+    """The page encoder's options -> (P, Hh, L, M, geometry).  P and Hh follow the page attention's rule
+    (its kernels run every layer); L an int in [1, 8], validated with P = 0 too; M (None: 2 P) a multiple of 4 in [4, 2048];
+    ``geometry`` a bool that needs P > 0."""
+    dim, heads = _check_width_and_heads(dim, heads, "page_encoder_dim", "page_encoder_heads", "no page encoder")
+    if isinstance(layers, bool) or not isinstance(layers, (int, np.integer)) or not 1 <= layers <= PAGE_ENCODER_MAX_LAYERS:
+        raise ValueError("page_encoder_layers must be an integer in [1, %d], got %r" % (PAGE_ENCODER_MAX_LAYERS, layers))
+    if ffn_dim is None or (dim == 0 and not isinstance(ffn_dim, bool) and isinstance(ffn_dim, (int, np.integer)) and ffn_dim == 0):
+        ffn_dim = 2 * dim                  # (0 with P = 0 is this function's own result: a checked tuple passes again)
+    elif (isinstance(ffn_dim, bool) or not isinstance(ffn_dim, (int, np.integer)) or ffn_dim % 4
+          or not 4 <= ffn_dim <= PAGE_ENCODER_MAX_FFN):
+        raise ValueError("page_encoder_ffn_dim must be a multiple of 4 in [4, %d] (None: 2 * page_encoder_dim), got %r"
+                         % (PAGE_ENCODER_MAX_FFN, ffn_dim))
+    if not isinstance(geometry, (bool, np.bool_)):
+        raise ValueError("page_encoder_geometry must be a bool, got %r" % (geometry,))
+    if geometry and dim <= 0:
+        raise ValueError("page_encoder_geometry=True needs page_encoder_dim > 0 (the bias belongs to the encoder's "
+                         "attention scores), got page_encoder_dim=%r" % (dim,))
+    return dim, heads, int(layers), int(ffn_dim), bool(geometry)
+
+
+def page_encoder_layer_prefix(l):
+    return "page_encoder.layers.%d." % l
+
+
+def page_encoder_entries(n_feat, dim, heads, layers, ffn_dim, geometry):
+    """Ordered (key, shape) list of the page encoder: the input projection, per layer norm1, qkv, (geometry,) out, norm2,
+    ffn1, ffn2, then the final norm."""
+    spec = [(PAGE_ENCODER_INPUT_KEY, (dim, n_feat))]
+    for l in range(layers):
+        p = page_encoder_layer_prefix(l)
+        spec += [(p + "norm1.weight", (dim,)), (p + "norm1.bias", (dim,)), (p + "qkv.weight", (3 * dim, dim))]
+        if geometry:
+            spec.append((p + "geometry.weight", (heads, EDGE_FEATURES)))
+        spec += [(p + "out.weight", (dim, dim)), (p + "out.bias", (dim,)),
+                 (p + "norm2.weight", (dim,)), (p + "norm2.bias", (dim,)),
+                 (p + "ffn1.weight", (ffn_dim, dim)), (p + "ffn1.bias", (ffn_dim,)),
+                 (p + "ffn2.weight", (dim, ffn_dim)), (p + "ffn2.bias", (dim,))]
+    return spec + [(PAGE_ENCODER_NORM_KEYS[0], (dim,)), (PAGE_ENCODER_NORM_KEYS[1], (dim,))]
+
+
+def is_layernorm_key(key):
+    """A LayerNorm affine parameter of the page encoder (``...norm1.``, ``...norm2.``, ``page_encoder.norm.``)."""
+    return key.startswith("page_encoder.") and key.rsplit(".", 2)[-2] in ("norm", "norm1", "norm2")
 
 
 def attention_of(weight, D, prefix="gat."):
@@ -139,7 +197,8 @@ def gat_prefixes(n_heads=1, n_gat_layers=1):
 def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=384,
                     bbox_hidden_dim=32, n_additional_feat=0, backbone="resnet18", n_heads=1,
                     n_gat_layers=1, backbone_layers=1, edge_geometry=False, attention="gat", page_context_dim=0,
-                    page_attention_dim=0, page_attention_heads=1, page_attention_geometry=False):
+                    page_attention_dim=0, page_attention_heads=1, page_attention_geometry=False, page_encoder_dim=0,
+                    page_encoder_heads=1, page_encoder_layers=1, page_encoder_ffn_dim=None, page_encoder_geometry=False):
     """Ordered (key, shape) list, identical to ``reference CoVA(...).state_dict()`` for the defaults.
 
     Extensions (BASELINE.json configs[2], configs[4]; absent from the reference, defaults keep its
@@ -161,12 +220,21 @@ def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidde
     [3E, n_feat], the same shape for every ``page_attention_heads``; the decoder is E columns wider;
     ``page_attention_geometry=True`` (needs ``page_attention_dim`` > 0) = ``page_attention.geometry.weight``
     [page_attention_heads, 8] directly behind ``page_attention.qkv.weight``: per head the weights of the relative-geometry
-    bias of the attention scores (cova_page_attn_fwd_geo); the decoder's width is unchanged."""
+    bias of the attention scores (cova_page_attn_fwd_geo); the decoder's width is unchanged;
+    ``page_encoder_dim=P`` > 0 = the page encoder (independent of ``use_context``, ``page_context_dim`` and
+    ``page_attention_dim``): behind the page attention's entries and in front of the decoder's,
+    ``page_encoder.input.weight`` [P, n_feat], then for each of ``page_encoder_layers`` layers under
+    ``page_encoder.layers.<l>.``: ``norm1.weight`` / ``.bias`` [P], ``qkv.weight`` [3P, P], ``geometry.weight``
+    [page_encoder_heads, 8] (``page_encoder_geometry=True`` only), ``out.weight`` [P, P], ``out.bias`` [P], ``norm2.weight`` /
+    ``.bias`` [P], ``ffn1.weight`` [M, P], ``ffn1.bias`` [M], ``ffn2.weight`` [P, M], ``ffn2.bias`` [P] with M =
+    ``page_encoder_ffn_dim`` (None: 2 P), then ``page_encoder.norm.weight`` / ``.bias`` [P]; the decoder is P columns wider."""
     check_backbone_layers(backbone, backbone_layers)
     check_attention(attention)
     page_context_dim = check_page_context_dim(page_context_dim)
     page_attention_dim, page_attention_heads = check_page_attention(page_attention_dim, page_attention_heads)
     page_attention_geometry = check_page_attention_geometry(page_attention_geometry, page_attention_dim)
+    enc = check_page_encoder(page_encoder_dim, page_encoder_heads, page_encoder_layers, page_encoder_ffn_dim,
+                             page_encoder_geometry)
     c = BACKBONE_CHANNELS
     spec = [("convnet.0.weight", (c, 3, 7, 7))]
     spec += _bn_entries("convnet.1.", c)
@@ -234,6 +302,9 @@ def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidde
         if page_attention_geometry:
             spec.append((PAGE_ATTENTION_GEO_KEY, (page_attention_heads, EDGE_FEATURES)))
         n_total += page_attention_dim
+    if enc[0] > 0:
+        spec += page_encoder_entries(n_feat, *enc)
+        n_total += enc[0]
     spec += [("decoder.1.weight", (n_total, n_total)), ("decoder.1.bias", (n_total,))]
     spec += _bn_entries("decoder.2.", n_total)
     spec += [("decoder.5.weight", (n_classes, n_total)), ("decoder.5.bias", (n_classes,))]
@@ -249,7 +320,9 @@ def seeded_state_dict(seed=123, logit_gain=1.0, **cfg):
     the last Linear so that integer-prediction tests have decisive logit margins.
     ``edge_layer.weight`` (edge_geometry=True) starts at ZERO without drawing from the stream: a fresh edge-aware model
     computes what the plain model of the same seed computes.  ``page_attention.geometry.weight``
-    (page_attention_geometry=True) starts at zero in the same way.
+    (page_attention_geometry=True) starts at zero in the same way, and so does every ``geometry.weight`` of the page
+    encoder (page_encoder_geometry=True).  The page encoder's LayerNorm weights and biases follow the BatchNorm affine rule
+    (away from 1 and 0).
     """
     rs = np.random.RandomState(seed)
     spec = state_dict_spec(**cfg)
@@ -257,11 +330,12 @@ def seeded_state_dict(seed=123, logit_gain=1.0, **cfg):
     sd = OrderedDict()
     for key, shape in spec:
         prefix, leaf = key.rsplit(".", 1)
-        is_bn = prefix in bn_prefixes
+        is_bn = prefix in bn_prefixes or is_layernorm_key(key)
         if leaf == "num_batches_tracked":
             sd[key] = torch.tensor(0, dtype=torch.long)
             continue
-        if prefix.endswith("edge_layer") or key == PAGE_ATTENTION_GEO_KEY:
+        if prefix.endswith("edge_layer") or key == PAGE_ATTENTION_GEO_KEY or (
+                key.startswith("page_encoder.") and key.endswith("geometry.weight")):
             sd[key] = torch.zeros(shape, dtype=torch.float32)
             continue
         if leaf == "running_mean":

@@ -779,6 +779,42 @@ int cova_page_attn_bwd_geo(const float *g, int ldg, const float *qkv, int ldq, c
                            const float *lse /*[N,Hh]*/, const int64_t *page_start /*[B+1]*/, const float *bboxes /*[N,5]*/,
                            const float *geo_w /*[Hh,8]*/, float img_w, float img_h, int B, int N, int E, int Hh, float *dqkv,
                            int lddq, float *d_geo_w /*[Hh,8]*/, float *workspace, void *stream);
+/* ---- row kernels of the page encoder (page_encoder.hip; opt-in: CoVA(page_encoder_dim=P)) ----
+ * LayerNorm over the C channels of each of R rows (rows at x + r*ldx), float32:
+ *   mean_r = sum_c x_rc / C,  rstd_r = 1 / sqrt(sum_c (x_rc - mean_r)^2 / C + eps)   (the biased variance, formed in TWO
+ *   passes over the row, which a wave holds in registers: never E[x^2] - mean^2),
+ *   out_rc = ((x_rc - mean_r) * rstd_r) * weight_c + bias_c       (the last two operations one fma)
+ * cova_layernorm_fwd writes out (rows at out + r*ldo), mean [R] and rstd [R].
+ * cova_layernorm_bwd, given g = dL/dout (rows at g + r*ldg), with xhat = (x - mean) * rstd re-formed from the saved mean
+ * and rstd by the forward's own operations and gw = g * weight:
+ *   dx_rc = (res ? res_rc : 0) + rstd_r * ((gw_rc - sum_c gw_rc / C) - xhat_rc * (sum_c gw_rc xhat_rc / C))
+ *   dweight_c = sum_r g_rc xhat_rc,  dbias_c = sum_r g_rc                 every entry of [C] written
+ * res (nullable; rows at res + r*ldr) is the gradient already on the residual stream: the add is fused, and res may BE dx
+ * (in place: an element is read and written by the one lane that owns it).  g and x must not alias dx.
+ * One wave per row, lanes over channels: float4 chunks lane, lane + 64 when C % 4 == 0 and every base and leading
+ * dimension is 16-byte aligned, scalar channels otherwise; no LDS in the forward, LDS only for the wave combine in the
+ * backward.  Orders (all f32): a row sum is a lane's channels ascending (plain adds; an fma chain for the two sums of
+ * products), then the xor butterfly (offsets 32 .. 1).  dweight / dbias: a block of four waves owns the rows
+ * [32 b, 32 b + 32); wave w adds the rows 32 b + w, + 4, ... ascending, the waves combine in wave order into the
+ * workspace [blocks][2][C], and a fold launch sums the blocks ascending.  cova_layernorm_workspace_floats(R, C) =
+ * ceil(R / 32) * 2 * C floats; 0 for R <= 0 or C outside [1, 512] (a negative value for a count beyond an int).  Every
+ * workspace entry is written before it is read.  Plain stores only, no host read: every order is a function of (R, C) alone, so
+ * reruns are bit-identical, and a row's out, mean, rstd and dx do not depend on the rows around it.
+ * 1 <= C <= 512, R >= 0, eps >= 0, ld* >= C, else COVA_ERR_BAD_ARG before anything is launched; R == 0 launches nothing and
+ * needs no pointer; otherwise a NULL operand (res excepted) is COVA_ERR_BAD_ARG.  Forward: one launch; backward: two.
+ * GELU, exact (erf) form, elementwise over R rows of C values:
+ *   cova_gelu_fwd: out = 0.5 z (1 + erff(z / sqrt 2));  cova_gelu_bwd: dz = g (0.5 (1 + erff(z / sqrt 2)) + z expf(-z^2 / 2) / sqrt(2 pi))
+ * z == 0 gives out == 0 and dz == 0.5 g exactly.  float4 under the alignment rule above, scalar otherwise; one grid-stride
+ * launch each.  C >= 1, R >= 0, ld* >= C, else COVA_ERR_BAD_ARG; R == 0 launches nothing and needs no pointer; otherwise a
+ * NULL operand is COVA_ERR_BAD_ARG.  The operands of one call must not alias. */
+int cova_layernorm_workspace_floats(int R, int C);
+int cova_layernorm_fwd(const float *x, int ldx, int R, int C, const float *weight /*[C]*/, const float *bias /*[C]*/,
+                       float eps, float *out, int ldo, float *mean /*[R]*/, float *rstd /*[R]*/, void *stream);
+int cova_layernorm_bwd(const float *g, int ldg, const float *x, int ldx, const float *mean /*[R]*/,
+                       const float *rstd /*[R]*/, const float *weight /*[C]*/, int R, int C, const float *res /*nullable*/,
+                       int ldr, float *dx, int lddx, float *dweight /*[C]*/, float *dbias /*[C]*/, float *ws, void *stream);
+int cova_gelu_fwd(const float *z, int ldz, long long R, int C, float *out, int ldo, void *stream);
+int cova_gelu_bwd(const float *g, int ldg, const float *z, int ldz, long long R, int C, float *dz, int lddz, void *stream);
 /* evaluation decision (train.py:131-153): per page and class column, page-local indices of the k
  * highest-scoring boxes, best first; page_start [n_pages+1] are box offsets; out [n_pages,NC,k] */
 int cova_page_class_topk(const float *logits, const int64_t *page_start, int n_pages, int NC, int k,
