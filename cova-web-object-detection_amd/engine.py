@@ -12,7 +12,7 @@ import os
 import torch
 
 from . import _lib
-from .weights import BACKBONE_CHANNELS as C64
+from .weights import BACKBONE_CHANNELS as C64, CONTEXT_LAYERS, head_layout
 
 GAT_MAX_K = 1024       # COVA_GAT_MAX_K of csrc/common.h: neighbour slots per node (up to sixteen 64-lane passes of a wavefront)
 
@@ -165,10 +165,8 @@ def check_batch(cfg, images, bboxes, additional_feats, context_indices, training
                              % (GAT_MAX_K, GAT_MAX_K // 2))
     if N == 1:
         # torch.nn.functional.batch_norm's _verify_batch_size, hit by the first train-mode BatchNorm1d of the forward
-        T = (backbone_feat(cfg) + cfg["bbox_hidden_dim"] + A + (cfg["hidden_dim"] if cfg["use_context"] else 0)
-             + cfg.get("page_context_dim", 0) + cfg.get("page_attention_dim", 0) + cfg.get("page_encoder_dim", 0))
         for width, prefix in ((cfg["bbox_hidden_dim"], "bbox_feat_encoder.1."), (A, "bn_additional_feat."),
-                              (T, "decoder.2.")):
+                              (head_layout(cfg, backbone_feat(cfg)).T, "decoder.2.")):
             if width and is_train(training, prefix):
                 raise ValueError("Expected more than 1 value per channel when training, got input size "
                                  "torch.Size([1, %d])" % width)
@@ -1296,18 +1294,24 @@ def _adjacent(a, b):
             a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr())
 
 
-def edge_geometry(bboxes, ctx, page_size):
-    """phi [N, K, 8]: the relative geometry of every edge of the context table (include/cova_hip.h, cova_edge_geometry).
-    ``page_size`` = (height, width) of the pages in pixels, as ``images.shape[2:]``.  One launch per batch; every head
-    and layer of the GAT stack shares the result."""
-    _check(bboxes)
-    _check(ctx, torch.int64)
+def _page_hw(page_size):
+    """``page_size`` = (height, width) of the pages in pixels, as ``images.shape[2:]`` -> two positive floats."""
     try:
         H, W = (float(v) for v in page_size)
     except (TypeError, ValueError):
         raise ValueError("page_size must be (height, width) in pixels, got %r" % (page_size,))
     if not (H > 0 and W > 0):
         raise ValueError("page_size must be positive, got %r" % (page_size,))
+    return H, W
+
+
+def edge_geometry(bboxes, ctx, page_size):
+    """phi [N, K, 8]: the relative geometry of every edge of the context table (include/cova_hip.h, cova_edge_geometry).
+    ``page_size`` = (height, width) of the pages in pixels, as ``images.shape[2:]``.  One launch per batch; every head
+    and layer of the GAT stack shares the result."""
+    _check(bboxes)
+    _check(ctx, torch.int64)
+    H, W = _page_hw(page_size)
     N, K = ctx.shape
     phi = _empty((N, K, 8), bboxes)
     call("cova_edge_geometry", bboxes, ctx, N, K, W, H, phi)
@@ -1556,9 +1560,13 @@ def page_start_of(bboxes, images, page_start=None, option="page_context_dim"):
     return torch.searchsorted(bboxes[:, 0].contiguous(), pages)
 
 
-def _page_option(G, E):
-    """The cfg entry a missing page table is reported under: the first page layer that is on."""
-    return "page_context_dim" if G > 0 else "page_attention_dim" if E > 0 else "page_encoder_dim"
+def _linear_bwd(dy, ldy, x, ldx, W, N, n_out, n_in, db, dW, dx, lddx, accumulate):
+    """Backward of y = x W^T (+ b) over N rows, W [n_out, n_in]: db = column sums of dy (cova_colsum; ``db`` None: no bias),
+    dW = dy^T x, and dx = dy W written, or with ``accumulate`` added to what dx holds (cova_sgemm twice)."""
+    if db is not None:
+        call("cova_colsum", dy, ldy, N, n_out, db)
+    call("cova_sgemm", 1, 0, n_out, n_in, N, dy, ldy, x, ldx, dW, n_in, None, 0)
+    call("cova_sgemm", 0, 0, N, n_in, n_out, dy, ldy, W, n_in, dx, lddx, None, 1 if accumulate else 0)
 
 
 def page_readout_fwd(h, ldh, N, F, page_start, params, out, ldo, prefix="page_readout."):
@@ -1590,12 +1598,54 @@ def page_readout_bwd(sv, g, ldg, params, dh, lddh, gout=None):
     call("cova_page_readout_bwd", g, ldg, sv["P"], G, sv["u"], sv["beta"], sv["r"], aw, sv["page_start"], B, N, G,
          LEAKY_SLOPE, dP, G, daw, dab, ws)
     dW = _gbuf(gout, prefix + "W.weight", (G, F), g)
-    call("cova_sgemm", 1, 0, G, F, N, dP, G, sv["h"], sv["ldh"], dW, F, None, 0)
-    call("cova_sgemm", 0, 0, N, F, G, dP, G, W, F, dh, lddh, None, 1)
+    _linear_bwd(dP, G, sv["h"], sv["ldh"], W, N, G, F, None, dW, dh, lddh, True)
     return {prefix + "W.weight": dW, prefix + "attention_layer.weight": daw, prefix + "attention_layer.bias": dab}
 
 
 # ------------------------------------------------------------------------------- page self-attention
+# The attention core: what the stand-alone layer and every block of the page encoder share.  ``geo`` = (geometry.weight
+# [heads, 8], bboxes, img_w, img_h) turns the box-geometry bias on (the _geo kernels), None leaves it off.
+def _page_geometry(bboxes, N, page_size, what):
+    """The inputs of the geometry bias -> (bboxes, img_w, img_h): ``bboxes`` dense float32 [N, 5] on the device and
+    ``page_size`` = (height, width) in pixels.  ``what`` names the weight that needs them."""
+    if bboxes is None or tuple(bboxes.shape) != (N, 5):
+        raise ValueError("%s: the geometry bias needs bboxes [%d, 5]" % (what, N))
+    _check(bboxes)
+    img_h, img_w = _page_hw(page_size)
+    return bboxes, img_w, img_h
+
+
+def _page_attn_core_fwd(qkv, ld, width, heads, page_start, geo, out, ldo, what=""):
+    """cova_page_attn_fwd(_geo) on the rows [Q | K | V] at qkv + n*ld -> lse [N, heads]; the output rows go to
+    out + n*ldo (``width`` columns).  Rows outside every page are written by neither kernel."""
+    N, B = qkv.shape[0], page_start.shape[0] - 1
+    lse = _empty((N, heads), qkv)
+    if geo is None:
+        call("cova_page_attn_fwd", qkv, ld, page_start, B, N, width, heads, out, ldo, lse)
+        return lse
+    gw, bboxes, img_w, img_h = geo
+    if tuple(gw.shape) != (heads, 8):
+        raise ValueError("%sgeometry.weight %s does not fit %d heads" % (what, tuple(gw.shape), heads))
+    call("cova_page_attn_fwd_geo", qkv, ld, page_start, bboxes, gw, img_w, img_h, B, N, width, heads, out, ldo, lse)
+    return lse
+
+
+def _page_attn_core_bwd(g, ldg, qkv, ld, out, ldo, lse, width, heads, page_start, geo, dgeo):
+    """cova_page_attn_bwd(_geo) -> dqkv [N, 3 width]; with ``geo`` the geometry weight's gradient goes to ``dgeo`` (the
+    kernel's workspace comes from the allocator).  dqkv is allocated here, as ZEROS: the kernels write the rows inside
+    pages only, and both callers run GEMMs over all N rows of it."""
+    N, B = qkv.shape[0], page_start.shape[0] - 1
+    dqkv = torch.zeros((N, 3 * width), dtype=torch.float32, device=g.device)
+    if geo is None:
+        call("cova_page_attn_bwd", g, ldg, qkv, ld, out, ldo, lse, page_start, B, N, width, heads, dqkv, 3 * width)
+        return dqkv
+    gw, bboxes, img_w, img_h = geo
+    ws = _empty((query("cova_page_attn_geo_workspace_floats", B, N, heads),), g)
+    call("cova_page_attn_bwd_geo", g, ldg, qkv, ld, out, ldo, lse, page_start, bboxes, gw, img_w, img_h, B, N, width,
+         heads, dqkv, 3 * width, dgeo, ws)
+    return dqkv
+
+
 def page_attn_fwd(h, ldh, N, F, page_start, params, heads, out, ldo, prefix="page_attention.", bboxes=None,
                   page_size=None):
     """The page self-attention (cova_page_attn_fwd): [Q | K | V] = h qkv.weight^T by cova_sgemm, then per page and head the
@@ -1609,53 +1659,35 @@ def page_attn_fwd(h, ldh, N, F, page_start, params, heads, out, ldo, prefix="pag
     E, B = W.shape[0] // 3, page_start.shape[0] - 1
     if W.shape[1] != F or W.shape[0] != 3 * E or E < 1:
         raise ValueError("%sqkv.weight %s does not fit %d own features" % (prefix, tuple(W.shape), F))
-    geo = params.get(prefix + "geometry.weight")
-    if geo is not None:
-        if tuple(geo.shape) != (heads, 8):
-            raise ValueError("%sgeometry.weight %s does not fit %d heads" % (prefix, tuple(geo.shape), heads))
-        if bboxes is None or tuple(bboxes.shape) != (N, 5):
-            raise ValueError("%sgeometry.weight: the geometry bias needs bboxes [%d, 5]" % (prefix, N))
-        _check(bboxes)
-        try:
-            img_h, img_w = (float(v) for v in page_size)
-        except (TypeError, ValueError):
-            raise ValueError("page_size must be (height, width) in pixels, got %r" % (page_size,))
-        if not (img_h > 0 and img_w > 0):
-            raise ValueError("page_size must be positive, got %r" % (page_size,))
+    gw = params.get(prefix + "geometry.weight")
+    geo = None if gw is None else (gw,) + _page_geometry(bboxes, N, page_size, prefix + "geometry.weight")
     qkv = _empty((N, 3 * E), h)
     call("cova_sgemm", 0, 1, N, 3 * E, F, h, ldh, W, F, qkv, 3 * E, None, 0)
-    lse = _empty((N, heads), h)
+    lse = _page_attn_core_fwd(qkv, 3 * E, E, heads, page_start, geo, out, ldo, prefix)
     sv = dict(h=h, ldh=ldh, N=N, F=F, E=E, B=B, heads=heads, qkv=qkv, lse=lse, out=out, ldo=ldo, page_start=page_start,
               prefix=prefix)
     if geo is not None:
-        call("cova_page_attn_fwd_geo", qkv, 3 * E, page_start, bboxes, geo, img_w, img_h, B, N, E, heads, out, ldo, lse)
-        sv.update(bboxes=bboxes, img_w=img_w, img_h=img_h)
-    else:
-        call("cova_page_attn_fwd", qkv, 3 * E, page_start, B, N, E, heads, out, ldo, lse)
+        sv.update(bboxes=bboxes, img_w=geo[2], img_h=geo[3])
     return sv
+
+
+def _saved_geo(sv, gw):
+    """The core's ``geo`` of a backward, from what the forward saved (``bboxes`` there: it took the geometry bias)."""
+    return (gw, sv["bboxes"], sv["img_w"], sv["img_h"]) if "bboxes" in sv else None
 
 
 def page_attn_bwd(sv, g, ldg, params, dh, lddh, gout=None):
     """g = dL/d(attention columns) (rows at g + n*ldg).  ACCUMULATES dL/dh into dh; returns the weight gradient (and
-    the geometry weight's, where the forward took the bias: cova_page_attn_bwd_geo, its workspace from the allocator)."""
-    N, F, E, B, prefix = sv["N"], sv["F"], sv["E"], sv["B"], sv["prefix"]
-    W = params[prefix + "qkv.weight"]
-    dqkv = _empty((N, 3 * E), g)
+    the geometry weight's, where the forward took the bias)."""
+    N, F, E, prefix = sv["N"], sv["F"], sv["E"], sv["prefix"]
     grads = {}
-    if "bboxes" in sv:                    # the forward took the geometry bias
-        Hh = sv["heads"]
-        dgeo = _gbuf(gout, prefix + "geometry.weight", (Hh, 8), g)
-        ws = _empty((query("cova_page_attn_geo_workspace_floats", B, N, Hh),), g)
-        call("cova_page_attn_bwd_geo", g, ldg, sv["qkv"], 3 * E, sv["out"], sv["ldo"], sv["lse"], sv["page_start"],
-             sv["bboxes"], params[prefix + "geometry.weight"], sv["img_w"], sv["img_h"], B, N, E, Hh, dqkv, 3 * E, dgeo, ws)
-        grads[prefix + "geometry.weight"] = dgeo
-    else:
-        call("cova_page_attn_bwd", g, ldg, sv["qkv"], 3 * E, sv["out"], sv["ldo"], sv["lse"], sv["page_start"], B, N, E,
-             sv["heads"], dqkv, 3 * E)
-    dW = _gbuf(gout, prefix + "qkv.weight", (3 * E, F), g)
-    call("cova_sgemm", 1, 0, 3 * E, F, N, dqkv, 3 * E, sv["h"], sv["ldh"], dW, F, None, 0)
-    call("cova_sgemm", 0, 0, N, F, 3 * E, dqkv, 3 * E, W, F, dh, lddh, None, 1)
-    grads[prefix + "qkv.weight"] = dW
+    geo = _saved_geo(sv, params.get(prefix + "geometry.weight"))
+    if geo is not None:
+        grads[prefix + "geometry.weight"] = _gbuf(gout, prefix + "geometry.weight", (sv["heads"], 8), g)
+    dqkv = _page_attn_core_bwd(g, ldg, sv["qkv"], 3 * E, sv["out"], sv["ldo"], sv["lse"], E, sv["heads"], sv["page_start"],
+                               geo, grads.get(prefix + "geometry.weight"))
+    grads[prefix + "qkv.weight"] = dW = _gbuf(gout, prefix + "qkv.weight", (3 * E, F), g)
+    _linear_bwd(dqkv, 3 * E, sv["h"], sv["ldh"], params[prefix + "qkv.weight"], N, 3 * E, F, None, dW, dh, lddh, True)
     return grads
 
 
@@ -1695,19 +1727,9 @@ def page_encoder_fwd(h, ldh, N, F, page_start, params, heads, layers, out, ldo, 
     P, B = W_in.shape[0], page_start.shape[0] - 1
     if W_in.shape[1] != F or P < 1:
         raise ValueError("%sinput.weight %s does not fit %d own features" % (prefix, tuple(W_in.shape), F))
-    geo = (prefix + "layers.0.geometry.weight") in params
     geo_args = None
-    if geo:
-        if bboxes is None or tuple(bboxes.shape) != (N, 5):
-            raise ValueError("%slayers.*.geometry.weight: the geometry bias needs bboxes [%d, 5]" % (prefix, N))
-        _check(bboxes)
-        try:
-            img_h, img_w = (float(v) for v in page_size)
-        except (TypeError, ValueError):
-            raise ValueError("page_size must be (height, width) in pixels, got %r" % (page_size,))
-        if not (img_h > 0 and img_w > 0):
-            raise ValueError("page_size must be positive, got %r" % (page_size,))
-        geo_args = (bboxes, img_w, img_h)
+    if (prefix + "layers.0.geometry.weight") in params:
+        geo_args = _page_geometry(bboxes, N, page_size, prefix + "layers.*.geometry.weight")
     x = _empty((N, P), h)
     call("cova_sgemm", 0, 1, N, P, F, h, ldh, W_in, F, x, P, None, 0)
     blocks = []
@@ -1722,17 +1744,10 @@ def page_encoder_fwd(h, ldh, N, F, page_start, params, heads, layers, out, ldo, 
         b["mean1"], b["rstd1"] = layernorm_fwd(x, P, N, P, params[p + "norm1.weight"], params[p + "norm1.bias"], a, P)
         b["qkv"] = qkv = _empty((N, 3 * P), h)
         call("cova_sgemm", 0, 1, N, 3 * P, P, a, P, Wqkv, P, qkv, 3 * P, None, 0)
-        b["lse"] = lse = _empty((N, heads), h)
         # rows outside every page are written by no attention kernel: they stay zero
         b["O"] = O = torch.zeros((N, P), dtype=torch.float32, device=h.device)
-        if geo:
-            gw = params[p + "geometry.weight"]
-            if tuple(gw.shape) != (heads, 8):
-                raise ValueError("%sgeometry.weight %s does not fit %d heads" % (p, tuple(gw.shape), heads))
-            call("cova_page_attn_fwd_geo", qkv, 3 * P, page_start, geo_args[0], gw, geo_args[1], geo_args[2], B, N, P,
-                 heads, O, P, lse)
-        else:
-            call("cova_page_attn_fwd", qkv, 3 * P, page_start, B, N, P, heads, O, P, lse)
+        geo = None if geo_args is None else (params[p + "geometry.weight"],) + geo_args
+        b["lse"] = _page_attn_core_fwd(qkv, 3 * P, P, heads, page_start, geo, O, P, p)
         x2 = _empty((N, P), h)
         x2.copy_(x)                                   # (a device copy: the stream at LN1's input is kept for its backward)
         call("cova_sgemm", 0, 1, N, P, P, O, P, params[p + "out.weight"], P, x2, P, params[p + "out.bias"], 1)
@@ -1750,17 +1765,17 @@ def page_encoder_fwd(h, ldh, N, F, page_start, params, heads, layers, out, ldo, 
     mean, rstd = layernorm_fwd(x, P, N, P, params[prefix + "norm.weight"], params[prefix + "norm.bias"], out, ldo)
     sv = dict(h=h, ldh=ldh, N=N, F=F, P=P, B=B, heads=heads, layers=layers, blocks=blocks, x=x, mean=mean, rstd=rstd,
               page_start=page_start, prefix=prefix)
-    if geo:
+    if geo_args is not None:
         sv.update(bboxes=bboxes, img_w=geo_args[1], img_h=geo_args[2])
     return sv
 
 
 def page_encoder_bwd(sv, g, ldg, params, dh, lddh, gout=None):
-    """g = dL/d(encoder columns) (rows at g + n*ldg).  Walks the blocks backwards: per Linear the two cova_sgemm (weight
-    gradient, data gradient), cova_colsum for out.bias / ffn1.bias / ffn2.bias, cova_gelu_bwd, cova_page_attn_bwd(_geo) and
+    """g = dL/d(encoder columns) (rows at g + n*ldg).  Walks the blocks backwards: per Linear _linear_bwd (cova_colsum for
+    out.bias / ffn1.bias / ffn2.bias, the two cova_sgemm), cova_gelu_bwd, the attention core's backward and
     cova_layernorm_bwd with ``res`` = the stream gradient, which is so read and written once per LayerNorm.  ACCUMULATES
     dL/dh into dh; returns every parameter gradient."""
-    N, F, P, B, Hh, prefix = sv["N"], sv["F"], sv["P"], sv["B"], sv["heads"], sv["prefix"]
+    N, F, P, Hh, prefix = sv["N"], sv["F"], sv["P"], sv["heads"], sv["prefix"]
     grads = {}
 
     def buf(key, shape):
@@ -1773,40 +1788,30 @@ def page_encoder_bwd(sv, g, ldg, params, dh, lddh, gout=None):
     for b in reversed(sv["blocks"]):
         p, M = b["prefix"], b["M"]
         # x3 = x2 + f ffn2.weight^T + ffn2.bias
-        call("cova_colsum", gx, P, N, P, buf(p + "ffn2.bias", (P,)))
-        call("cova_sgemm", 1, 0, P, M, N, gx, P, b["f"], M, buf(p + "ffn2.weight", (P, M)), M, None, 0)
         df = _empty((N, M), g)
-        call("cova_sgemm", 0, 0, N, M, P, gx, P, params[p + "ffn2.weight"], M, df, M, None, 0)
+        _linear_bwd(gx, P, b["f"], M, params[p + "ffn2.weight"], N, P, M, buf(p + "ffn2.bias", (P,)),
+                    buf(p + "ffn2.weight", (P, M)), df, M, False)
         dz = _empty((N, M), g)
         call("cova_gelu_bwd", df, M, b["z"], M, N, M, dz, M)
-        call("cova_colsum", dz, M, N, M, buf(p + "ffn1.bias", (M,)))
-        call("cova_sgemm", 1, 0, M, P, N, dz, M, b["m"], P, buf(p + "ffn1.weight", (M, P)), P, None, 0)
         dm = _empty((N, P), g)
-        call("cova_sgemm", 0, 0, N, P, M, dz, M, params[p + "ffn1.weight"], P, dm, P, None, 0)
+        _linear_bwd(dz, M, b["m"], P, params[p + "ffn1.weight"], N, M, P, buf(p + "ffn1.bias", (M,)),
+                    buf(p + "ffn1.weight", (M, P)), dm, P, False)
         layernorm_bwd(dm, P, b["x2"], P, b["mean2"], b["rstd2"], params[p + "norm2.weight"], N, P, gx, gx, P,
                       buf(p + "norm2.weight", (P,)), buf(p + "norm2.bias", (P,)))
         # x2 = x1 + O out.weight^T + out.bias
-        call("cova_colsum", gx, P, N, P, buf(p + "out.bias", (P,)))
-        call("cova_sgemm", 1, 0, P, P, N, gx, P, b["O"], P, buf(p + "out.weight", (P, P)), P, None, 0)
         dO = dm                                # (dead by now: reuse)
-        call("cova_sgemm", 0, 0, N, P, P, gx, P, params[p + "out.weight"], P, dO, P, None, 0)
-        # rows outside every page are written by no attention kernel: their dqkv stays zero
-        dqkv = torch.zeros((N, 3 * P), dtype=torch.float32, device=g.device)
-        if "bboxes" in sv:                    # the forward took the geometry bias
-            ws = _empty((query("cova_page_attn_geo_workspace_floats", B, N, Hh),), g)
-            call("cova_page_attn_bwd_geo", dO, P, b["qkv"], 3 * P, b["O"], P, b["lse"], sv["page_start"], sv["bboxes"],
-                 params[p + "geometry.weight"], sv["img_w"], sv["img_h"], B, N, P, Hh, dqkv, 3 * P,
-                 buf(p + "geometry.weight", (Hh, 8)), ws)
-        else:
-            call("cova_page_attn_bwd", dO, P, b["qkv"], 3 * P, b["O"], P, b["lse"], sv["page_start"], B, N, P, Hh, dqkv,
-                 3 * P)
-        call("cova_sgemm", 1, 0, 3 * P, P, N, dqkv, 3 * P, b["a"], P, buf(p + "qkv.weight", (3 * P, P)), P, None, 0)
+        _linear_bwd(gx, P, b["O"], P, params[p + "out.weight"], N, P, P, buf(p + "out.bias", (P,)),
+                    buf(p + "out.weight", (P, P)), dO, P, False)
+        geo = _saved_geo(sv, params.get(p + "geometry.weight"))
+        dqkv = _page_attn_core_bwd(dO, P, b["qkv"], 3 * P, b["O"], P, b["lse"], P, Hh, sv["page_start"], geo,
+                                   buf(p + "geometry.weight", (Hh, 8)) if geo is not None else None)
         da = _empty((N, P), g)
-        call("cova_sgemm", 0, 0, N, P, 3 * P, dqkv, 3 * P, params[p + "qkv.weight"], P, da, P, None, 0)
+        _linear_bwd(dqkv, 3 * P, b["a"], P, params[p + "qkv.weight"], N, 3 * P, P, None, buf(p + "qkv.weight", (3 * P, P)),
+                    da, P, False)
         layernorm_bwd(da, P, b["x1"], P, b["mean1"], b["rstd1"], params[p + "norm1.weight"], N, P, gx, gx, P,
                       buf(p + "norm1.weight", (P,)), buf(p + "norm1.bias", (P,)))
-    call("cova_sgemm", 1, 0, P, F, N, gx, P, sv["h"], sv["ldh"], buf(prefix + "input.weight", (P, F)), F, None, 0)
-    call("cova_sgemm", 0, 0, N, F, P, gx, P, params[prefix + "input.weight"], F, dh, lddh, None, 1)
+    _linear_bwd(gx, P, sv["h"], sv["ldh"], params[prefix + "input.weight"], N, P, F, None,
+                buf(prefix + "input.weight", (P, F)), dh, lddh, True)
     return grads
 
 
@@ -1878,12 +1883,13 @@ def decoder_bwd(sv, dlogits, params, gout=None):
 def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_indices, training,
               seeds=(0, 0), masks=None, save=True, plan=None, visual_feats=None, page_size=None, page_start=None):
     """CoVA.forward (models.py:94-122) -> (logits [N,n_classes], saved-for-backward or None).
-    ``page_start`` (device int64 [B + 1], the pages' row offsets) is read by cfg["page_context_dim"],
-    cfg["page_attention_dim"] and cfg["page_encoder_dim"] only: the batch's table
-    when given, else derived on the device from the page column of ``bboxes`` and the page count of ``images``
+    ``page_start`` (device int64 [B + 1], the pages' row offsets) is read by the context layers that work per page
+    (weights.CONTEXT_LAYERS: cfg["page_context_dim"], cfg["page_attention_dim"], cfg["page_encoder_dim"]) only: the batch's
+    table when given, else derived on the device from the page column of ``bboxes`` and the page count of ``images``
     (page_start_of); a batch without either raises ValueError.
-    ``page_size`` = (height, width) of the pages, read by cfg["edge_geometry"] only: by default ``images.shape[2:]``; a batch
-    without images (``visual_feats``) must name it (DeviceDataset batches carry it) or cfg["page_size"] must.
+    ``page_size`` = (height, width) of the pages, read by the geometry options (_geometry_on) only: by default
+    ``images.shape[2:]``; a batch without images (``visual_feats``) must name it (DeviceDataset batches carry it) or
+    cfg["page_size"] must.
     ``training``: a bool (whole model) or per-layer modes {BatchNorm prefix / Dropout name: bool} (is_train).
     ``plan`` (grad_plan, with ``save``): without its "convstack" stage the conv stack keeps no activations.
     ``visual_feats`` = (table [R, n_vis], row_ids int32 [N]) (features.FeatureCache): the conv stack and the RoI op are
@@ -1892,23 +1898,15 @@ def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_in
     if visual_feats is not None:
         return _model_fwd_cached(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks,
                                  save, plan, visual_feats, page_size, page_start)
-    N = bboxes.shape[0]
     PH, PW = cfg["roi_output_size"]
     n_vis = (C256 if is_bottleneck(params) else C128 if has_layer2(params) else C64) * PH * PW
-    Hd, A = cfg["bbox_hidden_dim"], cfg["n_additional_feat"]
-    F = n_vis + Hd + A
-    D = cfg["hidden_dim"] if cfg["use_context"] else 0
-    G, E, P = cfg.get("page_context_dim", 0), cfg.get("page_attention_dim", 0), cfg.get("page_encoder_dim", 0)
-    T = F + D + G + E + P
-    if G > 0 or E > 0 or P > 0:
-        page_start = page_start_of(bboxes, images, page_start, _page_option(G, E))
+    sv = _head_saved(cfg, n_vis, bboxes, images, page_size or cfg.get("page_size") or tuple(images.shape[2:]), page_start)
+    N, T = sv["N"], sv["T"]
     align = cfg.get("roi_op", "pool") == "align"
     save_conv = save and (plan is None or "convstack" in plan)
-    feat, sv_conv = convstack_fwd(images, params, buffers, training, save_conv, lazy_out=not align)
-    comb = _empty((N, T), images)
+    feat, sv["conv"] = convstack_fwd(images, params, buffers, training, save_conv, lazy_out=not align)
+    sv["comb"] = comb = _empty((N, T), images)
     scale = cfg.get("spatial_scale") or feat.shape[1] / images.shape[2]   # models.py:56
-    sv = dict(cfg=cfg, N=N, F=F, D=D, G=G, E=E, P=P, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=sv_conv, comb=comb,
-              page_size=page_size or cfg.get("page_size") or tuple(images.shape[2:]), page_start=page_start)
     if align:
         sv["roi"] = roialign_fwd(feat, bboxes, (PH, PW), scale, cfg.get("sampling_ratio", 2),
                                  cfg.get("roi_aligned", False), comb, T)
@@ -1917,10 +1915,77 @@ def model_fwd(cfg, params, buffers, images, bboxes, additional_feats, context_in
     return _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks, save, sv)
 
 
+def _head_saved(cfg, n_vis, bboxes, images, page_size, page_start):
+    """The saved dict both forms of model_fwd start from: the head's layout (weights.head_layout) as N, F, T, n_vis, Hd, A
+    and one width per context layer (D, G, E, P), the page size, and the page table where a layer that is on reads one."""
+    layout = head_layout(cfg, n_vis)
+    if layout.page_option is not None:
+        page_start = page_start_of(bboxes, images, page_start, layout.page_option)
+    sv = dict(cfg=cfg, N=bboxes.shape[0], F=layout.F, T=layout.T, n_vis=n_vis, Hd=layout.Hd, A=layout.A, layout=layout,
+              page_size=page_size, page_start=page_start)
+    for layer, (_, _, width) in zip(CONTEXT_LAYERS, layout.layers):
+        sv[layer.letter] = width
+    return sv
+
+
+def _geometry_on(cfg, sv, params, option, key=None):
+    """A geometry option of ``cfg`` -> bool.  On, it needs the page size (a batch without images must carry it); and the
+    parameters must agree with it: ``key``, the weight it adds, is there exactly when it is on."""
+    on = bool(cfg.get(option, False))
+    if on and sv.get("page_size") is None:
+        raise ValueError("%s: a batch without images must carry page_size = (height, width) (or the configuration a "
+                         "'page_size')" % option)
+    if key is not None and on != (key in params):
+        raise ValueError("%s=%r, but the parameters %s %s" % (option, on, "lack" if on else "hold", key))
+    return on
+
+
+# Per context layer its forward and backward behind one signature each.  The forward writes the columns ``out`` (rows at
+# out + n*T) and returns what its backward needs; the backward reads g = dL/d(those columns) and ACCUMULATES dL/d(own
+# features) into dcomb[:, :F].  Both walks below follow weights.CONTEXT_LAYERS, where the order is stated.
+def _gat_ctx_fwd(cfg, params, sv, out, bboxes, ctx, training, seeds):
+    edge = _geometry_on(cfg, sv, params, "edge_geometry")       # (gat_fwd holds every head's edge_layer.weight to it)
+    return gat_stack_fwd(sv["comb"], sv["T"], sv["N"], sv["F"], sv["D"], ctx, params, cfg.get("n_heads", 1),
+                         cfg.get("n_gat_layers", 1), bboxes if edge else None, sv.get("page_size"), edge,
+                         cfg.get("attention", "gat"), cfg.get("attention_dropout", 0.0), seeds[0], training)
+
+
+def _gat_ctx_bwd(sv, g, dcomb, params, gout):
+    return gat_stack_bwd(sv["gat"], dcomb, sv["T"], sv["N"], sv["F"], sv["D"], params, gout)
+
+
+def _readout_ctx_fwd(cfg, params, sv, out, bboxes, ctx, training, seeds):
+    return page_readout_fwd(sv["comb"], sv["T"], sv["N"], sv["F"], sv["page_start"], params, out, sv["T"])
+
+
+def _page_attn_ctx_fwd(cfg, params, sv, out, bboxes, ctx, training, seeds):
+    geo = _geometry_on(cfg, sv, params, "page_attention_geometry", "page_attention.geometry.weight")
+    return page_attn_fwd(sv["comb"], sv["T"], sv["N"], sv["F"], sv["page_start"], params, cfg.get("page_attention_heads", 1),
+                         out, sv["T"], bboxes=bboxes if geo else None, page_size=sv.get("page_size"))
+
+
+def _page_enc_ctx_fwd(cfg, params, sv, out, bboxes, ctx, training, seeds):
+    geo = _geometry_on(cfg, sv, params, "page_encoder_geometry", "page_encoder.layers.0.geometry.weight")
+    return page_encoder_fwd(sv["comb"], sv["T"], sv["N"], sv["F"], sv["page_start"], params,
+                            cfg.get("page_encoder_heads", 1), cfg.get("page_encoder_layers", 1), out, sv["T"],
+                            bboxes=bboxes if geo else None, page_size=sv.get("page_size"))
+
+
+def _page_ctx_bwd(key, bwd):
+    return lambda sv, g, dcomb, params, gout: bwd(sv[key], g, sv["T"], params, dcomb, sv["T"], gout)
+
+
+CONTEXT_STAGES = {"gat": (_gat_ctx_fwd, _gat_ctx_bwd),
+                  "readout": (_readout_ctx_fwd, _page_ctx_bwd("readout", page_readout_bwd)),
+                  "page_attn": (_page_attn_ctx_fwd, _page_ctx_bwd("page_attn", page_attn_bwd)),
+                  "page_enc": (_page_enc_ctx_fwd, _page_ctx_bwd("page_enc", page_encoder_bwd))}
+assert tuple(CONTEXT_STAGES) == tuple(layer.key for layer in CONTEXT_LAYERS)
+
+
 def _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks, save, sv):
-    """Everything behind the visual columns of ``sv["comb"]``: positional encoder, additional features, GAT, decoder."""
-    N, F, D, T, n_vis, Hd, A, comb = (sv[k] for k in ("N", "F", "D", "T", "n_vis", "Hd", "A", "comb"))
-    G, E, P = sv.get("G", 0), sv.get("E", 0), sv.get("P", 0)
+    """Everything behind the visual columns of ``sv["comb"]``: positional encoder, additional features, the context
+    layers that are on, decoder."""
+    N, T, n_vis, Hd, A, comb = (sv[k] for k in ("N", "T", "n_vis", "Hd", "A", "comb"))
     if Hd > 0:
         sv["bbox"] = bbox_fwd(bboxes, params, buffers, training, comb[:, n_vis:], T)
     if A > 0:
@@ -1928,38 +1993,9 @@ def _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, t
         sv["addl_in"] = additional_feats
         sv["addl"] = bn1d_fwd(additional_feats, A, N, A, "bn_additional_feat.", params, buffers,
                               training, comb[:, n_vis + Hd:], T, False)
-    if D > 0:
-        edge = bool(cfg.get("edge_geometry", False))
-        if edge and sv.get("page_size") is None:
-            raise ValueError("edge_geometry: a batch without images must carry page_size = (height, width) "
-                             "(or the configuration a 'page_size')")
-        sv["gat"] = gat_stack_fwd(comb, T, N, F, D, context_indices, params, cfg.get("n_heads", 1),
-                                  cfg.get("n_gat_layers", 1), bboxes if edge else None, sv.get("page_size"), edge,
-                                  cfg.get("attention", "gat"), cfg.get("attention_dropout", 0.0), seeds[0], training)
-    if G > 0:
-        sv["readout"] = page_readout_fwd(comb, T, N, F, sv["page_start"], params, comb[:, F + D:], T)
-    if E > 0:
-        geo = bool(cfg.get("page_attention_geometry", False))
-        if geo and sv.get("page_size") is None:
-            raise ValueError("page_attention_geometry: a batch without images must carry page_size = (height, width) "
-                             "(or the configuration a 'page_size')")
-        if geo != ("page_attention.geometry.weight" in params):
-            raise ValueError("page_attention_geometry=%r, but the parameters %s page_attention.geometry.weight"
-                             % (geo, "lack" if geo else "hold"))
-        sv["page_attn"] = page_attn_fwd(comb, T, N, F, sv["page_start"], params, cfg.get("page_attention_heads", 1),
-                                        comb[:, F + D + G:], T, bboxes=bboxes if geo else None,
-                                        page_size=sv.get("page_size"))
-    if P > 0:
-        geo = bool(cfg.get("page_encoder_geometry", False))
-        if geo and sv.get("page_size") is None:
-            raise ValueError("page_encoder_geometry: a batch without images must carry page_size = (height, width) "
-                             "(or the configuration a 'page_size')")
-        if geo != ("page_encoder.layers.0.geometry.weight" in params):
-            raise ValueError("page_encoder_geometry=%r, but the parameters %s page_encoder.layers.0.geometry.weight"
-                             % (geo, "lack" if geo else "hold"))
-        sv["page_enc"] = page_encoder_fwd(comb, T, N, F, sv["page_start"], params, cfg.get("page_encoder_heads", 1),
-                                          cfg.get("page_encoder_layers", 1), comb[:, F + D + G + E:], T,
-                                          bboxes=bboxes if geo else None, page_size=sv.get("page_size"))
+    for key, offset, width in sv["layout"].layers:
+        if width > 0:
+            sv[key] = CONTEXT_STAGES[key][0](cfg, params, sv, comb[:, offset:], bboxes, context_indices, training, seeds)
     logits, sv["dec"] = decoder_fwd(comb, N, T, params, buffers, training, cfg["drop_prob"], seeds,
                                     masks)
     return logits, (sv if save else None)
@@ -1998,16 +2034,10 @@ def _model_fwd_cached(cfg, params, buffers, bboxes, additional_feats, context_in
         raise ValueError("model_fwd: cached visual features keep nothing for the conv-stack backward; the gradient plan "
                          "must leave out 'convstack' (a frozen conv stack)")
     n_vis = table.shape[1]
-    Hd, A = cfg["bbox_hidden_dim"], cfg["n_additional_feat"]
-    F = n_vis + Hd + A
-    D = cfg["hidden_dim"] if cfg["use_context"] else 0
-    G, E, P = cfg.get("page_context_dim", 0), cfg.get("page_attention_dim", 0), cfg.get("page_encoder_dim", 0)
-    T = F + D + G + E + P
-    if G > 0 or E > 0 or P > 0:
-        page_start = page_start_of(bboxes, None, page_start, _page_option(G, E))
-    comb = _empty((N, T), bboxes)
-    sv = dict(cfg=cfg, N=N, F=F, D=D, G=G, E=E, P=P, T=T, n_vis=n_vis, Hd=Hd, A=A, conv=None, roi=None, comb=comb,
-              page_size=page_size or cfg.get("page_size"), page_start=page_start)
+    sv = _head_saved(cfg, n_vis, bboxes, None, page_size or cfg.get("page_size"), page_start)
+    T = sv["T"]
+    sv["conv"] = sv["roi"] = None
+    sv["comb"] = comb = _empty((N, T), bboxes)
     call("cova_feat_rows_gather", table, table.shape[0], n_vis, row_ids, N, comb, T)
     return _head_fwd(cfg, params, buffers, bboxes, additional_feats, context_indices, training, seeds, masks, save, sv)
 
@@ -2022,17 +2052,11 @@ def model_bwd(sv, dlogits, params, gout=None, after_head=None, want_dimg=False, 
     are absent from the result (the forward must have had the same plan)."""
     if plan is not None and want_dimg:
         plan = plan | {"convstack", "stem", "layer1"}
-    N, F, D, T, n_vis, Hd, A = (sv[k] for k in ("N", "F", "D", "T", "n_vis", "Hd", "A"))
+    N, T, n_vis, Hd, A = (sv[k] for k in ("N", "T", "n_vis", "Hd", "A"))
     dcomb, grads = decoder_bwd(sv["dec"], dlogits, params, gout)
-    if D > 0:
-        grads.update(gat_stack_bwd(sv["gat"], dcomb, T, N, F, D, params, gout))
-    if sv.get("G", 0) > 0:               # after the GAT's: both accumulate into dcomb[:, :F], in this order
-        grads.update(page_readout_bwd(sv["readout"], dcomb[:, F + D:], T, params, dcomb, T, gout))
-    if sv.get("E", 0) > 0:               # after the readout's: the third to accumulate into dcomb[:, :F], in this order
-        grads.update(page_attn_bwd(sv["page_attn"], dcomb[:, F + D + sv.get("G", 0):], T, params, dcomb, T, gout))
-    if sv.get("P", 0) > 0:               # after the page attention's: the fourth to accumulate into dcomb[:, :F], in this order
-        grads.update(page_encoder_bwd(sv["page_enc"], dcomb[:, F + D + sv.get("G", 0) + sv.get("E", 0):], T, params, dcomb,
-                                      T, gout))
+    for key, offset, width in sv["layout"].layers:          # (the forward's order: weights.CONTEXT_LAYERS says why)
+        if width > 0:
+            grads.update(CONTEXT_STAGES[key][1](sv, dcomb[:, offset:], dcomb, params, gout))
     if A > 0 and (plan is None or "addl" in plan):
         st = sv["addl"]
         dz = _empty((N, A), dcomb)

@@ -21,9 +21,9 @@ import torch
 import torch.nn as nn
 
 from . import engine
-from .weights import (EDGE_FEATURES, attention_of, backbone_channels, check_attention, check_attention_dropout,
-                      check_backbone_layers, check_page_attention, check_page_attention_geometry, check_page_context_dim,
-                      check_page_encoder)
+from .weights import (EDGE_FEATURES, PAGE_ENCODER_OPTIONS, attention_of, backbone_channels, check_attention,
+                      check_attention_dropout, check_backbone_layers, check_page_attention, check_page_context_dim,
+                      check_page_encoder, head_layout, page_options)
 
 GAT_MAX_K = engine.GAT_MAX_K
 LOSS_MAX_CLASSES = engine.LOSS_MAX_CLASSES
@@ -434,34 +434,63 @@ class MultiHeadGraphAttention(nn.Module):
         return (h, attn) if return_attn_wts else h
 
 
-class _PageReadoutFn(torch.autograd.Function):
+class _PageLayerFn(torch.autograd.Function):
+    """The one autograd node of the page modules (_PageLayer): ``layer`` names its state_dict prefix, the engine forward /
+    backward pair and which saved tensor, if any, is the non-differentiable second output; ``values`` are its parameters
+    in named_parameters() order."""
+
     @staticmethod
-    def forward(ctx, layer, h, page_start, W, att_w, att_b):
+    def forward(ctx, layer, h, page_start, bboxes, page_size, *values):
         h = _f32c(h)
-        N, F = h.shape
-        params = {"page_readout.W.weight": W.detach(), "page_readout.attention_layer.weight": att_w.detach(),
-                  "page_readout.attention_layer.bias": att_b.detach()}
-        out = torch.empty((N, layer.dim), device=h.device)
-        ctx.sv = engine.page_readout_fwd(h, F, N, F, _i64c(page_start), params, out, layer.dim)
-        ctx.params = params
-        ctx.mark_non_differentiable(ctx.sv["beta"])
-        return out, ctx.sv["beta"]
+        ctx.keys = [layer._prefix + k for k, _ in layer.named_parameters()]
+        ctx.params = {k: _f32c(v) for k, v in zip(ctx.keys, values)}
+        out = torch.empty((h.shape[0], layer.dim), device=h.device)
+        ctx.sv = layer._engine_fwd(h, _i64c(page_start), ctx.params, out, _f32c(bboxes) if layer.geometry_bias else None,
+                                   page_size)
+        ctx.bwd = layer._engine_bwd
+        if layer._second is None:
+            return out
+        ctx.mark_non_differentiable(ctx.sv[layer._second])
+        return out, ctx.sv[layer._second]
 
     @staticmethod
-    def backward(ctx, g, _gbeta):
+    def backward(ctx, g, _gsecond=None):
         sv = ctx.sv
-        dh = torch.zeros((sv["N"], sv["F"]), device=g.device)          # page_readout_bwd accumulates
-        grads = engine.page_readout_bwd(sv, g.contiguous(), sv["G"], ctx.params, dh, sv["F"])
-        return (None, dh, None, grads["page_readout.W.weight"], grads["page_readout.attention_layer.weight"],
-                grads["page_readout.attention_layer.bias"])
+        dh = torch.zeros((sv["N"], sv["F"]), device=g.device)          # the engine's page backwards accumulate
+        grads = ctx.bwd(sv, g.contiguous(), g.shape[1], ctx.params, dh, sv["F"])
+        return (None, dh, None, None, None) + tuple(grads[k] for k in ctx.keys)
 
 
-class PageReadout(nn.Module):
+class _PageLayer(nn.Module):
+    """What PageReadout, PageAttention and PageEncoder share: the input checks and the autograd node."""
+    _prefix = _second = None
+    geometry_bias = False
+
+    def _run(self, h, page_start, bboxes=None, page_size=None):
+        """The node's output(s) for checked inputs; None for an empty batch (the caller shapes its empty result)."""
+        _require_cuda(h, page_start)
+        if self.geometry_bias:
+            if bboxes is None or page_size is None or bboxes.dim() != 2 or tuple(bboxes.shape) != (h.shape[0], 5):
+                raise ValueError("a %s with geometry=True needs bboxes [N, 5] and page_size = (height, width)"
+                                 % type(self).__name__)
+            _require_cuda(bboxes)
+        if h.dim() != 2 or h.shape[1] != self.in_features:
+            raise RuntimeError("expected h [N, %d], got %s" % (self.in_features, tuple(h.shape)))
+        if page_start.dim() != 1 or page_start.shape[0] < 1 or page_start.is_floating_point():
+            raise ValueError("page_start must hold B + 1 integer row offsets, got shape %s" % (tuple(page_start.shape),))
+        if h.shape[0] == 0:
+            return None
+        return _PageLayerFn.apply(self, h, page_start, bboxes, page_size, *self.parameters())
+
+
+class PageReadout(_PageLayer):
     """Extension: the global-attention readout of Li et al. 2016 (gated graph networks; PyG ``AttentionalAggregation``)
     over the boxes of each page.  ``P = W h`` (Linear(in_features, dim), no bias), ``beta`` = softmax over the page's boxes
     of ``LeakyReLU(attention_layer(P))`` (Linear(dim, 1)), ``r_p = sum beta_i P_i``; every box of a page receives its
     page's ``r_p``.  ``forward(h [N, in_features], page_start int64 [B + 1])`` -> ``r_rows [N, dim]`` (and ``beta [N]`` with
     ``return_attn_wts``); one autograd node over cova_page_readout_fwd / cova_page_readout_bwd."""
+
+    _prefix, _second, _engine_bwd = "page_readout.", "beta", staticmethod(engine.page_readout_bwd)
 
     def __init__(self, in_features, dim, alpha=0.2):
         super().__init__()
@@ -473,45 +502,15 @@ class PageReadout(nn.Module):
         self.W = nn.Linear(in_features, self.dim, bias=False)
         self.attention_layer = nn.Linear(self.dim, 1)
 
+    def _engine_fwd(self, h, page_start, params, out, bboxes, page_size):
+        return engine.page_readout_fwd(h, h.shape[1], h.shape[0], h.shape[1], page_start, params, out, self.dim)
+
     def forward(self, h, page_start, return_attn_wts=False):
-        _require_cuda(h, page_start)
-        if h.dim() != 2 or h.shape[1] != self.in_features:
-            raise RuntimeError("expected h [N, %d], got %s" % (self.in_features, tuple(h.shape)))
-        if page_start.dim() != 1 or page_start.shape[0] < 1 or page_start.is_floating_point():
-            raise ValueError("page_start must hold B + 1 integer row offsets, got shape %s" % (tuple(page_start.shape),))
-        if h.shape[0] == 0:
-            return (h.new_empty((0, self.dim)), h.new_empty((0,))) if return_attn_wts else h.new_empty((0, self.dim))
-        out, beta = _PageReadoutFn.apply(self, h, page_start, self.W.weight, self.attention_layer.weight,
-                                         self.attention_layer.bias)
+        out, beta = self._run(h, page_start) or (h.new_empty((0, self.dim)), h.new_empty((0,)))
         return (out, beta) if return_attn_wts else out
 
 
-class _PageAttentionFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, layer, h, page_start, bboxes, page_size, W, Wgeo):
-        h = _f32c(h)
-        N, F = h.shape
-        params = {"page_attention.qkv.weight": W.detach()}
-        if Wgeo is not None:
-            params["page_attention.geometry.weight"] = _f32c(Wgeo.detach())
-            bboxes = _f32c(bboxes)
-        out = torch.empty((N, layer.dim), device=h.device)
-        ctx.sv = engine.page_attn_fwd(h, F, N, F, _i64c(page_start), params, layer.heads, out, layer.dim,
-                                      bboxes=bboxes, page_size=page_size)
-        ctx.params = params
-        ctx.mark_non_differentiable(ctx.sv["lse"])
-        return out, ctx.sv["lse"]
-
-    @staticmethod
-    def backward(ctx, g, _glse):
-        sv = ctx.sv
-        dh = torch.zeros((sv["N"], sv["F"]), device=g.device)          # page_attn_bwd accumulates
-        grads = engine.page_attn_bwd(sv, g.contiguous(), sv["E"], ctx.params, dh, sv["F"])
-        return (None, dh, None, None, None, grads["page_attention.qkv.weight"],
-                grads.get("page_attention.geometry.weight"))
-
-
-class PageAttention(nn.Module):
+class PageAttention(_PageLayer):
     """Extension: multi-head scaled dot-product self-attention (Vaswani et al. 2017) restricted to pages.  ``[Q | K | V] =
     qkv(h)`` (Linear(in_features, 3 dim), no bias); for a box i and a head of ``dim / heads`` columns, ``A_ij`` = softmax
     over ALL boxes j of i's page of ``Q_i . K_j / sqrt(dim / heads)`` and ``O_i = sum_j A_ij V_j``.  No output projection
@@ -523,6 +522,8 @@ class PageAttention(nn.Module):
     the plain layer's output) of the eight relative-geometry features of cova_edge_geometry, query box against key box,
     formed inside the kernels (cova_page_attn_fwd_geo / cova_page_attn_bwd_geo).  ``forward`` then needs ``bboxes``
     [N, 5] and ``page_size`` = (height, width) in pixels; the boxes get no gradient."""
+
+    _prefix, _second, _engine_bwd = "page_attention.", "lse", staticmethod(engine.page_attn_bwd)
 
     def __init__(self, in_features, dim, heads=1, geometry=False):
         super().__init__()
@@ -536,45 +537,14 @@ class PageAttention(nn.Module):
             self.geometry = nn.Linear(8, self.heads, bias=False)
             nn.init.zeros_(self.geometry.weight)
 
+    def _engine_fwd(self, h, page_start, params, out, bboxes, page_size):
+        return engine.page_attn_fwd(h, h.shape[1], h.shape[0], h.shape[1], page_start, params, self.heads, out, self.dim,
+                                    bboxes=bboxes, page_size=page_size)
+
     def forward(self, h, page_start, bboxes=None, page_size=None, return_lse=False):
-        _require_cuda(h, page_start)
-        wgeo = None
-        if self.geometry_bias:
-            if bboxes is None or page_size is None or bboxes.dim() != 2 or tuple(bboxes.shape) != (h.shape[0], 5):
-                raise ValueError("a PageAttention with geometry=True needs bboxes [N, 5] and page_size = (height, width)")
-            _require_cuda(bboxes)
-            wgeo = self.geometry.weight
-        if h.dim() != 2 or h.shape[1] != self.in_features:
-            raise RuntimeError("expected h [N, %d], got %s" % (self.in_features, tuple(h.shape)))
-        if page_start.dim() != 1 or page_start.shape[0] < 1 or page_start.is_floating_point():
-            raise ValueError("page_start must hold B + 1 integer row offsets, got shape %s" % (tuple(page_start.shape),))
-        if h.shape[0] == 0:
-            out, lse = h.new_empty((0, self.dim)), h.new_empty((0, self.heads))
-        else:
-            out, lse = _PageAttentionFn.apply(self, h, page_start, bboxes, page_size, self.qkv.weight, wgeo)
+        out, lse = (self._run(h, page_start, bboxes, page_size)
+                    or (h.new_empty((0, self.dim)), h.new_empty((0, self.heads))))
         return (out, lse) if return_lse else out
-
-
-class _PageEncoderFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, layer, h, page_start, bboxes, page_size, *values):
-        h = _f32c(h)
-        N, F = h.shape
-        params = {"page_encoder." + k: _f32c(v) for k, v in zip(layer._keys, values)}
-        if layer.geometry_bias:
-            bboxes = _f32c(bboxes)
-        out = torch.empty((N, layer.dim), device=h.device)
-        ctx.sv = engine.page_encoder_fwd(h, F, N, F, _i64c(page_start), params, layer.heads, layer.n_layers, out, layer.dim,
-                                         bboxes=bboxes if layer.geometry_bias else None, page_size=page_size)
-        ctx.params, ctx.keys = params, layer._keys
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        sv = ctx.sv
-        dh = torch.zeros((sv["N"], sv["F"]), device=g.device)          # page_encoder_bwd accumulates
-        grads = engine.page_encoder_bwd(sv, g.contiguous(), sv["P"], ctx.params, dh, sv["F"])
-        return (None, dh, None, None, None) + tuple(grads["page_encoder." + k] for k in ctx.keys)
 
 
 class _PageEncoderBlock(nn.Module):
@@ -596,7 +566,7 @@ class _PageEncoderBlock(nn.Module):
         raise RuntimeError("parameter container only; the block runs in libcova_hip.so (PageEncoder.forward)")
 
 
-class PageEncoder(nn.Module):
+class PageEncoder(_PageLayer):
     """Extension: an L-layer pre-LN transformer encoder (Vaswani et al. 2017; the pre-LN form of Xiong et al. 2020) over
     the boxes of each page -- torch's ``nn.TransformerEncoderLayer(norm_first=True, activation="gelu", dropout=0)`` per
     page with a zero ``in_proj_bias``, behind an input projection and in front of a final LayerNorm:
@@ -611,6 +581,8 @@ class PageEncoder(nn.Module):
     -> ``[N, dim]``; one autograd node over engine.page_encoder_fwd / page_encoder_bwd (cova_layernorm_*, cova_gelu_*,
     cova_page_attn_*, cova_sgemm, cova_colsum)."""
 
+    _prefix, _engine_bwd = "page_encoder.", staticmethod(engine.page_encoder_bwd)
+
     def __init__(self, in_features, dim, heads=1, layers=1, ffn_dim=None, geometry=False):
         super().__init__()
         self.in_features = in_features
@@ -622,21 +594,14 @@ class PageEncoder(nn.Module):
         self.layers = nn.ModuleList(_PageEncoderBlock(self.dim, self.heads, self.ffn_dim, self.geometry_bias)
                                     for _ in range(self.n_layers))
         self.norm = nn.LayerNorm(self.dim)
-        self._keys = [k for k, _ in self.named_parameters()]
+
+    def _engine_fwd(self, h, page_start, params, out, bboxes, page_size):
+        return engine.page_encoder_fwd(h, h.shape[1], h.shape[0], h.shape[1], page_start, params, self.heads, self.n_layers,
+                                       out, self.dim, bboxes=bboxes, page_size=page_size)
 
     def forward(self, h, page_start, bboxes=None, page_size=None):
-        _require_cuda(h, page_start)
-        if self.geometry_bias:
-            if bboxes is None or page_size is None or bboxes.dim() != 2 or tuple(bboxes.shape) != (h.shape[0], 5):
-                raise ValueError("a PageEncoder with geometry=True needs bboxes [N, 5] and page_size = (height, width)")
-            _require_cuda(bboxes)
-        if h.dim() != 2 or h.shape[1] != self.in_features:
-            raise RuntimeError("expected h [N, %d], got %s" % (self.in_features, tuple(h.shape)))
-        if page_start.dim() != 1 or page_start.shape[0] < 1 or page_start.is_floating_point():
-            raise ValueError("page_start must hold B + 1 integer row offsets, got shape %s" % (tuple(page_start.shape),))
-        if h.shape[0] == 0:
-            return h.new_empty((0, self.dim))
-        return _PageEncoderFn.apply(self, h, page_start, bboxes, page_size, *[p for _, p in self.named_parameters()])
+        out = self._run(h, page_start, bboxes, page_size)
+        return h.new_empty((0, self.dim)) if out is None else out
 
 
 class CoVA(nn.Module):
@@ -687,12 +652,7 @@ class CoVA(nn.Module):
         ``page_encoder_geometry=True`` (needs P > 0) gives every layer's scores the box-geometry bias
         (``page_encoder.layers.<l>.geometry.weight`` [Hh, 8], zero at construction).  No dropout inside the encoder;
         ``edge_geometry`` and ``attention_dropout`` belong to the GAT and do not reach it.  With 0 nothing changes."""
-        page_context_dim = check_page_context_dim(page_context_dim)
-        page_attention_dim, page_attention_heads = check_page_attention(page_attention_dim, page_attention_heads)
-        page_attention_geometry = check_page_attention_geometry(page_attention_geometry, page_attention_dim)
-        (page_encoder_dim, page_encoder_heads, page_encoder_layers, page_encoder_ffn_dim,
-         page_encoder_geometry) = check_page_encoder(page_encoder_dim, page_encoder_heads, page_encoder_layers,
-                                                     page_encoder_ffn_dim, page_encoder_geometry)
+        page = page_options(locals())
         check_backbone_layers(backbone, backbone_layers)
         check_attention(attention)
         attention_dropout = check_attention_dropout(attention_dropout)
@@ -752,25 +712,16 @@ class CoVA(nn.Module):
             else:
                 self.gat = MultiHeadGraphAttention(self.n_feat, self.hidden_dim, n_heads, n_gat_layers, edge_geometry,
                                                    attention, attention_dropout)
-        self.page_context_dim = page_context_dim
-        if page_context_dim > 0:
-            self.page_readout = PageReadout(self.n_feat, page_context_dim)
-        self.page_attention_dim, self.page_attention_heads = page_attention_dim, page_attention_heads
-        if page_attention_dim > 0:
-            self.page_attention = PageAttention(self.n_feat, page_attention_dim, page_attention_heads,
-                                                geometry=page_attention_geometry)
-        self.page_encoder_dim = page_encoder_dim
-        if page_encoder_dim > 0:
-            self.page_encoder = PageEncoder(self.n_feat, page_encoder_dim, page_encoder_heads, page_encoder_layers,
-                                            page_encoder_ffn_dim, page_encoder_geometry)
-        self.n_total_feat = (self.n_feat + (self.hidden_dim if self.use_context else 0) + page_context_dim
-                             + page_attention_dim + page_encoder_dim)
-        self.decoder = nn.Sequential(nn.Dropout(drop_prob),
-                                     nn.Linear(self.n_total_feat, self.n_total_feat),
-                                     nn.BatchNorm1d(self.n_total_feat), nn.ReLU(),
-                                     nn.Dropout(drop_prob),
-                                     nn.Linear(self.n_total_feat, self.n_classes))
-
+        self.page_context_dim = page["page_context_dim"]
+        if self.page_context_dim > 0:
+            self.page_readout = PageReadout(self.n_feat, self.page_context_dim)
+        self.page_attention_dim, self.page_attention_heads = page["page_attention_dim"], page["page_attention_heads"]
+        if self.page_attention_dim > 0:
+            self.page_attention = PageAttention(self.n_feat, self.page_attention_dim, self.page_attention_heads,
+                                                geometry=page["page_attention_geometry"])
+        self.page_encoder_dim = page["page_encoder_dim"]
+        if self.page_encoder_dim > 0:
+            self.page_encoder = PageEncoder(self.n_feat, *(page[k] for k in PAGE_ENCODER_OPTIONS))
         self._cfg = dict(roi_output_size=roi_output_size, n_classes=n_classes, use_context=use_context,
                          hidden_dim=hidden_dim, bbox_hidden_dim=bbox_hidden_dim,
                          n_additional_feat=n_additional_feat, drop_prob=float(drop_prob),
@@ -778,12 +729,14 @@ class CoVA(nn.Module):
                          n_heads=n_heads, n_gat_layers=n_gat_layers, roi_op=roi_op,
                          sampling_ratio=int(sampling_ratio), roi_aligned=bool(roi_aligned),
                          backbone_layers=backbone_layers, edge_geometry=bool(edge_geometry) and bool(use_context),
-                         attention=attention, attention_dropout=attention_dropout if use_context else 0.0,
-                         page_context_dim=page_context_dim, page_attention_dim=page_attention_dim,
-                         page_attention_heads=page_attention_heads, page_attention_geometry=page_attention_geometry,
-                         page_encoder_dim=page_encoder_dim, page_encoder_heads=page_encoder_heads,
-                         page_encoder_layers=page_encoder_layers, page_encoder_ffn_dim=page_encoder_ffn_dim,
-                         page_encoder_geometry=page_encoder_geometry)
+                         attention=attention, attention_dropout=attention_dropout if use_context else 0.0, **page)
+        self.n_total_feat = head_layout(self._cfg, self.n_visual_feat).T
+        self.decoder = nn.Sequential(nn.Dropout(drop_prob),
+                                     nn.Linear(self.n_total_feat, self.n_total_feat),
+                                     nn.BatchNorm1d(self.n_total_feat), nn.ReLU(),
+                                     nn.Dropout(drop_prob),
+                                     nn.Linear(self.n_total_feat, self.n_classes))
+
         self._param_keys = [k for k, _ in self.named_parameters()]
         self._conv_keys = [k for k in self._param_keys if k.startswith("convnet.")]
         self._bbox_keys = [k for k in self._param_keys if k.startswith("bbox_feat_encoder.")]

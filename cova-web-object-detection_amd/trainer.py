@@ -21,14 +21,42 @@ import os
 import torch
 
 from . import engine
-from .weights import (PAGE_ATTENTION_GEO_KEY, PAGE_ATTENTION_KEY, PAGE_ENCODER_INPUT_KEY, PAGE_READOUT_KEYS,
-                      check_attention_dropout, check_page_attention, check_page_attention_geometry, check_page_context_dim,
-                      check_page_encoder, page_encoder_layer_prefix, state_dict_spec)
-
-_PAGE_ENCODER_OPTIONS = ("page_encoder_dim", "page_encoder_heads", "page_encoder_layers", "page_encoder_ffn_dim",
-                         "page_encoder_geometry")
+from .weights import (PAGE_ATTENTION_GEO_KEY, PAGE_ATTENTION_KEY, PAGE_ENCODER_INPUT_KEY, PAGE_READOUT_KEYS, SPEC_OPTIONS,
+                      check_attention_dropout, page_encoder_layer_prefix, page_options, state_dict_spec)
 
 _BUF_SUFFIX = ("running_mean", "running_var", "num_batches_tracked")
+
+
+def _page_encoder_extras(cfg, state_dict, said):
+    """The page encoder's own part of HotPathTrainer._check_page_layers: its depth and its feed-forward width."""
+    L, M = cfg["page_encoder_layers"], cfg["page_encoder_ffn_dim"]
+    depth = 0
+    while page_encoder_layer_prefix(depth) + "qkv.weight" in state_dict:
+        depth += 1
+    if depth != L:
+        raise ValueError("%s page_encoder_layers=%d, the state_dict holds %d layer(s) under page_encoder.layers "
+                         "(page_encoder_layers=%d): a checkpoint loads into the page encoder it was trained with only"
+                         % (said, L, depth, depth))
+    for l in range(L):
+        k = page_encoder_layer_prefix(l) + "ffn1.weight"
+        w = state_dict.get(k)
+        if torch.is_tensor(w) and (w.dim() != 2 or w.shape[0] != M):
+            raise ValueError("%s page_encoder_ffn_dim=%d, the state_dict's %s has shape %s (page_encoder_ffn_dim=%s)"
+                             % (said, M, k, tuple(w.shape), w.shape[0] if w.dim() == 2 else "?"))
+
+
+# HotPathTrainer._check_page_layers, per page layer: (width option, the layer in words, key prefix, the keys a checkpoint
+# with the layer holds (the first one is probed: ITS rows / ``rows`` are the option's value), rows, geometry = (option,
+# heads option, cfg -> the geometry weights' keys) or None, the layer's own further checks or None)
+_PAGE_CHECKS = (
+    ("page_context_dim", "a page readout", "page_readout.", PAGE_READOUT_KEYS, 1, None, None),
+    ("page_attention_dim", "page attention", "page_attention.", (PAGE_ATTENTION_KEY,), 3,
+     ("page_attention_geometry", "page_attention_heads", lambda cfg: (PAGE_ATTENTION_GEO_KEY,)), None),
+    ("page_encoder_dim", "a page encoder", "page_encoder.", (PAGE_ENCODER_INPUT_KEY,), 1,
+     ("page_encoder_geometry", "page_encoder_heads",
+      lambda cfg: [page_encoder_layer_prefix(l) + "geometry.weight" for l in range(cfg["page_encoder_layers"])]),
+     _page_encoder_extras),
+)
 
 
 def is_param_key(k):
@@ -331,30 +359,10 @@ class HotPathTrainer:
         self.cfg = dict(cfg)
         if "attention_dropout" in cfg:          # (no weights: not an argument of state_dict_spec)
             self.cfg["attention_dropout"] = check_attention_dropout(cfg["attention_dropout"])
-        if "page_context_dim" in cfg:
-            self.cfg["page_context_dim"] = check_page_context_dim(cfg["page_context_dim"])
-        if "page_attention_dim" in cfg or "page_attention_heads" in cfg:
-            self.cfg["page_attention_dim"], self.cfg["page_attention_heads"] = check_page_attention(
-                cfg.get("page_attention_dim", 0), cfg.get("page_attention_heads", 1))
-        if "page_attention_geometry" in cfg:
-            self.cfg["page_attention_geometry"] = check_page_attention_geometry(
-                cfg["page_attention_geometry"], self.cfg.get("page_attention_dim", 0))
-        if any(k in cfg for k in _PAGE_ENCODER_OPTIONS):
-            self.cfg.update(zip(_PAGE_ENCODER_OPTIONS, check_page_encoder(
-                cfg.get("page_encoder_dim", 0), cfg.get("page_encoder_heads", 1), cfg.get("page_encoder_layers", 1),
-                cfg.get("page_encoder_ffn_dim"), cfg.get("page_encoder_geometry", False))))
-        self._check_page_readout(state_dict)        # (before any device work)
-        self._check_page_attention(state_dict)
-        self._check_page_encoder(state_dict)
+        self.cfg.update(page_options(cfg))
+        self._check_page_layers(state_dict)         # (before any device work)
         self.device = torch.device(device)
-        spec = state_dict_spec(**{k: cfg[k] for k in ("roi_output_size", "n_classes", "use_context",
-                                                     "hidden_dim", "bbox_hidden_dim", "n_additional_feat",
-                                                     "backbone", "n_heads", "n_gat_layers", "backbone_layers",
-                                                     "edge_geometry", "attention", "page_context_dim",
-                                                     "page_attention_dim", "page_attention_heads",
-                                                     "page_attention_geometry")
-                                  if k in cfg},
-                               **{k: self.cfg[k] for k in _PAGE_ENCODER_OPTIONS if k in self.cfg})
+        spec = state_dict_spec(**{k: self.cfg[k] for k in SPEC_OPTIONS if k in self.cfg})
         pshapes = OrderedDict((k, s) for k, s in spec if is_param_key(k))
         self.pbucket = FlatBucket(pshapes, self.device)
         self.gbucket = FlatBucket(pshapes, self.device)
@@ -404,94 +412,40 @@ class HotPathTrainer:
                                  % (mode, k, tuple(p.shape), tuple(v.shape),
                                     " (attention=%r)" % other if other and other != mode else ""))
 
-    def _check_page_readout(self, state_dict):
-        """A checkpoint trained without the page readout lacks the ``page_readout.*`` entries (and its decoder is narrower),
-        one trained with it carries them: name the option instead of failing on a key or a tensor size."""
-        G = self.cfg.get("page_context_dim", 0)
-        have = [k for k in PAGE_READOUT_KEYS if k in state_dict]
-        if G > 0 and len(have) < len(PAGE_READOUT_KEYS):
-            raise ValueError("this trainer was configured with page_context_dim=%d, the state_dict lacks %s: a checkpoint "
-                             "loads into the page_context_dim it was trained with only"
-                             % (G, [k for k in PAGE_READOUT_KEYS if k not in have]))
-        if G == 0 and have:
-            raise ValueError("this trainer was configured without a page readout (page_context_dim=0), the state_dict "
-                             "holds %s: a checkpoint loads into the page_context_dim it was trained with only" % have)
-        w = state_dict.get(PAGE_READOUT_KEYS[0]) if G > 0 else None
-        if torch.is_tensor(w) and (w.dim() != 2 or w.shape[0] != G):
-            raise ValueError("this trainer was configured with page_context_dim=%d, the state_dict's %s has shape %s "
-                             "(page_context_dim=%s)" % (G, PAGE_READOUT_KEYS[0], tuple(w.shape),
-                                                        w.shape[0] if w.dim() == 2 else "?"))
-
-    def _check_page_attention(self, state_dict):
-        """As _check_page_readout, for ``page_attention.qkv.weight``: a checkpoint of the other kind names the option."""
-        E = self.cfg.get("page_attention_dim", 0)
-        w = state_dict.get(PAGE_ATTENTION_KEY)
-        if E > 0 and w is None:
-            raise ValueError("this trainer was configured with page_attention_dim=%d, the state_dict lacks %s: a checkpoint "
-                             "loads into the page_attention_dim it was trained with only" % (E, PAGE_ATTENTION_KEY))
-        if E == 0 and w is not None:
-            raise ValueError("this trainer was configured without page attention (page_attention_dim=0), the state_dict "
-                             "holds %s: a checkpoint loads into the page_attention_dim it was trained with only"
-                             % PAGE_ATTENTION_KEY)
-        if E > 0 and torch.is_tensor(w) and (w.dim() != 2 or w.shape[0] != 3 * E):
-            raise ValueError("this trainer was configured with page_attention_dim=%d, the state_dict's %s has shape %s "
-                             "(page_attention_dim=%s)" % (E, PAGE_ATTENTION_KEY, tuple(w.shape),
-                                                          w.shape[0] // 3 if w.dim() == 2 else "?"))
-        geo, gw = bool(self.cfg.get("page_attention_geometry", False)), state_dict.get(PAGE_ATTENTION_GEO_KEY)
-        if geo and gw is None:
-            raise ValueError("this trainer was configured with page_attention_geometry=True, the state_dict lacks %s: a "
-                             "checkpoint loads into the page_attention_geometry it was trained with only"
-                             % PAGE_ATTENTION_GEO_KEY)
-        if not geo and gw is not None:
-            raise ValueError("this trainer was configured without the page attention's geometry bias "
-                             "(page_attention_geometry=False), the state_dict holds %s: a checkpoint loads into the "
-                             "page_attention_geometry it was trained with only" % PAGE_ATTENTION_GEO_KEY)
-        Hh = self.cfg.get("page_attention_heads", 1)
-        if geo and torch.is_tensor(gw) and tuple(gw.shape) != (Hh, 8):
-            raise ValueError("this trainer was configured with page_attention_geometry=True and page_attention_heads=%d, "
-                             "the state_dict's %s has shape %s" % (Hh, PAGE_ATTENTION_GEO_KEY, tuple(gw.shape)))
-
-    def _check_page_encoder(self, state_dict):
-        """As _check_page_attention, for the ``page_encoder.*`` entries: a checkpoint loads only into the width, depth,
-        feed-forward width and geometry option it was trained with, and the message names the option."""
-        P, L = self.cfg.get("page_encoder_dim", 0), self.cfg.get("page_encoder_layers", 1)
-        have = [k for k in state_dict if isinstance(k, str) and k.startswith("page_encoder.")]
-        tail = ": a checkpoint loads into the page encoder it was trained with only"
-        if P == 0:
-            if have:
-                raise ValueError("this trainer was configured without a page encoder (page_encoder_dim=0), the state_dict "
-                                 "holds %s%s" % (have[:2], tail))
-            return
-        w = state_dict.get(PAGE_ENCODER_INPUT_KEY)
-        if w is None:
-            raise ValueError("this trainer was configured with page_encoder_dim=%d, the state_dict lacks %s%s"
-                             % (P, PAGE_ENCODER_INPUT_KEY, tail))
-        if torch.is_tensor(w) and (w.dim() != 2 or w.shape[0] != P):
-            raise ValueError("this trainer was configured with page_encoder_dim=%d, the state_dict's %s has shape %s "
-                             "(page_encoder_dim=%s)" % (P, PAGE_ENCODER_INPUT_KEY, tuple(w.shape),
-                                                        w.shape[0] if w.dim() == 2 else "?"))
-        depth = 0
-        while page_encoder_layer_prefix(depth) + "qkv.weight" in state_dict:
-            depth += 1
-        if depth != L:
-            raise ValueError("this trainer was configured with page_encoder_layers=%d, the state_dict holds %d layer(s) "
-                             "under page_encoder.layers (page_encoder_layers=%d)%s" % (L, depth, depth, tail))
-        M, Hh = self.cfg["page_encoder_ffn_dim"], self.cfg.get("page_encoder_heads", 1)
-        geo = bool(self.cfg.get("page_encoder_geometry", False))
-        for l in range(L):
-            k = page_encoder_layer_prefix(l) + "ffn1.weight"
-            w = state_dict.get(k)
-            if torch.is_tensor(w) and (w.dim() != 2 or w.shape[0] != M):
-                raise ValueError("this trainer was configured with page_encoder_ffn_dim=%d, the state_dict's %s has shape "
-                                 "%s (page_encoder_ffn_dim=%s)" % (M, k, tuple(w.shape), w.shape[0] if w.dim() == 2 else "?"))
-            k = page_encoder_layer_prefix(l) + "geometry.weight"
-            gw = state_dict.get(k)
-            if geo != (gw is not None):
-                raise ValueError("this trainer was configured with page_encoder_geometry=%r, the state_dict %s %s%s"
-                                 % (geo, "lacks" if geo else "holds", k, tail))
-            if geo and torch.is_tensor(gw) and tuple(gw.shape) != (Hh, 8):
-                raise ValueError("this trainer was configured with page_encoder_geometry=True and page_encoder_heads=%d, "
-                                 "the state_dict's %s has shape %s" % (Hh, k, tuple(gw.shape)))
+    def _check_page_layers(self, state_dict):
+        """A checkpoint loads only into the page layers it was trained with: found from its keys and shapes, and the
+        message names the option instead of failing on a key or a tensor size (_PAGE_CHECKS: one row per layer)."""
+        said = "this trainer was configured with"
+        for option, what, prefix, keys, rows, geometry, extras in _PAGE_CHECKS:
+            value = self.cfg.get(option, 0)
+            tail = ": a checkpoint loads into the %s it was trained with only" % option
+            have = [k for k in state_dict if isinstance(k, str) and k.startswith(prefix)]
+            if value == 0:
+                if have:
+                    raise ValueError("%sout %s (%s=0), the state_dict holds %s%s" % (said, what, option, have[:2], tail))
+                continue
+            if any(k not in state_dict for k in keys):
+                raise ValueError("%s %s=%d, the state_dict lacks %s%s"
+                                 % (said, option, value, [k for k in keys if k not in state_dict], tail))
+            w = state_dict[keys[0]]
+            if torch.is_tensor(w) and (w.dim() != 2 or w.shape[0] != rows * value):
+                raise ValueError("%s %s=%d, the state_dict's %s has shape %s (%s=%s)"
+                                 % (said, option, value, keys[0], tuple(w.shape), option,
+                                    w.shape[0] // rows if w.dim() == 2 else "?"))
+            if extras is not None:
+                extras(self.cfg, state_dict, said)
+            if geometry is None:
+                continue
+            geo_option, heads_option, geo_keys = geometry
+            geo, Hh = bool(self.cfg.get(geo_option, False)), self.cfg.get(heads_option, 1)
+            for k in geo_keys(self.cfg):
+                gw = state_dict.get(k)
+                if geo != (gw is not None):
+                    raise ValueError("%s %s=%r, the state_dict %s %s: a checkpoint loads into the %s it was trained with "
+                                     "only" % (said, geo_option, geo, "lacks" if geo else "holds", k, geo_option))
+                if geo and torch.is_tensor(gw) and tuple(gw.shape) != (Hh, 8):
+                    raise ValueError("%s %s=True and %s=%d, the state_dict's %s has shape %s"
+                                     % (said, geo_option, heads_option, Hh, k, tuple(gw.shape)))
 
     def _flat_buffers(self, spec):
         """Live BatchNorm buffers of an averaging trainer -> {key: view}: ``bbucket`` (float32, running_mean /
@@ -898,9 +852,7 @@ class HotPathTrainer:
         With ``average=`` the average restarts from what was loaded, as reset_average() does; to resume an average,
         load the state dict first and the optimizer state (which carries the average) after it."""
         self._not_averaged("load_state_dict")
-        self._check_page_readout(state_dict)
-        self._check_page_attention(state_dict)
-        self._check_page_encoder(state_dict)
+        self._check_page_layers(state_dict)
         missing = [k for k in list(self.params) + list(self.buffers) if k not in state_dict]
         # sizes are part of the validation every rank agrees on BEFORE any copy / broadcast: a tensor of the wrong size on
         # one rank raising inside copy_ would leave the other ranks blocked in dist.broadcast

@@ -7,7 +7,8 @@ ImageNet weights are not available offline, so parity work and the benchmark use
 drawn from a fixed numpy ``RandomState`` stream (legacy MT19937 => identical on every box),
 shaped exactly like the reference's 50 ``state_dict`` entries.
 """
-from collections import OrderedDict
+import inspect
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -120,6 +121,60 @@ def check_page_encoder(dim, heads=1, layers=1, ffn_dim=None, geometry=False):
     return dim, heads, int(layers), int(ffn_dim), bool(geometry)
 
 
+# Every page option with its default, in the order of CoVA's and state_dict_spec's arguments.
+PAGE_OPTION_DEFAULTS = (("page_context_dim", 0), ("page_attention_dim", 0), ("page_attention_heads", 1),
+                        ("page_attention_geometry", False), ("page_encoder_dim", 0), ("page_encoder_heads", 1),
+                        ("page_encoder_layers", 1), ("page_encoder_ffn_dim", None), ("page_encoder_geometry", False))
+PAGE_ENCODER_OPTIONS = tuple(k for k, _ in PAGE_OPTION_DEFAULTS if k.startswith("page_encoder_"))   # check_page_encoder's order
+
+
+def page_options(cfg):
+    """The page options of a cfg-like mapping (missing ones at their defaults), each through its check_* function -> a
+    dict of all nine, normalised.  A normalised dict passes again unchanged."""
+    v = {k: cfg.get(k, default) for k, default in PAGE_OPTION_DEFAULTS}
+    out = {"page_context_dim": check_page_context_dim(v["page_context_dim"])}
+    out["page_attention_dim"], out["page_attention_heads"] = check_page_attention(v["page_attention_dim"],
+                                                                                  v["page_attention_heads"])
+    out["page_attention_geometry"] = check_page_attention_geometry(v["page_attention_geometry"], out["page_attention_dim"])
+    out.update(zip(PAGE_ENCODER_OPTIONS, check_page_encoder(*(v[k] for k in PAGE_ENCODER_OPTIONS))))
+    return out
+
+
+# The head's context layers: what stands behind the F own features of a box in the decoder's input, in COLUMN order, which
+# is also the order of their state_dict entries (between the additional-feature BatchNorm and the decoder) and the order
+# in which engine.model_bwd runs their backwards.  That last order is part of the result: every layer ACCUMULATES its data
+# gradient into dcomb[:, :F], float sums do not commute, so the GAT adds first, then the readout, the page attention and
+# the encoder.  It is stated here and nowhere else; a new layer goes at the end.
+#   key: the layer's entry of engine.model_fwd's saved dict;  letter: its width's entry there;  option: the cfg entry that
+#   sets the width;  prefix: of its state_dict keys;  paged: reads the batch's page table;  width: cfg -> columns (0: off)
+ContextLayer = namedtuple("ContextLayer", "key letter option prefix paged width")
+CONTEXT_LAYERS = (
+    ContextLayer("gat", "D", "hidden_dim", "gat.", False, lambda cfg: cfg["hidden_dim"] if cfg["use_context"] else 0),
+    ContextLayer("readout", "G", "page_context_dim", "page_readout.", True, lambda cfg: cfg.get("page_context_dim", 0)),
+    ContextLayer("page_attn", "E", "page_attention_dim", "page_attention.", True,
+                 lambda cfg: cfg.get("page_attention_dim", 0)),
+    ContextLayer("page_enc", "P", "page_encoder_dim", "page_encoder.", True, lambda cfg: cfg.get("page_encoder_dim", 0)),
+)
+HeadLayout = namedtuple("HeadLayout", "n_vis Hd A F layers T page_option")
+
+
+def head_layout(cfg, n_vis):
+    """Columns of the decoder's input for ``cfg`` over ``n_vis`` visual columns: [visual | bbox Hd | additional A] = the F
+    own features, then the context layers.  ``layers`` = ((key, offset, width), ...) in CONTEXT_LAYERS order, width 0 for
+    a layer that is off; ``T`` the total width; ``page_option`` the option of the first layer on that reads the page table
+    (None: the batch needs none).  The one place that adds the widths up."""
+    Hd, A = cfg["bbox_hidden_dim"], cfg["n_additional_feat"]
+    T = F = n_vis + Hd + A
+    layers, page_option = [], None
+    for layer in CONTEXT_LAYERS:
+        width = layer.width(cfg)
+        layers.append((layer.key, T, width))
+        T += width
+        if width > 0 and layer.paged and page_option is None:
+            page_option = layer.option
+    return HeadLayout(n_vis, Hd, A, F, tuple(layers), T, page_option)
+
+
 def page_encoder_layer_prefix(l):
     return "page_encoder.layers.%d." % l
 
@@ -230,11 +285,7 @@ def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidde
     ``page_encoder_ffn_dim`` (None: 2 P), then ``page_encoder.norm.weight`` / ``.bias`` [P]; the decoder is P columns wider."""
     check_backbone_layers(backbone, backbone_layers)
     check_attention(attention)
-    page_context_dim = check_page_context_dim(page_context_dim)
-    page_attention_dim, page_attention_heads = check_page_attention(page_attention_dim, page_attention_heads)
-    page_attention_geometry = check_page_attention_geometry(page_attention_geometry, page_attention_dim)
-    enc = check_page_encoder(page_encoder_dim, page_encoder_heads, page_encoder_layers, page_encoder_ffn_dim,
-                             page_encoder_geometry)
+    page = page_options(locals())
     c = BACKBONE_CHANNELS
     spec = [("convnet.0.weight", (c, 3, 7, 7))]
     spec += _bn_entries("convnet.1.", c)
@@ -271,14 +322,15 @@ def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidde
                 spec.append((p + "downsample.0.weight", (c2, c, 1, 1)))
                 spec += _bn_entries(p + "downsample.1.", c2)
     n_visual = backbone_channels(backbone, backbone_layers) * roi_output_size[0] * roi_output_size[1]
-    n_feat = n_visual + bbox_hidden_dim + n_additional_feat
+    layout = head_layout(dict(page, use_context=use_context, hidden_dim=hidden_dim, bbox_hidden_dim=bbox_hidden_dim,
+                              n_additional_feat=n_additional_feat), n_visual)
+    n_feat, n_total = layout.F, layout.T
     if bbox_hidden_dim > 0:
         spec += [("bbox_feat_encoder.0.weight", (bbox_hidden_dim, 5)),
                  ("bbox_feat_encoder.0.bias", (bbox_hidden_dim,))]
         spec += _bn_entries("bbox_feat_encoder.1.", bbox_hidden_dim)
     if n_additional_feat > 0:
         spec += _bn_entries("bn_additional_feat.", n_additional_feat)
-    n_total = n_feat
     if use_context:
         if hidden_dim % n_heads:
             raise ValueError("hidden_dim must be divisible by n_heads")
@@ -292,23 +344,22 @@ def state_dict_spec(roi_output_size=(3, 3), n_classes=4, use_context=True, hidde
                          (p + "attention_layer.bias", (1,))]
                 if edge_geometry:
                     spec.append((p + "edge_layer.weight", (1, EDGE_FEATURES)))
-        n_total += hidden_dim
-    if page_context_dim > 0:
-        spec += [(PAGE_READOUT_KEYS[0], (page_context_dim, n_feat)), (PAGE_READOUT_KEYS[1], (1, page_context_dim)),
-                 (PAGE_READOUT_KEYS[2], (1,))]
-        n_total += page_context_dim
-    if page_attention_dim > 0:
-        spec.append((PAGE_ATTENTION_KEY, (3 * page_attention_dim, n_feat)))
-        if page_attention_geometry:
-            spec.append((PAGE_ATTENTION_GEO_KEY, (page_attention_heads, EDGE_FEATURES)))
-        n_total += page_attention_dim
-    if enc[0] > 0:
-        spec += page_encoder_entries(n_feat, *enc)
-        n_total += enc[0]
+    G, E = page["page_context_dim"], page["page_attention_dim"]
+    if G > 0:
+        spec += [(PAGE_READOUT_KEYS[0], (G, n_feat)), (PAGE_READOUT_KEYS[1], (1, G)), (PAGE_READOUT_KEYS[2], (1,))]
+    if E > 0:
+        spec.append((PAGE_ATTENTION_KEY, (3 * E, n_feat)))
+        if page["page_attention_geometry"]:
+            spec.append((PAGE_ATTENTION_GEO_KEY, (page["page_attention_heads"], EDGE_FEATURES)))
+    if page["page_encoder_dim"] > 0:
+        spec += page_encoder_entries(n_feat, *(page[k] for k in PAGE_ENCODER_OPTIONS))
     spec += [("decoder.1.weight", (n_total, n_total)), ("decoder.1.bias", (n_total,))]
     spec += _bn_entries("decoder.2.", n_total)
     spec += [("decoder.5.weight", (n_classes, n_total)), ("decoder.5.bias", (n_classes,))]
     return spec
+
+
+SPEC_OPTIONS = tuple(inspect.signature(state_dict_spec).parameters)     # the cfg entries that shape the state_dict
 
 
 def seeded_state_dict(seed=123, logit_gain=1.0, **cfg):
