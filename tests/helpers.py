@@ -1,13 +1,116 @@
-"""Shared helpers for the parity tests (fixture loading, seeded regeneration of inputs)."""
+"""Shared helpers for the parity tests (fixture loading, seeded regeneration of inputs, the tolerances the whole model is
+held to, guarded buffers, launch counting)."""
 import os
+import socket
 
 import numpy as np
 import torch
 
 import cova_amd  # noqa: F401
-from cova_web_object_detection_amd import synthetic, weights
+from cova_web_object_detection_amd import _lib, synthetic, weights
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+DEV = "cuda:0"
+# The whole model against the reference's fixtures (tests/test_model_gpu.py::test_full_model_matches_reference_fixture):
+# ~5x the measured f32 round-off of logits (over the logit scale), the summed loss (relative) and every gradient (over its
+# tensor's scale, helpers.compare_grads).
+LOGIT_TOL, LOSS_TOL, GRAD_TOL = 5e-5, 2e-5, 1e-4
+# cova_sgemm against a float64 product, max error over max reference (tests/test_kernels_gpu.py)
+SGEMM_TOL = 2e-5
+GUARD = -7.0                               # the frame of framed(): no kernel under test produces it
+NAN = float("nan")
+
+
+def relerr(got, ref, scale=None):
+    """max |got - ref| over max |ref| (or over ``scale``), in float64"""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    return np.abs(got - ref).max() / max(np.abs(ref).max() if scale is None else scale, 1e-6)
+
+
+def close(got, ref, tol=1e-4, name=""):
+    """assert max |got - ref| <= tol * max |ref| over two tensors of one shape -> the ratio"""
+    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
+    assert got.shape == ref.shape, (name, got.shape, ref.shape)
+    err = (got - ref).abs().max().item() / max(ref.abs().max().item(), 1e-6)
+    print("%s: max|err|/max|ref| = %.3e (gate %.1e)" % (name, err, tol))
+    assert err <= tol, "%s: max|err|/max|ref| = %.3e > %.1e" % (name, err, tol)
+    return err
+
+
+def bits_equal(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
+
+
+def bits(t):
+    """a tensor or array on the host, float32 as its int32 bit patterns (integer buffers compare as they are)"""
+    t = t.detach().cpu() if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t))
+    return t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t
+
+
+def np_bits(a):
+    """a tensor or array as float32, viewed as numpy uint32 bit patterns"""
+    a = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def random_xyxy(rs, n, size=300.0, max_wh=80):
+    """[n, 4] corner boxes of one page; x2 = x1 + w in float32, as the collation adds them"""
+    wh = rs.uniform(4, max_wh, (n, 2))
+    xy = rs.uniform(0, 1, (n, 2)) * (size - wh)
+    b = np.concatenate([xy, wh], 1).astype(np.float32)
+    b[:, 2:] = b[:, :2] + b[:, 2:]
+    return b
+
+
+def profiled(fn):
+    """fn() with the library's launch log installed -> (fn's value, {entry point: number of calls})"""
+    _lib.PROFILE = {n: [] for n in _lib.lib().fn}
+    try:
+        out = fn()
+        torch.cuda.synchronize()
+    finally:
+        prof, _lib.PROFILE = _lib.PROFILE, None
+    return out, {n: len(v) for n, v in prof.items() if v}
+
+
+def free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def starts(sizes):
+    """page sizes -> the int64 page_start table [B + 1]"""
+    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+
+
+def framed(rows, cols, ld):
+    """A GUARD-filled [rows + 2, ld] buffer whose interior [1:rows+1, :cols] is NaN -> (buffer, interior view)."""
+    buf = torch.full((rows + 2, ld), GUARD, dtype=torch.float32, device=DEV)
+    buf[1:rows + 1, :cols] = NAN
+    return buf, buf[1:rows + 1]
+
+
+def padded(a, ld):
+    """The rows of ``a`` at leading dimension ld, the padding NaN: a kernel that reads past a row poisons its output."""
+    buf = torch.full((a.shape[0], ld), NAN, dtype=torch.float32, device=DEV)
+    buf[:, :a.shape[1]] = torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    return buf
+
+
+def survived(buf, rows, cols, unwritten=()):
+    """The interior of a framed buffer: every entry written (the rows ``unwritten`` not at all), the frame intact."""
+    host = buf.cpu().numpy()
+    inner = host[1:rows + 1, :cols].copy()
+    live = np.ones(rows, bool)
+    live[list(unwritten)] = False
+    assert np.isfinite(inner[live]).all(), "an output was not written"
+    assert np.isnan(inner[~live]).all(), "a row of an empty page was written"
+    host[1:rows + 1, :cols] = GUARD
+    assert (host == GUARD).all(), "a guard row or column was overwritten"
+    return inner
 FULL_CASES = ["cova_h64_n11", "cova_h64_n90", "cova_h128_ragged", "cova_h64_addfeat",
               # other points of the reference's hyper-parameter space (--roi, --context_size 0, head widths, -cs 1):
               "cova_roi1_bare", "cova_cs0", "cova_roi2x3_cs1", "cova_roi5_odd"]

@@ -20,11 +20,10 @@ import accumulate_oracle as GO  # noqa: E402
 from cova_web_object_detection_amd import _lib, evaluation, weights  # noqa: E402
 from cova_web_object_detection_amd import trainer as T  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
-from test_ddp_cpu import _free_port  # noqa: E402
+from config_cases import BASE as CFG, spec_of  # noqa: E402
+from helpers import free_port  # noqa: E402
 
-CFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8,
-           n_additional_feat=0, drop_prob=0.0)
-WCFG = {k: v for k, v in CFG.items() if k != "drop_prob"}
+WCFG = spec_of(CFG)
 SD = weights.seeded_state_dict(3, **WCFG)
 FROZEN = ("convnet.0.", "convnet.1.")
 
@@ -405,7 +404,7 @@ def _counter_worker(rank, world, port, out_dir):
 
 @pytest.mark.timeout(300)
 def test_counters_travel_with_broadcast_state_and_a_broadcast_optimizer_state(tmp_path):
-    world, port = 2, _free_port()
+    world, port = 2, free_port()
     mp.spawn(_counter_worker, args=(world, port, str(tmp_path)), nprocs=world, join=True)
     for r in (torch.load(os.path.join(str(tmp_path), "c%d.pt" % r)) for r in range(world)):
         assert r["after"] == (20, 9, 4, [True])              # rank 0's

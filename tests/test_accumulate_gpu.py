@@ -19,20 +19,17 @@ from cova_web_object_detection_amd.evaluation import evaluate_split, fit  # noqa
 from cova_web_object_detection_amd.pipeline import DeviceDataset  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
 import accumulate_oracle as GO  # noqa: E402
-from helpers import HARD_RAGGED as RAGGED, N_BACKING, N_RAGGED, on_device, ragged_inside, seg_table  # noqa: E402
+from helpers import (bits, DEV, HARD_RAGGED as RAGGED, N_BACKING,  # noqa: E402
+                     N_RAGGED, on_device, profiled, ragged_inside, seg_table)
+from config_cases import SPLIT_CFG as ECFG, TRAINER_CFG as CFG  # noqa: E402
+from trainer_cases import device_setup as trainer_setup, page_set  # noqa: E402
 
-DEV = "cuda:0"
 SENTINEL = 0x7FC12345                      # a NaN with a payload: any arithmetic on it, or any store over it, shows
 GARBAGE = 0x7FC0BEEF                       # what an accumulator holds before its first cycle
 
 # RAGGED is the hard ragged table of tests/helpers.py (the malformed row's [8900, 9000) keeps the sentinel).  The clips: the
 # full range; an unaligned start inside row (3005, 3007) and an end inside row (6600, 8800); an empty clip
 CLIPS = {"full": (0, N_RAGGED), "cut": (3006, 7001), "empty": (5000, 5000)}
-
-
-def bits(t):
-    t = t.detach().cpu() if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t))
-    return t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t
 
 
 def pattern(x):
@@ -116,28 +113,7 @@ def test_no_launch_and_error_cases():
 
 
 # ---------------------------------------------------------------------------------------------- the trainer
-CFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=48, bbox_hidden_dim=16,
-           n_additional_feat=0, drop_prob=0.0)
 FROZEN = ("convnet.0.", "convnet.1.")
-
-
-@functools.lru_cache(maxsize=None)
-def trainer_setup(seed=77):
-    """The tiny trainer of tests/test_weight_average_gpu.py."""
-    sd = weights.seeded_state_dict(seed, logit_gain=2.0, **{k: v for k, v in CFG.items() if k != "drop_prob"})
-    batches = [synthetic.make_batch(2, img_h=96, boxes_per_page=[20 + 3 * i, 11 + 2 * i], context_size=6, seed=900 + i)
-               for i in range(3)]
-    return sd, [{k: v.to(DEV) for k, v in b.items() if torch.is_tensor(v)} for b in batches]
-
-
-def _profiled(fn):
-    _lib.PROFILE = {n: [] for n in _lib.lib().fn}
-    try:
-        fn()
-        torch.cuda.synchronize()
-    finally:
-        prof, _lib.PROFILE = _lib.PROFILE, None
-    return {n: len(v) for n, v in prof.items() if v}
 
 
 def trainable_rows(tr):
@@ -243,18 +219,18 @@ def test_launch_counts_and_no_host_synchronisation(monkeypatch):
     sd, batches = trainer_setup()
     for kw in (dict(), dict(frozen=FROZEN), dict(optimizer="adamw", max_grad_norm=1.0)):
         parent, one = HotPathTrainer(CFG, sd, DEV, **kw), HotPathTrainer(CFG, sd, DEV, accumulate_steps=1, **kw)
-        step = _profiled(lambda: parent.train_step(batches[0]))
-        assert _profiled(lambda: one.train_step(batches[0])) == step and "cova_grad_accumulate" not in step
-        assert not hasattr(one, "accbucket") and _profiled(one.flush) == {}
-        fb = _profiled(lambda: parent.forward_backward(batches[0]))
+        step = profiled(lambda: parent.train_step(batches[0]))[1]
+        assert profiled(lambda: one.train_step(batches[0]))[1] == step and "cova_grad_accumulate" not in step
+        assert not hasattr(one, "accbucket") and profiled(one.flush)[1] == {}
+        fb = profiled(lambda: parent.forward_backward(batches[0]))[1]
         update = {k: v - fb.get(k, 0) for k, v in step.items() if v != fb.get(k, 0)}     # the optimizer's launches
         tr = HotPathTrainer(CFG, sd, DEV, accumulate_steps=3, **kw)
         for it in range(2):                                  # open, add: the backward's launches and one more
-            assert _profiled(lambda: tr.train_step(batches[0])) == dict(fb, cova_grad_accumulate=1), (kw, it)
-        assert _profiled(lambda: tr.train_step(batches[0])) == dict(step, cova_grad_accumulate=1), kw
-        assert _profiled(tr.flush) == {}                     # nothing pending: nothing launched
+            assert profiled(lambda: tr.train_step(batches[0]))[1] == dict(fb, cova_grad_accumulate=1), (kw, it)
+        assert profiled(lambda: tr.train_step(batches[0]))[1] == dict(step, cova_grad_accumulate=1), kw
+        assert profiled(tr.flush)[1] == {}                     # nothing pending: nothing launched
         tr.train_step(batches[0])
-        assert update and _profiled(tr.flush) == dict(update, cova_grad_accumulate=1), kw
+        assert update and profiled(tr.flush)[1] == dict(update, cova_grad_accumulate=1), kw
     # the order of the closing micro-step: the backward, the one accumulate launch, then the optimizer's launches
     tr = HotPathTrainer(CFG, sd, DEV, accumulate_steps=2, optimizer="adamw", max_grad_norm=1.0)
     calls = _recorded(monkeypatch)
@@ -371,24 +347,7 @@ def test_two_accumulated_halves_are_the_whole_batch():
 
 
 # ---------------------------------------------------------------------------------------------- fit
-ECFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8,
-            n_additional_feat=0, drop_prob=0.2)
 CS = 6
-
-
-def page_set(P, img=96, seed=4):
-    """The construction of tests/test_evaluation_gpu.py's page_set."""
-    rs = np.random.RandomState(seed)
-    u8 = rs.randint(0, 256, (P, img, img, 3)).astype(np.uint8)
-    rows = []
-    for _ in range(P):
-        n = int(rs.randint(11, 40))
-        wh = rs.uniform(6, 40, (n, 2))
-        xy = rs.uniform(0, 1, (n, 2)) * (img - wh)
-        lab = np.zeros((n, 1))
-        lab[rs.permutation(n)[:3], 0] = [1, 2, 3]
-        rows.append(np.concatenate([xy, wh, lab], 1).astype(np.float32))
-    return u8, rows
 
 
 def hand_loop(tr, train, val, n_epochs, bs, sf, seed, interval, k, lr_schedule):

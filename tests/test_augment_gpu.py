@@ -13,9 +13,8 @@ from cova_web_object_detection_amd.pipeline import DeviceCollate, DeviceDataset,
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
 import augment_oracle as AO  # noqa: E402
 import graph_oracle as GO  # noqa: E402
-from helpers import load_case  # noqa: E402
+from helpers import DEV, load_case, profiled  # noqa: E402
 
-DEV = "cuda:0"
 SENTINEL = 7.0
 FILLS = (0x000000, 0xFFFFFF, 0x010203)
 KEYS = ("images", "bboxes", "labels", "context_indices", "additional_feats", "page_start")
@@ -25,16 +24,6 @@ def same(a, b):
     a = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
     b = b.cpu().numpy() if torch.is_tensor(b) else np.asarray(b)
     return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a, b)
-
-
-def profiled(fn):
-    _lib.PROFILE = {n: [] for n in _lib.lib().fn}
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-    finally:
-        prof, _lib.PROFILE = _lib.PROFILE, None
-    return out, {n: len(v) for n, v in prof.items() if v}
 
 
 def run(store, idx, B, shift, color, fill, out=None):

@@ -44,15 +44,15 @@ from cova_web_object_detection_amd.features import FeatureCache  # noqa: E402
 from cova_web_object_detection_amd.models import CoVA  # noqa: E402
 from cova_web_object_detection_amd.pipeline import DeviceDataset  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
-from helpers import compare_grads, routing_from_saved  # noqa: E402
+from helpers import compare_grads, DEV, GRAD_TOL, LOGIT_TOL, LOSS_TOL, profiled, routing_from_saved, SGEMM_TOL  # noqa: E402
 from oracle import cova_oracle as O  # noqa: E402
 import attn_dropout_oracle as AD  # noqa: E402
 import combined_cases as CC  # noqa: E402
 import combined_oracle as CO  # noqa: E402
-from test_page_readout_gpu import CFG, DEV, device_gates, page_set, profiled  # noqa: E402
+from config_cases import SPLIT_CFG as CFG  # noqa: E402
+from gat_cases import device_gates  # noqa: E402
+from trainer_cases import page_set  # noqa: E402
 
-LOGIT_TOL, LOSS_TOL, GRAD_TOL = 5e-5, 2e-5, 1e-4          # tests/test_model_gpu.py
-SGEMM_TOL = 2e-5                                          # tests/test_kernels_gpu.py
 NEW_PREFIXES = ("gat.", "page_readout.", "page_attention.")
 relerr = CC.relerr
 

@@ -3,7 +3,6 @@ all-reduce.  The HIP kernels cannot run here, so each rank's local gradients com
 oracle (test infrastructure); what is under test is the host logic of trainer.py that the GPU
 path uses unchanged (FlatBucket, shard_batch, all_reduce_sum)."""
 import os
-import socket
 import sys
 
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
@@ -18,17 +17,8 @@ import torch.multiprocessing as mp
 from cova_web_object_detection_amd import synthetic, weights
 from cova_web_object_detection_amd.trainer import FlatBucket, is_param_key, shard_batch, shard_pages
 from oracle import cova_oracle as O
-
-CFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32,
-           bbox_hidden_dim=16, n_additional_feat=0, drop_prob=0.0)
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from config_cases import DDP_CFG as CFG
+from helpers import free_port
 
 
 def _local_grads(batch):
@@ -84,7 +74,7 @@ def test_flat_bucket_views_alias_one_buffer():
 
 @pytest.mark.timeout(300)
 def test_gloo_allreduce_of_flat_bucket_equals_sum_of_shard_gradients(tmp_path):
-    world, port = 2, _free_port()
+    world, port = 2, free_port()
     mp.spawn(_worker, args=(world, port, str(tmp_path)), nprocs=world, join=True)
     full = synthetic.make_batch(4, img_h=64, boxes_per_page=[11, 20, 15, 30], context_size=4, seed=9)
     expect = None
@@ -139,7 +129,7 @@ def _state_worker(rank, world, port, out_dir):
 def test_trainer_state_loads_are_local_unless_broadcast_is_asked_for(tmp_path):
     """load_state_dict / load_optimizer_state_dict involve a collective only with broadcast=True; then keys are
     validated on every rank before the broadcast, which carries what was loaded and nothing else."""
-    world, port = 2, _free_port()
+    world, port = 2, free_port()
     mp.spawn(_state_worker, args=(world, port, str(tmp_path)), nprocs=world, join=True)
     r0, r1 = (torch.load(os.path.join(str(tmp_path), "s%d.pt" % r)) for r in range(world))
     assert torch.equal(r0["start"], r1["start"])

@@ -10,6 +10,7 @@ from cova_web_object_detection_amd import _lib, weights
 
 import edge_oracle as EO
 from oracle import cova_oracle as O
+from config_cases import SPLIT_CFG  # noqa: E402
 
 
 def brute_force(bboxes, ctx, img_w, img_h):
@@ -163,8 +164,7 @@ def test_header_declares_the_edge_entry_points():
 from cova_web_object_detection_amd import engine  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
 
-TCFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8, n_additional_feat=0,
-            drop_prob=0.2, n_heads=2, n_gat_layers=2, edge_geometry=True)
+TCFG = dict(SPLIT_CFG, n_heads=2, n_gat_layers=2, edge_geometry=True)
 TSD = weights.seeded_state_dict(5, **{k: v for k, v in TCFG.items() if k != "drop_prob"})
 EDGE_KEYS = [k for k in TSD if k.endswith("edge_layer.weight")]
 

@@ -19,29 +19,18 @@ from cova_web_object_detection_amd.features import FeatureCache  # noqa: E402
 from cova_web_object_detection_amd.models import CoVA, GraphAttentionLayer, MultiHeadGraphAttention  # noqa: E402
 from cova_web_object_detection_amd.pipeline import DeviceDataset, attention_rows  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
-from helpers import compare_grads, load_case, routing_from_saved  # noqa: E402
+from helpers import (compare_grads, DEV, GRAD_TOL, GUARD, load_case,  # noqa: E402
+                     LOGIT_TOL, LOSS_TOL, profiled, random_xyxy, relerr, routing_from_saved)
 from oracle import cova_oracle as O  # noqa: E402
 import edge_oracle as EO  # noqa: E402
 import graph_oracle as GO  # noqa: E402
+from config_cases import SPLIT_CFG as CFG  # noqa: E402
+from gat_cases import EDGE_W  # noqa: E402
+from trainer_cases import five_steps, page_set, seeded  # noqa: E402
 
-DEV = "cuda:0"
-GUARD = -7.0
-LOGIT_TOL, LOSS_TOL, GRAD_TOL = 5e-5, 2e-5, 1e-4          # tests/test_model_gpu.py
 NEW = ("cova_edge_geometry", "cova_gat_fwd_edge", "cova_gat_bwd_edge")
 PAGE = (1280.0, 1280.0)                                   # (height, width) of the kernel tests' pages
-
-
-def relerr(got, ref):
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    return np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-6)
-
-
-def random_boxes(rs, n, size=1280.0):
-    wh = rs.uniform(4, 300, (n, 2))
-    xy = rs.uniform(0, 1, (n, 2)) * (size - wh)
-    b = np.concatenate([xy, wh], 1).astype(np.float32)
-    b[:, 2:] = b[:, :2] + b[:, 2:]
-    return b
+random_boxes = functools.partial(random_xyxy, size=1280.0, max_wh=300)
 
 
 def as_batch(pages):
@@ -172,9 +161,6 @@ def oracle64(case, edge_w):
     return dict(hp=hp.detach().numpy(), attn=attn.detach().numpy(), dWh=h.grad.numpy(),
                 daw=sd["gat.attention_layer.weight"].grad.numpy().reshape(-1),
                 dab=sd["gat.attention_layer.bias"].grad.numpy(), dew=sd["gat.edge_layer.weight"].grad.numpy().reshape(-1))
-
-
-EDGE_W = np.asarray([1.5, -2.0, 0.75, -0.5, 3.0, -1.25, 2.0, 0.6], np.float32)
 
 
 @functools.lru_cache(maxsize=None)
@@ -320,16 +306,6 @@ def test_edge_aware_layer_under_autograd_matches_the_oracle():
     assert out.shape == (N, D) and lens["cova_edge_geometry"] == 1 and lens["cova_gat_fwd_edge"] == 4
 
 
-def profiled(fn):
-    _lib.PROFILE = {n: [] for n in _lib.lib().fn}
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-    finally:
-        prof, _lib.PROFILE = _lib.PROFILE, None
-    return out, {n: len(v) for n, v in prof.items() if v}
-
-
 def edge_gates(sv, routing):
     """routing_from_saved's LeakyReLU decisions, restated with the edge term the HIP forward added to u."""
     for layer in sv["gat"]:
@@ -397,33 +373,7 @@ def test_edge_aware_model_matches_the_oracle_on_the_reference_inputs(monkeypatch
 
 
 # ---------------------------------------------------------------- 4. the trainer
-CFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8,
-           n_additional_feat=0, drop_prob=0.2)
 ECFG = dict(CFG, edge_geometry=True)
-
-
-def page_set(P=15, img=96, seed=4):
-    rs = np.random.RandomState(seed)
-    u8 = rs.randint(0, 256, (P, img, img, 3)).astype(np.uint8)
-    rows = []
-    for _ in range(P):
-        n = int(rs.randint(11, 40))
-        wh = rs.uniform(6, 40, (n, 2))
-        xy = rs.uniform(0, 1, (n, 2)) * (img - wh)
-        lab = np.zeros((n, 1))
-        lab[rs.permutation(n)[:3], 0] = [1, 2, 3]
-        rows.append(np.concatenate([xy, wh, lab], 1).astype(np.float32))
-    return u8, rows
-
-
-def seeded(cfg):
-    return weights.seeded_state_dict(77, logit_gain=2.0, **{k: v for k, v in cfg.items() if k != "drop_prob"})
-
-
-def five_steps(tr, ds):
-    losses = [tr.train_step(batch)[0] for batch in ds.batches(3, shuffle=True, sampling_fraction=0.9, seed=12, epoch=0)]
-    assert len(losses) == 5 and all(np.isfinite(float(x)) for x in losses)
-    return [float(x) for x in losses], tr.state_dict()
 
 
 @pytest.mark.parametrize("kw", [dict(), dict(optimizer="adamw", max_grad_norm=1.0,

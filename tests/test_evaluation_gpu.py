@@ -11,14 +11,16 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from cova_web_object_detection_amd import _lib, engine, evaluation, weights  # noqa: E402
+from cova_web_object_detection_amd import _lib, engine, evaluation  # noqa: E402
 from cova_web_object_detection_amd.evaluation import EvalReport, evaluate_split, fit, step_lr  # noqa: E402
 from cova_web_object_detection_amd.pipeline import DeviceDataset  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer, LossMetrics  # noqa: E402
 from oracle import cova_oracle as O  # noqa: E402
 import eval_oracle as EO  # noqa: E402
+from config_cases import SPLIT_CFG as CFG  # noqa: E402
+from helpers import DEV  # noqa: E402
+from trainer_cases import page_set, seeded  # noqa: E402
 
-DEV = "cuda:0"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
@@ -136,35 +138,14 @@ def test_rows_outside_the_batch_keep_minus_two_and_bad_ids_are_skipped():
 
 
 # ---------------------------------------------------------------- the split of the trainer tests
-CFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8,
-           n_additional_feat=0, drop_prob=0.2)
 CS = 6
-
-
-def page_set(P=15, img=96, seed=4):
-    """The construction of tests/test_sampling_gpu.py's page_set."""
-    rs = np.random.RandomState(seed)
-    u8 = rs.randint(0, 256, (P, img, img, 3)).astype(np.uint8)
-    rows = []
-    for _ in range(P):
-        n = int(rs.randint(11, 40))
-        wh = rs.uniform(6, 40, (n, 2))
-        xy = rs.uniform(0, 1, (n, 2)) * (img - wh)
-        lab = np.zeros((n, 1))
-        lab[rs.permutation(n)[:3], 0] = [1, 2, 3]
-        rows.append(np.concatenate([xy, wh, lab], 1).astype(np.float32))
-    return u8, rows
-
-
-def seeded(seed=77):
-    return weights.seeded_state_dict(seed, logit_gain=2.0, **{k: v for k, v in CFG.items() if k != "drop_prob"})
 
 
 @functools.lru_cache(maxsize=None)
 def split37():
     """37 pages and the CPU oracle's tables, margins and logit scale (O.collate_reference + O.forward at batch 10)."""
     u8, rows = page_set(P=37, seed=4)
-    sd = seeded()
+    sd = seeded(CFG)
     ranks, margin, scale = [], [], 0.0
     for s in range(0, 37, 10):
         b = O.collate_reference(u8[s:s + 10], rows[s:s + 10], CS)
@@ -191,7 +172,7 @@ def assert_ranks_equal_where_decided(got, ref, margin, scale):
 def test_evaluate_split_equals_the_per_batch_route():
     u8, rows = page_set(P=37, seed=4)
     ds = DeviceDataset(u8, rows, CS, DEV)
-    tr = HotPathTrainer(CFG, seeded(), DEV)
+    tr = HotPathTrainer(CFG, seeded(CFG), DEV)
     rep = evaluate_split(tr, ds)
     assert rep.evaluated.all() and rep.unlabelled.tolist() == [0, 0, 0, 0] and rep.loss is None
     assert rep.img_ids.tolist() == ds.img_ids.tolist()
@@ -210,7 +191,7 @@ def test_evaluate_split_equals_the_per_batch_route():
 
 def test_evaluate_split_against_the_cpu_oracle():
     u8, rows, ref, margin, scale = split37()
-    rep = evaluate_split(HotPathTrainer(CFG, seeded(), DEV), DeviceDataset(u8, rows, CS, DEV))
+    rep = evaluate_split(HotPathTrainer(CFG, seeded(CFG), DEV), DeviceDataset(u8, rows, CS, DEV))
     assert_ranks_equal_where_decided(rep.ranks, ref, margin, scale)
     ref_rep, decided = EvalReport(ref), margin > 1e-3 * scale
     for k in (1, 3):
@@ -220,7 +201,7 @@ def test_evaluate_split_against_the_cpu_oracle():
 
 def test_rank_shards_merge_to_the_single_rank_tables():
     u8, rows, _, margin, scale = split37()
-    ds, tr = DeviceDataset(u8, rows, CS, DEV), HotPathTrainer(CFG, seeded(), DEV)
+    ds, tr = DeviceDataset(u8, rows, CS, DEV), HotPathTrainer(CFG, seeded(CFG), DEV)
     whole = evaluate_split(tr, ds)
     parts = [evaluate_split(tr, ds, rank=r, world_size=2, merge=False) for r in (0, 1)]
     assert parts[0].evaluated.tolist() == [p < 19 for p in range(37)]
@@ -265,7 +246,7 @@ def allowing(fn, allowed, calls=None):
 @pytest.mark.parametrize("with_loss", [False, True])
 def test_evaluate_split_reads_back_once(monkeypatch, with_loss):
     u8, rows = page_set(P=23, seed=6)
-    ds, tr = DeviceDataset(u8, rows, CS, DEV), HotPathTrainer(CFG, seeded(), DEV)
+    ds, tr = DeviceDataset(u8, rows, CS, DEV), HotPathTrainer(CFG, seeded(CFG), DEV)
     ref = evaluate_split(tr, ds, with_loss=with_loss)
     allowed, copies = [0], []
     refuse_host_reads(monkeypatch, allowed)
@@ -284,7 +265,7 @@ def test_evaluate_split_reads_back_once(monkeypatch, with_loss):
 def test_with_loss_gives_the_validation_loss_and_confusion(options):
     u8, rows = page_set(P=23, seed=6)
     ds = DeviceDataset(u8, rows, CS, DEV)
-    tr = HotPathTrainer(CFG, seeded(), DEV, track_metrics=True, **options)
+    tr = HotPathTrainer(CFG, seeded(CFG), DEV, track_metrics=True, **options)
     rep = evaluate_split(tr, ds, with_loss=True)
     assert int(tr.metrics.buf.abs().sum()) == 0                                   # trainer.metrics is not touched
     conf = np.zeros((4, 4), dtype=np.int64)
@@ -331,7 +312,7 @@ def test_fit_equals_the_loop_written_out_by_hand(tmp_path):
     u8, rows = page_set()
     v8, vrows = page_set(P=37, seed=9)                  # 111 decisions at k = 3: some hit from the first epoch on
     train, val = DeviceDataset(u8, rows, CS, DEV), DeviceDataset(v8, vrows, CS, DEV)
-    sd = seeded()
+    sd = seeded(CFG)
     kw = dict(lr=2e-3, track_metrics=True)
     a, b, c = (HotPathTrainer(CFG, sd, DEV, **kw) for _ in range(3))
     log, ckpt = str(tmp_path / "log.txt"), str(tmp_path / "best.pth")
@@ -376,7 +357,7 @@ def test_fit_equals_the_loop_written_out_by_hand(tmp_path):
 def test_fit_decisions_follow_its_own_history_and_the_schedule_skips_the_stopping_epoch():
     u8, rows = page_set(P=6)
     ds = DeviceDataset(u8, rows, CS, DEV)
-    tr = HotPathTrainer(CFG, seeded(), DEV, track_metrics=True)
+    tr = HotPathTrainer(CFG, seeded(CFG), DEV, track_metrics=True)
     scheduled = []
     res = fit(tr, ds, ds, 8, 3, sampling_fraction=1.0, eval_interval=1, patience=1, k=3,
               lr_schedule=lambda e: scheduled.append(e) or 1.0)
@@ -393,7 +374,7 @@ def test_fit_decisions_follow_its_own_history_and_the_schedule_skips_the_stoppin
 def test_fit_step_loop_reads_nothing_back(monkeypatch):
     u8, rows = page_set(P=9)
     ds = DeviceDataset(u8, rows, CS, DEV)
-    tr = HotPathTrainer(CFG, seeded(), DEV, track_metrics=True)
+    tr = HotPathTrainer(CFG, seeded(CFG), DEV, track_metrics=True)
     allowed, reads, evals = [0], [], []
     refuse_host_reads(monkeypatch, allowed)
     monkeypatch.setattr(LossMetrics, "read", allowing(LossMetrics.read, allowed, reads))

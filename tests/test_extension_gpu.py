@@ -18,10 +18,9 @@ pytestmark = pytest.mark.gpu
 from cova_web_object_detection_amd import engine, synthetic, weights  # noqa: E402
 from cova_web_object_detection_amd._lib import call, query  # noqa: E402
 from cova_web_object_detection_amd.models import CoVA  # noqa: E402
-from helpers import assert_gate_flips_near_zero, compare_grads, margins_ok, routing_from_saved  # noqa: E402
+from helpers import assert_gate_flips_near_zero, compare_grads, DEV, margins_ok, routing_from_saved  # noqa: E402
 from oracle import cova_oracle as O  # noqa: E402
-
-DEV = "cuda:0"
+from config_cases import make_cfg  # noqa: E402
 
 
 def close(got, ref, tol, what):
@@ -272,8 +271,7 @@ def test_bn_act2():
 
 # ------------------------------------------------------------------------------------ whole model
 def run_case(cfg_kw, img_h, img_w, boxes, cs, seed, hidden=96, tight=1e-4, bbox_hidden=32):
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=hidden, bbox_hidden_dim=bbox_hidden,
-               n_additional_feat=0, drop_prob=0.0)
+    cfg = make_cfg((3, 3), hidden, bbox_hidden)
     sd = weights.seeded_state_dict(seed, logit_gain=4.0, **{k: v for k, v in cfg.items() if k != "drop_prob"},
                                    **cfg_kw)
     batch = synthetic.make_batch(len(boxes), img_h=img_h, img_w=img_w, boxes_per_page=boxes, context_size=cs,
@@ -375,8 +373,7 @@ def test_eval_mode_backward_uses_frozen_batchnorm():
     """model.eval() + backward (frozen-BN fine-tuning, saliency): BatchNorm is a fixed affine map, so
     dz = scale*dy (torch's eval-mode batch_norm backward), not the train-mode formula."""
     for kw in (dict(), dict(backbone="resnet50", n_heads=2)):
-        cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=96, bbox_hidden_dim=32,
-                   n_additional_feat=0, drop_prob=0.0)
+        cfg = make_cfg((3, 3), 96, 32)
         sd = weights.seeded_state_dict(41, logit_gain=4.0, **{k: v for k, v in cfg.items() if k != "drop_prob"}, **kw)
         batch = synthetic.make_batch(2, img_h=64, boxes_per_page=[19, 26], context_size=6, seed=41)
         m = CoVA((3, 3), 64, 4, True, 96, 32, 0, 0.0, None, **kw)
@@ -398,8 +395,7 @@ def test_full_size_long_page_train_step_properties():
     """One train step of the reference architecture on a full-size configs[4] page (4096 x 1280, 300 boxes,
     K = 48): finite, BatchNorm output moments, and the crop property of the conv stack against torch-CPU."""
     H, W = 4096, 1280
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=384, bbox_hidden_dim=32,
-               n_additional_feat=0, drop_prob=0.0)
+    cfg = make_cfg((3, 3), 384, 32)
     sd = weights.seeded_state_dict(7, **{k: v for k, v in cfg.items() if k != "drop_prob"})
     boxes = synthetic.make_boxes_only(1, H, W, 300, 24, 7)
     g = torch.Generator(device=DEV).manual_seed(7)
@@ -448,8 +444,7 @@ def test_config5_model_on_a_full_length_page():
     crop property: the first 96 feature rows depend on the first ~400 pixel rows only)."""
     H, W = 4096, 1280
     kw = dict(backbone="resnet50", n_heads=2, n_gat_layers=2)
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=384, bbox_hidden_dim=32,
-               n_additional_feat=0, drop_prob=0.0, **kw)
+    cfg = dict(make_cfg((3, 3), 384, 32), **kw)
     sd = weights.seeded_state_dict(9, **{k: v for k, v in cfg.items() if k != "drop_prob"})
     boxes = synthetic.make_boxes_only(1, H, W, 300, 24, 9)
     g = torch.Generator(device=DEV).manual_seed(9)
@@ -496,8 +491,7 @@ def test_config3_batch_of_32_pages_reproducible_with_batchnorm_identities():
     its saved pre-activation."""
     from cova_web_object_detection_amd.trainer import HotPathTrainer
     kw = dict(backbone="resnet50", n_heads=2, n_gat_layers=1)
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=384, bbox_hidden_dim=32,
-               n_additional_feat=0, drop_prob=0.2, **kw)
+    cfg = dict(make_cfg((3, 3), 384, 32, drop_prob=0.2), **kw)
     sd = weights.seeded_state_dict(123, **{k: v for k, v in cfg.items() if k != "drop_prob"})
     pages = 32
     b = synthetic.make_boxes_only(pages, 1280, 1280, 90, 12, 123)
@@ -529,8 +523,7 @@ def test_piecewise_visual_features_backward(kw):
     """The members extract_attn_wts_and_visualize.py:117-124 calls piecewise are differentiable on their own:
     d(sum(visual * g)) through `_get_visual_features` (materialised feature map, stand-alone mask + BatchNorm sums)
     against autograd of the oracle's conv stack + RoIPool, routing forced to the HIP forward's decisions."""
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=48, bbox_hidden_dim=16,
-               n_additional_feat=0, drop_prob=0.0)
+    cfg = make_cfg((3, 3), 48, 16)
     sd = weights.seeded_state_dict(51, **{k: v for k, v in cfg.items() if k != "drop_prob"}, **kw)
     batch = synthetic.make_batch(2, img_h=64, img_w=96, boxes_per_page=[14, 20], context_size=6, seed=51)
     m = CoVA((3, 3), 64, 4, True, 48, 16, 0, 0.0, None, **kw)
@@ -583,8 +576,7 @@ def test_roialign_kernels_match_self_oracle(sr, aligned, C):
 
 @pytest.mark.parametrize("kw", [dict(roi_op="align"), dict(roi_op="align", backbone="resnet50", n_heads=2, sampling_ratio=0)])
 def test_model_with_roialign_matches_self_oracle(kw):
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=64, bbox_hidden_dim=16,
-               n_additional_feat=0, drop_prob=0.0)
+    cfg = make_cfg((3, 3), 64, 16)
     wkw = {k: v for k, v in kw.items() if k in ("backbone", "n_heads", "n_gat_layers")}
     sd = weights.seeded_state_dict(61, logit_gain=4.0, **{k: v for k, v in cfg.items() if k != "drop_prob"}, **wkw)
     batch = synthetic.make_batch(2, img_h=96, img_w=128, boxes_per_page=[15, 22], context_size=6, seed=61)

@@ -6,9 +6,7 @@ import torch
 import cova_amd  # noqa: F401
 from cova_web_object_detection_amd import engine, weights
 from cova_web_object_detection_amd.trainer import HotPathTrainer, is_param_key
-
-CFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=48, bbox_hidden_dim=16,
-           n_additional_feat=3)
+from config_cases import ADDL_SPEC as CFG
 
 
 def keys(backbone="resnet18"):

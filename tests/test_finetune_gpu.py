@@ -11,27 +11,20 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from cova_web_object_detection_amd import _lib, engine, synthetic, weights  # noqa: E402
+from cova_web_object_detection_amd import engine, synthetic, weights  # noqa: E402
 from cova_web_object_detection_amd.models import CoVA  # noqa: E402
-from helpers import compare_grads, routing_from_saved  # noqa: E402
+from helpers import compare_grads, DEV, GRAD_TOL, LOGIT_TOL, LOSS_TOL, profiled, relerr, routing_from_saved  # noqa: E402
 from oracle import cova_oracle as O  # noqa: E402
+from config_cases import make_cfg  # noqa: E402
 
-LOGIT_TOL, LOSS_TOL, GRAD_TOL = 5e-5, 2e-5, 1e-4
 # resnet50 (2304 visual features) and RoIAlign: 2e-4, as tests/test_extension_gpu.py for these configurations (measured:
 # one entry of decoder.1.bias -- analytically zero in front of a train-mode BatchNorm, i.e. rounding noise -- above 1e-4)
 GRAD_TOL_EXT = 2e-4
-DEV = "cuda:0"
 P_DROP = 0.3
 
 
-def relerr(got, ref):
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    return np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-6)
-
-
 def setup(backbone="resnet18", roi_op="pool", drop_prob=0.0, seed=5):
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=48, bbox_hidden_dim=16,
-               n_additional_feat=0, drop_prob=drop_prob)
+    cfg = make_cfg((3, 3), 48, 16, drop_prob=drop_prob)
     sd = weights.seeded_state_dict(seed, logit_gain=2.0, backbone=backbone,
                                    **{k: v for k, v in cfg.items() if k != "drop_prob"})
     batch = synthetic.make_batch(2, img_h=96, boxes_per_page=[14, 9], context_size=3, seed=seed + 1)
@@ -184,26 +177,15 @@ def test_first_dropout_in_eval_mode_is_the_identity(monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------- work really skipped
-def _profiled(fn):
-    names = list(_lib.lib().fn)
-    _lib.PROFILE = {n: [] for n in names}
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-    finally:
-        prof, _lib.PROFILE = _lib.PROFILE, None
-    return out, {n: len(v) for n, v in prof.items() if v}
-
-
 def launches(prepare, backbone="resnet18"):
     """(forward launches, backward launches) by entry-point name of one module step."""
     _, _, batch, m = setup(backbone)
     prepare(m)
     img, bb, af, ctx = [batch[k].to(DEV) for k in ("images", "bboxes", "additional_feats", "context_indices")]
     labels = batch["labels"].to(DEV)
-    logits, fwd = _profiled(lambda: m(img, bb, af, ctx))
+    logits, fwd = profiled(lambda: m(img, bb, af, ctx))
     loss = torch.nn.CrossEntropyLoss(reduction="sum")(logits, labels)
-    _, bwd = _profiled(lambda: loss.backward())
+    _, bwd = profiled(lambda: loss.backward())
     return fwd, bwd
 
 
@@ -264,14 +246,14 @@ def test_agreeing_layer_modes_and_the_full_plan_issue_todays_launches(backbone):
         _, dl, _ = engine.ce_sum(logits, labels)
         return logits, engine.model_bwd(sv, dl, params, plan=plan)
 
-    (l_ref, g_ref), p_ref = _profiled(lambda: step(True, None))
-    (l_got, g_got), p_got = _profiled(lambda: step(all_train, engine.full_plan(params)))
+    (l_ref, g_ref), p_ref = profiled(lambda: step(True, None))
+    (l_got, g_got), p_got = profiled(lambda: step(all_train, engine.full_plan(params)))
     assert p_got == p_ref
     assert torch.equal(l_got, l_ref) and sorted(g_got) == sorted(g_ref)
     for k in g_ref:
         assert torch.equal(g_got[k], g_ref[k]), k
-    (e_ref, _), q_ref = _profiled(lambda: step(False, None, save=False))
-    (e_got, _), q_got = _profiled(lambda: step({p: False for p in all_train}, None, save=False))
+    (e_ref, _), q_ref = profiled(lambda: step(False, None, save=False))
+    (e_got, _), q_got = profiled(lambda: step({p: False for p in all_train}, None, save=False))
     assert q_got == q_ref and torch.equal(e_got, e_ref)
 
 
@@ -306,8 +288,7 @@ def test_trainer_frozen_backbone_follows_the_oracle(request):
     trainable keys only; frozen weights, their Adam moments and the eval-mode buffers stay bitwise as they started, and
     two runs of the same seeds are bit-identical."""
     from cova_web_object_detection_amd.trainer import HotPathTrainer
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=48, bbox_hidden_dim=16,
-               n_additional_feat=0, drop_prob=0.0)
+    cfg = make_cfg((3, 3), 48, 16)
     sd = weights.seeded_state_dict(77, logit_gain=2.0, **{k: v for k, v in cfg.items() if k != "drop_prob"})
     batches = [synthetic.make_batch(2, img_h=96, boxes_per_page=[20 + 3 * i, 11 + 2 * i], context_size=6, seed=900 + i)
                for i in range(3)]

@@ -16,11 +16,11 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from cova_web_object_detection_amd import _lib, engine, synthetic, weights  # noqa: E402
-from helpers import assert_routing_near_ties, compare_grads, routing_from_saved  # noqa: E402
+from helpers import assert_routing_near_ties, compare_grads, DEV, routing_from_saved  # noqa: E402
 from oracle import cova_oracle as O  # noqa: E402
+from config_cases import make_cfg  # noqa: E402
 
 call, query = _lib.call, _lib.query
-DEV = "cuda:0"
 
 
 def rel(a, b):
@@ -167,8 +167,7 @@ def test_bn_pool_full_size_properties():
 
 
 def test_single_page_train_step_full_resolution_matches_oracle():
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=384,
-               bbox_hidden_dim=32, n_additional_feat=0, drop_prob=0.0)
+    cfg = make_cfg((3, 3), 384, 32)
     wcfg = {k: v for k, v in cfg.items() if k != "drop_prob"}
     sd = weights.seeded_state_dict(7, logit_gain=4.0, **wcfg)
     batch = synthetic.make_batch(1, img_h=1280, boxes_per_page=90, context_size=12, seed=7)
@@ -206,8 +205,7 @@ def test_single_page_train_step_full_resolution_extension_matches_self_oracle(kw
     box count / K = 48 on a half-length page (2048x1280; the full 4096-row page is covered by
     tests/test_extension_gpu.py::test_full_size_long_page_train_step_properties), one page, whole train step against
     the self-oracle with every discrete decision forced: fp32 round-off only."""
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=384,
-               bbox_hidden_dim=32, n_additional_feat=0, drop_prob=0.0, **kw)
+    cfg = dict(make_cfg((3, 3), 384, 32), **kw)
     wcfg = {k: v for k, v in cfg.items() if k != "drop_prob"}
     sd = weights.seeded_state_dict(9, logit_gain=4.0, **wcfg)
     batch = synthetic.make_batch(1, img_h=H, img_w=W, boxes_per_page=n, context_size=cs, seed=9)

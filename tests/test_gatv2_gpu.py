@@ -9,8 +9,6 @@ dWh, d_att_w and d_edge_w; d_att_b is analytically ~0 (every softmax row's du su
 The kernel tests feed Wh: the float64 oracle sees the same f32 values, so its gates are the kernel's (an f32 sum of two f32
 numbers never has the wrong sign).  The whole model on the cova_h64_n11 inputs keeps tests/test_model_gpu.py's
 LOGIT_TOL / LOSS_TOL / GRAD_TOL."""
-import functools
-
 import numpy as np
 import pytest
 import torch
@@ -23,118 +21,20 @@ from cova_web_object_detection_amd.features import FeatureCache  # noqa: E402
 from cova_web_object_detection_amd.models import CoVA, GraphAttentionLayer, MultiHeadGraphAttention  # noqa: E402
 from cova_web_object_detection_amd.pipeline import DeviceDataset, attention_rows  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
-from helpers import compare_grads, load_case, routing_from_saved  # noqa: E402
+from helpers import (compare_grads, DEV, framed, GRAD_TOL, GUARD, load_case, LOGIT_TOL,  # noqa: E402
+                     LOSS_TOL, NAN, padded, profiled, relerr, routing_from_saved, SGEMM_TOL, survived)
 from oracle import cova_oracle as O  # noqa: E402
 import edge_oracle as EO  # noqa: E402
 import gatv2_oracle as G2  # noqa: E402
+from config_cases import SPLIT_CFG as CFG  # noqa: E402
+from gat_cases import (check_param_grads, device_gates, DUP_NBR, EDGE_W, gat_case,  # noqa: E402
+                       make_table, oracle64, random_boxes, recorded_heads, SHAPES, ZERO_ROW)
+from trainer_cases import five_steps, page_set, seeded  # noqa: E402
 
-DEV = "cuda:0"
-GUARD = -7.0
-NAN = float("nan")
-LOGIT_TOL, LOSS_TOL, GRAD_TOL = 5e-5, 2e-5, 1e-4          # tests/test_model_gpu.py
-SGEMM_TOL = 2e-5                                          # tests/test_kernels_gpu.py
 NEW = ("cova_gat2_fwd", "cova_gat2_bwd", "cova_gat2_workspace_floats")
-EDGE_W = np.asarray([1.5, -2.0, 0.75, -0.5, 3.0, -1.25, 2.0, 0.6], np.float32)
-ZERO_ROW, DUP_NBR = 7, 9                                  # node 7 names node 9 twice, on channels where z is +0.0 / -0.0
 
 
-def relerr(got, ref, scale=None):
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    return np.abs(got - ref).max() / max(np.abs(ref).max() if scale is None else scale, 1e-6)
-
-
-# ---------------------------------------------------------------- 1. the kernels through the C ABI
-#        N    K    D  pad   (pad: extra floats per row of Wh / h' / g / dWh; odd = unaligned rows = the scalar form)
-SHAPES = {"one": (1, 1, 6, 0),              # a single self-loop; fewer channels than lanes, scalar form
-          "scalar": (37, 24, 6, 3),         # D % 4 != 0
-          "passes": (37, 65, 64, 4),        # K > 64: two lane passes; float4 form, one chunk
-          "unaligned": (37, 24, 64, 1),     # D % 4 == 0 but odd leading dimensions: the scalar form at 64 channels
-          "wide": (130, 24, 384, 8),        # the second 256-channel chunk part-filled; a hub of in-degree 129
-          "general": (130, 100, 96, 4)}     # K = 100, 24 float4 lanes of 64
-
-
-def random_boxes(rs, n, size):
-    """[n, 5] boxes of one page: some overlap, some lie apart (every edge feature takes values off zero)."""
-    wh = rs.uniform(4, 0.25 * size, (n, 2))
-    xy = rs.uniform(0, 1, (n, 2)) * (size - wh)
-    return np.concatenate([np.zeros((n, 1)), xy, xy + wh], 1).astype(np.float32)
-
-
-def make_table(rs, N, K, out_of_range=True):
-    """Arbitrary ids with: an all-pad row (3), a row with one valid slot (4), ids >= N, self-loops, one neighbour named
-    twice in a row, a node nobody names (N - 1) and a hub every other row names (5)."""
-    ctx = rs.randint(-1, N, (N, K)).astype(np.int64)
-    if N == 1:
-        return np.zeros((1, K), np.int64)
-    ctx[::5, 0] = np.arange(N)[::5]                           # self-loops
-    if K >= 4:
-        ctx[:, K - 1] = 5                                     # the hub
-        ctx[ZERO_ROW, 1:3] = DUP_NBR                          # the same neighbour twice
-        if out_of_range:
-            ctx[11, 1], ctx[12, 2] = N, N + 1000
-    ctx[3] = -1
-    ctx[4] = -1
-    ctx[4, K // 2] = 8
-    ctx[ctx == N - 1] = -1                                    # in-degree 0
-    return ctx
-
-
-@functools.lru_cache(maxsize=None)
-def gat_case(name, out_of_range=True):
-    N, K, D, pad = SHAPES[name]
-    rs = np.random.RandomState(sum(map(ord, name)))
-    ctx = make_table(rs, N, K, out_of_range)
-    Wh = rs.standard_normal((N, 2 * D)).astype(np.float32)
-    if N > DUP_NBR and K >= 4:                                # z exactly +0.0 on channels 0, 1 and -0.0 on channel 2
-        Wh[DUP_NBR, D:D + 2] = -Wh[ZERO_ROW, :2]
-        Wh[ZERO_ROW, 2] = Wh[DUP_NBR, D + 2] = -0.0
-    bb = random_boxes(rs, N, 1280.0)
-    aw = (rs.standard_normal(D) / np.sqrt(D)).astype(np.float32)
-    aw[:3] = [0.5, -0.5, 0.5]                                 # the channels of the zero sums weigh in the gradient
-    case = dict(name=name, N=N, K=K, D=D, pad=pad, ctx=ctx, Wh=Wh, phi=EO.edge_features(bb, ctx, 1280.0, 1280.0),
-                aw=aw, ab=rs.standard_normal(1).astype(np.float32), g=rs.standard_normal((N, D)).astype(np.float32))
-    case["ref"] = oracle64(case, None)
-    case["ref_edge"] = oracle64(case, EDGE_W)
-    return case
-
-
-def oracle64(case, edge_w, gate=None, slope=0.2):
-    D = case["D"]
-    f64 = lambda a: torch.from_numpy(np.asarray(a, np.float64))
-    Wh = f64(case["Wh"]).requires_grad_(True)
-    aw, ab = f64(case["aw"]).requires_grad_(True), f64(case["ab"]).requires_grad_(True)
-    ew = None if edge_w is None else f64(edge_w).view(1, 8).requires_grad_(True)
-    hp, attn = G2.attend(Wh[:, :D], Wh[:, D:], torch.from_numpy(case["ctx"]), aw, ab, slope, ew,
-                         None if edge_w is None else f64(case["phi"]), gate)
-    (hp * f64(case["g"])).sum().backward()
-    return dict(hp=hp.detach().numpy(), attn=attn.detach().numpy(), dWh=Wh.grad.numpy(), daw=aw.grad.numpy(),
-                dab=ab.grad.numpy(), dew=None if ew is None else ew.grad.numpy().reshape(-1))
-
-
-def framed(rows, cols, ld):
-    """A GUARD-filled [rows + 2, ld] buffer whose interior [1:rows+1, :cols] is NaN -> (buffer, interior view)."""
-    buf = torch.full((rows + 2, ld), GUARD, dtype=torch.float32, device=DEV)
-    buf[1:rows + 1, :cols] = NAN
-    return buf, buf[1:rows + 1]
-
-
-def padded(a, ld):
-    """The rows of ``a`` at leading dimension ld, the padding NaN: a kernel that reads past a row poisons its output."""
-    buf = torch.full((a.shape[0], ld), NAN, dtype=torch.float32, device=DEV)
-    buf[:, :a.shape[1]] = torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-    return buf
-
-
-def survived(buf, rows, cols):
-    host = buf.cpu().numpy()
-    inner = host[1:rows + 1, :cols]
-    assert np.isfinite(inner).all(), "an output was not written"
-    host = host.copy()
-    host[1:rows + 1, :cols] = GUARD
-    assert (host == GUARD).all(), "a guard row or column was overwritten"
-    return inner
-
-
+# ---------------------------------------------------------------- 1. the kernels through the C ABI (cases: gat_cases.py)
 def launch(case, edge_w=None, slope=0.2):
     """cova_gat2_fwd + cova_gat2_bwd on framed buffers -> dict of host arrays (guards checked)."""
     N, K, D, pad = case["N"], case["K"], case["D"], case["pad"]
@@ -345,38 +245,6 @@ def test_entry_points_refuse_bad_arguments_and_skip_empty_work():
 
 
 # ---------------------------------------------------------------- 2. the modules
-def device_gates(Wh, ctx):
-    """(Wh_i + Wh_j[ctx]) > 0 in float32 from a head's saved Wh [N, 2D]: the kernels' own decisions."""
-    N, D = Wh.shape[0], Wh.shape[1] // 2
-    ok = (ctx >= 0) & (ctx < N)
-    rows = torch.cat((Wh[:, D:], Wh.new_zeros(1, D)))
-    return ((Wh[:, :D].unsqueeze(1) + rows[torch.where(ok, ctx, torch.full_like(ctx, N))]) > 0).cpu()
-
-
-def recorded_heads(monkeypatch):
-    """Every engine.gat_fwd call's saved dict, in call order (layer-major, heads ascending)."""
-    svs, real = [], engine.gat_fwd
-
-    def fn(*a, **kw):
-        sv = real(*a, **kw)
-        svs.append(sv)
-        return sv
-    monkeypatch.setattr(engine, "gat_fwd", fn)
-    return svs
-
-
-def check_param_grads(module, sd):
-    """Every parameter gradient to 1e-4; a v2 ``attention_layer.bias`` shifts all scores of a row alike, so its gradient
-    is analytically zero (round-off in both implementations) and is held on the scale of its head's attention weight."""
-    for key, p in module.named_parameters():
-        ref = sd["gat." + key].grad
-        scale = None
-        if key.endswith("attention_layer.bias"):
-            scale = float(sd["gat." + key[:-len("bias")] + "weight"].grad.abs().max())
-            assert scale > 0
-        assert relerr(p.grad.cpu(), ref, scale) < 1e-4, key
-
-
 def test_v2_layer_under_autograd_matches_the_oracle(monkeypatch):
     rs = np.random.RandomState(13)
     N, Fd, D, K = 131, 24, 8, 9
@@ -522,44 +390,8 @@ def test_v2_model_matches_the_oracle_on_the_reference_inputs(monkeypatch, edge):
 
 
 # ---------------------------------------------------------------- 3. the trainer
-CFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8,
-           n_additional_feat=0, drop_prob=0.2)
 VCFG = dict(CFG, attention="gatv2")
 AW = "gat.attention_layer.weight"
-
-
-def page_set(P=15, img=96, seed=4):
-    rs = np.random.RandomState(seed)
-    u8 = rs.randint(0, 256, (P, img, img, 3)).astype(np.uint8)
-    rows = []
-    for _ in range(P):
-        n = int(rs.randint(11, 40))
-        wh = rs.uniform(6, 40, (n, 2))
-        xy = rs.uniform(0, 1, (n, 2)) * (img - wh)
-        lab = np.zeros((n, 1))
-        lab[rs.permutation(n)[:3], 0] = [1, 2, 3]
-        rows.append(np.concatenate([xy, wh, lab], 1).astype(np.float32))
-    return u8, rows
-
-
-def seeded(cfg):
-    return weights.seeded_state_dict(77, logit_gain=2.0, **{k: v for k, v in cfg.items() if k != "drop_prob"})
-
-
-def five_steps(tr, ds):
-    losses = [tr.train_step(batch)[0] for batch in ds.batches(3, shuffle=True, sampling_fraction=0.9, seed=12, epoch=0)]
-    assert len(losses) == 5 and all(np.isfinite(float(x)) for x in losses)
-    return [float(x) for x in losses], tr.state_dict()
-
-
-def profiled(fn):
-    _lib.PROFILE = {n: [] for n in _lib.lib().fn}
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-    finally:
-        prof, _lib.PROFILE = _lib.PROFILE, None
-    return out, {n: len(v) for n, v in prof.items() if v}
 
 
 @pytest.mark.parametrize("kw", [dict(), dict(optimizer="adamw", max_grad_norm=1.0,

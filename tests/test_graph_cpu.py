@@ -11,14 +11,7 @@ import cova_amd  # noqa: F401
 from cova_web_object_detection_amd import _lib, engine, pipeline, synthetic
 
 import graph_oracle as GO
-
-
-def random_boxes(rs, n, size=300.0):
-    wh = rs.uniform(4, 80, (n, 2))
-    xy = rs.uniform(0, 1, (n, 2)) * (size - wh)
-    b = np.concatenate([xy, wh], 1).astype(np.float32)
-    b[:, 2:] = b[:, :2] + b[:, 2:]                            # float32 adds, as the collation does them
-    return b
+from helpers import random_xyxy as random_boxes
 
 
 def brute_force(boxes, cs, k):

@@ -13,7 +13,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from cova_web_object_detection_amd import _lib, engine, pipeline, weights  # noqa: E402
+from cova_web_object_detection_amd import _lib, engine, pipeline  # noqa: E402
 from cova_web_object_detection_amd.evaluation import evaluate_split, fit  # noqa: E402
 from cova_web_object_detection_amd.features import FeatureCache  # noqa: E402
 from cova_web_object_detection_amd.models import GraphAttentionLayer  # noqa: E402
@@ -22,20 +22,14 @@ from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
 from oracle import cova_oracle as O  # noqa: E402
 import graph_oracle as GO  # noqa: E402
 import sampling_oracle as SO  # noqa: E402
+from config_cases import SPLIT_CFG as CFG  # noqa: E402
+from helpers import DEV, profiled, random_xyxy as random_boxes, relerr  # noqa: E402
+from trainer_cases import page_set, seeded  # noqa: E402
 
-DEV = "cuda:0"
 GUARD = -7
 
 
 # ---------------------------------------------------------------- 1. the kernel against the oracle, through the C ABI
-def random_boxes(rs, n, size=300.0):
-    wh = rs.uniform(4, 80, (n, 2))
-    xy = rs.uniform(0, 1, (n, 2)) * (size - wh)
-    b = np.concatenate([xy, wh], 1).astype(np.float32)
-    b[:, 2:] = b[:, :2] + b[:, 2:]
-    return b
-
-
 def as_batch(pages):
     """list of [n,4] pages -> (bboxes [N,5] = page,x1,y1,x2,y2, page_start [B+1])."""
     ps = np.concatenate([[0], np.cumsum([p.shape[0] for p in pages])]).astype(np.int64)
@@ -143,16 +137,6 @@ def make_rows(rs, n, size=200.0):
     r[:, 2:4] = rs.uniform(2, 60, (n, 2))
     r[rs.permutation(n)[:min(3, n)], 4] = [1, 2, 3][:min(3, n)]
     return r
-
-
-def profiled(fn):
-    _lib.PROFILE = {n: [] for n in _lib.lib().fn}
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-    finally:
-        prof, _lib.PROFILE = _lib.PROFILE, None
-    return out, {n: len(v) for n, v in prof.items() if v}
 
 
 def test_hybrid_table_extends_the_collate_window_without_repeats():
@@ -313,32 +297,9 @@ def test_spatial_k_zero_is_the_path_without_the_argument():
 
 
 # ---------------------------------------------------------------- 5. through the model
-CFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8,
-           n_additional_feat=0, drop_prob=0.2)
-
-
-def page_set(P=15, img=96, seed=4):
-    """The construction of tests/test_sampling_gpu.py's page_set: 11..39 boxes a page, classes 1, 2, 3 once each."""
-    rs = np.random.RandomState(seed)
-    u8 = rs.randint(0, 256, (P, img, img, 3)).astype(np.uint8)
-    rows = []
-    for _ in range(P):
-        n = int(rs.randint(11, 40))
-        wh = rs.uniform(6, 40, (n, 2))
-        xy = rs.uniform(0, 1, (n, 2)) * (img - wh)
-        lab = np.zeros((n, 1))
-        lab[rs.permutation(n)[:3], 0] = [1, 2, 3]
-        rows.append(np.concatenate([xy, wh, lab], 1).astype(np.float32))
-    return u8, rows
-
-
-def seeded():
-    return weights.seeded_state_dict(77, logit_gain=2.0, **{k: v for k, v in CFG.items() if k != "drop_prob"})
-
-
 def test_five_train_steps_on_the_device_graph_equal_steps_on_the_oracle_graph_bit_for_bit():
     u8, rows = page_set()
-    sd = seeded()
+    sd = seeded(CFG)
     cs, k, bs, sf, seed, epoch = 0, 8, 3, 0.9, 12, 0
     ds = DeviceDataset(u8, rows, cs, DEV, spatial_k=k)
     a, b = HotPathTrainer(CFG, sd, DEV), HotPathTrainer(CFG, sd, DEV)
@@ -359,11 +320,6 @@ def test_five_train_steps_on_the_device_graph_equal_steps_on_the_oracle_graph_bi
     for key in sa:
         assert torch.equal(sa[key], sb[key]), key
     assert not torch.equal(sa["convnet.0.weight"], sd["convnet.0.weight"].to(DEV))          # the steps did train
-
-
-def relerr(got, ref):
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    return np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-6)
 
 
 def test_gat_layer_on_the_tie_grid_hub_matches_the_oracle():
@@ -399,7 +355,7 @@ def test_evaluate_split_and_fit_run_on_a_spatial_dataset():
     u8, rows = page_set(P=9, seed=4)
     v8, vrows = page_set(P=11, seed=9)
     train, val = DeviceDataset(u8, rows, 2, DEV, spatial_k=6), DeviceDataset(v8, vrows, 2, DEV, spatial_k=6)
-    tr = HotPathTrainer(CFG, seeded(), DEV, track_metrics=True)             # fit reads the epoch's loss from the metrics
+    tr = HotPathTrainer(CFG, seeded(CFG), DEV, track_metrics=True)             # fit reads the epoch's loss from the metrics
     rep = evaluate_split(tr, val, with_loss=True)
     assert rep.evaluated.all() and rep.ranks.shape == (11, 3) and (rep.ranks >= 0).all() and np.isfinite(rep.loss)
     # the same split, host-fed with the oracle's graph: the same ranks
@@ -417,7 +373,7 @@ def test_evaluate_split_and_fit_run_on_a_spatial_dataset():
 def test_one_feature_cache_serves_two_graphs(monkeypatch):
     u8, rows = page_set(P=6, seed=4)
     ds = DeviceDataset(u8, rows, 12, DEV)
-    tr = HotPathTrainer(CFG, seeded(), DEV, frozen=("convnet.",), bn_eval=("convnet.",))
+    tr = HotPathTrainer(CFG, seeded(CFG), DEV, frozen=("convnet.",), bn_eval=("convnet.",))
     cache = FeatureCache.build(tr, ds)
     cache.check(tr, ds)
     sib = ds.with_context(0, 24)

@@ -24,13 +24,10 @@ from cova_web_object_detection_amd.models import CoVA  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
 from oracle import cova_oracle as O  # noqa: E402
 import head_cases as HC  # noqa: E402
-from helpers import compare_grads, routing_from_saved  # noqa: E402
+from helpers import close, compare_grads, DEV, NAN, GRAD_TOL, LOGIT_TOL, relerr, routing_from_saved  # noqa: E402
 
-DEV = "cuda:0"
-NAN = float("nan")
 F32 = torch.float32
 LOSS_GATE, GRAD_GATE = 1e-5, 1e-5               # tests/test_loss_gpu.py: cova_ce_loss_fwd / _bwd with default options
-LOGIT_TOL, GRAD_TOL = 5e-5, 1e-4                # tests/test_model_gpu.py
 BN_FWD_TOL, BN_GRAD_TOL = 1e-5, 1e-4            # tests/test_kernels_gpu.py::test_batchnorm_train_fwd_bwd
 
 
@@ -52,14 +49,6 @@ def dev_in(t, ld=None, off=0):
 def dev_out(R, C, ld=None, off=0, dtype=F32):
     """(flat, view): output buffer pre-filled with the canary"""
     return HC.place((R, C, dtype), C if ld is None else ld, off, HC.CANARY, device=DEV)
-
-
-def close(got, ref, tol, name):
-    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
-    assert got.shape == ref.shape, (name, got.shape, ref.shape)
-    err = (got - ref).abs().max().item() / max(ref.abs().max().item(), 1e-6)
-    print("%s: max|err|/max|ref| = %.3e (gate %.1e)" % (name, err, tol))
-    assert err <= tol, "%s: max|err|/max|ref| = %.3e > %.1e" % (name, err, tol)
 
 
 def within_bound(got, ref, mag, L, name):
@@ -421,11 +410,6 @@ def build_model(cfg, sd):
     missing = m.load_state_dict(sd, strict=True)
     assert not missing.missing_keys and not missing.unexpected_keys
     return m.to(DEV)
-
-
-def relerr(got, ref):
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    return np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-6)
 
 
 @pytest.mark.parametrize("boxes", [[3, 4], [230]], ids=str)

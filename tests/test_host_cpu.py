@@ -9,6 +9,7 @@ import torch
 
 from cova_web_object_detection_amd import _lib, synthetic, weights
 from cova_web_object_detection_amd.models import CoVA, GraphAttentionLayer
+from config_cases import make_cfg
 
 
 def test_library_exports_every_declared_symbol():
@@ -159,8 +160,7 @@ def test_trainer_checkpoint_round_trip_on_cpu_buffers():
     """HotPathTrainer's flat buckets are device agnostic: the save-best / reload-best cycle of train.py:84,94 and an
     optimizer-state round trip can be checked without a GPU (no device work is launched)."""
     from cova_web_object_detection_amd.trainer import HotPathTrainer
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8,
-               n_additional_feat=0, drop_prob=0.2)
+    cfg = make_cfg((3, 3), 32, 8, drop_prob=0.2)
     wcfg = {k: v for k, v in cfg.items() if k != "drop_prob"}
     sd_a, sd_b = weights.seeded_state_dict(1, **wcfg), weights.seeded_state_dict(2, **wcfg)
     tr = HotPathTrainer(cfg, sd_a, "cpu")
@@ -183,8 +183,7 @@ def test_flat_bucket_layout_of_the_extension_model():
     """One flat parameter / gradient bucket also for the resnet50 + multi-head spec: every parameter has a 16-byte
     aligned view, conv-stack tensors come first (the two-phase all-reduce splits there), buffers stay outside."""
     from cova_web_object_detection_amd.trainer import HotPathTrainer, is_param_key
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=64, bbox_hidden_dim=8,
-               n_additional_feat=0, drop_prob=0.2, backbone="resnet50", n_heads=2, n_gat_layers=2)
+    cfg = dict(make_cfg((3, 3), 64, 8, drop_prob=0.2), backbone="resnet50", n_heads=2, n_gat_layers=2)
     sd = weights.seeded_state_dict(1, **{k: v for k, v in cfg.items() if k != "drop_prob"})
     tr = HotPathTrainer(cfg, sd, "cpu")
     pkeys = [k for k in sd if is_param_key(k)]
@@ -221,8 +220,7 @@ def test_launch_device_resolution_rejects_cpu_and_mixed_arguments():
 def test_check_batch_host_contract():
     """engine.check_batch is pure host logic: the shape errors of the reference's forward, no device read."""
     from cova_web_object_detection_amd import engine
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=384, bbox_hidden_dim=32,
-               n_additional_feat=0, drop_prob=0.2)
+    cfg = make_cfg((3, 3), 384, 32, drop_prob=0.2)
     img, bb, af = torch.zeros(2, 3, 8, 8), torch.zeros(6, 5), torch.zeros(6, 0)
     ctx = torch.zeros(6, 4, dtype=torch.long)
     engine.check_batch(cfg, img, bb, af, ctx, True)
@@ -288,3 +286,14 @@ def test_option_changes_opt_in_keeps_the_state_mutable():
     assert r["set"] == 0 and r["to0"] == 0 and r["to1"] == 0
     assert r["n1"] == r["n0"] == 8
     assert r["big1"] == 2 * r["big0"] > 0
+
+
+def test_no_test_module_imports_a_test_module():
+    """What more than one test module uses lives in a support module (helpers.py, *_cases.py, *_oracle.py)."""
+    import glob
+    import re
+    here = os.path.dirname(os.path.abspath(__file__))
+    found = ["%s:%d: %s" % (os.path.basename(path), n, line.strip())
+             for path in sorted(glob.glob(os.path.join(here, "*.py")))
+             for n, line in enumerate(open(path), 1) if re.match(r"\s*(from|import)\s+test_", line)]
+    assert not found, "\n".join(found)

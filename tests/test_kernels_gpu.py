@@ -14,18 +14,9 @@ pytestmark = pytest.mark.gpu
 
 from cova_web_object_detection_amd import _lib, engine, synthetic  # noqa: E402
 from oracle import cova_oracle as O  # noqa: E402
+from helpers import close, DEV  # noqa: E402
 
 call, query = _lib.call, _lib.query
-DEV = "cuda:0"
-
-
-def close(got, ref, tol=1e-4, name=""):
-    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
-    assert got.shape == ref.shape, (name, got.shape, ref.shape)
-    scale = max(ref.abs().max().item(), 1e-6)
-    err = (got - ref).abs().max().item() / scale
-    assert err <= tol, "%s: max|err|/max|ref| = %.3e > %.1e" % (name, err, tol)
-    return err
 
 
 def nhwc(x):   # NCHW cpu -> NHWC gpu

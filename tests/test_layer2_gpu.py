@@ -16,13 +16,13 @@ pytestmark = pytest.mark.gpu
 from cova_web_object_detection_amd import _lib, engine, synthetic, weights  # noqa: E402
 from cova_web_object_detection_amd.models import CoVA  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
-from helpers import compare_grads, routing_from_saved  # noqa: E402
+from helpers import compare_grads, DEV, GRAD_TOL, profiled, routing_from_saved  # noqa: E402
 from oracle import cova_oracle as O  # noqa: E402
 import layer2_oracle as L2O  # noqa: E402
+from config_cases import make_cfg, TRAINER_CFG  # noqa: E402
 
-DEV = "cuda:0"
 call, query = _lib.call, _lib.query
-LOGIT_TOL, GRAD_TOL = 1e-4, 1e-4
+L2_LOGIT_TOL = 1e-4                                     # this suite's own bound on the logits
 SHAPES = [(3, 64, 2, 1), (3, 128, 1, 1), (1, 64, 2, 0)]          # (k, Ci, stride, pad); Co = 128
 
 
@@ -151,8 +151,7 @@ def test_stride2_dgrad_joins_the_downsample(B, H, W):
 
 # ----------------------------------------------------------------------------------------------------- module level
 def setup(img_h=64, roi_op="pool", seed=11, boxes=(13, 7), img_w=None):
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=48, bbox_hidden_dim=16,
-               n_additional_feat=0, drop_prob=0.0)
+    cfg = make_cfg((3, 3), 48, 16)
     sd = weights.seeded_state_dict(seed, logit_gain=2.0, backbone_layers=2,
                                    **{k: v for k, v in cfg.items() if k != "drop_prob"})
     batch = synthetic.make_batch(len(boxes), img_h=img_h, img_w=img_w, boxes_per_page=list(boxes), context_size=3,
@@ -195,7 +194,7 @@ def module_case(monkeypatch, img_h, roi_op="pool", train=True, prepare=None, wan
     loss_ref, logits_ref, grads_ref, after, _ = O.loss_and_grads(
         sd, images, batch["bboxes"], batch["additional_feats"], batch["context_indices"], batch["labels"], cfg, None,
         routing, training=train)
-    assert rel(logits.detach().cpu(), logits_ref.double()) < LOGIT_TOL
+    assert rel(logits.detach().cpu(), logits_ref.double()) < L2_LOGIT_TOL
     trainable = {k for k, p in m.named_parameters() if p.requires_grad}
     for k, p in m.named_parameters():
         assert (p.grad is None) == (k not in trainable), k
@@ -264,7 +263,7 @@ def test_module_state_dict_round_trip_and_no_grad(monkeypatch):
     assert torch.equal(a, b)
     ref = O.forward(O.clone_state_dict(sd), batch["images"], batch["bboxes"], batch["additional_feats"],
                     batch["context_indices"], cfg, False)
-    assert rel(a.cpu(), ref.double()) < LOGIT_TOL
+    assert rel(a.cpu(), ref.double()) < L2_LOGIT_TOL
     vis = m._get_visual_features(args[0], args[1])
     assert vis.shape == (args[1].shape[0], 128 * 9)
 
@@ -280,8 +279,7 @@ def test_multihead_gat(monkeypatch):
 
 
 # ----------------------------------------------------------------------------------------------------- trainer
-TCFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=48, bbox_hidden_dim=16,
-            n_additional_feat=0, drop_prob=0.0, backbone_layers=2)
+TCFG = dict(TRAINER_CFG, backbone_layers=2)
 
 
 def trainer_run(steps=3, frozen=()):
@@ -315,16 +313,6 @@ def test_trainer_adam_trajectory_and_reruns():
     assert topk.shape == (2, 4, 1)
 
 
-def _profiled(fn):
-    _lib.PROFILE = {n: [] for n in _lib.lib().fn}
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-    finally:
-        prof, _lib.PROFILE = _lib.PROFILE, None
-    return out, {n: len(v) for n, v in prof.items() if v}
-
-
 def test_finetune_stem_and_layer1_frozen_launches():
     cfg, sd, batch, m = setup(64)
     m.train()
@@ -334,7 +322,7 @@ def test_finetune_stem_and_layer1_frozen_launches():
     args = [batch[k].to(DEV) for k in ("images", "bboxes", "additional_feats", "context_indices")]
     logits = m(*args)
     loss = torch.nn.CrossEntropyLoss(reduction="sum")(logits, batch["labels"].to(DEV))
-    _, bwd = _profiled(lambda: loss.backward())
+    _, bwd = profiled(lambda: loss.backward())
     assert bwd.get("cova_conv_nhwc_wgrad") == 5
     assert bwd.get("cova_conv_nhwc_dgrad") == 3                   # the three stride-1 ones; not block 0's stride-2 one
     assert not [n for n in bwd if n.startswith(("cova_conv1", "cova_conv3x3", "cova_pool_bwd", "cova_bn_relu_maxpool"))]
@@ -344,7 +332,7 @@ def test_finetune_stem_and_layer1_frozen_launches():
     cfg, sd, batch, m = setup(64)
     logits = m.train()(*args)
     loss = torch.nn.CrossEntropyLoss(reduction="sum")(logits, batch["labels"].to(DEV))
-    _, bwd = _profiled(lambda: loss.backward())
+    _, bwd = profiled(lambda: loss.backward())
     assert bwd.get("cova_conv_nhwc_dgrad") == 4
     assert bwd.get("cova_conv1_wgrad_poolbwd", 0) + bwd.get("cova_conv1_wgrad", 0) == 1
 

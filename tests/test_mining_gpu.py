@@ -17,11 +17,12 @@ from cova_web_object_detection_amd import _lib, engine  # noqa: E402
 from cova_web_object_detection_amd.models import CrossEntropyLoss  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
 import mining_oracle as MO  # noqa: E402
-from test_optim_gpu import CFG, _profiled, dev_batch, trainer_setup  # noqa: E402
+from config_cases import TRAINER_CFG as CFG  # noqa: E402
+from helpers import DEV, profiled  # noqa: E402
+from trainer_cases import dev_batch, trainer_setup  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 EPS32 = float(np.finfo(np.float32).eps)
 SELECT = "cova_hard_negative_select"
 PAIR = ("cova_ce_loss_fwd", "cova_ce_loss_bwd")
@@ -219,13 +220,13 @@ def test_trainer_launches():
     sd, batches = trainer_setup()
     tr = HotPathTrainer(CFG, sd, DEV, hard_negative_ratio=3, hard_negative_min=2)
     for b in (paged(batches[0], page_counts(0)), dev_batch(batches[1])):
-        prof = _profiled(lambda: tr.forward_backward(b))
+        prof = profiled(lambda: tr.forward_backward(b))[1]
         assert prof.get(SELECT) == 1 and [prof.get(n) for n in PAIR] == [1, 1] and "cova_ce_sum" not in prof, prof
     ref = HotPathTrainer(CFG, sd, DEV)
-    prof = _profiled(lambda: ref.forward_backward(dev_batch(batches[0])))
+    prof = profiled(lambda: ref.forward_backward(dev_batch(batches[0])))[1]
     assert prof.get("cova_ce_sum") == 1 and SELECT not in prof and not any(n in prof for n in PAIR), prof
     # mining is the only difference between the two profiles
-    mined = _profiled(lambda: tr.forward_backward(dev_batch(batches[0])))
+    mined = profiled(lambda: tr.forward_backward(dev_batch(batches[0])))[1]
     for name in (SELECT,) + PAIR:
         mined.pop(name)
     prof.pop("cova_ce_sum")

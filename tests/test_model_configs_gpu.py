@@ -25,22 +25,13 @@ pytestmark = pytest.mark.gpu
 from cova_web_object_detection_amd import engine, synthetic, weights  # noqa: E402
 from cova_web_object_detection_amd.models import CoVA  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
-from helpers import assert_routing_near_ties, compare_grads, load_case, routing_from_saved  # noqa: E402
+from helpers import (assert_routing_near_ties, compare_grads, DEV, GRAD_TOL,  # noqa: E402
+                     load_case, LOGIT_TOL, LOSS_TOL, relerr, routing_from_saved)
 from oracle import cova_oracle as O  # noqa: E402
+from config_cases import make_cfg, ORACLE_CASES  # noqa: E402
+from trainer_cases import seeded  # noqa: E402
 
-LOGIT_TOL, LOSS_TOL, GRAD_TOL = 5e-5, 2e-5, 1e-4          # tests/test_model_gpu.py
-DEV = "cuda:0"
 KEYS = ("images", "bboxes", "additional_feats", "context_indices")
-
-
-def relerr(got, ref):
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    return np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-6)
-
-
-def make_cfg(roi, hidden, bbox_hidden, use_context=True, addl=0, drop_prob=0.0):
-    return dict(roi_output_size=roi, n_classes=4, use_context=use_context, hidden_dim=hidden,
-                bbox_hidden_dim=bbox_hidden, n_additional_feat=addl, drop_prob=drop_prob)
 
 
 def build(cfg, img_h, sd, **kw):
@@ -51,17 +42,6 @@ def build(cfg, img_h, sd, **kw):
     return m.to(DEV)
 
 
-def seeded(cfg, seed, gain=2.0):
-    return weights.seeded_state_dict(seed, logit_gain=gain, **{k: v for k, v in cfg.items() if k != "drop_prob"})
-
-
-# ------------------------------------------------------------------------------ configurations held to the oracle only
-#          roi     img_h  boxes        cs  hidden  bbox_hidden  seed
-ORACLE_CASES = {
-    "roi7_T3232": ((7, 7), 96, [33, 20], 12, 64, 32, 211),     # T = 3136 + 32 + 64: the widest ResNet-18 head
-    "roi1_ctx": ((1, 1), 64, [14, 9], 2, 64, 16, 212),         # F = 80, T = 144
-    "roi4_h384": ((4, 4), 128, [11, 40, 3], 12, 384, 32, 213),  # n_vis = 1024, T = 1440, three pages
-}
 
 
 def oracle_case(roi, img_h, boxes, cs, hidden, bbox_hidden, seed, train, roi_op="pool", logit_tol=LOGIT_TOL,

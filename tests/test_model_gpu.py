@@ -26,10 +26,9 @@ from cova_web_object_detection_amd.models import CoVA, GraphAttentionLayer  # no
 from helpers import (FULL_CASES, GOLDEN, assert_gate_flips_near_zero, assert_routing_near_ties,  # noqa: E402
                      check_grads, compare_grads, load_case, margins_ok, routing_from_saved, unforced_fraction_above)
 
-LOGIT_TOL, LOSS_TOL, GRAD_TOL = 5e-5, 2e-5, 1e-4
 from oracle import cova_oracle as O  # noqa: E402
-
-DEV = "cuda:0"
+from config_cases import make_cfg  # noqa: E402
+from helpers import DEV, GRAD_TOL, LOGIT_TOL, LOSS_TOL, relerr  # noqa: E402
 
 
 def build(cfg, img_h, sd):
@@ -40,13 +39,8 @@ def build(cfg, img_h, sd):
     return m.to(DEV)
 
 
-def dev_batch(batch):
+def dev_args(batch):
     return [batch[k].to(DEV) for k in ("images", "bboxes", "additional_feats", "context_indices")]
-
-
-def relerr(got, ref):
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    return np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-6)
 
 
 @pytest.mark.parametrize("fixture", ["gat_layer", "gat_layer_k100"])     # K = 6; K = 100: two 64-lane passes per node
@@ -75,7 +69,7 @@ def test_gat_layer_matches_reference_fixture(fixture):
 def test_full_model_matches_reference_fixture(name):
     fx, cfg, sd, batch = load_case(name)
     img_h = int(fx["meta/img_h"])
-    args = dev_batch(batch)
+    args = dev_args(batch)
     # ---- eval mode: logits, attention, decisions
     m = build(cfg, img_h, sd)
     m.eval()
@@ -189,8 +183,7 @@ def test_full_model_matches_reference_fixture(name):
 def test_fused_loss_and_engine_step_match_oracle():
     """engine.model_fwd + ce_sum + model_bwd (the bench path) against the CPU oracle, with
     injected dropout keep-masks (train-mode parity needs a shared mask: SURVEY 8a row D)."""
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=96,
-               bbox_hidden_dim=32, n_additional_feat=0, drop_prob=0.2)
+    cfg = make_cfg((3, 3), 96, 32, drop_prob=0.2)
     wcfg = {k: v for k, v in cfg.items() if k != "drop_prob"}
     sd = weights.seeded_state_dict(77, logit_gain=4.0, **wcfg)
     batch = synthetic.make_batch(2, img_h=96, boxes_per_page=[30, 17], context_size=12, seed=77)
@@ -199,7 +192,7 @@ def test_fused_loss_and_engine_step_match_oracle():
     masks = [torch.from_numpy((rs.uniform(size=(N, T)) > 0.2).astype(np.uint8)) for _ in range(2)]
     params = {k: v.to(DEV) for k, v in sd.items() if k in O.param_keys(sd)}
     buffers = {k: v.to(DEV) for k, v in sd.items() if k not in params}
-    images, bboxes, addl, ctx = dev_batch(batch)
+    images, bboxes, addl, ctx = dev_args(batch)
     logits, sv = engine.model_fwd(cfg, params, buffers, images, bboxes, addl, ctx, True,
                                   masks=[m.to(DEV) for m in masks])
     loss, dl, pred = engine.ce_sum(logits, batch["labels"].to(DEV))
@@ -227,7 +220,7 @@ def test_module_surface_and_no_cpu_fallback():
         m(batch["images"], batch["bboxes"], batch["additional_feats"], batch["context_indices"])
     m = m.to(DEV)
     m.train()
-    args = dev_batch(batch)
+    args = dev_args(batch)
     m.seed_dropout(5)
     a = m(*args)
     m.seed_dropout(5)
@@ -247,12 +240,11 @@ def test_reference_style_train_loop_matches_fused_trainer_and_oracle():
     torch.optim.Adam(lr 5e-4, weight_decay 1e-3) as in main.py:133-139) driving the drop-in module,
     against (a) HotPathTrainer (fused CE + flat-buffer Adam kernel) and (b) the CPU oracle."""
     from cova_web_object_detection_amd.trainer import HotPathTrainer
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=64,
-               bbox_hidden_dim=16, n_additional_feat=0, drop_prob=0.0)
+    cfg = make_cfg((3, 3), 64, 16)
     wcfg = {k: v for k, v in cfg.items() if k != "drop_prob"}
     sd = weights.seeded_state_dict(31, logit_gain=2.0, **wcfg)
     batch = synthetic.make_batch(2, img_h=64, boxes_per_page=[25, 14], context_size=12, seed=31)
-    args = dev_batch(batch)
+    args = dev_args(batch)
     labels = batch["labels"].to(DEV)
     # (1) reference-style loop on the nn.Module
     m = build(cfg, 64, sd)
@@ -303,8 +295,7 @@ def test_training_trajectory_follows_the_cpu_oracle(request):
     rows and the per-page / per-class top-1 box of train.py:144-153.  The curve goes to profiles/ when COVA_WRITE_CURVE
     names a file."""
     from cova_web_object_detection_amd.trainer import HotPathTrainer
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=96,
-               bbox_hidden_dim=16, n_additional_feat=0, drop_prob=0.2)
+    cfg = make_cfg((3, 3), 96, 16, drop_prob=0.2)
     wcfg = {k: v for k, v in cfg.items() if k != "drop_prob"}
     sd = weights.seeded_state_dict(77, logit_gain=2.0, **wcfg)
     batches = [synthetic.make_batch(2, img_h=96, boxes_per_page=[30 + 3 * i, 21 + 2 * i], context_size=12, seed=700 + i)
@@ -425,8 +416,7 @@ def test_eval_decision_kernel_matches_reference_rule():
 
 def test_trainer_evaluate_matches_oracle_decision_rule():
     from cova_web_object_detection_amd.trainer import HotPathTrainer
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=64,
-               bbox_hidden_dim=16, n_additional_feat=0, drop_prob=0.2)
+    cfg = make_cfg((3, 3), 64, 16, drop_prob=0.2)
     wcfg = {k: v for k, v in cfg.items() if k != "drop_prob"}
     sd = weights.seeded_state_dict(41, logit_gain=3.0, **wcfg)
     counts = [25, 11, 40]
@@ -490,15 +480,14 @@ def test_gat_extreme_neighbour_counts(K):
 
 @pytest.mark.parametrize("use_context,boxes", [(False, [7, 30]), (True, [3, 4]), (True, [230])])
 def test_small_and_ragged_batches_match_oracle_forward(use_context, boxes):
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=use_context, hidden_dim=48,
-               bbox_hidden_dim=16, n_additional_feat=0, drop_prob=0.0)
+    cfg = make_cfg((3, 3), 48, 16, use_context=use_context)
     wcfg = {k: v for k, v in cfg.items() if k != "drop_prob"}
     sd = weights.seeded_state_dict(len(boxes) * 13 + boxes[0], logit_gain=2.0, **wcfg)
     batch = synthetic.make_batch(len(boxes), img_h=64, boxes_per_page=boxes, context_size=12, seed=boxes[0])
     if not use_context:
         batch["context_indices"] = torch.empty((0, 0), dtype=torch.long)
     m = build(cfg, 64, sd)
-    args = dev_batch(batch)
+    args = dev_args(batch)
     for training in (False, True):
         m.train(training)
         with torch.no_grad():
@@ -589,8 +578,7 @@ def test_prefetcher_overlapped_upload_matches_direct_collate():
             rows.append(np.concatenate([xy, wh, lab], 1).astype(np.float32))
         items.append((u8, rows))
     direct = [DeviceCollate(4, DEV)(*it) for it in items]
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8,
-               n_additional_feat=0, drop_prob=0.0)
+    cfg = make_cfg((3, 3), 32, 8)
     tr = HotPathTrainer(cfg, weights.seeded_state_dict(3, **{k: v for k, v in cfg.items() if k != "drop_prob"}), DEV)
     n = 0
     for got, ref in zip(Prefetcher(DeviceCollate(4, DEV, pin=True), items), direct):
@@ -611,8 +599,7 @@ def test_overlapped_gradient_exchange_path_on_rccl():
     import socket
     import torch.distributed as dist
     from cova_web_object_detection_amd.trainer import HotPathTrainer
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=64, bbox_hidden_dim=16,
-               n_additional_feat=0, drop_prob=0.2)
+    cfg = make_cfg((3, 3), 64, 16, drop_prob=0.2)
     wcfg = {k: v for k, v in cfg.items() if k != "drop_prob"}
     sd = weights.seeded_state_dict(17, **wcfg)
     batch = synthetic.make_batch(3, img_h=128, boxes_per_page=[20, 33, 9], context_size=6, seed=17)
@@ -646,8 +633,7 @@ def test_train_steps_are_bit_reproducible(kw):
     """No float atomics in the step: two trainers fed the same batches end with bit-identical gradients,
     parameters, Adam moments and running statistics (RoIPool / GAT backward gather in a fixed order)."""
     from cova_web_object_detection_amd.trainer import HotPathTrainer
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=64, bbox_hidden_dim=16,
-               n_additional_feat=0, drop_prob=0.2, **kw)
+    cfg = dict(make_cfg((3, 3), 64, 16, drop_prob=0.2), **kw)
     sd = weights.seeded_state_dict(19, **{k: v for k, v in cfg.items() if k != "drop_prob"})
     batches = [synthetic.make_batch(3, img_h=96, img_w=160, boxes_per_page=[70, 33, 90], context_size=12, seed=s)
                for s in (1, 2)]
@@ -674,12 +660,11 @@ def test_malformed_input_raises_like_the_reference_forward():
     CPU: ValueError from BatchNorm1d's train-mode batch-size check, RuntimeError from conv2d / cat / view,
     IndexError for a float index tensor, RuntimeError for a second backward); the HIP path takes raw
     pointers, so the same conditions are caught on the host with the same exception types."""
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=48, bbox_hidden_dim=16,
-               n_additional_feat=0, drop_prob=0.0)
+    cfg = make_cfg((3, 3), 48, 16)
     sd = weights.seeded_state_dict(3, logit_gain=2.0, **{k: v for k, v in cfg.items() if k != "drop_prob"})
     batch = synthetic.make_batch(2, img_h=64, boxes_per_page=12, context_size=2, seed=4)
     m = build(cfg, 64, sd)
-    img, bb, af, ctx = dev_batch(batch)
+    img, bb, af, ctx = dev_args(batch)
     m.train()
     one = (img, bb[:1], af[:1], torch.full((1, 4), -1, dtype=torch.long, device=DEV))
     with pytest.raises(ValueError, match="more than 1 value per channel"):
@@ -710,12 +695,11 @@ def test_input_layout_and_index_dtype_do_not_change_the_result():
     """Strided / channels_last pages and int32 neighbour ids (both accepted by the reference's torch ops)
     give the bits of the contiguous int64 call; ids outside [0, N) act as pads (memory-safe; the reference
     raises IndexError for them on CPU, a device-side assert on a GPU); a page without boxes is legal."""
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=48, bbox_hidden_dim=16,
-               n_additional_feat=0, drop_prob=0.0)
+    cfg = make_cfg((3, 3), 48, 16)
     sd = weights.seeded_state_dict(5, logit_gain=2.0, **{k: v for k, v in cfg.items() if k != "drop_prob"})
     batch = synthetic.make_batch(2, img_h=64, boxes_per_page=12, context_size=2, seed=6)
     m = build(cfg, 64, sd).eval()
-    img, bb, af, ctx = dev_batch(batch)
+    img, bb, af, ctx = dev_args(batch)
     with torch.no_grad():
         base = m(img, bb, af, ctx)
         assert torch.equal(m(img.to(memory_format=torch.channels_last), bb, af, ctx), base)
@@ -744,11 +728,10 @@ def test_gradient_with_respect_to_the_images(training):
     module returns it too -- cova_pool_bwd_dy1 + cova_conv1_dgrad behind the conv stack's backward -- and the parameter
     gradients of that backward are the ones of a call without it.  Against the CPU oracle forced to the HIP forward's
     discrete decisions; also through _get_visual_features."""
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=48, bbox_hidden_dim=16,
-               n_additional_feat=0, drop_prob=0.0)
+    cfg = make_cfg((3, 3), 48, 16)
     sd = weights.seeded_state_dict(5, logit_gain=2.0, **{k: v for k, v in cfg.items() if k != "drop_prob"})
     batch = synthetic.make_batch(2, img_h=96, boxes_per_page=[14, 9], context_size=3, seed=6)
-    img, bb, af, ctx = dev_batch(batch)
+    img, bb, af, ctx = dev_args(batch)
     m = build(cfg, 96, sd)
     m.train(training)
     x = img.clone().requires_grad_(True)
@@ -799,12 +782,11 @@ def test_no_kernel_reads_memory_nobody_wrote_and_steps_do_not_depend_on_the_allo
     proxy.empty = lambda *a, **k: poisoned(real_empty(*a, **k))
     proxy.empty_like = lambda *a, **k: poisoned(real_empty_like(*a, **k))
     monkeypatch.setattr(engine, "torch", proxy)
-    cfg = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=48, bbox_hidden_dim=16,
-               n_additional_feat=0, drop_prob=0.2)
+    cfg = make_cfg((3, 3), 48, 16, drop_prob=0.2)
     sd = weights.seeded_state_dict(5, logit_gain=2.0, **{k: v for k, v in cfg.items() if k != "drop_prob"})
     batch = synthetic.make_batch(2, img_h=96, boxes_per_page=[14, 9], context_size=3, seed=6)
     keys = O.param_keys(sd)
-    args = dev_batch(batch)
+    args = dev_args(batch)
     labels = batch["labels"].to(DEV)
     runs = []
     for rep in range(3):

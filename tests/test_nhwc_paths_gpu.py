@@ -22,9 +22,8 @@ pytestmark = pytest.mark.gpu
 from cova_web_object_detection_amd import _lib  # noqa: E402
 import head_cases as HC  # noqa: E402
 import nhwc_cases as NC  # noqa: E402
+from helpers import DEV, NAN  # noqa: E402
 
-DEV = "cuda:0"
-NAN = float("nan")
 F32 = torch.float32
 GUARD = 64                                      # floats in front of and behind every tensor (keeps 16-byte alignment)
 call, query = _lib.call, _lib.query

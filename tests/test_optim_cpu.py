@@ -8,9 +8,8 @@ import torch
 import cova_amd  # noqa: F401
 from cova_web_object_detection_amd import _lib, weights
 from cova_web_object_detection_amd.trainer import HotPathTrainer, group_runs
+from config_cases import BASE as CFG
 
-CFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8,
-           n_additional_feat=0, drop_prob=0.0)
 SD = weights.seeded_state_dict(3, **{k: v for k, v in CFG.items() if k != "drop_prob"})
 
 

@@ -6,21 +6,21 @@ of a default step."""
 import functools
 import math
 
-import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-from cova_web_object_detection_amd import _lib, engine, synthetic, weights  # noqa: E402
+from cova_web_object_detection_amd import _lib, engine  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
 from oracle import cova_oracle as O  # noqa: E402
 import optim_oracle as OO  # noqa: E402
-from helpers import HARD_RAGGED, N_BACKING, N_RAGGED as N_HARD, on_device, ragged_inside, seg_table  # noqa: E402
+from helpers import (bits, DEV, HARD_RAGGED, LOSS_TOL, N_BACKING,  # noqa: E402
+                     N_RAGGED as N_HARD, on_device, profiled, ragged_inside, seg_table)
+from config_cases import TRAINER_CFG as CFG  # noqa: E402
+from trainer_cases import dev_batch, no_decay, trainer_setup  # noqa: E402
 
-DEV = "cuda:0"
 F32_EPS = torch.finfo(torch.float32).eps
-LOSS_TOL = 2e-5
 # ragged rows (lo, hi, group) of a 13 300-element buffer: sizes 1, 3, 4097, 4, 9000, 1 with gaps between them
 RAGGED = [(0, 1, 0), (2, 5, 1), (8, 8 + 4097, 0), (4112, 4116, 1), (4120, 13120, 1), (13200, 13201, 0)]
 N_RAGGED = 13300
@@ -175,11 +175,6 @@ HARD_GROUPS = {"adam": [dict(lr=5e-4, weight_decay=1e-3, betas=(0.9, 0.999), eps
                        dict(lr=0.05, momentum=0.8, nesterov=True, weight_decay=0.0)]}
 
 
-def bits(t):
-    t = t.detach().cpu() if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t))
-    return t.contiguous().view(torch.int32)
-
-
 @functools.lru_cache(maxsize=None)
 def hard_inputs():
     """p, two gradients, m and v (>= 0) of N_BACKING floats: random inside the valid rows, the sentinel elsewhere."""
@@ -271,41 +266,16 @@ def test_grad_norm_over_the_hard_table_skips_poison_and_ignores_the_alignment():
 
 
 # ---------------------------------------------------------------------------------------------- the trainer
-CFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=48, bbox_hidden_dim=16,
-           n_additional_feat=0, drop_prob=0.0)
-
-
-def trainer_setup(seed=77):
-    sd = weights.seeded_state_dict(seed, logit_gain=2.0, **{k: v for k, v in CFG.items() if k != "drop_prob"})
-    batches = [synthetic.make_batch(2, img_h=96, boxes_per_page=[20 + 3 * i, 11 + 2 * i], context_size=6, seed=900 + i)
-               for i in range(3)]
-    return sd, batches
-
-
-def dev_batch(b):
-    return {k: v.to(DEV) for k, v in b.items() if torch.is_tensor(v)}
-
-
-def _profiled(fn):
-    _lib.PROFILE = {n: [] for n in _lib.lib().fn}
-    try:
-        fn()
-        torch.cuda.synchronize()
-    finally:
-        prof, _lib.PROFILE = _lib.PROFILE, None
-    return {n: len(v) for n, v in prof.items() if v}
-
-
 def test_default_step_issues_only_cova_adam_step():
     sd, batches = trainer_setup()
     for kw, launches in ((dict(), 1), (dict(frozen=("convnet.0.", "convnet.1.")), None)):
         tr = HotPathTrainer(CFG, sd, DEV, **kw)
         tr.forward_backward(dev_batch(batches[0]))
-        prof = _profiled(tr.optimizer_step)
+        prof = profiled(tr.optimizer_step)[1]
         assert prof == {"cova_adam_step": launches or len(tr._adam_runs)}, prof
     tr = HotPathTrainer(CFG, sd, DEV, optimizer="adamw", max_grad_norm=1.0)
     tr.forward_backward(dev_batch(batches[0]))
-    assert _profiled(tr.optimizer_step) == {"cova_grad_norm": 1, "cova_optim_step": 1}
+    assert profiled(tr.optimizer_step)[1] == {"cova_grad_norm": 1, "cova_optim_step": 1}
 
 
 def test_fused_adam_of_one_group_follows_todays_step_bit_for_bit():
@@ -332,10 +302,6 @@ def test_clipped_optimizer_step_makes_no_host_synchronisation():
         finally:
             torch.cuda.set_sync_debug_mode(0)
     assert tr.last_grad_norm.dim() == 0 and tr.last_grad_norm.is_cuda and float(tr.last_grad_norm) > 0
-
-
-def no_decay(k):
-    return k.endswith(".bias") or ".bn" in k
 
 
 @pytest.mark.parametrize("frozen", [(), ("convnet.0.", "convnet.1.")])

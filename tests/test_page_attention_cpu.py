@@ -12,6 +12,7 @@ from cova_web_object_detection_amd import weights
 from cova_web_object_detection_amd.models import CoVA, PageAttention
 from cova_web_object_detection_amd.trainer import HotPathTrainer
 import page_attn_oracle as PA
+from config_cases import PAGE_SPEC as BASE
 
 KEY = "page_attention.qkv.weight"
 RKEYS = ["page_readout.W.weight", "page_readout.attention_layer.weight", "page_readout.attention_layer.bias"]
@@ -115,9 +116,6 @@ def test_a_constant_added_to_every_K_row_of_a_page_leaves_A_unchanged():
 
 
 # ---------------------------------------------------------------- spec and module keys
-BASE = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8, n_additional_feat=2)
-
-
 @pytest.mark.parametrize("extra", [dict(), dict(use_context=False),
                                    dict(page_context_dim=16, n_heads=2, n_gat_layers=2, attention="gatv2")])
 def test_spec_keys_order_shapes_and_decoder_widths(extra):

@@ -13,6 +13,7 @@ from cova_web_object_detection_amd.models import CoVA, PageAttention
 from cova_web_object_detection_amd.trainer import HotPathTrainer
 import page_attn_geo_oracle as PG
 import page_attn_oracle as PA
+from config_cases import PAGE_SPEC as BASE
 
 KEY, GEO_KEY = "page_attention.qkv.weight", "page_attention.geometry.weight"
 SIZES, E, HEADS = (37, 0, 1, 5, 0), 8, 2
@@ -82,9 +83,6 @@ def test_exchanged_query_and_key_roles_move_A_beyond_the_gpu_bound():
 
 
 # ---------------------------------------------------------------- spec and module keys
-BASE = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8, n_additional_feat=2)
-
-
 @pytest.mark.parametrize("extra", [dict(), dict(use_context=False),
                                    dict(page_context_dim=16, n_heads=2, n_gat_layers=2, edge_geometry=True)])
 def test_spec_keys_order_and_shapes(extra):

@@ -21,14 +21,13 @@ from cova_web_object_detection_amd.features import FeatureCache  # noqa: E402
 from cova_web_object_detection_amd.models import CoVA, PageAttention  # noqa: E402
 from cova_web_object_detection_amd.pipeline import DeviceDataset  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
-from helpers import compare_grads, load_case, routing_from_saved  # noqa: E402
+from helpers import (bits_equal, compare_grads, DEV, framed, GRAD_TOL, GUARD, load_case, LOGIT_TOL,  # noqa: E402
+                     LOSS_TOL, padded, profiled, relerr, routing_from_saved, SGEMM_TOL, starts, survived)
 from oracle import cova_oracle as O  # noqa: E402
 import page_attn_oracle as PA  # noqa: E402
-from test_page_readout_gpu import (CFG, DEV, GUARD, bits_equal, five_steps, framed, n_params, padded,  # noqa: E402
-                                   page_set, profiled, relerr, seeded, starts, survived)
+from config_cases import SPLIT_CFG as CFG  # noqa: E402
+from trainer_cases import five_steps, n_params, page_set, seeded  # noqa: E402
 
-LOGIT_TOL, LOSS_TOL, GRAD_TOL = 5e-5, 2e-5, 1e-4          # tests/test_model_gpu.py
-SGEMM_TOL = 2e-5                                          # tests/test_kernels_gpu.py
 FWD, BWD = "cova_page_attn_fwd", "cova_page_attn_bwd"
 KEY = "page_attention.qkv.weight"
 

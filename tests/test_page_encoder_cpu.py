@@ -13,9 +13,8 @@ from cova_web_object_detection_amd import weights
 from cova_web_object_detection_amd.models import CoVA, PageEncoder
 from cova_web_object_detection_amd.trainer import HotPathTrainer
 import page_encoder_oracle as PE
-import test_model_configs_gpu as MC
+from config_cases import make_cfg, ORACLE_CASES, PAGE_SPEC as BASE
 
-BASE = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8, n_additional_feat=2)
 N_FEAT = 64 * 9 + 8 + 2
 LAYER_KEYS = ["norm1.weight", "norm1.bias", "qkv.weight", "geometry.weight", "out.weight", "out.bias", "norm2.weight",
               "norm2.bias", "ffn1.weight", "ffn1.bias", "ffn2.weight", "ffn2.bias"]
@@ -131,11 +130,11 @@ def test_spec_key_order_shapes_and_decoder_width(P, L, geometry):
     assert wide["page_encoder.layers.0.ffn1.weight"] == (12, P) and wide["page_encoder.layers.0.ffn2.weight"] == (P, 12)
 
 
-@pytest.mark.parametrize("name", list(MC.ORACLE_CASES))
+@pytest.mark.parametrize("name", list(ORACLE_CASES))
 def test_with_the_option_off_spec_and_seeded_weights_are_unchanged(name):
-    roi, _, _, _, hidden, bbox_hidden, seed = MC.ORACLE_CASES[name]
+    roi, _, _, _, hidden, bbox_hidden, seed = ORACLE_CASES[name]
     for context in (True, False):
-        cfg = {k: v for k, v in MC.make_cfg(roi, hidden, bbox_hidden, use_context=context).items() if k != "drop_prob"}
+        cfg = {k: v for k, v in make_cfg(roi, hidden, bbox_hidden, use_context=context).items() if k != "drop_prob"}
         off = dict(page_encoder_dim=0, page_encoder_heads=3, page_encoder_layers=5, page_encoder_ffn_dim=64)
         assert weights.state_dict_spec(**cfg, **off) == weights.state_dict_spec(**cfg)
         a, b = weights.seeded_state_dict(seed, **cfg), weights.seeded_state_dict(seed, **cfg, **off)

@@ -29,16 +29,17 @@ from cova_web_object_detection_amd.features import FeatureCache  # noqa: E402
 from cova_web_object_detection_amd.models import CoVA, PageEncoder  # noqa: E402
 from cova_web_object_detection_amd.pipeline import DeviceDataset  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
-from helpers import compare_grads, routing_from_saved  # noqa: E402
+from helpers import (bits_equal, compare_grads, DEV, framed, GRAD_TOL, GUARD, LOGIT_TOL,  # noqa: E402
+                     LOSS_TOL, NAN, padded, profiled, relerr, routing_from_saved, starts, survived)
 from oracle import cova_oracle as O  # noqa: E402
 import combined_cases as CC  # noqa: E402
 import combined_oracle as CO  # noqa: E402
 import page_attn_geo_oracle as PG  # noqa: E402
 import page_encoder_oracle as PE  # noqa: E402
-from test_page_readout_gpu import (CFG, DEV, GUARD, NAN, bits_equal, device_gates, five_steps, framed, padded, page_set,  # noqa: E402
-                                   profiled, relerr, seeded, starts, survived)
+from config_cases import SPLIT_CFG as CFG  # noqa: E402
+from gat_cases import device_gates  # noqa: E402
+from trainer_cases import five_steps, page_set, seeded  # noqa: E402
 
-LOGIT_TOL, LOSS_TOL, GRAD_TOL = 5e-5, 2e-5, 1e-4          # tests/test_model_gpu.py
 LN_FWD, LN_BWD, LN_WSQ = "cova_layernorm_fwd", "cova_layernorm_bwd", "cova_layernorm_workspace_floats"
 GELU_FWD, GELU_BWD = "cova_gelu_fwd", "cova_gelu_bwd"
 EPS = 1e-5

@@ -11,6 +11,7 @@ from cova_web_object_detection_amd import weights
 from cova_web_object_detection_amd.models import CoVA, PageReadout
 from cova_web_object_detection_amd.trainer import HotPathTrainer
 import readout_oracle as RO
+from config_cases import PAGE_SPEC as BASE
 
 KEYS = ["page_readout.W.weight", "page_readout.attention_layer.weight", "page_readout.attention_layer.bias"]
 
@@ -100,9 +101,6 @@ def test_shifting_the_bias_keeps_beta_only_while_all_gates_agree():
 
 
 # ---------------------------------------------------------------- spec and module keys
-BASE = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8, n_additional_feat=2)
-
-
 @pytest.mark.parametrize("extra", [dict(), dict(use_context=False), dict(n_heads=2, n_gat_layers=2, attention="gatv2"),
                                    dict(backbone_layers=2), dict(edge_geometry=True)])
 def test_spec_keys_order_shapes_and_decoder_widths(extra):

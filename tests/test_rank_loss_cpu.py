@@ -15,9 +15,8 @@ from cova_web_object_detection_amd import _lib, engine, weights  # noqa: E402
 from cova_web_object_detection_amd.models import CrossEntropyLoss  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
 import rank_oracle as RO  # noqa: E402
+from config_cases import BASE as CFG  # noqa: E402
 
-CFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8,
-           n_additional_feat=0, drop_prob=0.0)
 SD = weights.seeded_state_dict(3, **{k: v for k, v in CFG.items() if k != "drop_prob"})
 SIZES = [0, 1, 2, 65, 230]
 HEAD, TAIL = 3, 4                                  # rows outside every page

@@ -14,13 +14,10 @@ from cova_web_object_detection_amd.pipeline import PageAugment
 
 import augment_oracle as AO
 import resample_oracle as RO
+from helpers import np_bits as bits
 
 MAGS = dict(max_shift=(3, 5), brightness=0.2, contrast=0.3, saturation=0.4, channel_gain=0.15, invert_prob=0.3)
 DEN = 255 * 65536
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def random_color(rs, B):

@@ -14,18 +14,12 @@ from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
 import augment_oracle as AO  # noqa: E402
 import graph_oracle as GO  # noqa: E402
 import resample_oracle as RO  # noqa: E402
-from helpers import load_case  # noqa: E402
+from helpers import DEV, load_case, np_bits as bits, profiled  # noqa: E402
 
-DEV = "cuda:0"
 SENTINEL = 7.0
 FILLS = (0x000000, 0xFFFFFF, 0x123456)
 KEYS = ("images", "bboxes", "labels", "context_indices", "additional_feats", "page_start")
 STEPS = [(v, v) for v in (65536, 65535, 65537, 32768, 131072, 43691, 98304, 1, 1 << 22)] + [(32768, 131072), (131072, 43691)]
-
-
-def bits(a):
-    a = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def same(a, b):
@@ -34,16 +28,6 @@ def same(a, b):
     if a.dtype == np.float32 and b.dtype == np.float32:
         return a.shape == b.shape and np.array_equal(bits(a), bits(b))
     return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a, b)
-
-
-def profiled(fn):
-    _lib.PROFILE = {n: [] for n in _lib.lib().fn}
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-    finally:
-        prof, _lib.PROFILE = _lib.PROFILE, None
-    return out, {n: len(v) for n, v in prof.items() if v}
 
 
 def run(store, idx, B, step, origin, color, fill, out=None):

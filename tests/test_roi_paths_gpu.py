@@ -22,9 +22,8 @@ pytestmark = pytest.mark.gpu
 from cova_web_object_detection_amd import _lib, engine  # noqa: E402
 import head_cases as HC  # noqa: E402
 import roi_cases as RC  # noqa: E402
+from helpers import DEV, NAN  # noqa: E402
 
-DEV = "cuda:0"
-NAN = float("nan")
 I32 = torch.int32
 ALIGN_GATE = 1e-5                                    # tests/test_extension_gpu.py::test_roialign_kernels_match_self_oracle
 BAD_ARG = 10001                                      # COVA_ERR_BAD_ARG (include/cova_hip.h)

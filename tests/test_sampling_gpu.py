@@ -10,13 +10,15 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from cova_web_object_detection_amd import _lib, engine, pipeline, weights  # noqa: E402
+from cova_web_object_detection_amd import engine, pipeline, weights  # noqa: E402
 from cova_web_object_detection_amd.pipeline import DeviceCollate, DeviceDataset  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
 from oracle import cova_oracle as O  # noqa: E402
 import sampling_oracle as SO  # noqa: E402
+from config_cases import SPLIT_CFG as CFG  # noqa: E402
+from helpers import DEV, profiled  # noqa: E402
+from trainer_cases import page_set  # noqa: E402
 
-DEV = "cuda:0"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 KEYS = ("images", "bboxes", "labels", "context_indices", "additional_feats", "page_start")
 
@@ -38,16 +40,6 @@ def assert_batch_equals(got, ref, keys=KEYS):
         g = got[k].cpu().numpy() if torch.is_tensor(got[k]) else np.asarray(got[k])
         r = ref[k].cpu().numpy() if torch.is_tensor(ref[k]) else np.asarray(ref[k])
         assert g.shape == r.shape and g.dtype == r.dtype and np.array_equal(g, r), k
-
-
-def profiled(fn):
-    _lib.PROFILE = {n: [] for n in _lib.lib().fn}
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-    finally:
-        prof, _lib.PROFILE = _lib.PROFILE, None
-    return out, {n: len(v) for n, v in prof.items() if v}
 
 
 # ---------------------------------------------------------------- 5. injected keys against the reference's output
@@ -322,24 +314,6 @@ def test_a_pages_sample_does_not_depend_on_batch_size_or_position():
 
 
 # ---------------------------------------------------------------- 10. trajectory
-CFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8,
-           n_additional_feat=0, drop_prob=0.2)
-
-
-def page_set(P=15, img=96, seed=4):
-    rs = np.random.RandomState(seed)
-    u8 = rs.randint(0, 256, (P, img, img, 3)).astype(np.uint8)
-    rows = []
-    for _ in range(P):
-        n = int(rs.randint(11, 40))
-        wh = rs.uniform(6, 40, (n, 2))
-        xy = rs.uniform(0, 1, (n, 2)) * (img - wh)
-        lab = np.zeros((n, 1))
-        lab[rs.permutation(n)[:3], 0] = [1, 2, 3]
-        rows.append(np.concatenate([xy, wh, lab], 1).astype(np.float32))
-    return u8, rows
-
-
 def test_ten_train_steps_fed_by_the_dataset_equal_host_fed_steps_bit_for_bit():
     u8, rows = page_set()
     sd = weights.seeded_state_dict(77, logit_gain=2.0, **{k: v for k, v in CFG.items() if k != "drop_prob"})

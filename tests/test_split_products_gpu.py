@@ -22,8 +22,8 @@ pytestmark = pytest.mark.gpu
 import split_probe as sp  # noqa: E402
 from cova_web_object_detection_amd import engine  # noqa: E402
 from cova_web_object_detection_amd._lib import call, query  # noqa: E402
+from helpers import DEV  # noqa: E402
 
-DEV = "cuda:0"
 SHAPES = [(64, 64), (64, 256), (256, 64)]
 R_PROBE = 256 + 13      # nine 32-row tiles: even and odd ones (odd tiles run with negated activations), a ragged last one
 

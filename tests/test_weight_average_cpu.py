@@ -18,11 +18,10 @@ import average_oracle as AO  # noqa: E402
 from cova_web_object_detection_amd import _lib, evaluation, weights  # noqa: E402
 from cova_web_object_detection_amd import trainer as T  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
-from test_ddp_cpu import _free_port  # noqa: E402
+from config_cases import BASE as CFG, spec_of  # noqa: E402
+from helpers import free_port  # noqa: E402
 
-CFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8,
-           n_additional_feat=0, drop_prob=0.0)
-WCFG = {k: v for k, v in CFG.items() if k != "drop_prob"}
+WCFG = spec_of(CFG)
 SD = weights.seeded_state_dict(3, **WCFG)
 FROZEN = ("convnet.0.", "convnet.1.")
 
@@ -330,7 +329,7 @@ def _broadcast_worker(rank, world, port, out_dir):
 
 @pytest.mark.timeout(300)
 def test_broadcast_state_sends_the_average_and_its_counter(tmp_path):
-    world, port = 2, _free_port()
+    world, port = 2, free_port()
     mp.spawn(_broadcast_worker, args=(world, port, str(tmp_path)), nprocs=world, join=True)
     r0, r1 = (torch.load(os.path.join(str(tmp_path), "a%d.pt" % r)) for r in range(world))
     assert r0["start"][0] == r1["start"][0] == 0 and torch.equal(r0["start"][1], r1["start"][1])

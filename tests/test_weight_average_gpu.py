@@ -11,22 +11,18 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from cova_web_object_detection_amd import _lib, engine, synthetic, weights  # noqa: E402
+from cova_web_object_detection_amd import _lib, engine, weights  # noqa: E402
 from cova_web_object_detection_amd.evaluation import evaluate_split, fit  # noqa: E402
 from cova_web_object_detection_amd.pipeline import DeviceDataset  # noqa: E402
 from cova_web_object_detection_amd.trainer import HotPathTrainer  # noqa: E402
 import average_oracle as AO  # noqa: E402
-from helpers import HARD_RAGGED as RAGGED, N_BACKING, N_RAGGED, ragged_inside, seg_table  # noqa: E402
+from helpers import bits, DEV, HARD_RAGGED as RAGGED, N_BACKING, N_RAGGED, profiled, ragged_inside, seg_table  # noqa: E402
+from config_cases import SPLIT_CFG as ECFG, TRAINER_CFG as CFG  # noqa: E402
+from trainer_cases import device_setup as trainer_setup, page_set  # noqa: E402
 
-DEV = "cuda:0"
 SENTINEL = 0x7FC12345                      # a NaN with a payload: any arithmetic on it, or any store over it, shows
 
 # RAGGED is the hard ragged table of tests/helpers.py (the malformed row's [8900, 9000) keeps the sentinel)
-
-
-def bits(t):
-    t = t.detach().cpu() if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t))
-    return t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t     # (integer buffers compare as they are)
 
 
 @functools.lru_cache(maxsize=None)
@@ -84,29 +80,8 @@ def test_no_rows_or_no_elements_launch_nothing():
 
 
 # ---------------------------------------------------------------------------------------------- the trainer
-CFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=48, bbox_hidden_dim=16,
-           n_additional_feat=0, drop_prob=0.0)
 FROZEN = ("convnet.0.", "convnet.1.")
 STEPS = 6
-
-
-@functools.lru_cache(maxsize=None)
-def trainer_setup(seed=77):
-    """The tiny trainer of tests/test_optim_gpu.py."""
-    sd = weights.seeded_state_dict(seed, logit_gain=2.0, **{k: v for k, v in CFG.items() if k != "drop_prob"})
-    batches = [synthetic.make_batch(2, img_h=96, boxes_per_page=[20 + 3 * i, 11 + 2 * i], context_size=6, seed=900 + i)
-               for i in range(3)]
-    return sd, [{k: v.to(DEV) for k, v in b.items() if torch.is_tensor(v)} for b in batches]
-
-
-def _profiled(fn):
-    _lib.PROFILE = {n: [] for n in _lib.lib().fn}
-    try:
-        fn()
-        torch.cuda.synchronize()
-    finally:
-        prof, _lib.PROFILE = _lib.PROFILE, None
-    return {n: len(v) for n, v in prof.items() if v}
 
 
 @functools.lru_cache(maxsize=None)
@@ -185,12 +160,12 @@ def test_averaging_step_adds_its_launches_and_no_host_synchronisation():
     for kw in (dict(), dict(frozen=FROZEN), dict(optimizer="adamw", max_grad_norm=1.0)):   # plain, per-run and fused steps
         plain = HotPathTrainer(CFG, sd, DEV, **kw)
         plain.forward_backward(batches[0])
-        base = _profiled(plain.optimizer_step)
+        base = profiled(plain.optimizer_step)[1]
         assert "cova_weight_average" not in base
         for buffers in (True, False):
             tr = HotPathTrainer(CFG, sd, DEV, average="ema", average_buffers=buffers, **kw)
             tr.forward_backward(batches[0])
-            prof = _profiled(tr.optimizer_step)
+            prof = profiled(tr.optimizer_step)[1]
             assert prof == dict(base, cova_weight_average=2 if buffers else 1), (kw, buffers, prof)
     # steps 1 (before the start), 2 (the copy) and 3, 4 (updates): none reads anything back
     tr = HotPathTrainer(CFG, sd, DEV, average="swa", average_start=2)
@@ -206,24 +181,7 @@ def test_averaging_step_adds_its_launches_and_no_host_synchronisation():
 
 
 # ---------------------------------------------------------------------------------------------- evaluation and fit
-ECFG = dict(roi_output_size=(3, 3), n_classes=4, use_context=True, hidden_dim=32, bbox_hidden_dim=8,
-            n_additional_feat=0, drop_prob=0.2)
 CS = 6
-
-
-def page_set(P, img=96, seed=4):
-    """The construction of tests/test_evaluation_gpu.py's page_set."""
-    rs = np.random.RandomState(seed)
-    u8 = rs.randint(0, 256, (P, img, img, 3)).astype(np.uint8)
-    rows = []
-    for _ in range(P):
-        n = int(rs.randint(11, 40))
-        wh = rs.uniform(6, 40, (n, 2))
-        xy = rs.uniform(0, 1, (n, 2)) * (img - wh)
-        lab = np.zeros((n, 1))
-        lab[rs.permutation(n)[:3], 0] = [1, 2, 3]
-        rows.append(np.concatenate([xy, wh, lab], 1).astype(np.float32))
-    return u8, rows
 
 
 @functools.lru_cache(maxsize=None)

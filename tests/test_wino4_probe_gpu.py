@@ -18,13 +18,13 @@ pytestmark = pytest.mark.gpu
 
 import wino4_probe as wp  # noqa: E402
 from cova_web_object_detection_amd._lib import call, query  # noqa: E402
+from helpers import DEV  # noqa: E402
 
-DEV = "cuda:0"
 GUARD = 2 * 64          # guard rows (pixels of 64 channels) in front of and behind an out buffer
 GUARD_VALUE = -12345.0
 
 
-def framed(B, H, W):
+def framed_out(B, H, W):
     n = B * H * W
     buf = torch.full((n + 2 * GUARD, 64), GUARD_VALUE, device=DEV)
     out = buf[GUARD:GUARD + n].view(B, H, W, 64)
@@ -44,7 +44,7 @@ def launch(c, with_part):
     call("cova_conv3x3_wino4_prep", c.w.to(DEV), uf, ud)
     u = ud if c.dgrad else uf
     x = c.x.to(DEV)
-    buf, out = framed(B, H, W)
+    buf, out = framed_out(B, H, W)
     part = torch.zeros(query("cova_conv3x3_wino4_num_partials", B, H, W), 2, 64, device=DEV) if with_part else None
     N = None
     if c.form in ("fwd", "dgrad"):
