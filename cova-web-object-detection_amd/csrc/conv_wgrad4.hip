@@ -30,7 +30,12 @@
 //   * the next patch is requested once the first transform stage has read the current one (every copy is unconditional:
 //     edge patches clamp the address, the consumer zeroes padding);
 //   * the two waves of a SIMD (input role / gradient role) run an iteration in opposite order (transform then MFMAs /
-//     MFMAs then transform); operands are double buffered, one block barrier per K-step (LDS-only).
+//     MFMAs then transform); operands are double buffered, one block barrier per K-step (LDS-only);
+//   * the walk is CARRIED: a wave decides once per K-step (current patch interior or edge, next patch interior or edge, its
+//     turn at the side output) and runs a straight-line body for it; the 64-bit page bases and the divisions are taken at
+//     a segment change only, rows and block columns of a patch ride in lane offsets and immediate fields.  The two waves
+//     of a SIMD share its issue cycles: every scalar instruction of the bookkeeping cost its wave like a vector one
+//     (profiles/wgrad4_scalar_diet.txt).
 // Side output: the gradient operand A*dz + B*dz2 + C written once (gradient-role waves of the half-0 blocks), for the data-
 // gradient launch of the same convolution.
 // Operand prologues as the F(2x2) kernel's: activation = relu?(A*act + C) on load, gradient = A*dz + B*dz2 + C on load
@@ -42,9 +47,19 @@
 // Ablation builds of tools/wgrad4_bench.py (tools/wg4_abl_build.sh, -DWG4_ABL=<mask>; 0 in the product): 1 no MFMAs,
 // 2 no pixel copies, 8 no transform (reads + arithmetic + operand writes), 16 no operand reads of the
 // MFMA phase (stale registers), 32 copies always from the walker's first patch (L2-resident source), 64 both roles
-// in the same order (MFMAs first), 128 no row-pair ring (every patch requested whole)
+// in the same order (MFMAs first), 128 no row-pair ring (every patch requested whole).  Masks 32 and 128 were retired with
+// the carried walk state (their measurements: DESIGN.md 11.1 / 13.4).
 #ifndef WG4_ABL
 #define WG4_ABL 0
+#endif
+#if WG4_ABL & (32 | 128)
+#error "WG4_ABL masks 32 and 128 are retired"
+#endif
+// 1 (tools only): every pixel read of the first transform stage is waited for before the next one is issued -- the form the
+// branches around the side-output stores used to force.  0: the compiler groups the reads.  Without the branch and address
+// stream between them the grouped reads are the faster form (stand-alone 0.48 / 0.47 against 0.56 / 0.59 ms).
+#ifndef WG4_SERIAL_READS
+#define WG4_SERIAL_READS 0
 #endif
 
 // 157,696 B of static LDS (operand buffers 83,968 + wave-private pixel buffers 73,728): only gfx950's 160 KB per CU holds it
@@ -84,6 +99,16 @@ struct Wg4Args {
     int act_relu;
     int H, W, tiles_y, strips, nseg_y, seg_rows, nsegs;
 };
+
+// The kernel's argument block (Wg4Args is its only argument: offset 0 of the kernarg segment) behind a pointer the
+// compiler treats as new at every call: scalar loads where it is used, nothing carried in registers.
+typedef __attribute__((address_space(4))) const Wg4Args wg4_kernarg;
+__device__ __forceinline__ wg4_kernarg *wg4_kernarg_fresh()
+{
+    wg4_kernarg *p = reinterpret_cast<wg4_kernarg *>(reinterpret_cast<size_t>(__builtin_amdgcn_kernarg_segment_ptr()));
+    asm volatile("" : "+s"(p));
+    return p;
+}
 
 // B^T x for one 6-vector (second stage of the input transform; 12 operations)
 __device__ __forceinline__ void wg4_bt6(const float (&d)[6], float (&o)[6])
@@ -144,10 +169,46 @@ __device__ __forceinline__ void wg4_a_half(float g0, float g1, float g2, float g
     }
 }
 
-// position of the K-step stream: which segment (image, 16-pixel strip, run of tile rows) and which row of it
-struct Wg4It {
-    int seg, rr, nrows, b, strip, ty;
+// Position of a wave's K-step stream, CARRIED from patch to patch: which segment (image, 16-pixel strip, run of tile rows),
+// which row of it, and what the copies and stores of the patch there need.  The divisions and the 64-bit page bases are
+// taken at a segment change only; down a strip the patch origin advances by the constant 4 W 256 bytes.
+struct Wg4Walk {
+    int seg, rr, nrows, ty;          // segment, row of it, its rows; tile row of the map
+    int gx0;                         // first pixel column of this wave's patch (constant inside a strip)
+    unsigned cm;                     // column mask of the patch (constant inside a strip)
+    unsigned org;                    // byte offset of the patch's pixel (0, 0) inside its page (wraps below zero on the top / left edge)
+    const char *src, *src2;          // the page of the operand (and of the second gradient tensor)
+    char *out;                       // the page of the side output
 };
+
+// f(integral_constant<int, I>) for I = 0 .. N - 1: the index is a constant expression (immediate offset fields)
+template <int I, int N, class F>
+__device__ __forceinline__ void wg4_for(F &&f)
+{
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        wg4_for<I + 1, N>(f);
+    }
+}
+
+// one float of the LDS at a byte address (base register + immediate offset after inlining)
+__device__ __forceinline__ float wg4_lds_read(unsigned byte_addr)
+{
+    typedef __attribute__((address_space(3))) const float lds_cfloat;
+    float v = *reinterpret_cast<lds_cfloat *>((size_t)byte_addr);
+#if WG4_SERIAL_READS
+    asm volatile("" : "+v"(v) : : "memory");          // the value is waited for before the next read is issued
+#endif
+    return v;
+}
+
+// side-output store: wave-uniform 64-bit base + this lane's 32-bit byte offset + an immediate (the pixel column)
+template <int IMM>
+__device__ __forceinline__ void wg4_store_imm(char *base, unsigned off_bytes, float v)
+{
+    static_assert(IMM >= 0 && IMM < 4096, "global_store: 13-bit signed immediate offset");
+    asm volatile("global_store_dword %0, %1, %2 offset:%3" ::"v"(off_bytes), "v"(v), "s"(base), "i"(IMM));
+}
 
 // PROD: 0 plain gradient operand, 1 = A*dz + C, 2 = A*dz + B*dz2 + C on load
 template <bool PROA, int PROD>
@@ -178,24 +239,6 @@ __global__ __launch_bounds__(wg4::THREADS, 1) void conv3x3_wgrad4_kernel(const W
 
     int n_k = 0;                                  // K-steps of this block
     for (int s = walker; s < a.nsegs; s += NW) n_k += min(a.seg_rows, a.tiles_y - (s % a.nseg_y) * a.seg_rows);
-
-    auto seg_setup = [&](Wg4It &it) __attribute__((always_inline)) {
-        const int s = it.seg < a.nsegs ? it.seg : walker;        // past the end: a valid segment (its pixels are never used)
-        const int sy = s % a.nseg_y, st = (s / a.nseg_y) % a.strips;
-        it.b = s / (a.nseg_y * a.strips);
-        it.strip = st;
-        it.ty = sy * a.seg_rows;
-        it.nrows = min(a.seg_rows, a.tiles_y - it.ty);
-        it.rr = 0;
-    };
-    auto advance = [&](Wg4It &it) __attribute__((always_inline)) {
-        if (++it.rr < it.nrows) {
-            ++it.ty;
-        } else {
-            it.seg += NW;
-            seg_setup(it);
-        }
-    };
 
     f32x4 acc[9][4];            // [position of the group][co block i * 2 + ci block j]
 #pragma unroll
@@ -244,6 +287,8 @@ __global__ __launch_bounds__(wg4::THREADS, 1) void conv3x3_wgrad4_kernel(const W
         constexpr int NR = VROLE ? 6 : 4;                    // patch rows = columns
         constexpr int NB = NR / 2;                           // 2 x 2 pixel blocks per patch row / column
         constexpr bool TWO = !VROLE && PROD == 2;
+        constexpr int V = VROLE ? 1 : 0;                     // the input patch starts one pixel up and left of its tile
+        constexpr bool SIDE = !VROLE && PROD != 0;           // the role and variant that can write the side output
         // per-channel prologue constants (lane = channel); ReLU as max(., 0) or max(., -inf): one instruction either way
         const float relu_floor = a.act_relu ? 0.f : -INFINITY;
         float pA = 1.f, pB = 0.f, pC = 0.f;
@@ -258,62 +303,98 @@ __global__ __launch_bounds__(wg4::THREADS, 1) void conv3x3_wgrad4_kernel(const W
         // ONE lane offset; it lands in slot 4 j + s of the wave's pixel buffer ([slot][64 channels]; the second
         // gradient tensor behind the first: + 16 slots).
         const int sub = lane >> 4, c4 = lane & 15;
+        const unsigned W256 = (unsigned)W * 256u;            // bytes of a pixel row
         const unsigned laneoff = (unsigned)((((sub >> 1) * W + (sub & 1)) * 64 + c4 * 4) * 4);
-        float *raw = s_raw + wave * RAW_FLOATS;
-        const unsigned raw_lds = (unsigned)(size_t)(lds_void *)raw;
-        const float *raw_r = raw + lane;                     // slot s, this lane's channel: raw_r[64 s]
+        // (the row pair of a copy rides in the lane offset: loop-invariant vector registers instead of a scalar base per pair)
+        unsigned rowoff[NB];
+#pragma unroll
+        for (int br = 0; br < NB; ++br) rowoff[br] = laneoff + 2u * (unsigned)br * W256;
+        const unsigned raw_lds = (unsigned)(size_t)(lds_void *)(s_raw + wave * RAW_FLOATS);
+        const unsigned lane4 = (unsigned)lane * 4u;          // this lane's channel inside a pixel slot
         // pixel validity of a patch: bit r of the row mask / bit c of the column mask (wave-uniform; a few scalar operations:
         // the valid rows / columns of a patch are a contiguous range)
         auto range_mask = [&](int g0, int n) __attribute__((always_inline)) {        // bits i with 0 <= g0 + i < n, i < NR
             const int lo = max(-g0, 0), hi = min(n - g0, NR);
             return hi > lo ? (((1u << hi) - 1u) & ~((1u << lo) - 1u)) : 0u;
         };
-        auto masks = [&](const Wg4It &it, unsigned &rm, unsigned &cm) __attribute__((always_inline)) {
-            rm = range_mask(4 * it.ty - (VROLE ? 1 : 0), H);
-            cm = range_mask(16 * it.strip + 4 * tcol - (VROLE ? 1 : 0), W);
-        };
         constexpr unsigned FULL = (1u << NR) - 1u;
+        // ---- the walk: everything a segment decides is computed here, at a segment change, and nowhere else
+        auto seg_setup = [&](Wg4Walk &w) __attribute__((always_inline)) {
+            // (What only a segment change needs is read from the kernel-argument segment HERE, through a pointer the compiler
+            // cannot see through: nine arguments and the reciprocals of the two divisors would otherwise sit in scalar
+            // registers across the whole loop -- they were what spilled.)
+            wg4_kernarg *ka = wg4_kernarg_fresh();
+            const int nsegs = ka->nsegs, nseg_y = ka->nseg_y, strips = ka->strips, seg_rows = ka->seg_rows, tiles_y = ka->tiles_y;
+            const int s = w.seg < nsegs ? w.seg : walker;            // past the end: a valid segment (its pixels are never used)
+            const int q = s / nseg_y, sy = s - q * nseg_y;
+            const int b = q / strips, st = q - b * strips;
+            w.ty = sy * seg_rows;
+            w.nrows = min(seg_rows, tiles_y - w.ty);
+            w.rr = 0;
+            w.gx0 = 16 * st + 4 * tcol - V;
+            w.cm = range_mask(w.gx0, W);
+            w.org = (unsigned)(((4 * w.ty - V) * W + w.gx0) * 256);
+            // (64-bit base of the walk's page, wave-uniform; 32-bit byte offsets inside the page: any batch size)
+            const size_t pgb = (size_t)b * (size_t)H * (size_t)W * 256u;
+            w.src = reinterpret_cast<const char *>(VROLE ? ka->act : ka->dz) + pgb;
+            w.src2 = TWO ? reinterpret_cast<const char *>(ka->dz2) + pgb : nullptr;
+            w.out = SIDE ? reinterpret_cast<char *>(ka->dz_out) + pgb : nullptr;
+        };
+        auto advance = [&](Wg4Walk &w) __attribute__((always_inline)) {
+            if (++w.rr < w.nrows) {
+                ++w.ty;
+                w.org += 4u * W256;
+            } else {
+                w.seg += NW;
+                seg_setup(w);
+            }
+        };
+        // does any pixel of the patch lie outside the image? (the row part from the counter, the column part per strip)
+        auto is_edge = [&](const Wg4Walk &w) __attribute__((always_inline)) {
+            return w.cm != FULL || w.ty < V || 4 * w.ty - V + NR > H;
+        };
         // every pixel of the patch of `it` requested (unconditionally: an edge patch clamps its addresses, the consumer
         // zeroes what lies outside the image; the K-steps past the end re-request a valid patch)
         // Input role: the buffer is a RING of the patch's three row pairs -- walking down a strip, the bottom pair of a patch
         // is the top pair of the next one and stays where it is; only the two new pairs are requested (24 of 36 pixels).
-        // Row pair p of a patch with ring phase phi lives in pair slot (p + phi) % 3 (12 pixel slots each).
-        // one copy: block (br, bc) of the patch of `it` (and of the second gradient tensor)
-        auto piece = [&](const Wg4It &it_, bool edge, int phi, int br, int bc) __attribute__((always_inline)) {
+        // The LDS byte addresses of the three pair slots ROTATE with the walk (pb[p] = row pair p of the current patch) instead
+        // of a ring phase that every copy and every read decodes; the gradient role has no ring: two fixed pairs.
+        unsigned pb[3] = {raw_lds, raw_lds + (VROLE ? 3072u : 2048u), raw_lds + (VROLE ? 6144u : 4096u)};
+        // Interior patch, straight line: the row pairs br0 .. NB - 1 (br0 a constant for the caller that knows it).  ONE
+        // 64-bit base per tensor; the row pair rides in the lane offset, the block column in the immediate field -- which
+        // the hardware also adds to the LDS address: the slot's column step of 1024 = 512 in m0 + 512 in the field.
+        auto fetch_in = [&](const Wg4Walk &w, const unsigned (&nb)[3], int br0) __attribute__((always_inline)) {
             if (WG4_ABL & 2) return;
-            Wg4It it = it_;
-            if (WG4_ABL & 32) { it.seg = walker; seg_setup(it); }
-            const int gy0 = 4 * it.ty - (VROLE ? 1 : 0), gx0 = 16 * it.strip + 4 * tcol - (VROLE ? 1 : 0);
-            // (64-bit base of the walk's page, wave-uniform; 32-bit byte offsets inside the page: any batch size)
-            const size_t pgb = (size_t)it.b * (size_t)H * (size_t)W * 256u;
-            const char *src = reinterpret_cast<const char *>(VROLE ? a.act : a.dz) + pgb;
-            const char *src2 = TWO ? reinterpret_cast<const char *>(a.dz2) + pgb : nullptr;
-            int ps = br + phi;                                   // pair slot (the gradient role has no ring: phi = 0)
-            if (VROLE && ps >= 3) ps -= 3;
-            const unsigned dst = raw_lds + (VROLE ? 3072u * (unsigned)ps : 2048u * (unsigned)br) + 1024u * (unsigned)bc;
-            if (!edge) {                                         // scalar base of the row pair + the block column
-                const unsigned off = (unsigned)(((gy0 + 2 * br) * W + gx0) * 256 + 512 * bc);     // (a page < 4 GB: host check)
-                copy16_to_lds(src + off, laneoff, dst);
-                if (TWO) copy16_to_lds(src2 + off, laneoff, dst + 4096);
-            } else {
-                const int r = 2 * br + (sub >> 1), c = 2 * bc + (sub & 1);
-                const int gy = min(max(gy0 + r, 0), H - 1), gx = min(max(gx0 + c, 0), W - 1);
-                const unsigned eo = (unsigned)((gy * W + gx) * 256 + c4 * 16);
-                copy16_to_lds(src, eo, dst);
-                if (TWO) copy16_to_lds(src2, eo, dst + 4096);
-            }
+            const char *p = w.src + w.org;                       // (a page < 4 GB: host check)
+            const char *p2 = TWO ? w.src2 + w.org : nullptr;
+            wg4_for<0, NB>([&](auto br_t) __attribute__((always_inline)) {
+                constexpr int br = decltype(br_t)::value;
+                if (br < br0) return;
+                wg4_for<0, NB>([&](auto bc_t) __attribute__((always_inline)) {
+                    constexpr int bc = decltype(bc_t)::value;
+                    const unsigned base = VROLE ? nb[br] : raw_lds;          // (the rotating slot / the wave's buffer)
+                    constexpr int add = (VROLE ? 0 : 2048 * br) + 512 * bc;
+                    copy16_to_lds_imm<512 * bc, add>(p, rowoff[br], base);
+                    if (TWO) copy16_to_lds_imm<512 * bc, add + 4096>(p2, rowoff[br], base);
+                });
+            });
         };
-        // a continued walk of the input role keeps row pair 0 (wave-uniform)
-        auto first_pair = [&](const Wg4It &it) __attribute__((always_inline)) {
-            return (VROLE && it.rr != 0 && !(WG4_ABL & 128)) ? 1 : 0;
-        };
-        auto fetch = [&](const Wg4It &it, bool edge, int phi) __attribute__((always_inline)) {
-            const int br0 = first_pair(it);
+        // Edge patch: every lane clamps its own pixel (rare: the top / bottom tile row and the first / last column of a map)
+        auto fetch_edge = [&](const Wg4Walk &w, const unsigned (&nb)[3], int br0) __attribute__((always_inline)) {
+            if (WG4_ABL & 2) return;
+            const int gy0 = 4 * w.ty - V;
 #pragma unroll
             for (int br = 0; br < NB; ++br) {
                 if (br < br0) continue;
 #pragma unroll
-                for (int bc = 0; bc < NB; ++bc) piece(it, edge, phi, br, bc);
+                for (int bc = 0; bc < NB; ++bc) {
+                    const unsigned dst = nb[br] + 1024u * (unsigned)bc;
+                    const int r = 2 * br + (sub >> 1), c = 2 * bc + (sub & 1);
+                    const int gy = min(max(gy0 + r, 0), H - 1), gx = min(max(w.gx0 + c, 0), W - 1);
+                    const unsigned eo = (unsigned)((gy * W + gx) * 256 + c4 * 16);
+                    copy16_to_lds(w.src, eo, dst);
+                    if (TWO) copy16_to_lds(w.src2, eo, dst + 4096);
+                }
             }
         };
         // side output (gradient role): the operand as formed on load, written once -- the data-gradient launch of the same
@@ -321,73 +402,98 @@ __global__ __launch_bounds__(wg4::THREADS, 1) void conv3x3_wgrad4_kernel(const W
         // of a walk (blocks b, b + 8: same tiles, same order) take TURNS, tile by tile: with all the stores in half 0 that
         // block fell behind its partner, the pair stopped meeting in L2 and the launch fetched every pixel twice (FETCH_SIZE
         // of the step's launches 2.5 GB against 1.3 GB stand-alone without the side output: 3 GB moved in 0.59 ms)
-        const bool emit = !VROLE && PROD != 0 && a.dz_out != nullptr;
+        const bool emit = SIDE && a.dz_out != nullptr;
         int emit_k = 0;                                      // tiles transformed so far by this wave
-        unsigned emit_lane = (unsigned)lane * 4u;
-        asm volatile("" : "+v"(emit_lane));
-        unsigned cur_org = 0;                                // element offset of the current tile's pixel (0, 0) inside its page
-        char *cur_out = reinterpret_cast<char *>(a.dz_out);  // ... and that page of the side output
-        auto origin = [&](const Wg4It &it) __attribute__((always_inline)) {
-            cur_out = reinterpret_cast<char *>(a.dz_out) + (size_t)it.b * (size_t)H * (size_t)W * 256u;
-            return (unsigned)(((4 * it.ty) * W + 16 * it.strip + 4 * tcol) * 64);
-        };
-        int phi = 0;                                         // ring phase of the patch in the buffer
+        // (a pixel row of the tile rides in the lane offset of its stores, the pixel column in the immediate field: one
+        // scalar base per tile)
+        unsigned outoff[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) outoff[r] = lane4 + (unsigned)r * W256;
+        // the CURRENT patch (the one in the pixel buffer): what is left of its walk position once `nxt` has moved on
+        bool cur_edge = true;
+        int cur_ty = 0;
+        unsigned cur_cm = 0, cur_org = 0;                    // (gradient role: the tile's origin is the patch's)
+        char *cur_out = nullptr;
         int wg4_k = -1;                                      // (trace builds)
         (void)wg4_k;
         // (The two position halves of a walk -- blocks b, b ^ 8: same XCD, same pixels in the same order -- run free.  A pacing
         // through progress words was built and measured in round 5: same HBM traffic, 3 % slower)
-        auto transform = [&](float *buf, const Wg4It &nxt, unsigned crm, unsigned ccm, unsigned nrm, unsigned ncm) __attribute__((always_inline)) {
-            // this lane's channel of pair slot (p + phi) % 3, p = 0..2 (input role; gradient role: two fixed pairs)
-            const float *pair_r[3];
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                int ps = p + phi;
-                if (ps >= 3) ps -= 3;
-                pair_r[p] = raw_r + (VROLE ? 768 * ps : 512 * p);
-            }
+        // One K-step's transform, SPECIALISED by what the caller decided once for the K-step (all wave-uniform):
+        //   INTERIOR: the current patch and the next one lie wholly inside the image and the walk continues down its strip --
+        //             no mask, no clamp, no branch: the body is a straight line; EMIT (compile time) = this tile's turn at the
+        //             side output, all 16 stores or none;
+        //   otherwise the general body: masks on every pixel, the stores behind their pixel's mask and `emit_rt`, the
+        //             next patch by the path it needs.
+        // `nxt` is the walk position of the next patch (the one requested here).
+        auto transform = [&](float *buf, const Wg4Walk &nxt, auto interior_t, auto emit_t, bool emit_rt) __attribute__((always_inline)) {
+            constexpr bool INTERIOR = decltype(interior_t)::value;
+            constexpr bool EMIT = decltype(emit_t)::value;
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's copies of the patch have landed
-            const int nphi = (!VROLE || (WG4_ABL & 128)) ? 0 : (nxt.rr == 0 ? phi : (phi == 0 ? 2 : phi - 1));      // (phi + 2) % 3 down the strip
-            const bool nedge = nrm != FULL || ncm != FULL;
-            if (WG4_ABL & 8) { fetch(nxt, nedge, nphi); phi = nphi; return; }
+            // the pair slots of the next patch: down a strip its top pair is this one's bottom pair and stays where it is
+            const bool down = INTERIOR || nxt.rr != 0;
+            unsigned nb[3] = {pb[0], pb[1], pb[2]};
+            if (VROLE && down) { nb[0] = pb[2]; nb[1] = pb[0]; nb[2] = pb[1]; }
+            const int br0 = (VROLE && down) ? 1 : 0;                // a continued walk of the input role keeps row pair 0
+            auto fetch = [&]() __attribute__((always_inline)) {
+                if constexpr (INTERIOR) {
+                    fetch_in(nxt, nb, VROLE ? 1 : 0);
+                } else {
+                    if (is_edge(nxt)) fetch_edge(nxt, nb, br0);
+                    else fetch_in(nxt, nb, br0);
+                }
+#pragma unroll
+                for (int p = 0; p < 3; ++p) pb[p] = nb[p];
+            };
+            if (WG4_ABL & 8) { fetch(); return; }
             WG4_STAMP(1);
             float t[3][NR];
-            const bool emit_now = emit && ((emit_k & 1) == HALF);
-            ++emit_k;
-            auto stage1 = [&](auto cedge_t) __attribute__((always_inline)) {
-            constexpr bool cedge = decltype(cedge_t)::value;
+            unsigned crm = FULL, ccm = FULL;
+            if (!INTERIOR) { crm = range_mask(4 * cur_ty - V, H); ccm = cur_cm; }
+            unsigned ra[3];                                         // this lane's channel of row pair p
 #pragma unroll
-            for (int c = 0; c < NR; ++c) {
+            for (int p = 0; p < NB; ++p) ra[p] = pb[p] + lane4;
+            char *obase = SIDE ? cur_out + cur_org : nullptr;       // the tile's pixel (0, 0) in the side output
+            // (straight-line body: the 16 operand values wait in registers and are stored behind the last read -- a store
+            // between the reads would pin each read and its wait in front of it)
+            float keep[SIDE && INTERIOR && EMIT ? 4 : 1][4];
+            (void)keep;
+            wg4_for<0, NR>([&](auto c_t) __attribute__((always_inline)) {
+                constexpr int c = decltype(c_t)::value;
                 float d[NR];
-#pragma unroll
-                for (int r = 0; r < NR; ++r) {
-                    const int slot = 4 * (c >> 1) + 2 * (r & 1) + (c & 1);          // within the row pair's slots
-                    float v = pair_r[r >> 1][64 * slot];
+                wg4_for<0, NR>([&](auto r_t) __attribute__((always_inline)) {
+                    constexpr int r = decltype(r_t)::value;
+                    constexpr int slot = 4 * (c >> 1) + 2 * (r & 1) + (c & 1);          // within the row pair's slots
+                    float v = wg4_lds_read(ra[r >> 1] + 256u * slot);
                     if (VROLE && PROA) v = fmaxf(fmaf(pA, v, pC), relu_floor);     // same expression as the forward prologue
-                    if (TWO) v = fmaf(pA, v, fmaf(pB, pair_r[r >> 1][64 * (16 + slot)], pC));   // dz = A*dy + B*z + C
+                    if (TWO) v = fmaf(pA, v, fmaf(pB, wg4_lds_read(ra[r >> 1] + 256u * (16 + slot)), pC));   // dz = A*dy + B*z + C
                     if (!VROLE && PROD == 1) v = fmaf(pA, v, pC);
-                    if (cedge && !(((crm >> r) & (ccm >> c) & 1u) != 0u)) v = 0.f;              // zero padding stays zero
+                    const bool inside = INTERIOR || (((crm >> r) & (ccm >> c) & 1u) != 0u);
+                    if (!inside) v = 0.f;                                           // zero padding stays zero
                     d[r] = v;
-                    if (!VROLE && PROD != 0) {
-                        // (scalar base of the pixel + ONE lane offset: global_store with an SGPR pair, no per-lane pointers)
-                        if (emit_now && (!cedge || (((crm >> r) & (ccm >> c) & 1u) != 0u))) {
-                            unsigned ob = (cur_org + (unsigned)((r * W + c) * 64)) * 4u;
-                            asm volatile("" : "+s"(ob));
-                            *reinterpret_cast<float *>(cur_out + ob + emit_lane) = v;
+                    if constexpr (SIDE) {
+                        if constexpr (INTERIOR) {
+                            if constexpr (EMIT) keep[c][r] = v;
+                        } else {
+                            if (emit_rt && inside) wg4_store_imm<256 * c>(obase, outoff[r], v);
                         }
                     }
-                }
+                });
                 float o[3];
                 if constexpr (VROLE) wg4_bt_half<HALF>(d[0], d[1], d[2], d[3], d[4], d[5], o);
                 else wg4_a_half<HALF>(d[0], d[1], d[2], d[3], o);
                 t[0][c] = o[0]; t[1][c] = o[1]; t[2][c] = o[2];
+            });
+            if constexpr (SIDE && INTERIOR && EMIT) {
+                wg4_for<0, 4>([&](auto c_t) __attribute__((always_inline)) {
+                    wg4_for<0, 4>([&](auto r_t) __attribute__((always_inline)) {
+                        constexpr int c = decltype(c_t)::value, r = decltype(r_t)::value;
+                        wg4_store_imm<256 * c>(obase, outoff[r], keep[c][r]);
+                    });
+                });
             }
-            };
-            if (crm != FULL || ccm != FULL) stage1(std::true_type{});      // (wave-uniform: nothing but registers lives across)
-            else stage1(std::false_type{});
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the buffer has been read: it may be overwritten
             WG4_STAMP(2);
-            fetch(nxt, nedge, nphi);          // the buffer is free: the next patch is requested
-            phi = nphi;
+            fetch();                          // the buffer is free: the next patch is requested
             WG4_STAMP(3);
             // second stage row by row, stored as soon as a row is complete: position p = 6 al + b sits at float p of the
             // group-0 row (p < 9), at float p - 9 of the group-1 row otherwise
@@ -416,20 +522,30 @@ __global__ __launch_bounds__(wg4::THREADS, 1) void conv3x3_wgrad4_kernel(const W
             }
         };
 
-        Wg4It nxt;
+        using Tt = std::true_type;
+        using Ft = std::false_type;
+        Wg4Walk nxt;
         nxt.seg = walker;
         seg_setup(nxt);
-        unsigned crm, ccm, nrm, ncm;
-        masks(nxt, nrm, ncm);
-        fetch(nxt, true, 0);                                  // patch 0 (through the clamping path: once per block)
-        crm = nrm; ccm = ncm;
-        cur_org = origin(nxt);
-        advance(nxt);
-        masks(nxt, nrm, ncm);
-        transform(s_op, nxt, crm, ccm, nrm, ncm);             // patch 0 -> buffer 0; requests patch 1
-        crm = nrm; ccm = ncm;
-        cur_org = origin(nxt);
-        advance(nxt);
+        // `nxt` moves on to the patch after the one it named; what the transform still needs of that one stays behind
+        auto step_walk = [&]() __attribute__((always_inline)) {
+            cur_edge = is_edge(nxt);
+            cur_ty = nxt.ty;
+            cur_cm = nxt.cm;
+            cur_org = nxt.org;
+            cur_out = nxt.out;
+            advance(nxt);
+        };
+        // this tile's turn at the side output?  (the two position halves alternate, tile by tile)
+        auto my_turn = [&]() __attribute__((always_inline)) {
+            const bool now = emit && ((emit_k & 1) == HALF);
+            ++emit_k;
+            return now;
+        };
+        fetch_edge(nxt, pb, 0);                               // patch 0 (through the clamping path: once per block)
+        step_walk();
+        transform(s_op, nxt, Ft{}, Ft{}, my_turn());          // patch 0 -> buffer 0; requests patch 1
+        step_walk();
         lds_barrier();
         // The two waves of a SIMD (wave w: input role, wave w + 4: gradient role) run the iteration in OPPOSITE order --
         // transform then MFMAs / MFMAs then transform: one wave's pixel wait and transform arithmetic sit beside the
@@ -441,17 +557,20 @@ __global__ __launch_bounds__(wg4::THREADS, 1) void conv3x3_wgrad4_kernel(const W
             WG4_STAMP(0);
             if (!VROLE || (WG4_ABL & 64)) { mfma_phase(s_op + (k & 1) * BUF_FLOATS); WG4_STAMP(5); }
             const bool more = k + 1 < n_k;
-            if (more) {
-                masks(nxt, nrm, ncm);
-                transform(s_op + ((k + 1) & 1) * BUF_FLOATS, nxt, crm, ccm, nrm, ncm);      // patch k + 1
+            if (more) {                                       // patch k + 1: ONE decision, then a body without any
+                float *nbuf = s_op + ((k + 1) & 1) * BUF_FLOATS;
+                const bool turn = my_turn();
+                const bool interior = !cur_edge && !is_edge(nxt) && !(VROLE && nxt.rr == 0);
+                if (interior) {
+                    if (SIDE && turn) transform(nbuf, nxt, Tt{}, Tt{}, true);
+                    else transform(nbuf, nxt, Tt{}, Ft{}, false);
+                } else {
+                    transform(nbuf, nxt, Ft{}, Ft{}, turn);
+                }
             }
             WG4_STAMP(4);
             if (VROLE && !(WG4_ABL & 64)) { mfma_phase(s_op + (k & 1) * BUF_FLOATS); WG4_STAMP(5); }
-            if (more) {
-                crm = nrm; ccm = ncm;
-                cur_org = origin(nxt);
-                advance(nxt);
-            }
+            if (more) step_walk();
             lds_barrier();
             WG4_STAMP(6);
         }
@@ -519,7 +638,7 @@ __global__ __launch_bounds__(wg4::THREADS, 1) void conv3x3_wgrad4_kernel(const W
             }
         }
     };
-    float *dst = a.part + (size_t)blockIdx.x * PART_FLOATS;
+    float *dst = wg4_kernarg_fresh()->part + (size_t)blockIdx.x * PART_FLOATS;      // (not carried across the K loop)
     auto fold_round = [&](auto esel) __attribute__((always_inline)) {
         constexpr int e = decltype(esel)::value;
         using H0 = std::integral_constant<int, 0>;

@@ -30,6 +30,21 @@ __device__ __forceinline__ void copy16_to_lds(const void *base, unsigned off_byt
     asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_base_bytes), "v"(off_bytes), "s"(base) : "memory", "m0");
 }
 
+// The same copy with an immediate byte offset IMM in the instruction (13-bit signed field).  The hardware adds the field to
+// the global address AND to the LDS address: lane i reads base + off_bytes + IMM and lands at lds_base + LDS_ADD + IMM + 16 i.
+// LDS_ADD is a constant added while m0 is written (one scalar instruction either way): the destinations of a buffer's
+// pieces need ONE scalar register, not one each.
+template <int IMM, int LDS_ADD>
+__device__ __forceinline__ void copy16_to_lds_imm(const void *base, unsigned off_bytes, unsigned lds_base_bytes)
+{
+    static_assert(IMM >= 0 && IMM < 4096, "global_load_lds: 13-bit signed immediate offset");
+    static_assert(LDS_ADD >= 0 && LDS_ADD < 65536, "LDS byte offset");
+    if constexpr (LDS_ADD == 0)
+        asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%3" ::"s"(lds_base_bytes), "v"(off_bytes), "s"(base), "i"(IMM) : "memory", "m0");
+    else
+        asm volatile("s_add_u32 m0, %0, %4\n\tglobal_load_lds_dwordx4 %1, %2 offset:%3" ::"s"(lds_base_bytes), "v"(off_bytes), "s"(base), "i"(IMM), "i"(LDS_ADD) : "memory", "m0", "scc");
+}
+
 // Barrier that orders LDS accesses only: this wave's ds_writes are complete (lgkmcnt(0)) while global -> LDS copies,
 // global loads and global stores stay in flight.  __syncthreads() is a release fence over LDS, and a pending copy IS an
 // LDS store: it waits vmcnt(0).
