@@ -354,6 +354,7 @@ static int sgemm_launch(int transA, int transB, int M, int N, int K, const float
                         int accumulate, const uint8_t *emask, float einv, void *stream)
 {
     COVA_REQUIRE(A && B && C && M >= 0 && N >= 0 && K >= 0);
+    COVA_REQUIRE(lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N);      // a leading dimension shorter than its row
     if (M == 0 || N == 0) return COVA_OK;
     const dim3 grid(cdiv(N, BN), cdiv(M, BM));
     hipStream_t st = (hipStream_t)stream;

@@ -402,13 +402,17 @@ int cova_bbox_linear_bwd(const float *dz, const float *raw, float *dW, float *db
                          void *stream);
 
 /* ------------------------------------------------------------------ dense layers
- * replaces: nn.Linear forward/backward GEMMs (models.py:85,161-162): C (+)= op(A) op(B) (+ bias) */
+ * replaces: nn.Linear forward/backward GEMMs (models.py:85,161-162): C (+)= op(A) op(B) (+ bias)
+ * Row-major operands: A is [M,K] (transA = 0, lda >= K) or [K,M] (transA = 1, lda >= M), B is [K,N] (transB = 0, ldb >= N) or
+ * [N,K] (transB = 1, ldb >= K), C is [M,N] with ldc >= N.  A negative M, N or K, a null A, B or C and a leading dimension
+ * shorter than its operand's row are refused (COVA_ERR_BAD_ARG, nothing is launched); M == 0 or N == 0 returns 0 and writes
+ * nothing; K == 0 leaves C = bias (or 0), added to the old C under accumulate. */
 int cova_sgemm(int transA, int transB, int M, int N, int K, const float *A, int lda, const float *B,
                int ldb, float *C, int ldc, const float *bias /*nullable [N]*/, int accumulate,
                void *stream);
 /* cova_sgemm (no bias, no accumulate) with cova_dropout_bwd applied to its result in the epilogue:
  * C = keep ? op(A) op(B) / (1 - p) : 0, keep [M,N] uint8 contiguous -- the decoder's first Dropout backward
- * (models.py:84) behind the data gradient of decoder.1 (models.py:85); bit-identical to the two launches */
+ * (models.py:84) behind the data gradient of decoder.1 (models.py:85); bit-identical to the two launches.  cova_sgemm's refusals, and a null keep, p < 0 or p >= 1 */
 int cova_sgemm_dropout_bwd(int transA, int transB, int M, int N, int K, const float *A, int lda, const float *B,
                            int ldb, float *C, int ldc, const uint8_t *keep /*[M,N]*/, float p, void *stream);
 

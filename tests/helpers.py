@@ -15,7 +15,9 @@ DEV = "cuda:0"
 # ~5x the measured f32 round-off of logits (over the logit scale), the summed loss (relative) and every gradient (over its
 # tensor's scale, helpers.compare_grads).
 LOGIT_TOL, LOSS_TOL, GRAD_TOL = 5e-5, 2e-5, 1e-4
-# cova_sgemm against a float64 product, max error over max reference (tests/test_kernels_gpu.py)
+# cova_sgemm against a float64 product, max error over max reference (tests/test_kernels_gpu.py): a whole-matrix gate on
+# Gaussian operands, blind to a row or column of small magnitude.  The per-element gate -- exact on integer operands,
+# head_cases.sum_bound on scaled ones, every launch path -- lives in tests/test_gemm_paths_gpu.py (tests/gemm_cases.py).
 SGEMM_TOL = 2e-5
 GUARD = -7.0                               # the frame of framed(): no kernel under test produces it
 NAN = float("nan")
