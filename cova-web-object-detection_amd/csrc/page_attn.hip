@@ -51,6 +51,21 @@
 //     fold launch       per (a, e) one thread, from +0: pages ascending, inside a page its own tiles ascending (the blocks
 //                       behind the page's end hold zeros and are passed over: the sum's bits are the same)
 // No atomics, no host read: d w is bit-identical between reruns.  phi has no gradient (the boxes are data).
+//
+// The DROP instantiations (cova_page_attn_fwd_drop / cova_page_attn_bwd_drop and their _geo_ forms)
+// drop attention probabilities, torch's inverted dropout on A: rate p, inv = 1.f / (1.f - p), stream seed.  No mask is
+// stored.  The score of (query batch row i, head a, key batch row j) is kept when
+//   hash_uniform(seed, ((uint64)(i * Hh + a) << 32) | (uint64)j) >= p          (f32 compare; N * Hh < 2**32)
+// and all three kernels form that index from the same integers and call pa_dropped(): ONE rounded multiply v * inv on a
+// kept score, 0.f on a dropped one.  What DROP adds, every sum in its order above:
+//   forward, pass 2        l_i += p_ij as before (pass 1, m_i, l_i and lse_i keep the plain forward's bits); the V product
+//                          takes pa_dropped(p_ij): O_i = (sum_j D_ij inv p_ij V_j) / l_i
+//   both backward sides    dA_ij = pa_dropped(g_i . V_j) (the rounded product of the plain form, then the helper);
+//                          ds_ij = A_ij * (dA_ij - delta_i) with the undropped A_ij: a dropped score still takes
+//                          -A_ij delta_i through the softmax; delta_i = g_i . O_i holds with the dropped O
+//   key side               dV_j takes pa_dropped(A_ij)
+// A dropped score enters its sums as +0.  A row whose keys are all dropped has O = 0, delta = 0 and zero dqkv rows.
+// Everything DROP sits behind `if constexpr`: the other instantiations are what they were.
 #include "geometry.h"
 #include "mma.h"
 #include "rows.h"
@@ -220,11 +235,35 @@ __device__ __forceinline__ float pa_bias(const float4 qbox, const float4 kbox, f
     return b;
 }
 
-template <int DHB, bool GEO>
+// operands of the attention dropout; the other instantiations carry the empty form
+template <bool DROP>
+struct PaDrop {};
+
+template <>
+struct PaDrop<true> {
+    float p, inv;                          // rate, 1.f / (1.f - p)
+    unsigned long long seed;
+};
+
+// the mask word of (query batch row i, head a, key batch row j): the three kernels call this with the same integers
+__device__ __forceinline__ unsigned long long pa_drop_idx(int i, int Hh, int a, int j)
+{
+    return ((unsigned long long)((unsigned)i * (unsigned)Hh + (unsigned)a) << 32) | (unsigned long long)(unsigned)j;
+}
+
+// v * inv on a kept score, 0 on a dropped one: ONE rounded f32 multiply (never contracted into a neighbouring add), so the
+// forward and both sides of the backward form the same dropped value bit for bit (common.h: gat_dropped's statement)
+__device__ __forceinline__ float pa_dropped(const PaDrop<true> &dr, unsigned long long idx, float v)
+{
+    return hash_uniform(dr.seed, idx) >= dr.p ? __fmul_rn(v, dr.inv) : 0.f;
+}
+
+template <int DHB, bool GEO, bool DROP>
 __global__ __launch_bounds__(PA_THREADS) void pa_fwd_kernel(const float *__restrict__ qkv, int ldq,
                                                             const int64_t *__restrict__ page_start, int N, int E, int Hh,
                                                             int tiles, float *__restrict__ out, int ldo,
-                                                            float *__restrict__ lse, int vo, PaGeo<GEO> geo)
+                                                            float *__restrict__ lse, int vo, PaGeo<GEO> geo,
+                                                            PaDrop<DROP> dr)
 {
     using C = PaCfg<DHB>;
     __shared__ __attribute__((aligned(16))) float Ks[C::KT * C::LD];
@@ -295,8 +334,13 @@ __global__ __launch_bounds__(PA_THREADS) void pa_fwd_kernel(const float *__restr
                     const int o = sub * 16 + 4 * grp + r;
                     v = v + pa_bias(qbox, Bs[o], geo.W, geo.H, k0 + o - q, wt, phi);
                 }
-                pw[r] = k0 + sub * 16 + 4 * grp + r < n ? expf(v - m) : 0.f;
+                const bool kin = k0 + sub * 16 + 4 * grp + r < n;
+                pw[r] = kin ? expf(v - m) : 0.f;
                 l += pw[r];
+                if constexpr (DROP) {       // l keeps every key; the V product takes the dropped weight (a pair in range only)
+                    if (qok && kin)
+                        pw[r] = pa_dropped(dr, pa_drop_idx(b.base + q, Hh, b.head, b.base + k0 + sub * 16 + 4 * grp + r), pw[r]);
+                }
             }
             pa_acc<DHB>(Vs, sub, pw, acc, l16, grp);
         }
@@ -314,14 +358,14 @@ __global__ __launch_bounds__(PA_THREADS) void pa_fwd_kernel(const float *__restr
 }
 
 // query side of the backward: dQ_i = rs * sum_j ds_ij K_j, keys in ascending tiles
-template <int DHB, bool GEO>
+template <int DHB, bool GEO, bool DROP>
 __global__ __launch_bounds__(PA_THREADS) void pa_bwd_q_kernel(const float *__restrict__ g, int ldg,
                                                               const float *__restrict__ qkv, int ldq,
                                                               const float *__restrict__ out, int ldo,
                                                               const float *__restrict__ lse,
                                                               const int64_t *__restrict__ page_start, int N, int E, int Hh,
                                                               int tiles, float *__restrict__ dqkv, int lddq, int vg, int vo,
-                                                              int vd, PaGeo<GEO> geo)
+                                                              int vd, PaGeo<GEO> geo, PaDrop<DROP> dr)
 {
     using C = PaCfg<DHB>;
     __shared__ __attribute__((aligned(16))) float Ks[C::KT * C::LD];
@@ -380,7 +424,11 @@ __global__ __launch_bounds__(PA_THREADS) void pa_bwd_q_kernel(const float *__res
                     v = v + pa_bias(qbox, Bs[o], geo.W, geo.H, k0 + o - q, wt, phi);
                 }
                 const bool ok = qok && k0 + sub * 16 + 4 * grp + r < n;
-                ds[r] = ok ? expf(v - lse_q) * (dA[r] - delta) : 0.f;
+                float da = dA[r];
+                if constexpr (DROP) {       // (a pair in range only: ds is +0 elsewhere whatever da holds)
+                    if (ok) da = pa_dropped(dr, pa_drop_idx(b.base + q, Hh, b.head, b.base + k0 + sub * 16 + 4 * grp + r), da);
+                }
+                ds[r] = ok ? expf(v - lse_q) * (da - delta) : 0.f;
                 if constexpr (GEO) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) dw[e] = fmaf(ds[r], phi[e], dw[e]);
@@ -416,14 +464,14 @@ __global__ __launch_bounds__(PA_THREADS) void pa_bwd_q_kernel(const float *__res
 }
 
 // key side of the backward: dK_j = rs * sum_i ds_ij Q_i, dV_j = sum_i A_ij g_i, queries in ascending tiles
-template <int DHB, bool GEO>
+template <int DHB, bool GEO, bool DROP>
 __global__ __launch_bounds__(PA_THREADS) void pa_bwd_k_kernel(const float *__restrict__ g, int ldg,
                                                               const float *__restrict__ qkv, int ldq,
                                                               const float *__restrict__ out, int ldo,
                                                               const float *__restrict__ lse,
                                                               const int64_t *__restrict__ page_start, int N, int E, int Hh,
                                                               int tiles, float *__restrict__ dqkv, int lddq, int vg, int vo,
-                                                              int vd, PaGeo<GEO> geo)
+                                                              int vd, PaGeo<GEO> geo, PaDrop<DROP> dr)
 {
     using C = PaCfg<DHB>;
     __shared__ __attribute__((aligned(16))) float Qs[C::KT * C::LD];
@@ -488,7 +536,13 @@ __global__ __launch_bounds__(PA_THREADS) void pa_bwd_k_kernel(const float *__res
                     v = v + pa_bias(Bs[qi], kbox, geo.W, geo.H, k - (q0 + qi), wt, phi);
                 if (kok && q0 + qi < n) {
                     pw[r] = expf(v - lse_s[qi]);
-                    ds[r] = pw[r] * (dA[r] - del_s[qi]);
+                    if constexpr (DROP) {   // ds from the undropped A and the dropped dA; dV weighs with the dropped A
+                        const unsigned long long idx = pa_drop_idx(b.base + q0 + qi, Hh, b.head, b.base + k);
+                        ds[r] = pw[r] * (pa_dropped(dr, idx, dA[r]) - del_s[qi]);
+                        pw[r] = pa_dropped(dr, idx, pw[r]);
+                    } else {
+                        ds[r] = pw[r] * (dA[r] - del_s[qi]);
+                    }
                 } else {
                     pw[r] = ds[r] = 0.f;
                 }
@@ -538,20 +592,25 @@ __global__ __launch_bounds__(64) void pa_geo_fold_kernel(const float *__restrict
 
 }  // namespace
 
-#define PA_DISPATCH(KERNEL, GEO, ...)                                                                                      \
+#define PA_DISPATCH(KERNEL, GEO, DROP, ...)                                                                                \
     do {                                                                                                                   \
-        if (dh <= 16) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<1, GEO>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
-        else if (dh <= 32) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<2, GEO>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
-        else if (dh <= 64) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<4, GEO>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
-        else if (dh <= 96) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<6, GEO>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<8, GEO>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__);       \
+        if (dh <= 16) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<1, GEO, DROP>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
+        else if (dh <= 32) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<2, GEO, DROP>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
+        else if (dh <= 64) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<4, GEO, DROP>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
+        else if (dh <= 96) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<6, GEO, DROP>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<8, GEO, DROP>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__);       \
         COVA_LAUNCH_CHECK();                                                                                               \
     } while (0)
 
-// the checks and launches both forms share; the GEO entry points check their own operands first
-template <bool GEO>
+// 0 < p < 1 (a NaN fails both compares) and every mask index within its 32 + 32 bits
+static bool pa_drop_ok(float p, int N, int Hh) { return p > 0.f && p < 1.f && (long long)N * Hh < (1LL << 32); }
+
+static PaDrop<true> pa_drop_of(float p, unsigned long long seed) { return PaDrop<true>{p, 1.f / (1.f - p), seed}; }
+
+// the checks and launches every form shares; the GEO and DROP entry points check their own operands first
+template <bool GEO, bool DROP>
 static int pa_fwd(const float *qkv, int ldq, const int64_t *page_start, int B, int N, int E, int Hh, float *out, int ldo,
-                  float *lse, PaGeo<GEO> geo, void *stream)
+                  float *lse, PaGeo<GEO> geo, PaDrop<DROP> dr, void *stream)
 {
     COVA_REQUIRE(pa_shape_ok(B, N, E, Hh) && ldq >= 3 * E && ldo >= E);
     if (N == 0 || B == 0) return COVA_OK;
@@ -560,14 +619,14 @@ static int pa_fwd(const float *qkv, int ldq, const int64_t *page_start, int B, i
     const int dh = E / Hh, tiles = cdiv(N, PA_OWN), blocks = B * Hh * tiles;
     const int vo = vec4_ok(out, ldo);
     hipStream_t st = (hipStream_t)stream;
-    PA_DISPATCH(pa_fwd_kernel, GEO, qkv, ldq, page_start, N, E, Hh, tiles, out, ldo, lse, vo, geo);
+    PA_DISPATCH(pa_fwd_kernel, GEO, DROP, qkv, ldq, page_start, N, E, Hh, tiles, out, ldo, lse, vo, geo, dr);
     return COVA_OK;
 }
 
-template <bool GEO>
+template <bool GEO, bool DROP>
 static int pa_bwd(const float *g, int ldg, const float *qkv, int ldq, const float *out, int ldo, const float *lse,
                   const int64_t *page_start, int B, int N, int E, int Hh, float *dqkv, int lddq, PaGeo<GEO> geo,
-                  void *stream)
+                  PaDrop<DROP> dr, void *stream)
 {
     COVA_REQUIRE(pa_shape_ok(B, N, E, Hh) && ldg >= E && ldq >= 3 * E && ldo >= E && lddq >= 3 * E);
     if (N == 0 || B == 0) return COVA_OK;
@@ -576,24 +635,25 @@ static int pa_bwd(const float *g, int ldg, const float *qkv, int ldq, const floa
     const int dh = E / Hh, tiles = cdiv(N, PA_OWN), blocks = B * Hh * tiles;
     const int vg = vec4_ok(g, ldg), vo = vec4_ok(out, ldo), vd = vec4_ok(dqkv, lddq);
     hipStream_t st = (hipStream_t)stream;
-    PA_DISPATCH(pa_bwd_q_kernel, GEO, g, ldg, qkv, ldq, out, ldo, lse, page_start, N, E, Hh, tiles, dqkv, lddq, vg, vo, vd,
-                geo);
-    PA_DISPATCH(pa_bwd_k_kernel, GEO, g, ldg, qkv, ldq, out, ldo, lse, page_start, N, E, Hh, tiles, dqkv, lddq, vg, vo, vd,
-                geo);
+    PA_DISPATCH(pa_bwd_q_kernel, GEO, DROP, g, ldg, qkv, ldq, out, ldo, lse, page_start, N, E, Hh, tiles, dqkv, lddq, vg, vo,
+                vd, geo, dr);
+    PA_DISPATCH(pa_bwd_k_kernel, GEO, DROP, g, ldg, qkv, ldq, out, ldo, lse, page_start, N, E, Hh, tiles, dqkv, lddq, vg, vo,
+                vd, geo, dr);
     return COVA_OK;
 }
 
 COVA_API int cova_page_attn_fwd(const float *qkv, int ldq, const int64_t *page_start, int B, int N, int E, int Hh, float *out,
                                 int ldo, float *lse, void *stream)
 {
-    return pa_fwd<false>(qkv, ldq, page_start, B, N, E, Hh, out, ldo, lse, PaGeo<false>{}, stream);
+    return pa_fwd<false, false>(qkv, ldq, page_start, B, N, E, Hh, out, ldo, lse, PaGeo<false>{}, PaDrop<false>{}, stream);
 }
 
 COVA_API int cova_page_attn_bwd(const float *g, int ldg, const float *qkv, int ldq, const float *out, int ldo,
                                 const float *lse, const int64_t *page_start, int B, int N, int E, int Hh, float *dqkv,
                                 int lddq, void *stream)
 {
-    return pa_bwd<false>(g, ldg, qkv, ldq, out, ldo, lse, page_start, B, N, E, Hh, dqkv, lddq, PaGeo<false>{}, stream);
+    return pa_bwd<false, false>(g, ldg, qkv, ldq, out, ldo, lse, page_start, B, N, E, Hh, dqkv, lddq, PaGeo<false>{},
+                                PaDrop<false>{}, stream);
 }
 
 COVA_API int cova_page_attn_geo_workspace_floats(int B, int N, int Hh)
@@ -603,16 +663,46 @@ COVA_API int cova_page_attn_geo_workspace_floats(int B, int N, int Hh)
     return v <= 0x7fffffffLL ? (int)v : 0;
 }
 
-COVA_API int cova_page_attn_fwd_geo(const float *qkv, int ldq, const int64_t *page_start, const float *bboxes,
-                                    const float *geo_w, float img_w, float img_h, int B, int N, int E, int Hh, float *out,
-                                    int ldo, float *lse, void *stream)
+// the GEO entry points' own checks and launches, with and without DROP
+template <bool DROP>
+static int pa_fwd_geo(const float *qkv, int ldq, const int64_t *page_start, const float *bboxes, const float *geo_w,
+                      float img_w, float img_h, int B, int N, int E, int Hh, float *out, int ldo, float *lse, PaDrop<DROP> dr,
+                      void *stream)
 {
     COVA_REQUIRE(img_w > 0.f && img_h > 0.f);
     if (N > 0 && B > 0) {
         COVA_REQUIRE(bboxes && geo_w);
     }
-    return pa_fwd<true>(qkv, ldq, page_start, B, N, E, Hh, out, ldo, lse, PaGeo<true>{bboxes, geo_w, img_w, img_h, nullptr},
-                        stream);
+    return pa_fwd<true, DROP>(qkv, ldq, page_start, B, N, E, Hh, out, ldo, lse,
+                              PaGeo<true>{bboxes, geo_w, img_w, img_h, nullptr}, dr, stream);
+}
+
+template <bool DROP>
+static int pa_bwd_geo(const float *g, int ldg, const float *qkv, int ldq, const float *out, int ldo, const float *lse,
+                      const int64_t *page_start, const float *bboxes, const float *geo_w, float img_w, float img_h, int B,
+                      int N, int E, int Hh, float *dqkv, int lddq, float *d_geo_w, float *workspace, PaDrop<DROP> dr,
+                      void *stream)
+{
+    COVA_REQUIRE(img_w > 0.f && img_h > 0.f);
+    if (N > 0 && B > 0) {
+        COVA_REQUIRE(bboxes && geo_w && d_geo_w && workspace);
+        COVA_REQUIRE(Hh < 1 || cova_page_attn_geo_workspace_floats(B, N, Hh) > 0);      // the workspace's size fits an int
+    }
+    const int rc = pa_bwd<true, DROP>(g, ldg, qkv, ldq, out, ldo, lse, page_start, B, N, E, Hh, dqkv, lddq,
+                                      PaGeo<true>{bboxes, geo_w, img_w, img_h, workspace}, dr, stream);
+    if (rc != COVA_OK || N == 0 || B == 0) return rc;
+    hipLaunchKernelGGL(pa_geo_fold_kernel, dim3(cdiv(Hh * 8, 64)), dim3(64), 0, (hipStream_t)stream, workspace, page_start, B,
+                       N, Hh, cdiv(N, PA_OWN), d_geo_w);
+    COVA_LAUNCH_CHECK();
+    return COVA_OK;
+}
+
+COVA_API int cova_page_attn_fwd_geo(const float *qkv, int ldq, const int64_t *page_start, const float *bboxes,
+                                    const float *geo_w, float img_w, float img_h, int B, int N, int E, int Hh, float *out,
+                                    int ldo, float *lse, void *stream)
+{
+    return pa_fwd_geo<false>(qkv, ldq, page_start, bboxes, geo_w, img_w, img_h, B, N, E, Hh, out, ldo, lse, PaDrop<false>{},
+                             stream);
 }
 
 COVA_API int cova_page_attn_bwd_geo(const float *g, int ldg, const float *qkv, int ldq, const float *out, int ldo,
@@ -620,16 +710,43 @@ COVA_API int cova_page_attn_bwd_geo(const float *g, int ldg, const float *qkv, i
                                     float img_w, float img_h, int B, int N, int E, int Hh, float *dqkv, int lddq,
                                     float *d_geo_w, float *workspace, void *stream)
 {
-    COVA_REQUIRE(img_w > 0.f && img_h > 0.f);
-    if (N > 0 && B > 0) {
-        COVA_REQUIRE(bboxes && geo_w && d_geo_w && workspace);
-        COVA_REQUIRE(Hh < 1 || cova_page_attn_geo_workspace_floats(B, N, Hh) > 0);      // the workspace's size fits an int
-    }
-    const int rc = pa_bwd<true>(g, ldg, qkv, ldq, out, ldo, lse, page_start, B, N, E, Hh, dqkv, lddq,
-                                PaGeo<true>{bboxes, geo_w, img_w, img_h, workspace}, stream);
-    if (rc != COVA_OK || N == 0 || B == 0) return rc;
-    hipLaunchKernelGGL(pa_geo_fold_kernel, dim3(cdiv(Hh * 8, 64)), dim3(64), 0, (hipStream_t)stream, workspace, page_start, B,
-                       N, Hh, cdiv(N, PA_OWN), d_geo_w);
-    COVA_LAUNCH_CHECK();
-    return COVA_OK;
+    return pa_bwd_geo<false>(g, ldg, qkv, ldq, out, ldo, lse, page_start, bboxes, geo_w, img_w, img_h, B, N, E, Hh, dqkv, lddq,
+                             d_geo_w, workspace, PaDrop<false>{}, stream);
+}
+
+// ---- attention dropout: the pairs above on the DROP instantiations, 0 < p < 1
+COVA_API int cova_page_attn_fwd_drop(const float *qkv, int ldq, const int64_t *page_start, int B, int N, int E, int Hh,
+                                     float *out, int ldo, float *lse, float p, unsigned long long seed, void *stream)
+{
+    COVA_REQUIRE(pa_drop_ok(p, N, Hh));
+    return pa_fwd<false, true>(qkv, ldq, page_start, B, N, E, Hh, out, ldo, lse, PaGeo<false>{}, pa_drop_of(p, seed), stream);
+}
+
+COVA_API int cova_page_attn_bwd_drop(const float *g, int ldg, const float *qkv, int ldq, const float *out, int ldo,
+                                     const float *lse, const int64_t *page_start, int B, int N, int E, int Hh, float *dqkv,
+                                     int lddq, float p, unsigned long long seed, void *stream)
+{
+    COVA_REQUIRE(pa_drop_ok(p, N, Hh));
+    return pa_bwd<false, true>(g, ldg, qkv, ldq, out, ldo, lse, page_start, B, N, E, Hh, dqkv, lddq, PaGeo<false>{},
+                               pa_drop_of(p, seed), stream);
+}
+
+COVA_API int cova_page_attn_fwd_geo_drop(const float *qkv, int ldq, const int64_t *page_start, const float *bboxes,
+                                         const float *geo_w, float img_w, float img_h, int B, int N, int E, int Hh,
+                                         float *out, int ldo, float *lse, float p, unsigned long long seed, void *stream)
+{
+    COVA_REQUIRE(pa_drop_ok(p, N, Hh));
+    return pa_fwd_geo<true>(qkv, ldq, page_start, bboxes, geo_w, img_w, img_h, B, N, E, Hh, out, ldo, lse,
+                            pa_drop_of(p, seed), stream);
+}
+
+COVA_API int cova_page_attn_bwd_geo_drop(const float *g, int ldg, const float *qkv, int ldq, const float *out, int ldo,
+                                         const float *lse, const int64_t *page_start, const float *bboxes,
+                                         const float *geo_w, float img_w, float img_h, int B, int N, int E, int Hh,
+                                         float *dqkv, int lddq, float *d_geo_w, float *workspace, float p,
+                                         unsigned long long seed, void *stream)
+{
+    COVA_REQUIRE(pa_drop_ok(p, N, Hh));
+    return pa_bwd_geo<true>(g, ldg, qkv, ldq, out, ldo, lse, page_start, bboxes, geo_w, img_w, img_h, B, N, E, Hh, dqkv, lddq,
+                            d_geo_w, workspace, pa_drop_of(p, seed), stream);
 }

@@ -20,6 +20,15 @@
 //
 // GELU: elementwise, out = 0.5 z (1 + erff(z / sqrt 2)), dz = g (0.5 (1 + erff(z / sqrt 2)) + z expf(-z^2 / 2) / sqrt(2 pi));
 // float4 chunks under the same alignment rule, grid-stride.
+//
+// Dropout of the encoder's sites 1 to 3: torch's inverted dropout, rate p, inv = 1.f / (1.f - p), stream
+// seed.  Element (r, c) of an [R, C] operand is kept when hash_uniform(seed, r * C + c) >= p (f32 compare; the convention of
+// dropout_fwd_kernel); no mask is stored, the backward regenerates it from the same (seed, r * C + c).
+//   cova_gelu_fwd_drop       f  = keep ? gelu(z) * inv : 0        the DROP flag of the GELU forward; z stays the saved tensor
+//   cova_gelu_bwd_drop       dz = keep ? (g * inv) * gelu'(z) : 0 the DROP flag of the GELU backward
+//   cova_dropout_add_fwd     out = x + (keep ? y * inv : 0)       two roundings: the scaled value, then the residual add
+//   cova_dropout_regen_bwd   dy = keep ? g * inv : 0
+// Every `* inv` is one rounded multiply (__fmul_rn).  Same access rule and grid-stride launch as the GELU kernels.
 #include "rows.h"
 
 // the orders above count one rounding per written operation: only the fmaf calls fuse
@@ -218,9 +227,25 @@ constexpr float GELU_RSQRT2PI = 0.39894228040143267794f;    // 1 / sqrt(2 pi)
 
 __device__ __forceinline__ float gelu_cdf(float z) { return 0.5f * (1.f + erff(z * GELU_RSQRT2)); }
 
-template <int V>
+// operands of the row dropout; the plain instantiations carry the empty form
+template <bool DROP>
+struct RowDrop {};
+
+template <>
+struct RowDrop<true> {
+    float p, inv;                          // rate, 1.f / (1.f - p)
+    unsigned long long seed;
+};
+
+// element idx = r * C + c is kept: the forward and the regenerating backward ask with the same (seed, idx)
+__device__ __forceinline__ bool row_kept(const RowDrop<true> &dr, unsigned long long idx)
+{
+    return hash_uniform(dr.seed, idx) >= dr.p;
+}
+
+template <int V, bool DROP>
 __global__ __launch_bounds__(256) void gelu_fwd_kernel(const float *__restrict__ z, int ldz, long long R, int C,
-                                                       float *__restrict__ out, int ldo)
+                                                       float *__restrict__ out, int ldo, RowDrop<DROP> dr)
 {
     const int cpr = C / V;
     const long long total = R * cpr;
@@ -230,14 +255,18 @@ __global__ __launch_bounds__(256) void gelu_fwd_kernel(const float *__restrict__
         float a[V], o[V];
         ro_load<V>(z + (size_t)r * ldz + c, a);
 #pragma unroll
-        for (int v = 0; v < V; ++v) o[v] = a[v] * gelu_cdf(a[v]);
+        for (int v = 0; v < V; ++v) {
+            o[v] = a[v] * gelu_cdf(a[v]);
+            if constexpr (DROP) o[v] = row_kept(dr, (unsigned long long)r * C + c + v) ? __fmul_rn(o[v], dr.inv) : 0.f;
+        }
         ro_store<V>(out + (size_t)r * ldo + c, o);
     }
 }
 
-template <int V>
+template <int V, bool DROP>
 __global__ __launch_bounds__(256) void gelu_bwd_kernel(const float *__restrict__ g, int ldg, const float *__restrict__ z,
-                                                       int ldz, long long R, int C, float *__restrict__ dz, int lddz)
+                                                       int ldz, long long R, int C, float *__restrict__ dz, int lddz,
+                                                       RowDrop<DROP> dr)
 {
     const int cpr = C / V;
     const long long total = R * cpr;
@@ -248,9 +277,51 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const float *__restrict__
         ro_load<V>(z + (size_t)r * ldz + c, a);
         ro_load<V>(g + (size_t)r * ldg + c, gv);
 #pragma unroll
-        for (int v = 0; v < V; ++v)
-            o[v] = gv[v] * (gelu_cdf(a[v]) + a[v] * expf(-0.5f * a[v] * a[v]) * GELU_RSQRT2PI);
+        for (int v = 0; v < V; ++v) {
+            const float d = gelu_cdf(a[v]) + a[v] * expf(-0.5f * a[v] * a[v]) * GELU_RSQRT2PI;
+            if constexpr (DROP) o[v] = row_kept(dr, (unsigned long long)r * C + c + v) ? __fmul_rn(gv[v], dr.inv) * d : 0.f;
+            else o[v] = gv[v] * d;
+        }
         ro_store<V>(dz + (size_t)r * lddz + c, o);
+    }
+}
+
+// out = x + (keep ? y * inv : 0): the residual add behind a dropped sublayer output
+template <int V>
+__global__ __launch_bounds__(256) void dropout_add_fwd_kernel(const float *__restrict__ y, int ldy,
+                                                              const float *__restrict__ x, int ldx, long long R, int C,
+                                                              float *__restrict__ out, int ldo, RowDrop<true> dr)
+{
+    const int cpr = C / V;
+    const long long total = R * cpr;
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
+        const long long r = t / cpr;
+        const int c = (int)(t - r * cpr) * V;
+        float a[V], b[V], o[V];
+        ro_load<V>(y + (size_t)r * ldy + c, a);
+        ro_load<V>(x + (size_t)r * ldx + c, b);
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+            o[v] = b[v] + (row_kept(dr, (unsigned long long)r * C + c + v) ? __fmul_rn(a[v], dr.inv) : 0.f);
+        ro_store<V>(out + (size_t)r * ldo + c, o);
+    }
+}
+
+// dy = keep ? g * inv : 0 with the forward's mask regenerated
+template <int V>
+__global__ __launch_bounds__(256) void dropout_regen_bwd_kernel(const float *__restrict__ g, int ldg, long long R, int C,
+                                                                float *__restrict__ dy, int lddy, RowDrop<true> dr)
+{
+    const int cpr = C / V;
+    const long long total = R * cpr;
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
+        const long long r = t / cpr;
+        const int c = (int)(t - r * cpr) * V;
+        float a[V], o[V];
+        ro_load<V>(g + (size_t)r * ldg + c, a);
+#pragma unroll
+        for (int v = 0; v < V; ++v) o[v] = row_kept(dr, (unsigned long long)r * C + c + v) ? __fmul_rn(a[v], dr.inv) : 0.f;
+        ro_store<V>(dy + (size_t)r * lddy + c, o);
     }
 }
 
@@ -308,7 +379,8 @@ COVA_API int cova_layernorm_bwd(const float *g, int ldg, const float *x, int ldx
     return COVA_OK;
 }
 
-COVA_API int cova_gelu_fwd(const float *z, int ldz, long long R, int C, float *out, int ldo, void *stream)
+template <bool DROP>
+static int gelu_fwd(const float *z, int ldz, long long R, int C, float *out, int ldo, RowDrop<DROP> dr, void *stream)
 {
     COVA_REQUIRE(C >= 1 && R >= 0 && ldz >= C && ldo >= C);
     if (R == 0) return COVA_OK;
@@ -316,15 +388,18 @@ COVA_API int cova_gelu_fwd(const float *z, int ldz, long long R, int C, float *o
     const bool v4 = C % 4 == 0 && vec4_ok(z, ldz) && vec4_ok(out, ldo);
     hipStream_t st = (hipStream_t)stream;
     if (v4)
-        hipLaunchKernelGGL(gelu_fwd_kernel<4>, dim3(ew_grid(R * (C / 4))), dim3(256), 0, st, z, ldz, R, C, out, ldo);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(gelu_fwd_kernel<4, DROP>), dim3(ew_grid(R * (C / 4))), dim3(256), 0, st, z, ldz, R, C,
+                           out, ldo, dr);
     else
-        hipLaunchKernelGGL(gelu_fwd_kernel<1>, dim3(ew_grid(R * C)), dim3(256), 0, st, z, ldz, R, C, out, ldo);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(gelu_fwd_kernel<1, DROP>), dim3(ew_grid(R * C)), dim3(256), 0, st, z, ldz, R, C, out,
+                           ldo, dr);
     COVA_LAUNCH_CHECK();
     return COVA_OK;
 }
 
-COVA_API int cova_gelu_bwd(const float *g, int ldg, const float *z, int ldz, long long R, int C, float *dz, int lddz,
-                           void *stream)
+template <bool DROP>
+static int gelu_bwd(const float *g, int ldg, const float *z, int ldz, long long R, int C, float *dz, int lddz,
+                    RowDrop<DROP> dr, void *stream)
 {
     COVA_REQUIRE(C >= 1 && R >= 0 && ldg >= C && ldz >= C && lddz >= C);
     if (R == 0) return COVA_OK;
@@ -332,9 +407,78 @@ COVA_API int cova_gelu_bwd(const float *g, int ldg, const float *z, int ldz, lon
     const bool v4 = C % 4 == 0 && vec4_ok(g, ldg) && vec4_ok(z, ldz) && vec4_ok(dz, lddz);
     hipStream_t st = (hipStream_t)stream;
     if (v4)
-        hipLaunchKernelGGL(gelu_bwd_kernel<4>, dim3(ew_grid(R * (C / 4))), dim3(256), 0, st, g, ldg, z, ldz, R, C, dz, lddz);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(gelu_bwd_kernel<4, DROP>), dim3(ew_grid(R * (C / 4))), dim3(256), 0, st, g, ldg, z,
+                           ldz, R, C, dz, lddz, dr);
     else
-        hipLaunchKernelGGL(gelu_bwd_kernel<1>, dim3(ew_grid(R * C)), dim3(256), 0, st, g, ldg, z, ldz, R, C, dz, lddz);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(gelu_bwd_kernel<1, DROP>), dim3(ew_grid(R * C)), dim3(256), 0, st, g, ldg, z, ldz, R,
+                           C, dz, lddz, dr);
+    COVA_LAUNCH_CHECK();
+    return COVA_OK;
+}
+
+COVA_API int cova_gelu_fwd(const float *z, int ldz, long long R, int C, float *out, int ldo, void *stream)
+{
+    return gelu_fwd<false>(z, ldz, R, C, out, ldo, RowDrop<false>{}, stream);
+}
+
+COVA_API int cova_gelu_bwd(const float *g, int ldg, const float *z, int ldz, long long R, int C, float *dz, int lddz,
+                           void *stream)
+{
+    return gelu_bwd<false>(g, ldg, z, ldz, R, C, dz, lddz, RowDrop<false>{}, stream);
+}
+
+// 0 < p < 1: a NaN fails both compares
+static bool row_drop_ok(float p) { return p > 0.f && p < 1.f; }
+
+static RowDrop<true> row_drop_of(float p, unsigned long long seed) { return RowDrop<true>{p, 1.f / (1.f - p), seed}; }
+
+COVA_API int cova_gelu_fwd_drop(const float *z, int ldz, long long R, int C, float *out, int ldo, float p,
+                                unsigned long long seed, void *stream)
+{
+    COVA_REQUIRE(row_drop_ok(p));
+    return gelu_fwd<true>(z, ldz, R, C, out, ldo, row_drop_of(p, seed), stream);
+}
+
+COVA_API int cova_gelu_bwd_drop(const float *g, int ldg, const float *z, int ldz, long long R, int C, float *dz, int lddz,
+                                float p, unsigned long long seed, void *stream)
+{
+    COVA_REQUIRE(row_drop_ok(p));
+    return gelu_bwd<true>(g, ldg, z, ldz, R, C, dz, lddz, row_drop_of(p, seed), stream);
+}
+
+COVA_API int cova_dropout_add_fwd(const float *y, int ldy, const float *x, int ldx, float *out, int ldo, long long R, int C,
+                                  float p, unsigned long long seed, void *stream)
+{
+    COVA_REQUIRE(row_drop_ok(p) && C >= 1 && R >= 0 && ldy >= C && ldx >= C && ldo >= C);
+    if (R == 0) return COVA_OK;
+    COVA_REQUIRE(y && x && out && out != y && out != x);
+    const bool v4 = C % 4 == 0 && vec4_ok(y, ldy) && vec4_ok(x, ldx) && vec4_ok(out, ldo);
+    const RowDrop<true> dr = row_drop_of(p, seed);
+    hipStream_t st = (hipStream_t)stream;
+    if (v4)
+        hipLaunchKernelGGL(dropout_add_fwd_kernel<4>, dim3(ew_grid(R * (C / 4))), dim3(256), 0, st, y, ldy, x, ldx, R, C, out,
+                           ldo, dr);
+    else
+        hipLaunchKernelGGL(dropout_add_fwd_kernel<1>, dim3(ew_grid(R * C)), dim3(256), 0, st, y, ldy, x, ldx, R, C, out, ldo,
+                           dr);
+    COVA_LAUNCH_CHECK();
+    return COVA_OK;
+}
+
+COVA_API int cova_dropout_regen_bwd(const float *g, int ldg, float *dy, int lddy, long long R, int C, float p,
+                                    unsigned long long seed, void *stream)
+{
+    COVA_REQUIRE(row_drop_ok(p) && C >= 1 && R >= 0 && ldg >= C && lddy >= C);
+    if (R == 0) return COVA_OK;
+    COVA_REQUIRE(g && dy && g != dy);
+    const bool v4 = C % 4 == 0 && vec4_ok(g, ldg) && vec4_ok(dy, lddy);
+    const RowDrop<true> dr = row_drop_of(p, seed);
+    hipStream_t st = (hipStream_t)stream;
+    if (v4)
+        hipLaunchKernelGGL(dropout_regen_bwd_kernel<4>, dim3(ew_grid(R * (C / 4))), dim3(256), 0, st, g, ldg, R, C, dy, lddy,
+                           dr);
+    else
+        hipLaunchKernelGGL(dropout_regen_bwd_kernel<1>, dim3(ew_grid(R * C)), dim3(256), 0, st, g, ldg, R, C, dy, lddy, dr);
     COVA_LAUNCH_CHECK();
     return COVA_OK;
 }

@@ -27,8 +27,12 @@ BN_MOMENTUM, BN_EPS, LEAKY_SLOPE = 0.1, 1e-5, 0.2   # nn.BatchNorm defaults; mod
 # An eval-mode BatchNorm normalises with its running statistics and leaves its buffers alone; an eval-mode Dropout is the
 # identity.  A model built with ``attention_dropout`` > 0 also names the Dropout of every attention head, "<head prefix>attn_drop"
 # ("gat.attn_drop", "gat.layers.0.heads.1.attn_drop": ATTN_DROP_KEY behind weights.gat_prefixes).
+# A model built with ``page_attention_dropout`` / ``page_encoder_dropout`` > 0 names the one Dropout of that layer:
+# PAGE_ATTN_DROP_KEY / PAGE_ENC_DROP_KEY.
 DROPOUT_KEYS = ("decoder.0", "decoder.3")
 ATTN_DROP_KEY = "attn_drop"
+PAGE_ATTN_DROP_KEY = "page_attention.attn_drop"
+PAGE_ENC_DROP_KEY = "page_encoder.drop"
 
 
 def is_train(training, key):
@@ -1350,6 +1354,40 @@ def attention_dropout_seed(base, layer, head):
     return (layer + 1) << 56 | (head + 1) << 48 | base
 
 
+PAGE_DROP_SITES = 4         # of an encoder layer: attention probabilities, drop1, the FFN hidden activations, drop2
+
+
+def page_dropout_seed(base, layer, site):
+    """Stream of dropout site ``site`` of page layer ``layer`` in the step whose decoder Dropouts draw from ``base`` and
+    ``base + 1``: ``1 << 63 | (layer + 1) << 56 | (site + 1) << 48 | base``.  Encoder layer l is ``layer = l`` with the sites
+    0 attention probabilities, 1 drop1 (the attention sublayer's output), 2 the FFN hidden activations, 3 drop2 (the FFN's
+    output); the stand-alone page attention is ``layer = weights.PAGE_ENCODER_MAX_LAYERS``, ``site = 0``.
+    Every ``base`` is below 2**48 (dropout_base), so the decoder streams ``base`` and ``base + 1`` are at most 2**48, and an
+    attention_dropout_seed stream is below 127 << 56 | 255 << 48 | 2**48 < 2**63: bit 63 is clear in all of them and set in
+    every page stream, so no page stream is a decoder or a GAT attention stream of any step or seed.  (layer + 1) <= 9 fits
+    the bits 56 .. 62 and (site + 1) <= 4 the bits 48 .. 55, so two page streams are equal only for equal (base, layer,
+    site).  The counter hash finalises ``seed + golden * (idx + 1)`` with full avalanche (attention_dropout_seed says
+    so): streams that differ in high bits only are unrelated."""
+    from .weights import PAGE_ENCODER_MAX_LAYERS
+    base, layer, site = int(base), int(layer), int(site)
+    if not (0 <= base < 1 << 48 and 0 <= layer <= PAGE_ENCODER_MAX_LAYERS and 0 <= site < PAGE_DROP_SITES):
+        raise ValueError("page_dropout_seed: base in [0, 2**48), layer in [0, %d], site in [0, %d); got %r"
+                         % (PAGE_ENCODER_MAX_LAYERS, PAGE_DROP_SITES, (base, layer, site)))
+    return 1 << 63 | (layer + 1) << 56 | (site + 1) << 48 | base
+
+
+def check_page_drop(drop, option="page dropout"):
+    """``drop`` of the page attention core -> (p, seed) with p in (0, 1), or None when there is nothing to drop."""
+    if drop is None:
+        return None
+    from .weights import check_page_dropout
+    p, seed = drop
+    p, seed = check_page_dropout(p, option), int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("%s seed must fit 64 unsigned bits, got %r" % (option, seed))
+    return (p, seed) if p > 0.0 else None
+
+
 def check_gat_drop(drop):
     """``drop`` of gat_fwd -> (p, seed) with p in (0, 1), or None when there is nothing to drop (None, or p == 0)."""
     if drop is None:
@@ -1615,46 +1653,70 @@ def _page_geometry(bboxes, N, page_size, what):
     return bboxes, img_w, img_h
 
 
-def _page_attn_core_fwd(qkv, ld, width, heads, page_start, geo, out, ldo, what=""):
-    """cova_page_attn_fwd(_geo) on the rows [Q | K | V] at qkv + n*ld -> lse [N, heads]; the output rows go to
+# ``drop`` = (p, seed) with p in (0, 1) puts dropout on the probabilities (the _drop kernels), None leaves it off: four
+# kernel pairs, picked by (geo, drop).
+def _page_attn_core_fwd(qkv, ld, width, heads, page_start, geo, out, ldo, what="", drop=None):
+    """cova_page_attn_fwd(_geo)(_drop) on the rows [Q | K | V] at qkv + n*ld -> lse [N, heads]; the output rows go to
     out + n*ldo (``width`` columns).  Rows outside every page are written by neither kernel."""
     N, B = qkv.shape[0], page_start.shape[0] - 1
     lse = _empty((N, heads), qkv)
+    drop = check_page_drop(drop)                       # (a hand-made (p, seed) is held to the rule here, as gat_fwd's is)
+    tail = () if drop is None else drop
     if geo is None:
-        call("cova_page_attn_fwd", qkv, ld, page_start, B, N, width, heads, out, ldo, lse)
+        call("cova_page_attn_fwd_drop" if tail else "cova_page_attn_fwd", qkv, ld, page_start, B, N, width, heads, out, ldo,
+             lse, *tail)
         return lse
     gw, bboxes, img_w, img_h = geo
     if tuple(gw.shape) != (heads, 8):
         raise ValueError("%sgeometry.weight %s does not fit %d heads" % (what, tuple(gw.shape), heads))
-    call("cova_page_attn_fwd_geo", qkv, ld, page_start, bboxes, gw, img_w, img_h, B, N, width, heads, out, ldo, lse)
+    call("cova_page_attn_fwd_geo_drop" if tail else "cova_page_attn_fwd_geo", qkv, ld, page_start, bboxes, gw, img_w, img_h,
+         B, N, width, heads, out, ldo, lse, *tail)
     return lse
 
 
-def _page_attn_core_bwd(g, ldg, qkv, ld, out, ldo, lse, width, heads, page_start, geo, dgeo):
-    """cova_page_attn_bwd(_geo) -> dqkv [N, 3 width]; with ``geo`` the geometry weight's gradient goes to ``dgeo`` (the
-    kernel's workspace comes from the allocator).  dqkv is allocated here, as ZEROS: the kernels write the rows inside
-    pages only, and both callers run GEMMs over all N rows of it."""
+def _page_attn_core_bwd(g, ldg, qkv, ld, out, ldo, lse, width, heads, page_start, geo, dgeo, drop=None):
+    """cova_page_attn_bwd(_geo)(_drop) -> dqkv [N, 3 width]; with ``geo`` the geometry weight's gradient goes to ``dgeo``
+    (the kernel's workspace comes from the allocator); ``drop`` is the forward's.  dqkv is allocated here, as ZEROS: the
+    kernels write the rows inside pages only, and both callers run GEMMs over all N rows of it."""
     N, B = qkv.shape[0], page_start.shape[0] - 1
     dqkv = torch.zeros((N, 3 * width), dtype=torch.float32, device=g.device)
+    tail = () if drop is None else (float(drop[0]), int(drop[1]))
     if geo is None:
-        call("cova_page_attn_bwd", g, ldg, qkv, ld, out, ldo, lse, page_start, B, N, width, heads, dqkv, 3 * width)
+        call("cova_page_attn_bwd_drop" if tail else "cova_page_attn_bwd", g, ldg, qkv, ld, out, ldo, lse, page_start, B, N,
+             width, heads, dqkv, 3 * width, *tail)
         return dqkv
     gw, bboxes, img_w, img_h = geo
     ws = _empty((query("cova_page_attn_geo_workspace_floats", B, N, heads),), g)
-    call("cova_page_attn_bwd_geo", g, ldg, qkv, ld, out, ldo, lse, page_start, bboxes, gw, img_w, img_h, B, N, width,
-         heads, dqkv, 3 * width, dgeo, ws)
+    call("cova_page_attn_bwd_geo_drop" if tail else "cova_page_attn_bwd_geo", g, ldg, qkv, ld, out, ldo, lse, page_start,
+         bboxes, gw, img_w, img_h, B, N, width, heads, dqkv, 3 * width, dgeo, ws, *tail)
     return dqkv
 
 
+def _page_drop_rate(dropout, option, training, key):
+    """The rate a page layer drops at in this call: the checked ``dropout`` while its Dropout ``key`` is in train mode
+    (is_train), else 0.0 (the plain launches)."""
+    from .weights import check_page_dropout
+    p = check_page_dropout(dropout, option)
+    return p if p > 0.0 and is_train(training, key) else 0.0
+
+
 def page_attn_fwd(h, ldh, N, F, page_start, params, heads, out, ldo, prefix="page_attention.", bboxes=None,
-                  page_size=None):
+                  page_size=None, dropout=0.0, seed_base=0, training=True):
     """The page self-attention (cova_page_attn_fwd): [Q | K | V] = h qkv.weight^T by cova_sgemm, then per page and head the
     softmax of Q_i . K_j / sqrt(dh) over ALL rows j of the page and O_i = sum_j A_ij V_j, written to the rows out + n*ldo
     (E columns).  h rows at h + n*ldh (F values); ``page_start`` device int64 [B + 1].  -> saved dict for page_attn_bwd
     (qkv, lse [N, heads] and the output's place: the probabilities are recomputed).
     With ``geometry.weight`` [heads, 8] among the parameters the scores carry the box-geometry bias
-    (cova_page_attn_fwd_geo): ``bboxes`` [N, 5] and ``page_size`` = (height, width) in pixels are then required."""
+    (cova_page_attn_fwd_geo): ``bboxes`` [N, 5] and ``page_size`` = (height, width) in pixels are then required.
+    ``dropout`` > 0 (``page_attention_dropout``): while the layer's Dropout is in train mode (``training``: a bool
+    or per-layer modes, key PAGE_ATTN_DROP_KEY) the probabilities are dropped from the stream
+    page_dropout_seed(``seed_base``, weights.PAGE_ENCODER_MAX_LAYERS, 0) (cova_page_attn_fwd_drop / _geo_drop; ``seed_base``
+    is the step's first decoder seed); the saved dict carries (p, seed) as ``drop`` for page_attn_bwd.  With 0, or in eval
+    mode, exactly the calls above are issued."""
+    from .weights import PAGE_ATTENTION_DROPOUT_OPTION, PAGE_ENCODER_MAX_LAYERS
     _check(page_start, torch.int64)
+    p_drop = _page_drop_rate(dropout, PAGE_ATTENTION_DROPOUT_OPTION, training, PAGE_ATTN_DROP_KEY)
+    drop = (p_drop, page_dropout_seed(seed_base, PAGE_ENCODER_MAX_LAYERS, 0)) if p_drop > 0.0 else None
     W = params[prefix + "qkv.weight"]
     E, B = W.shape[0] // 3, page_start.shape[0] - 1
     if W.shape[1] != F or W.shape[0] != 3 * E or E < 1:
@@ -1663,9 +1725,9 @@ def page_attn_fwd(h, ldh, N, F, page_start, params, heads, out, ldo, prefix="pag
     geo = None if gw is None else (gw,) + _page_geometry(bboxes, N, page_size, prefix + "geometry.weight")
     qkv = _empty((N, 3 * E), h)
     call("cova_sgemm", 0, 1, N, 3 * E, F, h, ldh, W, F, qkv, 3 * E, None, 0)
-    lse = _page_attn_core_fwd(qkv, 3 * E, E, heads, page_start, geo, out, ldo, prefix)
+    lse = _page_attn_core_fwd(qkv, 3 * E, E, heads, page_start, geo, out, ldo, prefix, drop)
     sv = dict(h=h, ldh=ldh, N=N, F=F, E=E, B=B, heads=heads, qkv=qkv, lse=lse, out=out, ldo=ldo, page_start=page_start,
-              prefix=prefix)
+              prefix=prefix, drop=drop)
     if geo is not None:
         sv.update(bboxes=bboxes, img_w=geo[2], img_h=geo[3])
     return sv
@@ -1685,7 +1747,7 @@ def page_attn_bwd(sv, g, ldg, params, dh, lddh, gout=None):
     if geo is not None:
         grads[prefix + "geometry.weight"] = _gbuf(gout, prefix + "geometry.weight", (sv["heads"], 8), g)
     dqkv = _page_attn_core_bwd(g, ldg, sv["qkv"], 3 * E, sv["out"], sv["ldo"], sv["lse"], E, sv["heads"], sv["page_start"],
-                               geo, grads.get(prefix + "geometry.weight"))
+                               geo, grads.get(prefix + "geometry.weight"), sv.get("drop"))
     grads[prefix + "qkv.weight"] = dW = _gbuf(gout, prefix + "qkv.weight", (3 * E, F), g)
     _linear_bwd(dqkv, 3 * E, sv["h"], sv["ldh"], params[prefix + "qkv.weight"], N, 3 * E, F, None, dW, dh, lddh, True)
     return grads
@@ -1711,18 +1773,28 @@ def layernorm_bwd(g, ldg, x, ldx, mean, rstd, weight, N, C, res, dx, lddx, dweig
 
 
 def page_encoder_fwd(h, ldh, N, F, page_start, params, heads, layers, out, ldo, prefix="page_encoder.", bboxes=None,
-                     page_size=None):
+                     page_size=None, dropout=0.0, seed_base=0, training=True):
     """The page encoder: x = h input.weight^T, then ``layers`` pre-LN transformer blocks restricted to pages,
         a = LN1(x); qkv = a qkv.weight^T; O = page attention of qkv; x += O out.weight^T + out.bias
         m = LN2(x); z = m ffn1.weight^T + ffn1.bias; f = GELU(z); x += f ffn2.weight^T + ffn2.bias
     and the final LN, written to the rows out + n*ldo (P columns).  The GEMMs are cova_sgemm (a residual add is its bias +
     accumulate form into a copy of the stream), the attention is cova_page_attn_fwd on the layer's qkv, or with
     ``geometry.weight`` [heads, 8] among a layer's parameters cova_page_attn_fwd_geo (``bboxes`` [N, 5] and ``page_size`` =
-    (height, width) are then required); LayerNorm and GELU are cova_layernorm_fwd / cova_gelu_fwd.  There is no dropout in
-    the encoder; attention_dropout and edge_geometry belong to the GAT and do not reach it.
+    (height, width) are then required); LayerNorm and GELU are cova_layernorm_fwd / cova_gelu_fwd.  attention_dropout and
+    edge_geometry belong to the GAT and do not reach the encoder.
+    ``dropout`` = p > 0 (``page_encoder_dropout``; torch's ``dropout=`` of nn.TransformerEncoderLayer): while the
+    encoder's Dropout is in train mode (``training``: a bool or per-layer modes, key PAGE_ENC_DROP_KEY) every block runs
+        x += drop1(out(Attn_drop(qkv(LN1(x)))));   x += drop2(ffn2(drop_h(GELU(ffn1(LN2(x))))))
+    with layer l's four sites on the streams page_dropout_seed(``seed_base``, l, 0..3) (``seed_base``: the step's first
+    decoder seed): the attention runs the _drop kernels, GELU is cova_gelu_fwd_drop, and each sublayer GEMM writes its
+    output ``y`` (bias form) for cova_dropout_add_fwd, which stands in for the copy + accumulate pair.  No mask is stored;
+    the saved dict carries ``drop`` = p and ``seed_base``.  With 0, or in eval mode, exactly the calls above are issued.
     h rows at h + n*ldh (F values); ``page_start`` device int64 [B + 1].  -> saved dict for page_encoder_bwd: per layer the
     stream ``x`` at both LayerNorm inputs with their ``mean`` / ``rstd`` and outputs, ``qkv``, ``lse``, ``O``, ``z``, ``f``."""
+    from .weights import PAGE_ENCODER_DROPOUT_OPTION
     _check(page_start, torch.int64)
+    p_drop = _page_drop_rate(dropout, PAGE_ENCODER_DROPOUT_OPTION, training, PAGE_ENC_DROP_KEY)
+    seeds = (lambda l: tuple(page_dropout_seed(seed_base, l, i) for i in range(PAGE_DROP_SITES))) if p_drop > 0.0 else None
     W_in = params[prefix + "input.weight"]
     P, B = W_in.shape[0], page_start.shape[0] - 1
     if W_in.shape[1] != F or P < 1:
@@ -1747,24 +1819,37 @@ def page_encoder_fwd(h, ldh, N, F, page_start, params, heads, layers, out, ldo, 
         # rows outside every page are written by no attention kernel: they stay zero
         b["O"] = O = torch.zeros((N, P), dtype=torch.float32, device=h.device)
         geo = None if geo_args is None else (params[p + "geometry.weight"],) + geo_args
-        b["lse"] = _page_attn_core_fwd(qkv, 3 * P, P, heads, page_start, geo, O, P, p)
+        sd = seeds(l) if seeds is not None else None
+        b["lse"] = _page_attn_core_fwd(qkv, 3 * P, P, heads, page_start, geo, O, P, p,
+                                       (p_drop, sd[0]) if sd is not None else None)
         x2 = _empty((N, P), h)
-        x2.copy_(x)                                   # (a device copy: the stream at LN1's input is kept for its backward)
-        call("cova_sgemm", 0, 1, N, P, P, O, P, params[p + "out.weight"], P, x2, P, params[p + "out.bias"], 1)
+        if sd is None:
+            x2.copy_(x)                               # (a device copy: the stream at LN1's input is kept for its backward)
+            call("cova_sgemm", 0, 1, N, P, P, O, P, params[p + "out.weight"], P, x2, P, params[p + "out.bias"], 1)
+        else:
+            y = _empty((N, P), h)
+            call("cova_sgemm", 0, 1, N, P, P, O, P, params[p + "out.weight"], P, y, P, params[p + "out.bias"], 0)
+            call("cova_dropout_add_fwd", y, P, x, P, x2, P, N, P, p_drop, sd[1])
         b["x2"] = x2
         b["m"] = m = _empty((N, P), h)
         b["mean2"], b["rstd2"] = layernorm_fwd(x2, P, N, P, params[p + "norm2.weight"], params[p + "norm2.bias"], m, P)
         b["z"] = z = _empty((N, M), h)
         call("cova_sgemm", 0, 1, N, M, P, m, P, W1, P, z, M, params[p + "ffn1.bias"], 0)
         b["f"] = f = _empty((N, M), h)
-        call("cova_gelu_fwd", z, M, N, M, f, M)
         x = _empty((N, P), h)
-        x.copy_(x2)
-        call("cova_sgemm", 0, 1, N, P, M, f, M, params[p + "ffn2.weight"], M, x, P, params[p + "ffn2.bias"], 1)
+        if sd is None:
+            call("cova_gelu_fwd", z, M, N, M, f, M)
+            x.copy_(x2)
+            call("cova_sgemm", 0, 1, N, P, M, f, M, params[p + "ffn2.weight"], M, x, P, params[p + "ffn2.bias"], 1)
+        else:
+            call("cova_gelu_fwd_drop", z, M, N, M, f, M, p_drop, sd[2])        # f: the dropped activations, ffn2's input
+            y = _empty((N, P), h)
+            call("cova_sgemm", 0, 1, N, P, M, f, M, params[p + "ffn2.weight"], M, y, P, params[p + "ffn2.bias"], 0)
+            call("cova_dropout_add_fwd", y, P, x2, P, x, P, N, P, p_drop, sd[3])
         blocks.append(b)
     mean, rstd = layernorm_fwd(x, P, N, P, params[prefix + "norm.weight"], params[prefix + "norm.bias"], out, ldo)
     sv = dict(h=h, ldh=ldh, N=N, F=F, P=P, B=B, heads=heads, layers=layers, blocks=blocks, x=x, mean=mean, rstd=rstd,
-              page_start=page_start, prefix=prefix)
+              page_start=page_start, prefix=prefix, drop=p_drop, seed_base=seed_base)
     if geo_args is not None:
         sv.update(bboxes=bboxes, img_w=geo_args[1], img_h=geo_args[2])
     return sv
@@ -1773,9 +1858,13 @@ def page_encoder_fwd(h, ldh, N, F, page_start, params, heads, layers, out, ldo, 
 def page_encoder_bwd(sv, g, ldg, params, dh, lddh, gout=None):
     """g = dL/d(encoder columns) (rows at g + n*ldg).  Walks the blocks backwards: per Linear _linear_bwd (cova_colsum for
     out.bias / ffn1.bias / ffn2.bias, the two cova_sgemm), cova_gelu_bwd, the attention core's backward and
-    cova_layernorm_bwd with ``res`` = the stream gradient, which is so read and written once per LayerNorm.  ACCUMULATES
-    dL/dh into dh; returns every parameter gradient."""
+    cova_layernorm_bwd with ``res`` = the stream gradient, which is so read and written once per LayerNorm.  Where the
+    forward dropped (``drop`` > 0 in the saved dict) each sublayer's _linear_bwd is fed with cova_dropout_regen_bwd's
+    output instead of the stream gradient, GELU's backward is cova_gelu_bwd_drop and the attention core takes the
+    forward's (p, seed): every mask is regenerated from the forward's streams.  ACCUMULATES dL/dh into dh; returns every
+    parameter gradient."""
     N, F, P, Hh, prefix = sv["N"], sv["F"], sv["P"], sv["heads"], sv["prefix"]
+    p_drop = sv.get("drop", 0.0)
     grads = {}
 
     def buf(key, shape):
@@ -1785,14 +1874,22 @@ def page_encoder_bwd(sv, g, ldg, params, dh, lddh, gout=None):
     gx = _empty((N, P), g)                 # the gradient on the residual stream
     layernorm_bwd(g, ldg, sv["x"], P, sv["mean"], sv["rstd"], params[prefix + "norm.weight"], N, P, None, gx, P,
                   buf(prefix + "norm.weight", (P,)), buf(prefix + "norm.bias", (P,)))
-    for b in reversed(sv["blocks"]):
+    gy = _empty((N, P), g) if p_drop > 0.0 else None        # a sublayer output's gradient: the stream's through its mask
+    for l in reversed(range(len(sv["blocks"]))):
+        b = sv["blocks"][l]
         p, M = b["prefix"], b["M"]
+        sd = tuple(page_dropout_seed(sv["seed_base"], l, i) for i in range(PAGE_DROP_SITES)) if p_drop > 0.0 else None
         # x3 = x2 + f ffn2.weight^T + ffn2.bias
         df = _empty((N, M), g)
-        _linear_bwd(gx, P, b["f"], M, params[p + "ffn2.weight"], N, P, M, buf(p + "ffn2.bias", (P,)),
-                    buf(p + "ffn2.weight", (P, M)), df, M, False)
+        if sd is not None:
+            call("cova_dropout_regen_bwd", gx, P, gy, P, N, P, p_drop, sd[3])
+        _linear_bwd(gy if sd is not None else gx, P, b["f"], M, params[p + "ffn2.weight"], N, P, M,
+                    buf(p + "ffn2.bias", (P,)), buf(p + "ffn2.weight", (P, M)), df, M, False)
         dz = _empty((N, M), g)
-        call("cova_gelu_bwd", df, M, b["z"], M, N, M, dz, M)
+        if sd is not None:
+            call("cova_gelu_bwd_drop", df, M, b["z"], M, N, M, dz, M, p_drop, sd[2])
+        else:
+            call("cova_gelu_bwd", df, M, b["z"], M, N, M, dz, M)
         dm = _empty((N, P), g)
         _linear_bwd(dz, M, b["m"], P, params[p + "ffn1.weight"], N, M, P, buf(p + "ffn1.bias", (M,)),
                     buf(p + "ffn1.weight", (M, P)), dm, P, False)
@@ -1800,11 +1897,14 @@ def page_encoder_bwd(sv, g, ldg, params, dh, lddh, gout=None):
                       buf(p + "norm2.weight", (P,)), buf(p + "norm2.bias", (P,)))
         # x2 = x1 + O out.weight^T + out.bias
         dO = dm                                # (dead by now: reuse)
-        _linear_bwd(gx, P, b["O"], P, params[p + "out.weight"], N, P, P, buf(p + "out.bias", (P,)),
-                    buf(p + "out.weight", (P, P)), dO, P, False)
+        if sd is not None:
+            call("cova_dropout_regen_bwd", gx, P, gy, P, N, P, p_drop, sd[1])
+        _linear_bwd(gy if sd is not None else gx, P, b["O"], P, params[p + "out.weight"], N, P, P,
+                    buf(p + "out.bias", (P,)), buf(p + "out.weight", (P, P)), dO, P, False)
         geo = _saved_geo(sv, params.get(p + "geometry.weight"))
         dqkv = _page_attn_core_bwd(dO, P, b["qkv"], 3 * P, b["O"], P, b["lse"], P, Hh, sv["page_start"], geo,
-                                   buf(p + "geometry.weight", (Hh, 8)) if geo is not None else None)
+                                   buf(p + "geometry.weight", (Hh, 8)) if geo is not None else None,
+                                   (p_drop, sd[0]) if sd is not None else None)
         da = _empty((N, P), g)
         _linear_bwd(dqkv, 3 * P, b["a"], P, params[p + "qkv.weight"], N, 3 * P, P, None, buf(p + "qkv.weight", (3 * P, P)),
                     da, P, False)
@@ -1961,14 +2061,16 @@ def _readout_ctx_fwd(cfg, params, sv, out, bboxes, ctx, training, seeds):
 def _page_attn_ctx_fwd(cfg, params, sv, out, bboxes, ctx, training, seeds):
     geo = _geometry_on(cfg, sv, params, "page_attention_geometry", "page_attention.geometry.weight")
     return page_attn_fwd(sv["comb"], sv["T"], sv["N"], sv["F"], sv["page_start"], params, cfg.get("page_attention_heads", 1),
-                         out, sv["T"], bboxes=bboxes if geo else None, page_size=sv.get("page_size"))
+                         out, sv["T"], bboxes=bboxes if geo else None, page_size=sv.get("page_size"),
+                         dropout=cfg.get("page_attention_dropout", 0.0), seed_base=seeds[0], training=training)
 
 
 def _page_enc_ctx_fwd(cfg, params, sv, out, bboxes, ctx, training, seeds):
     geo = _geometry_on(cfg, sv, params, "page_encoder_geometry", "page_encoder.layers.0.geometry.weight")
     return page_encoder_fwd(sv["comb"], sv["T"], sv["N"], sv["F"], sv["page_start"], params,
                             cfg.get("page_encoder_heads", 1), cfg.get("page_encoder_layers", 1), out, sv["T"],
-                            bboxes=bboxes if geo else None, page_size=sv.get("page_size"))
+                            bboxes=bboxes if geo else None, page_size=sv.get("page_size"),
+                            dropout=cfg.get("page_encoder_dropout", 0.0), seed_base=seeds[0], training=training)
 
 
 def _page_ctx_bwd(key, bwd):

@@ -21,9 +21,10 @@ import torch
 import torch.nn as nn
 
 from . import engine
-from .weights import (EDGE_FEATURES, PAGE_ENCODER_OPTIONS, attention_of, backbone_channels, check_attention,
-                      check_attention_dropout, check_backbone_layers, check_page_attention, check_page_context_dim,
-                      check_page_encoder, head_layout, page_options)
+from .weights import (EDGE_FEATURES, PAGE_ATTENTION_DROPOUT_OPTION, PAGE_ENCODER_DROPOUT_OPTION, PAGE_ENCODER_OPTIONS,
+                      attention_of, backbone_channels, check_attention, check_attention_dropout, check_backbone_layers,
+                      check_page_attention, check_page_context_dim, check_page_dropout, check_page_encoder, head_layout,
+                      page_options)
 
 GAT_MAX_K = engine.GAT_MAX_K
 LOSS_MAX_CLASSES = engine.LOSS_MAX_CLASSES
@@ -462,9 +463,32 @@ class _PageLayerFn(torch.autograd.Function):
 
 
 class _PageLayer(nn.Module):
-    """What PageReadout, PageAttention and PageEncoder share: the input checks and the autograd node."""
-    _prefix = _second = None
+    """What PageReadout, PageAttention and PageEncoder share: the input checks, the autograd node and, for the two layers
+    that have one, the dropout of a module called on its own."""
+    _prefix = _second = _drop_name = None
     geometry_bias = False
+    dropout = 0.0
+    _dropout_seed, _dropout_calls = 0x5EED, 0
+
+    def _init_dropout(self, p, option):
+        """The layer's rate; with p > 0 its weightless nn.Dropout submodule ``_drop_name`` (rate and train / eval mode;
+        never called)."""
+        self.dropout = check_page_dropout(p, option)
+        if self.dropout > 0:
+            setattr(self, self._drop_name, nn.Dropout(self.dropout))
+
+    def seed_dropout(self, seed):
+        """Seed of the dropout masks of a layer called on its own (inside CoVA the model's seed governs): call c (1, 2, ...)
+        that drops draws from engine.page_dropout_seed(engine.dropout_base(seed, c), layer, site)."""
+        self._dropout_seed, self._dropout_calls = int(seed), 0
+
+    def _drop_args(self):
+        """dropout=, seed_base= and training= of the engine forward for this call."""
+        if self.dropout > 0 and getattr(self, self._drop_name).training:
+            self._dropout_calls += 1
+            return dict(dropout=self.dropout, seed_base=engine.dropout_base(self._dropout_seed, self._dropout_calls),
+                        training=True)
+        return dict(dropout=0.0, seed_base=0, training=False)
 
     def _run(self, h, page_start, bboxes=None, page_size=None):
         """The node's output(s) for checked inputs; None for an empty batch (the caller shapes its empty result)."""
@@ -514,18 +538,24 @@ class PageAttention(_PageLayer):
     """Extension: multi-head scaled dot-product self-attention (Vaswani et al. 2017) restricted to pages.  ``[Q | K | V] =
     qkv(h)`` (Linear(in_features, 3 dim), no bias); for a box i and a head of ``dim / heads`` columns, ``A_ij`` = softmax
     over ALL boxes j of i's page of ``Q_i . K_j / sqrt(dim / heads)`` and ``O_i = sum_j A_ij V_j``.  No output projection
-    (the decoder's first Linear follows), no dropout.  ``forward(h [N, in_features], page_start int64
+    (the decoder's first Linear follows).  ``forward(h [N, in_features], page_start int64
     [B + 1])`` -> ``O [N, dim]`` (and ``lse [N, heads]``, the log-sum-exp of each row's scores, with ``return_lse``); one
     autograd node over cova_page_attn_fwd / cova_page_attn_bwd.
     ``geometry=True`` (extension; the relative 2-D bias of LayoutLMv2, Xu et al. 2021, on this project's own features):
     the score of a pair also takes ``geometry`` (Linear(8, heads), no bias, zero at construction: the fresh layer computes
     the plain layer's output) of the eight relative-geometry features of cova_edge_geometry, query box against key box,
     formed inside the kernels (cova_page_attn_fwd_geo / cova_page_attn_bwd_geo).  ``forward`` then needs ``bboxes``
-    [N, 5] and ``page_size`` = (height, width) in pixels; the boxes get no gradient."""
+    [N, 5] and ``page_size`` = (height, width) in pixels; the boxes get no gradient.
+    ``dropout=p`` (extension, 0 <= p < 1; the ``dropout`` of nn.MultiheadAttention): inverted dropout on the probabilities
+    ``A`` while the layer's ``attn_drop`` submodule (a weightless nn.Dropout, created only when p > 0) is in train mode,
+    ``O_i = sum_j D_ij A_ij V_j / (1 - p)``; ``lse`` stays the undropped one.  No mask is stored: the kernels regenerate it
+    from a per-call seed (seed_dropout; cova_page_attn_fwd_drop / cova_page_attn_bwd_drop).  The GAT's ``attention_dropout``
+    does not reach this layer."""
 
     _prefix, _second, _engine_bwd = "page_attention.", "lse", staticmethod(engine.page_attn_bwd)
+    _drop_name = "attn_drop"
 
-    def __init__(self, in_features, dim, heads=1, geometry=False):
+    def __init__(self, in_features, dim, heads=1, geometry=False, dropout=0.0):
         super().__init__()
         self.in_features = in_features
         self.dim, self.heads = check_page_attention(dim, heads)
@@ -536,10 +566,11 @@ class PageAttention(_PageLayer):
         if self.geometry_bias:
             self.geometry = nn.Linear(8, self.heads, bias=False)
             nn.init.zeros_(self.geometry.weight)
+        self._init_dropout(dropout, PAGE_ATTENTION_DROPOUT_OPTION)
 
     def _engine_fwd(self, h, page_start, params, out, bboxes, page_size):
         return engine.page_attn_fwd(h, h.shape[1], h.shape[0], h.shape[1], page_start, params, self.heads, out, self.dim,
-                                    bboxes=bboxes, page_size=page_size)
+                                    bboxes=bboxes, page_size=page_size, **self._drop_args())
 
     def forward(self, h, page_start, bboxes=None, page_size=None, return_lse=False):
         out, lse = (self._run(h, page_start, bboxes, page_size)
@@ -568,7 +599,7 @@ class _PageEncoderBlock(nn.Module):
 
 class PageEncoder(_PageLayer):
     """Extension: an L-layer pre-LN transformer encoder (Vaswani et al. 2017; the pre-LN form of Xiong et al. 2020) over
-    the boxes of each page -- torch's ``nn.TransformerEncoderLayer(norm_first=True, activation="gelu", dropout=0)`` per
+    the boxes of each page -- torch's ``nn.TransformerEncoderLayer(norm_first=True, activation="gelu", dropout=p)`` per
     page with a zero ``in_proj_bias``, behind an input projection and in front of a final LayerNorm:
         x = input(h)                                  Linear(in_features, dim), no bias (a LayerNorm follows)
         per layer:  x = x + out(page attention of qkv(norm1(x)));   x = x + ffn2(GELU(ffn1(norm2(x))))
@@ -576,14 +607,22 @@ class PageEncoder(_PageLayer):
     The attention is PageAttention's (every box attends to ALL boxes of its page, ``heads`` heads, cova_page_attn_fwd);
     ``geometry=True`` gives every layer the box-geometry bias of PageAttention(geometry=True) (``layers.<l>.geometry``,
     Linear(8, heads), no bias, zero at construction; ``forward`` then needs ``bboxes`` [N, 5] and ``page_size`` = (height,
-    width)).  GELU is the exact (erf) form, eps = 1e-5.  There is no dropout inside the encoder, and the GAT's
-    ``attention_dropout`` and ``edge_geometry`` do not reach it.  ``forward(h [N, in_features], page_start int64 [B + 1])``
+    width)).  GELU is the exact (erf) form, eps = 1e-5.  The GAT's ``attention_dropout`` and ``edge_geometry`` do not
+    reach the encoder.
+    ``dropout=p`` (0 <= p < 1; torch's single ``dropout`` argument, default 0 here): while the encoder's ``drop`` submodule (a
+    weightless nn.Dropout, created only when p > 0) is in train mode every block runs
+        x = x + drop1(out(page attention with dropped probabilities));   x = x + drop2(ffn2(drop_h(GELU(ffn1(norm2(x))))))
+    four sites per layer, each on a stream of its own (engine.page_dropout_seed), none on the input projection or the
+    final LayerNorm.  No mask is stored: the kernels regenerate them from a per-call seed (seed_dropout).
+    ``forward(h [N, in_features], page_start int64 [B + 1])``
     -> ``[N, dim]``; one autograd node over engine.page_encoder_fwd / page_encoder_bwd (cova_layernorm_*, cova_gelu_*,
-    cova_page_attn_*, cova_sgemm, cova_colsum)."""
+    cova_page_attn_*, cova_sgemm, cova_colsum; with dropout cova_dropout_add_fwd / cova_dropout_regen_bwd and the _drop
+    forms)."""
 
     _prefix, _engine_bwd = "page_encoder.", staticmethod(engine.page_encoder_bwd)
+    _drop_name = "drop"
 
-    def __init__(self, in_features, dim, heads=1, layers=1, ffn_dim=None, geometry=False):
+    def __init__(self, in_features, dim, heads=1, layers=1, ffn_dim=None, geometry=False, dropout=0.0):
         super().__init__()
         self.in_features = in_features
         self.dim, self.heads, self.n_layers, self.ffn_dim, self.geometry_bias = check_page_encoder(dim, heads, layers,
@@ -594,10 +633,11 @@ class PageEncoder(_PageLayer):
         self.layers = nn.ModuleList(_PageEncoderBlock(self.dim, self.heads, self.ffn_dim, self.geometry_bias)
                                     for _ in range(self.n_layers))
         self.norm = nn.LayerNorm(self.dim)
+        self._init_dropout(dropout, PAGE_ENCODER_DROPOUT_OPTION)
 
     def _engine_fwd(self, h, page_start, params, out, bboxes, page_size):
         return engine.page_encoder_fwd(h, h.shape[1], h.shape[0], h.shape[1], page_start, params, self.heads, self.n_layers,
-                                       out, self.dim, bboxes=bboxes, page_size=page_size)
+                                       out, self.dim, bboxes=bboxes, page_size=page_size, **self._drop_args())
 
     def forward(self, h, page_start, bboxes=None, page_size=None):
         out = self._run(h, page_start, bboxes, page_size)
@@ -611,7 +651,8 @@ class CoVA(nn.Module):
                  sampling_ratio=2, roi_aligned=False, backbone_layers=1, edge_geometry=False, attention="gat",
                  attention_dropout=0.0, page_context_dim=0, page_attention_dim=0, page_attention_heads=1,
                  page_attention_geometry=False, page_encoder_dim=0, page_encoder_heads=1, page_encoder_layers=1,
-                 page_encoder_ffn_dim=None, page_encoder_geometry=False):
+                 page_encoder_ffn_dim=None, page_encoder_geometry=False, page_attention_dropout=0.0,
+                 page_encoder_dropout=0.0):
         """The first nine arguments exactly as the reference's CoVA (models.py:10-34; called positionally
         at main.py:122-132).  Keyword-only-in-practice extensions, whose defaults are the reference's
         model: ``backbone`` 'resnet18' | 'resnet50' (torchvision ``children()[:-5]`` of either),
@@ -640,7 +681,8 @@ class CoVA(nn.Module):
         [4, 128]; independent of ``use_context`` and of ``page_context_dim``): a PageAttention of the own features gives
         every box E more columns behind the readout's, its own attention-weighted view of ALL boxes of its page
         (``page_attention.qkv.weight``, between ``page_readout`` and ``decoder`` in the state_dict).  ``edge_geometry`` and
-        ``attention_dropout`` belong to the GAT and do not reach this layer.  With 0 nothing changes.
+        ``attention_dropout`` belong to the GAT and do not reach this layer (``page_attention_dropout`` does).  With 0 nothing
+        changes.
         ``page_attention_geometry=True`` (needs ``page_attention_dim`` > 0, else ValueError): the page attention's scores
         take a bias from the relative geometry of the two boxes (``page_attention.geometry.weight`` [Hh, 8], zero at
         construction, directly behind ``page_attention.qkv.weight``); the page size is taken from ``images``.
@@ -650,8 +692,15 @@ class CoVA(nn.Module):
         ``page_encoder_ffn_dim`` (a multiple of 4 in [4, 2048]; None: 2 P) -- gives every box P more columns behind the page
         attention's (``page_encoder.*``, between ``page_attention`` and ``decoder`` in the state_dict).
         ``page_encoder_geometry=True`` (needs P > 0) gives every layer's scores the box-geometry bias
-        (``page_encoder.layers.<l>.geometry.weight`` [Hh, 8], zero at construction).  No dropout inside the encoder;
-        ``edge_geometry`` and ``attention_dropout`` belong to the GAT and do not reach it.  With 0 nothing changes."""
+        (``page_encoder.layers.<l>.geometry.weight`` [Hh, 8], zero at construction).  ``edge_geometry`` and
+        ``attention_dropout`` belong to the GAT and do not reach it.  With 0 nothing changes.
+        ``page_attention_dropout=p`` (0 <= p < 1; needs ``page_attention_dim`` > 0, else ValueError): dropout on the page
+        attention's probabilities in train mode (PageAttention(dropout=), submodule ``page_attention.attn_drop``).
+        ``page_encoder_dropout=p`` (0 <= p < 1; needs ``page_encoder_dim`` > 0): torch's ``dropout=`` of
+        nn.TransformerEncoderLayer on the four sites of every encoder block (PageEncoder(dropout=), submodule
+        ``page_encoder.drop``).  Both follow seed_dropout() like the decoder's masks, from streams of their own
+        (engine.page_dropout_seed); no mask is stored, no weights: the state_dict is unchanged, and with p = 0 the module
+        list and every launch are too."""
         page = page_options(locals())
         check_backbone_layers(backbone, backbone_layers)
         check_attention(attention)
@@ -718,10 +767,12 @@ class CoVA(nn.Module):
         self.page_attention_dim, self.page_attention_heads = page["page_attention_dim"], page["page_attention_heads"]
         if self.page_attention_dim > 0:
             self.page_attention = PageAttention(self.n_feat, self.page_attention_dim, self.page_attention_heads,
-                                                geometry=page["page_attention_geometry"])
+                                                geometry=page["page_attention_geometry"],
+                                                dropout=page[PAGE_ATTENTION_DROPOUT_OPTION])
         self.page_encoder_dim = page["page_encoder_dim"]
         if self.page_encoder_dim > 0:
-            self.page_encoder = PageEncoder(self.n_feat, *(page[k] for k in PAGE_ENCODER_OPTIONS))
+            self.page_encoder = PageEncoder(self.n_feat, *(page[k] for k in PAGE_ENCODER_OPTIONS),
+                                            dropout=page[PAGE_ENCODER_DROPOUT_OPTION])
         self._cfg = dict(roi_output_size=roi_output_size, n_classes=n_classes, use_context=use_context,
                          hidden_dim=hidden_dim, bbox_hidden_dim=bbox_hidden_dim,
                          n_additional_feat=n_additional_feat, drop_prob=float(drop_prob),

@@ -340,7 +340,14 @@ class HotPathTrainer:
     plain sum (exact: the gradient of the summed loss), "mean" scales by 1 / m, the mean of the m micro-batch means, which
     is not the mean over the union when micro-batches score different numbers of boxes.  ``step_count`` counts
     micro-batches (the dropout streams), ``update_count`` parameter updates (Adam's bias correction, the averaging
-    schedule).  With the default 1 no tensor and no launch is added and update_count is step_count."""
+    schedule).  With the default 1 no tensor and no launch is added and update_count is step_count.
+
+    Page dropout ("Page dropout"): ``cfg["page_attention_dropout"]`` / ``cfg["page_encoder_dropout"]``
+    (weights.check_page_dropout; normalised into ``self.cfg`` with the other page options, so a checkpoint's cfg carries
+    them) drop inside the page attention and the page encoder in forward_backward(), on the streams
+    engine.page_dropout_seed(base, layer, site) of the step's decoder base: the same seeds as CoVA.seed_dropout(), with
+    or without cached features.  predict / evaluate / loss / evaluate_split and averaged_weights() run the eval-mode
+    forward: the plain launches.  With both 0 no launch changes."""
 
     def __init__(self, cfg, state_dict, device, lr=5e-4, weight_decay=1e-3, betas=(0.9, 0.999),
                  eps=1e-8, world_size=1, process_group=None, dropout_seed=123, sync_bn=False, frozen=(), bn_eval=(),

@@ -121,7 +121,31 @@ def check_page_encoder(dim, heads=1, layers=1, ffn_dim=None, geometry=False):
     return dim, heads, int(layers), int(ffn_dim), bool(geometry)
 
 
-# Every page option with its default, in the order of CoVA's and state_dict_spec's arguments.
+PAGE_ATTENTION_DROPOUT_OPTION = "page_attention_dropout"
+PAGE_ENCODER_DROPOUT_OPTION = "page_encoder_dropout"
+
+
+def check_page_dropout(p, option, width=None):
+    """Rate of a page layer's dropout (``page_attention_dropout`` on the page attention's probabilities,
+    cova_page_attn_fwd_drop; ``page_encoder_dropout``, torch's ``dropout=`` of nn.TransformerEncoderLayer, on the four
+    sites of every encoder block): check_attention_dropout's rule, a real number in [0, 1) -> float.  ``option`` names the
+    cfg entry in the error.  With ``width`` (the layer's page_attention_dim / page_encoder_dim) a rate > 0 needs the layer."""
+    try:
+        ok = not isinstance(p, bool) and 0.0 <= float(p) < 1.0          # (NaN fails both comparisons)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("%s must be a number in [0, 1), got %r" % (option, p))
+    if width is not None and float(p) > 0.0 and width <= 0:
+        layer = option[:-len("dropout")] + "dim"
+        raise ValueError("%s=%r needs %s > 0 (the dropout belongs to that layer), got %s=%r" % (option, p, layer, layer, width))
+    return float(p)
+
+
+# The page layers' dropout rates: no weights, so not arguments of state_dict_spec (as ``attention_dropout``).
+PAGE_DROPOUT_DEFAULTS = ((PAGE_ATTENTION_DROPOUT_OPTION, 0.0), (PAGE_ENCODER_DROPOUT_OPTION, 0.0))
+
+# Every page option that shapes the state_dict with its default, in the order of CoVA's and state_dict_spec's arguments.
 PAGE_OPTION_DEFAULTS = (("page_context_dim", 0), ("page_attention_dim", 0), ("page_attention_heads", 1),
                         ("page_attention_geometry", False), ("page_encoder_dim", 0), ("page_encoder_heads", 1),
                         ("page_encoder_layers", 1), ("page_encoder_ffn_dim", None), ("page_encoder_geometry", False))
@@ -130,13 +154,16 @@ PAGE_ENCODER_OPTIONS = tuple(k for k, _ in PAGE_OPTION_DEFAULTS if k.startswith(
 
 def page_options(cfg):
     """The page options of a cfg-like mapping (missing ones at their defaults), each through its check_* function -> a
-    dict of all nine, normalised.  A normalised dict passes again unchanged."""
+    dict of all nine and the two dropout rates (PAGE_DROPOUT_DEFAULTS), normalised.  A normalised dict passes again
+    unchanged."""
     v = {k: cfg.get(k, default) for k, default in PAGE_OPTION_DEFAULTS}
     out = {"page_context_dim": check_page_context_dim(v["page_context_dim"])}
     out["page_attention_dim"], out["page_attention_heads"] = check_page_attention(v["page_attention_dim"],
                                                                                   v["page_attention_heads"])
     out["page_attention_geometry"] = check_page_attention_geometry(v["page_attention_geometry"], out["page_attention_dim"])
     out.update(zip(PAGE_ENCODER_OPTIONS, check_page_encoder(*(v[k] for k in PAGE_ENCODER_OPTIONS))))
+    for (k, default), width in zip(PAGE_DROPOUT_DEFAULTS, ("page_attention_dim", "page_encoder_dim")):
+        out[k] = check_page_dropout(cfg.get(k, default), k, out[width])
     return out
 
 

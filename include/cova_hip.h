@@ -783,6 +783,38 @@ int cova_page_attn_bwd_geo(const float *g, int ldg, const float *qkv, int ldq, c
                            const float *lse /*[N,Hh]*/, const int64_t *page_start /*[B+1]*/, const float *bboxes /*[N,5]*/,
                            const float *geo_w /*[Hh,8]*/, float img_w, float img_h, int B, int N, int E, int Hh, float *dqkv,
                            int lddq, float *d_geo_w /*[Hh,8]*/, float *workspace, void *stream);
+/* ---- dropout on the page attention's probabilities (page_attn.hip, the DROP instantiations; opt-in:
+ * CoVA(page_attention_dropout=p) and, as site 0 of every encoder layer, CoVA(page_encoder_dropout=p)) ----
+ * replaces: the dropout_p of F.multi_head_attention_forward / F.scaled_dot_product_attention in train mode (the `dropout`
+ * argument of nn.MultiheadAttention inside nn.TransformerEncoderLayer): F.dropout on softmax(s) before the product with V.
+ * Inverted dropout at rate p, inv = 1.f / (1.f - p) (one f32 division).  The score of (query batch row i, head a, key batch
+ * row j) is kept (D_ij = 1) when hash_uniform(seed, ((uint64)(i * Hh + a) << 32) | (uint64)j) >= p, compared in f32.  No mask
+ * and no probability is stored: the forward and both sides of the backward regenerate D from the same integers and form
+ * the dropped value by one helper, ONE rounded multiply v * inv on a kept score and +0 on a dropped one.
+ *   A_ij = softmax_j s_ij as in the plain pair (with the geometry bias in the _geo_ forms); lse is the UNDROPPED one, bit-equal
+ *   to the plain forward's on the same inputs (row maximum and sum run over all keys)
+ *   O_i = sum_j D_ij inv A_ij V_j
+ *   delta_i = g_i . O_i,  dA_ij = D_ij inv (g_i . V_j),  ds_ij = A_ij (dA_ij - delta_i)       (a dropped score still takes
+ *   -A_ij delta_i through the softmax),  dV_j = sum_i (D_ij inv A_ij) g_i;  dQ, dK and d_geo_w follow from ds as before.
+ * Summation orders, launches and workspace are those of the plain pairs.  A row whose keys are all dropped has O = 0 and
+ * zero dqkv rows.  D depends on (seed, i, a, j) alone: reruns are bit-identical, and a page keeps its bits whatever other
+ * pages share the batch as long as it occupies the same batch rows.
+ * Refusals are those of the plain (or _geo) pair, plus p outside (0, 1) (NaN included) or N * Hh >= 2**32: COVA_ERR_BAD_ARG
+ * before anything is launched. */
+int cova_page_attn_fwd_drop(const float *qkv, int ldq, const int64_t *page_start /*[B+1]*/, int B, int N, int E, int Hh,
+                            float *out, int ldo, float *lse /*[N,Hh]*/, float p, unsigned long long seed, void *stream);
+int cova_page_attn_bwd_drop(const float *g, int ldg, const float *qkv, int ldq, const float *out, int ldo,
+                            const float *lse /*[N,Hh]*/, const int64_t *page_start /*[B+1]*/, int B, int N, int E, int Hh,
+                            float *dqkv, int lddq, float p, unsigned long long seed, void *stream);
+int cova_page_attn_fwd_geo_drop(const float *qkv, int ldq, const int64_t *page_start /*[B+1]*/,
+                                const float *bboxes /*[N,5]*/, const float *geo_w /*[Hh,8]*/, float img_w, float img_h,
+                                int B, int N, int E, int Hh, float *out, int ldo, float *lse /*[N,Hh]*/, float p,
+                                unsigned long long seed, void *stream);
+int cova_page_attn_bwd_geo_drop(const float *g, int ldg, const float *qkv, int ldq, const float *out, int ldo,
+                                const float *lse /*[N,Hh]*/, const int64_t *page_start /*[B+1]*/,
+                                const float *bboxes /*[N,5]*/, const float *geo_w /*[Hh,8]*/, float img_w, float img_h,
+                                int B, int N, int E, int Hh, float *dqkv, int lddq, float *d_geo_w /*[Hh,8]*/,
+                                float *workspace, float p, unsigned long long seed, void *stream);
 /* ---- row kernels of the page encoder (page_encoder.hip; opt-in: CoVA(page_encoder_dim=P)) ----
  * LayerNorm over the C channels of each of R rows (rows at x + r*ldx), float32:
  *   mean_r = sum_c x_rc / C,  rstd_r = 1 / sqrt(sum_c (x_rc - mean_r)^2 / C + eps)   (the biased variance, formed in TWO
@@ -819,6 +851,27 @@ int cova_layernorm_bwd(const float *g, int ldg, const float *x, int ldx, const f
                        int ldr, float *dx, int lddx, float *dweight /*[C]*/, float *dbias /*[C]*/, float *ws, void *stream);
 int cova_gelu_fwd(const float *z, int ldz, long long R, int C, float *out, int ldo, void *stream);
 int cova_gelu_bwd(const float *g, int ldg, const float *z, int ldz, long long R, int C, float *dz, int lddz, void *stream);
+/* ---- dropout of the page encoder's sublayers (page_encoder.hip; opt-in: CoVA(page_encoder_dropout=p)) ----
+ * replaces: the `dropout`, `dropout1` and `dropout2` submodules of nn.TransformerEncoderLayer(norm_first=True) in train
+ * mode (F.dropout on the FFN hidden activations and on each sublayer's output before its residual add).
+ * Inverted dropout at rate p, inv = 1.f / (1.f - p) (one f32 division): element (r, c) of an [R, C] operand is kept when
+ * hash_uniform(seed, r * C + c) >= p, compared in f32 (cova_dropout_fwd's convention).  No mask is stored: a backward
+ * regenerates it from the same (seed, r * C + c).  Every `* inv` is ONE rounded f32 multiply; a dropped element is +0.
+ *   cova_gelu_fwd_drop      out = keep ? gelu(z) * inv : 0           (gelu as cova_gelu_fwd; z stays the saved tensor)
+ *   cova_gelu_bwd_drop      dz  = keep ? (g * inv) * gelu'(z) : 0    (gelu' as cova_gelu_bwd, from the same saved z)
+ *   cova_dropout_add_fwd    out = x + (keep ? y * inv : 0)           two roundings; out may be neither y nor x
+ *   cova_dropout_regen_bwd  dy  = keep ? g * inv : 0                 dy may not be g
+ * float4 under the alignment rule of the GELU pair, scalar otherwise; one grid-stride launch each; reruns are bit-identical.
+ * 0 < p < 1 (NaN refused), C >= 1, R >= 0, ld* >= C, else COVA_ERR_BAD_ARG before anything is launched; R == 0 launches
+ * nothing, writes nothing and needs no pointer; otherwise a NULL or aliased operand is COVA_ERR_BAD_ARG. */
+int cova_gelu_fwd_drop(const float *z, int ldz, long long R, int C, float *out, int ldo, float p, unsigned long long seed,
+                       void *stream);
+int cova_gelu_bwd_drop(const float *g, int ldg, const float *z, int ldz, long long R, int C, float *dz, int lddz, float p,
+                       unsigned long long seed, void *stream);
+int cova_dropout_add_fwd(const float *y, int ldy, const float *x, int ldx, float *out, int ldo, long long R, int C, float p,
+                         unsigned long long seed, void *stream);
+int cova_dropout_regen_bwd(const float *g, int ldg, float *dy, int lddy, long long R, int C, float p,
+                           unsigned long long seed, void *stream);
 /* evaluation decision (train.py:131-153): per page and class column, page-local indices of the k
  * highest-scoring boxes, best first; page_start [n_pages+1] are box offsets; out [n_pages,NC,k] */
 int cova_page_class_topk(const float *logits, const int64_t *page_start, int n_pages, int NC, int k,
