@@ -515,7 +515,8 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_reduce_win_kernel(
             const int ky = pos[j] / 3, kx = pos[j] - ky * 3;
             const int iy = 2 * oy - 1 + ky, ix = 2 * ox - 1 + kx;
             const float yv = yb[((size_t)iy * W1 + ix) * 64 + j];
-            const float dy = (yv * scv[j] + shv[j] > 0.f) ? gv[j] : 0.f;
+            const float t = fmaf(yv, scv[j], shv[j]);            // the forward's ReLU decision, in the forward's form
+            const float dy = t > 0.f ? gv[j] : 0.f;
             s[j] += dy;
             q[j] += dy * ((yv - muv[j]) * isv[j]);
         }
@@ -601,7 +602,7 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_apply_quad_kernel(
                             if (id[i][j][c] == ky * 3 + kx) dy += g[i][j][c];
                         }
                     }
-                    const float t = yv[c] * sc[c] + sh[c];
+                    const float t = fmaf(yv[c], sc[c], sh[c]);      // the forward's ReLU decision, in the forward's form
                     if (!(t > 0.f)) dy = 0.f;
                     const float xh = (yv[c] - mu[c]) * is[c];
                     out[c] = sc[c] * (dy - k1[c] - xh * k2[c]);
