@@ -7,6 +7,8 @@ The oracle for the new pieces is the build's own torch-CPU restatement (oracle/c
 parity unpinned by the reference); geometry cases on the reference's own model use the reference-pinned oracle.
 Tolerances as in test_model_gpu.py (about 5x the measured round-off): forward 5e-5 of the tensor scale, loss 2e-5, gradients 1e-4 of each
 tensor's scale under forced routing.
+The per-element, every-launch-path gate of the 1x1 convolution kernels -- exact on lattice operands, every instantiation,
+multi-trip tile walks -- lives in tests/test_c11_paths_gpu.py (tests/c11_cases.py).
 """
 import numpy as np
 import pytest

@@ -12,7 +12,9 @@ f32) held to f32 on the MI355X:
 A statistical gate cannot hold the split for one-sign operands and long reductions -- the dropped terms average out of a
 max-relative metric (CPU emulation, vprod at R = 60001 with ReLU-like operands: without x1 w1 P moves by 8e-8, without x2 w0
 by 7e-8, the f32 GEMM's own error being 2e-7) -- which are the operand statistics the train step has.  The probes carry
-that case."""
+that case.
+The probes set every prologue and epilogue to the identity and run one tile per wave; the per-element gate with every
+constant present, on every launch path and multi-trip walk, lives in tests/test_c11_paths_gpu.py (tests/c11_cases.py)."""
 import pytest
 import torch
 import torch.nn.functional as F
