@@ -21,6 +21,14 @@ def needs_build():
 FILE_FLAGS = {"conv_wgrad4.hip": ["-fno-slp-vectorize"]}
 
 
+def flags(name=None):
+    """hipcc's flags for the translation unit `name` (its FILE_FLAGS included); every build of a csrc file starts from these.
+    -Werror=missing-prototypes: common.h includes include/cova_hip.h, so a COVA_API definition that the header does not
+    declare stops the build (one that disagrees with its declaration is a "conflicting types" error under any flags)."""
+    return (["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
+             "-Werror=missing-prototypes"] + FILE_FLAGS.get(os.path.basename(name) if name else None, []))
+
+
 def build(force=False, verbose=False):
     if not force and not needs_build():
         return LIB_PATH
@@ -28,13 +36,11 @@ def build(force=False, verbose=False):
     os.makedirs(os.path.dirname(LIB_PATH), exist_ok=True)
     objdir = os.path.join(PKG_DIR, "lib", "obj")
     os.makedirs(objdir, exist_ok=True)
-    common = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
-              "-Wall", "-Wno-unused-function"]
-    common += os.environ.get("COVA_EXTRA_FLAGS", "").split()
+    extra = os.environ.get("COVA_EXTRA_FLAGS", "").split()
     procs, objs = [], []
     for src in SOURCES:                        # one hipcc per translation unit, in parallel
         obj = os.path.join(objdir, os.path.basename(src)[:-4] + ".o")
-        cmd = common + FILE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
+        cmd = [hipcc] + flags(src) + extra + ["-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd))
         procs.append((cmd, subprocess.Popen(cmd)))

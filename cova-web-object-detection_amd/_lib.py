@@ -40,6 +40,20 @@ def parse_header(path=HEADER):
     return protos
 
 
+def parse_struct(name, path=HEADER):
+    """-> [(field, ctype), ...] of `typedef struct NAME { ... } NAME;` in the header, in declaration order: pointers are
+    c_void_p, scalars come from _CTYPES, and a declarator list (`float *a, *b;`, `float x, y;`) is split."""
+    src = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
+    body = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (name, name), src, flags=re.S).group(1)
+    fields = []
+    for decl in [d.strip() for d in body.split(";") if d.strip()]:
+        base, first = re.match(r"((?:const\s+)?(?:\w+\s+)*?\w+)\s*(\**\s*\w+\s*(?:,.*)?)$", decl, flags=re.S).groups()
+        base = re.sub(r"\bconst\b", "", base).strip()
+        for d in [d.strip() for d in first.split(",")]:
+            fields.append((d.lstrip("* "), ctypes.c_void_p if d.startswith("*") else _CTYPES[base]))
+    return fields
+
+
 class CovaHipError(RuntimeError):
     pass
 
@@ -95,21 +109,6 @@ def _arg(a):
 # leg): PROFILE = {entry point name: [(start_event, end_event, integer arguments of the call, which arguments were
 # non-NULL -- one bool per positional argument: the kernel variant a launch took follows from it), ...]}
 PROFILE = None
-
-
-def _device_of(name, args):
-    """The one ROCm device all tensor arguments live on (mixed devices are an error)."""
-    dev = None
-    for a in args:
-        if isinstance(a, torch.Tensor):
-            if not a.is_cuda:
-                raise CovaHipError("%s: got a %s tensor; the hot path runs on the ROCm device only "
-                                   "(no CPU fallback)" % (name, a.device))
-            if dev is None:
-                dev = a.device
-            elif a.device != dev:
-                raise CovaHipError("%s: tensor arguments on different devices (%s, %s)" % (name, dev, a.device))
-    return dev
 
 
 _Tensor = torch.Tensor

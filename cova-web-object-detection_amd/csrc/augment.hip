@@ -430,12 +430,11 @@ COVA_API int cova_pages_u8_resample_f32(const uint8_t *store_u8, const int *page
     const long long gx = work < cap ? work : cap;
     hipStream_t st = (hipStream_t)stream;
     if (vec)
-        hipLaunchKernelGGL(resample_vec4_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(64, 4), 0, st, store_u8, f32_nchw, P,
-                           B, H, W, page_idx, step, origin, color, (uint32_t)fill_rgb);
+        COVA_LAUNCH(resample_vec4_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(64, 4), st, store_u8, f32_nchw, P,
+                    B, H, W, page_idx, step, origin, color, (uint32_t)fill_rgb);
     else
-        hipLaunchKernelGGL(resample_scalar_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, store_u8, f32_nchw, P,
-                           B, H, W, page_idx, step, origin, color, (uint32_t)fill_rgb);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(resample_scalar_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), st, store_u8, f32_nchw, P,
+                    B, H, W, page_idx, step, origin, color, (uint32_t)fill_rgb);
     return COVA_OK;
 }
 
@@ -444,9 +443,8 @@ COVA_API int cova_boxes_affine(float *bboxes, int N, const float *affine, int B,
     COVA_REQUIRE(N >= 0 && B >= 0);
     if (N == 0) return COVA_OK;
     COVA_REQUIRE(bboxes && affine && B > 0);
-    hipLaunchKernelGGL(boxes_affine_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, bboxes, N,
-                       affine, B);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(boxes_affine_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), (hipStream_t)stream, bboxes, N,
+                affine, B);
     return COVA_OK;
 }
 
@@ -464,12 +462,11 @@ COVA_API int cova_pages_u8_augment_f32(const uint8_t *store_u8, const int *page_
     const long long gx = work < cap ? work : cap;
     hipStream_t st = (hipStream_t)stream;
     if (vec)
-        hipLaunchKernelGGL(augment_vec4_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(64, 4), 0, st, store_u8, f32_nchw, P, B,
-                           H, W, page_idx, shift, color, (uint32_t)fill_rgb);
+        COVA_LAUNCH(augment_vec4_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(64, 4), st, store_u8, f32_nchw, P, B,
+                    H, W, page_idx, shift, color, (uint32_t)fill_rgb);
     else
-        hipLaunchKernelGGL(augment_scalar_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, store_u8, f32_nchw, P,
-                           B, H, W, page_idx, shift, color, (uint32_t)fill_rgb);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(augment_scalar_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), st, store_u8, f32_nchw, P,
+                    B, H, W, page_idx, shift, color, (uint32_t)fill_rgb);
     return COVA_OK;
 }
 
@@ -478,8 +475,7 @@ COVA_API int cova_boxes_translate(float *bboxes, int N, const int *shift, int B,
     COVA_REQUIRE(N >= 0 && B >= 0);
     if (N == 0) return COVA_OK;
     COVA_REQUIRE(bboxes && shift && B > 0);
-    hipLaunchKernelGGL(boxes_translate_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, bboxes, N,
-                       shift, B);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(boxes_translate_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), (hipStream_t)stream, bboxes, N,
+                shift, B);
     return COVA_OK;
 }

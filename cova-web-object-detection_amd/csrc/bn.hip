@@ -639,9 +639,8 @@ COVA_API int cova_partials_fold(const float *partial, int nparts, int width, int
 {
     COVA_REQUIRE(partial && out && nparts > 0 && width > 0 && group > 0);
     const dim3 grid(cdiv(width, 256), cdiv(nparts, group));
-    hipLaunchKernelGGL(partials_fold_kernel, grid, dim3(256), 0, (hipStream_t)stream, partial, nparts,
-                       width, group, out);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(partials_fold_kernel, grid, dim3(256), (hipStream_t)stream, partial, nparts,
+                width, group, out);
     return COVA_OK;
 }
 
@@ -652,16 +651,14 @@ COVA_API int cova_colstats(const float *x, int ldx, long long R, int C, float *p
     const int rpc = cova_colreduce_rows_per_chunk(R, C);
     const dim3 grid((unsigned)cdivll(R, rpc), (unsigned)cdiv(C, pow2_cols_host(C)));
     if (C == 64 && ldx == 64 && vec4_ok(x, ldx)) {
-        hipLaunchKernelGGL(colreduce64_kernel<0>, dim3(grid.x), dim3(256), 0, (hipStream_t)stream, x,
-                           (const float *)nullptr, (const float *)nullptr, (const float *)nullptr,
-                           (const float *)nullptr, partial, R, rpc);
-        COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(colreduce64_kernel<0>, dim3(grid.x), dim3(256), (hipStream_t)stream, x,
+                    (const float *)nullptr, (const float *)nullptr, (const float *)nullptr,
+                    (const float *)nullptr, partial, R, rpc);
         return COVA_OK;
     }
-    hipLaunchKernelGGL(colreduce_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, x, ldx,
-                       (const float *)nullptr, 0, (const float *)nullptr, 0, (const float *)nullptr,
-                       (const float *)nullptr, partial, R, C, rpc);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(colreduce_kernel<0>, grid, dim3(256), (hipStream_t)stream, x, ldx,
+                (const float *)nullptr, 0, (const float *)nullptr, 0, (const float *)nullptr,
+                (const float *)nullptr, partial, R, C, rpc);
     return COVA_OK;
 }
 
@@ -674,10 +671,9 @@ COVA_API int cova_bn_finalize_fwd(const float *partial, int nparts, int C, doubl
                                   void *stream)
 {
     COVA_REQUIRE(partial && gamma && beta && scale && shift && mean && invstd && nparts > 0 && C > 0);
-    hipLaunchKernelGGL(bn_finalize_fwd_kernel, dim3(cdiv(C, 64)), dim3(1024), 0, (hipStream_t)stream,
-                       partial, nparts, C, count, gamma, beta, running_mean, running_var, momentum,
-                       eps, scale, shift, mean, invstd, num_batches_tracked);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(bn_finalize_fwd_kernel, dim3(cdiv(C, 64)), dim3(1024), (hipStream_t)stream,
+                partial, nparts, C, count, gamma, beta, running_mean, running_var, momentum,
+                eps, scale, shift, mean, invstd, num_batches_tracked);
     return COVA_OK;
 }
 
@@ -686,9 +682,8 @@ COVA_API int cova_bn_eval_params(const float *gamma, const float *beta, const fl
                                  float *shift, float *mean, float *invstd, void *stream)
 {
     COVA_REQUIRE(gamma && beta && running_mean && running_var && scale && shift && C > 0);
-    hipLaunchKernelGGL(bn_eval_params_kernel, dim3(cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream,
-                       gamma, beta, running_mean, running_var, eps, C, scale, shift, mean, invstd);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(bn_eval_params_kernel, dim3(cdiv(C, 256)), dim3(256), (hipStream_t)stream,
+                gamma, beta, running_mean, running_var, eps, C, scale, shift, mean, invstd);
     return COVA_OK;
 }
 
@@ -701,12 +696,11 @@ COVA_API int cova_bn_act_fwd(const float *z, int ldz, const float *scale, const 
     const bool v4 = (C % 4 == 0) && vec4_ok(z, ldz) && vec4_ok(res, ldres) && vec4_ok(out, ldo) &&
                     vec4_ok(scale, 0) && vec4_ok(shift, 0);
     if (v4)
-        hipLaunchKernelGGL(bn_act_fwd_kernel<4>, dim3(ew_grid(R * (C / 4))), dim3(256), 0,
-                           (hipStream_t)stream, z, ldz, scale, shift, res, ldres, out, ldo, R, C, relu);
+        COVA_LAUNCH(bn_act_fwd_kernel<4>, dim3(ew_grid(R * (C / 4))), dim3(256),
+                    (hipStream_t)stream, z, ldz, scale, shift, res, ldres, out, ldo, R, C, relu);
     else
-        hipLaunchKernelGGL(bn_act_fwd_kernel<1>, dim3(ew_grid(R * C)), dim3(256), 0,
-                           (hipStream_t)stream, z, ldz, scale, shift, res, ldres, out, ldo, R, C, relu);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(bn_act_fwd_kernel<1>, dim3(ew_grid(R * C)), dim3(256),
+                    (hipStream_t)stream, z, ldz, scale, shift, res, ldres, out, ldo, R, C, relu);
     return COVA_OK;
 }
 
@@ -716,9 +710,8 @@ COVA_API int cova_bn_act_fwd_bits(const float *z, const float *scale, const floa
 {
     COVA_REQUIRE(z && scale && shift && out && bits && R > 0);
     COVA_REQUIRE(vec4_ok(z, 64) && vec4_ok(res, 64) && vec4_ok(out, 64) && vec4_ok(scale, 0) && vec4_ok(shift, 0));
-    hipLaunchKernelGGL(bn_act_fwd_bits_kernel<1>, dim3(ew_grid(R * 16)), dim3(256), 0, (hipStream_t)stream, z, scale, shift,
-                       res, out, bits, R);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(bn_act_fwd_bits_kernel<1>, dim3(ew_grid(R * 16)), dim3(256), (hipStream_t)stream, z, scale, shift,
+                res, out, bits, R);
     return COVA_OK;
 }
 
@@ -730,9 +723,8 @@ COVA_API int cova_bn_act2_fwd(const float *z, const float *scale, const float *s
     COVA_REQUIRE(z && scale && shift && z2 && scale2 && shift2 && out && R > 0 && C > 0 && C % 4 == 0);
     COVA_REQUIRE(vec4_ok(z, C) && vec4_ok(z2, C) && vec4_ok(out, C) && vec4_ok(scale, 0) && vec4_ok(shift, 0) &&
                  vec4_ok(scale2, 0) && vec4_ok(shift2, 0));
-    hipLaunchKernelGGL(bn_act2_fwd_kernel, dim3(ew_grid(R * (C / 4))), dim3(256), 0, (hipStream_t)stream, z,
-                       scale, shift, z2, scale2, shift2, out, R, C, relu);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(bn_act2_fwd_kernel, dim3(ew_grid(R * (C / 4))), dim3(256), (hipStream_t)stream, z,
+                scale, shift, z2, scale2, shift2, out, R, C, relu);
     return COVA_OK;
 }
 
@@ -746,14 +738,12 @@ COVA_API int cova_bn_bwd_reduce(const float *dout, int ldd, const float *act, in
     const dim3 grid((unsigned)cdivll(R, rpc), (unsigned)cdiv(C, pow2_cols_host(C)));
     if (C == 64 && ldd == 64 && ldz == 64 && (act == nullptr || lda == 64) && vec4_ok(dout, ldd) &&
         vec4_ok(z, ldz) && vec4_ok(act, lda)) {
-        hipLaunchKernelGGL(colreduce64_kernel<1>, dim3(grid.x), dim3(256), 0, (hipStream_t)stream, dout,
-                           act, z, mean, invstd, partial, R, rpc);
-        COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(colreduce64_kernel<1>, dim3(grid.x), dim3(256), (hipStream_t)stream, dout,
+                    act, z, mean, invstd, partial, R, rpc);
         return COVA_OK;
     }
-    hipLaunchKernelGGL(colreduce_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, dout, ldd, act,
-                       lda, z, ldz, mean, invstd, partial, R, C, rpc);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(colreduce_kernel<1>, grid, dim3(256), (hipStream_t)stream, dout, ldd, act,
+                lda, z, ldz, mean, invstd, partial, R, C, rpc);
     return COVA_OK;
 }
 
@@ -762,9 +752,8 @@ COVA_API int cova_bn_finalize_bwd(const float *partial, int nparts, int C, doubl
                                   float *dgamma, float *dbeta, float *coef, void *stream)
 {
     COVA_REQUIRE(partial && coef && nparts > 0 && C > 0);
-    hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(cdiv(C, 64)), dim3(1024), 0, (hipStream_t)stream,
-                       partial, nparts, C, count, dgamma, dbeta, coef);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(bn_finalize_bwd_kernel, dim3(cdiv(C, 64)), dim3(1024), (hipStream_t)stream,
+                partial, nparts, C, count, dgamma, dbeta, coef);
     return COVA_OK;
 }
 
@@ -776,10 +765,9 @@ COVA_API int cova_bn_finalize_bwd_abc(const float *partial, int nparts, int C, d
                                       void *stream)
 {
     COVA_REQUIRE(partial && mean && invstd && scale && abc && nparts > 0 && C > 0);
-    hipLaunchKernelGGL(bn_finalize_bwd_abc_kernel, dim3(cdiv(C, 64)), dim3(1024), 0,
-                       (hipStream_t)stream, partial, nparts, C, count, dgamma, dbeta, mean, invstd,
-                       scale, abc);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(bn_finalize_bwd_abc_kernel, dim3(cdiv(C, 64)), dim3(1024),
+                (hipStream_t)stream, partial, nparts, C, count, dgamma, dbeta, mean, invstd,
+                scale, abc);
     return COVA_OK;
 }
 
@@ -793,14 +781,13 @@ COVA_API int cova_bn_bwd_apply(const float *dout, int ldd, const float *act, int
     const bool v4 = (C % 4 == 0) && vec4_ok(dout, ldd) && vec4_ok(act, lda) && vec4_ok(z, ldz) &&
                     vec4_ok(dz, lddz) && vec4_ok(dres, lddres);
     if (v4)
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, dim3(ew_grid(R * (C / 4))), dim3(256), 0,
-                           (hipStream_t)stream, dout, ldd, act, lda, z, ldz, mean, invstd, scale,
-                           coef, dz, lddz, dres, lddres, R, C);
+        COVA_LAUNCH(bn_bwd_apply_kernel<4>, dim3(ew_grid(R * (C / 4))), dim3(256),
+                    (hipStream_t)stream, dout, ldd, act, lda, z, ldz, mean, invstd, scale,
+                    coef, dz, lddz, dres, lddres, R, C);
     else
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3(ew_grid(R * C)), dim3(256), 0,
-                           (hipStream_t)stream, dout, ldd, act, lda, z, ldz, mean, invstd, scale,
-                           coef, dz, lddz, dres, lddres, R, C);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(bn_bwd_apply_kernel<1>, dim3(ew_grid(R * C)), dim3(256),
+                    (hipStream_t)stream, dout, ldd, act, lda, z, ldz, mean, invstd, scale,
+                    coef, dz, lddz, dres, lddres, R, C);
     return COVA_OK;
 }
 
@@ -817,9 +804,8 @@ COVA_API int cova_bn_relu_maxpool_fwd(const float *y, const float *scale, const 
     // one output row per thread on XCD-contiguous work blocks: the fastest of 17 launch shapes measured in round 5
     long long g = cdivll((long long)B * H2 * W2 * 16, 256);
     if (g > 0x7fffffffll) g = 0x7fffffffll;                          // (the kernel strides over what is left)
-    hipLaunchKernelGGL(bn_relu_maxpool_fwd_kernel<true>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, y, scale, shift,
-                       out, idx, ymax, B, H1, W1, H2, W2);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(bn_relu_maxpool_fwd_kernel<true>, dim3((unsigned)g), dim3(256), (hipStream_t)stream, y, scale, shift,
+                out, idx, ymax, B, H1, W1, H2, W2);
     return COVA_OK;
 }
 
@@ -840,10 +826,9 @@ COVA_API int cova_bn_relu_maxpool_bwd_reduce(const float *dp, const uint8_t *idx
     COVA_REQUIRE(dp && idx && y && scale && shift && mean && invstd && partial);
     const int H2 = (H1 + 2 - 3) / 2 + 1, W2 = (W1 + 2 - 3) / 2 + 1;
     const int grid = cova_bn_relu_maxpool_bwd_num_partials(B, H1, W1);
-    hipLaunchKernelGGL(bn_relu_maxpool_bwd_reduce_win_kernel, dim3(grid), dim3(256), 0,
-                       (hipStream_t)stream, dp, idx, y, scale, shift, mean, invstd, partial, B, H1, W1,
-                       H2, W2);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(bn_relu_maxpool_bwd_reduce_win_kernel, dim3(grid), dim3(256),
+                (hipStream_t)stream, dp, idx, y, scale, shift, mean, invstd, partial, B, H1, W1,
+                H2, W2);
     return COVA_OK;
 }
 
@@ -857,9 +842,8 @@ COVA_API int cova_bn_relu_maxpool_bwd_apply(const float *dp, const uint8_t *idx,
     COVA_REQUIRE(dp && idx && y && scale && shift && mean && invstd && coef && dz);
     const int H2 = (H1 + 2 - 3) / 2 + 1, W2 = (W1 + 2 - 3) / 2 + 1;
     const int grid = ew_grid((long long)B * H2 * W2 * 16);
-    hipLaunchKernelGGL(bn_relu_maxpool_bwd_apply_quad_kernel, dim3(grid), dim3(256), 0,
-                       (hipStream_t)stream, dp, idx, y, scale, shift, mean, invstd, coef, dz, B, H1, W1,
-                       H2, W2);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(bn_relu_maxpool_bwd_apply_quad_kernel, dim3(grid), dim3(256),
+                (hipStream_t)stream, dp, idx, y, scale, shift, mean, invstd, coef, dz, B, H1, W1,
+                H2, W2);
     return COVA_OK;
 }

@@ -363,10 +363,10 @@ COVA_API int cova_bn1d_fwd(const float *x, int ldx, int R, int C, const float *g
                     R <= 8 * V4_SLICES;
     if (v4) {
         const dim3 g4(cdiv(C, V4_COLS));
-#define BN1D_FWD_V4(NR_, DROP_)                                                                                             \
-        hipLaunchKernelGGL((bn1d_fwd_v4_kernel<NR_, DROP_>), g4, dim3(V4_THREADS), 0, (hipStream_t)stream, x, ldx, R, C, gamma, \
-                           beta, running_mean, running_var, num_batches_tracked, momentum, eps, relu, out, ldo, dropped,   \
-                           ld_dropped, mask, p, seed, mask_given, scale, shift, mean, invstd)
+#define BN1D_FWD_V4(NR_, DROP_)                                                                                       \
+        COVA_LAUNCH((bn1d_fwd_v4_kernel<NR_, DROP_>), g4, dim3(V4_THREADS), (hipStream_t)stream, x, ldx, R, C, gamma, \
+                    beta, running_mean, running_var, num_batches_tracked, momentum, eps, relu, out, ldo, dropped,     \
+                    ld_dropped, mask, p, seed, mask_given, scale, shift, mean, invstd)
         if (R <= 3 * V4_SLICES) { if (dropped) BN1D_FWD_V4(3, true); else BN1D_FWD_V4(3, false); }
         else if (R <= 6 * V4_SLICES) { if (dropped) BN1D_FWD_V4(6, true); else BN1D_FWD_V4(6, false); }
         else { if (dropped) BN1D_FWD_V4(8, true); else BN1D_FWD_V4(8, false); }
@@ -376,14 +376,13 @@ COVA_API int cova_bn1d_fwd(const float *x, int ldx, int R, int C, const float *g
     }
     const dim3 grid(cdiv(C, COLS));
     if (dropped)
-        hipLaunchKernelGGL(bn1d_fwd_kernel<true>, grid, dim3(THREADS), 0, (hipStream_t)stream, x, ldx, R, C, gamma, beta,
-                           running_mean, running_var, num_batches_tracked, momentum, eps, relu, out, ldo, dropped,
-                           ld_dropped, mask, p, seed, mask_given, scale, shift, mean, invstd);
+        COVA_LAUNCH(bn1d_fwd_kernel<true>, grid, dim3(THREADS), (hipStream_t)stream, x, ldx, R, C, gamma, beta,
+                    running_mean, running_var, num_batches_tracked, momentum, eps, relu, out, ldo, dropped,
+                    ld_dropped, mask, p, seed, mask_given, scale, shift, mean, invstd);
     else
-        hipLaunchKernelGGL(bn1d_fwd_kernel<false>, grid, dim3(THREADS), 0, (hipStream_t)stream, x, ldx, R, C, gamma, beta,
-                           running_mean, running_var, num_batches_tracked, momentum, eps, relu, out, ldo, dropped,
-                           ld_dropped, mask, p, seed, mask_given, scale, shift, mean, invstd);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(bn1d_fwd_kernel<false>, grid, dim3(THREADS), (hipStream_t)stream, x, ldx, R, C, gamma, beta,
+                    running_mean, running_var, num_batches_tracked, momentum, eps, relu, out, ldo, dropped,
+                    ld_dropped, mask, p, seed, mask_given, scale, shift, mean, invstd);
     return COVA_OK;
 }
 
@@ -398,9 +397,9 @@ COVA_API int cova_bn1d_bwd(const float *dout, int ldg, const uint8_t *drop_mask,
                     (drop_mask == nullptr || ((uintptr_t)drop_mask & 3) == 0) && R <= 6 * V4_SLICES;   // (8 rows: 128 registers, spills)
     if (v4) {
         const dim3 g4(cdiv(C, V4_COLS));
-#define BN1D_BWD_V4(NR_, DROP_)                                                                                             \
-        hipLaunchKernelGGL((bn1d_bwd_v4_kernel<NR_, DROP_>), g4, dim3(V4_THREADS), 0, (hipStream_t)stream, dout, ldg, drop_mask, \
-                           p, act, lda, z, ldz, mean, invstd, scale, R, C, dgamma, dbeta, dz, lddz, dz_colsum)
+#define BN1D_BWD_V4(NR_, DROP_)                                                                                        \
+        COVA_LAUNCH((bn1d_bwd_v4_kernel<NR_, DROP_>), g4, dim3(V4_THREADS), (hipStream_t)stream, dout, ldg, drop_mask, \
+                    p, act, lda, z, ldz, mean, invstd, scale, R, C, dgamma, dbeta, dz, lddz, dz_colsum)
         if (R <= 3 * V4_SLICES) { if (drop_mask) BN1D_BWD_V4(3, true); else BN1D_BWD_V4(3, false); }
         else { if (drop_mask) BN1D_BWD_V4(6, true); else BN1D_BWD_V4(6, false); }
 #undef BN1D_BWD_V4
@@ -409,11 +408,10 @@ COVA_API int cova_bn1d_bwd(const float *dout, int ldg, const uint8_t *drop_mask,
     }
     const dim3 grid(cdiv(C, COLS));
     if (drop_mask)
-        hipLaunchKernelGGL(bn1d_bwd_kernel<true>, grid, dim3(THREADS), 0, (hipStream_t)stream, dout, ldg, drop_mask, p, act,
-                           lda, z, ldz, mean, invstd, scale, R, C, dgamma, dbeta, dz, lddz, dz_colsum);
+        COVA_LAUNCH(bn1d_bwd_kernel<true>, grid, dim3(THREADS), (hipStream_t)stream, dout, ldg, drop_mask, p, act,
+                    lda, z, ldz, mean, invstd, scale, R, C, dgamma, dbeta, dz, lddz, dz_colsum);
     else
-        hipLaunchKernelGGL(bn1d_bwd_kernel<false>, grid, dim3(THREADS), 0, (hipStream_t)stream, dout, ldg, drop_mask, p, act,
-                           lda, z, ldz, mean, invstd, scale, R, C, dgamma, dbeta, dz, lddz, dz_colsum);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(bn1d_bwd_kernel<false>, grid, dim3(THREADS), (hipStream_t)stream, dout, ldg, drop_mask, p, act,
+                    lda, z, ldz, mean, invstd, scale, R, C, dgamma, dbeta, dz, lddz, dz_colsum);
     return COVA_OK;
 }

@@ -6,7 +6,6 @@
 #pragma once
 #include "common.h"
 
-#include "../../include/cova_hip.h"
 typedef cova_bn_tail BnTail;      // (a plain C struct of device pointers; passed to the kernels by value)
 
 // per-channel results from the fp64 totals -- shared with bn.hip's stand-alone kernels

@@ -4,17 +4,27 @@
 #include <stdint.h>
 #include <float.h>
 
+// The public C ABI, in front of every definition: a COVA_API function that disagrees with its prototype, or has none, does
+// not compile (-Werror=missing-prototypes, _build.py).  COVA_ERR_BAD_ARG, COVA_GAT_MAX_K and cova_bn_tail come from it.
+#include "../../include/cova_hip.h"
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #define COVA_OK 0
-#define COVA_ERR_BAD_ARG 10001
 
 #define COVA_LAUNCH_CHECK()                         \
     do {                                            \
         hipError_t e__ = hipGetLastError();         \
         if (e__ != hipSuccess) return (int)e__;     \
+    } while (0)
+
+// One kernel launch (no dynamic LDS) and its own check: returns the launch's error from the enclosing function.
+#define COVA_LAUNCH(kernel, grid, block, stream, ...)                           \
+    do {                                                                        \
+        hipLaunchKernelGGL((kernel), grid, block, 0, stream, __VA_ARGS__);      \
+        COVA_LAUNCH_CHECK();                                                    \
     } while (0)
 
 #define COVA_REQUIRE(cond)                          \
@@ -23,10 +33,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
     } while (0)
 
 #define COVA_API extern "C" __attribute__((visibility("default")))
-
-// neighbour slots per node the wave-per-node GAT kernels hold in registers: up to sixteen 64-lane passes (-cs <= 512: far
-// beyond the boxes of a page -- slots past a page's size are pads; models.py:171-177 itself takes any n_context)
-#define COVA_GAT_MAX_K 1024
 
 // v_mfma_f32_32x32x2_f32: D[32x32] += A[32x2] * B[2x32], exact f32 FMA chain.
 // lane l supplies A[i = l&31][k = l>>5] and B[k = l>>5][j = l&31];

@@ -1396,40 +1396,18 @@ __global__ __launch_bounds__(1024) void conv1_wgrad_reduce_kernel(const float *_
     }
 }
 
-inline int persistent_grid(int ntiles, int blocks_per_cu = 1)
-{
-    // compute units of the CURRENT device (the caller launches under the device guard of its tensors; the host
-    // queries run under the same guard): cached per device id, not once per process
-    static int cus_of[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    int cus = cus_of[dev];
-    if (cus == 0) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-        cus_of[dev] = cus;
-    }
-    int g = ntiles < cus * blocks_per_cu ? ntiles : cus * blocks_per_cu;
-    const int cap = cova_options().grid_cap;
-    if (cap > 0 && g > cap) g = cap;
-    return g;
-}
-
 }  // namespace
-
-// for the other translation units (options.h)
-int cova_internal_persistent_grid(int ntiles) { return persistent_grid(ntiles); }
-int cova_internal_persistent_grid2(int ntiles, int blocks_per_cu) { return persistent_grid(ntiles, blocks_per_cu); }
 
 // ====================================================================================
 // C ABI
 // ====================================================================================
 #ifdef C1B_TRACE
+COVA_API int cova_wg1b_trace_read(unsigned long long *host);      // (tools only: not in include/cova_hip.h)
 COVA_API int cova_wg1b_trace_read(unsigned long long *host)
 {
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_wg1b_trace), sizeof(unsigned long long) * 8 * 20 * 8);
 }
+COVA_API int cova_c1b_trace_read(unsigned long long *host);
 COVA_API int cova_c1b_trace_read(unsigned long long *host)
 {
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_c1b_trace), sizeof(unsigned long long) * 2 * 4 * 20 * 8);
@@ -1456,15 +1434,14 @@ static int conv1_fwd_tiles(int B, int H, int W)
 
 COVA_API int cova_conv1_num_partials(int B, int H, int W)
 {
-    return persistent_grid(conv1_fwd_tiles(B, H, W), cova_options().conv1_f32 ? 2 : 1);
+    return cova_internal_persistent_grid(conv1_fwd_tiles(B, H, W), cova_options().conv1_f32 ? 2 : 1);
 }
 
 COVA_API int cova_conv1_prep_weights(const float *w_oihw, float *w_k, void *stream)
 {
     COVA_REQUIRE(w_oihw && w_k);
-    hipLaunchKernelGGL(prep_w7x7_kernel, dim3(cdiv(c1::W_FLOATS, 256)), dim3(256), 0,
-                       (hipStream_t)stream, w_oihw, w_k);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(prep_w7x7_kernel, dim3(cdiv(c1::W_FLOATS, 256)), dim3(256),
+                (hipStream_t)stream, w_oihw, w_k);
     return COVA_OK;
 }
 
@@ -1482,27 +1459,25 @@ static int conv1_fwd_launch(const float *img, const float *w_k, int w_oihw, floa
     if (!cova_options().conv1_f32) {
         const int tiles_x = cdiv(W1, c1b::TW), tiles_y = cdiv(H1, c1b::TH);
         const int ntiles = B * tiles_x * tiles_y;
-        const dim3 pgrid(persistent_grid(ntiles, 1)), block(c1b::THREADS);
+        const dim3 pgrid(cova_internal_persistent_grid(ntiles, 1)), block(c1b::THREADS);
         if (stat_part)
-            hipLaunchKernelGGL(conv1_7x7_bf3_kernel<true>, pgrid, block, 0, (hipStream_t)stream, img, w_k, out, stat_part,
-                               H, W, H1, W1, tiles_x, tiles_y, ntiles, w_oihw, t);
+            COVA_LAUNCH(conv1_7x7_bf3_kernel<true>, pgrid, block, (hipStream_t)stream, img, w_k, out, stat_part,
+                        H, W, H1, W1, tiles_x, tiles_y, ntiles, w_oihw, t);
         else
-            hipLaunchKernelGGL(conv1_7x7_bf3_kernel<false>, pgrid, block, 0, (hipStream_t)stream, img, w_k, out,
-                               stat_part, H, W, H1, W1, tiles_x, tiles_y, ntiles, w_oihw, t);
-        COVA_LAUNCH_CHECK();
+            COVA_LAUNCH(conv1_7x7_bf3_kernel<false>, pgrid, block, (hipStream_t)stream, img, w_k, out,
+                        stat_part, H, W, H1, W1, tiles_x, tiles_y, ntiles, w_oihw, t);
         return COVA_OK;
     }
     const int tiles_x = cdiv(W1, c1::TW), tiles_y = cdiv(H1, c1::TH);
     const dim3 block(c1::THREADS);
     const int ntiles = B * tiles_x * tiles_y;
-    const dim3 pgrid(persistent_grid(ntiles, 2));
+    const dim3 pgrid(cova_internal_persistent_grid(ntiles, 2));
     if (stat_part)
-        hipLaunchKernelGGL(conv1_7x7_v2_kernel<true>, pgrid, block, 0, (hipStream_t)stream, img,
-                           w_k, out, stat_part, H, W, H1, W1, tiles_x, tiles_y, ntiles, w_oihw, t);
+        COVA_LAUNCH(conv1_7x7_v2_kernel<true>, pgrid, block, (hipStream_t)stream, img,
+                    w_k, out, stat_part, H, W, H1, W1, tiles_x, tiles_y, ntiles, w_oihw, t);
     else
-        hipLaunchKernelGGL(conv1_7x7_v2_kernel<false>, pgrid, block, 0, (hipStream_t)stream, img,
-                           w_k, out, stat_part, H, W, H1, W1, tiles_x, tiles_y, ntiles, w_oihw, t);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(conv1_7x7_v2_kernel<false>, pgrid, block, (hipStream_t)stream, img,
+                    w_k, out, stat_part, H, W, H1, W1, tiles_x, tiles_y, ntiles, w_oihw, t);
     return COVA_OK;
 }
 
@@ -1522,7 +1497,7 @@ COVA_API int cova_conv1_fwd_tail(const float *img, const float *w_oihw, float *o
 
 COVA_API int cova_conv1_wgrad_workspace_floats(int B, int H, int W)
 {
-    return persistent_grid(cova_conv1_num_tiles(B, H, W)) * 8 * 64 * 160;
+    return cova_internal_persistent_grid(cova_conv1_num_tiles(B, H, W)) * 8 * 64 * 160;
 }
 
 // POOL: gy = y1 and pb routes the pooled gradient through the BatchNorm+ReLU+MaxPool backward apply on load; else gy = dy
@@ -1532,25 +1507,21 @@ static int conv1_wgrad_launch(const float *img, const float *gy, const PoolBwd p
 {
     const int H1 = cova_conv_out_size(H, 7, 2, 3), W1 = cova_conv_out_size(W, 7, 2, 3);
     const int tiles_x = cdiv(W1, wg1::TW), tiles_y = cdiv(H1, wg1::TH);
-    const int grid = persistent_grid(B * tiles_x * tiles_y);
+    const int grid = cova_internal_persistent_grid(B * tiles_x * tiles_y);
     if (!cova_options().conv1_f32) {
         const int rtx = cdiv(W1, wg1r::TW), rty = cdiv(H1, wg1r::TH);
-        const int rgrid = persistent_grid(B * rtx * rty);
-        hipLaunchKernelGGL(conv1_wgrad_rs_kernel<POOL>, dim3(rgrid), dim3(wg1r::THREADS), 0, (hipStream_t)stream, img, gy,
-                           ws, H, W, H1, W1, rtx, rty, B * rtx * rty, pb);
-        COVA_LAUNCH_CHECK();
-        hipLaunchKernelGGL(conv1_wgrad_reduce_kernel, dim3(64 * 160 / 64), dim3(1024), 0, (hipStream_t)stream, ws,
-                           rgrid * 2, dw);
-        COVA_LAUNCH_CHECK();
+        const int rgrid = cova_internal_persistent_grid(B * rtx * rty);
+        COVA_LAUNCH(conv1_wgrad_rs_kernel<POOL>, dim3(rgrid), dim3(wg1r::THREADS), (hipStream_t)stream, img, gy,
+                    ws, H, W, H1, W1, rtx, rty, B * rtx * rty, pb);
+        COVA_LAUNCH(conv1_wgrad_reduce_kernel, dim3(64 * 160 / 64), dim3(1024), (hipStream_t)stream, ws,
+                    rgrid * 2, dw);
         return COVA_OK;
     }
-    hipLaunchKernelGGL(conv1_wgrad_v2_kernel<POOL>, dim3(grid), dim3(wg1::THREADS), 0,
-                       (hipStream_t)stream, img, gy, ws, H, W, H1, W1, tiles_x, tiles_y,
-                       B * tiles_x * tiles_y, pb);
-    COVA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(conv1_wgrad_reduce_kernel, dim3(64 * 160 / 64), dim3(1024), 0,
-                       (hipStream_t)stream, ws, grid * 4, dw);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(conv1_wgrad_v2_kernel<POOL>, dim3(grid), dim3(wg1::THREADS),
+                (hipStream_t)stream, img, gy, ws, H, W, H1, W1, tiles_x, tiles_y,
+                B * tiles_x * tiles_y, pb);
+    COVA_LAUNCH(conv1_wgrad_reduce_kernel, dim3(64 * 160 / 64), dim3(1024),
+                (hipStream_t)stream, ws, grid * 4, dw);
     return COVA_OK;
 }
 

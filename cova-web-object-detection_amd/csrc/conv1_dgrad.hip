@@ -103,8 +103,6 @@ __global__ __launch_bounds__(256) void conv1_dgrad_kernel(const float *__restric
 
 }  // namespace
 
-COVA_API int cova_conv_out_size(int in_size, int kernel, int stride, int pad);
-
 // dy1 NHWC [B,H1,W1,64] = abc[0]*route(dp, idx) + abc[1]*y1 + abc[2]: the operand cova_conv1_wgrad_poolbwd forms on load,
 // materialised (dp [B,H2,W2,64] already ReLU-masked, idx from cova_bn_relu_maxpool_fwd, abc [3,64])
 COVA_API int cova_pool_bwd_dy1(const float *dp, const uint8_t *idx, const float *y1, const float *abc, float *dy1, int B,
@@ -115,9 +113,8 @@ COVA_API int cova_pool_bwd_dy1(const float *dp, const uint8_t *idx, const float 
     const long long npix = (long long)B * H1 * W1;
     const long long want = cdivll(npix, 16);
     const int grid = (int)(want < 65536 ? want : 65536);
-    hipLaunchKernelGGL(pool_bwd_dy1_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, dp, idx, y1, abc, dy1, B, H1, W1,
-                       H2, W2);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(pool_bwd_dy1_kernel, dim3(grid), dim3(256), (hipStream_t)stream, dp, idx, y1, abc, dy1, B, H1, W1,
+                H2, W2);
     return COVA_OK;
 }
 
@@ -126,8 +123,7 @@ COVA_API int cova_conv1_dgrad(const float *dy1, const float *w_oihw, float *dimg
 {
     COVA_REQUIRE(dy1 && w_oihw && dimg && B > 0 && H > 0 && W > 0 && B <= 65535);
     const int H1 = cova_conv_out_size(H, 7, 2, 3), W1 = cova_conv_out_size(W, 7, 2, 3);
-    hipLaunchKernelGGL(conv1_dgrad_kernel, dim3(cdiv(W, 16), cdiv(H, 16), B), dim3(256), 0, (hipStream_t)stream, dy1, w_oihw,
-                       dimg, H, W, H1, W1);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(conv1_dgrad_kernel, dim3(cdiv(W, 16), cdiv(H, 16), B), dim3(256), (hipStream_t)stream, dy1, w_oihw,
+                dimg, H, W, H1, W1);
     return COVA_OK;
 }

@@ -3,7 +3,7 @@
 // and layer1 = 3 Bottleneck blocks: 1x1 Cin->64, 3x3 64->64, 1x1 64->256, + a 1x1 64->256
 // downsample branch in block 0).  The reference itself only wires resnet18 (models.py:49); this
 // file is the build-defined extension of that call site, with the same NHWC layout and the same
-// prologue / epilogue conventions as the Winograd 3x3 kernels (conv_wino.hip):
+// prologue / epilogue conventions as the Winograd 3x3 kernels (conv_wino4.hip):
 //
 //   out[r, co] = sum_ci f(A[ci]*in[r,ci] + B[ci]*in2[r,ci] + C[ci]) * w[co, ci]      r = pixel row
 //
@@ -748,21 +748,20 @@ int launch_c11(const C11Args &a, int epi, bool has_add, bool mask_act, bool has_
 {
     // eight waves, one block per CU (room for the coalesced-operand transposer): grid = c11_grid(R), which is also the
     // number of statistics rows (cova_conv1x1_num_partials)
-#define C11_LAUNCH(PRO, EPI, ADD, MA, X2)                                                            \
-    do {                                                                                             \
-        hipLaunchKernelGGL((conv1x1_kernel<CIN, COUT, PRO, EPI, ADD, MA, X2, false, 8>), dim3(grid), dim3(512), \
-                           0, st, a);                                                                \
-        return COVA_OK;                                                                              \
+#define C11_LAUNCH(PRO, EPI, ADD, MA, X2)                                                                        \
+    do {                                                                                                         \
+        COVA_LAUNCH((conv1x1_kernel<CIN, COUT, PRO, EPI, ADD, MA, X2, false, 8>), dim3(grid), dim3(512), st, a); \
+        return COVA_OK;                                                                                          \
     } while (0)
     if (a.side) {           // materialising consumer: 256 -> 64 forward with the two-tensor prologue
         if constexpr (CIN == 256) {
             if (pro != 2 || epi > 1) return COVA_ERR_BAD_ARG;
             if (epi == 1)
-                hipLaunchKernelGGL((conv1x1_kernel<CIN, COUT, 2, 1, false, false, false, false, 8, true>), dim3(grid),
-                                   dim3(512), 0, st, a);
+                COVA_LAUNCH((conv1x1_kernel<CIN, COUT, 2, 1, false, false, false, false, 8, true>), dim3(grid),
+                            dim3(512), st, a);
             else
-                hipLaunchKernelGGL((conv1x1_kernel<CIN, COUT, 2, 0, false, false, false, false, 8, true>), dim3(grid),
-                                   dim3(512), 0, st, a);
+                COVA_LAUNCH((conv1x1_kernel<CIN, COUT, 2, 0, false, false, false, false, 8, true>), dim3(grid),
+                            dim3(512), st, a);
             return COVA_OK;
         }
         return COVA_ERR_BAD_ARG;
@@ -804,7 +803,7 @@ int launch_c11(const C11Args &a, int epi, bool has_add, bool mask_act, bool has_
 inline int c11_grid(long long R)            // 32-row tiles, eight waves per block, one block per CU
 {
     const long long ntiles = (R + 31) / 32, nb = (ntiles + 7) / 8;
-    return cova_internal_persistent_grid2(nb > (1 << 30) ? (1 << 30) : (int)nb, 1);
+    return cova_internal_persistent_grid(nb > (1 << 30) ? (1 << 30) : (int)nb, 1);
 }
 
 }  // namespace
@@ -852,13 +851,10 @@ COVA_API int cova_conv1x1(const float *in, const float *in2, const float *pro_ab
     const bool masked = act != nullptr || act_bits != nullptr;
     const int grid = c11_grid(R);
     hipStream_t st = (hipStream_t)stream;
-    int rc = COVA_ERR_BAD_ARG;
-    if (Cin == 64 && Cout == 64) rc = launch_c11<64, 64>(a, epi, addend != nullptr, masked, z2 != nullptr, pro, grid, st);
-    else if (Cin == 64 && Cout == 256) rc = launch_c11<64, 256>(a, epi, addend != nullptr, masked, z2 != nullptr, pro, grid, st);
-    else if (Cin == 256 && Cout == 64) rc = launch_c11<256, 64>(a, epi, addend != nullptr, masked, z2 != nullptr, pro, grid, st);
-    if (rc != COVA_OK) return rc;
-    COVA_LAUNCH_CHECK();
-    return COVA_OK;
+    if (Cin == 64 && Cout == 64) return launch_c11<64, 64>(a, epi, addend != nullptr, masked, z2 != nullptr, pro, grid, st);
+    if (Cin == 64 && Cout == 256) return launch_c11<64, 256>(a, epi, addend != nullptr, masked, z2 != nullptr, pro, grid, st);
+    if (Cin == 256 && Cout == 64) return launch_c11<256, 64>(a, epi, addend != nullptr, masked, z2 != nullptr, pro, grid, st);
+    return COVA_ERR_BAD_ARG;
 }
 
 // cova_conv1x1 (Cin = 256, Cout = 64, forward) whose input is the previous Bottleneck's output
@@ -875,10 +871,7 @@ COVA_API int cova_conv1x1_materialize(const float *in, const float *in2, const f
     const C11Args a{in, in2, pro_abc, w, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                     nullptr, nullptr, out, stat_part, nullptr, R, 1, 0, nullptr, nullptr, nullptr, nullptr, 0, side,
                     side_bits, nullptr};
-    const int rc = launch_c11<256, 64>(a, stat_part ? 1 : 0, false, false, false, 2, c11_grid(R), (hipStream_t)stream);
-    if (rc != COVA_OK) return rc;
-    COVA_LAUNCH_CHECK();
-    return COVA_OK;
+    return launch_c11<256, 64>(a, stat_part ? 1 : 0, false, false, false, 2, c11_grid(R), (hipStream_t)stream);
 }
 
 // Data gradient of (1x1 conv 64->256, train-mode BatchNorm) in its LINEAR form (conv1x1_lin.hip): with
@@ -891,7 +884,7 @@ COVA_API int cova_conv1x1_materialize(const float *in, const float *in2, const f
 COVA_API int cova_conv1x1_lin_dgrad_num_partials(long long R)
 {
     const long long ntiles = (R + 31) / 32, nb = (ntiles + 7) / 8;
-    return cova_internal_persistent_grid2(nb > (1 << 30) ? (1 << 30) : (int)nb, 1);
+    return cova_internal_persistent_grid(nb > (1 << 30) ? (1 << 30) : (int)nb, 1);
 }
 
 COVA_API int cova_conv1x1_lin_dgrad(const float *v, const float *avec, const float *w, const float *act,
@@ -908,17 +901,16 @@ COVA_API int cova_conv1x1_lin_dgrad(const float *v, const float *avec, const flo
     const int grid = cova_conv1x1_lin_dgrad_num_partials(R);
     hipStream_t st = (hipStream_t)stream;
     if (addend)
-        hipLaunchKernelGGL((conv1x1_kernel<256, 64, 1, 2, true, false, false, true, 8>), dim3(grid), dim3(512), 0, st, a);
+        COVA_LAUNCH((conv1x1_kernel<256, 64, 1, 2, true, false, false, true, 8>), dim3(grid), dim3(512), st, a);
     else
-        hipLaunchKernelGGL((conv1x1_kernel<256, 64, 1, 2, false, false, false, true, 8>), dim3(grid), dim3(512), 0, st, a);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH((conv1x1_kernel<256, 64, 1, 2, false, false, false, true, 8>), dim3(grid), dim3(512), st, a);
     return COVA_OK;
 }
 
 COVA_API int cova_conv1x1_wgrad_workspace_floats(long long R, int Co, int Ci)
 {
     (void)R;
-    return cova_internal_persistent_grid2(1 << 30, 2) * Co * Ci;
+    return cova_internal_persistent_grid(1 << 30, 2) * Co * Ci;
 }
 
 // Weight gradient of the same convolution: dw [Co][Ci] (= OIHW [Co,Ci,1,1]) = sum_r fz(dz)[r,co] * fa(act)[r,ci]
@@ -932,24 +924,22 @@ COVA_API int cova_conv1x1_wgrad(const float *dz, const float *dz2, const float *
     COVA_REQUIRE(!dz_abc || dz2);
     const W11Args a{dz, dz2, dz_abc, act, act_abc, ws, R, act_relu};
     const long long npairs = (R + 1) / 2, want = (npairs + 63) / 64;       // >= 64 pairs per block
-    int grid = cova_internal_persistent_grid2(want > (1 << 30) ? (1 << 30) : (int)want, 2);
+    int grid = cova_internal_persistent_grid(want > (1 << 30) ? (1 << 30) : (int)want, 2);
     hipStream_t st = (hipStream_t)stream;
     const bool pz = dz_abc != nullptr, pa = act_abc != nullptr;
-#define W11_LAUNCH(CO, CI)                                                                                  \
-    do {                                                                                                    \
-        if (pz && pa) hipLaunchKernelGGL((conv1x1_wgrad_kernel<CO, CI, true, true>), dim3(grid), dim3(256), 0, st, a);   \
-        else if (pz) hipLaunchKernelGGL((conv1x1_wgrad_kernel<CO, CI, true, false>), dim3(grid), dim3(256), 0, st, a);   \
-        else if (pa) hipLaunchKernelGGL((conv1x1_wgrad_kernel<CO, CI, false, true>), dim3(grid), dim3(256), 0, st, a);   \
-        else hipLaunchKernelGGL((conv1x1_wgrad_kernel<CO, CI, false, false>), dim3(grid), dim3(256), 0, st, a);          \
+#define W11_LAUNCH(CO, CI)                                                                                   \
+    do {                                                                                                     \
+        if (pz && pa) COVA_LAUNCH((conv1x1_wgrad_kernel<CO, CI, true, true>), dim3(grid), dim3(256), st, a); \
+        else if (pz) COVA_LAUNCH((conv1x1_wgrad_kernel<CO, CI, true, false>), dim3(grid), dim3(256), st, a); \
+        else if (pa) COVA_LAUNCH((conv1x1_wgrad_kernel<CO, CI, false, true>), dim3(grid), dim3(256), st, a); \
+        else COVA_LAUNCH((conv1x1_wgrad_kernel<CO, CI, false, false>), dim3(grid), dim3(256), st, a);        \
     } while (0)
     if (Co == 64 && Ci == 64) W11_LAUNCH(64, 64);
     else if (Co == 256 && Ci == 64) W11_LAUNCH(256, 64);
     else if (Co == 64 && Ci == 256) W11_LAUNCH(64, 256);
     else return COVA_ERR_BAD_ARG;
 #undef W11_LAUNCH
-    COVA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(conv1x1_wgrad_reduce_kernel, dim3(cdiv(Co * Ci, 64)), dim3(1024), 0, st, ws, grid,
-                       Co * Ci, dw);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(conv1x1_wgrad_reduce_kernel, dim3(cdiv(Co * Ci, 64)), dim3(1024), st, ws, grid,
+                Co * Ci, dw);
     return COVA_OK;
 }

@@ -276,7 +276,7 @@ __global__ __launch_bounds__(64) void lin_finish_kernel(const float *__restrict_
 inline int vprod_grid(long long R)
 {
     const long long npairs = (R + 1) / 2, want = (npairs + 63) / 64;
-    return cova_internal_persistent_grid2(want > (1 << 30) ? (1 << 30) : (int)want, 2);
+    return cova_internal_persistent_grid(want > (1 << 30) ? (1 << 30) : (int)want, 2);
 }
 
 }  // namespace
@@ -289,7 +289,7 @@ COVA_API int cova_conv1x1_lin_floats(void) { return LIN_FLOATS; }
 COVA_API int cova_conv1x1_vprod_workspace_floats(long long R)
 {
     (void)R;
-    const long long nb = cova_internal_persistent_grid2(1 << 30, 2);
+    const long long nb = cova_internal_persistent_grid(1 << 30, 2);
     return (int)(nb * (CO * CI + 4 * CI * CI + 4 * CI + CO));
 }
 
@@ -302,10 +302,8 @@ COVA_API int cova_conv1x1_vprod(const float *v, const float *act, const float *a
     const VPArgs a{v, act, act_abc, ws, R, act_relu};
     const int grid = vprod_grid(R);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(conv1x1_vprod_kernel, dim3(grid), dim3(256), 0, st, a);
-    COVA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(vprod_reduce_kernel, dim3(cdiv(LIN_FLOATS, 64)), dim3(1024), 0, st, ws, grid, lin);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(conv1x1_vprod_kernel, dim3(grid), dim3(256), st, a);
+    COVA_LAUNCH(vprod_reduce_kernel, dim3(cdiv(LIN_FLOATS, 64)), dim3(1024), st, ws, grid, lin);
     return COVA_OK;
 }
 
@@ -314,8 +312,7 @@ COVA_API int cova_conv1x1_lin_bnsums(const float *lin, const float *w, const flo
                                      float *part, void *stream)
 {
     COVA_REQUIRE(lin && w && mean && invstd && part);
-    hipLaunchKernelGGL(lin_bnsums_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, lin, w, mean, invstd, part);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(lin_bnsums_kernel, dim3(1), dim3(256), (hipStream_t)stream, lin, w, mean, invstd, part);
     return COVA_OK;
 }
 
@@ -325,8 +322,7 @@ COVA_API int cova_conv1x1_lin_finish(const float *lin, const float *abc, const f
                                      float *cvec, float *avec, void *stream)
 {
     COVA_REQUIRE(lin && abc && w && dw && m && cvec && avec);
-    hipLaunchKernelGGL(lin_finish_kernel, dim3(CO + CI + 1), dim3(64), 0, (hipStream_t)stream, lin, abc, w, dw, m,
-                       cvec, avec);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(lin_finish_kernel, dim3(CO + CI + 1), dim3(64), (hipStream_t)stream, lin, abc, w, dw, m,
+                cvec, avec);
     return COVA_OK;
 }

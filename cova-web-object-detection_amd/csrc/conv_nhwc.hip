@@ -309,9 +309,8 @@ int launch_gather(const float *src0, const float *src1, const float *w0, const f
     if (mmax == 0) return COVA_OK;
     const long long gx = cdivll(mmax, BM);
     if (gx > 0x7fffffffLL) return COVA_ERR_BAD_ARG;
-    hipLaunchKernelGGL(conv_nhwc_gather_kernel<BN>, dim3((unsigned)gx, N / BN, plan.ncls), dim3(NTHREADS), 0, stream,
-                       src0, src1, w0, w1, addend, out, plan, B, Hs, Ws, Cs, Ho, Wo, N);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(conv_nhwc_gather_kernel<BN>, dim3((unsigned)gx, N / BN, plan.ncls), dim3(NTHREADS), stream,
+                src0, src1, w0, w1, addend, out, plan, B, Hs, Ws, Cs, Ho, Wo, N);
     return COVA_OK;
 }
 
@@ -331,9 +330,8 @@ COVA_API int cova_conv_nhwc_prep(const float *w_oihw, float *w_fwd, float *w_dgr
     hipStream_t stream = (hipStream_t)stream_;
     COVA_REQUIRE(w_oihw != nullptr && Co > 0 && Ci > 0 && k > 0);
     const int n = Co * Ci * k * k;
-    hipLaunchKernelGGL(conv_nhwc_prep_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, w_oihw, w_fwd, w_dgrad, Co, Ci,
-                       k * k);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(conv_nhwc_prep_kernel, dim3(cdiv(n, 256)), dim3(256), stream, w_oihw, w_fwd, w_dgrad, Co, Ci,
+                k * k);
     return COVA_OK;
 }
 
@@ -429,11 +427,9 @@ COVA_API int cova_conv_nhwc_wgrad(const float *in, const float *dy, float *dw /*
     const int row_tiles = K / WG_ROWS, col_tiles = Co / WG_COLS;
     const long long per = wgrad_per_part(M, row_tiles, col_tiles);
     const int parts = (int)cdivll(M, per);
-    hipLaunchKernelGGL(conv_nhwc_wgrad_partial_kernel, dim3(row_tiles, col_tiles, parts), dim3(NTHREADS), 0, stream,
-                       in, dy, ws, B, H, W, Ci, Ho, Wo, Co, k, stride, pad, per);
-    COVA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(conv_nhwc_wgrad_finish_kernel, dim3(cdiv(K * Co, 256)), dim3(256), 0, stream, ws, dw, parts, Ci,
-                       Co, k * k);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(conv_nhwc_wgrad_partial_kernel, dim3(row_tiles, col_tiles, parts), dim3(NTHREADS), stream,
+                in, dy, ws, B, H, W, Ci, Ho, Wo, Co, k, stride, pad, per);
+    COVA_LAUNCH(conv_nhwc_wgrad_finish_kernel, dim3(cdiv(K * Co, 256)), dim3(256), stream, ws, dw, parts, Ci,
+                Co, k * k);
     return COVA_OK;
 }

@@ -5,7 +5,7 @@
 //
 // i.e. for each of the 36 transform positions one GEMM  Q[pos][co][ci] = sum_tiles Wd[pos][co][tile] * V[pos][tile][ci]
 // with K = number of 4x4 tiles: 36 * 64 * 64 MACs per 16 pixels = 2.25 per (pixel, co, ci) instead of 9 (direct) or 4
-// (the F(2x2,3x3) kernel of conv_wino.hip: 1.78x more MFMAs).  fp32 error against fp64 on this layer: 3.7e-6 of the
+// (the F(2x2,3x3) kernel of tools/csrc/conv_wino_f2x2.hip: 1.78x more MFMAs).  fp32 error against fp64 on this layer: 3.7e-6 of the
 // gradient's scale (F(2x2): 5.9e-7, direct fp32: 2.9e-6; numpy study in DESIGN.md section 11).
 //
 // Mapping:
@@ -726,7 +726,7 @@ Wg4Geo wg4_geometry(int B, int H, int W)
     g.seg_rows = cdiv(g.tiles_y, g.nseg_y);
     g.nseg_y = cdiv(g.tiles_y, g.seg_rows);
     g.nsegs = B * g.strips * g.nseg_y;
-    const int cus = cova_internal_persistent_grid2(1 << 30, 1);                // (honours the tests' grid cap)
+    const int cus = cova_internal_persistent_grid(1 << 30, 1);                // (honours the tests' grid cap)
     int walkers = cus / 2 > 0 ? cus / 2 : 1;
     if (walkers > g.nsegs) walkers = g.nsegs;
     g.grid = 2 * walkers;
@@ -741,7 +741,7 @@ int launch_wgrad4(const float *act, const float *act_abc, int act_relu, const fl
                     g.tiles_y, g.strips, g.nseg_y, g.seg_rows, g.nsegs};
     const dim3 grid(g.grid), blk(wg4::THREADS);
     const int prod = !dz_abc ? 0 : (dz2 ? 2 : 1);
-#define COVA_WG4(PA, PD) hipLaunchKernelGGL((conv3x3_wgrad4_kernel<PA, PD>), grid, blk, 0, st, a)
+#define COVA_WG4(PA, PD) COVA_LAUNCH((conv3x3_wgrad4_kernel<PA, PD>), grid, blk, st, a)
     if (act_abc) { if (prod == 2) COVA_WG4(true, 2); else if (prod == 1) COVA_WG4(true, 1); else COVA_WG4(true, 0); }
     else         { if (prod == 2) COVA_WG4(false, 2); else if (prod == 1) COVA_WG4(false, 1); else COVA_WG4(false, 0); }
 #undef COVA_WG4
@@ -793,12 +793,12 @@ COVA_API int cova_conv3x3_wgrad4_finish(const float *ws0, float *dw0, const floa
         if (ws[i]) { jobs.part[n] = ws[i]; jobs.dw[n] = dw[i]; ++n; }
     if (n == 0) return COVA_OK;
     const int grid = wg4_geometry(B, H, W).grid;
-    hipLaunchKernelGGL(wgrad4_finish_kernel, dim3(4096 / 64, n), dim3(1024), 0, (hipStream_t)stream, jobs, grid);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(wgrad4_finish_kernel, dim3(4096 / 64, n), dim3(1024), (hipStream_t)stream, jobs, grid);
     return COVA_OK;
 }
 
 #ifdef WG4_TRACE
+COVA_API int cova_wg4_trace_read(unsigned long long *host64);     // (tools only: not in include/cova_hip.h)
 COVA_API int cova_wg4_trace_read(unsigned long long *host64)
 {
     return (int)hipMemcpyFromSymbol(host64, HIP_SYMBOL(g_wg4_trace), sizeof(unsigned long long) * 64);

@@ -1,5 +1,5 @@
 // Winograd F(4x4, 3x3) form of the 3x3 / 64->64 convolution (forward and data gradient): 36 multiplications per
-// 4x4 output tile and channel pair instead of 144 (F(2x2,3x3): 64) -- 1.78x fewer MFMAs than conv_wino.hip.
+// 4x4 output tile and channel pair instead of 144 (F(2x2,3x3): 64) -- 1.78x fewer MFMAs than tools/csrc/conv_wino_f2x2.hip.
 // fp32 error on this layer (post-ReLU input, 64 channels, against fp64): max 2.9e-6 of the output scale
 // (F(2x2,3x3) 1.9e-7, direct 3.0e-7), inside the 1e-4 forward / 2e-4 gradient gates of the parity tests.
 //
@@ -95,7 +95,7 @@ __device__ __forceinline__ void at6(const float (&m)[6], float (&o)[4])
     o[3] = fmaf(8.f, d2, d1) + m[5];
 }
 
-// Epilogue of the data-gradient launches (same contract as conv_wino.hip's BnBwdEpiW): ReLU mask + BatchNorm-backward
+// Epilogue of the data-gradient launches (same contract as tools/csrc/conv_wino_f2x2.hip's BnBwdEpiW): ReLU mask + BatchNorm-backward
 // sums.  The mask is act > 0, or, when the activation was never materialised (act == nullptr),
 // fma(msc, z, msh) > 0 -- the same expression the affine-on-load prologues evaluate.
 struct W4Epi {
@@ -329,7 +329,7 @@ __global__ __launch_bounds__(w4::THREADS, 1) void conv3x3_c64_wino4_kernel(const
         const float Bc = PRO == 2 ? s_pro[64 + ch] : 0.f;
 #pragma unroll
         for (int r = 0; r < 6; ++r) {
-            float v = fmaf(A, it.d[r], PRO == 2 ? fmaf(Bc, it.w[r], C) : C);      // same expression as conv_wino.hip's prologue
+            float v = fmaf(A, it.d[r], PRO == 2 ? fmaf(Bc, it.w[r], C) : C);      // same expression as tools/csrc/conv_wino_f2x2.hip's prologue
             if (a.pro_relu) v = fmaxf(v, 0.f);
             it.d[r] = ((vm[e] >> r) & 1u) ? v : 0.f;
         }
@@ -585,6 +585,7 @@ __global__ void prep_wino4_kernel(const PrepW pw, float *__restrict__ u_fwd, flo
 // C ABI
 // ====================================================================================
 #ifdef W4_TRACE
+COVA_API int cova_w4_trace_read(unsigned long long *host);        // (tools only: not in include/cova_hip.h)
 COVA_API int cova_w4_trace_read(unsigned long long *host)
 {
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_w4_trace), sizeof(unsigned long long) * 320);
@@ -601,7 +602,7 @@ COVA_API int cova_conv3x3_wino4_num_tiles(int B, int H, int W)
 static int w4_grid(int B, int H, int W)
 {
     const int tiles_x = cdiv(W, w4::TW), tiles_y = cdiv(H, w4::TH);
-    int g = cova_internal_persistent_grid2(B * tiles_x * tiles_y, 1);
+    int g = cova_internal_persistent_grid(B * tiles_x * tiles_y, 1);
     const int len_odd = B * tiles_x * (tiles_y / 2);
     if (len_odd > 0) {
         if (g > 2 * len_odd) g = 2 * len_odd;
@@ -623,9 +624,8 @@ COVA_API int cova_conv3x3_wino4_prep_multi(const float *w0, const float *w1, con
     COVA_REQUIRE(w0 && u_fwd && u_dgrad);
     const PrepW pw{{w0, w1, w2, w3}};
     const int n = w1 == nullptr ? 1 : w2 == nullptr ? 2 : w3 == nullptr ? 3 : 4;
-    hipLaunchKernelGGL(prep_wino4_kernel, dim3(cdiv(w4::U_FLOATS, 256), n), dim3(256), 0, (hipStream_t)stream, pw, u_fwd,
-                       u_dgrad);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(prep_wino4_kernel, dim3(cdiv(w4::U_FLOATS, 256), n), dim3(256), (hipStream_t)stream, pw, u_fwd,
+                u_dgrad);
     return COVA_OK;
 }
 
@@ -637,33 +637,34 @@ COVA_API int cova_conv3x3_wino4_prep(const float *w_oihw, float *u_fwd, float *u
 namespace {
 
 template <bool STATS, int PRO, bool ADD, int BN>
-void launch_w4(const W4Args &a, int grid, hipStream_t st)
+int launch_w4(const W4Args &a, int grid, hipStream_t st)
 {
     if constexpr (PRO != 2) {
         if (!cova_options().wino4_f32) {   // split main loop wherever it exists (one input tensor): the piece image sits behind the f32 image
             W4Args b = a;
             b.u = a.u + w4::U_FLOATS;
-            hipLaunchKernelGGL((conv3x3_c64_wino4s_kernel<STATS, PRO, ADD, BN>), dim3(grid), dim3(w4::THREADS), 0, st, b);
-            return;
+            COVA_LAUNCH((conv3x3_c64_wino4s_kernel<STATS, PRO, ADD, BN>), dim3(grid), dim3(w4::THREADS), st, b);
+            return COVA_OK;
         }
     }
-    hipLaunchKernelGGL((conv3x3_c64_wino4_kernel<STATS, PRO, ADD, BN>), dim3(grid), dim3(w4::THREADS), 0, st, a);
+    COVA_LAUNCH((conv3x3_c64_wino4_kernel<STATS, PRO, ADD, BN>), dim3(grid), dim3(w4::THREADS), st, a);
+    return COVA_OK;
 }
 
 template <int PRO>
-void launch_w4_pro(const W4Args &a, int grid, hipStream_t st)
+int launch_w4_pro(const W4Args &a, int grid, hipStream_t st)
 {
     const bool add = a.epi.addend != nullptr;
     const int bn = a.epi.z == nullptr ? 0 : (a.epi.act == nullptr && a.epi.act_bits == nullptr ? 1 : 2);
     if (a.epi.inference) {                                     // inference epilogue (no statistics)
-        if (add) launch_w4<false, PRO, true, 3>(a, grid, st); else launch_w4<false, PRO, false, 3>(a, grid, st);
+        if (add) return launch_w4<false, PRO, true, 3>(a, grid, st); else return launch_w4<false, PRO, false, 3>(a, grid, st);
     } else if (bn == 0) {
-        if (a.stat_part) { if (add) launch_w4<true, PRO, true, 0>(a, grid, st); else launch_w4<true, PRO, false, 0>(a, grid, st); }
-        else             { if (add) launch_w4<false, PRO, true, 0>(a, grid, st); else launch_w4<false, PRO, false, 0>(a, grid, st); }
+        if (a.stat_part) { if (add) return launch_w4<true, PRO, true, 0>(a, grid, st); else return launch_w4<true, PRO, false, 0>(a, grid, st); }
+        else             { if (add) return launch_w4<false, PRO, true, 0>(a, grid, st); else return launch_w4<false, PRO, false, 0>(a, grid, st); }
     } else if (bn == 1) {
-        if (add) launch_w4<true, PRO, true, 1>(a, grid, st); else launch_w4<true, PRO, false, 1>(a, grid, st);
+        if (add) return launch_w4<true, PRO, true, 1>(a, grid, st); else return launch_w4<true, PRO, false, 1>(a, grid, st);
     } else {
-        if (add) launch_w4<true, PRO, true, 2>(a, grid, st); else launch_w4<true, PRO, false, 2>(a, grid, st);
+        if (add) return launch_w4<true, PRO, true, 2>(a, grid, st); else return launch_w4<true, PRO, false, 2>(a, grid, st);
     }
 }
 
@@ -686,11 +687,9 @@ int run_w4(const float *in, const float *in2, const float *pro_abc, int pro_relu
     const int tiles_x = cdiv(W, w4::TW), tiles_y = cdiv(H, w4::TH), ntiles = B * tiles_x * tiles_y;
     const W4Args a{in, pro_abc ? in2 : nullptr, u, out, stat_part, H, W, tiles_x, tiles_y, ntiles, pro_abc, pro_relu, epi, t};
     const int grid = w4_grid(B, H, W);
-    if (!pro_abc) launch_w4_pro<0>(a, grid, (hipStream_t)stream);
-    else if (!in2) launch_w4_pro<1>(a, grid, (hipStream_t)stream);
-    else launch_w4_pro<2>(a, grid, (hipStream_t)stream);
-    COVA_LAUNCH_CHECK();
-    return COVA_OK;
+    if (!pro_abc) return launch_w4_pro<0>(a, grid, (hipStream_t)stream);
+    if (!in2) return launch_w4_pro<1>(a, grid, (hipStream_t)stream);
+    return launch_w4_pro<2>(a, grid, (hipStream_t)stream);
 }
 
 }  // namespace

@@ -192,10 +192,10 @@ COVA_API int cova_page_joint_decode(const float *logits, const int64_t *labels, 
 {
     COVA_REQUIRE(logits && page_start && choice && B > 0 && NC >= 2 && NC <= 7 && P > 0);
     COVA_REQUIRE((score_mode == 0 || score_mode == 1) && (!hit || labels));
-#define COVA_DECODE_CASE(C)                                                                                             \
-    case C + 1:                                                                                                        \
-        hipLaunchKernelGGL(page_joint_decode_kernel<C>, dim3(B), dim3(decode_threads<C>()), 0, (hipStream_t)stream,    \
-                           logits, labels, page_start, page_ids, P, score_mode, choice, hit, gap);                     \
+#define COVA_DECODE_CASE(C)                                                                               \
+    case C + 1:                                                                                           \
+        COVA_LAUNCH(page_joint_decode_kernel<C>, dim3(B), dim3(decode_threads<C>()), (hipStream_t)stream, \
+                    logits, labels, page_start, page_ids, P, score_mode, choice, hit, gap);               \
         break;
     switch (NC) {
         COVA_DECODE_CASE(1)

@@ -56,8 +56,7 @@ COVA_API int cova_eval_page_ranks(const float *logits, const int64_t *labels, co
                                   const int *page_ids, int B, int NC, int P, int *rank, int *top1, void *stream)
 {
     COVA_REQUIRE(logits && labels && page_start && rank && B > 0 && NC >= 2 && NC <= COVA_MAX_CLASSES && P > 0);
-    hipLaunchKernelGGL(eval_page_ranks_kernel, dim3(cdiv(B * (NC - 1), 4)), dim3(256), 0, (hipStream_t)stream, logits,
-                       labels, page_start, page_ids, B, NC, P, rank, top1);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(eval_page_ranks_kernel, dim3(cdiv(B * (NC - 1), 4)), dim3(256), (hipStream_t)stream, logits,
+                labels, page_start, page_ids, B, NC, P, rank, top1);
     return COVA_OK;
 }

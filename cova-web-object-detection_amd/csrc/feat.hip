@@ -32,18 +32,19 @@ __global__ __launch_bounds__(256) void feat_rows_gather_kernel(const float *__re
 }
 
 template <int VEC>
-void launch_gather(const float *table, long long R, int C, const int *row_ids, int N, float *out, int ld_out,
+int launch_gather(const float *table, long long R, int C, const int *row_ids, int N, float *out, int ld_out,
                    hipStream_t st)
 {
     const long long per_row = C / VEC, total = per_row * N;
     long long grid = (total + 255) / 256;
     if (grid > 2048) grid = 2048;                       // 256 CUs x 8 blocks; the rest by grid stride
     if (total < (1ll << 31))
-        hipLaunchKernelGGL((feat_rows_gather_kernel<VEC, unsigned int>), dim3((unsigned)grid), dim3(256), 0, st, table, R,
-                           C, row_ids, (unsigned int)total, (unsigned int)per_row, out, ld_out);
+        COVA_LAUNCH((feat_rows_gather_kernel<VEC, unsigned int>), dim3((unsigned)grid), dim3(256), st, table, R,
+                    C, row_ids, (unsigned int)total, (unsigned int)per_row, out, ld_out);
     else
-        hipLaunchKernelGGL((feat_rows_gather_kernel<VEC, unsigned long long>), dim3((unsigned)grid), dim3(256), 0, st,
-                           table, R, C, row_ids, (unsigned long long)total, (unsigned long long)per_row, out, ld_out);
+        COVA_LAUNCH((feat_rows_gather_kernel<VEC, unsigned long long>), dim3((unsigned)grid), dim3(256), st,
+                    table, R, C, row_ids, (unsigned long long)total, (unsigned long long)per_row, out, ld_out);
+    return COVA_OK;
 }
 
 }  // namespace
@@ -58,9 +59,6 @@ COVA_API int cova_feat_rows_gather(const float *table, long long R, int C, const
     hipStream_t st = (hipStream_t)stream;
     // the table is dense and C % 4 == 0, so its rows are 16-byte aligned whenever its base is
     if (C % 4 == 0 && ld_out % 4 == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)table & 15) == 0)
-        launch_gather<4>(table, R, C, row_ids, N, out, ld_out, st);
-    else
-        launch_gather<1>(table, R, C, row_ids, N, out, ld_out, st);
-    COVA_LAUNCH_CHECK();
-    return COVA_OK;
+        return launch_gather<4>(table, R, C, row_ids, N, out, ld_out, st);
+    return launch_gather<1>(table, R, C, row_ids, N, out, ld_out, st);
 }

@@ -498,12 +498,12 @@ int gat2_fwd_launch(const float *Wh, int ldw, const float *att_w, const float *a
     COVA_REQUIRE(nc > 0);
     const dim3 grid(cdiv(N, 4)), blk(256);
     hipStream_t st = (hipStream_t)stream;
-#define COVA_GAT2_FWD(NC, V)                                                                                        \
-    do {                                                                                                            \
-        if (phi) hipLaunchKernelGGL((gat2_fwd_kernel<NC, V, true, DROP>), grid, blk, 0, st, Wh, ldw, att_w, att_b, ctx, \
-                                    phi, edge_w, N, K, D, slope, attn, hprime, ldh, dr);                            \
-        else hipLaunchKernelGGL((gat2_fwd_kernel<NC, V, false, DROP>), grid, blk, 0, st, Wh, ldw, att_w, att_b, ctx, \
-                                phi, edge_w, N, K, D, slope, attn, hprime, ldh, dr);                                \
+#define COVA_GAT2_FWD(NC, V)                                                                                  \
+    do {                                                                                                      \
+        if (phi) COVA_LAUNCH((gat2_fwd_kernel<NC, V, true, DROP>), grid, blk, st, Wh, ldw, att_w, att_b, ctx, \
+                             phi, edge_w, N, K, D, slope, attn, hprime, ldh, dr);                             \
+        else COVA_LAUNCH((gat2_fwd_kernel<NC, V, false, DROP>), grid, blk, st, Wh, ldw, att_w, att_b, ctx,    \
+                         phi, edge_w, N, K, D, slope, attn, hprime, ldh, dr);                                 \
     } while (0)
     COVA_GAT2_DISPATCH(v4, nc, COVA_GAT2_FWD);
 #undef COVA_GAT2_FWD
@@ -557,22 +557,21 @@ int gat2_bwd_launch(const float *g, int ldg, const float *Wh, int ldw, const flo
     COVA_REQUIRE(nc > 0);
     const dim3 grid(cdiv(N, 4)), blk(256);
     hipStream_t st = (hipStream_t)stream;
-#define COVA_GAT2_BWD(NC, V)                                                                                        \
-    do {                                                                                                            \
-        if (phi) hipLaunchKernelGGL((gat2_bwd_src_kernel<NC, V, true, DROP>), grid, blk, 0, st, g, ldg, Wh, ldw, attn, \
-                                    ctx, att_w, phi, N, K, D, slope, dWh, lddw, du, workspace, dr);                 \
-        else hipLaunchKernelGGL((gat2_bwd_src_kernel<NC, V, false, DROP>), grid, blk, 0, st, g, ldg, Wh, ldw, attn,  \
-                                ctx, att_w, phi, N, K, D, slope, dWh, lddw, du, workspace, dr);                     \
-        hipLaunchKernelGGL((gat2_bwd_dst_kernel<NC, V, DROP>), grid, blk, 0, st, g, ldg, Wh, ldw, attn, du, csr,    \
-                           csr + N + 1, att_w, N, K, D, slope, dWh, lddw, dr);                                      \
+#define COVA_GAT2_BWD(NC, V)                                                                                 \
+    do {                                                                                                     \
+        if (phi) COVA_LAUNCH((gat2_bwd_src_kernel<NC, V, true, DROP>), grid, blk, st, g, ldg, Wh, ldw, attn, \
+                             ctx, att_w, phi, N, K, D, slope, dWh, lddw, du, workspace, dr);                 \
+        else COVA_LAUNCH((gat2_bwd_src_kernel<NC, V, false, DROP>), grid, blk, st, g, ldg, Wh, ldw, attn,    \
+                         ctx, att_w, phi, N, K, D, slope, dWh, lddw, du, workspace, dr);                     \
+        COVA_LAUNCH((gat2_bwd_dst_kernel<NC, V, DROP>), grid, blk, st, g, ldg, Wh, ldw, attn, du, csr,       \
+                    csr + N + 1, att_w, N, K, D, slope, dWh, lddw, dr);                                      \
     } while (0)
     COVA_GAT2_DISPATCH(v4, nc, COVA_GAT2_BWD);
 #undef COVA_GAT2_BWD
     COVA_LAUNCH_CHECK();
     const int ncols = D + 1 + (phi ? 8 : 0);
-    hipLaunchKernelGGL(gat2_fold_kernel, dim3(cdiv(ncols, 64)), dim3(1024), 0, st, workspace, cdiv(N, 4), D + 9, D, ncols,
-                       d_att_w, d_att_b, d_edge_w);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(gat2_fold_kernel, dim3(cdiv(ncols, 64)), dim3(1024), st, workspace, cdiv(N, 4), D + 9, D, ncols,
+                d_att_w, d_att_b, d_edge_w);
     return COVA_OK;
 }
 }  // namespace

@@ -372,11 +372,11 @@ static int sgemm_launch(int transA, int transB, int M, int N, int K, const float
         const long long blocks64 = (long long)cdiv(M, 64) * cdiv(N, 64), blocks32 = (long long)cdiv(M, 32) * cdiv(N, 64);
         const int shape = blocks32 <= 256 && K >= 8 * 32 ? 2 : (blocks64 <= 256 && K >= 16 * 32 ? 1 : 0);
         const dim3 g32(cdiv(N, 64), cdiv(M, 32));
-#define SGEMM_DMA(TA_, TB_)                                                                                                      \
-    do {                                                                                                                        \
-        if (shape == 0) hipLaunchKernelGGL((sgemm_dma_kernel<TA_, TB_, 2, 1, 4>), grid, dim3(256), 0, st, A, lda, B, ldb, C, ldc, bias, M, N, K, accumulate, emask, einv); \
-        else if (shape == 1) hipLaunchKernelGGL((sgemm_dma_kernel<TA_, TB_, 2, 2, 3>), grid, dim3(512), 0, st, A, lda, B, ldb, C, ldc, bias, M, N, K, accumulate, emask, einv); \
-        else hipLaunchKernelGGL((sgemm_dma_kernel<TA_, TB_, 1, 2, 4>), g32, dim3(256), 0, st, A, lda, B, ldb, C, ldc, bias, M, N, K, accumulate, emask, einv); \
+#define SGEMM_DMA(TA_, TB_)                                                                                                                                           \
+    do {                                                                                                                                                              \
+        if (shape == 0) COVA_LAUNCH((sgemm_dma_kernel<TA_, TB_, 2, 1, 4>), grid, dim3(256), st, A, lda, B, ldb, C, ldc, bias, M, N, K, accumulate, emask, einv);      \
+        else if (shape == 1) COVA_LAUNCH((sgemm_dma_kernel<TA_, TB_, 2, 2, 3>), grid, dim3(512), st, A, lda, B, ldb, C, ldc, bias, M, N, K, accumulate, emask, einv); \
+        else COVA_LAUNCH((sgemm_dma_kernel<TA_, TB_, 1, 2, 4>), g32, dim3(256), st, A, lda, B, ldb, C, ldc, bias, M, N, K, accumulate, emask, einv);                  \
     } while (0)
         if (!transA && !transB) SGEMM_DMA(false, false);
         else if (!transA && transB) SGEMM_DMA(false, true);
@@ -388,10 +388,10 @@ static int sgemm_launch(int transA, int transB, int M, int N, int K, const float
     }
     // two k-groups per block when there are at least four k-tiles and the grid alone does not fill the chip twice over
     const bool split = K >= 4 * BK && (long long)grid.x * grid.y < 2 * 4 * 256;
-#define SGEMM_LAUNCH(TA_, TB_)                                                                                              \
-    do {                                                                                                                    \
-        if (split) hipLaunchKernelGGL((sgemm_kernel<TA_, TB_, 2>), grid, dim3(512), 0, st, A, lda, B, ldb, C, ldc, bias, M, N, K, accumulate, va, vb, emask, einv); \
-        else hipLaunchKernelGGL((sgemm_kernel<TA_, TB_, 1>), grid, dim3(256), 0, st, A, lda, B, ldb, C, ldc, bias, M, N, K, accumulate, va, vb, emask, einv); \
+#define SGEMM_LAUNCH(TA_, TB_)                                                                                                                            \
+    do {                                                                                                                                                  \
+        if (split) COVA_LAUNCH((sgemm_kernel<TA_, TB_, 2>), grid, dim3(512), st, A, lda, B, ldb, C, ldc, bias, M, N, K, accumulate, va, vb, emask, einv); \
+        else COVA_LAUNCH((sgemm_kernel<TA_, TB_, 1>), grid, dim3(256), st, A, lda, B, ldb, C, ldc, bias, M, N, K, accumulate, va, vb, emask, einv);       \
     } while (0)
     if (!transA && !transB) SGEMM_LAUNCH(false, false);
     else if (!transA && transB) SGEMM_LAUNCH(false, true);

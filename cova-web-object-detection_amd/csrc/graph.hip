@@ -139,9 +139,8 @@ COVA_API int cova_edge_geometry(const float *bboxes, const long long *ctx, int N
     COVA_REQUIRE(bboxes && ctx && phi && ((uintptr_t)phi & 15) == 0 && img_w > 0.f && img_h > 0.f);
     long long blocks = ((long long)N * K + 255) / 256;
     if (blocks > 64 * 1024) blocks = 64 * 1024;
-    hipLaunchKernelGGL(edge_geometry_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, bboxes, ctx, N, K,
-                       img_w, img_h, phi);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(edge_geometry_kernel, dim3((unsigned)blocks), dim3(256), (hipStream_t)stream, bboxes, ctx, N, K,
+                img_w, img_h, phi);
     return COVA_OK;
 }
 
@@ -155,8 +154,7 @@ COVA_API int cova_context_knn(const float *bboxes, const int *page_offsets, int 
     COVA_REQUIRE(B > 0 && bboxes && page_offsets && ctx);
     long long blocks = ((long long)N + KNN_THREADS / 64 - 1) / (KNN_THREADS / 64);
     if (blocks > 256 * 1024) blocks = 256 * 1024;
-    hipLaunchKernelGGL(context_knn_kernel, dim3((unsigned)blocks), dim3(KNN_THREADS), 0, (hipStream_t)stream, bboxes,
-                       page_offsets, B, N, context_size, k_spatial, ctx);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(context_knn_kernel, dim3((unsigned)blocks), dim3(KNN_THREADS), (hipStream_t)stream, bboxes,
+                page_offsets, B, N, context_size, k_spatial, ctx);
     return COVA_OK;
 }

@@ -336,9 +336,8 @@ COVA_API int cova_dropout_fwd(const float *x, int ldx, float *out, int ldo, uint
                               void *stream)
 {
     COVA_REQUIRE(x && out && mask && R > 0 && C > 0 && p >= 0.f && p < 1.f);
-    hipLaunchKernelGGL(dropout_fwd_kernel, dim3(ew_grid(R * C)), dim3(256), 0, (hipStream_t)stream, x,
-                       ldx, out, ldo, mask, R, C, p, seed, mask_given);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(dropout_fwd_kernel, dim3(ew_grid(R * C)), dim3(256), (hipStream_t)stream, x,
+                ldx, out, ldo, mask, R, C, p, seed, mask_given);
     return COVA_OK;
 }
 
@@ -346,9 +345,8 @@ COVA_API int cova_dropout_bwd(const float *g, int ldg, const uint8_t *mask, floa
                               long long R, int C, float p, void *stream)
 {
     COVA_REQUIRE(g && mask && dx && R > 0 && C > 0 && p >= 0.f && p < 1.f);
-    hipLaunchKernelGGL(dropout_bwd_kernel, dim3(ew_grid(R * C)), dim3(256), 0, (hipStream_t)stream, g,
-                       ldg, mask, dx, ldx, R, C, p);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(dropout_bwd_kernel, dim3(ew_grid(R * C)), dim3(256), (hipStream_t)stream, g,
+                ldg, mask, dx, ldx, R, C, p);
     return COVA_OK;
 }
 
@@ -358,9 +356,8 @@ COVA_API int cova_linear_small_fwd(const float *x, int ldx, const float *W, cons
     COVA_REQUIRE(x && W && b && y && NC > 0 && NC <= COVA_MAX_CLASSES && Cin > 0);
     if (N == 0) return COVA_OK;
     const bool v4 = (Cin % 4 == 0) && (ldx % 4 == 0) && (((uintptr_t)x & 15) == 0) && (((uintptr_t)W & 15) == 0);
-    hipLaunchKernelGGL((v4 ? linear_small_fwd_kernel<4> : linear_small_fwd_kernel<1>), dim3(cdiv(N, 4)), dim3(256), 0,
-                       (hipStream_t)stream, x, ldx, W, b, y, N, Cin, NC);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH((v4 ? linear_small_fwd_kernel<4> : linear_small_fwd_kernel<1>), dim3(cdiv(N, 4)), dim3(256),
+                (hipStream_t)stream, x, ldx, W, b, y, N, Cin, NC);
     return COVA_OK;
 }
 
@@ -377,9 +374,8 @@ COVA_API int cova_linear_small_bwd(const float *dy, const float *x, int ldx, con
     long long nx = cdivll((long long)N * Cin, 1024);
     if (nx > 1024) nx = 1024;
     const dim3 wgrid(nw + (int)nx), wblock(1024);
-    if (NC <= 4) hipLaunchKernelGGL((v4 ? linear_small_bwd_w_kernel<4, 4> : linear_small_bwd_w_kernel<1, 4>), wgrid, wblock, 0, st, dy, x, ldx, dW, db, N, Cin, NC, W, dx, lddx, nw);
-    else hipLaunchKernelGGL((v4 ? linear_small_bwd_w_kernel<4, COVA_MAX_CLASSES> : linear_small_bwd_w_kernel<1, COVA_MAX_CLASSES>), wgrid, wblock, 0, st, dy, x, ldx, dW, db, N, Cin, NC, W, dx, lddx, nw);
-    COVA_LAUNCH_CHECK();
+    if (NC <= 4) COVA_LAUNCH((v4 ? linear_small_bwd_w_kernel<4, 4> : linear_small_bwd_w_kernel<1, 4>), wgrid, wblock, st, dy, x, ldx, dW, db, N, Cin, NC, W, dx, lddx, nw);
+    else COVA_LAUNCH((v4 ? linear_small_bwd_w_kernel<4, COVA_MAX_CLASSES> : linear_small_bwd_w_kernel<1, COVA_MAX_CLASSES>), wgrid, wblock, st, dy, x, ldx, dW, db, N, Cin, NC, W, dx, lddx, nw);
     return COVA_OK;
 }
 
@@ -388,9 +384,8 @@ COVA_API int cova_ce_sum(const float *logits, const int64_t *labels, int N, int 
                          float *loss, float *dlogits, int64_t *pred, void *stream)
 {
     COVA_REQUIRE(logits && N > 0 && NC > 0);
-    hipLaunchKernelGGL(ce_sum_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, logits, labels, N,
-                       NC, gscale, loss, dlogits, pred);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(ce_sum_kernel, dim3(1), dim3(1024), (hipStream_t)stream, logits, labels, N,
+                NC, gscale, loss, dlogits, pred);
     return COVA_OK;
 }
 
@@ -401,10 +396,9 @@ COVA_API int cova_adam_step(float *p, const float *g, float *m, float *v, long l
     COVA_REQUIRE(p && g && m && v && n > 0 && step >= 1);
     const float bc1 = (float)(1.0 - pow(beta1, (double)step));
     const float bc2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
-    hipLaunchKernelGGL(adam_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
-                       (float)lr, (float)beta1, (float)beta2, (float)eps, (float)weight_decay, bc1,
-                       bc2_sqrt);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(adam_kernel, dim3(ew_grid(n)), dim3(256), (hipStream_t)stream, p, g, m, v, n,
+                (float)lr, (float)beta1, (float)beta2, (float)eps, (float)weight_decay, bc1,
+                bc2_sqrt);
     return COVA_OK;
 }
 
@@ -412,9 +406,8 @@ COVA_API int cova_colsum(const float *x, int ldx, int R, int C, float *out, void
 {
     COVA_REQUIRE(x && out && R > 0 && C > 0);
     const bool v4 = (C % 4 == 0) && (ldx % 4 == 0) && (((uintptr_t)x & 15) == 0);
-    hipLaunchKernelGGL((v4 ? colsum_kernel<4> : colsum_kernel<1>), dim3(cdiv(C, 64)), dim3(1024), 0, (hipStream_t)stream, x, ldx, R,
-                       C, out);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH((v4 ? colsum_kernel<4> : colsum_kernel<1>), dim3(cdiv(C, 64)), dim3(1024), (hipStream_t)stream, x, ldx, R,
+                C, out);
     return COVA_OK;
 }
 
@@ -425,9 +418,8 @@ COVA_API int cova_page_class_topk(const float *logits, const int64_t *page_start
                                   int k, int64_t *out, void *stream)
 {
     COVA_REQUIRE(logits && page_start && out && n_pages > 0 && NC > 0 && k > 0);
-    hipLaunchKernelGGL(page_class_topk_kernel, dim3(cdiv(n_pages * NC, 4)), dim3(256), 0,
-                       (hipStream_t)stream, logits, page_start, n_pages, NC, k, out);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(page_class_topk_kernel, dim3(cdiv(n_pages * NC, 4)), dim3(256),
+                (hipStream_t)stream, logits, page_start, n_pages, NC, k, out);
     return COVA_OK;
 }
 
@@ -477,8 +469,7 @@ COVA_API int cova_attn_export_rows(const float *bboxes, const long long *ctx, co
     if (N == 0) return COVA_OK;
     long long g = ((long long)N * (5 + 5 * K) + 255) / 256;
     if (g > 8192) g = 8192;
-    hipLaunchKernelGGL(attn_export_rows_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream,
-                       bboxes, ctx, attn, labels, N, K, out);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(attn_export_rows_kernel, dim3((unsigned)g), dim3(256), (hipStream_t)stream,
+                bboxes, ctx, attn, labels, N, K, out);
     return COVA_OK;
 }

@@ -116,12 +116,11 @@ COVA_API int cova_images_u8_to_f32(const uint8_t *u8_nhwc, float *f32_nchw, int 
     const long long plane = (long long)H * W, total = plane * B;
     hipStream_t st = (hipStream_t)stream;
     if (plane % 4 == 0 && ((uintptr_t)u8_nhwc & 3) == 0 && ((uintptr_t)f32_nchw & 15) == 0)
-        hipLaunchKernelGGL(u8_nhwc_to_f32_nchw_kernel<false>, dim3(grid_for(total / 4)), dim3(256), 0, st,
-                           u8_nhwc, f32_nchw, total / 4, plane, total, (const int *)nullptr, 0);
+        COVA_LAUNCH(u8_nhwc_to_f32_nchw_kernel<false>, dim3(grid_for(total / 4)), dim3(256), st,
+                    u8_nhwc, f32_nchw, total / 4, plane, total, (const int *)nullptr, 0);
     else
-        hipLaunchKernelGGL(u8_nhwc_to_f32_nchw_scalar_kernel<false>, dim3(grid_for(total)), dim3(256), 0, st,
-                           u8_nhwc, f32_nchw, plane, total, (const int *)nullptr, 0);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(u8_nhwc_to_f32_nchw_scalar_kernel<false>, dim3(grid_for(total)), dim3(256), st,
+                    u8_nhwc, f32_nchw, plane, total, (const int *)nullptr, 0);
     return COVA_OK;
 }
 
@@ -133,12 +132,11 @@ COVA_API int cova_pages_u8_gather_f32(const uint8_t *store_u8, const int *page_i
     const long long plane = (long long)H * W, total = plane * B;
     hipStream_t st = (hipStream_t)stream;
     if (plane % 4 == 0 && ((uintptr_t)store_u8 & 3) == 0 && ((uintptr_t)f32_nchw & 15) == 0)
-        hipLaunchKernelGGL(u8_nhwc_to_f32_nchw_kernel<true>, dim3(grid_for(total / 4)), dim3(256), 0, st,
-                           store_u8, f32_nchw, total / 4, plane, total, page_idx, P);
+        COVA_LAUNCH(u8_nhwc_to_f32_nchw_kernel<true>, dim3(grid_for(total / 4)), dim3(256), st,
+                    store_u8, f32_nchw, total / 4, plane, total, page_idx, P);
     else
-        hipLaunchKernelGGL(u8_nhwc_to_f32_nchw_scalar_kernel<true>, dim3(grid_for(total)), dim3(256), 0, st,
-                           store_u8, f32_nchw, plane, total, page_idx, P);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(u8_nhwc_to_f32_nchw_scalar_kernel<true>, dim3(grid_for(total)), dim3(256), st,
+                    store_u8, f32_nchw, plane, total, page_idx, P);
     return COVA_OK;
 }
 
@@ -152,9 +150,8 @@ COVA_API int cova_collate_boxes(const float *rows, const int *page_offsets, int 
     COVA_REQUIRE(rows && page_offsets && bboxes && labels && B > 0 && N >= 0 && context_size >= 0);
     COVA_REQUIRE(context_size == 0 || ctx);
     if (N == 0) return COVA_OK;
-    hipLaunchKernelGGL(collate_boxes_kernel, dim3(grid_for((long long)N * (2 * context_size + 1))),
-                       dim3(256), 0, (hipStream_t)stream, rows, page_offsets, B, context_size, bboxes,
-                       labels, ctx, N);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(collate_boxes_kernel, dim3(grid_for((long long)N * (2 * context_size + 1))),
+                dim3(256), (hipStream_t)stream, rows, page_offsets, B, context_size, bboxes,
+                labels, ctx, N);
     return COVA_OK;
 }

@@ -225,12 +225,10 @@ COVA_API int cova_ce_loss_fwd(const float *logits, const int64_t *labels, int N,
     COVA_REQUIRE(loss_options(NC, label_smoothing, focal_gamma, ignore_index, has_ignore_index, &o));
     const int n_part = cdiv(N, LOSS_SLICE);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(ce_loss_fwd_kernel, dim3(n_part), dim3(LOSS_THREADS), 0, s, logits, labels, N, NC, class_weight,
-                       o, workspace, n_part, acc, pred, metrics);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(ce_loss_fwd_kernel, dim3(n_part), dim3(LOSS_THREADS), s, logits, labels, N, NC, class_weight,
+                o, workspace, n_part, acc, pred, metrics);
     if (n_part > 1) {
-        hipLaunchKernelGGL(ce_loss_fold_kernel, dim3(1), dim3(64), 0, s, workspace, n_part, acc, metrics, NC);
-        COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(ce_loss_fold_kernel, dim3(1), dim3(64), s, workspace, n_part, acc, metrics, NC);
     }
     return COVA_OK;
 }
@@ -244,8 +242,7 @@ COVA_API int cova_ce_loss_bwd(const float *logits, const int64_t *labels, int N,
     COVA_REQUIRE(logits && labels && acc_total && (loss_out || dlogits) && N > 0);
     COVA_REQUIRE(loss_options(NC, label_smoothing, focal_gamma, ignore_index, has_ignore_index, &o));
     const int grid = dlogits ? cdiv(N, LOSS_BWD_THREADS) : 1;
-    hipLaunchKernelGGL(ce_loss_bwd_kernel, dim3(grid), dim3(LOSS_BWD_THREADS), 0, (hipStream_t)stream, logits, labels,
-                       N, NC, class_weight, o, acc_total, reduction_mean, grad_scale, loss_out, dlogits);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(ce_loss_bwd_kernel, dim3(grid), dim3(LOSS_BWD_THREADS), (hipStream_t)stream, logits, labels,
+                N, NC, class_weight, o, acc_total, reduction_mean, grad_scale, loss_out, dlogits);
     return COVA_OK;
 }

@@ -139,8 +139,7 @@ COVA_API int cova_hard_negative_select(const float *logits, const int64_t *label
     COVA_REQUIRE(logits && labels && page_start && labels_out && B >= 1 && N >= 1);
     COVA_REQUIRE(NC >= 2 && NC <= COVA_MAX_CLASSES);
     COVA_REQUIRE(ratio >= 0.0 && ratio <= DBL_MAX && min_keep >= 0);
-    hipLaunchKernelGGL(mine_select_kernel, dim3(B), dim3(MINE_THREADS), 0, (hipStream_t)stream, logits, labels, page_start,
-                       B, N, NC, ratio, min_keep, drop_label, labels_out, score_out, counts);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(mine_select_kernel, dim3(B), dim3(MINE_THREADS), (hipStream_t)stream, logits, labels, page_start,
+                B, N, NC, ratio, min_keep, drop_label, labels_out, score_out, counts);
     return COVA_OK;
 }

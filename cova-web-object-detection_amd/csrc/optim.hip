@@ -401,9 +401,8 @@ COVA_API int cova_optim_step(int algo, float *p, const float *g, float *m, float
     hipStream_t s = (hipStream_t)stream;
     static constexpr decltype(&optim_step_kernel<ALGO_ADAM>) kernels[] = {
         optim_step_kernel<ALGO_ADAM>, optim_step_kernel<ALGO_ADAMW>, optim_step_kernel<ALGO_SGD>};   // by algorithm code
-    hipLaunchKernelGGL(kernels[algo], grid, block, 0, s, p, g, m, v, n, segs, n_seg, total, G, n_groups, gscale,
-                       vec4);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(kernels[algo], grid, block, s, p, g, m, v, n, segs, n_seg, total, G, n_groups, gscale,
+                vec4);
     return COVA_OK;
 }
 
@@ -420,12 +419,10 @@ COVA_API int cova_grad_norm(const float *g, long long n, const long long *segs, 
     COVA_REQUIRE(total == 0 || (segs && n_seg > 0));
     const int n_part = cova_grad_norm_workspace_doubles(total);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(n_part), dim3(OPT_THREADS), 0, s, g, n, segs, total ? n_seg : 0, total,
-                       (int)aligned16(g), workspace);                    // (no element: no row is read, segs may be null)
-    COVA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(OPT_THREADS), 0, s, workspace, n_part, (float)max_norm,
-                       out);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(grad_sumsq_kernel, dim3(n_part), dim3(OPT_THREADS), s, g, n, segs, total ? n_seg : 0, total,
+                (int)aligned16(g), workspace);                    // (no element: no row is read, segs may be null)
+    COVA_LAUNCH(grad_norm_finish_kernel, dim3(1), dim3(OPT_THREADS), s, workspace, n_part, (float)max_norm,
+                out);
     return COVA_OK;
 }
 
@@ -437,9 +434,8 @@ COVA_API int cova_weight_average(float *avg, const float *p, long long n, const 
     COVA_REQUIRE(avg && p && segs && n > 0 && total <= n);
     const float w = (float)one_minus_decay;                  // converted once: the kernel multiplies by this f32
     const dim3 grid((unsigned)cdivll(total, OPT_SLICE)), block(OPT_THREADS);
-    hipLaunchKernelGGL(weight_average_kernel, grid, block, 0, (hipStream_t)stream, avg, p, n, segs, n_seg, total, w,
-                       (int)(aligned16(avg) && aligned16(p)));
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(weight_average_kernel, grid, block, (hipStream_t)stream, avg, p, n, segs, n_seg, total, w,
+                (int)(aligned16(avg) && aligned16(p)));
     return COVA_OK;
 }
 
@@ -458,7 +454,6 @@ COVA_API int cova_grad_accumulate(int mode, float *acc, float *g, long long n, c
     static constexpr decltype(&grad_accumulate_kernel<ACC_OPEN>) kernels[] = {                       // by mode
         grad_accumulate_kernel<ACC_OPEN>, grad_accumulate_kernel<ACC_ADD>, grad_accumulate_kernel<ACC_CLOSE>,
         grad_accumulate_kernel<ACC_ADD_CLOSE>};
-    hipLaunchKernelGGL(kernels[mode], grid, block, 0, (hipStream_t)stream, acc, g, n, segs, n_seg, total, c0, c1, s, vec4);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(kernels[mode], grid, block, (hipStream_t)stream, acc, g, n, segs, n_seg, total, c0, c1, s, vec4);
     return COVA_OK;
 }

@@ -21,6 +21,5 @@ inline const CovaOptions &cova_options()
     return g_cova_options;
 }
 
-// min(ntiles, compute units of the current device * blocks_per_cu), under the grid cap (conv.hip)
-int cova_internal_persistent_grid(int ntiles);
-int cova_internal_persistent_grid2(int ntiles, int blocks_per_cu);
+// min(ntiles, compute units of the current device * blocks_per_cu), under the grid cap (options.hip)
+int cova_internal_persistent_grid(int ntiles, int blocks_per_cu = 1);

@@ -592,14 +592,13 @@ __global__ __launch_bounds__(64) void pa_geo_fold_kernel(const float *__restrict
 
 }  // namespace
 
-#define PA_DISPATCH(KERNEL, GEO, DROP, ...)                                                                                \
-    do {                                                                                                                   \
-        if (dh <= 16) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<1, GEO, DROP>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
-        else if (dh <= 32) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<2, GEO, DROP>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
-        else if (dh <= 64) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<4, GEO, DROP>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
-        else if (dh <= 96) hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<6, GEO, DROP>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__); \
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<8, GEO, DROP>), dim3(blocks), dim3(PA_THREADS), 0, st, __VA_ARGS__);       \
-        COVA_LAUNCH_CHECK();                                                                                               \
+#define PA_DISPATCH(KERNEL, GEO, DROP, ...)                                                                                     \
+    do {                                                                                                                        \
+        if (dh <= 16) COVA_LAUNCH(HIP_KERNEL_NAME(KERNEL<1, GEO, DROP>), dim3(blocks), dim3(PA_THREADS), st, __VA_ARGS__);      \
+        else if (dh <= 32) COVA_LAUNCH(HIP_KERNEL_NAME(KERNEL<2, GEO, DROP>), dim3(blocks), dim3(PA_THREADS), st, __VA_ARGS__); \
+        else if (dh <= 64) COVA_LAUNCH(HIP_KERNEL_NAME(KERNEL<4, GEO, DROP>), dim3(blocks), dim3(PA_THREADS), st, __VA_ARGS__); \
+        else if (dh <= 96) COVA_LAUNCH(HIP_KERNEL_NAME(KERNEL<6, GEO, DROP>), dim3(blocks), dim3(PA_THREADS), st, __VA_ARGS__); \
+        else COVA_LAUNCH(HIP_KERNEL_NAME(KERNEL<8, GEO, DROP>), dim3(blocks), dim3(PA_THREADS), st, __VA_ARGS__);               \
     } while (0)
 
 // 0 < p < 1 (a NaN fails both compares) and every mask index within its 32 + 32 bits
@@ -691,9 +690,8 @@ static int pa_bwd_geo(const float *g, int ldg, const float *qkv, int ldq, const 
     const int rc = pa_bwd<true, DROP>(g, ldg, qkv, ldq, out, ldo, lse, page_start, B, N, E, Hh, dqkv, lddq,
                                       PaGeo<true>{bboxes, geo_w, img_w, img_h, workspace}, dr, stream);
     if (rc != COVA_OK || N == 0 || B == 0) return rc;
-    hipLaunchKernelGGL(pa_geo_fold_kernel, dim3(cdiv(Hh * 8, 64)), dim3(64), 0, (hipStream_t)stream, workspace, page_start, B,
-                       N, Hh, cdiv(N, PA_OWN), d_geo_w);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(pa_geo_fold_kernel, dim3(cdiv(Hh * 8, 64)), dim3(64), (hipStream_t)stream, workspace, page_start, B,
+                N, Hh, cdiv(N, PA_OWN), d_geo_w);
     return COVA_OK;
 }
 

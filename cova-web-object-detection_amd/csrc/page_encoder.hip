@@ -345,12 +345,11 @@ COVA_API int cova_layernorm_fwd(const float *x, int ldx, int R, int C, const flo
     const int grid = cdiv(R, LN_WAVES) < LN_FWD_MAX_BLOCKS ? cdiv(R, LN_WAVES) : LN_FWD_MAX_BLOCKS;
     hipStream_t st = (hipStream_t)stream;
     if (v4)
-        hipLaunchKernelGGL(layernorm_fwd_kernel<4>, dim3(grid), dim3(LN_THREADS), 0, st, x, ldx, R, C, weight, bias, eps, out,
-                           ldo, mean, rstd);
+        COVA_LAUNCH(layernorm_fwd_kernel<4>, dim3(grid), dim3(LN_THREADS), st, x, ldx, R, C, weight, bias, eps, out,
+                    ldo, mean, rstd);
     else
-        hipLaunchKernelGGL(layernorm_fwd_kernel<1>, dim3(grid), dim3(LN_THREADS), 0, st, x, ldx, R, C, weight, bias, eps, out,
-                           ldo, mean, rstd);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(layernorm_fwd_kernel<1>, dim3(grid), dim3(LN_THREADS), st, x, ldx, R, C, weight, bias, eps, out,
+                    ldo, mean, rstd);
     return COVA_OK;
 }
 
@@ -367,15 +366,13 @@ COVA_API int cova_layernorm_bwd(const float *g, int ldg, const float *x, int ldx
     const int blocks = cdiv(R, LN_BWD_ROWS);
     hipStream_t st = (hipStream_t)stream;
     if (v4)
-        hipLaunchKernelGGL(layernorm_bwd_kernel<4>, dim3(blocks), dim3(LN_THREADS), 0, st, g, ldg, x, ldx, mean, rstd, weight,
-                           R, C, res, ldr, dx, lddx, ws);
+        COVA_LAUNCH(layernorm_bwd_kernel<4>, dim3(blocks), dim3(LN_THREADS), st, g, ldg, x, ldx, mean, rstd, weight,
+                    R, C, res, ldr, dx, lddx, ws);
     else
-        hipLaunchKernelGGL(layernorm_bwd_kernel<1>, dim3(blocks), dim3(LN_THREADS), 0, st, g, ldg, x, ldx, mean, rstd, weight,
-                           R, C, res, ldr, dx, lddx, ws);
-    COVA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(layernorm_fold_kernel, dim3(cdiv(2 * C, LN_FOLD_THREADS)), dim3(LN_FOLD_THREADS), 0, st, ws, blocks, C,
-                       dweight, dbias);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(layernorm_bwd_kernel<1>, dim3(blocks), dim3(LN_THREADS), st, g, ldg, x, ldx, mean, rstd, weight,
+                    R, C, res, ldr, dx, lddx, ws);
+    COVA_LAUNCH(layernorm_fold_kernel, dim3(cdiv(2 * C, LN_FOLD_THREADS)), dim3(LN_FOLD_THREADS), st, ws, blocks, C,
+                dweight, dbias);
     return COVA_OK;
 }
 
@@ -388,12 +385,11 @@ static int gelu_fwd(const float *z, int ldz, long long R, int C, float *out, int
     const bool v4 = C % 4 == 0 && vec4_ok(z, ldz) && vec4_ok(out, ldo);
     hipStream_t st = (hipStream_t)stream;
     if (v4)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(gelu_fwd_kernel<4, DROP>), dim3(ew_grid(R * (C / 4))), dim3(256), 0, st, z, ldz, R, C,
-                           out, ldo, dr);
+        COVA_LAUNCH(HIP_KERNEL_NAME(gelu_fwd_kernel<4, DROP>), dim3(ew_grid(R * (C / 4))), dim3(256), st, z, ldz, R, C,
+                    out, ldo, dr);
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(gelu_fwd_kernel<1, DROP>), dim3(ew_grid(R * C)), dim3(256), 0, st, z, ldz, R, C, out,
-                           ldo, dr);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(HIP_KERNEL_NAME(gelu_fwd_kernel<1, DROP>), dim3(ew_grid(R * C)), dim3(256), st, z, ldz, R, C, out,
+                    ldo, dr);
     return COVA_OK;
 }
 
@@ -407,12 +403,11 @@ static int gelu_bwd(const float *g, int ldg, const float *z, int ldz, long long 
     const bool v4 = C % 4 == 0 && vec4_ok(g, ldg) && vec4_ok(z, ldz) && vec4_ok(dz, lddz);
     hipStream_t st = (hipStream_t)stream;
     if (v4)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(gelu_bwd_kernel<4, DROP>), dim3(ew_grid(R * (C / 4))), dim3(256), 0, st, g, ldg, z,
-                           ldz, R, C, dz, lddz, dr);
+        COVA_LAUNCH(HIP_KERNEL_NAME(gelu_bwd_kernel<4, DROP>), dim3(ew_grid(R * (C / 4))), dim3(256), st, g, ldg, z,
+                    ldz, R, C, dz, lddz, dr);
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(gelu_bwd_kernel<1, DROP>), dim3(ew_grid(R * C)), dim3(256), 0, st, g, ldg, z, ldz, R,
-                           C, dz, lddz, dr);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(HIP_KERNEL_NAME(gelu_bwd_kernel<1, DROP>), dim3(ew_grid(R * C)), dim3(256), st, g, ldg, z, ldz, R,
+                    C, dz, lddz, dr);
     return COVA_OK;
 }
 
@@ -456,12 +451,11 @@ COVA_API int cova_dropout_add_fwd(const float *y, int ldy, const float *x, int l
     const RowDrop<true> dr = row_drop_of(p, seed);
     hipStream_t st = (hipStream_t)stream;
     if (v4)
-        hipLaunchKernelGGL(dropout_add_fwd_kernel<4>, dim3(ew_grid(R * (C / 4))), dim3(256), 0, st, y, ldy, x, ldx, R, C, out,
-                           ldo, dr);
+        COVA_LAUNCH(dropout_add_fwd_kernel<4>, dim3(ew_grid(R * (C / 4))), dim3(256), st, y, ldy, x, ldx, R, C, out,
+                    ldo, dr);
     else
-        hipLaunchKernelGGL(dropout_add_fwd_kernel<1>, dim3(ew_grid(R * C)), dim3(256), 0, st, y, ldy, x, ldx, R, C, out, ldo,
-                           dr);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(dropout_add_fwd_kernel<1>, dim3(ew_grid(R * C)), dim3(256), st, y, ldy, x, ldx, R, C, out, ldo,
+                    dr);
     return COVA_OK;
 }
 
@@ -475,10 +469,9 @@ COVA_API int cova_dropout_regen_bwd(const float *g, int ldg, float *dy, int lddy
     const RowDrop<true> dr = row_drop_of(p, seed);
     hipStream_t st = (hipStream_t)stream;
     if (v4)
-        hipLaunchKernelGGL(dropout_regen_bwd_kernel<4>, dim3(ew_grid(R * (C / 4))), dim3(256), 0, st, g, ldg, R, C, dy, lddy,
-                           dr);
+        COVA_LAUNCH(dropout_regen_bwd_kernel<4>, dim3(ew_grid(R * (C / 4))), dim3(256), st, g, ldg, R, C, dy, lddy,
+                    dr);
     else
-        hipLaunchKernelGGL(dropout_regen_bwd_kernel<1>, dim3(ew_grid(R * C)), dim3(256), 0, st, g, ldg, R, C, dy, lddy, dr);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(dropout_regen_bwd_kernel<1>, dim3(ew_grid(R * C)), dim3(256), st, g, ldg, R, C, dy, lddy, dr);
     return COVA_OK;
 }

@@ -162,11 +162,9 @@ COVA_API int cova_page_rank_loss_fwd(const float *logits, const int64_t *labels,
     const long long n_lists = (long long)B * (NC - 1);
     COVA_REQUIRE(n_lists <= INT32_MAX);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(rank_lists_kernel, dim3(cdiv((int)n_lists, RANK_THREADS / 64)), dim3(RANK_THREADS), 0, s, logits,
-                       labels, page_start, B, N, NC, ignore_index, has_ignore_index != 0, lists);
-    COVA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rank_fold_kernel, dim3(1), dim3(64), 0, s, lists, (int)n_lists, NC, class_weight, acc);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(rank_lists_kernel, dim3(cdiv((int)n_lists, RANK_THREADS / 64)), dim3(RANK_THREADS), s, logits,
+                labels, page_start, B, N, NC, ignore_index, has_ignore_index != 0, lists);
+    COVA_LAUNCH(rank_fold_kernel, dim3(1), dim3(64), s, lists, (int)n_lists, NC, class_weight, acc);
     return COVA_OK;
 }
 
@@ -181,9 +179,8 @@ COVA_API int cova_page_rank_loss_bwd(const float *logits, const int64_t *labels,
     COVA_REQUIRE((long long)B * (NC - 1) <= INT32_MAX);
     COVA_REQUIRE(rank_weight >= 0.0 && rank_weight <= DBL_MAX);
     const int grid = dlogits ? cdiv(N, RANK_THREADS) : 1;
-    hipLaunchKernelGGL(rank_bwd_kernel, dim3(grid), dim3(RANK_THREADS), 0, (hipStream_t)stream, logits, labels,
-                       page_start, B, N, NC, class_weight, ignore_index, has_ignore_index != 0, lists, acc_total,
-                       rank_weight, reduction_mean != 0, grad_scale, loss_inout, dlogits, accumulate != 0);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(rank_bwd_kernel, dim3(grid), dim3(RANK_THREADS), (hipStream_t)stream, logits, labels,
+                page_start, B, N, NC, class_weight, ignore_index, has_ignore_index != 0, lists, acc_total,
+                rank_weight, reduction_mean != 0, grad_scale, loss_inout, dlogits, accumulate != 0);
     return COVA_OK;
 }

@@ -311,12 +311,11 @@ COVA_API int cova_page_readout_fwd(const float *P, int ldp, const float *att_w, 
     const bool v4 = G % 4 == 0 && vec4_ok(P, ldp) && vec4_ok(out, ldo) && aligned16(att_w) && aligned16(r);
     hipStream_t st = (hipStream_t)stream;
     if (v4)
-        hipLaunchKernelGGL(readout_fwd_kernel<4>, dim3(B), dim3(RO_THREADS), 0, st, P, ldp, att_w, att_b, page_start, N, G,
-                           alpha, u, beta, r, out, ldo);
+        COVA_LAUNCH(readout_fwd_kernel<4>, dim3(B), dim3(RO_THREADS), st, P, ldp, att_w, att_b, page_start, N, G,
+                    alpha, u, beta, r, out, ldo);
     else
-        hipLaunchKernelGGL(readout_fwd_kernel<1>, dim3(B), dim3(RO_THREADS), 0, st, P, ldp, att_w, att_b, page_start, N, G,
-                           alpha, u, beta, r, out, ldo);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(readout_fwd_kernel<1>, dim3(B), dim3(RO_THREADS), st, P, ldp, att_w, att_b, page_start, N, G,
+                    alpha, u, beta, r, out, ldo);
     return COVA_OK;
 }
 
@@ -333,14 +332,12 @@ COVA_API int cova_page_readout_bwd(const float *g, int ldg, const float *P, int 
                     aligned16(r);
     hipStream_t st = (hipStream_t)stream;
     if (v4)
-        hipLaunchKernelGGL(readout_bwd_kernel<4>, dim3(B), dim3(RO_THREADS), 0, st, g, ldg, P, ldp, u, beta, r, att_w,
-                           page_start, N, G, alpha, dP, lddp, ws);
+        COVA_LAUNCH(readout_bwd_kernel<4>, dim3(B), dim3(RO_THREADS), st, g, ldg, P, ldp, u, beta, r, att_w,
+                    page_start, N, G, alpha, dP, lddp, ws);
     else
-        hipLaunchKernelGGL(readout_bwd_kernel<1>, dim3(B), dim3(RO_THREADS), 0, st, g, ldg, P, ldp, u, beta, r, att_w,
-                           page_start, N, G, alpha, dP, lddp, ws);
-    COVA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(readout_fold_kernel, dim3(cdiv(G + 1, RO_THREADS)), dim3(RO_THREADS), 0, st, ws, B, G, d_att_w,
-                       d_att_b);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(readout_bwd_kernel<1>, dim3(B), dim3(RO_THREADS), st, g, ldg, P, ldp, u, beta, r, att_w,
+                    page_start, N, G, alpha, dP, lddp, ws);
+    COVA_LAUNCH(readout_fold_kernel, dim3(cdiv(G + 1, RO_THREADS)), dim3(RO_THREADS), st, ws, B, G, d_att_w,
+                d_att_b);
     return COVA_OK;
 }

@@ -1111,7 +1111,7 @@ template <class Launch>
 int gat_dispatch(GatForm f, Launch launch)
 {
 #define COVA_GAT_FORM(KP, ND)                                                                   \
-    case 100 * ND + KP: launch(std::integral_constant<int, KP>{}, std::integral_constant<int, ND>{}); break
+    case 100 * ND + KP: return launch(std::integral_constant<int, KP>{}, std::integral_constant<int, ND>{})
     switch (100 * f.nd + f.kp) {
     COVA_GAT_FORM(1, 1); COVA_GAT_FORM(2, 1); COVA_GAT_FORM(3, 1); COVA_GAT_FORM(4, 1); COVA_GAT_FORM(5, 1);
     COVA_GAT_FORM(6, 1); COVA_GAT_FORM(7, 1); COVA_GAT_FORM(8, 1); COVA_GAT_FORM(12, 1); COVA_GAT_FORM(16, 1);
@@ -1119,7 +1119,6 @@ int gat_dispatch(GatForm f, Launch launch)
     default: return COVA_ERR_BAD_ARG;
     }
 #undef COVA_GAT_FORM
-    return COVA_OK;
 }
 
 }  // namespace
@@ -1135,9 +1134,9 @@ COVA_API int cova_roipool_fwd(const float *feat, const float *rois, int n_rois, 
 {
     COVA_REQUIRE(feat && rois && out && argmax && n_rois >= 0 && B > 0 && C > 0 && C % 64 == 0 && PH > 0 && PW > 0);
     if (n_rois == 0) return COVA_OK;
-#define COVA_ROIPOOL_FWD(LAZY_, U_, XCD_, F_, ZM_, LZ_)                                                                     \
-    hipLaunchKernelGGL((roipool_fwd_kernel<LAZY_, U_, XCD_>), dim3(cdiv(n_rois * PH * PW, 4)), dim3(256), 0,              \
-                       (hipStream_t)stream, F_, rois, n_rois, B, C, H, W, PH, PW, spatial_scale, out, ld_out, argmax, ZM_, LZ_)
+#define COVA_ROIPOOL_FWD(LAZY_, U_, XCD_, F_, ZM_, LZ_)                                             \
+    COVA_LAUNCH((roipool_fwd_kernel<LAZY_, U_, XCD_>), dim3(cdiv(n_rois * PH * PW, 4)), dim3(256),  \
+                (hipStream_t)stream, F_, rois, n_rois, B, C, H, W, PH, PW, spatial_scale, out, ld_out, argmax, ZM_, LZ_)
     {
         const LazyFeat none{nullptr, nullptr, nullptr};
         // (wider maps: the channel-block loop multiplies the trips, the launch is bandwidth bound and loses occupancy with eight
@@ -1172,7 +1171,7 @@ COVA_API int cova_roipool_fwd_bn(const float *z, const float *x, const float *sc
 static int roipool_bwd_grid(int B, int H, int W)
 {
     const long long ntask = ((long long)B * H * ((W + ROI_XW - 1) / ROI_XW) + 3) / 4;       // 4 owner waves per block
-    return cova_internal_persistent_grid2(ntask > (1 << 30) ? (1 << 30) : (int)ntask, 4);
+    return cova_internal_persistent_grid(ntask > (1 << 30) ? (1 << 30) : (int)ntask, 4);
 }
 
 // gfeat NHWC [B,H,W,C] = sum over (box, bin) of gout routed to the arg-max positions; fully written here
@@ -1180,14 +1179,11 @@ static int roipool_bwd_grid(int B, int H, int W)
 static int roipool_page_ranges(const float *rois, int n_rois, int B, int *range, hipStream_t st)
 {
     if (n_rois <= (1 << 18)) {
-        hipLaunchKernelGGL(roipool_page_range_block_kernel, dim3(1), dim3(1024), 0, st, rois, n_rois, B, range);
-        COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(roipool_page_range_block_kernel, dim3(1), dim3(1024), st, rois, n_rois, B, range);
         return COVA_OK;
     }
-    hipLaunchKernelGGL(roipool_page_range_init_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, B, range);
-    COVA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(roipool_page_range_kernel, dim3(cdiv(n_rois, 256)), dim3(256), 0, st, rois, n_rois, B, range);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(roipool_page_range_init_kernel, dim3(cdiv(B, 256)), dim3(256), st, B, range);
+    COVA_LAUNCH(roipool_page_range_kernel, dim3(cdiv(n_rois, 256)), dim3(256), st, rois, n_rois, B, range);
     return COVA_OK;
 }
 
@@ -1219,29 +1215,27 @@ static int launch_roipool_bwd(const float *gout, int ld_g, const float *pooled, 
         t = *tail;
     }
     if (PH * PW == 9 && t.mode != 0)
-        hipLaunchKernelGGL((roipool_bwd_prep_kernel<true, true, 9>), pgrid, dim3(256), 0, st, gout, ld_g, pooled, ld_p, zmax,
-                           argmax, n_rois, C, 9, mean, invstd, gT, amT, partial, rois, B, page_range, t);
+        COVA_LAUNCH((roipool_bwd_prep_kernel<true, true, 9>), pgrid, dim3(256), st, gout, ld_g, pooled, ld_p, zmax,
+                    argmax, n_rois, C, 9, mean, invstd, gT, amT, partial, rois, B, page_range, t);
     else if (PH * PW == 9 && partial)
-        hipLaunchKernelGGL((roipool_bwd_prep_kernel<true, false, 9>), pgrid, dim3(256), 0, st, gout, ld_g, pooled, ld_p, zmax,
-                           argmax, n_rois, C, 9, mean, invstd, gT, amT, partial, rois, B, page_range, t);
+        COVA_LAUNCH((roipool_bwd_prep_kernel<true, false, 9>), pgrid, dim3(256), st, gout, ld_g, pooled, ld_p, zmax,
+                    argmax, n_rois, C, 9, mean, invstd, gT, amT, partial, rois, B, page_range, t);
     else if (PH * PW == 9)
-        hipLaunchKernelGGL((roipool_bwd_prep_kernel<false, false, 9>), pgrid, dim3(256), 0, st, gout, ld_g, pooled, ld_p, zmax,
-                           argmax, n_rois, C, 9, mean, invstd, gT, amT, partial, rois, B, page_range, t);
+        COVA_LAUNCH((roipool_bwd_prep_kernel<false, false, 9>), pgrid, dim3(256), st, gout, ld_g, pooled, ld_p, zmax,
+                    argmax, n_rois, C, 9, mean, invstd, gT, amT, partial, rois, B, page_range, t);
     else if (t.mode != 0)
-        hipLaunchKernelGGL((roipool_bwd_prep_kernel<true, true>), pgrid, dim3(256), 0, st, gout, ld_g, pooled, ld_p, zmax,
-                           argmax, n_rois, C, PH * PW, mean, invstd, gT, amT, partial, rois, B, page_range, t);
+        COVA_LAUNCH((roipool_bwd_prep_kernel<true, true>), pgrid, dim3(256), st, gout, ld_g, pooled, ld_p, zmax,
+                    argmax, n_rois, C, PH * PW, mean, invstd, gT, amT, partial, rois, B, page_range, t);
     else if (partial)
-        hipLaunchKernelGGL((roipool_bwd_prep_kernel<true, false>), pgrid, dim3(256), 0, st, gout, ld_g, pooled, ld_p, zmax,
-                           argmax, n_rois, C, PH * PW, mean, invstd, gT, amT, partial, rois, B, page_range, t);
+        COVA_LAUNCH((roipool_bwd_prep_kernel<true, false>), pgrid, dim3(256), st, gout, ld_g, pooled, ld_p, zmax,
+                    argmax, n_rois, C, PH * PW, mean, invstd, gT, amT, partial, rois, B, page_range, t);
     else
-        hipLaunchKernelGGL((roipool_bwd_prep_kernel<false, false>), pgrid, dim3(256), 0, st, gout, ld_g, pooled, ld_p, zmax,
-                           argmax, n_rois, C, PH * PW, mean, invstd, gT, amT, partial, rois, B, page_range, t);
-    COVA_LAUNCH_CHECK();
-    hipLaunchKernelGGL((PH == 3 && PW == 3 ? roipool_bwd_rows_kernel<true, 2>
-                                           : roipool_bwd_rows_kernel<false>),
-                       dim3(roipool_bwd_grid(B, H, W), C / 64), dim3(256), 0, st, gT, amT, rois, page_range, n_rois,
-                       B, C, H, W, PH, PW, spatial_scale, gfeat);
-    COVA_LAUNCH_CHECK();
+        COVA_LAUNCH((roipool_bwd_prep_kernel<false, false>), pgrid, dim3(256), st, gout, ld_g, pooled, ld_p, zmax,
+                    argmax, n_rois, C, PH * PW, mean, invstd, gT, amT, partial, rois, B, page_range, t);
+    COVA_LAUNCH((PH == 3 && PW == 3 ? roipool_bwd_rows_kernel<true, 2>
+                                    : roipool_bwd_rows_kernel<false>),
+                dim3(roipool_bwd_grid(B, H, W), C / 64), dim3(256), st, gT, amT, rois, page_range, n_rois,
+                B, C, H, W, PH, PW, spatial_scale, gfeat);
     return COVA_OK;
 }
 
@@ -1291,9 +1285,8 @@ COVA_API int cova_roialign_fwd(const float *feat, const float *rois, int n_rois,
 {
     COVA_REQUIRE(feat && rois && out && n_rois >= 0 && B > 0 && C > 0 && PH > 0 && PW > 0);
     if (n_rois == 0) return COVA_OK;
-    hipLaunchKernelGGL(roialign_fwd_kernel, dim3(cdiv(n_rois * PH * PW, 4)), dim3(256), 0, (hipStream_t)stream,
-                       feat, rois, n_rois, B, C, H, W, PH, PW, spatial_scale, sampling_ratio, aligned, out, ld_out);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(roialign_fwd_kernel, dim3(cdiv(n_rois * PH * PW, 4)), dim3(256), (hipStream_t)stream,
+                feat, rois, n_rois, B, C, H, W, PH, PW, spatial_scale, sampling_ratio, aligned, out, ld_out);
     return COVA_OK;
 }
 
@@ -1307,10 +1300,9 @@ COVA_API int cova_roialign_bwd(const float *gout, int ld_g, const float *rois, i
     int *page_range = (int *)ws;
     const int rc = roipool_page_ranges(rois, n_rois, B, page_range, st);
     if (rc != COVA_OK) return rc;
-    hipLaunchKernelGGL(roialign_bwd_rows_kernel, dim3(roipool_bwd_grid(B, H, W), C / 64), dim3(256), 0, st, gout,
-                       ld_g, rois, page_range, n_rois, B, C, H, W, PH, PW, spatial_scale, sampling_ratio, aligned,
-                       gfeat);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(roialign_bwd_rows_kernel, dim3(roipool_bwd_grid(B, H, W), C / 64), dim3(256), st, gout,
+                ld_g, rois, page_range, n_rois, B, C, H, W, PH, PW, spatial_scale, sampling_ratio, aligned,
+                gfeat);
     return COVA_OK;
 }
 
@@ -1319,9 +1311,8 @@ COVA_API int cova_bbox_linear_fwd(const float *bboxes, const float *W, const flo
 {
     COVA_REQUIRE(bboxes && W && bias && raw && z && N >= 0 && Hd > 0);
     if (N == 0) return COVA_OK;
-    hipLaunchKernelGGL(bbox_linear_fwd_kernel, dim3(cdiv(N * Hd, 256)), dim3(256), 0,
-                       (hipStream_t)stream, bboxes, W, bias, raw, z, N, Hd);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(bbox_linear_fwd_kernel, dim3(cdiv(N * Hd, 256)), dim3(256),
+                (hipStream_t)stream, bboxes, W, bias, raw, z, N, Hd);
     return COVA_OK;
 }
 
@@ -1329,9 +1320,8 @@ COVA_API int cova_bbox_linear_bwd(const float *dz, const float *raw, float *dW, 
                                   int Hd, void *stream)
 {
     COVA_REQUIRE(dz && raw && dW && db && Hd > 0);
-    hipLaunchKernelGGL(bbox_linear_bwd_kernel, dim3(Hd), dim3(256), 0, (hipStream_t)stream, dz, raw,
-                       dW, db, N, Hd);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(bbox_linear_bwd_kernel, dim3(Hd), dim3(256), (hipStream_t)stream, dz, raw,
+                dW, db, N, Hd);
     return COVA_OK;
 }
 
@@ -1349,15 +1339,12 @@ int gat_fwd_launch(const float *Wh, int ldw, const float *att_w, const float *at
     if (N == 0) return COVA_OK;
     const dim3 grid(cdiv(N, 4)), blk(256);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(gat_scores_kernel, grid, blk, 0, st, Wh, ldw, att_w, att_b, s, t, N, D);
-    COVA_LAUNCH_CHECK();
-    const int rc = gat_dispatch(gat_form(K, D), [&](auto kp, auto nd) {
-        hipLaunchKernelGGL((gat_fwd_kernel<decltype(kp)::value, decltype(nd)::value, EDGE, DROP>), grid, blk, 0, st, Wh,
-                           ldw, s, t, ctx, N, K, D, slope, attn, hprime, ldh, phi, edge_w, dr);
+    COVA_LAUNCH(gat_scores_kernel, grid, blk, st, Wh, ldw, att_w, att_b, s, t, N, D);
+    return gat_dispatch(gat_form(K, D), [&](auto kp, auto nd) -> int {
+        COVA_LAUNCH((gat_fwd_kernel<decltype(kp)::value, decltype(nd)::value, EDGE, DROP>), grid, blk, st, Wh,
+                    ldw, s, t, ctx, N, K, D, slope, attn, hprime, ldh, phi, edge_w, dr);
+        return COVA_OK;
     });
-    if (rc != COVA_OK) return rc;
-    COVA_LAUNCH_CHECK();
-    return COVA_OK;
 }
 }  // namespace
 
@@ -1391,14 +1378,10 @@ COVA_API int cova_gat_transpose(const int64_t *ctx, int N, int K, int *csr, void
     int *row_ptr = csr, *edges = csr + N + 1, *tmp = edges + E, *deg = tmp + E, *cursor = deg + N;
     hipError_t e = hipMemsetAsync(deg, 0, sizeof(int) * 2 * (size_t)N, st);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(csr_count_kernel, dim3(cdiv(E, 256)), dim3(256), 0, st, ctx, E, N, deg);
-    COVA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(csr_scan_kernel, dim3(1), dim3(1024), 0, st, deg, N, row_ptr);
-    COVA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(csr_fill_kernel, dim3(cdiv(E, 256)), dim3(256), 0, st, ctx, E, N, row_ptr, cursor, tmp);
-    COVA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(csr_sort_rows_kernel, dim3(cdiv(N, 4)), dim3(256), 0, st, row_ptr, tmp, N, edges, (int *)nullptr);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(csr_count_kernel, dim3(cdiv(E, 256)), dim3(256), st, ctx, E, N, deg);
+    COVA_LAUNCH(csr_scan_kernel, dim3(1), dim3(1024), st, deg, N, row_ptr);
+    COVA_LAUNCH(csr_fill_kernel, dim3(cdiv(E, 256)), dim3(256), st, ctx, E, N, row_ptr, cursor, tmp);
+    COVA_LAUNCH(csr_sort_rows_kernel, dim3(cdiv(N, 4)), dim3(256), st, row_ptr, tmp, N, edges, (int *)nullptr);
     return COVA_OK;
 }
 
@@ -1411,12 +1394,9 @@ COVA_API int cova_gat_transpose_reuse(const int64_t *ctx, int N, int K, int *csr
     hipStream_t st = (hipStream_t)stream;
     const int E = N * K;
     int *row_ptr = csr, *edges = csr + N + 1, *tmp = edges + E, *deg = tmp + E, *cursor = deg + N, *ticket = cursor + N;
-    hipLaunchKernelGGL(csr_count_scan_kernel, dim3(cdiv(E, 256)), dim3(256), 0, st, ctx, E, N, deg, ticket, row_ptr);
-    COVA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(csr_fill_kernel, dim3(cdiv(E, 256)), dim3(256), 0, st, ctx, E, N, row_ptr, cursor, tmp);
-    COVA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(csr_sort_rows_kernel, dim3(cdiv(N, 4)), dim3(256), 0, st, row_ptr, tmp, N, edges, deg);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(csr_count_scan_kernel, dim3(cdiv(E, 256)), dim3(256), st, ctx, E, N, deg, ticket, row_ptr);
+    COVA_LAUNCH(csr_fill_kernel, dim3(cdiv(E, 256)), dim3(256), st, ctx, E, N, row_ptr, cursor, tmp);
+    COVA_LAUNCH(csr_sort_rows_kernel, dim3(cdiv(N, 4)), dim3(256), st, row_ptr, tmp, N, edges, deg);
     return COVA_OK;
 }
 
@@ -1435,25 +1415,22 @@ int gat_bwd_launch(const float *g, int ldg, const float *Wh, int ldw, const floa
     COVA_REQUIRE(K > 0 && K <= COVA_GAT_MAX_K && D > 0 && N > 0);
     const dim3 grid(cdiv(N, 4)), blk(256);
     hipStream_t st = (hipStream_t)stream;
-    const int rc = gat_dispatch(gat_form(K, D), [&](auto kp, auto nd) {
-        hipLaunchKernelGGL((gat_bwd_src_kernel<decltype(kp)::value, decltype(nd)::value, EDGE, DROP>), grid, blk, 0, st, g,
-                           ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, du, phi, edge_w, dr);
-        hipLaunchKernelGGL((gat_bwd_dst_kernel<decltype(nd)::value, DROP>), grid, blk, 0, st, g, ldg, attn, du, csr,
-                           csr + N + 1, att_w, N, K, D, dWh, lddw, dt, dr);
+    const int rc = gat_dispatch(gat_form(K, D), [&](auto kp, auto nd) -> int {
+        COVA_LAUNCH((gat_bwd_src_kernel<decltype(kp)::value, decltype(nd)::value, EDGE, DROP>), grid, blk, st, g,
+                    ldg, Wh, ldw, s, t, attn, ctx, att_w, N, K, D, slope, dWh, lddw, ds, du, phi, edge_w, dr);
+        COVA_LAUNCH((gat_bwd_dst_kernel<decltype(nd)::value, DROP>), grid, blk, st, g, ldg, attn, du, csr,
+                    csr + N + 1, att_w, N, K, D, dWh, lddw, dt, dr);
+        return COVA_OK;
     });
     if (rc != COVA_OK) return rc;
-    COVA_LAUNCH_CHECK();
     const bool v4 = (D % 4 == 0) && (ldw % 4 == 0) && (((uintptr_t)Wh & 15) == 0);
-    hipLaunchKernelGGL((v4 ? gat_bwd_att_kernel<4> : gat_bwd_att_kernel<1>), dim3(cdiv(2 * D + 1, 64)), dim3(1024), 0,
-                       st, Wh, ldw, ds, dt, d_att_w, d_att_b, N, D);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH((v4 ? gat_bwd_att_kernel<4> : gat_bwd_att_kernel<1>), dim3(cdiv(2 * D + 1, 64)), dim3(1024),
+                st, Wh, ldw, ds, dt, d_att_w, d_att_b, N, D);
     if (EDGE) {                 // the edge weight's gradient from the du the source-side kernel wrote: two launches
         const long long E = (long long)N * K;
         const int nparts = (int)cdivll(E, EDGE_CHUNK);
-        hipLaunchKernelGGL(gat_edge_wgrad_partial_kernel, dim3(nparts), dim3(256), 0, st, du, phi, E, edge_ws);
-        COVA_LAUNCH_CHECK();
-        hipLaunchKernelGGL(gat_edge_wgrad_final_kernel, dim3(1), dim3(256), 0, st, edge_ws, nparts, d_edge_w);
-        COVA_LAUNCH_CHECK();
+        COVA_LAUNCH(gat_edge_wgrad_partial_kernel, dim3(nparts), dim3(256), st, du, phi, E, edge_ws);
+        COVA_LAUNCH(gat_edge_wgrad_final_kernel, dim3(1), dim3(256), st, edge_ws, nparts, d_edge_w);
     }
     return COVA_OK;
 }

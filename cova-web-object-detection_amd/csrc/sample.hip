@@ -159,12 +159,10 @@ COVA_API int cova_sample_boxes(const float *rows, const int *page_offsets, const
     COVA_REQUIRE(N == 0 || (rows && sel));
     hipStream_t st = (hipStream_t)stream;
     int *local_sel = workspace, *counts = workspace + N;
-    hipLaunchKernelGGL(sample_mark_kernel, dim3(B), dim3(SAMPLE_THREADS), 0, st, rows, page_offsets, row_starts, page_ids,
-                       keep_counts, N, keys, stream_seed, local_sel, counts);
-    COVA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sample_compact_kernel, dim3(B), dim3(SAMPLE_THREADS), 0, st, page_offsets, local_sel, counts, B, N,
-                       sel, out_offsets);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(sample_mark_kernel, dim3(B), dim3(SAMPLE_THREADS), st, rows, page_offsets, row_starts, page_ids,
+                keep_counts, N, keys, stream_seed, local_sel, counts);
+    COVA_LAUNCH(sample_compact_kernel, dim3(B), dim3(SAMPLE_THREADS), st, page_offsets, local_sel, counts, B, N,
+                sel, out_offsets);
     return COVA_OK;
 }
 
@@ -177,9 +175,8 @@ COVA_API int cova_collate_selected(const float *rows, const int *sel, const int 
     COVA_REQUIRE(rows && sel && bboxes && labels);
     COVA_REQUIRE(context_size == 0 || ctx);
     COVA_REQUIRE(A == 0 || (addl_in && addl_out));
-    hipLaunchKernelGGL(collate_selected_kernel, dim3(grid_for((long long)N_out * (2 * context_size + 1))), dim3(256), 0,
-                       (hipStream_t)stream, rows, sel, out_offsets, B, context_size, bboxes, labels, ctx, addl_in, A,
-                       addl_out, N_out);
-    COVA_LAUNCH_CHECK();
+    COVA_LAUNCH(collate_selected_kernel, dim3(grid_for((long long)N_out * (2 * context_size + 1))), dim3(256),
+                (hipStream_t)stream, rows, sel, out_offsets, B, context_size, bboxes, labels, ctx, addl_in, A,
+                addl_out, N_out);
     return COVA_OK;
 }

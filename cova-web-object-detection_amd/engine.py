@@ -14,7 +14,9 @@ import torch
 from . import _lib
 from .weights import BACKBONE_CHANNELS as C64, CONTEXT_LAYERS, head_layout
 
-GAT_MAX_K = 1024       # COVA_GAT_MAX_K of csrc/common.h: neighbour slots per node (up to sixteen 64-lane passes of a wavefront)
+# COVA_GAT_MAX_K of include/cova_hip.h (tests/test_host_cpu.py holds the two equal): neighbour slots per node, up to sixteen
+# 64-lane passes of a wavefront
+GAT_MAX_K = 1024
 
 call, query = _lib.call, _lib.query
 BN_MOMENTUM, BN_EPS, LEAKY_SLOPE = 0.1, 1e-5, 0.2   # nn.BatchNorm defaults; models.py:156
@@ -363,13 +365,8 @@ def bn_backward(dout, ldd, act, lda, z, ldz, st, R, dz, lddz, dres=None, lddres=
 # the two convs of a block and the BatchNorm-backward "apply" passes are evaluated on load inside the consuming
 # convolutions: a1 and dz are never written to HBM.
 class _BnTailStruct(ctypes.Structure):
-    """cova_bn_tail of include/cova_hip.h (a HOST struct of device pointers, read by the launch call)"""
-    _fields_ = [("mode", ctypes.c_int), ("counter", ctypes.c_void_p), ("count", ctypes.c_double),
-                ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p), ("running_mean", ctypes.c_void_p),
-                ("running_var", ctypes.c_void_p), ("num_batches_tracked", ctypes.c_void_p),
-                ("momentum", ctypes.c_float), ("eps", ctypes.c_float), ("scale", ctypes.c_void_p),
-                ("shift", ctypes.c_void_p), ("mean", ctypes.c_void_p), ("invstd", ctypes.c_void_p),
-                ("dgamma", ctypes.c_void_p), ("dbeta", ctypes.c_void_p), ("abc", ctypes.c_void_p)]
+    """cova_bn_tail as include/cova_hip.h defines it (a HOST struct of device pointers, read by the launch call)"""
+    _fields_ = _lib.parse_struct("cova_bn_tail")
 
 
 class BnTail:

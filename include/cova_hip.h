@@ -33,6 +33,11 @@ extern "C" {
 
 #define COVA_ERR_BAD_ARG 10001
 
+/* largest K (neighbour slots per node) the cova_gat_* entry points take: sixteen 64-lane passes of the wave-per-node kernels
+ * (-cs <= 512: far beyond the boxes of a page -- slots past a page's size are pads; models.py:171-177 itself takes any
+ * n_context) */
+#define COVA_GAT_MAX_K 1024
+
 /* BatchNorm finalize as the TAIL of the launch that produced the statistics partials (cova_conv1_fwd_tail,
  * cova_conv3x3_wino4_full_tail): the last block to finish folds the partial rows and writes what
  * cova_bn_finalize_fwd (mode 1) or cova_bn_finalize_bwd_abc (mode 2) would write in a launch of its own -- same

@@ -197,24 +197,35 @@ def test_flat_bucket_layout_of_the_extension_model():
     assert pkeys[len(conv)].startswith("bbox_feat_encoder.") and "gat.layers.1.heads.1.W_j.weight" in tr.params
 
 
-def test_launch_device_resolution_rejects_cpu_and_mixed_arguments():
+def test_launch_device_resolution_rejects_cpu_and_mixed_arguments(monkeypatch):
     """_lib.call launches on the device its tensor arguments live on (the reference picks cuda:<-d> without
     set_device, main.py:17); CPU tensors and mixed devices are refused before anything is launched."""
+    launched = []
+    monkeypatch.setattr(_lib, "_launch", lambda L, name, args, cargs, stream: launched.append((name, cargs)))
     with pytest.raises(_lib.CovaHipError, match="no CPU fallback"):
-        _lib._device_of("cova_x", (torch.zeros(2), 3, None))
-    assert _lib._device_of("cova_x", (3, None, 1.5)) is None
+        _lib.call("cova_x", torch.zeros(2), 3, None)
+    assert launched == []
+    _lib.call("cova_x", 3, None, 1.5)             # no tensor argument: nothing to resolve, the current device
+    assert launched == [("cova_x", [3, None, 1.5])]
 
     class Fake:                                   # two "cuda" tensors on different devices, without a GPU
+        is_cuda = True
+
         def __init__(self, idx):
-            self.is_cuda, self.device = True, torch.device("cuda", idx)
-    orig = torch.Tensor
-    try:
-        _lib.torch.Tensor = Fake                  # isinstance check inside _device_of
-        with pytest.raises(_lib.CovaHipError, match="different devices"):
-            _lib._device_of("cova_x", (Fake(0), Fake(1)))
-        assert _lib._device_of("cova_x", (Fake(1), Fake(1))) == torch.device("cuda", 1)
-    finally:
-        _lib.torch.Tensor = orig
+            self.idx, self.device = idx, torch.device("cuda", idx)
+
+        def get_device(self):
+            return self.idx
+
+        def data_ptr(self):
+            return 4096 + self.idx
+    monkeypatch.setattr(_lib, "_Tensor", Fake)    # the isinstance check inside call
+    monkeypatch.setattr(torch.cuda, "current_device", lambda: 1)
+    with pytest.raises(_lib.CovaHipError, match="different devices"):
+        _lib.call("cova_x", Fake(0), Fake(1))
+    assert len(launched) == 1
+    _lib.call("cova_x", Fake(1), 7, Fake(1))      # one device, the current one: launched with the pointers
+    assert launched[1] == ("cova_x", [4097, 7, 4097])
 
 
 def test_check_batch_host_contract():
@@ -297,3 +308,89 @@ def test_no_test_module_imports_a_test_module():
              for path in sorted(glob.glob(os.path.join(here, "*.py")))
              for n, line in enumerate(open(path), 1) if re.match(r"\s*(from|import)\s+test_", line)]
     assert not found, "\n".join(found)
+
+
+# ---- the C ABI is checked by the compiler: csrc/common.h includes include/cova_hip.h in front of every definition and
+# _build.flags() carries -Werror=missing-prototypes
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
+CSRC = os.path.join(_lib.PKG_DIR, "csrc")
+
+
+def _compile_probe(tmp_path, definition):
+    """host-side syntax check of a file that includes csrc/common.h and defines one COVA_API function, under the build's flags"""
+    import subprocess
+    from cova_web_object_detection_amd import _build
+    src = tmp_path / "probe.hip"
+    src.write_text('#include "%s"\n%s\n' % (os.path.join(CSRC, "common.h"), definition))
+    return subprocess.run([HIPCC] + _build.flags(str(src)) + ["--cuda-host-only", "-fsyntax-only", str(src)],
+                          capture_output=True, text=True, timeout=300)
+
+
+@needs_hipcc
+def test_definition_that_matches_its_prototype_compiles(tmp_path):
+    r = _compile_probe(tmp_path, "COVA_API int cova_conv_out_size(int in_size, int kernel, int stride, int pad) "
+                                 "{ return (in_size + 2 * pad - kernel) / stride + 1; }")
+    assert r.returncode == 0, r.stderr[-2000:]
+
+
+@needs_hipcc
+def test_definition_that_disagrees_with_its_prototype_does_not_compile(tmp_path):
+    r = _compile_probe(tmp_path, "COVA_API int cova_conv_out_size(int in_size, long long kernel, int stride, int pad) "
+                                 "{ return (int)((in_size + 2 * pad - kernel) / stride + 1); }")
+    assert r.returncode != 0
+    assert "conflicting types for 'cova_conv_out_size'" in r.stderr, r.stderr[-2000:]
+
+
+@needs_hipcc
+def test_exported_function_outside_the_header_does_not_compile(tmp_path):
+    r = _compile_probe(tmp_path, "COVA_API int cova_not_in_the_header(int x) { return x; }")
+    assert r.returncode != 0
+    assert "no previous prototype for function 'cova_not_in_the_header'" in r.stderr, r.stderr[-2000:]
+
+
+BN_TAIL_FIELDS = ["mode", "counter", "count", "gamma", "beta", "running_mean", "running_var", "num_batches_tracked", "momentum",
+                  "eps", "scale", "shift", "mean", "invstd", "dgamma", "dbeta", "abc"]
+
+
+def test_bn_tail_struct_layout_is_the_compilers(tmp_path):
+    """engine._BnTailStruct is generated from the header's cova_bn_tail: same field names in the same order as the structure
+    written by hand before, and the size and every offset a C compiler gives the header's struct."""
+    import shutil
+    import subprocess
+    from cova_web_object_detection_amd import engine
+    fields = _lib.parse_struct("cova_bn_tail")
+    assert [f for f, _ in fields] == BN_TAIL_FIELDS
+    assert [f for f, _ in engine._BnTailStruct._fields_] == BN_TAIL_FIELDS
+    cc = os.environ.get("CC") or "/opt/rocm/llvm/bin/clang"
+    if shutil.which(cc) is None:
+        pytest.skip("no C compiler (%s)" % cc)
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "%s"\nint main(void)\n{\n'
+                   '    printf("%%zu\\n", sizeof(cova_bn_tail));\n%s    return 0;\n}\n'
+                   % (os.path.abspath(_lib.HEADER),
+                      "".join('    printf("%%zu\\n", offsetof(cova_bn_tail, %s));\n' % f for f in BN_TAIL_FIELDS)))
+    subprocess.run([cc, str(src), "-o", str(exe)], check=True, capture_output=True, timeout=120)
+    got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True, timeout=60).stdout.split()]
+    assert got[0] == ctypes.sizeof(engine._BnTailStruct)
+    assert got[1:] == [getattr(engine._BnTailStruct, f).offset for f in BN_TAIL_FIELDS]
+
+
+def test_defined_entry_points_are_the_declared_ones():
+    """Every `COVA_API int cova_...(` defined in csrc/*.hip (outside the tools-only ..._TRACE blocks) is declared in the header,
+    and every declared one is defined."""
+    import glob
+    import re
+    defined = set()
+    for path in glob.glob(os.path.join(CSRC, "*.hip")):
+        src = re.sub(r"#ifdef \w+_TRACE\n.*?#endif", "", open(path).read(), flags=re.S)
+        defined.update(re.findall(r"^COVA_API\s+int\s+(cova_\w+)\s*\(", src, flags=re.M))
+    declared = set(_lib.parse_header())
+    assert defined - declared == set() and declared - defined == set()
+
+
+def test_gat_max_k_is_the_headers():
+    import re
+    from cova_web_object_detection_amd import engine
+    m = re.search(r"^#define\s+COVA_GAT_MAX_K\s+(\d+)\s*$", open(_lib.HEADER).read(), flags=re.M)
+    assert m is not None and engine.GAT_MAX_K == int(m.group(1))

@@ -1,8 +1,9 @@
 // Direct-form (implicit GEMM) 3x3 / 64->64 convolution kernels: forward / data gradient with the fused
 // statistics and BatchNorm-backward epilogues, and the weight gradient.  They were the product path of round 1
-// before the Winograd kernels (cova-web-object-detection_amd/csrc/conv_wino.hip, conv_wino4.hip) replaced them; they
+// before the Winograd kernels (tools/csrc/conv_wino_f2x2.hip, then cova-web-object-detection_amd/csrc/conv_wino4.hip) replaced them; they
 // live here, in the TOOLS library (tools/lib/libcova_direct.so, tools/direct_lib.py), as the measured reference
 // point of DESIGN.md section 4.1 (133 TFLOP/s = 0.85 of the f32-MFMA peak) and for tools/conv_bench.py.
+#include "../include/cova_direct.h"      // this library's own C ABI, in front of its definitions
 #include "../../cova-web-object-detection_amd/csrc/common.h"
 
 // Ablation switches (key 5) exist only in builds made with COVA_ABLATE=1 in the environment (-DCOVA_ABLATE); otherwise the mask

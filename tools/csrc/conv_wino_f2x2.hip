@@ -20,6 +20,7 @@
 //     a double-buffered 2 x 20 KB LDS ring, one 4-channel chunk per barrier; a lane's 16 positions
 //     are contiguous (4 ds_read_b128 per channel block), rows padded to 20 floats (conflict free).
 // Per tile: 16 chunks x (16 A reads + 32 adds + 32 B reads + 32 MFMAs) per wave.
+#include "../include/cova_wino_f2x2.h"      // this library's own C ABI, in front of its definitions
 #include "../../cova-web-object-detection_amd/csrc/common.h"
 
 // Ablation switches (key 5) exist only in builds made with COVA_ABLATE=1 in the environment (-DCOVA_ABLATE); otherwise the mask

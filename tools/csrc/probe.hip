@@ -1,5 +1,6 @@
 // Diagnostic probes (not on the product path): sustained f32-MFMA rate of this GPU under load,
 // the practical ceiling the conv kernels are compared with besides the 157.3 TFLOP/s spec peak.
+#include "../include/cova_probe.h"      // this library's own C ABI, in front of its definitions
 #include "../../cova-web-object-detection_amd/csrc/common.h"
 
 namespace {
@@ -233,8 +234,8 @@ COVA_API int cova_probe_mfma_f32(float *scratch, int blocks, int iters, void *st
 // lane>>4 = 16-byte slice),  mode 1: fully contiguous (16 lanes = one pixel),  mode 2: 4 consecutive
 // lanes = one 64-byte segment.  8 float4 loads in flight per lane, then 8 stores.  lds_bytes of dynamic
 // LDS limit the blocks per CU (the conv kernels run 2 waves per SIMD).
-__global__ __launch_bounds__(512) void lane_pattern_probe_kernel(const float *__restrict__ in, float *__restrict__ out,
-                                                                 long long nruns, int mode, int loads_only)
+static __global__ __launch_bounds__(512) void lane_pattern_probe_kernel(const float *__restrict__ in, float *__restrict__ out,
+                                                                        long long nruns, int mode, int loads_only)
 {
     extern __shared__ float dyn_lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -328,7 +329,7 @@ COVA_API int cova_probe_lane_pattern(const float *in, float *out, long long npix
 // ---- LDS poison: every CU's 160 KB of LDS filled with a bit pattern (a quiet NaN as float, a huge value as int) in front of a
 // product launch -- a kernel that reads LDS it did not write then produces NaN instead of silently inheriting its predecessor's
 // data (tools/poison_check.py with POISON_LDS=1)
-__global__ __launch_bounds__(1024) void lds_fill_kernel(unsigned pattern, unsigned *sink)
+static __global__ __launch_bounds__(1024) void lds_fill_kernel(unsigned pattern, unsigned *sink)
 {
     extern __shared__ unsigned s_all[];
     for (int i = threadIdx.x; i < 160 * 1024 / 4; i += 1024) s_all[i] = pattern;

@@ -17,7 +17,7 @@ def build(force=False):
         return LIB
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
     cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
-           "-fvisibility=hidden", "-fno-slp-vectorize", "-shared", SRC, "-o", LIB]
+           "-fvisibility=hidden", "-Werror=missing-prototypes", "-fno-slp-vectorize", "-shared", SRC, "-o", LIB]
     if os.environ.get("COVA_ABLATE"):
         cmd.insert(1, "-DCOVA_ABLATE=1")
     subprocess.check_call(cmd)

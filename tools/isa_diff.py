@@ -42,8 +42,7 @@ def assembly(src):
     """the device assembly of one file, or None when the file does not exist on that side"""
     if not os.path.exists(src):
         return None
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-w"]
-    cmd += B.FILE_FLAGS.get(os.path.basename(src), []) + ["--cuda-device-only", "-S", src, "-o", "-"]
+    cmd = [HIPCC] + B.flags(src) + ["-w", "--cuda-device-only", "-S", src, "-o", "-"]
     return subprocess.run(cmd, check=True, stdout=subprocess.PIPE, text=True).stdout
 
 

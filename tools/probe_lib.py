@@ -16,7 +16,7 @@ def build():
         return LIB
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
     subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O3", "-std=c++17",
-                           "-fPIC", "-fvisibility=hidden", "-shared", SRC, "-o", LIB])
+                           "-fPIC", "-fvisibility=hidden", "-Werror=missing-prototypes", "-shared", SRC, "-o", LIB])
     return LIB
 
 
